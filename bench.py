@@ -13,7 +13,12 @@ gather buffer (two slots).  With N > 1 the gather of step i is launched non-bloc
 behind its back-trace.  The region ends with a device synchronisation and the completion of every gather: all K
 steps are complete inside it.  `--serial` runs forward, back-trace and gather of a step back to back on one stream.
 
-Rank 0 prints ONE JSON line (always the last line of stdout).  At N = 1 it also carries, measured in the same process:
+Rank 0 prints ONE JSON line (always the last line of stdout): the headline, with the kernel times and roofline fractions of the
+timed steps themselves.  `--dump-outputs DIR` writes what the last timed step computed (decoded paths and log-likelihoods, see
+dump_outputs()) before that line is printed.  With `--full` at N = 1 the line also carries, measured in the same process after
+the timed steps:
+  "pmc"      HBM traffic of the headline's kernels from two rocprofv3 --pmc passes of their own (--no-traffic skips them),
+  "serial_schedule" the headline's steps on one stream,
   "sweep"    B = 256 / 512 / 1024 / 2048 at S=361 fp32 (the saturation regime; songs repeat with period 32): serial and
              overlapped schedules, the wave form with its half and its full delta history, dense emissions, a ragged batch,
              and the back-trace's data-dependent event counts per 1000 frames,
@@ -22,6 +27,7 @@ Rank 0 prints ONE JSON line (always the last line of stdout).  At N = 1 it also 
              songs -- which doubles as a parity check of the GPU result -- and the C restatement on all cores.
 
     python bench.py --gpus 1 --steps 10 --warmup 2
+    python bench.py --gpus 1 --steps 10 --warmup 2 --full      (everything listed above; a few minutes)
     python bench.py --gpus N --steps K --warmup W          (N > 1 without torchrun's environment: launches its own N workers,
                                                             launch_workers() below, and relays rank 0's JSON line)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -101,13 +107,40 @@ def parse():
     ap.add_argument("--transition", default="tonet", choices=["tonet", "dense", "durrieu"])
     ap.add_argument("--f16", action="store_true", help="store emissions as float16")
     ap.add_argument("--dmax", type=int, default=14, help="band half-width of the tonet-recipe transition (tonet 14, jdc 40, imm 56)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the sweep / configs4 blocks")
-    ap.add_argument("--no-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes (roofline.traffic from profiles/traffic.json)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also the PMC traffic passes, the one-stream schedule, the CPU "
+                                                         "baseline and the sweep / configs4 / pipeline blocks (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the sweep / configs4 blocks")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: do not run the two rocprofv3 --pmc passes (roofline.traffic from profiles/traffic.json)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--serial", action="store_true", help="one stream: no overlap between consecutive steps")
     ap.add_argument("--option", action="append", default=[], help="vit_plan_set_option key=value (kernel-selection override)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's paths and log-likelihoods to DIR/*.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(path, states, loglik):
+    """What a caller of the timed path receives from its last step, as float32 .npy files (the states are bin indices < 2^24: exact):
+    loglik.npy [B] and states.npy [B, T].  Where the paths exceed the 64 MB budget, states.npy holds a fixed sample of whole songs
+    (seeded, sorted) and song_index.npy says which rows of the batch they are."""
+    os.makedirs(path, exist_ok=True)
+    B, T = states.shape
+    ll = loglik.float().cpu().numpy()
+    np.save(os.path.join(path, "loglik.npy"), ll)
+    n = min(B, (DUMP_BYTES - ll.nbytes - 4096) // (4 * T + 8))
+    if n < 1:
+        raise SystemExit(f"--dump-outputs: one path of {T} frames does not fit {DUMP_BYTES} bytes")
+    if n < B:
+        idx = np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+        np.save(os.path.join(path, "song_index.npy"), idx.astype(np.float64))
+        states = states[torch.from_numpy(idx).to(states.device)]
+    np.save(os.path.join(path, "states.npy"), states.cpu().numpy().astype(np.float32))
 
 
 def make_params(transition, S, dmax):
@@ -844,6 +877,12 @@ def main():
     drain()
     elapsed, events = timed(args.steps, True)
     states, loglik = states_k[(args.steps - 1) % NSLOT], loglik_k[(args.steps - 1) % NSLOT]
+    if args.dump_outputs and rank == 0:
+        if pipe is not None:           # rank 0's caller receives every rank's songs
+            g_states, g_loglik = pipe.result((args.steps - 1) % NSLOT)
+            dump_outputs(args.dump_outputs, g_states.reshape(n_total, T), g_loglik.reshape(n_total))
+        else:
+            dump_outputs(args.dump_outputs, states, loglik)
     fwd_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in events]))
     bt_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in events]))
 
@@ -901,7 +940,7 @@ def main():
             "whole_path_bytes_per_frame": bpf + 6,
             "whole_path_hbm_frac": value * 1e6 * (bpf + 6) / 1e9 / (HBM_PEAK_GBS * world),
         }
-        if world == 1 and not use_dist:
+        if args.full and world == 1 and not use_dist:
             torch.cuda.synchronize()
             if not args.no_traffic and (S, args.transition, args.dmax, args.f16, args.emissions) == (361, "tonet", 14, False, "peaks"):
                 pm = measure_traffic(B, T, algo, args.option)

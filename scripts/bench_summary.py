@@ -1,4 +1,5 @@
-"""Print the interesting numbers of a bench.py JSON line (test infrastructure).  usage: bench_summary.py file"""
+"""Print the interesting numbers of a bench.py JSON line (test infrastructure; the blocks after the headline come from
+`bench.py --full`).  usage: bench_summary.py file"""
 import json
 import sys
 

@@ -29,7 +29,9 @@ pi = synth.dense_random_log_transition(S, seed=6)[0].copy()
 pipe = sharded.GatherPipeline(b, T, torch.device("cpu"), n_slots=2)
 st_k = [torch.empty((b, T), dtype=torch.int32) for _ in range(2)]
 ll_k = [torch.empty((b,), dtype=torch.float32) for _ in range(2)]
-print(f"rank {rank} of {world} up", flush=True)
+# whole lines in one write each: under PYTHONUNBUFFERED print() writes text and newline separately, and the ranks share one pipe
+sys.stdout.write(f"rank {rank} of {world} up\n")
+sys.stdout.flush()
 if rank == args.fail_rank:
     os._exit(3)          # a crashed worker (sys.exit would wait in the process group destructor for its peers)
 for i in range(args.steps):
@@ -45,6 +47,7 @@ if rank == 0:
     E = synth.emissions_dense(world * b, T, S, seed=20 + args.steps - 1).numpy()
     ref, rl = vo.decode_c(A, pi, E)
     ok = bool(np.array_equal(o[0].numpy().reshape(world * b, T), ref) and np.array_equal(o[1].numpy().reshape(-1), rl))
-    print(json.dumps({"world_size": dist.get_world_size(), "steps": args.steps, "gathers": pipe.launched, "last_step_equals_oracle": ok}), flush=True)
+    sys.stdout.write(json.dumps({"world_size": dist.get_world_size(), "steps": args.steps, "gathers": pipe.launched, "last_step_equals_oracle": ok}) + "\n")
+    sys.stdout.flush()
 dist.barrier()
 dist.destroy_process_group()
