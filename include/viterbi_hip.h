@@ -108,8 +108,8 @@ int vit_plan_query(const vit_plan *plan, vit_plan_info *info);
  *                      instead of per wavefront (banded plans, full history; up to 256 chunks per song; VIT_EUNSUPPORTED elsewhere)
  *   "dense_songs"      songs per workgroup of the dense kernel (0 auto); "dense_one_thread" 1 = one thread per target;
  *                      "dense_form" 0 = matrix-resident dense kernel where it applies (64 < S <= 368), 1 = always stream the matrix
- *   "step_form"        step-structured kernel: 0 four targets per lane, bands split over two waves | 1 one target per lane |
- *                      2 off (plain dense kernel) | 3 four targets per lane, one wave per lane group
+ *   "step_form"        step-structured kernel, four targets per lane: 0 bands split over two waves | 3 one wave per lane group
+ *                      (VIT_ALGO_DENSE is the plain dense kernel)
  *   "bt_chunks", "bt_warm"   time-parallel back-trace: chunks per song (0 auto), warm-up frames (-1 default); "bt_fast_rows" 1 = every
  *                      row through the general code of the sparse kernels (0: the unexceptional rows run in a loop of their own)
  *   "bt_block_waves"   half history's back-trace: waves per workgroup, 0 = 16 | 8 | 4.  Eight-wave workgroups (208 registers per SIMD) can start

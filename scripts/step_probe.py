@@ -18,7 +18,7 @@ for B in (64, 128, 256, 512, 1024):
     E = base.repeat(B // 32, 1, 1).contiguous()
     st = torch.empty((B, T), dtype=torch.int32, device=dev)
     ll = torch.empty((B,), dtype=torch.float32, device=dev)
-    for form in (0, 3, 1):
+    for form in (0, 3):
         dec.set_option("step_form", form)
         dec.decode_into(E, st, ll, phase="forward")
         torch.cuda.synchronize()

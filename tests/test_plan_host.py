@@ -171,7 +171,7 @@ def test_step_structure_of_the_durrieu_matrix(golden):
     B[300, 310] = np.nextafter(B[300, 310], np.float32(0))          # one entry one ulp off: not a step matrix any more
     assert not HostPlan(B, pi).step_ok
     assert not HostPlan(p["dense361_logA_T"], p["dense361_log_pi"]).step_ok
-    # host replay of step_forward_kernel's arithmetic
+    # host replay of the step kernels' arithmetic
     S, n, BW, KB = 722, 721, 20, 9
     E = synth.emissions_dense(1, 40, S, seed=12)[0].numpy()
     ref, rl, rdelta = vo.decode_c(A, pi, E, return_delta=True)

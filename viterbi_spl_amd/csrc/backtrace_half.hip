@@ -19,18 +19,11 @@
 // the whole row -- from global memory at an even frame, rebuilt in full (361 x 35 candidates) at an odd one: rare (e.g.
 // a voiced -> unvoiced switch), exact either way.  Chunking, speculative warm-up and the verify-and-repair pass are
 // those of sparse_backtrace_kernel; a chunk's guess row is always an even frame.
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "kernels.hpp"
+#include "device_common.hpp"
 
 namespace vit {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kHbR = 8;             // stored rows per tile
 constexpr int kHbND = 96;           // delta span columns (a 32-wide window of 32-wide windows is 63 columns)
@@ -42,48 +35,12 @@ constexpr int kHbWX1 = kHbW + kMaxExtras + 1;
 constexpr int kHbWXS = (kHbWX1 + 3) / 4 * 4;      // row stride of the candidate table in LDS: 16-byte aligned rows (and halves of a window)
 constexpr int kHbCB = kHbW + kMaxExtras;    // candidate lane of the bound
 
-__device__ __forceinline__ int hb_song_length(const int64_t* lengths, int song, int T) {
-    if (!lengths) return T;
-    long long v = lengths[song];
-    v = v < 1 ? 1 : v;
-    return v > T ? T : (int)v;
-}
-__device__ __forceinline__ int hb_clamp(int x, int hi) {   // min(max(x, 0), hi): one v_med3_i32
-    int r;
-    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(hi));
-    return r;
-}
-__device__ __forceinline__ float hb_wave_max(float x) {   // kernels.hip wave_max_all
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(x));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
 // max(x[l], x[l ^ 32]) in every lane: v_permlane32_swap exchanges the upper 32 lanes of its first operand with the lower 32
 // of its second; fed two copies of x it leaves {x.lo, x.lo} and {x.hi, x.hi}
 __device__ __forceinline__ float hb_other_half(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
-
-template <typename ET>
-__device__ __forceinline__ float hb_ld(const ET* p);
-template <>
-__device__ __forceinline__ float hb_ld<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float hb_ld<__half>(const __half* p) { return __half2float(*p); }
 
 }  // namespace
 
@@ -111,7 +68,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
     const int song = MODE == 0 ? gw / C : gw;
     const int chunk = MODE == 0 ? gw % C : 0;
     if (song >= a.B) return;
-    const int Tb = hb_song_length(a.lengths, song, T);
+    const int Tb = song_length(a.lengths, song, T);
     int32_t* __restrict__ states = a.states + (size_t)song * T;
     const float* __restrict__ hist = a.hist + (size_t)song * a.hist_rows * SD;
     const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
@@ -166,7 +123,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
         for (int r = 0; r < kHbR; ++r) {
             int f = 2 * (r_lo + (r < rows ? r : rows - 1)) + 1;
             f = f > Tb - 1 ? Tb - 1 : f;
-            tr.se[r] = hb_ld<ET>(E + (size_t)f * S + ce0 + lane);
+            tr.se[r] = load_e<ET>(E + (size_t)f * S + ce0 + lane);
         }
     };
     auto tile_store = [&](const TileRegs& tr) {
@@ -231,13 +188,13 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
                     for (;;) {
                         int curv;
                         asm volatile("v_mov_b32 %0, %1" : "=v"(curv) : "s"(cur));
-                        const int lov = hb_clamp(curv - lo_off, lo_max);
+                        const int lov = clamp_med3(curv - lo_off, lo_max);
                         const int rr = (f >> 1) - r_lo;
                         const int rowd = rr * kHbND, rowa = rr * kHbAux;
                         float dv;
                         if (f & 1) {
                             const int iv = lov + il;
-                            const int li = hb_clamp(iv - lo_off, lo_max);
+                            const int li = clamp_med3(iv - lo_off, lo_max);
                             const float* __restrict__ src = td + (rowd - g + 16 * hh) + li;
                             const float* __restrict__ wt = tabX + __umul24(iv, WXS);
                             // every read of the rebuild goes out before the first sum (left alone the compiler reads a pair, waits, adds: eight
@@ -267,7 +224,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
                             dv = (isw ? td + rowd + lov + lane_mg : ta + rowa + aux_even)[0];
                         }
                         const float v = dv + tabX[__umul24(curv, WXS) + tb];
-                        const float m = hb_wave_max(cand ? v : -INFINITY);
+                        const float m = wave_max_all(cand ? v : -INFINITY);
                         const unsigned long long ge = __ballot(v >= m) & cand_or_bound;
                         if ((__ballot((unsigned)(lov - lo_a) > lo_span) | (ge & (1ull << CB))) != 0) break;
                         const unsigned gw = (unsigned)ge;                      // (W = 32: the window candidates are lanes 0 .. 31)
@@ -312,7 +269,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
                 const float av = tabX[curv * WXS + tb];
                 float v = dv + av;
                 const float vc = cand ? v : -INFINITY;
-                const float m = hb_wave_max(vc);
+                const float m = wave_max_all(vc);
                 // one compare: a candidate lane with v >= m attains the maximum; the bound lane with fl(M_f + c_cur) >= m means a
                 // row-constant candidate may tie or win
                 const unsigned long long ge = __ballot(v >= m) & cand_or_bound;
@@ -357,7 +314,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
 #pragma unroll 8
                             for (int w = 0; w < W; ++w) acc = fmaxf(acc, src[w] + wt[w]);
                             for (int k = 0; k < nx; ++k) acc = fmaxf(acc, ar[a.xcol0 + k] + wt[W + k]);
-                            d[e] = inS[e] ? acc + hb_ld<ET>(E + (size_t)f * S + ic) : -INFINITY;
+                            d[e] = inS[e] ? acc + load_e<ET>(E + (size_t)f * S + ic) : -INFINITY;
                         }
                         rebuilt = true;
                         ++n_reb;
@@ -371,7 +328,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
                         vf[e] = excl ? -INFINITY : d[e] + cj;
                         m2 = fmaxf(m2, vf[e]);
                     }
-                    const float mm = fmaxf(m, hb_wave_max(m2));
+                    const float mm = fmaxf(m, wave_max_all(m2));
 #pragma unroll
                     for (int e = 0; e < EPL; ++e) {
                         const unsigned long long mk = __ballot(vf[e] == mm && inS[e]);
@@ -417,7 +374,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
                 d[e] = inS[e] ? g[e * 64 + lane] : -INFINITY;
                 m = fmaxf(m, d[e]);
             }
-            m = hb_wave_max(m);
+            m = wave_max_all(m);
             unsigned idx = 0x7fffffffu;
 #pragma unroll
             for (int e = 0; e < EPL; ++e) {
@@ -481,7 +438,7 @@ bool half_backtrace_applies(const BtArgs& a) {
         const int s_lo = a.col0 + lo_of(lo) - c0, s_hi = a.col0 + lo_of(lo + kHbW - 1) + kHbW - c0;
         if (wlo < 0 || wlo + kHbW > kHbND || s_lo < 0 || s_hi > kHbND || lo < ce0 || lo + kHbW > ce0 + kHbNE) return false;
     }
-    return half_lds_bytes(a, 16) + 1024 <= 160 * 1024;
+    return half_lds_bytes(a, 16) + 1024 <= kLdsBytes;
 }
 
 template <typename ET>

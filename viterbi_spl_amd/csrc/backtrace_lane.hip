@@ -21,47 +21,15 @@
 // above their upper boundary (lane_spec_kernel); lane_verify_kernel compares what every chunk assumed at its upper boundary
 // with what the chunk above it decided there, and lane_repair_kernel (one lane per song) re-chases the chunks whose guess was
 // wrong until the new path meets the stored one.  Exact whatever the guesses were (the scheme of banded_backtrace_kernel).
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "kernels.hpp"
+#include "device_common.hpp"
 
 namespace vit {
 
 namespace {
 
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));
-typedef int i32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-
-constexpr int kLnBig = 0x7fffffff;
 constexpr int kLnThreads = 512;
 
-__device__ __forceinline__ int ln_song_length(const BtArgs& a, int song) {
-    if (!a.lengths) return a.T;
-    long long v = a.lengths[song];
-    v = v < 1 ? 1 : v;
-    return v > a.T ? a.T : (int)v;
-}
-__device__ __forceinline__ float ln_wave_max(float x) {   // kernels.hip wave_max_all
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(x));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
+__device__ __forceinline__ int song_length(const BtArgs& a, int song) { return vit::song_length(a.lengths, song, a.T); }
 __device__ __forceinline__ const float* ln_readlane_ptr(const float* p, int l) {
     const unsigned long long v = reinterpret_cast<unsigned long long>(p);
     const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)v, l), hi = __builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
@@ -119,7 +87,7 @@ struct LaneDecider {
             vf[e] = excl ? -INFINITY : d[e] + cj_l;
             m2 = fmaxf(m2, vf[e]);
         }
-        const float mm = fmaxf(m_l, ln_wave_max(m2));
+        const float mm = fmaxf(m_l, wave_max_all(m2));
         unsigned idx = 0x7fffffffu;
 #pragma unroll
         for (int e = NWT - 1; e >= 0; --e) {
@@ -179,7 +147,7 @@ struct LaneDecider {
             for (int k = 0; k < kMaxExtras; ++k) dx[k] = k < nx ? row[a.xcol0 >= 0 ? a.xcol0 + k : a.col0 + a.extras[k]] : 0.f;
         }
         float m = -INFINITY;
-        int arg = kLnBig;
+        int arg = kBig;
         float cj;
         if (GT) {
             const float* __restrict__ wt = reinterpret_cast<const float*>(a.image + a.off_tabX) + (size_t)cur * WX1;
@@ -199,7 +167,7 @@ struct LaneDecider {
                     m = gt ? v : m;
                     arg = gt ? 4 * q + r : arg;
                 }
-            arg = arg == kLnBig ? kLnBig : arg + lo;
+            arg = arg == kBig ? kBig : arg + lo;
 #pragma unroll
             for (int k = 0; k < kMaxExtras; ++k)
                 if (k < nx) {
@@ -220,7 +188,7 @@ struct LaneDecider {
                     m = gt ? v : m;
                     arg = gt ? 4 * q + r : arg;
                 }
-            arg = arg == kLnBig ? kLnBig : arg + lo;
+            arg = arg == kBig ? kBig : arg + lo;
 #pragma unroll
             for (int k = 0; k < kMaxExtras; ++k)
                 if (k < nx) {
@@ -313,7 +281,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_spec_kernel(BtArgs a) {
         if (a.skip_nonpositive && a.lengths[song] < 1) valid = false;       // segment of a checkpointed decode this song does not reach
     }
     const long long off = packed ? a.offsets[song] : 0;
-    const int Tb = packed ? (int)(a.offsets[song + 1] - off) : ln_song_length(a, song), Lf = Tb - 1;
+    const int Tb = packed ? (int)(a.offsets[song + 1] - off) : song_length(a, song), Lf = Tb - 1;
     int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride);
     const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows) * SD;
     int32_t* __restrict__ entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
@@ -372,7 +340,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_spec_kernel(BtArgs a) {
 // frames past a ragged song's end
 __global__ void lane_pad_kernel(BtArgs a) {      // eight workgroups per song
     const int song = blockIdx.x >> 3;
-    const int Tb = ln_song_length(a, song);
+    const int Tb = song_length(a, song);
     int32_t* __restrict__ states = a.states + (size_t)song * a.states_stride;
     for (int t = Tb + (blockIdx.x & 7) * blockDim.x + threadIdx.x; t < a.T; t += 8 * blockDim.x) states[t] = -1;
 }
@@ -396,7 +364,7 @@ __global__ void lane_verify_kernel(BtArgs a, uint32_t* __restrict__ mask) {
     }
     if (c >= C - 1) return;
     const long long off = packed ? a.offsets[song] : 0;
-    const int Lf = (packed ? (int)(a.offsets[song + 1] - off) : ln_song_length(a, song)) - 1;
+    const int Lf = (packed ? (int)(a.offsets[song + 1] - off) : song_length(a, song)) - 1;
     int lo_c, hi_c;
     ln_chunk_bounds(Lf, c, C, lo_c, hi_c);
     if (hi_c <= lo_c) return;
@@ -428,7 +396,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_repair_kernel(BtArgs a, const
     if (!__syncthreads_or(any_bit)) return;          // nothing to repair in this workgroup (the common case)
     ln_load_tables<WQ, GT>(a, tabL, loL);
     const long long off = packed ? a.offsets[song] : 0;
-    const int Lf = (packed ? (int)(a.offsets[song + 1] - off) : ln_song_length(a, song)) - 1;
+    const int Lf = (packed ? (int)(a.offsets[song + 1] - off) : song_length(a, song)) - 1;
     int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride);
     const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows) * SD;
     const int32_t* entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
@@ -520,7 +488,7 @@ static bool lane_table_fits(const BtArgs& a) { return lane_lds_bytes(a, true) <=
 
 // Banded plans without dense rows whose forward pass left the frame maximum in every history row (full history).
 bool lane_backtrace_applies(const BtArgs& a) {
-    return a.banded && a.have_fmax && a.n_dense == 0 && !a.hist_half && a.W >= 4 && a.W % 4 == 0 && a.W <= 128 && a.W <= a.S &&
+    return a.banded && a.have_fmax && a.n_dense == 0 && !a.hist_half && banded_width_instantiated(a.W) && a.W <= a.S &&
            a.col0 + a.S <= a.SD && a.mask != nullptr;
 }
 
@@ -560,6 +528,7 @@ static hipError_t launch_lane_s(const BtArgs& a, hipStream_t st, int phases) {
 
 hipError_t launch_backtrace_lane(const BtArgs& a, hipStream_t st, int phases) {
     if (!lane_backtrace_applies(a) || a.chunks < 1 || a.chunks > kLaneMaxChunks) return hipErrorInvalidConfiguration;
+    static_assert(sizeof(kBandedWidths) / sizeof(int) == 6, "one case per instantiated window width");
     switch (a.W) {
         case 16: return launch_lane_s<4>(a, st, phases);
         case 32: return launch_lane_s<8>(a, st, phases);

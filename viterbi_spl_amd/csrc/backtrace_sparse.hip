@@ -1,6 +1,6 @@
 // backtrace_sparse.hip -- exact, time-parallel back-trace that fetches only the part of the delta history it uses.
 //
-// banded_backtrace_kernel (kernels.hip) stages whole history rows through LDS: 1456 B per frame to use ~33 floats, and it
+// banded_backtrace_kernel (backtrace_rows.hip) stages whole history rows through LDS: 1456 B per frame to use ~33 floats, and it
 // is HBM-bound doing so (5.5 TB/s; 21 % of a step at B = 1024).  The path moves slowly -- a band transition moves it by
 // at most the band half-width, and in music it moves by a bin or two per frame -- so this kernel fetches, for a tile of
 // K frames, only
@@ -14,52 +14,17 @@
 // global memory -- exact either way.  When the path leaves the span (a jump through the floor or an extra column, or
 // accumulated drift) the tile is dropped and re-fetched around the new state, starting at the frame that missed.
 // Chunking, speculative warm-up and the verify-and-repair pass are those of banded_backtrace_kernel.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "kernels.hpp"
+#include "device_common.hpp"
 
 namespace vit {
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kSpK = 16;            // rows per tile
 constexpr int kSpAux = 8;           // auxiliary floats per row: [0] frame maximum, [1 + k] extra column k
 // span columns per row (multiple of 4): the window plus at least 16 columns of guard on either side
 constexpr int sp_span(int kc) { return kc == 1 ? 64 : (kc == 2 ? 128 : 160); }
 
-__device__ __forceinline__ int sp_song_length(const int64_t* lengths, int song, int T) {
-    if (!lengths) return T;
-    long long v = lengths[song];
-    v = v < 1 ? 1 : v;
-    return v > T ? T : (int)v;
-}
-__device__ __forceinline__ int sp_clamp(int x, int hi) {   // min(max(x, 0), hi): one v_med3_i32
-    int r;
-    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(hi));
-    return r;
-}
-__device__ __forceinline__ float sp_wave_max(float x) {   // kernels.hip wave_max_all
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(x));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
 
 }  // namespace
 
@@ -101,7 +66,7 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
     const int chunk = MODE == 0 ? gw % C : 0;
     if (song >= a.B) return;
     if (a.skip_nonpositive && a.lengths[song] < 1) return;        // segment of a checkpointed decode this song does not reach
-    const int Tb = sp_song_length(a.lengths, song, T);
+    const int Tb = song_length(a.lengths, song, T);
     int32_t* __restrict__ states = a.states + (size_t)song * a.states_stride;
     const float* __restrict__ hist = a.hist + (size_t)song * a.hist_rows * SD;
     float* tile = tiles + wv * kSpK * kSpRS;
@@ -202,13 +167,13 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
                         for (;;) {
                             int curv;
                             asm volatile("v_mov_b32 %0, %1" : "=v"(curv) : "s"(cur));
-                            const int lov = sp_clamp(curv - a.lo_off, lo_max);
+                            const int lov = clamp_med3(curv - a.lo_off, lo_max);
                             const int wlov = lov + (a.col0 - c0);
                             // (a window that left the span reads entries of the tile that are not its own -- or nothing: LDS reads beyond the
                             //  allocation return zero -- and the row is an exceptional one whatever they hold)
                             const float dv = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(tile + r * kSpRS) + __umul24(wlov, fr_mul) + fr_off);
                             const float vv = dv + tabX[__umul24(curv, WX1) + tb[0]];
-                            const float mx = sp_wave_max(cand[0] ? vv : -INFINITY);
+                            const float mx = wave_max_all(cand[0] ? vv : -INFINITY);
                             const unsigned long long ge = __ballot(vv >= mx) & cand_or_bound;
                             if ((__ballot((unsigned)wlov > (unsigned)(kSpNS - W)) | (ge & (1ull << CB))) != 0) break;
                             const unsigned long long gw = ge & wmask[0];
@@ -242,7 +207,7 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
                     av[0] = tabX[curv * WX1 + tb[0]];
                     const float vv = dv + av[0];
                     v[0] = cand[0] ? vv : -INFINITY;
-                    m = sp_wave_max(v[0]);
+                    m = wave_max_all(v[0]);
                     ge = __ballot(vv >= m) & cand_or_bound;
                     fail = (ge >> CB) & 1ull;
                     lo = __builtin_amdgcn_readfirstlane(lov);
@@ -268,7 +233,7 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
                         v[k] = cand[k] ? v[k] : -INFINITY;
                         mloc = fmaxf(mloc, v[k]);
                     }
-                    m = sp_wave_max(mloc);
+                    m = wave_max_all(mloc);
                     fail = !(mf < m);
                 }
                 auto lowest_candidate = [&](const float mm) -> unsigned {
@@ -314,7 +279,7 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
                         vf[e] = excl ? -INFINITY : d + cj;
                         m2 = fmaxf(m2, vf[e]);
                     }
-                    const float mm = fmaxf(m, sp_wave_max(m2));
+                    const float mm = fmaxf(m, wave_max_all(m2));
 #pragma unroll
                     for (int e = 0; e < EPL; ++e) {
                         const unsigned long long mk = __ballot(vf[e] == mm && inS[e]);
@@ -359,7 +324,7 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
                 d[e] = inS[e] ? g[e * 64 + lane] : -INFINITY;
                 m = fmaxf(m, d[e]);
             }
-            m = sp_wave_max(m);
+            m = wave_max_all(m);
             unsigned idx = 0x7fffffffu;
 #pragma unroll
             for (int e = 0; e < EPL; ++e) {
@@ -406,7 +371,7 @@ static size_t sparse_lds_bytes(const BtArgs& a, int nwaves, bool table_in_lds) {
     const int rs = sp_span(sparse_kc(a)) + kSpAux;
     return sizeof(float) * ((size_t)nwaves * kSpK * rs + (table_in_lds ? (size_t)a.SP * (a.W + kMaxExtras + 1) : 0)) + sizeof(int32_t) * a.SP;
 }
-static bool sparse_table_fits(const BtArgs& a) { return sparse_lds_bytes(a, 4, true) + 1024 <= 160 * 1024; }
+static bool sparse_table_fits(const BtArgs& a) { return sparse_lds_bytes(a, 4, true) + 1024 <= kLdsBytes; }
 
 // The sparse kernel takes banded plans without dense rows whose forward pass left the frame maximum in the history,
 // with at most three candidates per lane and the span inside a row.
@@ -419,7 +384,7 @@ bool sparse_backtrace_applies(const BtArgs& a) {
 template <int NWT, bool AFF, int KC, bool GT>
 static hipError_t launch_sparse_t(const BtArgs& a, hipStream_t st, int phases) {
     int nw = 16;
-    while (nw > 4 && sparse_lds_bytes(a, nw, !GT) + 1024 > 160 * 1024) nw >>= 1;
+    while (nw > 4 && sparse_lds_bytes(a, nw, !GT) + 1024 > kLdsBytes) nw >>= 1;
     const size_t lds = sparse_lds_bytes(a, nw, !GT);
     const long long waves0 = (long long)a.B * a.chunks;
     hipError_t e = hipSuccess;

@@ -1,0 +1,839 @@
+// banded.hip -- banded forward kernels (plan.ok): the scan form, the floor-max form and its two-targets-per-lane variant,
+// and the DPP self-test of the wave primitives they are built from.
+#include "device_common.hpp"
+
+namespace vit {
+
+// ---------------------------------------------------------------------------------------
+// Banded forward kernel: one song per workgroup, value-only.
+//
+// For a banded target j (window [lo_j, lo_j+W), row constant c_j, extra columns X):
+//   m_j = max( max_w fl(delta_{lo_j+w} + logA_T[j][lo_j+w]),   W register-resident window entries
+//              fl( max(Pv[lo_j], Sv[lo_j+W]) + c_j ),          Pv/Sv: prefix / suffix max of the RAW delta
+//              fl(delta_x + logA_T[j][x]), x in X )             (extra columns are excluded from the scans)
+// Rounding is monotone, so max_i fl(delta_i + c_j) = fl(max_i delta_i + c_j): the value equals the max
+// of the fl32 sums the dense recursion forms, and delta is bit-identical.  Dense rows (none for the
+// reference's matrices) are a full max over all sources.
+//
+// Wave roles (NWT target waves, 64*NWT >= S):
+//   waves 0..NWT-1  one thread per target: window max, merge, delta_t, history row
+//   wave  NWT       prefix-max scan over all sources (NWT per lane)
+//   wave  NWT+1     suffix-max scan (lanes hold the sources in descending blocks)
+//   wave  NWT+2     dense rows
+// A SIMD retires one wave64 VALU instruction per 4 cycles, shared by the waves resident on it, so
+// the frame time is set by the VALU instruction count of the busiest SIMD plus the two barriers.
+// Two workgroup barriers per frame; emission rows are fetched two frames ahead.
+// ---------------------------------------------------------------------------------------
+// DBG = true adds the timing-experiment hooks (ablation mask, cycle stamps); the production instantiation has none.
+// NXT >= 0 specialises for exactly NXT extra columns and no dense rows (the reference's matrices: NXT = 1);
+// NXT < 0 is the generic form (run-time counts).  Every untaken branch costs an issue slot per frame.
+template <int W, int NWT, bool DW, bool DBG, int NXT, typename ET>
+__global__ void __launch_bounds__((NWT + (DW ? 3 : 2)) * 64) banded_forward_kernel(FwdArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int NP = NWT * 64;
+    constexpr int EPL = NWT;
+    const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
+    // delta_{t-1} is kept as four copies shifted by 0..3 entries (entry m of copy c = delta[m + c], copy c
+    // at dls + c*DC + 4): every lane reads its window with aligned 16-byte LDS reads (256 B/clk instead of
+    // the 128 B/clk of 4-/8-byte reads, which bound the window phase) from the copy that makes its window
+    // start 16-byte aligned.  Each copy has 4 pad entries in front, so the four writes of a new delta value
+    // (entry j - c of copy c) need no bounds test.  Entries >= S stay -inf.
+    constexpr int DC = NP + 16;                   // copy stride = 16 banks mod 64: a 16-lane read group covers all 64 banks
+    float* dls = reinterpret_cast<float*>(smem);  // [4][DC]
+    float* dl = dls + 4;                          // copy 0 (unshifted)
+    float* Pv = dls + 4 * DC;                     // [NP+1]  Pv[q] = max_{i<q}  raw delta (extras excluded)
+    float* Sv = Pv + NP + 1;                      // [NP+1]  Sv[q] = max_{i>=q} raw delta
+    float* Dv = Sv + NP + 1;                      // [4]     dense-row maxima
+    VI* tot = reinterpret_cast<VI*>(Dv + kMaxDenseRows);  // [16] terminal argmax scratch (4*DC + 2*NP + 6 floats before: 8-byte aligned)
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform for the compiler
+    const int song = blockIdx.x;
+    const int Tb = song_length(a.lengths, song, T);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
+    float* __restrict__ hist = a.hist + (size_t)song * T * SD;
+    constexpr bool GEN = NXT < 0;
+    constexpr int NXL = GEN ? kMaxExtras : NXT;            // extra columns the loops are unrolled for
+    const int nx = GEN ? a.n_extras : NXT, nd = GEN ? a.n_dense : 0;
+#ifdef VIT_TIMING_HOOKS
+    const int dbg = DBG ? a.debug : 0;
+#else
+    constexpr int dbg = 0;          // the ablation / probe hooks exist only in VIT_TIMING_HOOKS builds (scripts/)
+#endif
+
+    // ---------------- per-role setup
+    const bool is_target = wv < NWT;
+    const int j = tid;
+    const bool tvalid = is_target && j < S;
+    const int jst = j < S ? j : S + 1;                     // idle lanes store into pad column S+1 of the history row (SD >= S+2 always)
+    const int jld = j < S ? j : S - 1;
+    const int jc = j < SP ? j : 0;
+    int lo = 0, kind = -2;
+    float cj = 0.f;
+    float aw[W];
+    float xa[kMaxExtras];
+    int xcol[kMaxExtras];
+#pragma unroll
+    for (int k = 0; k < kMaxExtras; ++k) { xa[k] = -INFINITY; xcol[k] = a.extras[k]; }
+#pragma unroll
+    for (int w = 0; w < W; ++w) aw[w] = 0.f;
+    if (is_target) {
+        cj = reinterpret_cast<const float*>(a.image + a.off_rowc)[jc];
+        lo = reinterpret_cast<const int32_t*>(a.image + a.off_lo)[jc];
+        kind = j < SP ? reinterpret_cast<const int32_t*>(a.image + a.off_kind)[jc] : -2;
+        const float* __restrict__ tab = reinterpret_cast<const float*>(a.image + a.off_tabA);
+        const float* __restrict__ xaT = reinterpret_cast<const float*>(a.image + a.off_extraA);
+#pragma unroll
+        for (int w = 0; w < W; ++w) aw[w] = tab[(size_t)w * SP + jc];
+#pragma unroll
+        for (int k = 0; k < kMaxExtras; ++k) xa[k] = xaT[(size_t)k * SP + jc];
+    }
+    const int role = wv - NWT;                 // 0 prefix, 1 suffix, 2 dense rows (DW) -- else the suffix wave reduces them
+    constexpr int kDenseRole = DW ? 2 : 1;
+    const int blk = role == 1 ? 63 - lane : lane;
+    const int i0 = blk * EPL;
+    bool smask[EPL];
+    float dA[kMaxDenseRows][EPL];
+    {
+        const float* __restrict__ daT = reinterpret_cast<const float*>(a.image + a.off_denseA);
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) {
+            const int i = i0 + e;
+            bool m = i >= S;
+#pragma unroll
+            for (int k = 0; k < kMaxExtras; ++k) m |= (k < nx && i == xcol[k]);
+            smask[e] = m;
+#pragma unroll
+            for (int d = 0; d < kMaxDenseRows; ++d)
+                dA[d][e] = (role == kDenseRole && i < S && d < nd) ? daT[(size_t)d * SP + i] : -INFINITY;
+        }
+    }
+
+    // ---------------- frame 0
+    for (int k = tid; k < 4 * DC; k += blockDim.x) dls[k] = -INFINITY;
+    __syncthreads();
+    if (is_target) {
+        if (tvalid) {
+            const float d = reinterpret_cast<const float*>(a.image + a.off_logpi)[j] + load_e<ET>(E + j);
+            hist[j] = d;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) dl[c * DC + j - c] = d;
+        }
+    } else if (lane == 0) {
+        if (role == 0) Pv[0] = -INFINITY;
+        if (role == 1) Sv[NP] = -INFINITY;
+    }
+    // Emission rows are fetched two frames ahead and consumed only at the end of a frame: vmcnt
+    // retires in order, so a wait on a younger load would also wait for the previous frame's store.
+    float e_a = (tvalid && Tb > 1) ? load_e<ET>(E + S + j) : 0.f;
+    float e_b = (tvalid && Tb > 2) ? load_e<ET>(E + 2 * (size_t)S + j) : 0.f;
+    // Retire every set-up load here so the frame loop only sees the two memory ops it issues.
+#pragma unroll
+    for (int w = 0; w < W; ++w) asm volatile("" ::"v"(aw[w]));
+#pragma unroll
+    for (int k = 0; k < kMaxExtras; ++k) asm volatile("" ::"v"(xa[k]));
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+#pragma unroll
+        for (int d = 0; d < kMaxDenseRows; ++d) asm volatile("" ::"v"(dA[d][e]));
+    }
+    asm volatile("" ::"v"(lo), "v"(kind), "v"(cj), "v"(e_a), "v"(e_b));
+    __syncthreads();
+
+    unsigned long long ph0 = 0, ph1 = 0, ph2 = 0, ph3 = 0;   // timing experiments only (dbg & 256)
+    auto stamp = [&]() -> unsigned long long {
+        unsigned long long v;
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v)::"memory");
+        return v;
+    };
+    auto frame = [&](const int t, float& e_slot) {
+        float m = -INFINITY;
+        const bool prof = (dbg & 256) != 0;
+        const unsigned long long s0 = prof ? stamp() : 0ull;
+        if (is_target) {
+            // ---- window max (reads delta_{t-1}); four independent max3 chains
+            float m0 = -INFINITY, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
+            float xd[NXL > 0 ? NXL : 1];
+#pragma unroll
+            for (int k = 0; k < NXL; ++k) xd[k] = (!GEN || k < nx) ? dl[xcol[k]] : -INFINITY;
+            if (!(dbg & 1)) {
+                // copy (lo & 3), entry (lo & ~3): delta[lo .. lo+W) as W/4 aligned 16-byte reads
+                const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(dl + (lo & 3) * DC + (lo & ~3));
+#pragma unroll
+                for (int w = 0; w + 7 < W; w += 8) {
+                    const f32x4 da = win[w / 4], db = win[w / 4 + 1];
+                    // v_pk_add_f32: two fl32 adds per instruction (each lane still rounds separately)
+                    const f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[w + 0], aw[w + 1]};
+                    const f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[w + 2], aw[w + 3]};
+                    const f32x2 c2_ = f32x2{db.x, db.y} + f32x2{aw[w + 4], aw[w + 5]};
+                    const f32x2 c3_ = f32x2{db.z, db.w} + f32x2{aw[w + 6], aw[w + 7]};
+                    m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
+                    m1 = fmaxf(fmaxf(m1, c1_.x), c1_.y);
+                    m2 = fmaxf(fmaxf(m2, c2_.x), c2_.y);
+                    m3 = fmaxf(fmaxf(m3, c3_.x), c3_.y);
+                }
+            }
+            // extra columns are consumed after the window so that their LDS read shares the window's wait
+#pragma unroll
+            for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
+            m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+        } else if (!(dbg & 2)) {
+            float d[EPL];
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) d[e] = dl[i0 + e];
+            if (role == 0) {
+                float p[EPL];
+                float run = -INFINITY;
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) {
+                    run = fmaxf(run, smask[e] ? -INFINITY : d[e]);
+                    p[e] = run;
+                }
+                const float inc = wave_scan_max(run);
+                const float ex = wave_shift_up(inc, -INFINITY);                 // sources of all lower lanes
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) Pv[i0 + e + 1] = fmaxf(ex, p[e]);
+                // max of delta_{t-1} over the non-extra sources: bounds every row-constant candidate in the back-trace
+                if (lane == 63 && !(dbg & 8)) hist[(size_t)(t - 1) * SD + S] = inc;   // pad column S of row t-1
+            } else {
+                if (role == 1) {
+                    float p[EPL];
+                    float run = -INFINITY;
+#pragma unroll
+                    for (int e = EPL - 1; e >= 0; --e) {
+                        run = fmaxf(run, smask[e] ? -INFINITY : d[e]);
+                        p[e] = run;
+                    }
+                    const float ex = wave_shift_up(wave_scan_max(run), -INFINITY);  // sources of all higher blocks
+#pragma unroll
+                    for (int e = 0; e < EPL; ++e) Sv[i0 + e] = fmaxf(ex, p[e]);
+                }
+                if (GEN && role == kDenseRole) {
+#pragma unroll
+                    for (int dr = 0; dr < kMaxDenseRows; ++dr) {
+                        if (dr < nd) {
+                            float dm = -INFINITY;
+#pragma unroll
+                            for (int e = 0; e < EPL; ++e) dm = fmaxf(dm, d[e] + dA[dr][e]);
+                            dm = wave_max_all(dm);
+                            if (lane == 0) Dv[dr] = dm;
+                        }
+                    }
+                }
+            }
+        }
+        const unsigned long long s1 = prof ? stamp() : 0ull;
+        __syncthreads();
+        const unsigned long long s2 = prof ? stamp() : 0ull;
+
+        if (is_target && !(dbg & 4)) {
+            m = fmaxf(m, fmaxf(Pv[lo], Sv[lo + W]) + cj);
+            if (GEN) {
+                const float dres = Dv[kind >= 0 ? kind : 0];
+                if (kind >= 0) m = dres;
+            }
+            {
+                // Every target lane stores and prefetches unconditionally (idle lanes: a pad column of the
+                // history row / the last valid emission) so that the in-order vmcnt of the next use is exact
+                // -- a conditional would make the compiler wait for the previous frame's store as well.
+                const float dn = tvalid ? m + e_slot : -INFINITY;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) dl[c * DC + j - c] = dn;
+                if (!(dbg & 8)) {
+                    float* __restrict__ hrow = hist + (size_t)t * SD;          // wave-uniform row bases:
+                    const int tn = t + 2 < Tb ? t + 2 : Tb - 1;                 // scalar base + lane offset
+                    const ET* __restrict__ erow = E + (size_t)tn * S;
+                    hrow[jst] = dn;
+                    e_slot = load_e<ET>(erow + jld);
+                }
+            }
+        }
+        const unsigned long long s3 = prof ? stamp() : 0ull;
+        __syncthreads();
+        if (prof) {
+            const unsigned long long s4 = stamp();
+            ph0 += s1 - s0; ph1 += s2 - s1; ph2 += s3 - s2; ph3 += s4 - s3;
+        }
+    };
+    const unsigned long long clk0 = (dbg & 48) ? __builtin_amdgcn_s_memtime() : 0ull;
+    const unsigned long long rt0 = (dbg & 48) ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    int t = 1;
+    for (; t + 1 < Tb; t += 2) {
+        frame(t, e_a);
+        frame(t + 1, e_b);
+    }
+    if (t < Tb) frame(t, e_a);
+
+    terminal_argmax(is_target ? dl[j] : -INFINITY, j, tvalid, tot, NWT + (DW ? 3 : 2), a.last_state, a.loglik, song);
+    if ((dbg & 256) && lane == 0 && Tb > 1) {   // per-wave phase averages -> fmax[song][4*wave .. 4*wave+3]
+        float* o = a.fmax + (size_t)song * 64 + 4 * wv;
+        const float n = (float)(Tb - 1);
+        o[0] = (float)ph0 / n; o[1] = (float)ph1 / n; o[2] = (float)ph2 / n; o[3] = (float)ph3 / n;
+    }
+    if ((dbg & 48) && tid == 0) {  // timing experiments only: cycles (16) or 100 MHz ticks (32) per frame -> scratch slot 63
+        const unsigned long long d = (dbg & 16) ? __builtin_amdgcn_s_memtime() - clk0 : __builtin_amdgcn_s_memrealtime() - rt0;
+        a.fmax[(size_t)song * 64 + 63] = (float)d / (float)(Tb > 1 ? Tb - 1 : 1);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Banded forward kernel, "floor-max" form (plan.floor_ok): one song per workgroup, value-only, ONE barrier
+// and no scan waves per frame.
+//
+// The plan proved that no in-window entry of a banded row is below the row constant c_j.  Let M be the max of
+// the RAW delta_{t-1} over all non-extra sources, attained at i*.  If i* is outside the window of target j,
+// fl(M + c_j) IS the out-of-window term.  If i* is inside, fl(M + c_j) <= fl(delta_i* + logA_T[j][i*]) (rounding
+// is monotone and logA_T[j][i*] >= c_j), which the window max already contains, and every out-of-window term is
+// <= fl(M + c_j) -- so in both cases
+//   m_j = max( window max, fl(M + c_j), extra-column terms )
+// is the value the dense recursion computes, bit for bit.  M is one number per frame: every wave reduces the
+// delta values it has just produced (six DPP max steps) and publishes one float; after the frame's only barrier
+// every lane combines the NWT wave maxima.  delta is double-buffered in LDS (four shifted copies each, see
+// banded_forward_kernel), so nothing a wave reads in frame t is written before the barrier that ends frame t.
+// M (= the back-trace's bound on every row-constant candidate) is stored in pad column S of the history row.
+// ---------------------------------------------------------------------------------------
+template <int W, int NWT, int NXT, int PF, typename ET>
+__global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int NP = NWT * 64;
+    constexpr int DC = NP + 16;                   // copy stride (see banded_forward_kernel)
+    constexpr int BUF = 4 * DC;                   // floats per delta buffer
+    constexpr int NWM = (NWT + 3) / 4 * 4;        // wave maxima per buffer, padded to whole float4s with -inf
+    float* dls = reinterpret_cast<float*>(smem);  // [2][4][DC]
+    float* wm = dls + 2 * BUF;                    // [2][NWM]
+    float* dump = wm + 2 * NWM;                   // [64 + NWM] per-lane dump slots (lanes that do not own a wave max)
+    VI* tot = reinterpret_cast<VI*>(dump + 64 + NWM);
+    // W = 128 with twelve waves (S > 512) leaves 168 registers per thread: the last 32 window weights then live in LDS
+    // ([8][NP] float4-interleaved, read with conflict-free 16-byte reads next to the delta window)
+    constexpr int WR = (W == 128 && NWT > 8) ? 96 : W;     // register-resident window weights
+    f32x4* awl = reinterpret_cast<f32x4*>(tot + 16);       // [(W - WR) / 4][NP]
+    const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
+    constexpr bool GEN = NXT < 0;
+    constexpr int NXL = GEN ? kMaxExtras : NXT;
+    const int nx = GEN ? a.n_extras : NXT;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int song = blockIdx.x;
+    const int Tb = song_length(a.lengths, song, T);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
+    float* __restrict__ hist = a.hist + (size_t)song * T * SD;
+
+    // ---------------- per-lane constants.  Idle lanes (j >= S) carry -inf tables: their delta stays -inf.
+    const int j = tid;
+    const bool tvalid = j < S;
+    const int jc = tvalid ? j : 0;
+    const int jld = tvalid ? j : S - 1;                                   // emission column an idle lane (harmlessly) loads
+    // history store of frame t, relative to row t-1: own column of row t | lane S: M into pad column S of row t-1
+    // | other idle lanes: pad column S+1 of row t (never read)
+    const unsigned hoff = tvalid ? (unsigned)(SD + j) : (j == S ? (unsigned)S : (unsigned)(SD + S + 1));
+    const bool is_fm = j == S;
+    const int lo = reinterpret_cast<const int32_t*>(a.image + a.off_lo)[jc];
+    const float cj = tvalid ? reinterpret_cast<const float*>(a.image + a.off_rowc)[jc] : -INFINITY;
+    float aw[WR];
+    float xa[NXL > 0 ? NXL : 1];
+    int xcol[NXL > 0 ? NXL : 1];
+    bool is_x = false;                                                    // this lane's state is an extra column: not part of M
+    {
+        const float* __restrict__ tab = reinterpret_cast<const float*>(a.image + a.off_tabA);
+        const float* __restrict__ xaT = reinterpret_cast<const float*>(a.image + a.off_extraA);
+#pragma unroll
+        for (int w = 0; w < WR; ++w) aw[w] = tvalid ? tab[(size_t)w * SP + jc] : -INFINITY;
+#pragma unroll
+        for (int q = 0; q < (W - WR) / 4; ++q) {
+            f32x4 wv4;
+            wv4.x = tvalid ? tab[(size_t)(WR + 4 * q + 0) * SP + jc] : -INFINITY;
+            wv4.y = tvalid ? tab[(size_t)(WR + 4 * q + 1) * SP + jc] : -INFINITY;
+            wv4.z = tvalid ? tab[(size_t)(WR + 4 * q + 2) * SP + jc] : -INFINITY;
+            wv4.w = tvalid ? tab[(size_t)(WR + 4 * q + 3) * SP + jc] : -INFINITY;
+            awl[q * NP + j] = wv4;
+        }
+#pragma unroll
+        for (int k = 0; k < NXL; ++k) {
+            xcol[k] = k < nx ? a.extras[k] : 0;
+            xa[k] = (tvalid && k < nx) ? xaT[(size_t)k * SP + jc] : -INFINITY;
+            is_x |= (k < nx && j == xcol[k]);
+        }
+    }
+    // delta[i] lives at float position 4 + sh + i - c of copy c (sh = a.win_shift): lane j reads its window from the copy
+    // that makes delta[lo_j] 16-byte aligned.  With sh = lo_off mod 4 the sixteen lanes of one LDS read group start on
+    // sixteen different 4-bank groups; without it the first and the last lane of a group collide (2-way conflict on
+    // every ds_read_b128: 128 instead of 256 B/clk).
+    const int sh = a.win_shift;
+    const int lov = (tvalid ? lo : 0) + sh;
+    const float* rp = dls + 4 + (lov & 3) * DC + (lov & ~3);              // window start in the copy that aligns it
+    float* wp = dls + 4 + sh + j;                                         // own entry of copy 0 (copy c: + c*DC - c)
+    float* wmp = lane == 63 ? wm + wv : dump + lane;                      // lane 63 ends up with the wave maximum
+
+    for (int k = tid; k < 2 * BUF + 2 * NWM; k += NWT * 64) dls[k] = -INFINITY;
+    __syncthreads();
+
+    // produce(): publish a new delta value -- four shifted copies and the wave's share of M -- into buffer WB
+    auto produce = [&](const float dn, const int WB) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) wp[WB * BUF + c * DC - c] = dn;
+        const float inc = wave_scan_max((NXL > 0 && is_x) ? -INFINITY : dn);
+        wmp[WB * NWM] = inc;
+    };
+
+    // ---------------- frame 0
+    {
+        const float d0 = tvalid ? reinterpret_cast<const float*>(a.image + a.off_logpi)[j] + load_e<ET>(E + j) : -INFINITY;
+        if (tvalid) hist[j] = d0;
+        produce(d0, 0);
+    }
+    // Emission rows are fetched PF frames ahead (PF even): a global load takes ~2 us under load, several frame times,
+    // and the s_waitcnt before a frame's "+ e" must not be what paces the recursion.
+    float er[PF];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S + jld);
+#pragma unroll
+    for (int w = 0; w < WR; ++w) asm volatile("" ::"v"(aw[w]));
+#pragma unroll
+    for (int k = 0; k < NXL; ++k) asm volatile("" ::"v"(xa[k]));
+    asm volatile("" ::"v"(cj));
+    __syncthreads();
+
+    auto frame = [&](const int t, float& e_slot, const int RB) {
+        const int WB = RB ^ 1;
+        // ---- everything this frame reads from LDS: the window, the extra columns, the wave maxima
+        const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
+        float xd[NXL > 0 ? NXL : 1];
+        // the NWT wave maxima: whole float4s, plus one float2 when NWT % 4 is 2 or 3 (slots >= NWT hold -inf)
+        f32x4 wq[NWT / 4 > 0 ? NWT / 4 : 1];
+        f32x2 wr = f32x2{-INFINITY, -INFINITY};
+        float wl = -INFINITY;
+        // The small reads go out first and the first chunk of the window right behind them, and only then is M reduced: left to
+        // itself the compiler reduces M before it issues the window reads -- a full LDS round trip with nothing else in flight.
+        // (M reduced last instead lengthens the dependent tail after the last window read lands: measured slower.)
+        auto small_reads = [&]() {
+#pragma unroll
+            for (int k = 0; k < NXL; ++k) xd[k] = dls[4 + sh + RB * BUF + xcol[k]];
+#pragma unroll
+            for (int q = 0; q < NWT / 4; ++q) wq[q] = reinterpret_cast<const f32x4*>(wm + RB * NWM)[q];
+            if (NWT % 4 >= 2) wr = *reinterpret_cast<const f32x2*>(wm + RB * NWM + (NWT / 4) * 4);
+            if (NWT % 4 == 1 || NWT % 4 == 3) wl = wm[RB * NWM + NWT - 1];
+        };
+        // the window in chunks of 32 sources (8 reads): wide windows (W = 96, 128) must not hold all their data at once
+        float m0 = -INFINITY, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
+        float M = -INFINITY;
+        small_reads();
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int w0 = 0; w0 < W; w0 += 32) {
+        // W > 64: one chunk of reads in flight at a time (W register-resident weights leave no room for more; with
+        // twelve waves per workgroup the other waves of the SIMD cover the read latency)
+        if ((W > 64 || (W == 64 && NWT > 8)) && w0 > 0) asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3)::"memory");
+        f32x4 dw[8];
+#ifdef VIT_ABL_READS
+        // result-breaking ablation (make TIMING=1 ABL=n builds only): read n of every chunk's window quads, the others reuse them --
+        // what does the LDS return path cost a frame?
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (w0 + 4 * q < W) { if (q < VIT_ABL_READS) dw[q] = win[w0 / 4 + q]; else dw[q] = dw[q % VIT_ABL_READS]; }
+#else
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            if (w0 + 4 * q < W) dw[q] = win[w0 / 4 + q];
+#endif
+        if (w0 == 0) {
+            __builtin_amdgcn_sched_barrier(0);
+            // M = max of delta_{t-1} over the non-extra sources
+            M = wl;
+            if (NWT % 4 >= 2) M = fmaxf(fmaxf(M, wr.x), wr.y);
+#pragma unroll
+            for (int q = 0; q < NWT / 4; ++q) M = fmaxf(fmaxf(fmaxf(M, wq[q].x), wq[q].y), fmaxf(wq[q].z, wq[q].w));
+            m0 = M + cj;
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int w = w0; w + 7 < W && w < w0 + 32; w += 8) {
+            const f32x4 da = dw[(w - w0) / 4], db = dw[(w - w0) / 4 + 1];
+            f32x4 wa, wb;
+            if (w < WR) {
+                wa = f32x4{aw[w < WR ? w + 0 : 0], aw[w < WR ? w + 1 : 0], aw[w < WR ? w + 2 : 0], aw[w < WR ? w + 3 : 0]};
+                wb = f32x4{aw[w < WR ? w + 4 : 0], aw[w < WR ? w + 5 : 0], aw[w < WR ? w + 6 : 0], aw[w < WR ? w + 7 : 0]};
+            } else {
+                wa = awl[((w - WR) / 4) * NP + j];
+                wb = awl[((w - WR) / 4 + 1) * NP + j];
+            }
+            const f32x2 c0_ = f32x2{da.x, da.y} + f32x2{wa.x, wa.y};
+            const f32x2 c1_ = f32x2{da.z, da.w} + f32x2{wa.z, wa.w};
+            const f32x2 c2_ = f32x2{db.x, db.y} + f32x2{wb.x, wb.y};
+            const f32x2 c3_ = f32x2{db.z, db.w} + f32x2{wb.z, wb.w};
+            m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
+            m1 = fmaxf(fmaxf(m1, c1_.x), c1_.y);
+            m2 = fmaxf(fmaxf(m2, c2_.x), c2_.y);
+            m3 = fmaxf(fmaxf(m3, c3_.x), c3_.y);
+        }
+        if (W % 8 == 4 && w0 + 32 >= W) {          // W = 84: the last four sources (one read, two packed adds)
+            static_assert(W % 8 != 4 || W <= WR, "an odd float4 count only with register-resident weights");
+            const f32x4 da = dw[((W - 4 - w0) / 4) & 7];
+            const f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[W - 4], aw[W - 3]};
+            const f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[W - 2], aw[W - 1]};
+            m2 = fmaxf(fmaxf(m2, c0_.x), c0_.y);
+            m3 = fmaxf(fmaxf(m3, c1_.x), c1_.y);
+        }
+        }
+#pragma unroll
+        for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
+        const float dn = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)) + e_slot;
+        produce(dn, WB);
+        asm volatile("" ::: "memory");   // keep the global store / prefetch behind the wave-max publication: they fill the
+                                         // wait for the LDS write acknowledgement before the barrier (-2 %)
+        // Unconditional store + prefetch: exact in-order vmcnt accounting (see banded_forward_kernel).  Row bases are
+        // scalar index arithmetic on purpose: the SALU is idle, the VALU is not (running 64-bit per-lane pointers
+        // measured 3.5% slower).
+        const int tn = t + PF < Tb ? t + PF : Tb - 1;
+        hist[(size_t)(t - 1) * SD + hoff] = is_fm ? M : dn;
+        e_slot = load_e<ET>(E + (size_t)tn * S + jld);
+        __syncthreads();
+    };
+#ifdef VIT_TIMING_HOOKS
+    const bool probe = (a.debug & 48) != 0;
+#else
+    constexpr bool probe = false;   // cycle probe: VIT_TIMING_HOOKS builds only; it writes the per-song scratch, never an output
+#endif
+    const unsigned long long clk0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
+    const unsigned long long rt0 = probe ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    int t = 1;
+    for (; t + PF - 1 < Tb; t += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) frame(t + k, er[k], k & 1);
+    }
+#pragma unroll
+    for (int k = 0; k < PF - 1; ++k)
+        if (t + k < Tb) frame(t + k, er[k], k & 1);
+
+    const int fb = (Tb - 1) & 1;                                          // buffer holding delta_{Tb-1}
+    terminal_argmax(tvalid ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, tvalid, tot, NWT, a.last_state, a.loglik, song);
+    if (probe && tid == 0) {  // timing experiments only: cycles (16) or 100 MHz ticks (32) per frame -> scratch slot 63
+        const unsigned long long d = (a.debug & 16) ? __builtin_amdgcn_s_memtime() - clk0 : __builtin_amdgcn_s_memrealtime() - rt0;
+        a.fmax[(size_t)song * 64 + 63] = (float)d / (float)(Tb > 1 ? Tb - 1 : 1);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Floor-max banded forward kernel, two targets per lane (plan.pair_ok && plan.floor_ok; what the bench runs).
+//
+// What bounds a frame of banded_floor_forward_kernel is the LDS return path: every target pulls its own W floats
+// into registers (46 KB per frame at S = 361) and ds_read_b128 delivers ~128 B/clk per CU, ~380 of the ~870 cycles.
+// The plan proves that the exception spans of targets 2p and 2p+1 together fit one window [lo2_p, lo2_p + W); entries
+// of that window outside a row's own span are that row's constant (or an extra column), i.e. still >= c_j, so the
+// floor-max identity holds for the common window.  One lane therefore evaluates BOTH targets from one set of W/4
+// window reads: half the LDS traffic and half the waves (three at S = 361, one per SIMD), the same packed adds and
+// max3 per target.  Everything else is as in banded_floor_forward_kernel.
+// ---------------------------------------------------------------------------------------
+template <int W, int NPW, int NXT, int PF, typename ET>
+__global__ void __launch_bounds__(NPW * 64) banded_floor_pair_forward_kernel(FwdArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int NP = NPW * 128;                 // padded state count
+    constexpr int DC = NP + 16;                   // copy stride (see banded_forward_kernel)
+    constexpr int BUF = 4 * DC;                   // floats per delta buffer
+    constexpr int NWM = (NPW + 3) / 4 * 4;        // wave maxima per buffer, whole float4s (slots >= NPW hold -inf)
+    float* dls = reinterpret_cast<float*>(smem);  // [2][4][DC]
+    float* wm = dls + 2 * BUF;                    // [2][NWM]
+    float* dump = wm + 2 * NWM;                   // [64 + NWM]
+    VI* tot = reinterpret_cast<VI*>(dump + 64 + NWM);
+    const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
+    constexpr bool GEN = NXT < 0;
+    constexpr int NXL = GEN ? kMaxExtras : NXT;
+    const int nx = GEN ? a.n_extras : NXT;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int song = blockIdx.x;
+    const int Tb = song_length(a.lengths, song, T);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
+    float* __restrict__ hist = a.hist + (size_t)song * T * SD;
+
+    // ---------------- per-lane constants.  Slots past S carry -inf tables: their delta stays -inf.
+    const int j0 = 2 * tid, j1 = 2 * tid + 1;
+    const bool v0 = j0 < S, v1 = j1 < S;
+    const int jc0 = v0 ? j0 : 0, jc1 = v1 ? j1 : jc0;
+    const int jl0 = v0 ? j0 : S - 1, jl1 = v1 ? j1 : S - 1;               // emission columns (idle slots load a valid one)
+    // history stores of frame t, relative to row t-1: own column of row t | slot S: M into pad column S of row t-1
+    // | other idle slots: pad column S+1 of row t (never read)
+    const unsigned hoff0 = v0 ? (unsigned)(SD + j0) : (j0 == S ? (unsigned)S : (unsigned)(SD + S + 1));
+    const unsigned hoff1 = v1 ? (unsigned)(SD + j1) : (j1 == S ? (unsigned)S : (unsigned)(SD + S + 1));
+    const bool fm0 = j0 == S, fm1 = j1 == S;
+    const int lo2 = v0 ? reinterpret_cast<const int32_t*>(a.image + a.off_lo2)[jc0 >> 1] : 0;
+    const float* __restrict__ rc = reinterpret_cast<const float*>(a.image + a.off_rowc);
+    f32x2 cj = f32x2{v0 ? rc[jc0] : -INFINITY, v1 ? rc[jc1] : -INFINITY};
+    float aw0[W], aw1[W];
+    f32x2 xa[NXL > 0 ? NXL : 1];
+    int xcol[NXL > 0 ? NXL : 1];
+    bool x0 = false, x1 = false;                                          // slot is an extra column: not part of M
+    {
+        const float* __restrict__ tab = reinterpret_cast<const float*>(a.image + a.off_tabP);
+        const float* __restrict__ xaT = reinterpret_cast<const float*>(a.image + a.off_extraA);
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            aw0[w] = v0 ? tab[(size_t)w * SP + jc0] : -INFINITY;
+            aw1[w] = v1 ? tab[(size_t)w * SP + jc1] : -INFINITY;
+        }
+#pragma unroll
+        for (int k = 0; k < NXL; ++k) {
+            xcol[k] = k < nx ? a.extras[k] : 0;
+            xa[k] = f32x2{(v0 && k < nx) ? xaT[(size_t)k * SP + jc0] : -INFINITY, (v1 && k < nx) ? xaT[(size_t)k * SP + jc1] : -INFINITY};
+            x0 |= (k < nx && j0 == xcol[k]);
+            x1 |= (k < nx && j1 == xcol[k]);
+        }
+    }
+    // delta[i] lives at float position 4 + sh + i - c of copy c; the lane reads the common window from the copy that
+    // makes delta[lo2] 16-byte aligned (sh: see banded_floor_forward_kernel)
+    const int sh = a.win_shift2;
+    const int lov = lo2 + sh;
+    const float* rp = dls + 4 + (lov & 3) * DC + (lov & ~3);
+    float* wp = dls + 4 + sh + j0;                                        // slot 0 of copy 0 (copy c: + c*DC - c), slot 1 follows
+    float* wmp = lane == 63 ? wm + wv : dump + lane;
+
+    for (int k = tid; k < 2 * BUF + 2 * NWM; k += NPW * 64) dls[k] = -INFINITY;
+    __syncthreads();
+
+    auto produce = [&](const f32x2 dn, const int WB) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            wp[WB * BUF + c * DC - c] = dn.x;
+            wp[WB * BUF + c * DC - c + 1] = dn.y;
+        }
+        const float inc = wave_scan_max(fmaxf((NXL > 0 && x0) ? -INFINITY : dn.x, (NXL > 0 && x1) ? -INFINITY : dn.y));
+        wmp[WB * NWM] = inc;
+    };
+
+    // ---------------- frame 0
+    {
+        const float* __restrict__ lpi = reinterpret_cast<const float*>(a.image + a.off_logpi);
+        f32x2 d0 = f32x2{-INFINITY, -INFINITY};
+        if (v0) { d0.x = lpi[j0] + load_e<ET>(E + j0); hist[j0] = d0.x; }
+        if (v1) { d0.y = lpi[j1] + load_e<ET>(E + j1); hist[j1] = d0.y; }
+        produce(d0, 0);
+    }
+    f32x2 er[PF];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+        const ET* __restrict__ row = E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S;
+        er[k] = f32x2{load_e<ET>(row + jl0), load_e<ET>(row + jl1)};
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w) asm volatile("" ::"v"(aw0[w]), "v"(aw1[w]));
+#pragma unroll
+    for (int k = 0; k < NXL; ++k) asm volatile("" ::"v"(xa[k]));
+    asm volatile("" ::"v"(cj));
+    __syncthreads();
+
+    auto frame = [&](const int t, f32x2& e_slot, const int RB) {
+        const int WB = RB ^ 1;
+        const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
+        float xd[NXL > 0 ? NXL : 1];
+#pragma unroll
+        for (int k = 0; k < NXL; ++k) xd[k] = dls[4 + sh + RB * BUF + xcol[k]];
+        f32x4 wq[NWM / 4];
+#pragma unroll
+        for (int q = 0; q < NWM / 4; ++q) wq[q] = reinterpret_cast<const f32x4*>(wm + RB * NWM)[q];
+        f32x4 dw[W / 4];
+#pragma unroll
+        for (int q = 0; q < W / 4; ++q) dw[q] = win[q];
+        float m0 = -INFINITY, m1 = -INFINITY, n0 = -INFINITY, n1 = -INFINITY;   // two max3 chains per target
+#pragma unroll
+        for (int w = 0; w + 3 < W; w += 4) {
+            const f32x4 d = dw[w / 4];
+            const f32x2 a0 = f32x2{d.x, d.y} + f32x2{aw0[w + 0], aw0[w + 1]};
+            const f32x2 a1 = f32x2{d.z, d.w} + f32x2{aw0[w + 2], aw0[w + 3]};
+            const f32x2 b0 = f32x2{d.x, d.y} + f32x2{aw1[w + 0], aw1[w + 1]};
+            const f32x2 b1 = f32x2{d.z, d.w} + f32x2{aw1[w + 2], aw1[w + 3]};
+            m0 = fmaxf(fmaxf(m0, a0.x), a0.y);
+            n0 = fmaxf(fmaxf(n0, a1.x), a1.y);
+            m1 = fmaxf(fmaxf(m1, b0.x), b0.y);
+            n1 = fmaxf(fmaxf(n1, b1.x), b1.y);
+        }
+        // M = max of delta_{t-1} over the non-extra sources; slots >= NPW of wq hold -inf
+        float M = fmaxf(fmaxf(wq[0].x, wq[0].y), fmaxf(wq[0].z, wq[0].w));
+#pragma unroll
+        for (int q = 1; q < NWM / 4; ++q) M = fmaxf(fmaxf(fmaxf(M, wq[q].x), wq[q].y), fmaxf(wq[q].z, wq[q].w));
+        const f32x2 fl = f32x2{M, M} + cj;
+        m0 = fmaxf(m0, fl.x);
+        m1 = fmaxf(m1, fl.y);
+#pragma unroll
+        for (int k = 0; k < NXL; ++k) {
+            const f32x2 xv = f32x2{xd[k], xd[k]} + xa[k];
+            n0 = fmaxf(n0, xv.x);
+            n1 = fmaxf(n1, xv.y);
+        }
+        const f32x2 dn = f32x2{fmaxf(m0, n0), fmaxf(m1, n1)} + e_slot;
+        produce(dn, WB);
+        asm volatile("" ::: "memory");   // history stores / prefetch behind the wave-max publication
+        const int tn = t + PF < Tb ? t + PF : Tb - 1;
+        float* __restrict__ hb = hist + (size_t)(t - 1) * SD;
+        const ET* __restrict__ erow = E + (size_t)tn * S;
+        hb[hoff0] = fm0 ? M : dn.x;
+        hb[hoff1] = fm1 ? M : dn.y;
+        e_slot = f32x2{load_e<ET>(erow + jl0), load_e<ET>(erow + jl1)};
+        __syncthreads();
+    };
+#ifdef VIT_TIMING_HOOKS
+    const bool probe = (a.debug & 48) != 0;
+#else
+    constexpr bool probe = false;   // cycle probe: VIT_TIMING_HOOKS builds only; it writes the per-song scratch, never an output
+#endif
+    const unsigned long long clk0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
+    const unsigned long long rt0 = probe ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    int t = 1;
+    for (; t + PF - 1 < Tb; t += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) frame(t + k, er[k], k & 1);
+    }
+#pragma unroll
+    for (int k = 0; k < PF - 1; ++k)
+        if (t + k < Tb) frame(t + k, er[k], k & 1);
+
+    // terminal state: lowest-index argmax of delta_{T-1}; a lane holds two adjacent states
+    {
+        const int fb = (Tb - 1) & 1;
+        const float* fin = dls + 4 + sh + fb * BUF;
+        VI x = vi_identity();
+        if (v0) x = VI{fin[j0], j0};
+        if (v1) x = op_fwd(x, VI{fin[j1], j1});
+        x = wave_scan<false>(x);
+        if (lane == 63) tot[wv] = x;
+        __syncthreads();
+        if (tid == 0) {
+            VI acc = vi_identity();
+            for (int b = 0; b < NPW; ++b) acc = op_fwd(acc, tot[b]);
+            if (acc.i == kBig) acc.i = 0;
+            a.last_state[song] = acc.i;
+            if (a.loglik) a.loglik[song] = acc.v;
+        }
+    }
+    if (probe && tid == 0) {  // timing experiments only: cycles (16) or 100 MHz ticks (32) per frame -> scratch slot 63
+        const unsigned long long d = (a.debug & 16) ? __builtin_amdgcn_s_memtime() - clk0 : __builtin_amdgcn_s_memrealtime() - rt0;
+        a.fmax[(size_t)song * 64 + 63] = (float)d / (float)(Tb > 1 ? Tb - 1 : 1);
+    }
+}
+
+// DPP self-test: mode 0/1 = (value, index) first-max scan fwd/rev; mode 2 = value-only prefix max;
+// mode 3 = wave_shift_up of the prefix max; mode 4 = wave_max_all.
+__global__ void scan_selftest_kernel(const float* __restrict__ vals, int mode, float* __restrict__ out_v,
+                                     int32_t* __restrict__ out_i) {
+    const int j = threadIdx.x + blockIdx.x * blockDim.x;
+    VI x{vals[j], (int)threadIdx.x};
+    if (mode == 0) x = wave_scan<false>(x);
+    else if (mode == 1) x = wave_scan<true>(x);
+    else if (mode == 2) x.v = wave_scan_max(x.v);
+    else if (mode == 3) x.v = wave_shift_up(wave_scan_max(x.v), -INFINITY);
+    else x.v = wave_max_all(x.v);
+    out_v[j] = x.v;
+    out_i[j] = x.i;
+}
+
+// ---------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------
+// floor-max forms (plan.floor_ok; idle slot S stores the frame maximum: needs S < 64 * NWT)
+template <int W, int NWT, typename ET>
+static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
+    constexpr int NP = NWT * 64;
+    constexpr int PF = W <= 32 ? 12 : 4;   // emission rows in flight: a row is requested PF frames (0.34 us each) before its use; under the overlapped
+                                            // back-trace 4 left ~2 % on the table (B = 128: 4 -> 10.35, 8 -> 10.20, 12 -> 10.12, 16 -> 10.14 ms per forward pass)
+    // Up to two songs per CU the one-target-per-lane kernel is (slightly) faster; beyond that the two-targets-per-lane
+    // kernel wins because it moves half the window bytes through LDS (B = 512: 14.5 vs 15.5 ms).
+    // FwdArgs::fwd_form 1 / 2 force one or the other.
+    if constexpr (W <= 32 && NWT <= 8) {   // (at twelve waves, S = 722, the one-target kernel measured faster at every batch size)
+        const bool pair = a.pair_ok && ((a.B > 256 && a.fwd_form != 1) || a.fwd_form == 2);
+        if (pair) {
+            constexpr int NPW = (NWT + 1) / 2;
+            constexpr int PFP = 4;             // (two workgroups share a CU here and cover each other's waits: 12 rows in flight measured 9 % slower)
+            constexpr int NWMP = (NPW + 3) / 4 * 4;
+            const size_t ldsp = sizeof(float) * (8 * (NPW * 128 + 16) + 2 * NWMP + 64 + NWMP) + sizeof(VI) * 16;
+            if (W == 32 && a.n_extras == 1)
+                hipLaunchKernelGGL((banded_floor_pair_forward_kernel<W, NPW, (W == 32 ? 1 : -1), PFP, ET>), dim3((int)a.B), dim3(NPW * 64), ldsp, st, a);
+            else
+                hipLaunchKernelGGL((banded_floor_pair_forward_kernel<W, NPW, -1, PFP, ET>), dim3((int)a.B), dim3(NPW * 64), ldsp, st, a);
+            return hipGetLastError();
+        }
+    }
+    constexpr int NWM = (NWT + 3) / 4 * 4;
+    const size_t ldsf = sizeof(float) * (8 * (NP + 16) + 2 * NWM + 64 + NWM) + sizeof(VI) * 16 +
+                        ((W == 128 && NWT > 8) ? sizeof(f32x4) * 8 * NP : 0);
+    if ((W == 32 || W >= 84) && a.n_extras == 1)   // the reference's matrices: band + unvoiced column (compile-time extras count)
+        hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, ((W == 32 || W >= 84) ? 1 : -1), PF, ET>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
+    else
+        hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, -1, PF, ET>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
+    return hipGetLastError();
+}
+
+// general (scan) form
+template <int W, int NWT, typename ET>
+static hipError_t launch_scan_t(const FwdArgs& a, hipStream_t st) {
+    constexpr int NP = NWT * 64;
+    const size_t lds = sizeof(float) * (4 * (NP + 16) + 2 * (NP + 1) + kMaxDenseRows) + sizeof(VI) * 16;
+    // NWT + 2 waves put exactly two on each SIMD at S = 361 and let two workgroups share a CU.  Only a
+    // plan with dense rows, run at one workgroup per CU, gets a separate wave for them (it would
+    // otherwise lengthen the suffix wave, the critical one).
+    if (a.n_dense > 0 && a.B <= 256)
+        hipLaunchKernelGGL((banded_forward_kernel<W, NWT, true, false, -1, ET>), dim3((int)a.B), dim3((NWT + 3) * 64), lds, st, a);
+#ifdef VIT_TIMING_HOOKS
+    else if (a.debug)
+        hipLaunchKernelGGL((banded_forward_kernel<W, NWT, false, true, -1, ET>), dim3((int)a.B), dim3((NWT + 2) * 64), lds, st, a);
+#endif
+    else if (W == 32 && a.n_dense == 0 && a.n_extras == 1)   // the reference's matrices: band + unvoiced column
+        hipLaunchKernelGGL((banded_forward_kernel<W, NWT, false, false, (W == 32 ? 1 : -1), ET>), dim3((int)a.B), dim3((NWT + 2) * 64), lds, st, a);
+    else if (W == 32 && a.n_dense == 0 && a.n_extras == 0)
+        hipLaunchKernelGGL((banded_forward_kernel<W, NWT, false, false, (W == 32 ? 0 : -1), ET>), dim3((int)a.B), dim3((NWT + 2) * 64), lds, st, a);
+    else
+        hipLaunchKernelGGL((banded_forward_kernel<W, NWT, false, false, -1, ET>), dim3((int)a.B), dim3((NWT + 2) * 64), lds, st, a);
+    return hipGetLastError();
+}
+
+template <int W, int NWT, typename ET>
+static hipError_t launch_banded_t(const FwdArgs& a, hipStream_t st) {
+    // fwd_form 3 forces the general (scan) kernel; so do the ablation bits of a VIT_TIMING_HOOKS build (48 = cycle probes
+    // exist in the floor kernels as well)
+    const bool floor_ok = a.floor_ok && a.S < NWT * 64 && a.fwd_form != 3 && !(a.debug & ~48);
+    if constexpr (floor_form_instantiated(W, NWT)) {
+        if (floor_ok) return launch_floor_t<W, NWT, ET>(a, st);
+    }
+    if constexpr (scan_form_instantiated(W, NWT)) return launch_scan_t<W, NWT, ET>(a, st);
+    return hipErrorInvalidConfiguration;
+}
+
+template <int W, typename ET>
+static hipError_t launch_banded_w(const FwdArgs& a, hipStream_t st) {
+    switch (banded_waves_for(a.S)) {
+        case 2: return launch_banded_t<W, 2, ET>(a, st);
+        case 4: return launch_banded_t<W, 4, ET>(a, st);
+        case 6: return launch_banded_t<W, 6, ET>(a, st);
+        case 8: return launch_banded_t<W, 8, ET>(a, st);
+        case 12: return launch_banded_t<W, 12, ET>(a, st);
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+
+template <typename ET>
+static hipError_t launch_banded_e(const FwdArgs& a, hipStream_t st) {
+    static_assert(sizeof(kBandedWidths) / sizeof(int) == 6, "one case per instantiated window width");
+    switch (a.W) {
+        case 16: return launch_banded_w<16, ET>(a, st);
+        case 32: return launch_banded_w<32, ET>(a, st);
+        case 64: return launch_banded_w<64, ET>(a, st);
+        case 84: return launch_banded_w<84, ET>(a, st);
+        case 96: return launch_banded_w<96, ET>(a, st);
+        case 128: return launch_banded_w<128, ET>(a, st);
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+
+hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st) {
+    return f16 ? launch_banded_e<__half>(a, st) : launch_banded_e<float>(a, st);
+}
+
+hipError_t launch_scan_selftest(const float* vals, int n_waves, int mode, float* out_v, int32_t* out_i,
+                                hipStream_t st) {
+    hipLaunchKernelGGL(scan_selftest_kernel, dim3(n_waves), dim3(64), 0, st, vals, mode, out_v, out_i);
+    return hipGetLastError();
+}
+
+}  // namespace vit

@@ -26,7 +26,7 @@ struct Tuning {
     int dense_songs = 0;       // songs per workgroup of the dense kernel (0 = by batch size)
     int dense_one_thread = 0;  // 1: one thread per target in the dense kernel even where two fit
     int dense_form = 0;        // 0: matrix-resident dense kernel where it applies (64 < S <= 368) | 1: always the streaming kernel
-    int step_form = 0;         // step-structured kernel: 0 four targets per lane, split | 1 one | 2 never (plain dense kernel) | 3 four, one wave
+    int step_form = 0;         // step-structured kernel, four targets per lane: 0 bands split over two waves | 3 one wave
     int bt_chunks = 0;         // time-parallel back-trace: chunks per song (0 = auto)
     int bt_warm = -1;          //                            warm-up frames (-1 = default)
     int win_shift = -1;        // LDS window shift of the floor kernels (-1 = from the plan)
@@ -430,8 +430,7 @@ int vit_forward(const vit_plan* plan, const void* logE, int emis_dtype, int64_t 
         e = vit::launch_wave(a, emis_dtype == VIT_F16, (hipStream_t)stream);
     } else if (family == 2) {
         e = vit::launch_banded(a, emis_dtype == VIT_F16, (hipStream_t)stream);
-    } else if (algo == VIT_ALGO_AUTO && a.step_ok && vit::step_kernel_instantiated(a.S, a.step_bw, a.step_kb) &&
-               tn.step_form != 2) {
+    } else if (algo == VIT_ALGO_AUTO && a.step_ok && vit::step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) {
         // dense matrix with step structure (Durrieu): VIT_ALGO_DENSE still means the plain dense kernel
         e = vit::launch_step(a, emis_dtype == VIT_F16, (hipStream_t)stream);
     } else {

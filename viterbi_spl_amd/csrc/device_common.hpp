@@ -1,0 +1,163 @@
+// device_common.hpp -- device helpers shared by the gfx950 (MI355X) kernel files of the float32 log-domain Viterbi decoder.
+//
+// Semantics (reference: imm/tf_viterbi.py:91-107, tonet/for_paper.py:1855-1868):
+//   delta_0[j]  = fl32(log_pi[j] + logE[0][j])
+//   m_j         = max_i fl32(delta_{t-1}[i] + logA_T[j][i]);  psi_t[j] = LOWEST i attaining it
+//   delta_t[j]  = fl32(m_j + logE[t][j])
+//   s_{T-1}     = lowest argmax_j delta_{T-1}[j];  s_t = psi_{t+1}[s_{t+1}]
+// Only add / compare / select (built with -ffp-contract=off): bit-identical to the reference's
+// NumPy float32 loop.
+//
+// "Lazy back-pointers": gfx950 retires one wave64 VALU instruction per 4 cycles per SIMD, and
+// tracking the argmax index of every (frame, state) costs more instructions than the max itself,
+// while the back-trace consumes ONE back-pointer per frame.  So
+//   * the forward kernels are value-only (packed adds + max3) and store the delta row of every
+//     frame (the reference's T1, tonet/for_paper.py:1852) instead of the back-pointer rows (T2);
+//   * the back-trace recomputes psi_{t+1}[s_{t+1}] exactly -- the same fl32 sums, first index
+//     attaining the max -- only for the state on the path.
+// No MFMA: the recurrence is max-plus, not an add-contract.
+#pragma once
+#include <hip/hip_fp16.h>
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "kernels.hpp"
+
+namespace vit {
+
+inline constexpr int kBig = 0x7fffffff;           // index sentinel: "no state yet" (loses every first-max tie)
+inline constexpr size_t kLdsBytes = 160 * 1024;   // LDS of one CU (gfx950): the most one workgroup can allocate
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// element-aligned vector views: a lane's columns start on a 4-byte (f32) / 2-byte (f16) boundary only
+typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
+typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));
+typedef int i32x4_u __attribute__((ext_vector_type(4), aligned(4)));
+typedef _Float16 f16x2_u __attribute__((ext_vector_type(2), aligned(2)));
+typedef _Float16 f16x4_u __attribute__((ext_vector_type(4), aligned(2)));
+
+// frames of song `song`: lengths[song] clamped to [1, T] (T when there is no lengths tensor)
+__device__ __forceinline__ int song_length(const int64_t* lengths, int song, int T) {
+    if (!lengths) return T;
+    long long v = lengths[song];
+    v = v < 1 ? 1 : v;
+    return v > T ? T : (int)v;
+}
+// min(max(x, 0), hi): one v_med3_i32
+__device__ __forceinline__ int clamp_med3(int x, int hi) {
+    int r;
+    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(r) : "v"(x), "s"(hi));
+    return r;
+}
+
+template <typename ET>
+__device__ __forceinline__ float load_e(const ET* p);
+template <>
+__device__ __forceinline__ float load_e<float>(const float* p) { return *p; }
+template <>
+__device__ __forceinline__ float load_e<__half>(const __half* p) { return __half2float(*p); }
+
+// ---- value-only wave primitives
+// Inclusive prefix max over lanes 0..lane: six v_max_f32 with a DPP source operand
+// (row_shr:1/2/4/8, row_bcast:15 on rows 1,3, row_bcast:31 on rows 2,3).  A lane whose DPP source
+// is invalid or whose row is masked is not written and keeps its own value.  The s_nop 1 pairs are
+// the two wait states a DPP read of a just-written VGPR needs.
+__device__ __forceinline__ float wave_scan_max(float x) {
+    asm volatile(
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 1\n\t"
+        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "s_nop 1"
+        : "+v"(x));
+    return x;
+}
+// max over all 64 lanes, returned in every lane (wave-uniform)
+__device__ __forceinline__ float wave_max_all(float x) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_scan_max(x)), 63));
+}
+// lane l <- x[l-1], lane 0 <- fill   (wave_shr:1)
+__device__ __forceinline__ float wave_shift_up(float x, float fill) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(x), 0x138, 0xf, 0xf, false));
+}
+// lane l <- x[l+1], lane 63 <- fill   (wave_shl:1)
+__device__ __forceinline__ float wave_shift_down(float x, float fill) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(x), 0x130, 0xf, 0xf, false));
+}
+// The same shifts with bound_ctrl: the lane without a source reads 0 and no fill value is moved in (one v_mov fewer per
+// shift).  For callers to whom that lane's value does not matter.
+__device__ __forceinline__ float dpp_shr1(float x) {   // lane l <- x[l-1]
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float dpp_shl1(float x) {   // lane l <- x[l+1]
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x130, 0xf, 0xf, true));
+}
+
+// ---- (value, index) first-max wave primitives
+struct VI {
+    float v;
+    int i;
+};
+
+__device__ __forceinline__ VI vi_identity() { return VI{-INFINITY, kBig}; }
+// first-max: `later` (higher index) replaces `earlier` only if strictly greater
+__device__ __forceinline__ VI op_fwd(VI earlier, VI later) { return later.v > earlier.v ? later : earlier; }
+// pieces visited in DESCENDING index order: the next (lower-index) piece wins ties
+__device__ __forceinline__ VI op_rev(VI acc, VI next) { return next.v >= acc.v ? next : acc; }
+
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ VI dpp_fetch(VI x) {
+    VI r;
+    r.v = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(-INFINITY), __float_as_int(x.v), CTRL,
+                                                     ROW_MASK, 0xf, false));
+    r.i = __builtin_amdgcn_update_dpp(kBig, x.i, CTRL, ROW_MASK, 0xf, false);
+    return r;
+}
+
+// Inclusive wave64 scan with the ordered first-max operator (value, index).
+// DPP: row_shr:1/2/4/8 inside each row of 16, then row_bcast:15 (rows 1,3), row_bcast:31 (rows 2,3).
+template <bool REV>
+__device__ __forceinline__ VI wave_scan(VI x) {
+#define VIT_SCAN_STEP(CTRL, MASK)                        \
+    {                                                    \
+        VI s = dpp_fetch<CTRL, MASK>(x);                 \
+        x = REV ? op_rev(s, x) : op_fwd(s, x);           \
+    }
+    VIT_SCAN_STEP(0x111, 0xf)
+    VIT_SCAN_STEP(0x112, 0xf)
+    VIT_SCAN_STEP(0x114, 0xf)
+    VIT_SCAN_STEP(0x118, 0xf)
+    VIT_SCAN_STEP(0x142, 0xa)
+    VIT_SCAN_STEP(0x143, 0xc)
+#undef VIT_SCAN_STEP
+    return x;
+}
+
+// Workgroup-wide lowest-index argmax of delta (terminal state); every thread of the workgroup calls.
+__device__ __forceinline__ void terminal_argmax(float dj, int j, bool valid, VI* tot, int nw, int32_t* last_state,
+                                                float* loglik, int song) {
+    VI x{valid ? dj : -INFINITY, valid ? j : kBig};
+    x = wave_scan<false>(x);
+    if ((threadIdx.x & 63) == 63) tot[threadIdx.x >> 6] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        VI acc = vi_identity();
+        for (int b = 0; b < nw; ++b) acc = op_fwd(acc, tot[b]);
+        if (acc.i == kBig) acc.i = 0;
+        last_state[song] = acc.i;
+        if (loglik) loglik[song] = acc.v;
+    }
+}
+
+}  // namespace vit

@@ -11,11 +11,7 @@
 // Parity: peak picking and the voicing decision are exact (compares; the voicing logit in float64 like
 // the reference); exp/log/sum are the GPU's, so probabilities agree to a few ulp, not bit for bit
 // (tests compare with a tolerance and require the structural zeros -> log(tiny) to be exact).
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "kernels.hpp"
+#include "device_common.hpp"
 
 namespace vit {
 
@@ -215,53 +211,26 @@ __global__ void __launch_bounds__(kObsWaves * 64) observation_kernel(const float
 // lane (U <= 64 NPL: the 320-, 360- and 721-bin grids and what lies between); other geometries keep the LDS form.
 namespace {
 
-typedef float ob_f4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float ob_f2u __attribute__((ext_vector_type(2), aligned(4)));
-
 // a lane's NPL consecutive floats as 16- / 8- / 4-byte pieces at 4-byte alignment (coalesced across the wave)
 template <int NPL>
 __device__ __forceinline__ void ob_load(const float* __restrict__ p, float (&v)[NPL]) {
     int k = 0;
 #pragma unroll
-    for (; k + 3 < NPL; k += 4) { const ob_f4u t = *reinterpret_cast<const ob_f4u*>(p + k); v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w; }
+    for (; k + 3 < NPL; k += 4) { const f32x4_u t = *reinterpret_cast<const f32x4_u*>(p + k); v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w; }
 #pragma unroll
-    for (; k + 1 < NPL; k += 2) { const ob_f2u t = *reinterpret_cast<const ob_f2u*>(p + k); v[k] = t.x; v[k + 1] = t.y; }
+    for (; k + 1 < NPL; k += 2) { const f32x2_u t = *reinterpret_cast<const f32x2_u*>(p + k); v[k] = t.x; v[k + 1] = t.y; }
     if (k < NPL) v[k] = p[k];
 }
 template <int NPL>
 __device__ __forceinline__ void ob_store(float* __restrict__ p, const float (&v)[NPL]) {
     int k = 0;
 #pragma unroll
-    for (; k + 3 < NPL; k += 4) { ob_f4u t; t.x = v[k]; t.y = v[k + 1]; t.z = v[k + 2]; t.w = v[k + 3]; *reinterpret_cast<ob_f4u*>(p + k) = t; }
+    for (; k + 3 < NPL; k += 4) { f32x4_u t; t.x = v[k]; t.y = v[k + 1]; t.z = v[k + 2]; t.w = v[k + 3]; *reinterpret_cast<f32x4_u*>(p + k) = t; }
 #pragma unroll
-    for (; k + 1 < NPL; k += 2) { ob_f2u t; t.x = v[k]; t.y = v[k + 1]; *reinterpret_cast<ob_f2u*>(p + k) = t; }
+    for (; k + 1 < NPL; k += 2) { f32x2_u t; t.x = v[k]; t.y = v[k + 1]; *reinterpret_cast<f32x2_u*>(p + k) = t; }
     if (k < NPL) p[k] = v[k];
 }
 
-__device__ __forceinline__ float ob_shr1(float x) {   // lane l <- x[l-1]; lane 0 (no source) gets -inf: the bins in front of the row
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(-INFINITY), __float_as_int(x), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float ob_shl1(float x) {   // lane l <- x[l+1]; lane 63 gets -inf
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(-INFINITY), __float_as_int(x), 0x130, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float ob_wave_max(float x) {
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(x));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
 __device__ __forceinline__ float ob_wave_sum(float x) {   // inclusive scan by rows, lane 63 holds the total
     asm volatile(
         "s_nop 1\n\t"
@@ -368,9 +337,9 @@ __global__ void __launch_bounds__(256) observation_reg_kernel(const float* __res
 #pragma unroll
                 for (int k = 0; k < NPL; ++k) {
                     const int dl = h * NPL - k;               // sl[k] after h shifts = bin NPL*(lane-h) + k = own start - dl
-                    if (dl <= SPW) { sl[k] = ob_shr1(sl[k]); a[SPW - dl] = sl[k]; }      // (a slot that is out of reach at h stays out of reach)
+                    if (dl <= SPW) { sl[k] = wave_shift_up(sl[k], -INFINITY); a[SPW - dl] = sl[k]; }      // (a slot that is out of reach at h stays out of reach)
                     const int dr = (h - 1) * NPL + k;         // sr[k] after h shifts = bin NPL*(lane+h) + k = own end + 1 + dr
-                    if (dr < SPW) { sr[k] = ob_shl1(sr[k]); a[SPW + NPL + dr] = sr[k]; }
+                    if (dr < SPW) { sr[k] = wave_shift_down(sr[k], -INFINITY); a[SPW + NPL + dr] = sr[k]; }
                 }
             }
         }
@@ -389,7 +358,7 @@ __global__ void __launch_bounds__(256) observation_reg_kernel(const float* __res
             lmax = pk[k] ? fmaxf(lmax, c) : lmax;
         }
         const float x0 = MODE == 1 ? x0f : (MODE == 2 ? (float)threshold : -INFINITY);     // the unvoiced logit (always in the peak set)
-        float g = ob_wave_max(lmax);
+        float g = wave_max_all(lmax);
         const bool any_peak = g > -INFINITY;
         if (MODE >= 1) g = fmaxf(g, x0);
         float ex[NPL];
@@ -565,6 +534,25 @@ hipError_t launch_voicing_notes(const int32_t* states, int64_t n, int32_t n_bins
     int64_t blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(voicing_notes_kernel, dim3((int)blocks), dim3(256), 0, st, states, n, n_bins, note_range, voiced, bins, notes, notes_v);
+    return hipGetLastError();
+}
+
+// voiced = state < n_bins; bins = min(state, n_bins-1)  (tonet/for_paper.py:1828-1829)
+__global__ void voicing_map_kernel(const int32_t* __restrict__ states, int64_t n, int32_t n_bins,
+                                   uint8_t* __restrict__ voiced, int32_t* __restrict__ bins) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t s = states[i];
+        voiced[i] = (s >= 0 && s < n_bins) ? 1 : 0;
+        bins[i] = s < 0 ? -1 : (s < n_bins - 1 ? s : n_bins - 1);
+    }
+}
+
+hipError_t launch_voicing_map(const int32_t* states, int64_t n, int32_t n_bins, uint8_t* voiced, int32_t* bins,
+                              hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(voicing_map_kernel, dim3((int)blocks), dim3(256), 0, st, states, n, n_bins, voiced, bins);
     return hipGetLastError();
 }
 

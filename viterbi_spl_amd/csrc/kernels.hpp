@@ -1,4 +1,5 @@
-// kernels.hpp -- launch interface between the C ABI (capi.hip) and kernels.hip.
+// kernels.hpp -- launch interface between the C ABI (capi.hip) and the kernel files (dense, step, banded, wave, emission,
+// backtrace_rows / _sparse / _half / _lane .hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -49,11 +50,11 @@ struct FwdArgs {
     int fwd_form;           // banded forward form: 0 by batch size | 1 one target per lane | 2 two targets per lane | 3 scan
     int dense_kt1;          // dense kernel: one thread per target even where two fit
     int dense_form;         // dense kernel: 0 matrix-resident form where it applies | 1 always the streaming form
-    int step_form;          // step kernel: 1 = one target per lane
+    int step_form;          // step kernel: 3 = four targets per lane in one wave (step4_forward_kernel)
     size_t off_logpi, off_A4, off_lo, off_kind, off_tabA, off_extraA, off_denseA, off_rowc, off_lo2, off_tabP;
     int pair_ok;            // the plan proved pair windows: use the two-targets-per-lane kernel
     int floor_ok;           // the plan proved the one-maximum form (banded_floor_forward_kernel)
-    int step_ok, step_bw, step_kb;   // step structure (step_forward_kernel)
+    int step_ok, step_bw, step_kb;   // step structure (step.hip)
     float step_cn;          // logA_T[j][S-1] for every voiced target j
     size_t off_stepC, off_Arow;
     int win_shift2;         // the same for the pair windows of banded_floor_pair_forward_kernel

@@ -17,8 +17,6 @@ static inline uint32_t f2u(float f) {
 
 static inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
-static const int kWidths[] = {16, 32, 64, 84, 96, 128};  // window widths the banded kernels are instantiated for
-
 BandedPlan analyze_banded(const float* A, int S) {
     BandedPlan bp;
     bp.S = S;
@@ -82,7 +80,7 @@ BandedPlan analyze_banded(const float* A, int S) {
     // 4. evaluated window width: the narrowest instantiated width that leaves at most kMaxDenseRows rows outside
     //    (those become "dense rows": a full max over every source) and still beats the dense kernel (2W <= S)
     int W = 0;
-    for (int w : kWidths) {
+    for (int w : kBandedWidths) {
         int outliers = 0;
         for (int j = 0; j < S; ++j) outliers += (hi[j] - lo[j] + 1 > w);
         if (outliers <= kMaxDenseRows && w <= S && 2 * w <= S) { W = w; break; }

@@ -23,7 +23,15 @@ namespace vit {
 
 constexpr int kMaxExtras = 4;
 constexpr int kMaxDenseRows = 4;
-constexpr int kMaxWindow = 128;  // widest window the banded kernels are instantiated for (jdc: d_max 40 -> 82, imm: 56 -> 114)
+// Window widths the banded kernels are instantiated for (jdc: d_max 40 -> 82, imm: 56 -> 114), narrowest first: the plan picks
+// from these, and launch_banded_e (banded.hip) and launch_backtrace_lane (backtrace_lane.hip) have one case per entry (a
+// static_assert next to each counts them).
+inline constexpr int kBandedWidths[] = {16, 32, 64, 84, 96, 128};
+constexpr bool banded_width_instantiated(int W) {
+    for (int w : kBandedWidths)
+        if (w == W) return true;
+    return false;
+}
 
 struct BandedPlan {
     bool ok = false;          // the decomposition was proven for this matrix

@@ -1,6 +1,6 @@
 // wave.hip -- "wave" form of the banded forward pass: ONE SONG PER WAVEFRONT (gfx950).
 //
-// The workgroup kernels of kernels.hip advance a song one frame per LDS round trip and barrier: ~830 cycles per
+// The workgroup kernels of banded.hip advance a song one frame per LDS round trip and barrier: ~830 cycles per
 // frame whatever the arithmetic, which is what a small batch needs (latency) and what a large batch does not
 // (throughput: four songs per CU still leave the VALU ~60 % idle).  Here a song never leaves one wavefront:
 //
@@ -23,63 +23,13 @@
 // 64*NPL floats; layout at the kernel below) and vit_forward records that layout for the back-trace kernels.
 // Measured (S = 361, fp32, T = 30000): 19.9 ms for 1024 songs, 35.7 ms for 2048 -- HBM-bound at 4.5-5 TB/s of real
 // traffic.
-#include <hip/hip_fp16.h>
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
 #include <type_traits>
 
-#include "kernels.hpp"
+#include "device_common.hpp"
 
 namespace vit {
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// element-aligned vector views: a lane's NPL columns start on a 4-byte (f32) / 2-byte (f16) boundary only
-typedef float f32x4_u __attribute__((ext_vector_type(4), aligned(4)));
-typedef float f32x2_u __attribute__((ext_vector_type(2), aligned(4)));
-typedef _Float16 f16x2_u __attribute__((ext_vector_type(2), aligned(2)));
-typedef _Float16 f16x4_u __attribute__((ext_vector_type(4), aligned(2)));
-
-constexpr int kBigI = 0x7fffffff;
-
-__device__ __forceinline__ int song_length_of(const int64_t* lengths, int song, int T) {
-    if (!lengths) return T;
-    long long v = lengths[song];
-    v = v < 1 ? 1 : v;
-    return v > T ? T : (int)v;
-}
-
-// Wave-wide shifts by one lane.  bound_ctrl: the lane without a source reads 0 -- any finite value would do: the
-// sources that lane stands for do not exist (state < 0 or >= S) and their window weights are -inf (plan.cpp), so the
-// candidate is -inf whatever the shift delivers.  (A fill value would cost a v_mov per shift.)
-__device__ __forceinline__ float dpp_shr1(float x) {   // lane l <- x[l-1]
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float dpp_shl1(float x) {   // lane l <- x[l+1]
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x130, 0xf, 0xf, true));
-}
-// max over the wave, wave-uniform result (six v_max_f32 with a DPP operand + v_readlane; see kernels.hip wave_scan_max)
-__device__ __forceinline__ float wave_max(float x) {
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_max_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(x));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
-
 
 template <int NPL, typename ET>
 struct RowIO;
@@ -95,7 +45,6 @@ struct RowIO<NPL, float> {
         for (; k + 1 < NPL; k += 2) { const f32x2_u v = *reinterpret_cast<const f32x2_u*>(p + k); e[k] = v.x; e[k + 1] = v.y; }
         if (k < NPL) e[k] = p[k];
     }
-    static __device__ __forceinline__ float load1(const float* __restrict__ p) { return *p; }
 };
 template <int NPL>
 struct RowIO<NPL, __half> {
@@ -108,7 +57,6 @@ struct RowIO<NPL, __half> {
         for (; k + 1 < NPL; k += 2) { const f16x2_u v = *reinterpret_cast<const f16x2_u*>(p + k); e[k] = (float)v.x; e[k + 1] = (float)v.y; }
         if (k < NPL) e[k] = (float)p[k];
     }
-    static __device__ __forceinline__ float load1(const __half* __restrict__ p) { return __half2float(*p); }
 };
 
 template <int NPL>
@@ -220,7 +168,7 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
     const long long off = PK ? a.offsets[song] : (long long)song * a.T;           // first emission row of the song in the tensor
     const int T = PK ? (int)(a.offsets[song + 1] - off) : a.T;                     // rows the song owns (packed: its length)
     const int t0 = HM == 6 ? a.t_begin : 0;                                    // first frame of this launch
-    const int Tl = PK ? T : song_length_of(a.lengths, song, T);
+    const int Tl = PK ? T : song_length(a.lengths, song, T);
     const int Tb = HM == 6 && a.t_end < Tl ? a.t_end : Tl;                     // one past the last frame of this launch
     if (Tb <= t0) continue;                                                    // (segments: the song ended before this one)
     const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)off * S;
@@ -281,7 +229,7 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
 #pragma unroll
         for (int k = 0; k < NPL; ++k) {
             const int j = j0 + k;
-            d[k] = j >= 0 ? lpi[j] + RowIO<NPL, ET>::load1(E + j) : -INFINITY;
+            d[k] = j >= 0 ? lpi[j] + load_e<ET>(E + j) : -INFINITY;
         }
     } else {
         const float* __restrict__ ir = a.init_rows + (size_t)song * a.init_stride + NPL * lane;
@@ -292,7 +240,7 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
         float loc = v[0];
 #pragma unroll
         for (int k = 1; k < NPL; ++k) loc = fmaxf(loc, v[k]);
-        return wave_max(loc);
+        return wave_max_all(loc);
     };
     float M = frame_max(d);
     float xd[NX > 0 ? NX : 1] = {};
@@ -310,7 +258,9 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
         for (int m = 0; m < NPM; ++m) asm volatile("" ::"v"(aw[k][m]));
 
     auto frame = [&](const int t, float (&e)[NPL], auto stored) {
-        // ---- neighbourhood: group g holds delta of lane l - H + g
+        // ---- neighbourhood: group g holds delta of lane l - H + g.  The bound_ctrl shifts deliver 0 to the lane without a
+        //      source -- any finite value would do: the sources that lane stands for do not exist (state < 0 or >= S) and
+        //      their window weights are -inf (plan.cpp), so the candidate is -inf whatever the shift delivers.
         float nb[NG][NPL];
 #pragma unroll
         for (int k = 0; k < NPL; ++k) nb[H][k] = d[k];
@@ -398,16 +348,16 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
     // ---------------- terminal state: lowest-index argmax of delta_{Tb-1} (not in a segment launch)
     if (HM != 6 || a.t_end >= T) {
         float bv = -INFINITY;
-        int bi = kBigI;
+        int bi = kBig;
 #pragma unroll
         for (int k = 0; k < NPL; ++k)
-            if (j0 + k >= 0 && (d[k] > bv || bi == kBigI)) { bv = d[k]; bi = j0 + k; }   // first state of the lane, then strictly greater
+            if (j0 + k >= 0 && (d[k] > bv || bi == kBig)) { bv = d[k]; bi = j0 + k; }   // first state of the lane, then strictly greater
         // lanes ascend with the state index: an ordered (value, index) scan keeps the first maximum
 #define VIT_WSTEP(CTRL, MASK)                                                                                      \
     {                                                                                                              \
         const float sv = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(-INFINITY), __float_as_int(bv), CTRL, MASK, 0xf, false)); \
-        const int si = __builtin_amdgcn_update_dpp(kBigI, bi, CTRL, MASK, 0xf, false);                               \
-        const bool keep_earlier = !(bv > sv);   /* kernels.hip op_fwd: the later piece wins only if strictly greater */ \
+        const int si = __builtin_amdgcn_update_dpp(kBig, bi, CTRL, MASK, 0xf, false);                               \
+        const bool keep_earlier = !(bv > sv);   /* op_fwd: the later piece wins only if strictly greater */ \
         bv = keep_earlier ? sv : bv;                                                                               \
         bi = keep_earlier ? si : bi;                                                                               \
     }
@@ -419,7 +369,7 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
         VIT_WSTEP(0x143, 0xc)
 #undef VIT_WSTEP
         if (lane == 63) {
-            a.last_state[song] = bi == kBigI ? 0 : bi;
+            a.last_state[song] = bi == kBig ? 0 : bi;
             if (a.loglik) a.loglik[song] = bv;
         }
     }
@@ -504,7 +454,7 @@ __global__ void segment_prep_kernel(const int64_t* __restrict__ lengths, int64_t
                                     const int32_t* __restrict__ last, int64_t* __restrict__ seg_len, int32_t* __restrict__ seg_last) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int Tb = song_length_of(lengths, (int)b, T);
+    const int Tb = song_length(lengths, (int)b, T);
     if (Tb > e0) {                    // the song goes on behind this segment: its state at frame e0 is decided already
         seg_len[b] = e0 - s0 + 1;
         seg_last[b] = states[(size_t)b * T + e0];
