@@ -4,7 +4,8 @@
 The classes live in tonet/for_paper.py, whose module top imports TF / torch / librosa / medleydb;
 only the ast.FunctionDef nodes of the needed methods are compiled (with `np` in scope) and bound to
 a bare namespace object carrying the attributes their __init__ would set (for_paper.py:1691-1701,
-:1881-1887).  Outputs: tests/golden/obs_goldens.npz (seeds -> expected probabilities)."""
+:1881-1887).  Outputs: tests/golden/obs_goldens.npz (seeds -> expected probabilities); with --range,
+tests/golden/obs_range_goldens.npz (the range-edge frames of tests.common.range_edge_logits -> expected probabilities)."""
 import ast
 import os
 import sys
@@ -33,7 +34,7 @@ def extract(class_name, method_names, path=None):
     return ns
 
 
-from tests.common import logits_case  # noqa: E402  (shared with the tests)
+from tests.common import RANGE_SPANS, RANGE_TOPS, logits_case, range_edge_logits  # noqa: E402  (shared with the tests)
 
 
 def main():
@@ -85,5 +86,50 @@ def main():
     print("wrote obs_goldens.npz")
 
 
+# the range-edge cases: (name, n_bins, spw, tops); scaled / unscaled run dcnet's builder at voicing_threshold_prob 0.5 (unvoiced
+# logit 0) with the spans among the tops, so that the unvoiced logit is the far one
+RANGE_CASES = (("shaun", 360, 5, RANGE_TOPS), ("softmax", 360, 15, RANGE_TOPS),
+               ("scaled", 320, 5, RANGE_TOPS + RANGE_SPANS), ("unscaled", 320, 5, RANGE_TOPS + RANGE_SPANS))
+
+
+def range_main():
+    """Probabilities at the float32 range edge of exp (subnormal e^-d), from the reference's own builders."""
+    v = extract("Viterbi", ["expit", "find_peaks_all_at_once_np_fn", "observation_probs_fn"])
+    s = extract("SoftMaxViterbi", ["find_peaks_all_at_once_np_fn", "observation_probs_fn"])
+    d = extract("SoftMaxViterbi", ["find_peaks_all_at_once_np_fn", "observation_probs_fn"], "/root/reference/dcnet/softmax_viterbi.py")
+    prior = np.load(os.path.join(HERE, "params.npz"))["msnet321_pi"]
+    out = {"spans": np.asarray(RANGE_SPANS)}
+    for name, U, spw, tops in RANGE_CASES:
+        if name == "shaun":
+            self_v = types.SimpleNamespace(num_freq_bins=U, single_side_peak_width=spw, threshold=np.log(0.32 / (1. - 0.32)))
+            self_v.find_peaks_all_at_once_np_fn = lambda fl, _s=self_v: v["find_peaks_all_at_once_np_fn"](_s, fl)
+            v["Viterbi"] = types.SimpleNamespace(expit=v["expit"])
+            x = range_edge_logits(U, spw, tops)
+            ref = np.ascontiguousarray(v["observation_probs_fn"](self_v, x.copy()).T)
+            mine = np.ascontiguousarray(oo.shaun_observation_probs(x.copy(), 0.32, spw=spw).T)
+        elif name == "softmax":
+            self_s = types.SimpleNamespace(num_freq_bins=U, single_side_peak_width=spw)
+            self_s.find_peaks_all_at_once_np_fn = lambda lg, _s=self_s: s["find_peaks_all_at_once_np_fn"](_s, lg)
+            x = range_edge_logits(U, spw, tops, unvoiced_column=True)
+            ref = s["observation_probs_fn"](self_s, x.copy())
+            mine = oo.softmax_observation_probs(x.copy(), spw=spw)
+        else:
+            scaled = name == "scaled"
+            self_d = types.SimpleNamespace(num_freq_bins=U, single_side_peak_width=spw, scaled=scaled, ini_probs=prior,
+                                           voicing_threshold_prob_tf_var=types.SimpleNamespace(numpy=lambda: np.float32(0.5)))
+            self_d.find_peaks_all_at_once_np_fn = lambda lg, _s=self_d: d["find_peaks_all_at_once_np_fn"](_s, lg)
+            x = range_edge_logits(U, spw, tops)
+            ref = d["observation_probs_fn"](self_d, x.copy())
+            mine = oo.softmax_scaled_observation_probs(x.copy(), np.float32(0.5), prior, scaled=scaled, spw=spw)
+        assert ref.dtype == np.float32 and ref.shape == (len(x), U + 1)
+        assert ref.tobytes() == mine.tobytes(), f"{name}: restatement differs at the range edge"
+        sub = int(np.sum((ref > 0) & (ref < np.finfo(np.float32).tiny)))
+        out[f"{name}_args"] = np.asarray([U, spw] + list(tops))
+        out[f"{name}_probs"] = ref
+        print(f"range {name}: {ref.shape} ok; {sub} subnormal probabilities")
+    np.savez_compressed(os.path.join(HERE, "obs_range_goldens.npz"), **out)
+    print("wrote obs_range_goldens.npz")
+
+
 if __name__ == "__main__":
-    main()
+    range_main() if sys.argv[1:] == ["--range"] else main()

@@ -121,3 +121,26 @@ def test_c_oracle_matches_family_b_goldens_at_full_length():
     states, _ = vo.decode_c(logA_T, log_pi, logE)
     assert np.array_equal(states, gold["states_B"].astype(np.int32)) and np.array_equal(gold["states_B"], gold["states_C"])
     assert int(np.sum(states == 360)) == man["unvoiced_frames"]
+
+
+def test_observation_oracle_matches_reference_goldens_at_the_range_edge():
+    """The emission-builder restatements at the float32 range edge of exp (tests/golden/obs_range_goldens.npz: the reference's own
+    builders on tests.common.range_edge_logits): spans whose e^-d is subnormal stay subnormal, bit for bit."""
+    import os
+    from oracle import observation_oracle as oo
+    from tests.common import RANGE_SPANS, range_edge_logits
+    og = np.load(os.path.join(os.path.dirname(__file__), "golden", "obs_range_goldens.npz"))
+    assert tuple(og["spans"]) == RANGE_SPANS
+    prior = np.load(os.path.join(os.path.dirname(__file__), "golden", "params.npz"))["msnet321_pi"]
+    tiny = np.finfo(np.float32).tiny
+    for name in ("shaun", "softmax", "scaled", "unscaled"):
+        U, spw, *tops = (int(a) for a in og[f"{name}_args"])
+        if name == "shaun":
+            got = np.ascontiguousarray(oo.shaun_observation_probs(range_edge_logits(U, spw, tops), 0.32, spw=spw).T)
+        elif name == "softmax":
+            got = oo.softmax_observation_probs(range_edge_logits(U, spw, tops, unvoiced_column=True), spw=spw)
+        else:
+            got = oo.softmax_scaled_observation_probs(range_edge_logits(U, spw, tops), np.float32(0.5), prior, scaled=name == "scaled", spw=spw)
+        want = og[f"{name}_probs"]
+        assert got.tobytes() == want.tobytes(), name
+        assert np.any((want > 0) & (want < tiny)), name                  # the subnormal band is populated

@@ -205,8 +205,11 @@ __global__ void __launch_bounds__(kObsWaves * 64) observation_kernel(const float
 // wave-wide DPP shifts of whole registers (wave_shr:1 / wave_shl:1, chained for SPW > NPL; -inf beyond the row's ends), every
 // window maximum is a chain of v_max3_f32 over registers with compile-time indices, and the reflect padding is never built: what
 // it adds to the windows reduces to two rules at the left end (at the kernel).  exp / log run densely on the owner lanes with the
-// hardware's v_exp_f32 / v_log_f32 and a compensated range scaling (a few ulp) instead of through a compacted peak list, the
-// wave reductions are DPP; the soft-voicing sigmoid stays in float64 like the reference's.  No LDS, no barrier.
+// hardware's v_exp_f32 / v_log_f32 and a compensated argument split (a few ulp) instead of through a compacted peak list;
+// v_exp_f32 returns no subnormals, so a frame with a peak or unvoiced logit more than 80 nats below its top takes a scaled exp
+// (ob_exp_far) and true divisions (a ballot per frame, a wave-uniform branch) and keeps the subnormal probabilities the
+// reference's float32 np.exp and division give.  The wave reductions are DPP; the soft-voicing sigmoid stays in float64 like the
+// reference's.  No LDS, no barrier.
 // Instantiated for the reference's half-widths 5 ("shaun", dcnet's scaled likelihood) and 15 (softmax) and 5 / 6 / 8 / 12 bins per
 // lane (U <= 64 NPL: the 320-, 360- and 721-bin grids and what lies between); other geometries keep the LDS form.
 namespace {
@@ -256,6 +259,17 @@ __device__ __forceinline__ float ob_exp(float x) {
     const float lo = __builtin_fmaf(x, 1.44269502f, -hi);              // the product's rounding error, exactly
     const float e2 = __builtin_amdgcn_exp2f(hi);
     return __builtin_fmaf(e2, lo * 0.693147182f, e2);                   // (what float(log2 e) itself is off by adds |x| * 1.3e-8: < 1 ulp up to |x| = 8)
+}
+// e^x for any x: v_exp_f32 flushes results below 2^-126 (x < -87.34) to 0, where float32 has subnormals (down to e^-103.3) and the
+// reference's np.exp keeps them.  There the exponent is raised by 64 before the instruction and the result scaled by 2^-64 after it:
+// one rounding into the subnormal range, as a full expf does.  (e^-1000 is still 0.)
+__device__ __forceinline__ float ob_exp_far(float x) {
+    const float hi = x * 1.44269502f;
+    const float lo = __builtin_fmaf(x, 1.44269502f, -hi);
+    const bool sub = hi < -126.f;
+    const float e2 = __builtin_amdgcn_exp2f(sub ? hi + 64.f : hi);    // (hi + 64 is exact)
+    const float r = __builtin_fmaf(e2, lo * 0.693147182f, e2);
+    return sub ? r * 5.42101086e-20f : r;                               // 2^-64
 }
 // ln y through v_log_f32 (log2, 1 ulp), ln 2 = hi + lo
 __device__ __forceinline__ float ob_log(float y) {
@@ -362,11 +376,28 @@ __global__ void __launch_bounds__(256) observation_reg_kernel(const float* __res
         const bool any_peak = g > -INFINITY;
         if (MODE >= 1) g = fmaxf(g, x0);
         float ex[NPL];
-        float lsum = 0.f;
+        float lsum = 0.f, e0 = 0.f;
+        // (e^-1000 = 0: a select on the argument, no branch around the exp.)  A peak or unvoiced logit more than 80 nats below the top
+        // may have a subnormal e^x (below -87.3, which v_exp_f32 flushes) or e^x / tot (tot <= U + 1 <= e^6.65): such a frame (rare on
+        // real logits) takes ob_exp_far and true divisions, the branch is wave-uniform
+        bool far = MODE >= 1 && x0 - g < -80.f;
 #pragma unroll
-        for (int k = 0; k < NPL; ++k) {
-            ex[k] = ob_exp(pk[k] ? a[SPW + k] - g : -1000.f);          // (e^-1000 = 0: a select on the argument, no branch around the exp)
-            lsum += ex[k];
+        for (int k = 0; k < NPL; ++k) far = far || (pk[k] && a[SPW + k] - g < -80.f);
+        const bool far_frame = __ballot(far) != 0;
+        if (far_frame) {
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) {
+                ex[k] = ob_exp_far(pk[k] ? a[SPW + k] - g : -1000.f);
+                lsum += ex[k];
+            }
+            if (MODE >= 1) e0 = ob_exp_far(x0 - g);
+        } else {
+#pragma unroll
+            for (int k = 0; k < NPL; ++k) {
+                ex[k] = ob_exp(pk[k] ? a[SPW + k] - g : -1000.f);
+                lsum += ex[k];
+            }
+            if (MODE >= 1) e0 = ob_exp(x0 - g);
         }
         float tot = ob_wave_sum(lsum);
         float last;                                      // probability of the unvoiced state
@@ -392,17 +423,24 @@ __global__ void __launch_bounds__(256) observation_reg_kernel(const float* __res
                 v[k] = pk[k] ? lg : kLogTiny;
             }
         } else {
-            const float e0 = ob_exp(x0 - g);
             tot += e0;
-            const float tf = 1.f / tot;
-            last = any_peak ? e0 * tf : 1.f;
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) {
-                float pr = ex[k] * tf;
+            auto emit = [&](const int k, float pr) {
                 if (MODE == 2) pr *= rprior[k];
                 float lg = ob_log(pr + kTiny);
                 asm volatile("" : "+v"(lg));                          // (evaluate, then select: no branch per slot)
                 v[k] = pk[k] ? lg : kLogTiny;
+            };
+            if (far_frame) {
+                // e^x / tot may be subnormal, where a product with 1 / tot can round to a neighbouring multiple of 2^-149 (tens of %
+                // at a few units) and MODE 2's prior scaling lifts that error into the normal range: divide, as the reference does
+                last = any_peak ? e0 / tot : 1.f;
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) emit(k, ex[k] / tot);
+            } else {
+                const float tf = 1.f / tot;
+                last = any_peak ? e0 * tf : 1.f;
+#pragma unroll
+                for (int k = 0; k < NPL; ++k) emit(k, ex[k] * tf);
             }
         }
         if (full) ob_store<NPL>(o + col0, v);
