@@ -287,23 +287,57 @@ __global__ void __launch_bounds__((NWT + (DW ? 3 : 2)) * 64) banded_forward_kern
 // is monotone and logA_T[j][i*] >= c_j), which the window max already contains, and every out-of-window term is
 // <= fl(M + c_j) -- so in both cases
 //   m_j = max( window max, fl(M + c_j), extra-column terms )
-// is the value the dense recursion computes, bit for bit.  M is one number per frame: every wave reduces the
-// delta values it has just produced (six DPP max steps) and publishes one float; after the frame's only barrier
-// every lane combines the NWT wave maxima.  delta is double-buffered in LDS (four shifted copies each, see
-// banded_forward_kernel), so nothing a wave reads in frame t is written before the barrier that ends frame t.
-// M (= the back-trace's bound on every row-constant candidate) is stored in pad column S of the history row.
+// is the value the dense recursion computes, bit for bit.  M is one number per frame, formed by LDS float atomics:
+// every lane (after a max over its quad, two DPP steps) sends its new delta value with a no-return ds_max_f32 into one
+// of four slots of the frame's slot group, in the same burst as its four delta copy writes; after the frame's only
+// barrier every lane reads the four slots back (one ds_read_b128).  Four slot groups rotate: frame t adds into
+// group t % 4, reads group (t - 1) % 4 and resets group (t + 1) % 4 to -inf (last read in frame t - 2; frame t + 1 is
+// the first to add into it).  Four, not three, so that both emission prefetch depths (PF = 12 and 4) unroll into whole
+// rounds.  delta is double-buffered in LDS (four shifted copies each, see banded_forward_kernel), so nothing a wave
+// reads in frame t is written before the barrier that ends frame t.  M (= the back-trace's bound on every
+// row-constant candidate) is stored in pad column S of the history row.
 // ---------------------------------------------------------------------------------------
+// Global row access with a wave-uniform row base: a raw buffer descriptor (stride 0, no range limit) built on the SALU and
+// the lane's 32-bit byte offset -- no 64-bit per-lane address arithmetic on the VALU.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* row) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(row), (short)0, -1, 0x00020000);
+}
+__device__ __forceinline__ void row_store_f32(float* row, unsigned off, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), row_rsrc(row), off, 0, 0);
+}
+template <typename ET>
+__device__ __forceinline__ float row_load_e(const ET* row, unsigned off);
+template <>
+__device__ __forceinline__ float row_load_e<float>(const float* row, unsigned off) {
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(row_rsrc(row), off, 0, 0));
+}
+template <>
+__device__ __forceinline__ float row_load_e<__half>(const __half* row, unsigned off) {
+    return __half2float(__ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(row_rsrc(row), off, 0, 0)));
+}
+
+// Frame-maximum slots of the floor-max kernel: a two-step DPP max over each quad of lanes, then lane l adds into slot
+// 4 * (l & 3) + ((l >> 2) & 3) -- slots 0..3 between them see all sixteen quads; slots 4..15 are written and never read.
+inline constexpr int kFmGroups = 4;                       // slot groups in rotation (written, read, being reset, idle)
+inline constexpr int kFmGroupFloats = 64;                 // a group's 16 slots + the rest of the reset wave's 64 lanes
+inline constexpr int kFmSlots = 4;                        // slots read back per frame
+__device__ __forceinline__ int fm_slot(int lane) { return 4 * (lane & 3) + ((lane >> 2) & 3); }
+// max over the lane's quad, then a no-return ds_max_f32 into its slot
+__device__ __forceinline__ void fm_publish(float* slot, float v) {
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xb1, 0xf, 0xf, false)));   // quad_perm:[1,0,3,2]
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4e, 0xf, 0xf, false)));   // quad_perm:[2,3,0,1]
+    __hip_atomic_fetch_max(slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 template <int W, int NWT, int NXT, int PF, typename ET>
 __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NP = NWT * 64;
     constexpr int DC = NP + 16;                   // copy stride (see banded_forward_kernel)
     constexpr int BUF = 4 * DC;                   // floats per delta buffer
-    constexpr int NWM = (NWT + 3) / 4 * 4;        // wave maxima per buffer, padded to whole float4s with -inf
     float* dls = reinterpret_cast<float*>(smem);  // [2][4][DC]
-    float* wm = dls + 2 * BUF;                    // [2][NWM]
-    float* dump = wm + 2 * NWM;                   // [64 + NWM] per-lane dump slots (lanes that do not own a wave max)
-    VI* tot = reinterpret_cast<VI*>(dump + 64 + NWM);
+    float* fmg = dls + 2 * BUF;                   // [kFmGroups][kFmGroupFloats] frame-maximum slot groups
+    VI* tot = reinterpret_cast<VI*>(fmg + kFmGroups * kFmGroupFloats);
     // W = 128 with twelve waves (S > 512) leaves 168 registers per thread: the last 32 window weights then live in LDS
     // ([8][NP] float4-interleaved, read with conflict-free 16-byte reads next to the delta window)
     constexpr int WR = (W == 128 && NWT > 8) ? 96 : W;     // register-resident window weights
@@ -330,6 +364,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     // | other idle lanes: pad column S+1 of row t (never read)
     const unsigned hoff = tvalid ? (unsigned)(SD + j) : (j == S ? (unsigned)S : (unsigned)(SD + S + 1));
     const bool is_fm = j == S;
+    const unsigned hoffb = 4u * hoff, eoffb = (unsigned)(sizeof(ET) * jld);   // per-lane byte offsets from the frame's row bases
     const int lo = reinterpret_cast<const int32_t*>(a.image + a.off_lo)[jc];
     const float cj = tvalid ? reinterpret_cast<const float*>(a.image + a.off_rowc)[jc] : -INFINITY;
     float aw[WR];
@@ -365,24 +400,27 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     const int lov = (tvalid ? lo : 0) + sh;
     const float* rp = dls + 4 + (lov & 3) * DC + (lov & ~3);              // window start in the copy that aligns it
     float* wp = dls + 4 + sh + j;                                         // own entry of copy 0 (copy c: + c*DC - c)
-    float* wmp = lane == 63 ? wm + wv : dump + lane;                      // lane 63 ends up with the wave maximum
+    float* fmp = fmg + fm_slot(lane);                                     // own frame-maximum slot in group 0 (group g: + g*kFmGroupFloats)
 
-    for (int k = tid; k < 2 * BUF + 2 * NWM; k += NWT * 64) dls[k] = -INFINITY;
+    for (int k = tid; k < 2 * BUF + kFmGroups * kFmGroupFloats; k += NWT * 64) dls[k] = -INFINITY;
     __syncthreads();
 
-    // produce(): publish a new delta value -- four shifted copies and the wave's share of M -- into buffer WB
-    auto produce = [&](const float dn, const int WB) {
+    // produce(): publish a new delta value -- four shifted copies into buffer WB and the lane's share of M into slot group G --
+    // and reset slot group Z for the frame after next
+    auto produce = [&](const float dn, const int WB, const int G, const int Z) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) wp[WB * BUF + c * DC - c] = dn;
-        const float inc = wave_scan_max((NXL > 0 && is_x) ? -INFINITY : dn);
-        wmp[WB * NWM] = inc;
+        fm_publish(fmp + G * kFmGroupFloats, (NXL > 0 && is_x) ? -INFINITY : dn);
+        int w = wv;
+        asm volatile("" : "+s"(w));   // a fresh SGPR test per frame: hoisted, the wave test became two VALU instructions a frame
+        if (w == NWT - 1) fmg[Z * kFmGroupFloats + lane] = -INFINITY;
     };
 
     // ---------------- frame 0
     {
         const float d0 = tvalid ? reinterpret_cast<const float*>(a.image + a.off_logpi)[j] + load_e<ET>(E + j) : -INFINITY;
         if (tvalid) hist[j] = d0;
-        produce(d0, 0);
+        produce(d0, 0, 0, 1);   // (group 1 is still -inf)
     }
     // Emission rows are fetched PF frames ahead (PF even): a global load takes ~2 us under load, several frame times,
     // and the s_waitcnt before a frame's "+ e" must not be what paces the recursion.
@@ -396,15 +434,16 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     asm volatile("" ::"v"(cj));
     __syncthreads();
 
-    auto frame = [&](const int t, float& e_slot, const int RB) {
-        const int WB = RB ^ 1;
-        // ---- everything this frame reads from LDS: the window, the extra columns, the wave maxima
+    // frame t = 1 + PF*n + u: delta buffers u & 1 (read) / (u & 1) ^ 1 (write); slot groups u % 4 read, (u + 1) % 4 written,
+    // (u + 2) % 4 reset (PF % 4 == 0: every index is a compile-time constant)
+    static_assert(PF % 2 == 0 && PF % kFmGroups == 0, "the unrolled frames must cycle through whole buffer and slot-group rounds");
+    auto frame = [&](const int t, float& e_slot, const int u) {
+        const int RB = u & 1, WB = RB ^ 1;
+        const int GR = u % kFmGroups, GW = (u + 1) % kFmGroups, GZ = (u + 2) % kFmGroups;
+        // ---- everything this frame reads from LDS: the window, the extra columns, the frame-maximum slots
         const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
         float xd[NXL > 0 ? NXL : 1];
-        // the NWT wave maxima: whole float4s, plus one float2 when NWT % 4 is 2 or 3 (slots >= NWT hold -inf)
-        f32x4 wq[NWT / 4 > 0 ? NWT / 4 : 1];
-        f32x2 wr = f32x2{-INFINITY, -INFINITY};
-        float wl = -INFINITY;
+        f32x4 fq[kFmSlots / 4];
         // The small reads go out first and the first chunk of the window right behind them, and only then is M reduced: left to
         // itself the compiler reduces M before it issues the window reads -- a full LDS round trip with nothing else in flight.
         // (M reduced last instead lengthens the dependent tail after the last window read lands: measured slower.)
@@ -412,9 +451,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
 #pragma unroll
             for (int k = 0; k < NXL; ++k) xd[k] = dls[4 + sh + RB * BUF + xcol[k]];
 #pragma unroll
-            for (int q = 0; q < NWT / 4; ++q) wq[q] = reinterpret_cast<const f32x4*>(wm + RB * NWM)[q];
-            if (NWT % 4 >= 2) wr = *reinterpret_cast<const f32x2*>(wm + RB * NWM + (NWT / 4) * 4);
-            if (NWT % 4 == 1 || NWT % 4 == 3) wl = wm[RB * NWM + NWT - 1];
+            for (int q = 0; q < kFmSlots / 4; ++q) fq[q] = reinterpret_cast<const f32x4*>(fmg + GR * kFmGroupFloats)[q];
         };
         // the window in chunks of 32 sources (8 reads): wide windows (W = 96, 128) must not hold all their data at once
         float m0 = -INFINITY, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
@@ -441,10 +478,9 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         if (w0 == 0) {
             __builtin_amdgcn_sched_barrier(0);
             // M = max of delta_{t-1} over the non-extra sources
-            M = wl;
-            if (NWT % 4 >= 2) M = fmaxf(fmaxf(M, wr.x), wr.y);
+            M = fmaxf(fmaxf(fq[0].x, fq[0].y), fmaxf(fq[0].z, fq[0].w));
 #pragma unroll
-            for (int q = 0; q < NWT / 4; ++q) M = fmaxf(fmaxf(fmaxf(M, wq[q].x), wq[q].y), fmaxf(wq[q].z, wq[q].w));
+            for (int q = 1; q < kFmSlots / 4; ++q) M = fmaxf(fmaxf(fmaxf(M, fq[q].x), fq[q].y), fmaxf(fq[q].z, fq[q].w));
             m0 = M + cj;
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -459,10 +495,13 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
                 wa = awl[((w - WR) / 4) * NP + j];
                 wb = awl[((w - WR) / 4 + 1) * NP + j];
             }
-            const f32x2 c0_ = f32x2{da.x, da.y} + f32x2{wa.x, wa.y};
-            const f32x2 c1_ = f32x2{da.z, da.w} + f32x2{wa.z, wa.w};
-            const f32x2 c2_ = f32x2{db.x, db.y} + f32x2{wb.x, wb.y};
-            const f32x2 c3_ = f32x2{db.z, db.w} + f32x2{wb.z, wb.w};
+            f32x2 c0_ = f32x2{da.x, da.y} + f32x2{wa.x, wa.y};
+            f32x2 c1_ = f32x2{da.z, da.w} + f32x2{wa.z, wa.w};
+            f32x2 c2_ = f32x2{db.x, db.y} + f32x2{wb.x, wb.y};
+            f32x2 c3_ = f32x2{db.z, db.w} + f32x2{wb.z, wb.w};
+            // (W <= 32: all of a group's sums before its maxima.  Left alone, the compiler folds each sum into its chain at once,
+            // and a max3 right behind the packed add it reads needs an s_nop: eleven a frame.)
+            if (W <= 32) asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_));
             m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
             m1 = fmaxf(fmaxf(m1, c1_.x), c1_.y);
             m2 = fmaxf(fmaxf(m2, c2_.x), c2_.y);
@@ -480,15 +519,16 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
 #pragma unroll
         for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
         const float dn = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)) + e_slot;
-        produce(dn, WB);
-        asm volatile("" ::: "memory");   // keep the global store / prefetch behind the wave-max publication: they fill the
-                                         // wait for the LDS write acknowledgement before the barrier (-2 %)
+        produce(dn, WB, GW, GZ);
+        asm volatile("" ::: "memory");   // keep the global store / prefetch behind the frame-maximum publication: they fill
+                                         // the wait for the LDS write acknowledgement before the barrier (-2 %)
         // Unconditional store + prefetch: exact in-order vmcnt accounting (see banded_forward_kernel).  Row bases are
         // scalar index arithmetic on purpose: the SALU is idle, the VALU is not (running 64-bit per-lane pointers
-        // measured 3.5% slower).
+        // measured 3.5% slower).  Both are buffer instructions: a descriptor built on the SALU from the row base plus the lane's
+        // fixed 32-bit byte offset, no per-frame 64-bit address add on the VALU.
         const int tn = t + PF < Tb ? t + PF : Tb - 1;
-        hist[(size_t)(t - 1) * SD + hoff] = is_fm ? M : dn;
-        e_slot = load_e<ET>(E + (size_t)tn * S + jld);
+        row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, is_fm ? M : dn);
+        e_slot = row_load_e<ET>(E + (size_t)tn * S, eoffb);
         __syncthreads();
     };
 #ifdef VIT_TIMING_HOOKS
@@ -501,11 +541,11 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     int t = 1;
     for (; t + PF - 1 < Tb; t += PF) {
 #pragma unroll
-        for (int k = 0; k < PF; ++k) frame(t + k, er[k], k & 1);
+        for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
     }
 #pragma unroll
     for (int k = 0; k < PF - 1; ++k)
-        if (t + k < Tb) frame(t + k, er[k], k & 1);
+        if (t + k < Tb) frame(t + k, er[k], k);
 
     const int fb = (Tb - 1) & 1;                                          // buffer holding delta_{Tb-1}
     terminal_argmax(tvalid ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, tvalid, tot, NWT, a.last_state, a.loglik, song);
@@ -524,7 +564,8 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
 // of that window outside a row's own span are that row's constant (or an extra column), i.e. still >= c_j, so the
 // floor-max identity holds for the common window.  One lane therefore evaluates BOTH targets from one set of W/4
 // window reads: half the LDS traffic and half the waves (three at S = 361, one per SIMD), the same packed adds and
-// max3 per target.  Everything else is as in banded_floor_forward_kernel.
+// max3 per target.  Everything else is as in banded_floor_forward_kernel, except that M is still published through the
+// six-step wave scan and the history / emission rows are addressed with 64-bit per-lane pointers.
 // ---------------------------------------------------------------------------------------
 template <int W, int NPW, int NXT, int PF, typename ET>
 __global__ void __launch_bounds__(NPW * 64) banded_floor_pair_forward_kernel(FwdArgs a) {
@@ -755,8 +796,7 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
             return hipGetLastError();
         }
     }
-    constexpr int NWM = (NWT + 3) / 4 * 4;
-    const size_t ldsf = sizeof(float) * (8 * (NP + 16) + 2 * NWM + 64 + NWM) + sizeof(VI) * 16 +
+    const size_t ldsf = sizeof(float) * (8 * (NP + 16) + kFmGroups * kFmGroupFloats) + sizeof(VI) * 16 +
                         ((W == 128 && NWT > 8) ? sizeof(f32x4) * 8 * NP : 0);
     if ((W == 32 || W >= 84) && a.n_extras == 1)   // the reference's matrices: band + unvoiced column (compile-time extras count)
         hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, ((W == 32 || W >= 84) ? 1 : -1), PF, ET>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
