@@ -103,7 +103,9 @@ int vit_plan_query(const vit_plan *plan, vit_plan_info *info);
  * Kernel-selection overrides, per plan.  Every setting decodes the same bits -- they exist so that tests and timing
  * scripts can reach each kernel form (the library reads NO environment variables).  Keys:
  *   "forward_form"     banded plans: 0 by batch size | 1 one target per lane | 2 two targets per lane | 3 scan form |
- *                      4 wave form | 5 never the wave form
+ *                      4 wave form | 5 never the wave form | 6 floor form, split windows over eight waves (window 32 wide,
+ *                      256 < S < 384: the six-wave grids; what 0 picks there up to 256 songs with fp32 emissions.  Elsewhere 6 runs the
+ *                      one-target kernel, as 2 does for a plan without pair_ok)
  *   "backtrace_form"   0 auto | 1 generic kernel | 2 whole-row kernels (no sparse fetch) | 4 one (song, chunk) stream per LANE
  *                      instead of per wavefront (banded plans, full history; up to 256 chunks per song; VIT_EUNSUPPORTED elsewhere)
  *   "dense_songs"      songs per workgroup of the dense kernel (0 auto); "dense_one_thread" 1 = one thread per target;

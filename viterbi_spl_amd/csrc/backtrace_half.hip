@@ -35,13 +35,6 @@ constexpr int kHbWX1 = kHbW + kMaxExtras + 1;
 constexpr int kHbWXS = (kHbWX1 + 3) / 4 * 4;      // row stride of the candidate table in LDS: 16-byte aligned rows (and halves of a window)
 constexpr int kHbCB = kHbW + kMaxExtras;    // candidate lane of the bound
 
-// max(x[l], x[l ^ 32]) in every lane: v_permlane32_swap exchanges the upper 32 lanes of its first operand with the lower 32
-// of its second; fed two copies of x it leaves {x.lo, x.lo} and {x.hi, x.hi}
-__device__ __forceinline__ float hb_other_half(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-
 }  // namespace
 
 // MODE 0: speculative pass, one wave per (song, chunk).  MODE 1: verify-and-repair pass, one wave per song.
@@ -216,7 +209,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
                                 acc0 = fmaxf(fmaxf(acc0, sv[4 * q] + w4[q].x), sv[4 * q + 2] + w4[q].z);
                                 acc1 = fmaxf(fmaxf(acc1, sv[4 * q + 1] + w4[q].y), sv[4 * q + 3] + w4[q].w);
                             }
-                            float acc = hb_other_half(fmaxf(acc0, acc1));
+                            float acc = max_other_half(fmaxf(acc0, acc1));
                             acc = fmaxf(fmaxf(acc, fl_), xt_);
                             const float dw = acc + te[rr * kHbNE - ce0 + iv];
                             dv = isw ? dw : ta[rowa + kHbAux + aux_odd];
@@ -257,7 +250,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
                         acc0 = fmaxf(acc0, src[q] + wt[16 * hh + q]);
                         acc1 = fmaxf(acc1, src[q + 1] + wt[16 * hh + q + 1]);
                     }
-                    float acc = hb_other_half(fmaxf(acc0, acc1));
+                    float acc = max_other_half(fmaxf(acc0, acc1));
                     const float* __restrict__ ar = ta + rowa;
                     acc = fmaxf(acc, ar[a.mcol] + wt[CB]);
                     for (int k = 0; k < nx; ++k) acc = fmaxf(acc, ar[a.xcol0 + k] + wt[W + k]);

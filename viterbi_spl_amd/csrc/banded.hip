@@ -329,7 +329,43 @@ __device__ __forceinline__ void fm_publish(float* slot, float v) {
     __hip_atomic_fetch_max(slot, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <int W, int NWT, int NXT, int PF, typename ET>
+#ifdef VIT_TIMING_HOOKS
+// Per-wave probe of the floor kernels (timing option 64; hooks builds only, the <.., WPR = true> instantiations of the
+// S = 361 production shape).  Every wave accumulates over its frames
+//   work = s_memtime at "last max3 done" (just before the publication) - s_memtime right after the preceding barrier
+//   wait = s_memtime after the barrier release - s_memtime after the s_waitcnt lgkmcnt(0) in front of the barrier
+// and lane 0 of wave w leaves {SIMD_ID of HW_REG_HW_ID, mean work, mean wait, frames} in scratch floats 4w .. 4w+3 of its song.
+// The two s_memtime around the barrier return behind it (one more s_waitcnt per frame, the same for every wave): compare
+// waves with each other, and take the frame time from a run without the probe.
+struct WaveProbe {
+    unsigned long long t_rel = 0, t_pub = 0, work = 0, wait = 0;
+    __device__ __forceinline__ void start() { t_rel = __builtin_amdgcn_s_memtime(); }
+    __device__ __forceinline__ void before_publish(float dn) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" ::"v"(dn));
+        t_pub = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    __device__ __forceinline__ void barrier() {
+        unsigned long long t_in, t_out;
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_barrier\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(t_in), "=&s"(t_out) : "s"(t_pub) : "memory");
+        work += t_pub - t_rel;
+        wait += t_out - t_in;
+        t_rel = t_out;
+    }
+    __device__ __forceinline__ void finish(float* scratch, int wv, int lane, int frames) const {
+        if (lane != 0) return;
+        const float n = (float)(frames > 0 ? frames : 1);
+        scratch[4 * wv + 0] = (float)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);   // HW_REG_HW_ID bits 5:4 = SIMD_ID
+        scratch[4 * wv + 1] = (float)work / n;
+        scratch[4 * wv + 2] = (float)wait / n;
+        scratch[4 * wv + 3] = n;
+    }
+};
+#endif
+
+template <int W, int NWT, int NXT, int PF, typename ET, bool WPR = false>
 __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NP = NWT * 64;
@@ -437,6 +473,10 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     // frame t = 1 + PF*n + u: delta buffers u & 1 (read) / (u & 1) ^ 1 (write); slot groups u % 4 read, (u + 1) % 4 written,
     // (u + 2) % 4 reset (PF % 4 == 0: every index is a compile-time constant)
     static_assert(PF % 2 == 0 && PF % kFmGroups == 0, "the unrolled frames must cycle through whole buffer and slot-group rounds");
+#ifdef VIT_TIMING_HOOKS
+    constexpr bool wprobe = WPR;   // per-wave probe (see WaveProbe): an instantiation of its own, the loop without it is the release loop
+    WaveProbe wp_;
+#endif
     auto frame = [&](const int t, float& e_slot, const int u) {
         const int RB = u & 1, WB = RB ^ 1;
         const int GR = u % kFmGroups, GW = (u + 1) % kFmGroups, GZ = (u + 2) % kFmGroups;
@@ -519,6 +559,9 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
 #pragma unroll
         for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
         const float dn = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)) + e_slot;
+#ifdef VIT_TIMING_HOOKS
+        if constexpr (wprobe) wp_.before_publish(dn);
+#endif
         produce(dn, WB, GW, GZ);
         asm volatile("" ::: "memory");   // keep the global store / prefetch behind the frame-maximum publication: they fill
                                          // the wait for the LDS write acknowledgement before the barrier (-2 %)
@@ -529,10 +572,14 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         const int tn = t + PF < Tb ? t + PF : Tb - 1;
         row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, is_fm ? M : dn);
         e_slot = row_load_e<ET>(E + (size_t)tn * S, eoffb);
+#ifdef VIT_TIMING_HOOKS
+        if constexpr (wprobe) wp_.barrier(); else
+#endif
         __syncthreads();
     };
 #ifdef VIT_TIMING_HOOKS
     const bool probe = (a.debug & 48) != 0;
+    if constexpr (wprobe) wp_.start();
 #else
     constexpr bool probe = false;   // cycle probe: VIT_TIMING_HOOKS builds only; it writes the per-song scratch, never an output
 #endif
@@ -553,6 +600,216 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         const unsigned long long d = (a.debug & 16) ? __builtin_amdgcn_s_memtime() - clk0 : __builtin_amdgcn_s_memrealtime() - rt0;
         a.fmax[(size_t)song * 64 + 63] = (float)d / (float)(Tb > 1 ? Tb - 1 : 1);
     }
+#ifdef VIT_TIMING_HOOKS
+    if constexpr (wprobe) wp_.finish(a.fmax + (size_t)song * 64, wv, lane, Tb - 1);
+#endif
+}
+
+// ---------------------------------------------------------------------------------------
+// Floor-max banded forward kernel with split windows: eight waves for the grids that take six (256 < S < 384, W = 32).
+//
+// Six waves on four SIMDs put two waves on SIMD 0 and 1 and one on SIMD 2 and 3, and the frame waits for the full ones.
+// Here every SIMD carries one FULL wave (waves 0-3: one target per lane, the whole window, exactly the frame body of
+// banded_floor_forward_kernel) and one HALF-WINDOW wave (waves 4-7): lane l < 32 of wave w evaluates sources 0-15 of target
+// 256 + 32 (w - 4) + l, lane l + 32 sources 16-31 of the same target (4 reads, 8 packed adds, 8 max3 each).  The lower half
+// also carries the floor candidate fl(M + c_j), the upper half the extra columns; the other half holds -inf for them, so one
+// instruction stream serves both.  The two partial maxima are joined in registers (v_permlane32_swap + v_max_f32) and only
+// then is the emission added: max is exact and order-free, every candidate still gets exactly one rounded add, so the
+// result is the float the one-target kernel forms.  After the join both lanes of a target hold its new delta; the lower
+// lane writes copies 0 and 1 of it, the upper lane copies 2 and 3 (two ds_write each, nothing dead), and both add it into
+// the frame-maximum slots (a duplicate changes no maximum).  Both lanes store the history column (the same bits to the
+// same address), and the two lanes of idle slot S play the one-target kernel's "lane S" (M into pad column S of the previous
+// row); the other idle slots hit pad column S + 1 with -inf as they do there.  LDS layout (copy stride from the 384 state slots), barrier, read order, pinning, prefetch depth
+// and the history rows, pad columns included, are those of banded_floor_forward_kernel<32, 6, ...>, byte for byte.
+// The wave role is a scalar test outside the frame loop: two loop bodies with the same barriers.
+// ---------------------------------------------------------------------------------------
+inline constexpr int kSplitFullWaves = 4, kSplitHalfWaves = 4;
+inline constexpr int kSplitStates = 64 * kSplitFullWaves + 32 * kSplitHalfWaves;   // 384 target slots
+
+template <int NXT, int PF, typename ET, bool WPR = false>
+__global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) banded_floor_split_forward_kernel(FwdArgs a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int W = 32;
+    constexpr int NWF = kSplitFullWaves, NW = kSplitFullWaves + kSplitHalfWaves;
+    constexpr int DC = kSplitStates + 16;         // copy stride: from the state slots, not from the thread count
+    constexpr int BUF = 4 * DC;                   // floats per delta buffer
+    float* dls = reinterpret_cast<float*>(smem);  // [2][4][DC]
+    float* fmg = dls + 2 * BUF;                   // [kFmGroups][kFmGroupFloats] frame-maximum slot groups
+    VI* tot = reinterpret_cast<VI*>(fmg + kFmGroups * kFmGroupFloats);
+    const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
+    constexpr bool GEN = NXT < 0;
+    constexpr int NXL = GEN ? kMaxExtras : NXT;
+    const int nx = GEN ? a.n_extras : NXT;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const bool half = wv >= NWF;                                          // wave-uniform role
+    const int hh = half ? lane >> 5 : 0;                                  // which half of the window (half waves)
+    const int song = blockIdx.x;
+    const int Tb = song_length(a.lengths, song, T);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
+    float* __restrict__ hist = a.hist + (size_t)song * T * SD;
+
+    // ---------------- per-lane constants.  Idle targets (j >= S) carry -inf tables: their delta stays -inf.
+    const int j = half ? 64 * NWF + 32 * (wv - NWF) + (lane & 31) : tid;
+    const bool tvalid = j < S;
+    const bool own = tvalid && hh == 0;                                   // the lane that answers for its target (frame 0, terminal state)
+    const int jc = tvalid ? j : 0;
+    const int jld = tvalid ? j : S - 1;
+    // history store of frame t, relative to row t-1, by target slot exactly as in the one-target kernel: own column of row t |
+    // slot S: M into pad column S of row t-1 | the other idle slots: pad column S+1 of row t (never read).  Both lanes of a
+    // split target store the same bits to the same address (S >= 256: slot S lies in the half waves).
+    const bool is_fm = j == S;
+    const unsigned hoff = tvalid ? (unsigned)(SD + j) : (is_fm ? (unsigned)S : (unsigned)(SD + S + 1));
+    const unsigned hoffb = 4u * hoff, eoffb = (unsigned)(sizeof(ET) * jld);
+    const int lo = reinterpret_cast<const int32_t*>(a.image + a.off_lo)[jc];
+    int xcol[NXL > 0 ? NXL : 1];
+    bool is_x = false;
+#pragma unroll
+    for (int k = 0; k < NXL; ++k) {
+        xcol[k] = k < nx ? a.extras[k] : 0;
+        is_x |= (k < nx && j == xcol[k]);
+    }
+    const int sh = a.win_shift;                                           // (see banded_floor_forward_kernel)
+    const int lov = (tvalid ? lo : 0) + sh;
+    const float* rp = dls + 4 + (lov & 3) * DC + (lov & ~3) + 16 * hh;    // (half of the) window in the copy that aligns it
+    float* fmp = fmg + fm_slot(lane);
+
+    for (int k = tid; k < 2 * BUF + kFmGroups * kFmGroupFloats; k += NW * 64) dls[k] = -INFINITY;
+    __syncthreads();
+
+#ifdef VIT_TIMING_HOOKS
+    const bool probe = (a.debug & 48) != 0;
+    constexpr bool wprobe = WPR;   // per-wave probe (see WaveProbe): an instantiation of its own, the loop without it is the release loop
+    WaveProbe wp_;
+#else
+    constexpr bool probe = false;
+#endif
+    unsigned long long clk0 = 0ull, rt0 = 0ull;
+
+    // one role's share of the song: HALF = false the full-window waves, true the half-window waves
+    auto body = [&](auto role) {
+        constexpr bool HALF = decltype(role)::value;
+        constexpr int WL = HALF ? W / 2 : W;                              // window sources per lane
+        const float cj = own ? reinterpret_cast<const float*>(a.image + a.off_rowc)[jc] : -INFINITY;   // (upper half: -inf)
+        float aw[WL];
+        float xa[NXL > 0 ? NXL : 1];
+        {
+            const float* __restrict__ tab = reinterpret_cast<const float*>(a.image + a.off_tabA);
+            const float* __restrict__ xaT = reinterpret_cast<const float*>(a.image + a.off_extraA);
+#pragma unroll
+            for (int w = 0; w < WL; ++w) aw[w] = tvalid ? tab[(size_t)(w + (HALF ? 16 * hh : 0)) * SP + jc] : -INFINITY;
+#pragma unroll
+            for (int k = 0; k < NXL; ++k)
+                xa[k] = (tvalid && k < nx && (!HALF || hh == 1)) ? xaT[(size_t)k * SP + jc] : -INFINITY;   // (lower half: -inf)
+        }
+        // own entry of copy 0 (copy c: + c*DC - c); an upper lane starts at copy 2
+        float* wp = dls + 4 + sh + j + (HALF ? hh * (2 * DC - 2) : 0);
+
+        auto produce = [&](const float dn, const int WB, const int G, const int Z) {
+#pragma unroll
+            for (int c = 0; c < (HALF ? 2 : 4); ++c) wp[WB * BUF + c * DC - c] = dn;
+            fm_publish(fmp + G * kFmGroupFloats, (NXL > 0 && is_x) ? -INFINITY : dn);
+            if constexpr (HALF) {
+                int w = wv;
+                asm volatile("" : "+s"(w));   // (see banded_floor_forward_kernel)
+                if (w == NW - 1) fmg[Z * kFmGroupFloats + lane] = -INFINITY;
+            }
+        };
+
+        // ---------------- frame 0 (both lanes of a split target hold it)
+        {
+            const float d0 = tvalid ? reinterpret_cast<const float*>(a.image + a.off_logpi)[j] + load_e<ET>(E + j) : -INFINITY;
+            if (own) hist[j] = d0;
+            produce(d0, 0, 0, 1);
+        }
+        float er[PF];
+#pragma unroll
+        for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S + jld);
+#pragma unroll
+        for (int w = 0; w < WL; ++w) asm volatile("" ::"v"(aw[w]));
+#pragma unroll
+        for (int k = 0; k < NXL; ++k) asm volatile("" ::"v"(xa[k]));
+        asm volatile("" ::"v"(cj));
+        __syncthreads();
+
+        auto frame = [&](const int t, float& e_slot, const int u) {
+            const int RB = u & 1, WB = RB ^ 1;
+            const int GR = u % kFmGroups, GW = (u + 1) % kFmGroups, GZ = (u + 2) % kFmGroups;
+            const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
+            float xd[NXL > 0 ? NXL : 1];
+            f32x4 fq;
+            float m0, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
+            // small reads first, the window right behind them, then M (see banded_floor_forward_kernel)
+#pragma unroll
+            for (int k = 0; k < NXL; ++k) xd[k] = dls[4 + sh + RB * BUF + xcol[k]];
+            fq = reinterpret_cast<const f32x4*>(fmg + GR * kFmGroupFloats)[0];
+            asm volatile("" ::: "memory");
+            f32x4 dw[WL / 4];
+#pragma unroll
+            for (int q = 0; q < WL / 4; ++q) dw[q] = win[q];
+            __builtin_amdgcn_sched_barrier(0);
+            const float M = fmaxf(fmaxf(fq.x, fq.y), fmaxf(fq.z, fq.w));
+            m0 = M + cj;
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int w = 0; w < WL; w += 8) {
+                const f32x4 da = dw[w / 4], db = dw[w / 4 + 1];
+                f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[w + 0], aw[w + 1]};
+                f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[w + 2], aw[w + 3]};
+                f32x2 c2_ = f32x2{db.x, db.y} + f32x2{aw[w + 4], aw[w + 5]};
+                f32x2 c3_ = f32x2{db.z, db.w} + f32x2{aw[w + 6], aw[w + 7]};
+                asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_));   // a group's sums before its maxima: no hazard s_nop
+                m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
+                m1 = fmaxf(fmaxf(m1, c1_.x), c1_.y);
+                m2 = fmaxf(fmaxf(m2, c2_.x), c2_.y);
+                m3 = fmaxf(fmaxf(m3, c3_.x), c3_.y);
+            }
+#pragma unroll
+            for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
+            float mx = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+            if constexpr (HALF) mx = max_other_half(mx);                  // join the two halves of the window
+            const float dn = mx + e_slot;
+#ifdef VIT_TIMING_HOOKS
+            if constexpr (wprobe) wp_.before_publish(dn);
+#endif
+            produce(dn, WB, GW, GZ);
+            asm volatile("" ::: "memory");   // the global store / prefetch fill the wait for the LDS write acknowledgement
+            const int tn = t + PF < Tb ? t + PF : Tb - 1;
+            row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, (HALF && is_fm) ? M : dn);   // (full waves hold live targets only)
+            e_slot = row_load_e<ET>(E + (size_t)tn * S, eoffb);
+#ifdef VIT_TIMING_HOOKS
+            if constexpr (wprobe) wp_.barrier(); else
+#endif
+            __syncthreads();
+        };
+#ifdef VIT_TIMING_HOOKS
+        if constexpr (wprobe) wp_.start();
+#endif
+        clk0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
+        rt0 = probe ? __builtin_amdgcn_s_memrealtime() : 0ull;
+        int t = 1;
+        for (; t + PF - 1 < Tb; t += PF) {
+#pragma unroll
+            for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
+        }
+#pragma unroll
+        for (int k = 0; k < PF - 1; ++k)
+            if (t + k < Tb) frame(t + k, er[k], k);
+    };
+    static_assert(PF % 2 == 0 && PF % kFmGroups == 0, "the unrolled frames must cycle through whole buffer and slot-group rounds");
+    if (half) body(std::true_type{}); else body(std::false_type{});
+
+    const int fb = (Tb - 1) & 1;                                          // buffer holding delta_{Tb-1}
+    terminal_argmax(own ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, own, tot, NW, a.last_state, a.loglik, song);
+    if (probe && tid == 0) {  // timing experiments only: cycles (16) or 100 MHz ticks (32) per frame -> scratch slot 63
+        const unsigned long long d = (a.debug & 16) ? __builtin_amdgcn_s_memtime() - clk0 : __builtin_amdgcn_s_memrealtime() - rt0;
+        a.fmax[(size_t)song * 64 + 63] = (float)d / (float)(Tb > 1 ? Tb - 1 : 1);
+    }
+#ifdef VIT_TIMING_HOOKS
+    if constexpr (wprobe) wp_.finish(a.fmax + (size_t)song * 64, wv, lane, Tb - 1);
+#endif
 }
 
 // ---------------------------------------------------------------------------------------
@@ -782,8 +1039,31 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
     // Up to two songs per CU the one-target-per-lane kernel is (slightly) faster; beyond that the two-targets-per-lane
     // kernel wins because it moves half the window bytes through LDS (B = 512: 14.5 vs 15.5 ms).
     // FwdArgs::fwd_form 1 / 2 force one or the other.
+    // Split windows over eight waves (fwd_form 6 forces it): the six-wave grids at W = 32, up to one song per CU, fp32
+    // emissions.  Forward pass at [B, 30000, S], one-target -> split: S = 361 fp32 9.48 -> 8.98 ms (B = 128), 9.50 -> 9.03
+    // (B = 256); S = 321 fp32 9.46 -> 8.97, 9.52 -> 9.05.  With fp16 emissions the split kernel is 50 % SLOWER
+    // (S = 361: 10.28 -> 15.67 ms, S = 321: 10.27 -> 15.51 ms: its loops convert the 16-bit emission right behind the
+    // prefetch load and wait for it every frame), so the default leaves those to the one-target kernel (profiles/r06_logs/floor_split_ab.log).
+    if constexpr (W == 32 && NWT == 6) {
+        static_assert(kSplitStates == NP, "the split kernel keeps the six-wave kernel's LDS and history layout");
+        if (a.fwd_form == 6 || (a.fwd_form == 0 && a.B <= 256 && std::is_same_v<ET, float>)) {
+            const size_t ldss = sizeof(float) * (8 * (kSplitStates + 16) + kFmGroups * kFmGroupFloats) + sizeof(VI) * 16;
+            constexpr int NWS = kSplitFullWaves + kSplitHalfWaves;
+#ifdef VIT_TIMING_HOOKS
+            if ((a.debug & 64) && a.n_extras == 1)
+                hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET, true>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
+            else
+#endif
+            if (a.n_extras == 1)
+                hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
+            else
+                hipLaunchKernelGGL((banded_floor_split_forward_kernel<-1, PF, ET>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
+            return hipGetLastError();
+        }
+    }
     if constexpr (W <= 32 && NWT <= 8) {   // (at twelve waves, S = 722, the one-target kernel measured faster at every batch size)
-        const bool pair = a.pair_ok && ((a.B > 256 && a.fwd_form != 1) || a.fwd_form == 2);
+        // (fwd_form 6 where the split kernel does not exist: the one-target kernel, as fwd_form 2 without pair_ok)
+        const bool pair = a.pair_ok && ((a.B > 256 && a.fwd_form != 1 && a.fwd_form != 6) || a.fwd_form == 2);
         if (pair) {
             constexpr int NPW = (NWT + 1) / 2;
             constexpr int PFP = 4;             // (two workgroups share a CU here and cover each other's waits: 12 rows in flight measured 9 % slower)
@@ -798,6 +1078,14 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
     }
     const size_t ldsf = sizeof(float) * (8 * (NP + 16) + kFmGroups * kFmGroupFloats) + sizeof(VI) * 16 +
                         ((W == 128 && NWT > 8) ? sizeof(f32x4) * 8 * NP : 0);
+#ifdef VIT_TIMING_HOOKS
+    if constexpr (W == 32 && NWT == 6) {
+        if ((a.debug & 64) && a.n_extras == 1) {
+            hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, 1, PF, ET, true>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
+            return hipGetLastError();
+        }
+    }
+#endif
     if ((W == 32 || W >= 84) && a.n_extras == 1)   // the reference's matrices: band + unvoiced column (compile-time extras count)
         hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, ((W == 32 || W >= 84) ? 1 : -1), PF, ET>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
     else
@@ -830,9 +1118,9 @@ static hipError_t launch_scan_t(const FwdArgs& a, hipStream_t st) {
 
 template <int W, int NWT, typename ET>
 static hipError_t launch_banded_t(const FwdArgs& a, hipStream_t st) {
-    // fwd_form 3 forces the general (scan) kernel; so do the ablation bits of a VIT_TIMING_HOOKS build (48 = cycle probes
-    // exist in the floor kernels as well)
-    const bool floor_ok = a.floor_ok && a.S < NWT * 64 && a.fwd_form != 3 && !(a.debug & ~48);
+    // fwd_form 3 forces the general (scan) kernel; so do the ablation bits of a VIT_TIMING_HOOKS build (48 = cycle probes,
+    // 64 = per-wave probe: they exist in the floor kernels as well)
+    const bool floor_ok = a.floor_ok && a.S < NWT * 64 && a.fwd_form != 3 && !(a.debug & ~112);
     if constexpr (floor_form_instantiated(W, NWT)) {
         if (floor_ok) return launch_floor_t<W, NWT, ET>(a, st);
     }

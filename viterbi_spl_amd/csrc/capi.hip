@@ -19,7 +19,7 @@
 // timing scripts can reach each kernel form.  `timing` carries the ablation / probe mask of a -DVIT_TIMING_HOOKS build and
 // is refused by a release build (those bits DO change results).
 struct Tuning {
-    int forward_form = 0;      // banded plans: 0 by batch size | 1 one target per lane | 2 two targets per lane | 3 scan form
+    int forward_form = 0;      // banded plans: 0 by batch size | 1 one target per lane | 2 two targets per lane | 3 scan form | 6 split windows
                                //               | 4 wave form (one song per wavefront) | 5 never the wave form
     int backtrace_form = 0;    // 0 auto (sparse fetch, one stream per wavefront, where it applies) | 1 generic (lazy) kernel | 2 whole-row kernels |
                                // 4 one stream per LANE (backtrace_lane.hip; VIT_EUNSUPPORTED where it does not apply)
@@ -334,7 +334,7 @@ static void fwd_args_from_plan(const vit_plan* plan, vit::FwdArgs& a) {
     for (int k = 0; k < vit::kMaxExtras; ++k) a.extras[k] = plan->bp.extras[k];
     a.c0 = plan->bp.c0;
     a.debug = tn.timing;          // 0 unless built with -DVIT_TIMING_HOOKS (vit_plan_set_option refuses it otherwise)
-    a.fwd_form = tn.forward_form >= 1 && tn.forward_form <= 3 ? tn.forward_form : 0;
+    a.fwd_form = (tn.forward_form >= 1 && tn.forward_form <= 3) || tn.forward_form == 6 ? tn.forward_form : 0;
     a.dense_kt1 = tn.dense_one_thread;
     a.dense_form = tn.dense_form;
     a.step_form = tn.step_form;

@@ -87,6 +87,12 @@ __device__ __forceinline__ float wave_scan_max(float x) {
 __device__ __forceinline__ float wave_max_all(float x) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_scan_max(x)), 63));
 }
+// max(x[l], x[l ^ 32]) in every lane: v_permlane32_swap exchanges the upper 32 lanes of its first operand with the lower 32
+// of its second; fed two copies of x it leaves {x.lo, x.lo} and {x.hi, x.hi}
+__device__ __forceinline__ float max_other_half(float x) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
 // lane l <- x[l-1], lane 0 <- fill   (wave_shr:1)
 __device__ __forceinline__ float wave_shift_up(float x, float fill) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(x), 0x138, 0xf, 0xf, false));

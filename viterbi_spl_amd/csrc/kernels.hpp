@@ -47,7 +47,7 @@ struct FwdArgs {
     int extras[kMaxExtras];
     float c0;
     int debug;              // timing-only ablation mask; always 0 unless built with -DVIT_TIMING_HOOKS
-    int fwd_form;           // banded forward form: 0 by batch size | 1 one target per lane | 2 two targets per lane | 3 scan
+    int fwd_form;           // banded forward form: 0 by batch size | 1 one target per lane | 2 two targets per lane | 3 scan | 6 split windows (eight waves)
     int dense_kt1;          // dense kernel: one thread per target even where two fit
     int dense_form;         // dense kernel: 0 matrix-resident form where it applies | 1 always the streaming form
     int step_form;          // step kernel: 3 = four targets per lane in one wave (step4_forward_kernel)
