@@ -211,12 +211,23 @@ int vit_decode_checkpointed(const vit_plan *plan, const void *logE, int emis_dty
  *   offsets : HOST, [B+1] int64, offsets[0] = 0, strictly increasing (every song holds at least one frame)
  *   states  : device, [offsets[B]] int32, packed like the emission rows
  *   loglik  : device, [B] float32 or NULL
- * Plans with the wave form only (vit_plan_info reserved[2] bit 3; VIT_EUNSUPPORTED otherwise): the forward pass runs
- * min(B, 8 x compute units) wavefronts, each decoding a host-packed list of songs back to back (longest-first greedy bins by
- * frame count), so a launch costs (total frames / wavefronts), not its longest song, and neither memory nor time is spent on
- * padding; the back-trace cuts every song into chunks of about equal length, one chunk per lane ("backtrace_form" 4's kernels).  The library builds the slot and chunk tables on
+ * Which plans: (a) plans with the wave form (vit_plan_info reserved[2] bit 3): the forward pass runs min(B, 8 x compute units)
+ * wavefronts, each decoding a host-packed list of songs back to back (longest-first greedy bins by frame count), so a launch
+ * costs (total frames / wavefronts), not its longest song, and neither memory nor time is spent on padding; the back-trace cuts
+ * every song into chunks of about equal length, one chunk per lane ("backtrace_form" 4's kernels).  (b) Banded plans without the
+ * wave form whose floor form is proven (reserved[1]; the 722-state jdc grids): the same scheme with one WORKGROUP per slot -- as
+ * many slots as workgroups of the floor kernel are resident at once (an occupancy query x compute units), at most B and at most
+ * total frames / longest song --, history rows in the workgroup layout (stride ceil((S+2)/4)*4, state i in column i, the frame
+ * maximum in column S), the same lane back-trace.  (c) Step-structured plans (reserved[2] bit 2; the Durrieu matrix): the step
+ * kernel per slot and the generic (lazy) back-trace with at most 32 chunks per song, none shorter than 1024 frames.  Every other
+ * plan (unstructured matrices, banded plans that only have the scan form) gets 0 from vit_workspace_bytes_packed and
+ * VIT_EUNSUPPORTED from vit_decode_packed, before anything is enqueued; a size > 0 means the decode launches.  Of the plan's
+ * options the packed decode of (b) / (c) honours "bt_warm" and "win_shift" and ignores "forward_form", "step_form",
+ * "backtrace_form" and "bt_chunks".
+ * The library builds the slot and chunk tables on
  * the host from `offsets` and uploads them through a pinned staging buffer it owns (it waits for the previous call's upload
- * before reusing it; otherwise no host synchronisation).  Bit-identical to vit_decode() of each song alone.  Not thread-safe against
+ * before reusing it; otherwise no host synchronisation; the first packed decode of a plan of (b) / (c) asks the runtime for the
+ * kernel's occupancy).  Bit-identical to vit_decode() of each song alone.  Not thread-safe against
  * concurrent packed decodes on the same plan (one staging buffer per plan); `lengths`-style padding does not exist here, so states
  * carries no -1 entries.
  */

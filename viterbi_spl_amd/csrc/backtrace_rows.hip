@@ -283,7 +283,10 @@ __global__ void __launch_bounds__(512) banded_backtrace_kernel(BtArgs a) {
 constexpr int kBtWaves = 4;
 
 // MODE 0: speculative pass, one wave per (song, chunk).  MODE 1: verify pass, one wave per song.
-template <int NWT, int MODE>
+// PK: packed batch (vit_decode_packed for plans the lane form does not serve).  MODE 0 runs one wave per entry of wave_song; song b
+// owns the waves and the chunk entries chunk_base[b] .. chunk_base[b+1]-1, so its chunk count grows with its length; its history
+// rows and states sit at row offsets[b] of the packed buffers and there are no frames past its end to fill.
+template <int NWT, int MODE, bool PK = false>
 __global__ void __launch_bounds__(kBtWaves * 64) lazy_backtrace_kernel(BtArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int EPL = NWT;               // sources per lane, strided: i = e*64 + lane
@@ -323,14 +326,19 @@ __global__ void __launch_bounds__(kBtWaves * 64) lazy_backtrace_kernel(BtArgs a)
     }
     __syncthreads();
 
-    const int C = a.chunks;
     const int gw = blockIdx.x * kBtWaves + wv;          // global wave index
-    const int song = MODE == 0 ? gw / C : gw;
-    const int chunk = MODE == 0 ? gw % C : 0;
+    if (PK && MODE == 0 && gw >= a.n_waves) return;
+    const int song = PK ? (MODE == 0 ? a.wave_song[gw] : gw) : (MODE == 0 ? gw / a.chunks : gw);
     if (song >= a.B) return;
-    const int Tb = song_length(a.lengths, song, T);
-    int32_t* __restrict__ states = a.states + (size_t)song * T;
-    const float* __restrict__ hist = a.hist + (size_t)song * T * SD;
+    const int cbase = PK ? a.chunk_base[song] : 0;
+    const int C = PK ? a.chunk_base[song + 1] - cbase : a.chunks;
+    const int chunk = MODE == 0 ? (PK ? gw - cbase : gw % C) : 0;
+    const long long row0 = PK ? a.offsets[song] : (long long)song * T;  // first history row / state of the song
+    const int Tb = PK ? (int)(a.offsets[song + 1] - row0) : song_length(a.lengths, song, T);
+    const int Tpad = PK ? Tb : T;                       // frames past the song's end are filled with -1 up to here
+    int32_t* __restrict__ states = a.states + (size_t)row0;
+    const float* __restrict__ hist = a.hist + (size_t)row0 * SD;
+    int32_t* __restrict__ entry = a.entry + (PK ? (size_t)cbase : (size_t)song * C);   // [C] of this song
     const float* __restrict__ Arow = reinterpret_cast<const float*>(a.image + a.off_Arow);
     float* tile = reinterpret_cast<float*>(tiles + wv * kBtVec * 64);
     int32_t* out = outs + wv * 64;
@@ -520,7 +528,7 @@ __global__ void __launch_bounds__(kBtWaves * 64) lazy_backtrace_kernel(BtArgs a)
     if (MODE == 0) {
         const int lo_c = (int)((long long)L * chunk / C), hi_c = (int)((long long)L * (chunk + 1) / C);
         if (chunk == C - 1) {
-            for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
+            for (int t = Tb + lane; t < Tpad; t += 64) states[t] = -1;
             if (lane == 0) states[Tb - 1] = a.last_state[song];
         }
         int top = hi_c - 1 + a.warm;
@@ -549,18 +557,18 @@ __global__ void __launch_bounds__(kBtWaves * 64) lazy_backtrace_kernel(BtArgs a)
             cur = idx == 0x7fffffffu ? 0 : (int)idx;
         }
         if (hi_c <= lo_c) {                       // empty chunk (very short song)
-            if (lane == 0) a.entry[(size_t)song * C + chunk] = cur;
+            if (lane == 0) entry[chunk] = cur;
             return;
         }
         cur = chase(top, hi_c, cur, false);       // warm-up: frames top .. hi_c, nothing written
-        if (lane == 0) a.entry[(size_t)song * C + chunk] = cur;   // state this chunk assumed at frame hi_c
+        if (lane == 0) entry[chunk] = cur;   // state this chunk assumed at frame hi_c
         chase(hi_c - 1, lo_c, cur, true);
     } else {
         int truth = -1;                           // verified state at frame hi_c of the chunk being checked
         for (int c = C - 2; c >= 0; --c) {
             const int lo_c = (int)((long long)L * c / C), hi_c = (int)((long long)L * (c + 1) / C);
             if (truth < 0) truth = __builtin_amdgcn_readfirstlane(states[hi_c]);
-            const int assumed = __builtin_amdgcn_readfirstlane(a.entry[(size_t)song * C + c]);
+            const int assumed = __builtin_amdgcn_readfirstlane(entry[c]);
             if (hi_c > lo_c && assumed != truth) {
                 truth = chase(hi_c - 1, lo_c, truth, true);   // re-chase from the true state; ends at frame lo_c
             } else {
@@ -629,6 +637,25 @@ static hipError_t launch_bt_t(BtArgs a, hipStream_t st) {
     if (e != hipSuccess || a.chunks <= 1) return e;
     hipLaunchKernelGGL((lazy_backtrace_kernel<NWT, 1>), dim3((int)((a.B + kBtWaves - 1) / kBtWaves)), dim3(kBtWaves * 64),
                        lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_backtrace_rows_packed(BtArgs a, hipStream_t st) {
+    if (!a.offsets || !a.wave_song || !a.chunk_base || a.n_waves < 1 || a.chunks < 1 || a.chunks > kBtMaxChunks) return hipErrorInvalidValue;
+    if (a.banded) return hipErrorInvalidConfiguration;         // (banded plans take the lane form)
+    a.K = backtrace_tile_rows(a.SD);
+    a.have_fmax = 0;
+    size_t lds = sizeof(f32x4) * kBtWaves * kBtVec * 64 + sizeof(int32_t) * kBtWaves * 64;
+    if (a.step_ok) lds += sizeof(float) * (a.step_kb + 1) * a.SP;
+    const int nwt = (a.S + 63) / 64;
+    const dim3 g0((unsigned)((a.n_waves + kBtWaves - 1) / kBtWaves)), g1((unsigned)((a.B + kBtWaves - 1) / kBtWaves)), blk(kBtWaves * 64);
+    if (nwt > 16) return hipErrorInvalidConfiguration;
+    if (nwt <= 12) hipLaunchKernelGGL((lazy_backtrace_kernel<12, 0, true>), g0, blk, lds, st, a);
+    else hipLaunchKernelGGL((lazy_backtrace_kernel<16, 0, true>), g0, blk, lds, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || a.chunks <= 1) return e;
+    if (nwt <= 12) hipLaunchKernelGGL((lazy_backtrace_kernel<12, 1, true>), g1, blk, lds, st, a);
+    else hipLaunchKernelGGL((lazy_backtrace_kernel<16, 1, true>), g1, blk, lds, st, a);
     return hipGetLastError();
 }
 

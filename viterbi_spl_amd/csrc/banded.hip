@@ -365,8 +365,15 @@ struct WaveProbe {
 };
 #endif
 
-template <int W, int NWT, int NXT, int PF, typename ET, bool WPR = false>
+// PK = true is the packed variant (vit_decode_packed, plans without the wave form): the workgroup is a SLOT and decodes the
+// songs slot_songs[slot_begin[w] .. slot_begin[w+1]) back to back, as a wave does in wave.hip.  Emission and history rows of
+// a song start at row offsets[song] of the packed buffers (row strides S and SD; T plays no role).  The per-lane tables and
+// the LDS-resident weights are loaded once; between two songs both delta buffers and every slot group go back to -inf behind
+// a barrier.  The history layout is the unpacked one (the frame maximum of row t in pad column S of row t), so a song
+// writes its own rows only.  PK = false compiles to the code it was before the parameter existed.
+template <int W, int NWT, int NXT, int PF, typename ET, bool WPR = false, bool PK = false>
 __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs a) {
+    static_assert(!(PK && WPR), "the per-wave probe exists for the unpacked kernel only");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NP = NWT * 64;
     constexpr int DC = NP + 16;                   // copy stride (see banded_forward_kernel)
@@ -376,7 +383,8 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     VI* tot = reinterpret_cast<VI*>(fmg + kFmGroups * kFmGroupFloats);
     // W = 128 with twelve waves (S > 512) leaves 168 registers per thread: the last 32 window weights then live in LDS
     // ([8][NP] float4-interleaved, read with conflict-free 16-byte reads next to the delta window)
-    constexpr int WR = (W == 128 && NWT > 8) ? 96 : W;     // register-resident window weights
+    // (PK: 88 -- the song loop keeps a few more values alive, and 168 registers leave nothing to spill into)
+    constexpr int WR = (W == 128 && NWT > 8) ? (PK ? 88 : 96) : W;     // register-resident window weights
     f32x4* awl = reinterpret_cast<f32x4*>(tot + 16);       // [(W - WR) / 4][NP]
     const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
     constexpr bool GEN = NXT < 0;
@@ -386,10 +394,25 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int song = blockIdx.x;
-    const int Tb = song_length(a.lengths, song, T);
-    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
-    float* __restrict__ hist = a.hist + (size_t)song * T * SD;
+    // the song being decoded: the workgroup's own, or (PK) the slot's songs one after the other
+    int song = blockIdx.x;
+    int Tb = PK ? 1 : song_length(a.lengths, song, T);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PK ? (size_t)0 : (size_t)song * T * S);
+    float* __restrict__ hist = a.hist + (PK ? (size_t)0 : (size_t)song * T * SD);
+    int si = 0, si_end = 1;                                               // (PK) position in slot_songs, end of the slot's list
+    auto take_song = [&]() {                                              // (PK) wave-uniform: scalar loads
+        song = a.slot_songs[si];
+        const long long r0 = a.offsets[song];
+        Tb = (int)(a.offsets[song + 1] - r0);
+        E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
+        hist = a.hist + (size_t)r0 * SD;
+    };
+    if constexpr (PK) {
+        si = a.slot_begin[blockIdx.x];
+        si_end = a.slot_begin[blockIdx.x + 1];
+        if (si >= si_end) return;                                         // an empty slot (the host makes none)
+        take_song();
+    }
 
     // ---------------- per-lane constants.  Idle lanes (j >= S) carry -inf tables: their delta stays -inf.
     const int j = tid;
@@ -452,157 +475,178 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         if (w == NWT - 1) fmg[Z * kFmGroupFloats + lane] = -INFINITY;
     };
 
-    // ---------------- frame 0
-    {
-        const float d0 = tvalid ? reinterpret_cast<const float*>(a.image + a.off_logpi)[j] + load_e<ET>(E + j) : -INFINITY;
-        if (tvalid) hist[j] = d0;
-        produce(d0, 0, 0, 1);   // (group 1 is still -inf)
-    }
-    // Emission rows are fetched PF frames ahead (PF even): a global load takes ~2 us under load, several frame times,
-    // and the s_waitcnt before a frame's "+ e" must not be what paces the recursion.
-    float er[PF];
-#pragma unroll
-    for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S + jld);
-#pragma unroll
-    for (int w = 0; w < WR; ++w) asm volatile("" ::"v"(aw[w]));
-#pragma unroll
-    for (int k = 0; k < NXL; ++k) asm volatile("" ::"v"(xa[k]));
-    asm volatile("" ::"v"(cj));
-    __syncthreads();
-
-    // frame t = 1 + PF*n + u: delta buffers u & 1 (read) / (u & 1) ^ 1 (write); slot groups u % 4 read, (u + 1) % 4 written,
-    // (u + 2) % 4 reset (PF % 4 == 0: every index is a compile-time constant)
-    static_assert(PF % 2 == 0 && PF % kFmGroups == 0, "the unrolled frames must cycle through whole buffer and slot-group rounds");
-#ifdef VIT_TIMING_HOOKS
-    constexpr bool wprobe = WPR;   // per-wave probe (see WaveProbe): an instantiation of its own, the loop without it is the release loop
-    WaveProbe wp_;
-#endif
-    auto frame = [&](const int t, float& e_slot, const int u) {
-        const int RB = u & 1, WB = RB ^ 1;
-        const int GR = u % kFmGroups, GW = (u + 1) % kFmGroups, GZ = (u + 2) % kFmGroups;
-        // ---- everything this frame reads from LDS: the window, the extra columns, the frame-maximum slots
-        const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
-        float xd[NXL > 0 ? NXL : 1];
-        f32x4 fq[kFmSlots / 4];
-        // The small reads go out first and the first chunk of the window right behind them, and only then is M reduced: left to
-        // itself the compiler reduces M before it issues the window reads -- a full LDS round trip with nothing else in flight.
-        // (M reduced last instead lengthens the dependent tail after the last window read lands: measured slower.)
-        auto small_reads = [&]() {
-#pragma unroll
-            for (int k = 0; k < NXL; ++k) xd[k] = dls[4 + sh + RB * BUF + xcol[k]];
-#pragma unroll
-            for (int q = 0; q < kFmSlots / 4; ++q) fq[q] = reinterpret_cast<const f32x4*>(fmg + GR * kFmGroupFloats)[q];
-        };
-        // the window in chunks of 32 sources (8 reads): wide windows (W = 96, 128) must not hold all their data at once
-        float m0 = -INFINITY, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
-        float M = -INFINITY;
-        small_reads();
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int w0 = 0; w0 < W; w0 += 32) {
-        // W > 64: one chunk of reads in flight at a time (W register-resident weights leave no room for more; with
-        // twelve waves per workgroup the other waves of the SIMD cover the read latency)
-        if ((W > 64 || (W == 64 && NWT > 8)) && w0 > 0) asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3)::"memory");
-        f32x4 dw[8];
-#ifdef VIT_ABL_READS
-        // result-breaking ablation (make TIMING=1 ABL=n builds only): read n of every chunk's window quads, the others reuse them --
-        // what does the LDS return path cost a frame?
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            if (w0 + 4 * q < W) { if (q < VIT_ABL_READS) dw[q] = win[w0 / 4 + q]; else dw[q] = dw[q % VIT_ABL_READS]; }
-#else
-#pragma unroll
-        for (int q = 0; q < 8; ++q)
-            if (w0 + 4 * q < W) dw[q] = win[w0 / 4 + q];
-#endif
-        if (w0 == 0) {
-            __builtin_amdgcn_sched_barrier(0);
-            // M = max of delta_{t-1} over the non-extra sources
-            M = fmaxf(fmaxf(fq[0].x, fq[0].y), fmaxf(fq[0].z, fq[0].w));
-#pragma unroll
-            for (int q = 1; q < kFmSlots / 4; ++q) M = fmaxf(fmaxf(fmaxf(M, fq[q].x), fq[q].y), fmaxf(fq[q].z, fq[q].w));
-            m0 = M + cj;
-            __builtin_amdgcn_sched_barrier(0);
+    // ---------------- one pass per song (PK: the songs of the slot, back to back)
+    for (;;) {
+        // ---------------- frame 0
+        // (PK: the lane's column index is made opaque once per song, so that the 64-bit addresses of this preamble are formed here
+        // and do not stay in registers across the frame loop for the next song -- W = 128 with twelve waves has none to spare)
+        int jf = j;
+        if constexpr (PK) asm volatile("" : "+v"(jf));
+        const bool tvf = PK ? jf < S : tvalid;
+        const int jldf = PK ? (tvf ? jf : S - 1) : jld;
+        {
+            const float d0 = tvf ? reinterpret_cast<const float*>(a.image + a.off_logpi)[jf] + load_e<ET>(E + jf) : -INFINITY;
+            if (tvf) hist[jf] = d0;
+            produce(d0, 0, 0, 1);   // (group 1 is still -inf)
         }
+        // Emission rows are fetched PF frames ahead (PF even): a global load takes ~2 us under load, several frame times,
+        // and the s_waitcnt before a frame's "+ e" must not be what paces the recursion.
+        float er[PF];
 #pragma unroll
-        for (int w = w0; w + 7 < W && w < w0 + 32; w += 8) {
-            const f32x4 da = dw[(w - w0) / 4], db = dw[(w - w0) / 4 + 1];
-            f32x4 wa, wb;
-            if (w < WR) {
-                wa = f32x4{aw[w < WR ? w + 0 : 0], aw[w < WR ? w + 1 : 0], aw[w < WR ? w + 2 : 0], aw[w < WR ? w + 3 : 0]};
-                wb = f32x4{aw[w < WR ? w + 4 : 0], aw[w < WR ? w + 5 : 0], aw[w < WR ? w + 6 : 0], aw[w < WR ? w + 7 : 0]};
-            } else {
-                wa = awl[((w - WR) / 4) * NP + j];
-                wb = awl[((w - WR) / 4 + 1) * NP + j];
-            }
-            f32x2 c0_ = f32x2{da.x, da.y} + f32x2{wa.x, wa.y};
-            f32x2 c1_ = f32x2{da.z, da.w} + f32x2{wa.z, wa.w};
-            f32x2 c2_ = f32x2{db.x, db.y} + f32x2{wb.x, wb.y};
-            f32x2 c3_ = f32x2{db.z, db.w} + f32x2{wb.z, wb.w};
-            // (W <= 32: all of a group's sums before its maxima.  Left alone, the compiler folds each sum into its chain at once,
-            // and a max3 right behind the packed add it reads needs an s_nop: eleven a frame.)
-            if (W <= 32) asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_));
-            m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
-            m1 = fmaxf(fmaxf(m1, c1_.x), c1_.y);
-            m2 = fmaxf(fmaxf(m2, c2_.x), c2_.y);
-            m3 = fmaxf(fmaxf(m3, c3_.x), c3_.y);
-        }
-        if (W % 8 == 4 && w0 + 32 >= W) {          // W = 84: the last four sources (one read, two packed adds)
-            static_assert(W % 8 != 4 || W <= WR, "an odd float4 count only with register-resident weights");
-            const f32x4 da = dw[((W - 4 - w0) / 4) & 7];
-            const f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[W - 4], aw[W - 3]};
-            const f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[W - 2], aw[W - 1]};
-            m2 = fmaxf(fmaxf(m2, c0_.x), c0_.y);
-            m3 = fmaxf(fmaxf(m3, c1_.x), c1_.y);
-        }
-        }
+        for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S + jldf);
 #pragma unroll
-        for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
-        const float dn = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)) + e_slot;
-#ifdef VIT_TIMING_HOOKS
-        if constexpr (wprobe) wp_.before_publish(dn);
-#endif
-        produce(dn, WB, GW, GZ);
-        asm volatile("" ::: "memory");   // keep the global store / prefetch behind the frame-maximum publication: they fill
-                                         // the wait for the LDS write acknowledgement before the barrier (-2 %)
-        // Unconditional store + prefetch: exact in-order vmcnt accounting (see banded_forward_kernel).  Row bases are
-        // scalar index arithmetic on purpose: the SALU is idle, the VALU is not (running 64-bit per-lane pointers
-        // measured 3.5% slower).  Both are buffer instructions: a descriptor built on the SALU from the row base plus the lane's
-        // fixed 32-bit byte offset, no per-frame 64-bit address add on the VALU.
-        const int tn = t + PF < Tb ? t + PF : Tb - 1;
-        row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, is_fm ? M : dn);
-        e_slot = row_load_e<ET>(E + (size_t)tn * S, eoffb);
-#ifdef VIT_TIMING_HOOKS
-        if constexpr (wprobe) wp_.barrier(); else
-#endif
+        for (int w = 0; w < WR; ++w) asm volatile("" ::"v"(aw[w]));
+#pragma unroll
+        for (int k = 0; k < NXL; ++k) asm volatile("" ::"v"(xa[k]));
+        asm volatile("" ::"v"(cj));
         __syncthreads();
-    };
-#ifdef VIT_TIMING_HOOKS
-    const bool probe = (a.debug & 48) != 0;
-    if constexpr (wprobe) wp_.start();
-#else
-    constexpr bool probe = false;   // cycle probe: VIT_TIMING_HOOKS builds only; it writes the per-song scratch, never an output
-#endif
-    const unsigned long long clk0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
-    const unsigned long long rt0 = probe ? __builtin_amdgcn_s_memrealtime() : 0ull;
-    int t = 1;
-    for (; t + PF - 1 < Tb; t += PF) {
-#pragma unroll
-        for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
-    }
-#pragma unroll
-    for (int k = 0; k < PF - 1; ++k)
-        if (t + k < Tb) frame(t + k, er[k], k);
 
-    const int fb = (Tb - 1) & 1;                                          // buffer holding delta_{Tb-1}
-    terminal_argmax(tvalid ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, tvalid, tot, NWT, a.last_state, a.loglik, song);
-    if (probe && tid == 0) {  // timing experiments only: cycles (16) or 100 MHz ticks (32) per frame -> scratch slot 63
-        const unsigned long long d = (a.debug & 16) ? __builtin_amdgcn_s_memtime() - clk0 : __builtin_amdgcn_s_memrealtime() - rt0;
-        a.fmax[(size_t)song * 64 + 63] = (float)d / (float)(Tb > 1 ? Tb - 1 : 1);
-    }
+        // frame t = 1 + PF*n + u: delta buffers u & 1 (read) / (u & 1) ^ 1 (write); slot groups u % 4 read, (u + 1) % 4 written,
+        // (u + 2) % 4 reset (PF % 4 == 0: every index is a compile-time constant)
+        static_assert(PF % 2 == 0 && PF % kFmGroups == 0, "the unrolled frames must cycle through whole buffer and slot-group rounds");
 #ifdef VIT_TIMING_HOOKS
-    if constexpr (wprobe) wp_.finish(a.fmax + (size_t)song * 64, wv, lane, Tb - 1);
+        constexpr bool wprobe = WPR;   // per-wave probe (see WaveProbe): an instantiation of its own, the loop without it is the release loop
+        WaveProbe wp_;
 #endif
+        auto frame = [&](const int t, float& e_slot, const int u) {
+            const int RB = u & 1, WB = RB ^ 1;
+            const int GR = u % kFmGroups, GW = (u + 1) % kFmGroups, GZ = (u + 2) % kFmGroups;
+            // ---- everything this frame reads from LDS: the window, the extra columns, the frame-maximum slots
+            const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
+            float xd[NXL > 0 ? NXL : 1];
+            f32x4 fq[kFmSlots / 4];
+            // The small reads go out first and the first chunk of the window right behind them, and only then is M reduced: left to
+            // itself the compiler reduces M before it issues the window reads -- a full LDS round trip with nothing else in flight.
+            // (M reduced last instead lengthens the dependent tail after the last window read lands: measured slower.)
+            auto small_reads = [&]() {
+#pragma unroll
+                for (int k = 0; k < NXL; ++k) xd[k] = dls[4 + sh + RB * BUF + xcol[k]];
+#pragma unroll
+                for (int q = 0; q < kFmSlots / 4; ++q) fq[q] = reinterpret_cast<const f32x4*>(fmg + GR * kFmGroupFloats)[q];
+            };
+            // the window in chunks of 32 sources (8 reads): wide windows (W = 96, 128) must not hold all their data at once
+            float m0 = -INFINITY, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
+            float M = -INFINITY;
+            small_reads();
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int w0 = 0; w0 < W; w0 += 32) {
+            // W > 64: one chunk of reads in flight at a time (W register-resident weights leave no room for more; with
+            // twelve waves per workgroup the other waves of the SIMD cover the read latency)
+            if ((W > 64 || (W == 64 && NWT > 8)) && w0 > 0) asm volatile("" : "+v"(m0), "+v"(m1), "+v"(m2), "+v"(m3)::"memory");
+            f32x4 dw[8];
+#ifdef VIT_ABL_READS
+            // result-breaking ablation (make TIMING=1 ABL=n builds only): read n of every chunk's window quads, the others reuse them --
+            // what does the LDS return path cost a frame?
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (w0 + 4 * q < W) { if (q < VIT_ABL_READS) dw[q] = win[w0 / 4 + q]; else dw[q] = dw[q % VIT_ABL_READS]; }
+#else
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                if (w0 + 4 * q < W) dw[q] = win[w0 / 4 + q];
+#endif
+            if (w0 == 0) {
+                __builtin_amdgcn_sched_barrier(0);
+                // M = max of delta_{t-1} over the non-extra sources
+                M = fmaxf(fmaxf(fq[0].x, fq[0].y), fmaxf(fq[0].z, fq[0].w));
+#pragma unroll
+                for (int q = 1; q < kFmSlots / 4; ++q) M = fmaxf(fmaxf(fmaxf(M, fq[q].x), fq[q].y), fmaxf(fq[q].z, fq[q].w));
+                m0 = M + cj;
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int w = w0; w + 7 < W && w < w0 + 32; w += 8) {
+                const f32x4 da = dw[(w - w0) / 4], db = dw[(w - w0) / 4 + 1];
+                f32x4 wa, wb;
+                if (w < WR) {
+                    wa = f32x4{aw[w < WR ? w + 0 : 0], aw[w < WR ? w + 1 : 0], aw[w < WR ? w + 2 : 0], aw[w < WR ? w + 3 : 0]};
+                    wb = f32x4{aw[w < WR ? w + 4 : 0], aw[w < WR ? w + 5 : 0], aw[w < WR ? w + 6 : 0], aw[w < WR ? w + 7 : 0]};
+                } else {
+                    wa = awl[((w - WR) / 4) * NP + j];
+                    wb = awl[((w - WR) / 4 + 1) * NP + j];
+                }
+                f32x2 c0_ = f32x2{da.x, da.y} + f32x2{wa.x, wa.y};
+                f32x2 c1_ = f32x2{da.z, da.w} + f32x2{wa.z, wa.w};
+                f32x2 c2_ = f32x2{db.x, db.y} + f32x2{wb.x, wb.y};
+                f32x2 c3_ = f32x2{db.z, db.w} + f32x2{wb.z, wb.w};
+                // (W <= 32: all of a group's sums before its maxima.  Left alone, the compiler folds each sum into its chain at once,
+                // and a max3 right behind the packed add it reads needs an s_nop: eleven a frame.)
+                if (W <= 32) asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_));
+                m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
+                m1 = fmaxf(fmaxf(m1, c1_.x), c1_.y);
+                m2 = fmaxf(fmaxf(m2, c2_.x), c2_.y);
+                m3 = fmaxf(fmaxf(m3, c3_.x), c3_.y);
+            }
+            if (W % 8 == 4 && w0 + 32 >= W) {          // W = 84: the last four sources (one read, two packed adds)
+                static_assert(W % 8 != 4 || W <= WR, "an odd float4 count only with register-resident weights");
+                const f32x4 da = dw[((W - 4 - w0) / 4) & 7];
+                const f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[W - 4], aw[W - 3]};
+                const f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[W - 2], aw[W - 1]};
+                m2 = fmaxf(fmaxf(m2, c0_.x), c0_.y);
+                m3 = fmaxf(fmaxf(m3, c1_.x), c1_.y);
+            }
+            }
+#pragma unroll
+            for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
+            const float dn = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)) + e_slot;
+#ifdef VIT_TIMING_HOOKS
+            if constexpr (wprobe) wp_.before_publish(dn);
+#endif
+            produce(dn, WB, GW, GZ);
+            asm volatile("" ::: "memory");   // keep the global store / prefetch behind the frame-maximum publication: they fill
+                                             // the wait for the LDS write acknowledgement before the barrier (-2 %)
+            // Unconditional store + prefetch: exact in-order vmcnt accounting (see banded_forward_kernel).  Row bases are
+            // scalar index arithmetic on purpose: the SALU is idle, the VALU is not (running 64-bit per-lane pointers
+            // measured 3.5% slower).  Both are buffer instructions: a descriptor built on the SALU from the row base plus the lane's
+            // fixed 32-bit byte offset, no per-frame 64-bit address add on the VALU.
+            const int tn = t + PF < Tb ? t + PF : Tb - 1;
+            row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, is_fm ? M : dn);
+            e_slot = row_load_e<ET>(E + (size_t)tn * S, eoffb);
+#ifdef VIT_TIMING_HOOKS
+            if constexpr (wprobe) wp_.barrier(); else
+#endif
+            __syncthreads();
+        };
+#ifdef VIT_TIMING_HOOKS
+        const bool probe = !PK && (a.debug & 48) != 0;
+        if constexpr (wprobe) wp_.start();
+#else
+        constexpr bool probe = false;   // cycle probe: VIT_TIMING_HOOKS builds only; it writes the per-song scratch, never an output
+#endif
+        const unsigned long long clk0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
+        const unsigned long long rt0 = probe ? __builtin_amdgcn_s_memrealtime() : 0ull;
+        int t = 1;
+        for (; t + PF - 1 < Tb; t += PF) {
+#pragma unroll
+            for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
+        }
+#pragma unroll
+        for (int k = 0; k < PF - 1; ++k)
+            if (t + k < Tb) frame(t + k, er[k], k);
+
+        const int fb = (Tb - 1) & 1;                                          // buffer holding delta_{Tb-1}
+        if constexpr (PK) terminal_argmax_w(tvalid ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, tvalid, tot, NWT, wv, lane, a.last_state, a.loglik, song);
+        else terminal_argmax(tvalid ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, tvalid, tot, NWT, a.last_state, a.loglik, song);
+        if (probe && tid == 0) {  // timing experiments only: cycles (16) or 100 MHz ticks (32) per frame -> scratch slot 63
+            const unsigned long long d = (a.debug & 16) ? __builtin_amdgcn_s_memtime() - clk0 : __builtin_amdgcn_s_memrealtime() - rt0;
+            a.fmax[(size_t)song * 64 + 63] = (float)d / (float)(Tb > 1 ? Tb - 1 : 1);
+        }
+#ifdef VIT_TIMING_HOOKS
+        if constexpr (wprobe) wp_.finish(a.fmax + (size_t)song * 64, wv, lane, Tb - 1);
+#endif
+        if constexpr (!PK) {
+            break;
+        } else {
+            if (++si >= si_end) break;
+            take_song();
+            // every wave has read the last delta row (terminal_argmax) before both buffers and all slot groups go back to -inf,
+            // and no wave starts frame 0 of the next song before they have
+            __syncthreads();
+            for (int k = tid; k < 2 * BUF + kFmGroups * kFmGroupFloats; k += NWT * 64) dls[k] = -INFINITY;
+            __syncthreads();
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1093,6 +1137,52 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
     return hipGetLastError();
 }
 
+// The packed variant of the one-target floor kernel: one workgroup per slot (vit_decode_packed).  NXT and PF as above.  With
+// `per_cu` the launch is replaced by the occupancy query of that instantiation at its dynamic LDS size.
+template <int W, int NWT, typename ET>
+static hipError_t packed_floor_t(const FwdArgs& a, hipStream_t st, int* per_cu) {
+    constexpr int NP = NWT * 64;
+    constexpr int PF = W <= 32 ? 12 : 4;
+    const size_t ldsf = sizeof(float) * (8 * (NP + 16) + kFmGroups * kFmGroupFloats) + sizeof(VI) * 16 +
+                        ((W == 128 && NWT > 8) ? sizeof(f32x4) * 10 * NP : 0);      // (88 register-resident weights, 40 in LDS)
+    auto go = [&](auto kern) -> hipError_t {
+        if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, NWT * 64, ldsf);
+        hipLaunchKernelGGL(kern, dim3(a.n_slots), dim3(NWT * 64), ldsf, st, a);
+        return hipGetLastError();
+    };
+    if ((W == 32 || W >= 84) && a.n_extras == 1)
+        return go(banded_floor_forward_kernel<W, NWT, ((W == 32 || W >= 84) ? 1 : -1), PF, ET, false, true>);
+    return go(banded_floor_forward_kernel<W, NWT, -1, PF, ET, false, true>);
+}
+
+template <int W, typename ET>
+static hipError_t packed_floor_w(const FwdArgs& a, hipStream_t st, int* per_cu) {
+    const int nwt = banded_waves_for(a.S);
+    if (!floor_packed_applies(a.S, a.W, a.floor_ok != 0, a.n_dense)) return hipErrorInvalidConfiguration;
+    switch (nwt) {
+        case 2: return packed_floor_t<W, 2, ET>(a, st, per_cu);
+        case 4: return packed_floor_t<W, 4, ET>(a, st, per_cu);
+        case 6: return packed_floor_t<W, 6, ET>(a, st, per_cu);
+        case 8: return packed_floor_t<W, 8, ET>(a, st, per_cu);
+        case 12: return packed_floor_t<W, 12, ET>(a, st, per_cu);
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+
+template <typename ET>
+static hipError_t packed_floor_e(const FwdArgs& a, hipStream_t st, int* per_cu) {
+    static_assert(sizeof(kBandedWidths) / sizeof(int) == 6, "one case per instantiated window width");
+    switch (a.W) {
+        case 16: return packed_floor_w<16, ET>(a, st, per_cu);
+        case 32: return packed_floor_w<32, ET>(a, st, per_cu);
+        case 64: return packed_floor_w<64, ET>(a, st, per_cu);
+        case 84: return packed_floor_w<84, ET>(a, st, per_cu);
+        case 96: return packed_floor_w<96, ET>(a, st, per_cu);
+        case 128: return packed_floor_w<128, ET>(a, st, per_cu);
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+
 // general (scan) form
 template <int W, int NWT, typename ET>
 static hipError_t launch_scan_t(const FwdArgs& a, hipStream_t st) {
@@ -1156,6 +1246,15 @@ static hipError_t launch_banded_e(const FwdArgs& a, hipStream_t st) {
 
 hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st) {
     return f16 ? launch_banded_e<__half>(a, st) : launch_banded_e<float>(a, st);
+}
+
+hipError_t launch_banded_packed(const FwdArgs& a, bool f16, hipStream_t st) {
+    if (!a.offsets || !a.slot_begin || !a.slot_songs || a.n_slots < 1) return hipErrorInvalidValue;
+    return f16 ? packed_floor_e<__half>(a, st, nullptr) : packed_floor_e<float>(a, st, nullptr);
+}
+
+hipError_t banded_packed_resident(const FwdArgs& a, bool f16, int* per_cu) {
+    return f16 ? packed_floor_e<__half>(a, nullptr, per_cu) : packed_floor_e<float>(a, nullptr, per_cu);
 }
 
 hipError_t launch_scan_selftest(const float* vals, int n_waves, int mode, float* out_v, int32_t* out_i,

@@ -68,6 +68,7 @@ struct vit_plan {
     mutable void* pk_host = nullptr;
     mutable size_t pk_host_bytes = 0;
     mutable hipEvent_t pk_event = nullptr;
+    mutable int pk_resident[2] = {0, 0};   // workgroups per CU of the packed workgroup-form kernel (fp32 / fp16 emissions), 0 = not asked yet
     ~vit_plan() {
         if (pk_event) (void)hipEventDestroy(pk_event);
         if (pk_host) (void)hipHostFree(pk_host);
@@ -729,7 +730,22 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
 // form (backtrace_lane.hip): every song is cut into chunks of about equal length (total frames / resident LANES), one lane per
 // chunk -- the one-stream-per-wavefront kernels hold 16 streams per CU, fewer than a ragged batch of thousands of songs needs
 // (3250 songs: a second round of waves, 14 instead of 6 ms).
+// Plans without the wave form (the 722-state grids) run the same scheme with a WORKGROUP per slot: banded plans with the floor
+// form proven take banded_floor_forward_kernel<.., PK> and the lane back-trace over the workgroup history layout, step plans take
+// step4s_forward_kernel<.., PK> and the lazy back-trace over per-song chunk lists.  Slots: as many workgroups as are resident at once.
 namespace {
+
+// The forward family a packed decode of this plan runs (FwdStamp::family numbering), 0 = none: the ONE predicate behind
+// vit_workspace_bytes_packed and vit_decode_packed, so that a size > 0 implies a decode that launches.
+int pk_family(const vit_plan* p) {
+    if (p->bp.ok && p->bp.wave_ok) return 3;
+    if (p->bp.ok)      // banded, no wave form: the floor form and the lane back-trace (lane_backtrace_applies: width instantiated, W <= S)
+        return vit::floor_packed_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && p->bp.W <= p->S ? 2 : 0;
+    if (p->bp.step_ok && vit::step_kernel_instantiated(p->S, p->bp.step_bw, p->bp.step_kb)) return 1;
+    return 0;
+}
+// history row stride of that family
+int pk_hist_stride(const vit_plan* p, int family) { return family == 3 ? vit::wave_hist_stride(p->bp.wave_npl) : hist_stride(p->S); }
 
 struct PkLayout {
     int64_t n_slots, max_waves;
@@ -738,9 +754,11 @@ struct PkLayout {
 };
 inline int64_t pk_slots(const vit_plan* p, int64_t B) { const int64_t cap = 8 * (int64_t)p->n_cus; return B < cap ? B : cap; }
 inline int64_t pk_max_waves(const vit_plan* p, int64_t B) { return B + 16 * 64 * (int64_t)p->n_cus; }     // (song, chunk) streams of the back-trace: one per lane
-PkLayout pk_layout(const vit_plan* p, int64_t B, int64_t N) {
+// sd_floats: the history row stride of the form that runs.  n_slots is an upper bound here (it sizes slot_begin): the decode
+// lowers it to the workgroups resident at once (workgroup forms: a device query) and to total frames / longest song.
+PkLayout pk_layout(const vit_plan* p, int sd_floats, int64_t B, int64_t N) {
     PkLayout k;
-    const size_t sd = (size_t)vit::wave_hist_stride(p->bp.wave_npl) * sizeof(float);
+    const size_t sd = (size_t)sd_floats * sizeof(float);
     k.n_slots = pk_slots(p, B);
     k.max_waves = pk_max_waves(p, B);
     k.off_hist = 0;
@@ -761,8 +779,10 @@ PkLayout pk_layout(const vit_plan* p, int64_t B, int64_t N) {
 }  // namespace
 
 size_t vit_workspace_bytes_packed(const vit_plan* plan, int64_t B, int64_t total_frames) {
-    if (!plan || B < 0 || total_frames < 0 || !(plan->bp.ok && plan->bp.wave_ok)) return 0;
-    return pk_layout(plan, B, total_frames).bytes;
+    if (!plan || B < 0 || total_frames < 0) return 0;
+    const int family = pk_family(plan);
+    if (family == 0) return 0;
+    return pk_layout(plan, pk_hist_stride(plan, family), B, total_frames).bytes;
 }
 
 int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
@@ -772,7 +792,8 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     if (!plan->dev_image) return VIT_ENOTUPLOADED;
     if (((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
     if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
-    if (!(plan->bp.ok && plan->bp.wave_ok)) return VIT_EUNSUPPORTED;
+    const int family = pk_family(plan);
+    if (family == 0) return VIT_EUNSUPPORTED;
     if (offsets[0] != 0) return VIT_EINVAL;
     for (int64_t b = 0; b < B; ++b) {
         const int64_t tb = offsets[b + 1] - offsets[b];
@@ -781,8 +802,27 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     const int64_t N = offsets[B];
     if (B == 0) return VIT_OK;
     if (!logE || !states) return VIT_EINVAL;
-    PkLayout k = pk_layout(plan, B, N);
+    PkLayout k = pk_layout(plan, pk_hist_stride(plan, family), B, N);
     if (workspace_bytes < k.bytes) return VIT_EWORKSPACE;
+    const bool f16 = emis_dtype == VIT_F16;
+    vit::FwdArgs a{};
+    fwd_args_from_plan(plan, a);
+    if (family != 3) {   // workgroup forms: one slot per workgroup that is resident at once (the occupancy of that instantiation x CUs)
+        int per_cu;
+        {
+            std::lock_guard<std::mutex> g(plan->mu);
+            per_cu = plan->pk_resident[f16 ? 1 : 0];
+        }
+        if (per_cu < 1) {
+            hipError_t eq = family == 2 ? vit::banded_packed_resident(a, f16, &per_cu) : vit::step_packed_resident(a, f16, &per_cu);
+            if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: pk_family asked the same predicates)
+            if (eq != hipSuccess) return hip_fail(eq);
+            if (per_cu < 1) return VIT_EUNSUPPORTED;
+            std::lock_guard<std::mutex> g(plan->mu);
+            plan->pk_resident[f16 ? 1 : 0] = per_cu;
+        }
+        k.n_slots = std::min<int64_t>(k.n_slots, (int64_t)per_cu * plan->n_cus);
+    }
     {   // fewer slots than songs when the batch is short of frames: a slot's load should not fall below the longest song, which bounds
         // the launch anyway (1623 songs of 7500..30000 frames: 1024 slots of ~30000 frames, one wave per SIMD, instead of 1623 waves
         // of which the longest share their SIMDs to the end)
@@ -843,16 +883,20 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
         for (int32_t sng : order) h_slot_songs[fill[(size_t)slot_of[(size_t)sng]]++] = sng;     // a slot walks its songs longest first
         // back-trace streams (one per lane: backtrace_lane.hip): chunks of about (total frames / resident lanes) frames, never shorter
         // than four warm-ups, at most kLaneMaxChunks per song
-        const int64_t resident = 16 * 64 * (int64_t)plan->n_cus;
+        // (step plans, lazy back-trace: one WAVE per chunk -- about eight waves per CU, chunks no shorter than the 8 * kBtWarm frames
+        // of backtrace_chunks, at most kBtMaxChunks per song)
+        const bool lazy = family == 1;
+        const int64_t resident = lazy ? 8 * (int64_t)plan->n_cus : 16 * 64 * (int64_t)plan->n_cus;
+        const int64_t cmax = lazy ? vit::kBtMaxChunks : vit::kLaneMaxChunks;
         int64_t cf = (N + resident - 1) / resident, tmax = 0;
         for (int64_t b = 0; b < B; ++b) tmax = std::max<int64_t>(tmax, offsets[b + 1] - offsets[b]);
-        cf = std::max<int64_t>(cf, 4 * vit::kBtWarmSparse);
-        cf = std::max<int64_t>(cf, (tmax + vit::kLaneMaxChunks - 1) / vit::kLaneMaxChunks);
+        cf = std::max<int64_t>(cf, lazy ? 8 * vit::kBtWarm : 4 * vit::kBtWarmSparse);
+        cf = std::max<int64_t>(cf, (tmax + cmax - 1) / cmax);
         int64_t w = 0;
         for (int64_t b = 0; b < B; ++b) {
             const int64_t tb = offsets[b + 1] - offsets[b];
-            int64_t c = (tb + cf / 2) / cf;
-            c = c < 1 ? 1 : (c > vit::kLaneMaxChunks ? vit::kLaneMaxChunks : c);
+            int64_t c = lazy ? tb / cf : (tb + cf / 2) / cf;      // (lazy: rounded down, no chunk shorter than cf)
+            c = c < 1 ? 1 : (c > cmax ? cmax : c);
             h_chunk_base[b] = (int32_t)w;
             for (int64_t q = 0; q < c; ++q) h_wave_song[w + q] = (int32_t)b;
             w += c;
@@ -871,9 +915,7 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     e = hipMemsetAsync(ws + k.off_cnt, 0, k.off_last - k.off_cnt, st);
     if (e != hipSuccess) return hip_fail(e);
 
-    // ---- forward: one wave per slot
-    vit::FwdArgs a{};
-    fwd_args_from_plan(plan, a);
+    // ---- forward: one wave (wave form) or one workgroup per slot
     a.logE = logE;
     a.lengths = nullptr;
     a.hist = reinterpret_cast<float*>(ws + k.off_hist);
@@ -889,18 +931,27 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     a.n_slots = (int)k.n_slots;
     a.slot_begin = reinterpret_cast<const int32_t*>(ws + k.off_slot_begin);
     a.slot_songs = reinterpret_cast<const int32_t*>(ws + k.off_slot_songs);
-    e = vit::launch_wave(a, emis_dtype == VIT_F16, st);
+    e = family == 3 ? vit::launch_wave(a, f16, st) : (family == 2 ? vit::launch_banded_packed(a, f16, st) : vit::launch_step_packed(a, f16, st));
     if (e != hipSuccess) return hip_fail(e);
 
-    // ---- back-trace: one wave per (song, chunk)
+    // ---- back-trace: one lane (banded plans) or one wave (step plans) per (song, chunk)
     vit::BtArgs b{};
     bt_args_from_plan(plan, b);
-    b.SD = vit::wave_hist_stride(plan->bp.wave_npl);
-    b.col0 = b.SD - plan->S;
-    b.mcol = 0;
-    b.xcol0 = 1;
-    b.aux_frames = (a.wave_flags & 4) ? 1 : vit::wave_aux_frames(plan->bp.wave_npl, plan->S, b.n_extras);
-    b.have_fmax = 1;
+    if (family == 3) {
+        b.SD = vit::wave_hist_stride(plan->bp.wave_npl);
+        b.col0 = b.SD - plan->S;
+        b.mcol = 0;
+        b.xcol0 = 1;
+        b.aux_frames = (a.wave_flags & 4) ? 1 : vit::wave_aux_frames(plan->bp.wave_npl, plan->S, b.n_extras);
+        b.have_fmax = 1;
+    } else {             // the workgroup kernels' rows: state i in column i, the frame maximum (banded) in pad column S
+        b.SD = a.SD;
+        b.col0 = 0;
+        b.mcol = plan->S;
+        b.xcol0 = -1;
+        b.aux_frames = 1;
+        b.have_fmax = family == 2 ? 1 : 0;
+    }
     b.hist = reinterpret_cast<const float*>(ws + k.off_hist);
     b.hist_rows = 0;
     b.last_state = reinterpret_cast<const int32_t*>(ws + k.off_last);
@@ -917,6 +968,12 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     b.chunk_base = reinterpret_cast<const int32_t*>(ws + k.off_chunk_base);
     b.n_waves = n_waves;
     b.chunks = (int)max_chunks;
+    if (family == 1) {
+        b.warm = plan->tune.bt_warm >= 0 ? plan->tune.bt_warm : vit::kBtWarm;
+        b.bt_form = 1;
+        e = vit::launch_backtrace_rows_packed(b, st);
+        return e == hipSuccess ? VIT_OK : hip_fail(e);
+    }
     b.warm = plan->tune.bt_warm >= 0 ? plan->tune.bt_warm : vit::kBtWarmSparse;
     b.bt_form = 4;
     if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;

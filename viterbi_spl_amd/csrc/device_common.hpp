@@ -166,4 +166,22 @@ __device__ __forceinline__ void terminal_argmax(float dj, int j, bool valid, VI*
     }
 }
 
+// The same for callers that hold their wave index in a scalar register (`wave`, wave-uniform) and their lane: the slot of `tot` is
+// scalar arithmetic, and no per-thread address has to stay in a vector register up to the call (kernels that call it once per
+// song of a list with every register spoken for).
+__device__ __forceinline__ void terminal_argmax_w(float dj, int j, bool valid, VI* tot, int nw, int wave, int lane, int32_t* last_state,
+                                                  float* loglik, int song) {
+    VI x{valid ? dj : -INFINITY, valid ? j : kBig};
+    x = wave_scan<false>(x);
+    if (lane == 63) tot[wave] = x;
+    __syncthreads();
+    if (wave == 0 && lane == 0) {
+        VI acc = vi_identity();
+        for (int b = 0; b < nw; ++b) acc = op_fwd(acc, tot[b]);
+        if (acc.i == kBig) acc.i = 0;
+        last_state[song] = acc.i;
+        if (loglik) loglik[song] = acc.v;
+    }
+}
+
 }  // namespace vit

@@ -27,6 +27,12 @@ constexpr int banded_target_waves(int S, int W) {
     const int nwt = banded_waves_for(S);
     return scan_form_instantiated(W, nwt) ? nwt : 0;
 }
+// packed variant of the one-target floor kernel (banded_floor_forward_kernel<.., PK = true>, vit_decode_packed for plans without
+// the wave form): every instantiated (W, NWT) pair of the floor form; idle slot S stores the frame maximum, so S < 64 * NWT
+constexpr bool floor_packed_applies(int S, int W, bool floor_ok, int n_dense) {
+    const int nwt = banded_waves_for(S);
+    return floor_ok && n_dense == 0 && nwt > 0 && S < nwt * 64 && banded_width_instantiated(W) && floor_form_instantiated(W, nwt);
+}
 // step-structured kernel (plan.step_ok): instantiated for the Durrieu geometry -- 20-bin bands, 9 near bands, 705..768 voiced states
 constexpr bool step_kernel_instantiated(int S, int bw, int kb) { return bw == 20 && kb == 9 && S - 1 > 704 && S - 1 <= 768; }
 // the dense kernel keeps NS running (best, arg) pairs per thread
@@ -70,8 +76,9 @@ struct FwdArgs {
     int ckpt_every, t_begin, t_end;
     const float* init_rows;
     int64_t init_stride;    // floats from one song's init row to the next
-    // packed batch (vit_decode_packed; wave form): emission rows of song b are rows offsets[b] .. offsets[b+1]-1 of logE, its history rows
-    // sit at the same offsets; wave w (slot w < n_slots) decodes songs slot_songs[slot_begin[w] .. slot_begin[w+1]) back to back
+    // packed batch (vit_decode_packed): emission rows of song b are rows offsets[b] .. offsets[b+1]-1 of logE, its history rows sit at
+    // the same offsets; slot w < n_slots (a wave of the wave form, a workgroup of the packed floor / step kernels) decodes songs
+    // slot_songs[slot_begin[w] .. slot_begin[w+1]) back to back
     const int64_t* offsets; // device [B+1], or null
     int n_slots;
     const int32_t* slot_begin;   // device [n_slots + 1]
@@ -121,6 +128,7 @@ struct BtArgs {
     // packed batch (vit_decode_packed): history rows / states of song b at offsets[b] (its length: offsets[b+1] - offsets[b]); the
     // speculative pass runs one wave per entry of wave_song (song b owns waves chunk_base[b] .. chunk_base[b+1]-1 = its chunks;
     // chunk entries are indexed the same way)
+    // (lane form and, for plans that are not banded, the lazy kernel of backtrace_rows.hip: launch_backtrace_rows_packed)
     const int64_t* offsets; // device [B+1], or null
     const int32_t* wave_song;    // device [n_waves]
     const int32_t* chunk_base;   // device [B+1]
@@ -132,6 +140,12 @@ hipError_t launch_dense(const FwdArgs& a, int songs_per_group, bool f16, hipStre
 hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_wave(const FwdArgs& a, bool f16, hipStream_t st);   // wave.hip: one song per wavefront
+// packed decode of plans without the wave form: one workgroup per slot (a.n_slots, a.offsets, a.slot_begin, a.slot_songs).
+// *_packed_resident: workgroups of that instantiation one compute unit holds at once (the occupancy query at its LDS size).
+hipError_t launch_banded_packed(const FwdArgs& a, bool f16, hipStream_t st);
+hipError_t banded_packed_resident(const FwdArgs& a, bool f16, int* per_cu);
+hipError_t launch_step_packed(const FwdArgs& a, bool f16, hipStream_t st);
+hipError_t step_packed_resident(const FwdArgs& a, bool f16, int* per_cu);
 // per song, for the segment [s0, e0) of a checkpointed decode: the sub-problem's length (0: the song ends before s0) and the state
 // its back-trace starts from (the state already decided at frame e0, or the song's terminal state)
 hipError_t launch_segment_prep(const int64_t* lengths, int64_t B, int T, int s0, int e0, const int32_t* states, const int32_t* last,
@@ -144,6 +158,8 @@ constexpr int wave_aux_frames(int npl, int S, int n_extras) { return n_extras ==
 // the row the back-trace takes the scalars of frame t from: the next row with t % 3 == 2, or the last row written
 __host__ __device__ constexpr int wave_aux_row(int t, int last) { return t - t % 3 + 2 < last ? t - t % 3 + 2 : last; }
 hipError_t launch_backtrace(BtArgs a, hipStream_t st);
+// the lazy kernel over a packed batch: one wave per entry of wave_song, then one wave per song (a.chunks = the largest per-song count)
+hipError_t launch_backtrace_rows_packed(BtArgs a, hipStream_t st);
 // backtrace_sparse.hip: fetches only the span of each history row around the path (banded plans, candidates on one lane)
 bool sparse_backtrace_applies(const BtArgs& a);
 // phases: bit 0 the speculative pass (one wave per (song, chunk)), bit 1 the verify-and-repair pass (one wave per song)

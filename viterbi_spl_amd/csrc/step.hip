@@ -292,7 +292,11 @@ __global__ void __launch_bounds__(256) step4_forward_kernel(FwdArgs a) {
 // delta_t.  Two waves per SIMD issue alternately (2 cycles per instruction), each half moves half the bytes through the LDS
 // store path, and with a barrier on either side of the reads V needs no second buffer: 60 KB of LDS instead of 112.
 // ---------------------------------------------------------------------------------------
-template <int BW, int KB, int PF, typename ET>
+// PK = true is the packed variant (vit_decode_packed): the workgroup is a slot and decodes the songs
+// slot_songs[slot_begin[w] .. slot_begin[w+1]) back to back, rows of a song at offsets[song] of the packed buffers.  The band
+// tables c[] and rown[] stay in registers; V, F, dl, X, wm and dun go back to -inf between two songs, behind a barrier.
+// PK = false compiles to the code it was before the parameter existed.
+template <int BW, int KB, int PF, typename ET, bool PK = false>
 __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     static_assert(BW == 20 && KB == 9 && PF % 2 == 0, "written for nine 20-bin bands");
     extern __shared__ __align__(16) unsigned char smem[];
@@ -319,11 +323,26 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = wv < 3 ? 0 : (wv < 6 ? 1 : 2);                        // 2: the unvoiced state's wave
     const int ql = tid - NQL * (half == 1 ? 1 : 0);                       // lane within the half (halves 0, 1)
-    const int song = blockIdx.x;
-    const int Tb = song_length(a.lengths, song, T);
-    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
-    float* __restrict__ hist = a.hist + (size_t)song * T * SD;
+    // the song being decoded: the workgroup's own, or (PK) the slot's songs one after the other
+    int song = blockIdx.x;
+    int Tb = PK ? 1 : song_length(a.lengths, song, T);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PK ? (size_t)0 : (size_t)song * T * S);
+    float* __restrict__ hist = a.hist + (PK ? (size_t)0 : (size_t)song * T * SD);
     const float* __restrict__ lpi = reinterpret_cast<const float*>(a.image + a.off_logpi);
+    int si = 0, si_end = 1;                                               // (PK) position in slot_songs, end of the slot's list
+    auto take_song = [&]() {                                              // (PK) wave-uniform: scalar loads
+        song = a.slot_songs[si];
+        const long long r0 = a.offsets[song];
+        Tb = (int)(a.offsets[song + 1] - r0);
+        E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
+        hist = a.hist + (size_t)r0 * SD;
+    };
+    if constexpr (PK) {
+        si = a.slot_begin[blockIdx.x];
+        si_end = a.slot_begin[blockIdx.x + 1];
+        if (si >= si_end) return;                                         // an empty slot (the host makes none)
+        take_song();
+    }
 
     for (int k = tid; k < KB * VLEN + KB * FLEN + DLEN + 8 * NQL + 8; k += 448) V[k] = -INFINITY;
     __syncthreads();
@@ -395,7 +414,7 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     for (int k = 0; k < PF; ++k) er[k] = load4(1 + k < Tb ? 1 + k : Tb - 1);
 
 #ifdef VIT_TIMING_HOOKS
-    const bool prof = (a.debug & 256) != 0;      // phase stamps: publish | barrier | reads | exchange + store -> scratch[song][4*wave ..]
+    const bool prof = !PK && (a.debug & 256) != 0;      // phase stamps: publish | barrier | reads | exchange + store -> scratch[song][4*wave ..]
 #else
     constexpr bool prof = false;
 #endif
@@ -526,44 +545,88 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
             ph0 += s1 - s0; ph1 += s2 - s1; ph2 += s3 - s2; ph3 += s4 - s3;
         }
     };
-    int t = 1;
-    for (; t + PF - 1 < Tb; t += PF) {
+    // ---------------- one pass per song (PK: the songs of the slot, back to back)
+    for (;;) {
+        int t = 1;
+        for (; t + PF - 1 < Tb; t += PF) {
 #pragma unroll
-        for (int k = 0; k < PF; ++k) frame(t + k, er[k]);
-    }
-#pragma unroll
-    for (int k = 0; k < PF - 1; ++k)
-        if (t + k < Tb) frame(t + k, er[k]);
-    if (prof && lane == 0 && Tb > 1) {
-        float* o = a.fmax + (size_t)song * 64 + 4 * wv;
-        const float nf = (float)(Tb - 1);
-        o[0] = (float)ph0 / nf; o[1] = (float)ph1 / nf; o[2] = (float)ph2 / nf; o[3] = (float)ph3 / nf;
-    }
-
-    // terminal state: lowest-index argmax over half A's lanes (four adjacent states each) and the unvoiced state
-    __syncthreads();
-    {
-        VI x = vi_identity();
-        if (half == 0) {
-            if (val[0]) x = VI{dn.x, j0};
-            if (val[1]) x = op_fwd(x, VI{dn.y, j0 + 1});
-            if (val[2]) x = op_fwd(x, VI{dn.z, j0 + 2});
-            if (val[3]) x = op_fwd(x, VI{dn.w, j0 + 3});
-        } else if (half == 2 && lane == 0) {
-            x = VI{dn.x, n};
+            for (int k = 0; k < PF; ++k) frame(t + k, er[k]);
         }
-        x = wave_scan<false>(x);
-        if (lane == 63) tot[wv] = x;
+#pragma unroll
+        for (int k = 0; k < PF - 1; ++k)
+            if (t + k < Tb) frame(t + k, er[k]);
+        if (prof && lane == 0 && Tb > 1) {
+            float* o = a.fmax + (size_t)song * 64 + 4 * wv;
+            const float nf = (float)(Tb - 1);
+            o[0] = (float)ph0 / nf; o[1] = (float)ph1 / nf; o[2] = (float)ph2 / nf; o[3] = (float)ph3 / nf;
+        }
+
+        // terminal state: lowest-index argmax over half A's lanes (four adjacent states each) and the unvoiced state
         __syncthreads();
-        if (tid == 0) {
-            VI acc = vi_identity();
-            for (int bq = 0; bq < 7; ++bq) acc = op_fwd(acc, tot[bq]);
-            if (acc.i == kBig) acc.i = 0;
-            a.last_state[song] = acc.i;
-            if (a.loglik) a.loglik[song] = acc.v;
+        {
+            VI x = vi_identity();
+            if (half == 0) {
+                if (val[0]) x = VI{dn.x, j0};
+                if (val[1]) x = op_fwd(x, VI{dn.y, j0 + 1});
+                if (val[2]) x = op_fwd(x, VI{dn.z, j0 + 2});
+                if (val[3]) x = op_fwd(x, VI{dn.w, j0 + 3});
+            } else if (half == 2 && lane == 0) {
+                x = VI{dn.x, n};
+            }
+            x = wave_scan<false>(x);
+            if (lane == 63) tot[wv] = x;
+            __syncthreads();
+            if (tid == 0) {
+                VI acc = vi_identity();
+                for (int bq = 0; bq < 7; ++bq) acc = op_fwd(acc, tot[bq]);
+                if (acc.i == kBig) acc.i = 0;
+                a.last_state[song] = acc.i;
+                if (a.loglik) a.loglik[song] = acc.v;
+            }
+        }
+        if constexpr (!PK) {
+            break;
+        } else {
+            if (++si >= si_end) break;
+            take_song();
+            // every wave is past its last read of the song before V, F, dl, X, wm and dun go back to -inf, and none publishes
+            // frame 0 of the next song before they have
+            __syncthreads();
+            for (int k = tid; k < KB * VLEN + KB * FLEN + DLEN + 8 * NQL + 8; k += 448) V[k] = -INFINITY;
+            __syncthreads();
+            {                                                             // frame 0 and the first PF emission rows, as above
+                const f32x4 e0 = load4(0);
+                int cq[4] = {col[0], col[1], col[2], col[3]};             // (opaque: the prior's addresses are formed here, per song)
+                asm volatile("" : "+v"(cq[0]), "+v"(cq[1]), "+v"(cq[2]), "+v"(cq[3]));
+                dn = mask4(f32x4{lpi[cq[0]], lpi[cq[1]], lpi[cq[2]], lpi[cq[3]]} + e0);
+                store4(0, dn);
+            }
+#pragma unroll
+            for (int k = 0; k < PF; ++k) er[k] = load4(1 + k < Tb ? 1 + k : Tb - 1);
         }
     }
 }
+
+// packed variant of step4s_forward_kernel: one workgroup per slot; with `per_cu` the occupancy query instead of the launch
+static hipError_t step_packed(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu) {
+    constexpr int BW = 20, KB = 9, PF = 2;
+    if (!step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) return hipErrorInvalidConfiguration;
+    constexpr int VL4 = 768 + 2 * (KB * BW + BW);
+    const size_t ldss = sizeof(float) * (KB * VL4 + KB * (VL4 / 4) + (768 + 64) + 8 * 192 + 8) + sizeof(VI) * 16;
+    auto go = [&](auto kern) -> hipError_t {
+        if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, 448, ldss);
+        hipLaunchKernelGGL(kern, dim3(a.n_slots), dim3(448), ldss, st, a);
+        return hipGetLastError();
+    };
+    return f16 ? go(step4s_forward_kernel<BW, KB, PF, __half, true>) : go(step4s_forward_kernel<BW, KB, PF, float, true>);
+}
+
+hipError_t launch_step_packed(const FwdArgs& a, bool f16, hipStream_t st) {
+    if (!a.offsets || !a.slot_begin || !a.slot_songs || a.n_slots < 1) return hipErrorInvalidValue;
+    return step_packed(a, f16, st, nullptr);
+}
+
+hipError_t step_packed_resident(const FwdArgs& a, bool f16, int* per_cu) { return step_packed(a, f16, nullptr, per_cu); }
 
 hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st) {
     constexpr int BW = 20, KB = 9, PF = 2;

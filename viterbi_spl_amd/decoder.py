@@ -331,7 +331,9 @@ class ViterbiDecoder:
         """Decode B recordings of different lengths without padding (``vit_decode_packed``): ``emission_logits`` is
         ``[sum T_b, S]`` (the rows of recording b are ``offsets[b] : offsets[b+1]``), ``offsets`` a host sequence of B + 1
         frame offsets starting at 0.  Returns ``(states [sum T_b], loglik [B])``, packed like the input -- what the reference
-        computes recording by recording (tonet/for_paper.py:2304-2309).  Plans with the wave form only."""
+        computes recording by recording (tonet/for_paper.py:2304-2309).  For plans with the wave form (S = 321 / 361), banded
+        plans whose floor form is proven (the 722-state jdc grids, one workgroup per forward slot) and step-structured plans (the
+        Durrieu matrix); any other plan (unstructured matrices, banded plans with only the scan form) raises ``ViterbiHipError``."""
         lib = _lib.load()
         if not isinstance(emission_logits, torch.Tensor) or emission_logits.device != self.device:
             raise ValueError("emission_logits must be a torch tensor on the decoder's device")
@@ -352,7 +354,8 @@ class ViterbiDecoder:
         if B > 0:
             need = int(lib.vit_workspace_bytes_packed(self._plan, B, N))
             if need == 0:
-                raise _lib.ViterbiHipError("the packed decode needs a plan with the wave form")
+                raise _lib.ViterbiHipError("the packed decode needs a plan with the wave form, the floor form or the step form "
+                                           "(unstructured matrices and scan-only banded plans: pad and use decode(lengths=))")
             ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
             if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
                 raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
@@ -367,6 +370,8 @@ class ViterbiDecoder:
         return states, loglik
 
     def workspace_bytes_packed(self, B: int, total_frames: int) -> int:
+        """Workspace bytes of ``decode_packed`` for B recordings of ``total_frames`` frames together; 0 when the plan has none of
+        the forms the packed decode runs (see ``decode_packed``)."""
         return int(_lib.load().vit_workspace_bytes_packed(self._plan, int(B), int(total_frames)))
 
     def voicing(self, states: torch.Tensor, n_bins: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
