@@ -193,11 +193,22 @@ int vit_forward_family(const vit_plan *plan, int64_t B, int algo);
  * delta rows per song instead of T (the reference keeps its work buffers T1 / T2 for one song at a time,
  * tonet/for_paper.py:1852-1853; vit_decode keeps a history for the whole batch).  Pass 1 runs the forward recursion and keeps
  * one row per segment of segment_frames frames; pass 2 re-runs it segment by segment from the last to the first and
- * back-traces each.  Exact by construction; about twice the forward work.  Plans with the wave form only (vit_plan_info
- * reserved[2] bit 3; VIT_EUNSUPPORTED otherwise); 64 <= segment_frames (values above T act like T).  Of the plan's options
- * only "bt_fast_rows" and "wave_two" are honoured: the passes run the general wave kernel with a full history of the segment
- * and the sparse back-trace ("wave_history", "wave_uniform", "backtrace_form", "bt_chunks" are ignored).  The library does
- * not record this call for vit_backtrace().
+ * back-traces each.  Exact by construction; about twice the forward work.  64 <= segment_frames <= 2^24 (values above T act
+ * like T; out of range: VIT_EINVAL, size 0).  Three kinds of plan are served, whatever VIT_ALGO_* a normal decode would take:
+ *   - plans with the wave form (vit_plan_info reserved[2] bit 3): the general wave kernel with a full history of the segment and
+ *     the sparse back-trace.  Honoured options: "bt_fast_rows", "wave_two"; ignored: "wave_history", "wave_uniform",
+ *     "backtrace_form", "bt_chunks", "bt_warm".
+ *   - banded plans without the wave form whose floor form is proven (reserved[1]) and that have no dense rows (the 722-state jdc
+ *     grids): one song per workgroup, always the one-target floor kernel, and the sparse back-trace over its rows (the lane form
+ *     where the sparse one does not apply).  Window widths >= 64 or more than 384 states.
+ *   - step-structured plans (reserved[2] bit 2, the Durrieu matrix): the step kernel with the bands split over two waves, and
+ *     the generic back-trace with the chunk count taken from the segment length.
+ *   For the last two, honoured: "bt_fast_rows", "bt_warm", "win_shift"; ignored: "forward_form", "step_form", "backtrace_form",
+ *   "bt_chunks".
+ * Every other plan (unstructured matrices, banded plans with only the scan form or with dense rows) gets size 0 and
+ * VIT_EUNSUPPORTED, before anything is enqueued.  The workspace holds per song T / segment_frames checkpoint rows and
+ * segment_frames + 1 rows (wave form; 64 * ceil(S / 64) floats each) or segment_frames + 2 rows (the other two; ceil((S + 2) / 4) * 4
+ * floats each) of the segment being walked.  The library does not record this call for vit_backtrace().
  */
 size_t vit_workspace_bytes_checkpointed(const vit_plan *plan, int64_t B, int64_t T, int64_t segment_frames);
 int vit_decode_checkpointed(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B, int64_t T,

@@ -1,6 +1,7 @@
 """Randomised parity run (test infrastructure; run on the GPU box): random state counts, band half-widths, matrix families,
 batch shapes, ragged lengths, emission kinds and storage types; every kernel family the plan allows and both back-trace forms, the wave
-form's half history, the checkpointed decode, the lane form of the back-trace (chunk counts up to 256) and the packed decode against the C
+form's half history, the checkpointed decode (wave-form plans and the workgroup-form plans of the 722-state grids, random segment
+lengths), the lane form of the back-trace (chunk counts up to 256) and the packed decode against the C
 restatement in oracle/.  argv: seconds to run (default 240), seed (default 1)."""
 import os
 import sys
@@ -17,11 +18,16 @@ from viterbi_spl_amd import ViterbiDecoder, synth  # noqa: E402
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 240.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 dev = torch.device("cuda:0")
+GOLDEN_722 = ["jdc722", "jdc721", "imm722w", "durrieu722", "durrieu721"]      # the reference's 722-state grids (tests/golden/params.npz)
 GEN = {"peaks": synth.emissions_peaks, "dense": synth.emissions_dense, "ties": synth.emissions_ties, "scaled": synth.emissions_scaled}
 
 
 def random_matrix():
-    fam = rng.choice(["band", "band", "band", "band_novoice", "dense", "durrieu", "band_edit"])
+    fam = rng.choice(["band", "band", "band", "band_novoice", "dense", "durrieu", "band_edit", "golden722"])
+    if fam == "golden722":
+        name = str(rng.choice(GOLDEN_722))
+        params = np.load(os.path.join(ROOT, "tests", "golden", "params.npz"))
+        return name, np.ascontiguousarray(params[f"{name}_logA_T"], np.float32), np.ascontiguousarray(params[f"{name}_log_pi"], np.float32)
     if fam == "durrieu":
         n = int(rng.choice([705, 721, 740, 767]))
         A = synth.durrieu_transition(n, 20)
@@ -77,6 +83,8 @@ while time.time() - t0 < budget:
                 forms += [("group", 4)]           # one (song, chunk) stream per lane
             if dec.info["wave_ok"]:
                 forms += [("wave", 0), ("wave", 2), ("wave", 4), ("wave-half", 0), ("checkpointed", 0), ("packed", 0)]
+        if not dec.info["wave_ok"] and dec.workspace_bytes_checkpointed_or_zero(B, T, 64) > 0:
+            forms += [("checkpointed", 0), ("checkpointed", 4)]      # workgroup-form plans: floor form or step form (backtrace_form is ignored)
         if S <= 400 or rng.random() < 0.3:
             forms += [("dense", 0)]
         chunks = int(rng.choice([0, 0, 2, 7, 32]))

@@ -286,8 +286,13 @@ constexpr int kBtWaves = 4;
 // PK: packed batch (vit_decode_packed for plans the lane form does not serve).  MODE 0 runs one wave per entry of wave_song; song b
 // owns the waves and the chunk entries chunk_base[b] .. chunk_base[b+1]-1, so its chunk count grows with its length; its history
 // rows and states sit at row offsets[b] of the packed buffers and there are no frames past its end to fill.
-template <int NWT, int MODE, bool PK = false>
+// SG: one segment of a checkpointed decode (vit_decode_checkpointed for step plans), in both passes what the sparse and lane kernels
+// do: the song's history rows start at row song * hist_rows (the segment buffer), its states at song * states_stride (the segment's
+// first frame within the whole song's row), and a song whose lengths[] entry is < 1 (skip_nonpositive: the segment does not reach it)
+// is skipped, not clamped to one frame.  PK = SG = false compiles to the code it was before the parameters existed.
+template <int NWT, int MODE, bool PK = false, bool SG = false>
 __global__ void __launch_bounds__(kBtWaves * 64) lazy_backtrace_kernel(BtArgs a) {
+    static_assert(!(PK && SG), "a segment is a segment of a padded batch");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int EPL = NWT;               // sources per lane, strided: i = e*64 + lane
     const int S = a.S, SP = a.SP, SD = a.SD, T = a.T, W = a.W, K = a.K;
@@ -333,11 +338,14 @@ __global__ void __launch_bounds__(kBtWaves * 64) lazy_backtrace_kernel(BtArgs a)
     const int cbase = PK ? a.chunk_base[song] : 0;
     const int C = PK ? a.chunk_base[song + 1] - cbase : a.chunks;
     const int chunk = MODE == 0 ? (PK ? gw - cbase : gw % C) : 0;
+    if constexpr (SG) {
+        if (a.skip_nonpositive && a.lengths[song] < 1) return;          // segment of a checkpointed decode this song does not reach
+    }
     const long long row0 = PK ? a.offsets[song] : (long long)song * T;  // first history row / state of the song
     const int Tb = PK ? (int)(a.offsets[song + 1] - row0) : song_length(a.lengths, song, T);
     const int Tpad = PK ? Tb : T;                       // frames past the song's end are filled with -1 up to here
-    int32_t* __restrict__ states = a.states + (size_t)row0;
-    const float* __restrict__ hist = a.hist + (size_t)row0 * SD;
+    int32_t* __restrict__ states = a.states + (SG ? (size_t)song * (size_t)a.states_stride : (size_t)row0);
+    const float* __restrict__ hist = a.hist + (SG ? (size_t)song * (size_t)a.hist_rows : (size_t)row0) * SD;
     int32_t* __restrict__ entry = a.entry + (PK ? (size_t)cbase : (size_t)song * C);   // [C] of this song
     const float* __restrict__ Arow = reinterpret_cast<const float*>(a.image + a.off_Arow);
     float* tile = reinterpret_cast<float*>(tiles + wv * kBtVec * 64);
@@ -656,6 +664,26 @@ hipError_t launch_backtrace_rows_packed(BtArgs a, hipStream_t st) {
     if (e != hipSuccess || a.chunks <= 1) return e;
     if (nwt <= 12) hipLaunchKernelGGL((lazy_backtrace_kernel<12, 1, true>), g1, blk, lds, st, a);
     else hipLaunchKernelGGL((lazy_backtrace_kernel<16, 1, true>), g1, blk, lds, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_backtrace_rows_segment(BtArgs a, hipStream_t st) {
+    if (!a.lengths || a.offsets || a.hist_rows < a.T || a.chunks < 1 || a.chunks > kBtMaxChunks) return hipErrorInvalidValue;
+    if (a.banded) return hipErrorInvalidConfiguration;         // (banded plans take the sparse or the lane form)
+    a.K = backtrace_tile_rows(a.SD);
+    a.have_fmax = 0;
+    size_t lds = sizeof(f32x4) * kBtWaves * kBtVec * 64 + sizeof(int32_t) * kBtWaves * 64;
+    if (a.step_ok) lds += sizeof(float) * (a.step_kb + 1) * a.SP;
+    const int nwt = (a.S + 63) / 64;
+    const long long waves0 = (long long)a.B * a.chunks;
+    const dim3 g0((unsigned)((waves0 + kBtWaves - 1) / kBtWaves)), g1((unsigned)((a.B + kBtWaves - 1) / kBtWaves)), blk(kBtWaves * 64);
+    if (nwt > 16) return hipErrorInvalidConfiguration;
+    if (nwt <= 12) hipLaunchKernelGGL((lazy_backtrace_kernel<12, 0, false, true>), g0, blk, lds, st, a);
+    else hipLaunchKernelGGL((lazy_backtrace_kernel<16, 0, false, true>), g0, blk, lds, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || a.chunks <= 1) return e;
+    if (nwt <= 12) hipLaunchKernelGGL((lazy_backtrace_kernel<12, 1, false, true>), g1, blk, lds, st, a);
+    else hipLaunchKernelGGL((lazy_backtrace_kernel<16, 1, false, true>), g1, blk, lds, st, a);
     return hipGetLastError();
 }
 

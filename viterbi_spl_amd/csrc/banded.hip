@@ -371,9 +371,22 @@ struct WaveProbe {
 // the LDS-resident weights are loaded once; between two songs both delta buffers and every slot group go back to -inf behind
 // a barrier.  The history layout is the unpacked one (the frame maximum of row t in pad column S of row t), so a song
 // writes its own rows only.  PK = false compiles to the code it was before the parameter existed.
-template <int W, int NWT, int NXT, int PF, typename ET, bool WPR = false, bool PK = false>
+// CK = true is the checkpoint / resume variant (vit_decode_checkpointed, plans without the wave form), driven by the FwdArgs fields
+// the wave form uses:
+//   pass 1 (ckpt_every = K > 0): every frame of the song; frame mK - 1 goes to row m - 1 of the song's hist_rows rows, every other
+//     frame to its last row (scratch).  The store stays unconditional, only its row base is selected (on the SALU).  The frame maximum
+//     is not kept (lane S writes it into pad column S + 1 of the row being stored, which nothing reads): a resumed segment re-forms
+//     it from the delta values.
+//   segment (ckpt_every = 0): frames t_begin .. min(length, t_end + 1) - 1 -- one frame past the segment where the song goes on, so
+//     that M of the segment's last row is stored too.  t_begin > 0 publishes init_rows[song] = delta_{t_begin - 1} instead of
+//     log_pi + e_0; row t is stored at t - t_begin.  Lane S stores M of frame t - 1 into row t - 1 - t_begin: for the first frame
+//     that is the row IN FRONT of a.hist, which the caller must own (the segment buffer starts one row before a.hist).  A workgroup
+//     whose song ended before t_begin leaves without writing; the terminal state is pass 1's business.
+// CK = false compiles to the code it was before the parameter existed.
+template <int W, int NWT, int NXT, int PF, typename ET, bool WPR = false, bool PK = false, bool CK = false>
 __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs a) {
     static_assert(!(PK && WPR), "the per-wave probe exists for the unpacked kernel only");
+    static_assert(!(CK && (PK || WPR)), "the checkpoint / resume variant is a variant of the plain unpacked kernel");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NP = NWT * 64;
     constexpr int DC = NP + 16;                   // copy stride (see banded_forward_kernel)
@@ -383,8 +396,8 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     VI* tot = reinterpret_cast<VI*>(fmg + kFmGroups * kFmGroupFloats);
     // W = 128 with twelve waves (S > 512) leaves 168 registers per thread: the last 32 window weights then live in LDS
     // ([8][NP] float4-interleaved, read with conflict-free 16-byte reads next to the delta window)
-    // (PK: 88 -- the song loop keeps a few more values alive, and 168 registers leave nothing to spill into)
-    constexpr int WR = (W == 128 && NWT > 8) ? (PK ? 88 : 96) : W;     // register-resident window weights
+    // (PK, CK: 88 -- the song loop / the row selection keep a few more values alive, and 168 registers leave nothing to spill into)
+    constexpr int WR = (W == 128 && NWT > 8) ? ((PK || CK) ? 88 : 96) : W;     // register-resident window weights
     f32x4* awl = reinterpret_cast<f32x4*>(tot + 16);       // [(W - WR) / 4][NP]
     const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
     constexpr bool GEN = NXT < 0;
@@ -398,7 +411,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     int song = blockIdx.x;
     int Tb = PK ? 1 : song_length(a.lengths, song, T);
     const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PK ? (size_t)0 : (size_t)song * T * S);
-    float* __restrict__ hist = a.hist + (PK ? (size_t)0 : (size_t)song * T * SD);
+    float* __restrict__ hist = a.hist + (PK ? (size_t)0 : (CK ? (size_t)song * (size_t)a.hist_rows * SD : (size_t)song * T * SD));
     int si = 0, si_end = 1;                                               // (PK) position in slot_songs, end of the slot's list
     auto take_song = [&]() {                                              // (PK) wave-uniform: scalar loads
         song = a.slot_songs[si];
@@ -413,6 +426,17 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         if (si >= si_end) return;                                         // an empty slot (the host makes none)
         take_song();
     }
+    // (CK) first frame of this launch, first frame the loop computes, pass 1's segment length and its row bookkeeping (all wave-uniform)
+    [[maybe_unused]] const int t0 = CK ? a.t_begin : 0;
+    [[maybe_unused]] const int t1 = CK && t0 > 0 ? t0 : 1;
+    [[maybe_unused]] const int ck_every = CK ? a.ckpt_every : 0;
+    [[maybe_unused]] const int ck_scratch = CK ? (int)a.hist_rows - 1 : 0;
+    [[maybe_unused]] int ck_next = ck_every - 1, ck_row = 0;              // the next frame that is a checkpoint, and its row
+    if constexpr (CK) {
+        const int stop = ck_every > 0 || a.t_end >= T ? T : a.t_end + 1;
+        Tb = Tb < stop ? Tb : stop;
+        if (Tb <= t0) return;                                             // (segments: the song ended before this one)
+    }
 
     // ---------------- per-lane constants.  Idle lanes (j >= S) carry -inf tables: their delta stays -inf.
     const int j = tid;
@@ -421,7 +445,8 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     const int jld = tvalid ? j : S - 1;                                   // emission column an idle lane (harmlessly) loads
     // history store of frame t, relative to row t-1: own column of row t | lane S: M into pad column S of row t-1
     // | other idle lanes: pad column S+1 of row t (never read)
-    const unsigned hoff = tvalid ? (unsigned)(SD + j) : (j == S ? (unsigned)S : (unsigned)(SD + S + 1));
+    // (CK, pass 1: lane S joins the other idle lanes -- the row before the one being stored is not this frame's to write)
+    const unsigned hoff = tvalid ? (unsigned)(SD + j) : ((j == S && !(CK && ck_every > 0)) ? (unsigned)S : (unsigned)(SD + S + 1));
     const bool is_fm = j == S;
     const unsigned hoffb = 4u * hoff, eoffb = (unsigned)(sizeof(ET) * jld);   // per-lane byte offsets from the frame's row bases
     const int lo = reinterpret_cast<const int32_t*>(a.image + a.off_lo)[jc];
@@ -484,7 +509,16 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         if constexpr (PK) asm volatile("" : "+v"(jf));
         const bool tvf = PK ? jf < S : tvalid;
         const int jldf = PK ? (tvf ? jf : S - 1) : jld;
-        {
+        if constexpr (CK) {         // frame 0 (pass 1: into the scratch row), or the checkpoint row in front of this segment
+            float d0 = -INFINITY;
+            if (t0 > 0) {
+                if (tvf) d0 = a.init_rows[(size_t)song * a.init_stride + jf];
+            } else if (tvf) {
+                d0 = reinterpret_cast<const float*>(a.image + a.off_logpi)[jf] + load_e<ET>(E + jf);
+                hist[(size_t)(ck_every > 0 ? ck_scratch : 0) * SD + jf] = d0;
+            }
+            produce(d0, 0, 0, 1);
+        } else {
             const float d0 = tvf ? reinterpret_cast<const float*>(a.image + a.off_logpi)[jf] + load_e<ET>(E + jf) : -INFINITY;
             if (tvf) hist[jf] = d0;
             produce(d0, 0, 0, 1);   // (group 1 is still -inf)
@@ -493,7 +527,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         // and the s_waitcnt before a frame's "+ e" must not be what paces the recursion.
         float er[PF];
 #pragma unroll
-        for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S + jldf);
+        for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)((CK ? t1 : 1) + k < Tb ? (CK ? t1 : 1) + k : Tb - 1) * S + jldf);
 #pragma unroll
         for (int w = 0; w < WR; ++w) asm volatile("" ::"v"(aw[w]));
 #pragma unroll
@@ -601,7 +635,20 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
             // measured 3.5% slower).  Both are buffer instructions: a descriptor built on the SALU from the row base plus the lane's
             // fixed 32-bit byte offset, no per-frame 64-bit address add on the VALU.
             const int tn = t + PF < Tb ? t + PF : Tb - 1;
-            row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, is_fm ? M : dn);
+            if constexpr (CK) {
+                // the row in front of the one this frame's delta goes to (the lanes' offsets are relative to row t - 1): a segment
+                // stores frame t at t - t0, pass 1 at the next checkpoint row or the scratch row.  Scalar selects, the store as ever.
+                long long rb = (long long)t - 1 - t0;
+                if (ck_every > 0) {
+                    const bool hit = t == ck_next;
+                    rb = (hit ? ck_row : ck_scratch) - 1;
+                    ck_next += hit ? ck_every : 0;
+                    ck_row += hit ? 1 : 0;
+                }
+                row_store_f32(hist + rb * SD, hoffb, is_fm ? M : dn);
+            } else {
+                row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, is_fm ? M : dn);
+            }
             e_slot = row_load_e<ET>(E + (size_t)tn * S, eoffb);
 #ifdef VIT_TIMING_HOOKS
             if constexpr (wprobe) wp_.barrier(); else
@@ -609,14 +656,14 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
             __syncthreads();
         };
 #ifdef VIT_TIMING_HOOKS
-        const bool probe = !PK && (a.debug & 48) != 0;
+        const bool probe = !PK && !CK && (a.debug & 48) != 0;
         if constexpr (wprobe) wp_.start();
 #else
         constexpr bool probe = false;   // cycle probe: VIT_TIMING_HOOKS builds only; it writes the per-song scratch, never an output
 #endif
         const unsigned long long clk0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
         const unsigned long long rt0 = probe ? __builtin_amdgcn_s_memrealtime() : 0ull;
-        int t = 1;
+        int t = CK ? t1 : 1;
         for (; t + PF - 1 < Tb; t += PF) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
@@ -625,7 +672,10 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         for (int k = 0; k < PF - 1; ++k)
             if (t + k < Tb) frame(t + k, er[k], k);
 
-        const int fb = (Tb - 1) & 1;                                          // buffer holding delta_{Tb-1}
+        const int fb = (Tb - (CK ? t1 : 1)) & 1;                              // buffer holding delta_{Tb-1}
+        if constexpr (CK) {         // the terminal state and the log-likelihood come from pass 1 (uniform test: every thread reaches the barrier inside)
+            if (ck_every > 0) terminal_argmax(tvalid ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, tvalid, tot, NWT, a.last_state, a.loglik, song);
+        } else
         if constexpr (PK) terminal_argmax_w(tvalid ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, tvalid, tot, NWT, wv, lane, a.last_state, a.loglik, song);
         else terminal_argmax(tvalid ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, tvalid, tot, NWT, a.last_state, a.loglik, song);
         if (probe && tid == 0) {  // timing experiments only: cycles (16) or 100 MHz ticks (32) per frame -> scratch slot 63
@@ -1155,6 +1205,48 @@ static hipError_t packed_floor_t(const FwdArgs& a, hipStream_t st, int* per_cu) 
     return go(banded_floor_forward_kernel<W, NWT, -1, PF, ET, false, true>);
 }
 
+// The checkpoint / resume variant of the one-target floor kernel (vit_decode_checkpointed): one workgroup per song.
+template <int W, int NWT, typename ET>
+static hipError_t ckpt_floor_t(const FwdArgs& a, hipStream_t st) {
+    constexpr int NP = NWT * 64;
+    constexpr int PF = W <= 32 ? 12 : 4;
+    const size_t ldsf = sizeof(float) * (8 * (NP + 16) + kFmGroups * kFmGroupFloats) + sizeof(VI) * 16 +
+                        ((W == 128 && NWT > 8) ? sizeof(f32x4) * 10 * NP : 0);      // (88 register-resident weights, 40 in LDS)
+    if ((W == 32 || W >= 84) && a.n_extras == 1)
+        hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, ((W == 32 || W >= 84) ? 1 : -1), PF, ET, false, false, true>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
+    else
+        hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, -1, PF, ET, false, false, true>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
+    return hipGetLastError();
+}
+
+template <int W, typename ET>
+static hipError_t ckpt_floor_w(const FwdArgs& a, hipStream_t st) {
+    if (!floor_ckpt_applies(a.S, a.W, a.floor_ok != 0, a.n_dense)) return hipErrorInvalidConfiguration;
+    switch (banded_waves_for(a.S)) {
+        case 2: if constexpr (floor_ckpt_pair(W, 2)) return ckpt_floor_t<W, 2, ET>(a, st); break;
+        case 4: if constexpr (floor_ckpt_pair(W, 4)) return ckpt_floor_t<W, 4, ET>(a, st); break;
+        case 6: if constexpr (floor_ckpt_pair(W, 6)) return ckpt_floor_t<W, 6, ET>(a, st); break;
+        case 8: if constexpr (floor_ckpt_pair(W, 8)) return ckpt_floor_t<W, 8, ET>(a, st); break;
+        case 12: if constexpr (floor_ckpt_pair(W, 12)) return ckpt_floor_t<W, 12, ET>(a, st); break;
+        default: break;
+    }
+    return hipErrorInvalidConfiguration;
+}
+
+template <typename ET>
+static hipError_t ckpt_floor_e(const FwdArgs& a, hipStream_t st) {
+    static_assert(sizeof(kBandedWidths) / sizeof(int) == 6, "one case per instantiated window width");
+    switch (a.W) {
+        case 16: return ckpt_floor_w<16, ET>(a, st);
+        case 32: return ckpt_floor_w<32, ET>(a, st);
+        case 64: return ckpt_floor_w<64, ET>(a, st);
+        case 84: return ckpt_floor_w<84, ET>(a, st);
+        case 96: return ckpt_floor_w<96, ET>(a, st);
+        case 128: return ckpt_floor_w<128, ET>(a, st);
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+
 template <int W, typename ET>
 static hipError_t packed_floor_w(const FwdArgs& a, hipStream_t st, int* per_cu) {
     const int nwt = banded_waves_for(a.S);
@@ -1251,6 +1343,11 @@ hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st) {
 hipError_t launch_banded_packed(const FwdArgs& a, bool f16, hipStream_t st) {
     if (!a.offsets || !a.slot_begin || !a.slot_songs || a.n_slots < 1) return hipErrorInvalidValue;
     return f16 ? packed_floor_e<__half>(a, st, nullptr) : packed_floor_e<float>(a, st, nullptr);
+}
+
+hipError_t launch_banded_ckpt(const FwdArgs& a, bool f16, hipStream_t st) {
+    if (a.offsets || a.hist_rows < 1 || (a.t_begin > 0 && !a.init_rows) || (a.ckpt_every > 0 && a.t_begin > 0)) return hipErrorInvalidValue;
+    return f16 ? ckpt_floor_e<__half>(a, st) : ckpt_floor_e<float>(a, st);
 }
 
 hipError_t banded_packed_resident(const FwdArgs& a, bool f16, int* per_cu) {

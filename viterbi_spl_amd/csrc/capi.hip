@@ -18,6 +18,9 @@
 // Kernel-selection overrides (vit_plan_set_option).  Every combination decodes the same bits; they exist so that tests and
 // timing scripts can reach each kernel form.  `timing` carries the ablation / probe mask of a -DVIT_TIMING_HOOKS build and
 // is refused by a release build (those bits DO change results).
+// vit_decode_checkpointed of a plan without the wave form always runs the one-target floor kernel / the two-wave step kernel and picks
+// its back-trace from the plan: it does not consult forward_form, step_form, backtrace_form or bt_chunks (bt_fast_rows, bt_warm and
+// win_shift it does).
 struct Tuning {
     int forward_form = 0;      // banded plans: 0 by batch size | 1 one target per lane | 2 two targets per lane | 3 scan form | 6 split windows
                                //               | 4 wave form (one song per wavefront) | 5 never the wave form
@@ -594,40 +597,80 @@ int vit_decode(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Bounded-workspace decode (wave-form plans).  The reference keeps T1 / T2 for ONE song (tonet/for_paper.py:1852-1853); the
-// batched decode above keeps a delta history for the whole batch (46 MB per song at T = 30000).  Here the history never
-// exists at once: pass 1 runs the forward recursion over all T frames and keeps one delta row per segment of K frames (the row
-// in front of the segment) plus the terminal state; pass 2 walks the segments from the last to the first, re-runs the
-// forward kernel over one segment from its checkpoint row into a K-row buffer and back-traces it from the state the segment
-// behind it decided at its first frame.  Exact by construction (the same kernels, the same sums); twice the forward work.
+// Bounded-workspace decode.  The reference keeps T1 / T2 for ONE song (tonet/for_paper.py:1852-1853); the
+// batched decode above keeps a delta history for the whole batch (46 MB per song at T = 30000, 87 MB with 722 states).  Here the
+// history never exists at once: pass 1 runs the forward recursion over all T frames and keeps one delta row per segment of K frames
+// (the row in front of the segment) plus the terminal state; pass 2 walks the segments from the last to the first, re-runs the
+// forward kernel over one segment from its checkpoint row into a buffer of about K rows and back-traces it from the state the
+// segment behind it decided at its first frame.  Exact by construction (the same kernels, the same sums); twice the forward work.
+// Three families (ck_family): plans with the wave form (wave.hip HM 5 / 6, the sparse back-trace); banded plans without it whose
+// floor form is proven (banded_floor_forward_kernel<.., CK>, the sparse back-trace over the workgroup layout, or the lane form);
+// step plans (step4s_forward_kernel<.., CK>, the lazy back-trace).  The workgroup families always run that one kernel:
+// forward_form, step_form, backtrace_form and bt_chunks are not consulted; bt_fast_rows, bt_warm and win_shift are.
 namespace {
 
+// the sparse back-trace serves the history layout a checkpointed decode of this plan writes (family 3: the wave layout, 2: workgroup rows)
+bool ck_sparse_applies(const vit_plan* p, int family) {
+    vit::BtArgs b{};
+    b.S = p->S;
+    b.SP = p->L.SP;
+    b.SD = family == 3 ? vit::wave_hist_stride(p->bp.wave_npl) : hist_stride(p->S);
+    b.col0 = family == 3 ? b.SD - p->S : 0;
+    b.W = p->bp.W;
+    b.banded = 1;
+    b.have_fmax = 1;
+    b.n_extras = p->bp.n_extras;
+    b.n_dense = p->bp.n_dense;
+    return vit::sparse_backtrace_applies(b);
+}
+// the lane back-trace does (lane_backtrace_applies for the workgroup rows: width instantiated, W <= S, no dense rows)
+bool ck_lane_applies(const vit_plan* p) { return p->bp.n_dense == 0 && vit::banded_width_instantiated(p->bp.W) && p->bp.W <= p->S; }
+
+// The forward family a checkpointed decode of this plan runs (FwdStamp::family numbering), 0 = none: the ONE predicate behind
+// vit_workspace_bytes_checkpointed and vit_decode_checkpointed, so that a size > 0 implies a decode that launches.
+int ck_family(const vit_plan* p) {
+    if (p->bp.ok && p->bp.wave_ok) return ck_sparse_applies(p, 3) ? 3 : 0;
+    if (p->bp.ok)      // banded, no wave form: the floor form (no dense rows) and a back-trace over its rows
+        return vit::floor_ckpt_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && (ck_sparse_applies(p, 2) || ck_lane_applies(p)) ? 2 : 0;
+    if (p->bp.step_ok && vit::step_kernel_instantiated(p->S, p->bp.step_bw, p->bp.step_kb)) return 1;
+    return 0;
+}
+inline bool ck_segment_ok(int64_t K) { return K >= 64 && K <= (int64_t)1 << 24; }
+
 struct CkLayout {
-    int64_t nseg;
-    size_t off_ckpt, off_seg, off_cnt, off_last, off_entry, off_slen, off_slast, bytes;
+    int64_t nseg, seg_rows;
+    size_t off_ckpt, off_seg, off_cnt, off_mask, off_last, off_entry, off_slen, off_slast, bytes;
 };
-CkLayout ck_layout(const vit_plan* p, int64_t B, int64_t T, int64_t K) {
+// Family 3 keeps the byte counts it had when it was the only one.  Families 1 and 2: rows of hist_stride(S) floats; the segment
+// buffer holds K + 2 rows per song -- one in FRONT of the segment (the banded kernel stores the frame maximum of frame t - 1 into row
+// t - 1 while it computes frame t: for a resumed segment's first frame that is the checkpoint's place) and one behind it (the
+// forward pass runs one frame past the segment where the song goes on, for the frame maximum of its last row).  Family 2 may
+// back-trace with the lane form: its chunk flags and kLaneMaxChunks entries per song.
+CkLayout ck_layout(const vit_plan* p, int family, int64_t B, int64_t T, int64_t K) {
     CkLayout c;
     K = K > T ? T : K;                                                           // (a segment longer than the songs: one segment of T frames)
-    const size_t sd = (size_t)vit::wave_hist_stride(p->bp.wave_npl) * sizeof(float);
+    const size_t sd = (size_t)(family == 3 ? vit::wave_hist_stride(p->bp.wave_npl) : hist_stride(p->S)) * sizeof(float);
     c.nseg = (T + K - 1) / K;
+    c.seg_rows = family == 3 ? K + 1 : K + 2;
     c.off_ckpt = 0;                                                              // [B][nseg] rows: nseg - 1 checkpoints + the scratch row
-    c.off_seg = align256((size_t)B * (size_t)c.nseg * sd);                       // [B][K + 1] rows of the segment being walked
-    c.off_cnt = c.off_seg + align256((size_t)B * (size_t)(K + 1) * sd);
-    c.off_last = c.off_cnt + align256((size_t)B * 64 * sizeof(float));
+    c.off_seg = align256((size_t)B * (size_t)c.nseg * sd);                       // [B][seg_rows] rows of the segment being walked
+    c.off_cnt = c.off_seg + align256((size_t)B * (size_t)c.seg_rows * sd);
+    c.off_mask = c.off_cnt + align256((size_t)B * 64 * sizeof(float));           // (counters; timing builds: the forward kernels' scratch)
+    c.off_last = c.off_mask + (family == 2 ? align256((size_t)B * vit::kLaneMaskWords * sizeof(uint32_t)) : 0);
     c.off_entry = c.off_last + align256((size_t)B * sizeof(int32_t));
-    c.off_slen = c.off_entry + align256((size_t)B * vit::kBtMaxChunks * sizeof(int32_t));
+    c.off_slen = c.off_entry + align256((size_t)B * (family == 2 ? vit::kLaneMaxChunks : vit::kBtMaxChunks) * sizeof(int32_t));
     c.off_slast = c.off_slen + align256((size_t)B * sizeof(int64_t));
     c.bytes = c.off_slast + align256((size_t)B * sizeof(int32_t));
     return c;
 }
-bool ck_supported(const vit_plan* p, int64_t K) { return p->bp.ok && p->bp.wave_ok && K >= 64 && K <= (int64_t)1 << 24; }
 
 }  // namespace
 
 size_t vit_workspace_bytes_checkpointed(const vit_plan* plan, int64_t B, int64_t T, int64_t segment_frames) {
-    if (!plan || B < 0 || T < 1 || !ck_supported(plan, segment_frames)) return 0;
-    return ck_layout(plan, B, T, segment_frames).bytes;
+    if (!plan || B < 0 || T < 1 || !ck_segment_ok(segment_frames)) return 0;
+    const int family = ck_family(plan);
+    if (family == 0) return 0;
+    return ck_layout(plan, family, B, T, segment_frames).bytes;
 }
 
 int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T, const int64_t* lengths,
@@ -637,16 +680,23 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
     if (rc != VIT_OK) return rc;
     if (!logE || !states) return VIT_EINVAL;
     if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
-    if (!ck_supported(plan, segment_frames)) return segment_frames < 64 || segment_frames > (int64_t)1 << 24 ? VIT_EINVAL : VIT_EUNSUPPORTED;
+    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
+    const int family = ck_family(plan);             // (everything that can refuse the plan is asked here, before anything is enqueued)
+    if (family == 0) return VIT_EUNSUPPORTED;
     const int64_t K = segment_frames > T ? T : segment_frames;
-    const CkLayout c = ck_layout(plan, B, T, K);
+    const CkLayout c = ck_layout(plan, family, B, T, K);
     if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
     if (B == 0) return VIT_OK;
     stamp_erase(plan, workspace);
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
     const bool f16 = emis_dtype == VIT_F16;
-    const int SDW = vit::wave_hist_stride(plan->bp.wave_npl);
+    const Tuning& tn = plan->tune;
+    const int SDH = family == 3 ? vit::wave_hist_stride(plan->bp.wave_npl) : hist_stride(plan->S);    // row stride of the family's history layout
+    const bool lane_bt = family == 2 && !ck_sparse_applies(plan, 2);
+    auto forward = [&](const vit::FwdArgs& f) {
+        return family == 3 ? vit::launch_wave(f, f16, st) : (family == 2 ? vit::launch_banded_ckpt(f, f16, st) : vit::launch_step_ckpt(f, f16, st));
+    };
     hipError_t e;
     if (lengths) {     // frames past a song's end: -1 (segments a song does not reach are skipped, not written)
         e = hipMemsetAsync(states, 0xff, (size_t)B * (size_t)T * sizeof(int32_t), st);
@@ -658,7 +708,7 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
 
     // ---- pass 1: checkpoint rows + terminal state
     vit::FwdArgs a{};
-    fwd_args_from_plan(plan, a);
+    fwd_args_from_plan(plan, a);          // (a.SD: the workgroup kernels' row stride; the wave kernel has its own)
     a.logE = logE;
     a.lengths = lengths;
     a.hist = reinterpret_cast<float*>(ws + c.off_ckpt);
@@ -671,20 +721,28 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
     a.ckpt_every = (int)K;
     a.t_begin = 0;
     a.t_end = (int)T;
-    e = vit::launch_wave(a, f16, st);
+    e = forward(a);
     if (e != hipSuccess) return hip_fail(e);
 
     // ---- pass 2: segments, last to first
     vit::BtArgs b{};
     bt_args_from_plan(plan, b);
-    b.SD = SDW;
-    b.col0 = SDW - plan->S;
-    b.mcol = 0;
-    b.xcol0 = 1;
-    b.aux_frames = 1;       // (a segment's sub-problem ends one frame behind the rows its forward pass wrote: every frame's scalars from its own row)
-    b.have_fmax = 1;
-    b.hist = reinterpret_cast<const float*>(ws + c.off_seg);
-    b.hist_rows = K + 1;
+    b.SD = SDH;
+    if (family == 3) {
+        b.col0 = SDH - plan->S;
+        b.mcol = 0;
+        b.xcol0 = 1;
+    } else {                // the workgroup kernels' rows: state i in column i, the frame maximum (banded) in pad column S
+        b.col0 = 0;
+        b.mcol = plan->S;
+        b.xcol0 = -1;
+    }
+    b.aux_frames = 1;       // (a segment's sub-problem ends one frame behind the rows it decides from: every frame's scalars from its own row)
+    b.have_fmax = family == 1 ? 0 : 1;
+    // families 1, 2: the segment's row 0 is the buffer's second row (ck_layout)
+    float* seg = reinterpret_cast<float*>(ws + c.off_seg) + (family == 3 ? 0 : SDH);
+    b.hist = seg;
+    b.hist_rows = c.seg_rows;
     b.last_state = reinterpret_cast<const int32_t*>(ws + c.off_slast);
     b.lengths = reinterpret_cast<const int64_t*>(ws + c.off_slen);
     b.entry = reinterpret_cast<int32_t*>(ws + c.off_entry);
@@ -692,29 +750,44 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
     b.states_stride = T;
     b.skip_nonpositive = 1;
     b.counters = counters;
-    b.bt_form = 0;
-    if (!vit::sparse_backtrace_applies(b)) return VIT_EUNSUPPORTED;
+    b.mask = family == 2 ? reinterpret_cast<uint32_t*>(ws + c.off_mask) : nullptr;
+    b.bt_form = family == 1 ? 1 : (lane_bt ? 4 : 0);
+    if (lane_bt && !vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;      // (cannot happen: ck_family asked the same predicates)
     for (int64_t sgm = c.nseg - 1; sgm >= 0; --sgm) {
         const int64_t s0 = sgm * K, e0 = s0 + K < T ? s0 + K : T;
         vit::FwdArgs f = a;
         f.ckpt_every = 0;
-        f.hist = reinterpret_cast<float*>(ws + c.off_seg);
-        f.hist_rows = K + 1;
+        f.hist = seg;
+        f.hist_rows = c.seg_rows;
         f.loglik = nullptr;
         f.t_begin = (int)s0;
         f.t_end = (int)e0;
-        f.init_rows = sgm > 0 ? reinterpret_cast<const float*>(ws + c.off_ckpt) + (size_t)(sgm - 1) * SDW : nullptr;
-        f.init_stride = (int64_t)c.nseg * SDW;
-        e = vit::launch_wave(f, f16, st);
+        f.init_rows = sgm > 0 ? reinterpret_cast<const float*>(ws + c.off_ckpt) + (size_t)(sgm - 1) * SDH : nullptr;
+        f.init_stride = (int64_t)c.nseg * SDH;
+        e = forward(f);
         if (e != hipSuccess) return hip_fail(e);
         e = vit::launch_segment_prep(lengths, B, (int)T, (int)s0, (int)e0, states, reinterpret_cast<const int32_t*>(ws + c.off_last),
                                      reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast), st);
         if (e != hipSuccess) return hip_fail(e);
         b.T = (int)(e0 < T ? e0 - s0 + 1 : e0 - s0);      // the frame behind the segment is the sub-problem's terminal frame
         b.states = states + s0;
-        b.chunks = vit::sparse_backtrace_chunks(B, b.T, plan->n_cus);
-        b.warm = vit::kBtWarmSparse;
-        e = vit::launch_backtrace_sparse(b, st);
+        if (family == 1) {              // step plans: the lazy kernel, one wave per (song, chunk)
+            b.chunks = vit::backtrace_chunks(B, b.T);
+            b.warm = tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarm;
+            e = vit::launch_backtrace_rows_segment(b, st);
+        } else if (lane_bt) {
+            b.warm = tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarmSparse;
+            b.chunks = vit::lane_backtrace_chunks(B, b.T, plan->n_cus, b.warm);
+            if (b.chunks > 1) {         // the chunk flags of this segment
+                e = hipMemsetAsync(ws + c.off_mask, 0, (size_t)B * vit::kLaneMaskWords * sizeof(uint32_t), st);
+                if (e != hipSuccess) return hip_fail(e);
+            }
+            e = vit::launch_backtrace_lane(b, st);
+        } else {
+            b.chunks = vit::sparse_backtrace_chunks(B, b.T, plan->n_cus);
+            b.warm = family == 3 || tn.bt_warm < 0 ? vit::kBtWarmSparse : tn.bt_warm;
+            e = vit::launch_backtrace_sparse(b, st);
+        }
         if (e != hipSuccess) return hip_fail(e);
     }
     return VIT_OK;

@@ -33,6 +33,13 @@ constexpr bool floor_packed_applies(int S, int W, bool floor_ok, int n_dense) {
     const int nwt = banded_waves_for(S);
     return floor_ok && n_dense == 0 && nwt > 0 && S < nwt * 64 && banded_width_instantiated(W) && floor_form_instantiated(W, nwt);
 }
+// checkpoint / resume variant of the same kernel (banded_floor_forward_kernel<.., CK = true>, vit_decode_checkpointed for plans without
+// the wave form): the packed variant's pairs but the narrow windows on few waves (W <= 32, S <= 384) -- plans that narrow take the
+// wave form, but for the odd one with three extra columns or S = 64 * npl, and banded.hip is the longest compile as it is
+constexpr bool floor_ckpt_pair(int W, int nwt) { return W >= 64 || nwt >= 8; }
+constexpr bool floor_ckpt_applies(int S, int W, bool floor_ok, int n_dense) {
+    return floor_packed_applies(S, W, floor_ok, n_dense) && floor_ckpt_pair(W, banded_waves_for(S));
+}
 // step-structured kernel (plan.step_ok): instantiated for the Durrieu geometry -- 20-bin bands, 9 near bands, 705..768 voiced states
 constexpr bool step_kernel_instantiated(int S, int bw, int kb) { return bw == 20 && kb == 9 && S - 1 > 704 && S - 1 <= 768; }
 // the dense kernel keeps NS running (best, arg) pairs per thread
@@ -71,8 +78,9 @@ struct FwdArgs {
     int wave_flags;         // bit 0: force the 256-register (two waves per SIMD) instantiation, bit 1: the 512-register one up to 1024 songs
     int hist_half;          // wave form: 1 = only the delta rows of even frames are stored (wave.hip, HM 1)
     int64_t hist_rows;      // history rows per song: T, or (T + 1) / 2 with hist_half; checkpoint pass: segments + 1
-    // wave form, vit_decode_checkpointed: ckpt_every > 0 = pass 1 (checkpoint rows only, wave.hip HM 5); t_begin > 0 / t_end < T = a
-    // segment resumed from init_rows [B][64 * npl] (row t stored at t - t_begin)
+    // vit_decode_checkpointed: ckpt_every > 0 = pass 1 (checkpoint rows only; wave.hip HM 5, the CK variants of the floor and step
+    // kernels); t_begin > 0 / t_end < T = a segment resumed from init_rows (one row per song in the history layout of the form that
+    // runs; row t stored at t - t_begin)
     int ckpt_every, t_begin, t_end;
     const float* init_rows;
     int64_t init_stride;    // floats from one song's init row to the next
@@ -123,7 +131,8 @@ struct BtArgs {
     int64_t states_stride;  // states of song b start at states + b * states_stride (T; a segment of a checkpointed decode: the whole song's T)
     int block_waves;        // half back-trace: waves per workgroup (0 / 16 default | 8 | 4: small enough to start beside resident forward waves)
     int no_fast_rows;       // sparse / half back-trace: 1 = every row through the general code (vit_plan_set_option "bt_fast_rows" 1; tests)
-    int skip_nonpositive;   // sparse kernel: a song whose lengths[] entry is < 1 is skipped (segments; vit_decode clamps to 1 instead)
+    int skip_nonpositive;   // sparse, lane and lazy (launch_backtrace_rows_segment) kernels: a song whose lengths[] entry is < 1 is skipped
+                            // (segments; vit_decode clamps to 1 instead)
     int32_t* counters;      // [B][kBtCounters] per-song event counts of the sparse / half / half-wave kernels (zeroed by vit_backtrace)
     // packed batch (vit_decode_packed): history rows / states of song b at offsets[b] (its length: offsets[b+1] - offsets[b]); the
     // speculative pass runs one wave per entry of wave_song (song b owns waves chunk_base[b] .. chunk_base[b+1]-1 = its chunks;
@@ -146,6 +155,11 @@ hipError_t launch_banded_packed(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t banded_packed_resident(const FwdArgs& a, bool f16, int* per_cu);
 hipError_t launch_step_packed(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t step_packed_resident(const FwdArgs& a, bool f16, int* per_cu);
+// checkpointed decode of plans without the wave form, one workgroup per song: pass 1 (a.ckpt_every > 0: checkpoint rows + terminal
+// state) or one segment (a.t_begin / a.t_end, resumed from a.init_rows; the banded kernel also writes one pad column of the row in
+// front of a.hist, see banded.hip)
+hipError_t launch_banded_ckpt(const FwdArgs& a, bool f16, hipStream_t st);
+hipError_t launch_step_ckpt(const FwdArgs& a, bool f16, hipStream_t st);
 // per song, for the segment [s0, e0) of a checkpointed decode: the sub-problem's length (0: the song ends before s0) and the state
 // its back-trace starts from (the state already decided at frame e0, or the song's terminal state)
 hipError_t launch_segment_prep(const int64_t* lengths, int64_t B, int T, int s0, int e0, const int32_t* states, const int32_t* last,
@@ -167,6 +181,9 @@ hipError_t launch_backtrace_sparse(const BtArgs& a, hipStream_t st, int phases =
 // backtrace_half.hip: the same for a half history (wave form, even rows only): odd frames are rebuilt from the row before them
 bool half_backtrace_applies(const BtArgs& a);
 hipError_t launch_backtrace_half(const BtArgs& a, hipStream_t st, int phases = 3);
+// the lazy kernel over one segment of a checkpointed decode (plans that are not banded): song bases from hist_rows / states_stride,
+// songs with lengths[] < 1 skipped (skip_nonpositive), a.chunks from the segment length
+hipError_t launch_backtrace_rows_segment(BtArgs a, hipStream_t st);
 int sparse_backtrace_chunks(int64_t B, int T, int n_cus);
 // backtrace_lane.hip: one (song, chunk) stream per LANE (banded plans, full history): ~130 wave instructions per 64 decisions
 bool lane_backtrace_applies(const BtArgs& a);

@@ -296,9 +296,18 @@ __global__ void __launch_bounds__(256) step4_forward_kernel(FwdArgs a) {
 // slot_songs[slot_begin[w] .. slot_begin[w+1]) back to back, rows of a song at offsets[song] of the packed buffers.  The band
 // tables c[] and rown[] stay in registers; V, F, dl, X, wm and dun go back to -inf between two songs, behind a barrier.
 // PK = false compiles to the code it was before the parameter existed.
-template <int BW, int KB, int PF, typename ET, bool PK = false>
+// CK = true is the checkpoint / resume variant (vit_decode_checkpointed), driven by the FwdArgs fields the wave form uses.  The only
+// state this kernel carries from frame to frame is dn (V, F, dl, X, wm and dun are published anew every frame), so
+//   pass 1 (ckpt_every = K > 0): every frame; frame mK - 1 is stored to row m - 1 of the song's hist_rows rows, every other frame to
+//     its last row (scratch);
+//   segment (ckpt_every = 0): frames t_begin .. min(length, t_end) - 1, row t stored at t - t_begin; t_begin > 0 loads dn from
+//     init_rows[song] = delta_{t_begin - 1} instead of forming log_pi + e_0.  A workgroup whose song ended before t_begin leaves
+//     without writing; the terminal state is pass 1's business.
+// CK = false compiles to the code it was before the parameter existed.
+template <int BW, int KB, int PF, typename ET, bool PK = false, bool CK = false>
 __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     static_assert(BW == 20 && KB == 9 && PF % 2 == 0, "written for nine 20-bin bands");
+    static_assert(!(PK && CK), "the checkpoint / resume variant is a variant of the unpacked kernel");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NQL = 192;                      // lanes per half: 192 x 4 states
     constexpr int NPV = 4 * NQL;                  // padded voiced states
@@ -327,8 +336,19 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     int song = blockIdx.x;
     int Tb = PK ? 1 : song_length(a.lengths, song, T);
     const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PK ? (size_t)0 : (size_t)song * T * S);
-    float* __restrict__ hist = a.hist + (PK ? (size_t)0 : (size_t)song * T * SD);
+    float* __restrict__ hist = a.hist + (PK ? (size_t)0 : (CK ? (size_t)song * (size_t)a.hist_rows * SD : (size_t)song * T * SD));
     const float* __restrict__ lpi = reinterpret_cast<const float*>(a.image + a.off_logpi);
+    // (CK) first frame of this launch, first frame the loop computes, pass 1's segment length and its row bookkeeping (all wave-uniform)
+    [[maybe_unused]] const int t0 = CK ? a.t_begin : 0;
+    [[maybe_unused]] const int t1 = CK && t0 > 0 ? t0 : 1;
+    [[maybe_unused]] const int ck_every = CK ? a.ckpt_every : 0;
+    [[maybe_unused]] const int ck_scratch = CK ? (int)a.hist_rows - 1 : 0;
+    [[maybe_unused]] int ck_next = ck_every - 1, ck_row = 0;              // the next frame that is a checkpoint, and its row
+    if constexpr (CK) {
+        const int stop = ck_every > 0 || a.t_end >= T ? T : a.t_end;
+        Tb = Tb < stop ? Tb : stop;
+        if (Tb <= t0) return;                                             // (segments: the song ended before this one)
+    }
     int si = 0, si_end = 1;                                               // (PK) position in slot_songs, end of the slot's list
     auto take_song = [&]() {                                              // (PK) wave-uniform: scalar loads
         song = a.slot_songs[si];
@@ -404,17 +424,26 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     auto mx3 = [](float acc, float x, float y) { return fmaxf(fmaxf(acc, x), y); };
 
     f32x4 dn;                                                             // delta of the own states (unvoiced wave: .x = state n, every lane)
-    {
+    if constexpr (CK) {                                                   // frame 0 (pass 1: into the scratch row), or the checkpoint row
+        if (t0 > 0) {
+            const float* __restrict__ ir = a.init_rows + (size_t)song * a.init_stride;
+            dn = mask4(f32x4{ir[col[0]], ir[col[1]], ir[col[2]], ir[col[3]]});
+        } else {
+            const f32x4 e0 = load4(0);
+            dn = mask4(f32x4{lpi[col[0]], lpi[col[1]], lpi[col[2]], lpi[col[3]]} + e0);
+            store4(ck_every > 0 ? ck_scratch : 0, dn);
+        }
+    } else {
         const f32x4 e0 = load4(0);
         dn = mask4(f32x4{lpi[col[0]], lpi[col[1]], lpi[col[2]], lpi[col[3]]} + e0);
         store4(0, dn);
     }
     f32x4 er[PF];
 #pragma unroll
-    for (int k = 0; k < PF; ++k) er[k] = load4(1 + k < Tb ? 1 + k : Tb - 1);
+    for (int k = 0; k < PF; ++k) er[k] = load4((CK ? t1 : 1) + k < Tb ? (CK ? t1 : 1) + k : Tb - 1);
 
 #ifdef VIT_TIMING_HOOKS
-    const bool prof = !PK && (a.debug & 256) != 0;      // phase stamps: publish | barrier | reads | exchange + store -> scratch[song][4*wave ..]
+    const bool prof = !PK && !CK && (a.debug & 256) != 0;      // phase stamps: publish | barrier | reads | exchange + store -> scratch[song][4*wave ..]
 #else
     constexpr bool prof = false;
 #endif
@@ -538,7 +567,18 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
         }
         dn = mask4(m + e_slot);
         const int tn = t + PF < Tb ? t + PF : Tb - 1;
-        store4(t, dn);
+        if constexpr (CK) {         // a segment stores frame t at t - t0, pass 1 at the next checkpoint row or the scratch row (scalar selects)
+            int row = t - t0;
+            if (ck_every > 0) {
+                const bool hit = t == ck_next;
+                row = hit ? ck_row : ck_scratch;
+                ck_next += hit ? ck_every : 0;
+                ck_row += hit ? 1 : 0;
+            }
+            store4(row, dn);
+        } else {
+            store4(t, dn);
+        }
         e_slot = load4(tn);
         if (prof) {
             const unsigned long long s4 = stamp();
@@ -547,7 +587,7 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     };
     // ---------------- one pass per song (PK: the songs of the slot, back to back)
     for (;;) {
-        int t = 1;
+        int t = CK ? t1 : 1;
         for (; t + PF - 1 < Tb; t += PF) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) frame(t + k, er[k]);
@@ -562,8 +602,9 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
         }
 
         // terminal state: lowest-index argmax over half A's lanes (four adjacent states each) and the unvoiced state
+        // (CK: pass 1 only -- a uniform test, every thread reaches the barriers or none does)
         __syncthreads();
-        {
+        if (!CK || ck_every > 0) {
             VI x = vi_identity();
             if (half == 0) {
                 if (val[0]) x = VI{dn.x, j0};
@@ -619,6 +660,19 @@ static hipError_t step_packed(const FwdArgs& a, bool f16, hipStream_t st, int* p
         return hipGetLastError();
     };
     return f16 ? go(step4s_forward_kernel<BW, KB, PF, __half, true>) : go(step4s_forward_kernel<BW, KB, PF, float, true>);
+}
+
+hipError_t launch_step_ckpt(const FwdArgs& a, bool f16, hipStream_t st) {
+    constexpr int BW = 20, KB = 9, PF = 2;
+    if (!step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) return hipErrorInvalidConfiguration;
+    if (a.offsets || a.hist_rows < 1 || (a.t_begin > 0 && !a.init_rows) || (a.ckpt_every > 0 && a.t_begin > 0)) return hipErrorInvalidValue;
+    constexpr int VL4 = 768 + 2 * (KB * BW + BW);
+    const size_t ldss = sizeof(float) * (KB * VL4 + KB * (VL4 / 4) + (768 + 64) + 8 * 192 + 8) + sizeof(VI) * 16;
+    if (f16)
+        hipLaunchKernelGGL((step4s_forward_kernel<BW, KB, PF, __half, false, true>), dim3((int)a.B), dim3(448), ldss, st, a);
+    else
+        hipLaunchKernelGGL((step4s_forward_kernel<BW, KB, PF, float, false, true>), dim3((int)a.B), dim3(448), ldss, st, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_step_packed(const FwdArgs& a, bool f16, hipStream_t st) {

@@ -235,20 +235,27 @@ class ViterbiDecoder:
         * ``{"mode": "half"}``  -- the wave form with the rows of even frames only (``wave_history`` 2: half the workspace, a
           slower back-trace), where the plan has it;
         * ``{"mode": "checkpointed", "segment_frames": K}`` -- ``vit_decode_checkpointed`` with the largest K that fits (about
-          twice the forward work; wave-form plans).
+          twice the forward work; wave-form plans, and the workgroup-form plans of the 722-state grids: banded with the floor
+          form proven, or step-structured -- those have no half history and fall straight from "full" to here).
 
         Raises ViterbiHipError when nothing fits.  Every mode decodes the same bits."""
         need = self.workspace_bytes(B, T, algo)
         if max_workspace_bytes is None or need <= max_workspace_bytes:
             return {"mode": "full", "workspace_bytes": need}
-        if self.info["wave_ok"] and algo in ("auto", "banded", "wave") and T >= 2:
-            lib = _lib.load()
+        lib = _lib.load()
+        wave = self.info["wave_ok"] and algo in ("auto", "banded", "wave") and T >= 2
+        # plans without the wave form: the workgroup kernels of the checkpointed decode stand in for the banded workgroup family
+        # or (step plans) for what "auto" picks; an `algo` that means the dense kernel keeps raising
+        group = not self.info["wave_ok"] and ((self.info["banded_ok"] and algo in ("auto", "banded", "group")) or
+                                              (not self.info["banded_ok"] and self.info["step_ok"] and algo == "auto"))
+        if wave:
             prev = self._options.get("wave_history", 0)
             _lib.check(lib.vit_plan_set_option(self._plan, b"wave_history", 2), "vit_plan_set_option(wave_history)")
             half = int(lib.vit_workspace_bytes_for(self._plan, B, T, _lib.ALGO["wave"]))
             _lib.check(lib.vit_plan_set_option(self._plan, b"wave_history", prev), "vit_plan_set_option(wave_history)")
             if 0 < half <= max_workspace_bytes:
                 return {"mode": "half", "workspace_bytes": half}
+        if wave or group:
             K = 8192
             while K >= 64:
                 ck = int(lib.vit_workspace_bytes_checkpointed(self._plan, B, T, K))
@@ -263,9 +270,9 @@ class ViterbiDecoder:
         """Returns (states [B,T] or [T] of ``out_dtype`` (reference: int64), loglik float32 [B] or scalar).
 
         ``max_workspace_bytes``: a budget for the delta history (the reference keeps its work buffers for ONE song,
-        tonet/for_paper.py:1852-1853; a batch of 2048 full-length songs asks for 94 GB).  The decode falls from the full history to
-        the wave form's half history to the checkpointed decode (``plan_workspace``) instead of running out of memory; the result
-        is the same in every mode."""
+        tonet/for_paper.py:1852-1853; a batch of 2048 full-length songs asks for 94 GB, 178 GB with 722 states).  The decode falls
+        from the full history to the wave form's half history (where the plan has one) to the checkpointed decode
+        (``plan_workspace``) instead of running out of memory; the result is the same in every mode."""
         logE, single, _ = self._check_emissions(emission_logits)
         B, T, _ = logE.shape
         if B > 0 and max_workspace_bytes is not None:
@@ -292,17 +299,27 @@ class ViterbiDecoder:
 
     # ------------------------------------------------------------------ bounded-workspace decode
     def workspace_bytes_checkpointed(self, B: int, T: int, segment_frames: int) -> int:
+        """Workspace bytes of ``decode_checkpointed``; raises ViterbiHipError for a plan or a segment length it does not serve."""
         need = int(_lib.load().vit_workspace_bytes_checkpointed(self._plan, B, T, int(segment_frames)))
         if need == 0 and B > 0:
-            raise _lib.ViterbiHipError("checkpointed decode needs a plan with the wave form and segment_frames >= 64")
+            raise _lib.ViterbiHipError("the checkpointed decode needs 64 <= segment_frames <= 2**24 and a plan with the wave form, the "
+                                       "floor form (banded, no dense rows) or the step form (unstructured matrices and scan-only "
+                                       "banded plans: decode() with the full history)")
         return need
+
+    def workspace_bytes_checkpointed_or_zero(self, B: int, T: int, segment_frames: int) -> int:
+        """The same without the exception: 0 when the checkpointed decode does not serve this plan or segment length."""
+        return int(_lib.load().vit_workspace_bytes_checkpointed(self._plan, int(B), int(T), int(segment_frames)))
 
     def decode_checkpointed(self, emission_logits: torch.Tensor, segment_frames: int = 1024, lengths: Optional[torch.Tensor] = None,
                             out_dtype: torch.dtype = torch.int64, workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """``decode`` with a bounded workspace (``vit_decode_checkpointed``): about ``T / segment_frames + segment_frames`` delta
         rows per song instead of ``T`` -- the reference keeps its work buffers for one song at a time
-        (tonet/for_paper.py:1852-1853).  Same states, same log-likelihood; about twice the forward work.  ``workspace``: an
-        optional uint8 tensor of at least ``workspace_bytes_checkpointed(...) + 256`` bytes to decode in."""
+        (tonet/for_paper.py:1852-1853).  Same states, same log-likelihood; about twice the forward work.  For plans with the wave
+        form (S = 321 / 361), banded plans whose floor form is proven (the 722-state jdc grids) and step-structured plans (the
+        Durrieu matrix); any other plan raises ``ViterbiHipError`` before anything is enqueued.  ``workspace``: an optional uint8
+        tensor of at least ``workspace_bytes_checkpointed(...) + 256`` bytes to decode in (the caller then keeps it alive until the
+        stream has run the decode: the call does not synchronise)."""
         lib = _lib.load()
         logE, single, dt = self._check_emissions(emission_logits)
         B, T, _ = logE.shape
@@ -320,7 +337,8 @@ class ViterbiDecoder:
                                                  (ws.data_ptr() + 255) & ~255, ws.numel() - 256, states.data_ptr(), loglik.data_ptr(),
                                                  int(segment_frames), torch.cuda.current_stream(self.device).cuda_stream)
             _lib.check(rc, "vit_decode_checkpointed")
-            torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
+            if workspace is None:
+                torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
         if out_dtype != torch.int32:
             states = states.to(out_dtype)
         return (states[0], loglik[0]) if single else (states, loglik)
@@ -428,9 +446,11 @@ def get_decoder(transition_matrix, init_probs, device=None) -> ViterbiDecoder:
 
 
 def decode(emission_logits: torch.Tensor, transition_matrix, init_probs, lengths: Optional[torch.Tensor] = None,
-           algo: str = "auto", out_dtype: torch.dtype = torch.int64) -> Tuple[torch.Tensor, torch.Tensor]:
-    """decode(emission_logits, transition_matrix, init_probs) -> (states, loglik).  See module docstring."""
+           algo: str = "auto", out_dtype: torch.dtype = torch.int64,
+           max_workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """decode(emission_logits, transition_matrix, init_probs) -> (states, loglik).  See module docstring.
+    ``max_workspace_bytes``: the workspace budget of ``ViterbiDecoder.decode``."""
     if not isinstance(emission_logits, torch.Tensor) or emission_logits.device.type != "cuda":
         raise ValueError("emission_logits must be a torch tensor on a ROCm GPU (there is no CPU path)")
     dec = get_decoder(transition_matrix, init_probs, emission_logits.device)
-    return dec.decode(emission_logits, lengths=lengths, algo=algo, out_dtype=out_dtype)
+    return dec.decode(emission_logits, lengths=lengths, algo=algo, out_dtype=out_dtype, max_workspace_bytes=max_workspace_bytes)
