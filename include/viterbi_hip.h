@@ -246,6 +246,40 @@ size_t vit_workspace_bytes_packed(const vit_plan *plan, int64_t B, int64_t total
 int vit_decode_packed(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B, const int64_t *offsets,
                       void *workspace, size_t workspace_bytes, int32_t *states, float *loglik, vit_stream stream);
 
+/*
+ * Fused logits -> path decode: what callers of the reference run is Viterbi.__call__ (tonet/for_paper.py:1817-1831) -- pitch
+ * logits -> observation log-probabilities -> Viterbi decode.  vit_obs_*() + vit_decode() do that with a [B,T,S] float32
+ * emission tensor written to and read back from device memory (2 x 4 S bytes per frame, 44 GB for [1024, 30000, 361]); here the
+ * emission rows are built inside the forward pass, in the workgroup that consumes them, and exist in LDS only.
+ *   obs       : HOST, the arguments of vit_obs_shaun (mode 0) / vit_obs_softmax (1) / vit_obs_softmax_scaled (2); obs->prior is a
+ *               device pointer.  obs->n_bins + 1 must be the plan's S (VIT_EINVAL otherwise).
+ *   logits    : device, [B,T,n_bins] float32 (mode 1: [B,T,n_bins+1], unvoiced column first), C-order
+ *   lengths, workspace, states, loglik : as for vit_decode(); workspace >= vit_workspace_bytes_logits(plan, obs, B, T) -- a full
+ *               delta history in the wave layout (64 * 6 floats per frame and song) and nothing for emissions
+ *   logE_out  : NULL, or device [B,T,S] float32: the emission rows are ALSO written there (frames inside a song's length only),
+ *               bit for bit what vit_obs_*() writes
+ * States and log-likelihoods are bit-identical to vit_obs_*() into a buffer followed by vit_decode(..., VIT_ALGO_WAVE).
+ * Which plans and builders: plans with the wave form (vit_plan_info reserved[2] bit 3) whose one extra column is the last state
+ * (the reference's 321- and 361-state matrices), n_bins 320 or 360, and the reference's three builder geometries -- mode 0 with
+ * spw 5, mode 1 with spw 15, mode 2 with spw 5.  Everything else (no wave form, the 722-state grids, two extra columns, other
+ * peak widths, "wave_uniform" 1) gets 0 from vit_workspace_bytes_logits and VIT_EUNSUPPORTED from vit_decode_logits before
+ * anything is enqueued; a size > 0 means the decode launches.  Honoured options: "bt_chunks", "bt_warm", "bt_fast_rows",
+ * "bt_block_waves", "backtrace_form", "wave_uniform"; ignored: "wave_history" (a half history re-reads emissions, which do not exist
+ * here), "forward_form", "wave_two".  No host synchronisation, no allocation.  The library does not record this call for
+ * vit_backtrace().
+ */
+typedef struct vit_obs_params {
+    int32_t mode;                    /* 0 shaun | 1 softmax (logits [.., n_bins+1], unvoiced first) | 2 scaled softmax */
+    int32_t n_bins, spw;
+    double threshold_logit;          /* mode 0: threshold logit; mode 2: the unvoiced logit */
+    double offset, scale;            /* mode 0 */
+    const float *prior;              /* mode 2: device [n_bins+1] or NULL */
+} vit_obs_params;
+size_t vit_workspace_bytes_logits(const vit_plan *plan, const vit_obs_params *obs, int64_t B, int64_t T);
+int vit_decode_logits(const vit_plan *plan, const float *logits, const vit_obs_params *obs, int64_t B, int64_t T,
+                      const int64_t *lengths, void *workspace, size_t workspace_bytes, float *logE_out,
+                      int32_t *states, float *loglik, vit_stream stream);
+
 /* Event counts of the last vit_backtrace() on this workspace (banded plans; all zero for the kernels that do not count):
  * *offset = byte offset, inside the workspace, of an int32 [B][*n_per_song] device array (valid once the back-trace has run
  * on its stream): per song [0] tiles fetched, [1] span misses (the path left the fetched columns), [2] whole-row evaluations

@@ -22,6 +22,7 @@ EXPORTS = (
     "vit_forward", "vit_backtrace", "vit_voicing_map", "vit_obs_shaun", "vit_obs_softmax", "vit_obs_softmax_scaled", "vit_plan_set_option", "vit_snippets_append", "vit_voicing_notes",
     "vit_workspace_bytes_for", "vit_debug_scan", "vit_backtrace_counters", "vit_workspace_bytes_checkpointed", "vit_decode_checkpointed",
     "vit_backtrace_checked", "vit_forward_family", "vit_workspace_bytes_packed", "vit_decode_packed",
+    "vit_workspace_bytes_logits", "vit_decode_logits",
 )
 ABI_VERSION = 4
 
@@ -31,6 +32,15 @@ class PlanInfo(ctypes.Structure):
         ("S", ctypes.c_int64), ("banded_ok", ctypes.c_int32), ("n_consts", ctypes.c_int32),
         ("n_extras", ctypes.c_int32), ("max_window", ctypes.c_int32), ("group_window", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 3), ("consts", ctypes.c_float * 4), ("extras", ctypes.c_int32 * 4),
+    ]
+
+
+class ObsParams(ctypes.Structure):
+    """``vit_obs_params``: the emission-builder arguments of ``vit_decode_logits`` (mode 0 shaun | 1 softmax | 2 scaled softmax)."""
+    _fields_ = [
+        ("mode", ctypes.c_int32), ("n_bins", ctypes.c_int32), ("spw", ctypes.c_int32),
+        ("threshold_logit", ctypes.c_double), ("offset", ctypes.c_double), ("scale", ctypes.c_double),
+        ("prior", ctypes.c_void_p),
     ]
 
 
@@ -99,6 +109,10 @@ def load() -> ctypes.CDLL:
     lib.vit_workspace_bytes_packed.argtypes = [vp, i64, i64]
     lib.vit_decode_packed.restype = i32
     lib.vit_decode_packed.argtypes = [vp, vp, i32, i64, vp, vp, sz, vp, vp, vp]
+    lib.vit_workspace_bytes_logits.restype = sz
+    lib.vit_workspace_bytes_logits.argtypes = [vp, ctypes.POINTER(ObsParams), i64, i64]
+    lib.vit_decode_logits.restype = i32
+    lib.vit_decode_logits.argtypes = [vp, vp, ctypes.POINTER(ObsParams), i64, i64, vp, vp, sz, vp, vp, vp, vp]
     lib.vit_forward_family.restype = i32
     lib.vit_forward_family.argtypes = [vp, i64, i32]
     lib.vit_voicing_map.restype = i32

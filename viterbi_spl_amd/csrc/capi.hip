@@ -1054,6 +1054,87 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     return e == hipSuccess ? VIT_OK : hip_fail(e);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Fused logits -> path decode (fused.hip): the emission builder and the wave-form forward recursion share a workgroup, the
+// emission rows cross the CU through LDS and no [B, T, S] emission tensor exists.  Then the ordinary full-history back-trace of
+// the wave layout.
+namespace {
+
+// the ONE predicate behind vit_workspace_bytes_logits and vit_decode_logits (a size > 0 implies a decode that launches)
+bool lg_applies(const vit_plan* p, const vit_obs_params* obs) {
+    vit::FwdArgs a{};
+    fwd_args_from_plan(p, a);          // (wave_u5 after the "wave_uniform" option)
+    return vit::fused_logits_applies(p->S, a.wave_ok, a.wave_npl, a.wave_dk, a.n_extras, a.wave_u5, obs->mode, obs->n_bins, obs->spw);
+}
+
+}  // namespace
+
+size_t vit_workspace_bytes_logits(const vit_plan* plan, const vit_obs_params* obs, int64_t B, int64_t T) {
+    if (!plan || !obs || B < 0 || T < 1) return 0;
+    if (!lg_applies(plan, obs)) return 0;
+    return ws_layout_hist(B, (size_t)T, (size_t)vit::wave_hist_stride(plan->bp.wave_npl)).bytes;
+}
+
+int vit_decode_logits(const vit_plan* plan, const float* logits, const vit_obs_params* obs, int64_t B, int64_t T, const int64_t* lengths,
+                      void* workspace, size_t workspace_bytes, float* logE_out, int32_t* states, float* loglik, vit_stream stream) {
+    if (!plan || !obs) return VIT_EINVAL;
+    if (!plan->dev_image) return VIT_ENOTUPLOADED;
+    int rc = check_common(plan, B, T, workspace);
+    if (rc != VIT_OK) return rc;
+    if (obs->mode < 0 || obs->mode > 2 || obs->n_bins < 2 || (int64_t)obs->n_bins + 1 != plan->S) return VIT_EINVAL;
+    if (!lg_applies(plan, obs)) return VIT_EUNSUPPORTED;      // (everything that can refuse the plan or the builder is asked here)
+    if (B > 0 && (!logits || !states)) return VIT_EINVAL;
+    const int SDH = vit::wave_hist_stride(plan->bp.wave_npl);
+    const WsLayout w = ws_layout_hist(B, (size_t)T, (size_t)SDH);
+    if (workspace_bytes < w.bytes) return VIT_EWORKSPACE;
+    if (B == 0) return VIT_OK;
+    stamp_erase(plan, workspace);
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    vit::FusedArgs fa{};
+    fwd_args_from_plan(plan, fa.f);
+    fa.f.logE = nullptr;
+    fa.f.lengths = lengths;
+    fa.f.hist = reinterpret_cast<float*>(ws + w.off_hist);
+    fa.f.fmax = reinterpret_cast<float*>(ws + w.off_fmax);
+    fa.f.last_state = reinterpret_cast<int32_t*>(ws + w.off_last);
+    fa.f.loglik = loglik;
+    fa.f.B = B;
+    fa.f.T = (int)T;
+    fa.f.hist_half = 0;
+    fa.f.hist_rows = T;
+    fa.f.t_begin = 0;
+    fa.f.t_end = (int)T;
+    fa.logits = logits;
+    fa.logE_out = logE_out;
+    fa.mode = obs->mode;
+    fa.n_bins = obs->n_bins;
+    fa.spw = obs->spw;
+    fa.threshold = obs->threshold_logit;
+    fa.offset = obs->mode == 0 ? obs->offset : 0.0;
+    fa.scale = obs->mode == 0 ? obs->scale : 0.0;
+    fa.prior = obs->mode == 2 ? obs->prior : nullptr;
+    hipError_t e = vit::launch_fused_logits(fa, (hipStream_t)stream);
+    if (e == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;     // (cannot happen: lg_applies asked the same predicate)
+    if (e != hipSuccess) return hip_fail(e);
+    // the back-trace of a full wave-layout history, through the record vit_backtrace reads; the record does not outlive the call
+    FwdStamp st;
+    st.ws = workspace;
+    st.B = B;
+    st.T = T;
+    st.family = 3;
+    st.SD = SDH;
+    st.col0 = SDH - plan->S;
+    st.mcol = 0;
+    st.xcol0 = 1;
+    st.aux_frames = vit::wave_aux_frames(plan->bp.wave_npl, plan->S, fa.f.n_extras);
+    st.have_fmax = 1;
+    st.half = 0;
+    stamp_put(plan, st);
+    rc = backtrace_impl(plan, nullptr, 0, false, B, T, lengths, workspace, workspace_bytes, states, stream);
+    stamp_erase(plan, workspace);
+    return rc;
+}
+
 int vit_voicing_map(const int32_t* states, int64_t n, int32_t n_bins, uint8_t* voiced, int32_t* bins,
                     vit_stream stream) {
     if (n < 0 || n_bins < 1 || (n > 0 && (!states || !voiced || !bins))) return VIT_EINVAL;

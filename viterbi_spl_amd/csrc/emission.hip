@@ -12,12 +12,11 @@
 // the reference); exp/log/sum are the GPU's, so probabilities agree to a few ulp, not bit for bit
 // (tests compare with a tolerance and require the structural zeros -> log(tiny) to be exact).
 #include "device_common.hpp"
+#include "obs_frame.hpp"
 
 namespace vit {
 
 constexpr int kObsWaves = 4;
-constexpr float kTiny = 1.1754944e-38f;        // np.finfo(np.float32).tiny
-constexpr float kLogTiny = -87.33654475f;      // float32 log(tiny) = -87.33655 (bits 0xC2AEAC50)
 
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
@@ -212,73 +211,6 @@ __global__ void __launch_bounds__(kObsWaves * 64) observation_kernel(const float
 // reference's.  No LDS, no barrier.
 // Instantiated for the reference's half-widths 5 ("shaun", dcnet's scaled likelihood) and 15 (softmax) and 5 / 6 / 8 / 12 bins per
 // lane (U <= 64 NPL: the 320-, 360- and 721-bin grids and what lies between); other geometries keep the LDS form.
-namespace {
-
-// a lane's NPL consecutive floats as 16- / 8- / 4-byte pieces at 4-byte alignment (coalesced across the wave)
-template <int NPL>
-__device__ __forceinline__ void ob_load(const float* __restrict__ p, float (&v)[NPL]) {
-    int k = 0;
-#pragma unroll
-    for (; k + 3 < NPL; k += 4) { const f32x4_u t = *reinterpret_cast<const f32x4_u*>(p + k); v[k] = t.x; v[k + 1] = t.y; v[k + 2] = t.z; v[k + 3] = t.w; }
-#pragma unroll
-    for (; k + 1 < NPL; k += 2) { const f32x2_u t = *reinterpret_cast<const f32x2_u*>(p + k); v[k] = t.x; v[k + 1] = t.y; }
-    if (k < NPL) v[k] = p[k];
-}
-template <int NPL>
-__device__ __forceinline__ void ob_store(float* __restrict__ p, const float (&v)[NPL]) {
-    int k = 0;
-#pragma unroll
-    for (; k + 3 < NPL; k += 4) { f32x4_u t; t.x = v[k]; t.y = v[k + 1]; t.z = v[k + 2]; t.w = v[k + 3]; *reinterpret_cast<f32x4_u*>(p + k) = t; }
-#pragma unroll
-    for (; k + 1 < NPL; k += 2) { f32x2_u t; t.x = v[k]; t.y = v[k + 1]; *reinterpret_cast<f32x2_u*>(p + k) = t; }
-    if (k < NPL) p[k] = v[k];
-}
-
-__device__ __forceinline__ float ob_wave_sum(float x) {   // inclusive scan by rows, lane 63 holds the total
-    asm volatile(
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
-        "s_nop 1"
-        : "+v"(x));
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-}
-// e^x through v_exp_f32 (2^y, 1 ulp): log2(e) = hi + lo, the rounding error of x * hi is recovered with an fma and applied as
-// the factor 2^lo ~ 1 + lo ln 2 -- ~2 ulp where a plain x * log2(e) would lose |x| * 1e-7
-__device__ __forceinline__ float ob_exp(float x) {
-    const float hi = x * 1.44269502f;
-    const float lo = __builtin_fmaf(x, 1.44269502f, -hi);              // the product's rounding error, exactly
-    const float e2 = __builtin_amdgcn_exp2f(hi);
-    return __builtin_fmaf(e2, lo * 0.693147182f, e2);                   // (what float(log2 e) itself is off by adds |x| * 1.3e-8: < 1 ulp up to |x| = 8)
-}
-// e^x for any x: v_exp_f32 flushes results below 2^-126 (x < -87.34) to 0, where float32 has subnormals (down to e^-103.3) and the
-// reference's np.exp keeps them.  There the exponent is raised by 64 before the instruction and the result scaled by 2^-64 after it:
-// one rounding into the subnormal range, as a full expf does.  (e^-1000 is still 0.)
-__device__ __forceinline__ float ob_exp_far(float x) {
-    const float hi = x * 1.44269502f;
-    const float lo = __builtin_fmaf(x, 1.44269502f, -hi);
-    const bool sub = hi < -126.f;
-    const float e2 = __builtin_amdgcn_exp2f(sub ? hi + 64.f : hi);    // (hi + 64 is exact)
-    const float r = __builtin_fmaf(e2, lo * 0.693147182f, e2);
-    return sub ? r * 5.42101086e-20f : r;                               // 2^-64
-}
-// ln y through v_log_f32 (log2, 1 ulp), ln 2 = hi + lo
-__device__ __forceinline__ float ob_log(float y) {
-    const float l2 = __builtin_amdgcn_logf(y);
-    return __builtin_fmaf(l2, 0.693147182f, l2 * -1.90465421e-9f);
-}
-
-}  // namespace
-
 template <int NPL, int SPW, int MODE>
 __global__ void __launch_bounds__(256) observation_reg_kernel(const float* __restrict__ logits, int64_t n_frames, int U, double threshold,
                                                              double offset, double scale, const float* __restrict__ prior,
@@ -340,109 +272,7 @@ __global__ void __launch_bounds__(256) observation_reg_kernel(const float* __res
 #pragma unroll
         for (int k = 0; k < NPL; ++k) a[SPW + k] = xn[k];
         if (f + 2 * fstep < n_frames) fetch(f + 2 * fstep, xn, x0n);
-        // ---- neighbours: a[SPW - d] = bin NPL*lane - d lives in lane - ceil(d / NPL); shifted copies chained; a lane without a source
-        //      keeps -inf (the DPP `old` operand)
-        {
-            float sl[NPL], sr[NPL];
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) { sl[k] = a[SPW + k]; sr[k] = a[SPW + k]; }
-#pragma unroll
-            for (int h = 1; h <= H; ++h) {
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) {
-                    const int dl = h * NPL - k;               // sl[k] after h shifts = bin NPL*(lane-h) + k = own start - dl
-                    if (dl <= SPW) { sl[k] = wave_shift_up(sl[k], -INFINITY); a[SPW - dl] = sl[k]; }      // (a slot that is out of reach at h stays out of reach)
-                    const int dr = (h - 1) * NPL + k;         // sr[k] after h shifts = bin NPL*(lane+h) + k = own end + 1 + dr
-                    if (dr < SPW) { sr[k] = wave_shift_down(sr[k], -INFINITY); a[SPW + NPL + dr] = sr[k]; }
-                }
-            }
-        }
-        // ---- peaks: the FIRST maximum of its window: c > max(left SPW) and c >= max(right SPW)
-        bool pk[NPL];
-        float lmax = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) {
-            float ml = a[k], mr = a[SPW + k + 1];
-#pragma unroll
-            for (int j = 1; j + 1 < SPW; j += 2) { ml = fmaxf(fmaxf(ml, a[k + j]), a[k + j + 1]); mr = fmaxf(fmaxf(mr, a[SPW + k + 1 + j]), a[SPW + k + 2 + j]); }
-            if (SPW % 2 == 0) { ml = fmaxf(ml, a[k + SPW - 1]); mr = fmaxf(mr, a[2 * SPW + k]); }
-            const float c = a[SPW + k];
-            const bool std_pk = c > ml && c >= mr, first_pk = c > mr;
-            pk[k] = real[k] && !never[k] && (first[k] ? first_pk : std_pk);
-            lmax = pk[k] ? fmaxf(lmax, c) : lmax;
-        }
-        const float x0 = MODE == 1 ? x0f : (MODE == 2 ? (float)threshold : -INFINITY);     // the unvoiced logit (always in the peak set)
-        float g = wave_max_all(lmax);
-        const bool any_peak = g > -INFINITY;
-        if (MODE >= 1) g = fmaxf(g, x0);
-        float ex[NPL];
-        float lsum = 0.f, e0 = 0.f;
-        // (e^-1000 = 0: a select on the argument, no branch around the exp.)  A peak or unvoiced logit more than 80 nats below the top
-        // may have a subnormal e^x (below -87.3, which v_exp_f32 flushes) or e^x / tot (tot <= U + 1 <= e^6.65): such a frame (rare on
-        // real logits) takes ob_exp_far and true divisions, the branch is wave-uniform
-        bool far = MODE >= 1 && x0 - g < -80.f;
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) far = far || (pk[k] && a[SPW + k] - g < -80.f);
-        const bool far_frame = __ballot(far) != 0;
-        if (far_frame) {
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) {
-                ex[k] = ob_exp_far(pk[k] ? a[SPW + k] - g : -1000.f);
-                lsum += ex[k];
-            }
-            if (MODE >= 1) e0 = ob_exp_far(x0 - g);
-        } else {
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) {
-                ex[k] = ob_exp(pk[k] ? a[SPW + k] - g : -1000.f);
-                lsum += ex[k];
-            }
-            if (MODE >= 1) e0 = ob_exp(x0 - g);
-        }
-        float tot = ob_wave_sum(lsum);
-        float last;                                      // probability of the unvoiced state
-        float v[NPL];
-        if (MODE == 0) {
-            // soft voicing on the strongest peak (tonet/for_paper.py:1703-1712, :1757-1764) in float64 exactly like the reference:
-            // 1 - expit(s) is formed by subtraction there, so for s > ~37 the unvoiced probability is EXACTLY 0 (-> log tiny) and below
-            // that it carries the float64 cancellation noise of the reference (2e-5 relative at 1 - pv = 6e-12); a float32 expit(-s)
-            // would be more accurate and would not be the reference's number
-            double pv = 0.0;
-            if (any_peak) {
-                const double gd = (double)g;
-                const double s_ = gd >= threshold ? scale * (gd - threshold) + offset : scale * (gd - threshold) - offset;
-                if (s_ > 0) pv = 1.0 / (1.0 + exp(-s_));
-                else { const double q = exp(s_); pv = q / (1.0 + q); }
-            }
-            const double t = any_peak ? pv / (double)tot : 0.0;
-            last = any_peak ? (float)(1.0 - pv) : 1.f;
-#pragma unroll
-            for (int k = 0; k < NPL; ++k) {
-                float lg = ob_log((float)((double)ex[k] * t) + kTiny);
-                asm volatile("" : "+v"(lg));                          // (evaluate, then select: no branch per slot)
-                v[k] = pk[k] ? lg : kLogTiny;
-            }
-        } else {
-            tot += e0;
-            auto emit = [&](const int k, float pr) {
-                if (MODE == 2) pr *= rprior[k];
-                float lg = ob_log(pr + kTiny);
-                asm volatile("" : "+v"(lg));                          // (evaluate, then select: no branch per slot)
-                v[k] = pk[k] ? lg : kLogTiny;
-            };
-            if (far_frame) {
-                // e^x / tot may be subnormal, where a product with 1 / tot can round to a neighbouring multiple of 2^-149 (tens of %
-                // at a few units) and MODE 2's prior scaling lifts that error into the normal range: divide, as the reference does
-                last = any_peak ? e0 / tot : 1.f;
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) emit(k, ex[k] / tot);
-            } else {
-                const float tf = 1.f / tot;
-                last = any_peak ? e0 * tf : 1.f;
-#pragma unroll
-                for (int k = 0; k < NPL; ++k) emit(k, ex[k] * tf);
-            }
-        }
+#include "obs_frame_body.inc"
         if (full) ob_store<NPL>(o + col0, v);
         if (partial) {
 #pragma unroll

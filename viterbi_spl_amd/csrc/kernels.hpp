@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface between the C ABI (capi.hip) and the kernel files (dense, step, banded, wave, emission,
+// kernels.hpp -- launch interface between the C ABI (capi.hip) and the kernel files (dense, step, banded, wave, emission, fused,
 // backtrace_rows / _sparse / _half / _lane .hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -145,6 +145,25 @@ struct BtArgs {
     uint32_t* mask;         // [B][kLaneMaskWords] lane form: bit c = chunk c assumed the wrong state at its upper boundary (zeroed by vit_backtrace)
 };
 
+// fused.hip: emission builder + wave-form forward recursion in one workgroup (vit_decode_logits).  f: the forward pass's arguments
+// (logE unused: the emission rows never leave the CU; hist_rows = T, full history in the wave layout); the rest: the builder's
+// (emission.hip; mode 0 "shaun" | 1 softmax, logits [B, T, n_bins + 1] with the unvoiced column first | 2 scaled softmax).
+struct FusedArgs {
+    FwdArgs f;
+    const float* logits;    // [B, T, n_bins] (mode 1: n_bins + 1) float32
+    float* logE_out;        // [B, T, n_bins + 1] or null: the producers also write their rows here
+    int mode, n_bins, spw;
+    double threshold, offset, scale;   // mode 0: threshold logit, offset, scale; mode 2: threshold = the unvoiced logit
+    const float* prior;     // mode 2: [n_bins + 1] or null
+};
+// what fused.hip is instantiated for: the wave form with six states per lane and ONE extra column that is the last state (wave_u5 =
+// FwdArgs::wave_u5 after the plan's options, 1 .. 3), and the builders the reference ships for the 320- and 360-bin grids
+constexpr bool fused_logits_applies(int S, int wave_ok, int wave_npl, int wave_dk, int n_extras, int wave_u5, int mode, int n_bins, int spw) {
+    return wave_ok && wave_npl == 6 && wave_dk == 14 && n_extras == 1 && wave_u5 >= 1 && wave_u5 <= 3 && n_bins + 1 == S &&
+           (n_bins == 360 || (n_bins == 320 && wave_u5 != 2)) && 64 * 6 - S >= 6 &&
+           ((mode == 0 && spw == 5) || (mode == 1 && spw == 15) || (mode == 2 && spw == 5));
+}
+hipError_t launch_fused_logits(const FusedArgs& fa, hipStream_t st);
 hipError_t launch_dense(const FwdArgs& a, int songs_per_group, bool f16, hipStream_t st);
 hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st);

@@ -392,6 +392,84 @@ class ViterbiDecoder:
         the forms the packed decode runs (see ``decode_packed``)."""
         return int(_lib.load().vit_workspace_bytes_packed(self._plan, int(B), int(total_frames)))
 
+    # ------------------------------------------------------------------ fused logits -> path decode
+    @staticmethod
+    def obs_params(mode: str, n_bins: int, single_side_peak_width: int, threshold_logit: float = 0.0, offset: float = 0.0,
+                   scale: float = 0.0, prior: Optional[torch.Tensor] = None) -> dict:
+        """The emission-builder arguments ``decode_logits`` takes (``vit_obs_params``): ``mode`` "shaun" (``vit_obs_shaun``:
+        threshold logit, offset, scale), "softmax" (``vit_obs_softmax``: logits carry the unvoiced column first) or
+        "softmax_scaled" (``vit_obs_softmax_scaled``: ``threshold_logit`` is the unvoiced logit, ``prior`` the state prior on the
+        GPU or None)."""
+        modes = {"shaun": 0, "softmax": 1, "softmax_scaled": 2}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)}")
+        return {"mode": modes[mode], "n_bins": int(n_bins), "spw": int(single_side_peak_width), "threshold_logit": float(threshold_logit),
+                "offset": float(offset), "scale": float(scale), "prior": prior}
+
+    def _obs_struct(self, obs: dict) -> "_lib.ObsParams":
+        prior = obs.get("prior")
+        if prior is not None:
+            if (not isinstance(prior, torch.Tensor) or prior.device != self.device or prior.dtype != torch.float32 or
+                    tuple(prior.shape) != (obs["n_bins"] + 1,) or not prior.is_contiguous()):
+                raise ValueError(f"prior must be a contiguous float32 [{obs['n_bins'] + 1}] tensor on the decoder's device")
+        return _lib.ObsParams(obs["mode"], obs["n_bins"], obs["spw"], obs["threshold_logit"], obs["offset"], obs["scale"],
+                              prior.data_ptr() if prior is not None else None)
+
+    def workspace_bytes_logits(self, obs: dict, B: int, T: int) -> int:
+        """Workspace bytes of ``decode_logits`` (a full delta history in the wave layout, nothing for emissions); 0 when the
+        fused kernel does not serve this plan or builder geometry (see ``decode_logits``)."""
+        op = self._obs_struct(obs)
+        return int(_lib.load().vit_workspace_bytes_logits(self._plan, ctypes.byref(op), int(B), int(T)))
+
+    def decode_logits(self, logits: torch.Tensor, obs: dict, lengths: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.int64,
+                      emissions_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Pitch logits -> (states, loglik) in one forward launch (``vit_decode_logits``): the emission builder runs inside the
+        forward pass and its rows never reach device memory -- no ``[B, T, S]`` emission tensor (44 GB for 1024 songs of 30000
+        frames).  ``logits``: ``[B, T, cols]`` or ``[T, cols]`` float32 on the GPU, ``cols`` = n_bins ("softmax": n_bins + 1,
+        unvoiced first); ``obs``: ``obs_params(...)``.  States and log-likelihoods are bit-identical to the builder of
+        ``emissions.py`` followed by ``decode(algo="wave")``.  ``emissions_out``: an optional contiguous float32 ``[B, T, S]`` (or
+        ``[T, S]``) tensor that also receives the emission rows (frames inside a song's length).  For plans with the wave form
+        whose extra column is the last state (S = 321 / 361) and the reference's builder geometries; anything else raises
+        ``ViterbiHipError`` before anything is enqueued.  ``workspace``: as for ``decode_checkpointed``."""
+        lib = _lib.load()
+        if not isinstance(logits, torch.Tensor) or logits.device != self.device:
+            raise ValueError("logits must be a torch tensor on the decoder's device")
+        cols = obs["n_bins"] + (1 if obs["mode"] == 1 else 0)
+        single = logits.dim() == 2
+        lg = logits.unsqueeze(0) if single else logits
+        if lg.dtype != torch.float32 or lg.dim() != 3 or lg.shape[2] != cols or lg.shape[1] < 1 or not lg.is_contiguous():
+            raise ValueError(f"logits must be a C-contiguous float32 [B,T,{cols}] or [T,{cols}] tensor with T >= 1")
+        B, T, _ = lg.shape
+        if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
+            raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
+        if emissions_out is not None:
+            eo = emissions_out
+            if (eo.dtype != torch.float32 or eo.device != self.device or not eo.is_contiguous() or
+                    tuple(eo.shape) != ((T, self.S) if single else (B, T, self.S))):
+                raise ValueError(f"emissions_out must be a contiguous float32 tensor shaped like the logits with {self.S} columns")
+        op = self._obs_struct(obs)
+        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
+        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
+        if B > 0:
+            need = int(lib.vit_workspace_bytes_logits(self._plan, ctypes.byref(op), B, T))
+            if need == 0:
+                raise _lib.ViterbiHipError("the fused logits decode needs a plan with the wave form whose extra column is the last state "
+                                           "(S = 321 / 361), n_bins = S - 1, and a builder geometry of the reference (shaun / scaled "
+                                           "softmax with peak width 5, softmax with 15): build the emissions and use decode()")
+            ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
+                raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
+            with torch.cuda.device(self.device):
+                rc = lib.vit_decode_logits(self._plan, lg.data_ptr(), ctypes.byref(op), B, T, lengths.data_ptr() if lengths is not None else None,
+                                           (ws.data_ptr() + 255) & ~255, ws.numel() - 256, emissions_out.data_ptr() if emissions_out is not None else None,
+                                           states.data_ptr(), loglik.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(rc, "vit_decode_logits")
+            if workspace is None:
+                torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
+        if out_dtype != torch.int32:
+            states = states.to(out_dtype)
+        return (states[0], loglik[0]) if single else (states, loglik)
+
     def voicing(self, states: torch.Tensor, n_bins: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """voiced = state < n_bins, bins = min(state, n_bins-1) (tonet/for_paper.py:1828-1829)."""
         n_bins = self.S - 1 if n_bins is None else int(n_bins)

@@ -184,6 +184,34 @@ class _PreparedViterbi:
             return self._decoder.voicing(states, self.num_freq_bins)
         return self._decoder.voicing_notes(states, note_range, self.num_freq_bins)
 
+    def _obs_params(self) -> dict:
+        """This class's emission-builder arguments for ``ViterbiDecoder.decode_logits``, computed as emissions.py computes them."""
+        raise NotImplementedError
+
+    def decode_logits_batch(self, logits, lengths=None, note_range=None, fused=False):
+        """``decode_logits`` over a batch: logits ``[B, frames, columns]`` (NumPy or torch), ``lengths`` an optional int64 ``[B]``
+        tensor (frames past a song's length: voiced False, bins -1).  Returns ``(voiced bool[B, T], bins int32[B, T])`` plus
+        ``notes float32[B, T]`` when ``note_range`` is given; row b equals ``decode_logits(logits[b])``.
+        ``fused=False``: the emission builder into a ``[B, T, S]`` tensor, then ``decode``.  ``fused=True``: one forward launch that
+        builds the emissions where they are consumed (``ViterbiDecoder.decode_logits``; no emission tensor: B * T * S * 4 bytes
+        less device memory), the same bits; raises ``ViterbiHipError`` where the plan is not served (the 722-state grids).
+        Measured on one MI355X (`[B, 30000, 360]`, profiles/fused_logits_time.json): the fused path is slower at every batch size --
+        2.7x at 256 songs, 1.7x at 512, 1.23-1.27x at 1024 and 2048 -- there is no crossover, so it is for batches whose emission
+        tensor does not fit, and the default stays unfused."""
+        dev = self._decoder.device
+        lg = logits if isinstance(logits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(logits, np.float32))
+        lg = lg.to(dev).contiguous()
+        assert lg.dim() == 3
+        if lengths is not None:
+            lengths = (lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths), dtype=torch.int64)).to(dev)
+        if fused:
+            states, _ = self._decoder.decode_logits(lg, self._obs_params(), lengths=lengths, out_dtype=torch.int32)
+        else:
+            states, _ = self._decoder.decode(self._log_emissions(lg), lengths=lengths, out_dtype=torch.int32)
+        if note_range is None:
+            return self._decoder.voicing(states, self.num_freq_bins)
+        return self._decoder.voicing_notes(states, note_range, self.num_freq_bins)
+
     def decode_recordings(self, logits_list):
         """Many recordings in ONE pass: what the reference does recording by recording (one ``viterbi(logits)`` call each,
         tonet/for_paper.py:2304-2319) as a single emission-builder launch over the concatenated frames, a single packed decode
@@ -240,6 +268,12 @@ class Viterbi(_PreparedViterbi):
         from .emissions import shaun_log_emissions
         return shaun_log_emissions(logits, self.voicing_threshold, self.single_side_peak_width)
 
+    def _obs_params(self):
+        import math
+        th, p = self.voicing_threshold, 0.8                 # shaun_log_emissions' defaults: p = 0.8, scale = 2.0
+        return ViterbiDecoder.obs_params("shaun", self.num_freq_bins, self.single_side_peak_width, math.log(th / (1.0 - th)),
+                                         math.log(p / (1.0 - p)), 2.0)
+
 
 class SoftMaxViterbi(_PreparedViterbi):
     """Family C (tonet/for_paper.py:1873-2037): C-contiguous [T, S] probabilities (values may
@@ -264,6 +298,9 @@ class SoftMaxViterbi(_PreparedViterbi):
         from .emissions import softmax_log_emissions
         return softmax_log_emissions(logits, self.single_side_peak_width)
 
+    def _obs_params(self):
+        return ViterbiDecoder.obs_params("softmax", self.num_freq_bins, self.single_side_peak_width)
+
 
 class ScaledSoftMaxViterbi(SoftMaxViterbi):
     """dcnet's SoftMaxViterbi (dcnet/softmax_viterbi.py:2486-2674; same class in ftanet / jdc / msnet): logits carry
@@ -284,6 +321,12 @@ class ScaledSoftMaxViterbi(SoftMaxViterbi):
     def _log_emissions(self, logits):
         from .emissions import softmax_scaled_log_emissions
         return softmax_scaled_log_emissions(logits, self.voicing_threshold_prob, self._prior_dev, self.single_side_peak_width)
+
+    def _obs_params(self):
+        vth = np.float32(self.voicing_threshold_prob)       # float32 arithmetic, as softmax_scaled_log_emissions hands it to the kernel
+        unvoiced_logit = float(np.log(vth / (np.float32(1) - vth)))
+        return ViterbiDecoder.obs_params("softmax_scaled", self.num_freq_bins, self.single_side_peak_width, unvoiced_logit,
+                                         prior=self._prior_dev)
 
 
 class RecordingAccumulator:
