@@ -333,6 +333,35 @@ int vit_obs_softmax(const float *logits, int64_t n_frames, int32_t n_bins, int32
 int vit_obs_softmax_scaled(const float *logits, int64_t n_frames, int32_t n_bins, int32_t spw, double unvoiced_logit,
                            const float *prior, float *logE, vit_stream stream);
 
+/*
+ * Activation front-end of imm's decoder (Viterbi.process_HF0_fn, imm/tf_imm.py:70-88; the decoder it feeds is
+ * Viterbi.__call__, :129-135): NMF source activations -> log-emissions in the [frames, n_bins+1] layout vit_decode() /
+ * vit_decode_packed() read (unvoiced state last).  Per recording the reference takes t = the smallest positive entry
+ * (replaced by exp(-87) when log(t) < -87), E = log(HF0 + t), pads one unvoiced row filled with min(E) and transposes.
+ *   hf0          : device, float32 [n_bins, total_frames] bins x frames with row stride ld >= total_frames (elements); B
+ *                  recordings side by side along the frame axis, recording b owns columns offsets[b] .. offsets[b+1]-1
+ *   offsets_dev  : DEVICE, [B+1] int64, offsets[0] = 0, strictly increasing, offsets[B] = total_frames (not checked: the call
+ *                  does not read device memory on the host; whatever it holds, no access leaves the buffers)
+ *   clamp_below, clamp_to : t = (min positive < clamp_below) ? clamp_to : min positive.  The caller derives both on the host --
+ *                  clamp_to = float32(exp(-87)), clamp_below = the smallest float32 x with not (log(x) < -87) under the log
+ *                  it wants to match -- so the clamp decision is a compare of bit patterns and never the device's log
+ *   stats        : device float32 [B][4] = {min positive, min, t, _min}, written by the call (valid once it has run on its
+ *                  stream; _min = the minimum of the values written to columns 0 .. n_bins-1 of that recording's rows)
+ *   logE         : device [total_frames, n_bins+1] float32 or float16 (out_dtype; the float16 value is the float32 value
+ *                  rounded to nearest even).  logE[offsets[b] + n][u] = log(hf0[u][n] + t_b) for u < n_bins -- a float32 add
+ *                  and the device's accurate logf, a few ulp from NumPy's --, column n_bins = _min_b, bit-equal to the minimum
+ *                  of the recording's other columns.  The minima are reduced on bit patterns: exact, order-independent, a
+ *                  subnormal counts as positive.
+ * Every statistic is per recording, as the reference calls the function once per recording.  Contract: entries finite and >= 0,
+ * at least one positive entry per recording (the reference raises otherwise; here the output is then unspecified, nothing
+ * faults), 1 <= n_bins <= 1023, every recording holds at least one frame.  VIT_EINVAL: a null pointer, ld < total_frames,
+ * n_bins out of range, B < 1, total_frames < B, a bad out_dtype.  Four kernel launches on `stream`; no host synchronisation,
+ * no allocation.
+ */
+int vit_obs_activations(const float *hf0, int64_t ld, int32_t n_bins, int64_t B, const int64_t *offsets_dev,
+                        int64_t total_frames, float clamp_below, float clamp_to, float *stats, void *logE, int out_dtype,
+                        vit_stream stream);
+
 /* Self-test hook of the wave-wide DPP scan primitives the kernels are built on (tests/test_gpu_parity.py): vals [n_waves*64]
  * device float32; mode 0 / 1 ordered (value, index) first-maximum scan forward / reverse, 2 value-only prefix maximum, 3 the
  * prefix maximum shifted up one lane, 4 wave-wide maximum; out_v / out_i [n_waves*64]. */

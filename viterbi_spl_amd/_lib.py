@@ -22,7 +22,7 @@ EXPORTS = (
     "vit_forward", "vit_backtrace", "vit_voicing_map", "vit_obs_shaun", "vit_obs_softmax", "vit_obs_softmax_scaled", "vit_plan_set_option", "vit_snippets_append", "vit_voicing_notes",
     "vit_workspace_bytes_for", "vit_debug_scan", "vit_backtrace_counters", "vit_workspace_bytes_checkpointed", "vit_decode_checkpointed",
     "vit_backtrace_checked", "vit_forward_family", "vit_workspace_bytes_packed", "vit_decode_packed",
-    "vit_workspace_bytes_logits", "vit_decode_logits",
+    "vit_workspace_bytes_logits", "vit_decode_logits", "vit_obs_activations",
 )
 ABI_VERSION = 4
 
@@ -124,6 +124,8 @@ def load() -> ctypes.CDLL:
     lib.vit_obs_softmax.argtypes = [vp, i64, i32, i32, vp, vp]
     lib.vit_obs_softmax_scaled.restype = i32
     lib.vit_obs_softmax_scaled.argtypes = [vp, i64, i32, i32, f64, vp, vp, vp]
+    lib.vit_obs_activations.restype = i32
+    lib.vit_obs_activations.argtypes = [vp, i64, i32, i64, vp, i64, ctypes.c_float, ctypes.c_float, vp, vp, i32, vp]
     lib.vit_snippets_append.restype = i32
     lib.vit_snippets_append.argtypes = [vp, i32, i32, i32, i32, vp, i64, vp]
     lib.vit_voicing_notes.restype = i32

@@ -1165,6 +1165,19 @@ int vit_obs_softmax_scaled(const float* logits, int64_t n_frames, int32_t n_bins
     return e == hipSuccess ? VIT_OK : hip_fail(e);
 }
 
+int vit_obs_activations(const float* hf0, int64_t ld, int32_t n_bins, int64_t B, const int64_t* offsets_dev, int64_t total_frames,
+                        float clamp_below, float clamp_to, float* stats, void* logE, int out_dtype, vit_stream stream) {
+    if (!hf0 || !offsets_dev || !stats || !logE) return VIT_EINVAL;
+    if (n_bins < 1 || n_bins > 1023 || B < 1 || B > (int64_t)1 << 30 || total_frames < B || total_frames > (int64_t)1 << 36) return VIT_EINVAL;
+    if (ld < total_frames) return VIT_EINVAL;
+    if (out_dtype != VIT_F32 && out_dtype != VIT_F16) return VIT_EINVAL;
+    uint32_t below_bits;
+    memcpy(&below_bits, &clamp_below, sizeof(below_bits));
+    hipError_t e = vit::launch_activations(hf0, ld, n_bins, (int)B, offsets_dev, total_frames, below_bits, clamp_to, stats, logE,
+                                           out_dtype == VIT_F16, (hipStream_t)stream);
+    return e == hipSuccess ? VIT_OK : hip_fail(e);
+}
+
 int vit_snippets_append(const float* snippets, int32_t n_snippets, int32_t n_channels, int32_t n_frames, int32_t mode,
                         float* rows_out, int64_t n_rows, vit_stream stream) {
     if (n_snippets < 0 || n_channels < 2 || n_frames < 1 || (mode != 0 && mode != 1) || n_rows < 0 ||

@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface between the C ABI (capi.hip) and the kernel files (dense, step, banded, wave, emission, fused,
+// kernels.hpp -- launch interface between the C ABI (capi.hip) and the kernel files (dense, step, banded, wave, emission, activations, fused,
 // backtrace_rows / _sparse / _half / _lane .hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -217,6 +217,10 @@ hipError_t launch_obs_shaun(const float* logits, int64_t n_frames, int U, int sp
 hipError_t launch_obs_softmax(const float* logits, int64_t n_frames, int U, int spw, float* out, hipStream_t st);
 hipError_t launch_obs_softmax_scaled(const float* logits, int64_t n_frames, int U, int spw, double unvoiced_logit,
                                      const float* prior, float* out, hipStream_t st);
+// activations.hip: imm's activation front-end (vit_obs_activations): hf0 [U, total] with row stride ld -> log(hf0 + t_b) transposed to
+// [total, U + 1], statistics per recording into stats [B][4]
+hipError_t launch_activations(const float* hf0, int64_t ld, int U, int B, const int64_t* offsets, int64_t total, uint32_t clamp_below_bits,
+                              float clamp_to, float* stats, void* out, bool f16, hipStream_t st);
 hipError_t launch_snippets_append(const float* snips, int n, int C, int F, int mode, float* out, int64_t rows, hipStream_t st);
 hipError_t launch_voicing_notes(const int32_t* states, int64_t n, int32_t n_bins, const float* note_range, uint8_t* voiced,
                                 int32_t* bins, float* notes, float* notes_v, hipStream_t st);

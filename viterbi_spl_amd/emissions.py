@@ -9,6 +9,7 @@ visit the host (the ``.cpu().numpy()`` round trip at tonet/for_paper.py:2282).
 """
 from __future__ import annotations
 
+import functools
 import math
 
 import numpy as np
@@ -92,3 +93,68 @@ def softmax_scaled_log_emissions(logits: torch.Tensor, voicing_threshold_prob: f
                                                 torch.cuda.current_stream(logits.device).cuda_stream)
     _lib.check(rc, "vit_obs_softmax_scaled")
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def activation_clamp_constants():
+    """``(clamp_below, clamp_to)`` of ``vit_obs_activations`` as float32 scalars: the reference replaces the smallest positive
+    activation ``t`` by ``exp(-87)`` when ``np.log(t) < -87`` (imm/tf_imm.py:81-82).  ``clamp_below`` is the smallest float32 whose
+    NumPy float32 log is NOT below -87, found by bisection over the bit patterns of the positive floats, so that the kernel
+    decides the clamp with an integer compare and agrees with the host for every input."""
+    def below(bits):
+        return bool(np.log(np.uint32(bits).view(np.float32)) < -87)
+    lo, hi = 1, 0x3F800000                 # the smallest subnormal (log = -103.3) .. 1.0
+    assert below(lo) and not below(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if below(mid):
+            lo = mid
+        else:
+            hi = mid
+    return np.uint32(hi).view(np.float32), np.float32(np.exp(-87))
+
+
+def activation_log_emissions(hf0: torch.Tensor, offsets=None, out: torch.Tensor | None = None, dtype: torch.dtype = torch.float32,
+                             return_stats: bool = False):
+    """imm's ``Viterbi.process_HF0_fn`` (imm/tf_imm.py:70-88) on the GPU: source activations ``hf0 [U, N]`` (bins x frames,
+    float32, unit stride along frames; a column slice of a wider buffer is fine) -> log-emissions ``[N, U + 1]`` in ``dtype``
+    (float32 or float16), the layout ``decode`` / ``decode_packed`` read: ``log(hf0 + t)`` transposed, the unvoiced column
+    filled with the minimum of the others (``vit_obs_activations``).  ``offsets``: B + 1 frame offsets from 0 to N when ``hf0``
+    holds B recordings side by side (host sequence or int64 tensor; None: one recording) -- ``t`` and the minimum are per
+    recording, as the reference computes them.  ``return_stats=True``: also the float32 ``[B, 4]`` tensor
+    ``{min positive, min, t, _min}`` per recording.  Entries must be finite and >= 0 with a positive one in every recording."""
+    if not isinstance(hf0, torch.Tensor) or hf0.device.type != "cuda":
+        raise ValueError("hf0 must be a torch tensor on a ROCm GPU (there is no CPU path)")
+    if hf0.dtype != torch.float32 or hf0.dim() != 2 or hf0.shape[0] < 1 or hf0.shape[0] > 1023 or hf0.shape[1] < 1:
+        raise ValueError("hf0 must be float32 [U, N] with 1 <= U <= 1023 and N >= 1")
+    U, N = int(hf0.shape[0]), int(hf0.shape[1])
+    if hf0.stride(1) != 1 or (U > 1 and hf0.stride(0) < N):
+        raise ValueError("hf0 must have unit stride along frames and a row stride >= N")
+    ld = int(hf0.stride(0)) if U > 1 else N
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError("dtype must be torch.float32 or torch.float16")
+    if offsets is None:
+        offsets = [0, N]
+    if isinstance(offsets, torch.Tensor) and offsets.device == hf0.device:
+        if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 2 or not offsets.is_contiguous():
+            raise ValueError("offsets must be a contiguous int64 [B + 1] tensor")
+        off_dev = offsets                                       # (device-resident: taken as it is, no host visit)
+    else:
+        off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
+        if off.ndim != 1 or off.size < 2 or off[0] != 0 or (np.diff(off) < 1).any() or off[-1] != N:
+            raise ValueError("offsets must be B + 1 strictly increasing frame offsets from 0 to the number of frames")
+        off_dev = torch.from_numpy(off).to(hf0.device)
+    B = int(off_dev.numel()) - 1
+    shape = (N, U + 1)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=hf0.device)
+    elif out.dtype != dtype or tuple(out.shape) != shape or out.device != hf0.device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {dtype} {shape} tensor on hf0's device")
+    stats = torch.empty((B, 4), dtype=torch.float32, device=hf0.device)
+    clamp_below, clamp_to = activation_clamp_constants()
+    with torch.cuda.device(hf0.device):
+        rc = _lib.load().vit_obs_activations(hf0.data_ptr(), ld, U, B, off_dev.data_ptr(), N, float(clamp_below), float(clamp_to),
+                                             stats.data_ptr(), out.data_ptr(), _lib.VIT_F16 if dtype == torch.float16 else _lib.VIT_F32,
+                                             torch.cuda.current_stream(hf0.device).cuda_stream)
+    _lib.check(rc, "vit_obs_activations")
+    return (out, stats) if return_stats else out

@@ -15,6 +15,7 @@ last bit a GPU cannot be trusted to reproduce.
   TF eager  tf_viterbi_librosa_fn(*, tf_log_transition_matrix_T, ...) -> int32    imm/tf_viterbi.py:8-72
   family B  Viterbi.viterbi_librosa_fn(self, probs_st)          tonet/for_paper.py:1833-1870
   family C  SoftMaxViterbi.viterbi_librosa_fn(self, probs_ts)   tonet/for_paper.py:1999-2037
+  imm       Viterbi(bins_per_semitone, n_bins).__call__(HF0)    imm/tf_imm.py:48-135, call site :692  (ImmViterbi here)
 """
 from __future__ import annotations
 
@@ -327,6 +328,125 @@ class ScaledSoftMaxViterbi(SoftMaxViterbi):
         unvoiced_logit = float(np.log(vth / (np.float32(1) - vth)))
         return ViterbiDecoder.obs_params("softmax_scaled", self.num_freq_bins, self.single_side_peak_width, unvoiced_logit,
                                          prior=self._prior_dev)
+
+
+# ----------------------------------------------------------------------------- imm's decoder (activations in)
+class ImmViterbi:
+    """imm's ``Viterbi`` (imm/tf_imm.py:48-135): the dense Durrieu matrix over ``n_bins`` pitch bins plus the unvoiced state,
+    a uniform prior, and a front-end that turns NMF source activations ``HF0 [n_bins, T]`` into log-emissions.
+
+    Constructor as in the reference (:51-68): ``log_transition_matrix_T = np.log(A.T)`` with NO ``tiny`` added (the matrix is
+    asserted positive), float32 C order; ``log_prob_init`` = the uniform prior logged in float64, then cast to float32.
+
+    * ``process_HF0_fn`` / ``viterbi_librosa_fn`` -- the reference's two steps with its array conventions: the first is host
+      NumPy and byte-equal to the reference's, the second decodes on the GPU and is bit-exact.
+    * ``__call__(HF0)`` -- the reference's call surface (``int64[T]`` states as NumPy), with the front-end on the GPU as well
+      (``vit_obs_activations``): float32 add, the device's ``logf`` (a few ulp from NumPy's; the path can differ from the
+      host-exact one only where two paths tie to that precision), the clamp decided exactly as the host decides it.
+    * ``decode_activations`` / ``decode_activations_recordings`` -- the same with torch tensors that stay on the GPU, one
+      recording or many in one builder launch and one packed decode.
+
+    ``emission_dtype``: storage of the emission tensor the GPU front-end writes, "float32" or "float16" (the float32 value
+    rounded to nearest even; the range [-87.4, 89] fits).
+
+    A note on NumPy versions: the reference adds ``np.exp(-87)``, a float64 scalar, in the clamp case.  NumPy 1.x keeps the
+    float32 array type there; NumPy >= 2 promotes the sum to float64, and the reference's own ``viterbi_librosa_fn`` then
+    rejects the result.  ``process_HF0_fn`` follows whichever NumPy runs, like the reference; the GPU front-end always adds in
+    float32 (``clamp_to = float32(exp(-87))``)."""
+
+    def __init__(self, bins_per_semitone, n_bins, device=None, emission_dtype="float32"):
+        from .synth import durrieu_transition
+        self.b = bins_per_semitone
+        self.n_bins = n_bins
+        A = durrieu_transition(n_bins=n_bins, bins_per_semitone=bins_per_semitone)
+        assert np.all(A > 0)
+        t = np.log(A.T)
+        assert not np.any(np.isneginf(t))
+        self.log_transition_matrix_T = np.require(t, np.float32, ['C'])
+        p = np.empty([n_bins + 1])
+        p.fill(1. / (n_bins + 1))
+        self.log_prob_init = np.log(p).astype(np.float32)
+        if emission_dtype not in ("float32", "float16"):
+            raise ValueError('emission_dtype must be "float32" or "float16"')
+        self.emission_dtype = emission_dtype
+        self._device = device
+        self._dec = None
+
+    @property
+    def _decoder(self) -> ViterbiDecoder:
+        """The plan on the GPU, made on first use: the parameters and ``process_HF0_fn`` are host-only."""
+        if self._dec is None:
+            self._dec = ViterbiDecoder(self.log_transition_matrix_T, self.log_prob_init, self._device)
+        return self._dec
+
+    # ---- the reference's two steps
+    def process_HF0_fn(self, HF0):
+        """Host NumPy, the reference's arithmetic operation by operation (imm/tf_imm.py:70-88): ``[n_bins, T]`` activations ->
+        ``[n_bins + 1, T]`` log-emissions, the unvoiced row last."""
+        HF0 = _to_numpy(HF0)
+        assert isinstance(HF0, np.ndarray)
+        assert HF0.shape[0] == self.n_bins
+        t = HF0[HF0 > 0].min()                       # (raises on an empty mask, as the reference does)
+        if np.log(t) < -87:
+            t = np.exp(-87)
+        log_HF0 = np.log(HF0 + t)
+        return np.pad(log_HF0, [[0, 1], [0, 0]], mode='constant', constant_values=np.min(log_HF0))
+
+    def viterbi_librosa_fn(self, log_HF0):
+        """``[n_bins + 1, T]`` float32 log-emissions -> ``int64[T]`` states (imm/tf_imm.py:90-127); bit-exact."""
+        S = self.n_bins + 1
+        assert isinstance(log_HF0, np.ndarray)
+        assert log_HF0.dtype == np.float32
+        assert log_HF0.shape[0] == S
+        probs = np.require(np.transpose(log_HF0), np.float32, ['C'])
+        return _run(self.log_transition_matrix_T, self.log_prob_init, probs, self._decoder)
+
+    # ---- activations in, path out, on the GPU
+    def _torch_dtype(self):
+        return torch.float16 if self.emission_dtype == "float16" else torch.float32
+
+    def _to_device(self, HF0) -> torch.Tensor:
+        x = HF0 if isinstance(HF0, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(_to_numpy(HF0), np.float32))
+        x = x.to(device=self._decoder.device, dtype=torch.float32)
+        if x.dim() != 2 or x.shape[0] != self.n_bins or x.shape[1] < 1:
+            raise ValueError(f"HF0 must be [{self.n_bins}, T] with T >= 1")
+        return x if x.stride(1) == 1 and (x.stride(0) >= x.shape[1] or x.shape[0] == 1) else x.contiguous()
+
+    def decode_activations(self, HF0) -> torch.Tensor:
+        """``HF0 [n_bins, T]`` (NumPy or torch) -> ``int64[T]`` states as a torch tensor on the decoder's device: the emission
+        builder (``emissions.activation_log_emissions``) and the decode, no host visit for GPU-resident activations."""
+        from .emissions import activation_log_emissions
+        E = activation_log_emissions(self._to_device(HF0), dtype=self._torch_dtype())
+        states, _ = self._decoder.decode(E, out_dtype=torch.int64)
+        return states
+
+    def decode_activations_recordings(self, hf0_cat, offsets=None):
+        """Many recordings in one pass: ``hf0_cat [n_bins, sum T_b]`` holds them side by side along the frame axis, recording b in
+        columns ``offsets[b] : offsets[b+1]`` (``offsets``: a host sequence of B + 1 frame offsets from 0).  One emission-builder
+        call with per-recording statistics and one packed decode (``vit_decode_packed``; the step-structured plan of the Durrieu
+        matrix is served there).  ``hf0_cat`` may also be a list of ``[n_bins, T_b]`` tensors or arrays, which are concatenated
+        along frames first -- that is a copy of every recording; callers that can should fill one buffer.  Returns a list of
+        ``int64[T_b]`` state tensors on the GPU, each equal to ``decode_activations`` of that recording alone."""
+        from .emissions import activation_log_emissions
+        if isinstance(hf0_cat, (list, tuple)):
+            if offsets is not None:
+                raise ValueError("offsets come from the list's lengths")
+            parts = [self._to_device(x) for x in hf0_cat]
+            if not parts:
+                return []
+            offsets = np.concatenate([[0], np.cumsum([int(x.shape[1]) for x in parts])])
+            hf0_cat = torch.cat(parts, dim=1)
+        elif offsets is None:
+            raise ValueError("offsets are required with a concatenated hf0")
+        x = self._to_device(hf0_cat)
+        off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
+        E = activation_log_emissions(x, offsets=off, dtype=self._torch_dtype())
+        states, _ = self._decoder.decode_packed(E, off, out_dtype=torch.int64)
+        return [states[off[b]:off[b + 1]] for b in range(off.size - 1)]
+
+    def __call__(self, HF0):
+        """``viterbi(HF0) -> int64[T]`` states as a NumPy array, the reference's call surface (imm/tf_imm.py:129-135, :692)."""
+        return self.decode_activations(HF0).cpu().numpy()
 
 
 class RecordingAccumulator:

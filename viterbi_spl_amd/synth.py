@@ -134,6 +134,28 @@ def emissions_scaled(B: int, T: int, S: int, seed: int = 0, device="cpu", dtype=
     return out
 
 
+def hf0_activations(U: int, T: int, seed: int = 0, device="cpu", denormal_min: bool = False) -> torch.Tensor:
+    """Synthetic NMF source activations ``HF0 [U, T]`` float32 (bins x frames), the input of imm's decoder
+    (imm/tf_imm.py:70-88, :692): non-negative, one entry in eight exactly zero, the rest spread over 2^-40 .. 2^4 (a wide dynamic
+    range, as NMF activations have) and three large partials (2^4 .. 2^10) per frame, so every frame holds a positive entry.
+    The float32 bit patterns are assembled from integer hashes (exponent field and mantissa): no libm call, the same bits on
+    the host and on the GPU.  ``denormal_min=True`` plants one subnormal entry (about 1e-42), the recording's smallest positive
+    value: the case in which the reference replaces it by exp(-87)."""
+    rows = _row_hash(_song_base(seed ^ 0x2545F491, 0), U, device)
+    cols = torch.arange(T, dtype=torch.int64, device=device)
+    h = _cell_hash(rows, cols)                                              # [U, T]
+    bits = ((87 + (h >> 3) % 44) << 23) | (_mix32(h ^ 0x9E3779B9) & 0x7FFFFF)
+    bits = torch.where(h % 8 == 0, torch.zeros_like(bits), bits)
+    fh = _mix32(_mul32(cols, 0x85EBCA6B) ^ _song_base(seed ^ 0x27220A95, 1))
+    for k in range(3):
+        pos = _mix32(fh ^ (0x7000 + k)) % U
+        bits[pos, cols] = ((131 + _mix32(fh ^ (0x7100 + k)) % 6) << 23) | (_mix32(fh ^ (0x7200 + k)) & 0x7FFFFF)
+    if denormal_min:
+        b = _song_base(seed ^ 0x632BE5AB, 2)
+        bits.view(-1)[b % (U * T)] = 0x200 + (b >> 20)
+    return bits.to(torch.int32).view(torch.float32)
+
+
 def emissions_ties(B: int, T: int, S: int, seed: int = 0, device="cpu", dtype=torch.float32) -> torch.Tensor:
     """Adversarial-tie emissions: values from {0, -1, -2} only, so many
     candidates coincide exactly and the lowest-index tie-break decides."""
