@@ -247,6 +247,40 @@ int vit_decode_packed(const vit_plan *plan, const void *logE, int emis_dtype, in
                       void *workspace, size_t workspace_bytes, int32_t *states, float *loglik, vit_stream stream);
 
 /*
+ * Packed decode under a workspace budget: vit_decode_packed() with the bounded workspace of vit_decode_checkpointed().  The
+ * reference decodes one recording at a time, each with its own length (tonet/for_paper.py:2304-2309), and keeps its work buffers
+ * T1 / T2 for that one recording (:1852-1853); vit_decode_packed keeps a delta row for every frame it is handed.
+ *   logE, offsets, states, loglik : exactly as for vit_decode_packed (offsets on the HOST; states packed, no -1 entries)
+ *   segment_frames : the rule of vit_decode_checkpointed: 64 <= K <= 2^24, a value above the longest song acts like that length
+ *                    (out of range: VIT_EINVAL, size 0)
+ * Segments are per song: song b has n_b = ceil(T_b / K).  Pass 1 is the packed forward pass (min(B, 8 x compute units, total frames /
+ * longest song) wavefronts walking host-packed song lists) and keeps the delta row in front of every segment but a song's first --
+ * sum (n_b - 1) <= total frames / K rows -- and every song's terminal state and log-likelihood.  Pass 2 works on (song, segment)
+ * units, one wavefront each: the units of a song run from its last segment to its first, units of different songs are independent;
+ * the host lists the launches up front, each with up to n_units = min(B, 8 x compute units) units, at most one per song, the songs
+ * with the most segments left first -- about max(longest n_b, total units / n_units) launches.  A launch re-runs the forward
+ * recursion of its units from their checkpoint rows into K + 1 rows per unit and back-traces them (the sparse back-trace of
+ * vit_decode_checkpointed).  States and log-likelihoods are bit-identical to vit_decode_packed on the same input, hence to
+ * vit_decode() of each song alone; about twice the forward work.
+ * Workspace: n_units x (K + 1) rows + sum (n_b - 1) checkpoint rows + one scratch row per wavefront of pass 1, 64 * ceil(S / 64)
+ * floats each, + the tables: it depends on the lengths, so the size function takes `offsets` (256-byte aligned base required).
+ * Which plans: plans with the wave form (vit_plan_info reserved[2] bit 3): the reference's 321- and 361-state matrices.  Every
+ * other plan (the 722-state floor and step plans, unstructured matrices, scan-only banded plans) gets size 0 and VIT_EUNSUPPORTED
+ * before anything is enqueued; a size > 0 means the decode launches.  Honoured options: "wave_uniform", "wave_two",
+ * "bt_fast_rows"; ignored: "wave_history", "forward_form", "backtrace_form", "bt_chunks", "bt_warm", "wave_min_batch".
+ * VIT_EINVAL: a null pointer, offsets that do not start at 0 or do not increase strictly, K out of range, a bad dtype;
+ * VIT_EWORKSPACE: a workspace below the size function's answer.  The tables (slot lists, unit lists, checkpoint bases) are built on
+ * the host and go through the plan's pinned staging buffer in one upload: the call waits for the previous upload from that buffer
+ * (this call's or vit_decode_packed's) and synchronises nowhere else; no device allocation.  Not thread-safe against concurrent
+ * packed decodes on the same plan.  The library does not record this call for vit_backtrace().
+ */
+size_t vit_workspace_bytes_packed_checkpointed(const vit_plan *plan, int64_t B, const int64_t *offsets /* HOST, [B+1] */,
+                                               int64_t segment_frames);
+int vit_decode_packed_checkpointed(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B, const int64_t *offsets,
+                                   void *workspace, size_t workspace_bytes, int32_t *states, float *loglik,
+                                   int64_t segment_frames, vit_stream stream);
+
+/*
  * Fused logits -> path decode: what callers of the reference run is Viterbi.__call__ (tonet/for_paper.py:1817-1831) -- pitch
  * logits -> observation log-probabilities -> Viterbi decode.  vit_obs_*() + vit_decode() do that with a [B,T,S] float32
  * emission tensor written to and read back from device memory (2 x 4 S bytes per frame, 44 GB for [1024, 30000, 361]); here the

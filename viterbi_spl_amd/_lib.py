@@ -23,6 +23,7 @@ EXPORTS = (
     "vit_workspace_bytes_for", "vit_debug_scan", "vit_backtrace_counters", "vit_workspace_bytes_checkpointed", "vit_decode_checkpointed",
     "vit_backtrace_checked", "vit_forward_family", "vit_workspace_bytes_packed", "vit_decode_packed",
     "vit_workspace_bytes_logits", "vit_decode_logits", "vit_obs_activations",
+    "vit_workspace_bytes_packed_checkpointed", "vit_decode_packed_checkpointed",
 )
 ABI_VERSION = 4
 
@@ -109,6 +110,10 @@ def load() -> ctypes.CDLL:
     lib.vit_workspace_bytes_packed.argtypes = [vp, i64, i64]
     lib.vit_decode_packed.restype = i32
     lib.vit_decode_packed.argtypes = [vp, vp, i32, i64, vp, vp, sz, vp, vp, vp]
+    lib.vit_workspace_bytes_packed_checkpointed.restype = sz
+    lib.vit_workspace_bytes_packed_checkpointed.argtypes = [vp, i64, vp, i64]
+    lib.vit_decode_packed_checkpointed.restype = i32
+    lib.vit_decode_packed_checkpointed.argtypes = [vp, vp, i32, i64, vp, vp, sz, vp, vp, i64, vp]
     lib.vit_workspace_bytes_logits.restype = sz
     lib.vit_workspace_bytes_logits.argtypes = [vp, ctypes.POINTER(ObsParams), i64, i64]
     lib.vit_decode_logits.restype = i32

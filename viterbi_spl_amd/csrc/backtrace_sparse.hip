@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
     if (song >= a.B) return;
     if (a.skip_nonpositive && a.lengths[song] < 1) return;        // segment of a checkpointed decode this song does not reach
     const int Tb = song_length(a.lengths, song, T);
-    int32_t* __restrict__ states = a.states + (size_t)song * a.states_stride;
+    int32_t* __restrict__ states = a.states + (a.unit_states ? (size_t)a.unit_states[song] : (size_t)song * a.states_stride);
     const float* __restrict__ hist = a.hist + (size_t)song * a.hist_rows * SD;
     float* tile = tiles + wv * kSpK * kSpRS;
 
@@ -306,7 +306,8 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
     if (MODE == 0) {
         const int lo_c = (int)((long long)Lf * chunk / C), hi_c = (int)((long long)Lf * (chunk + 1) / C);
         if (chunk == C - 1) {
-            for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
+            if (!a.unit_states)          // (a unit of a packed decode: the entries behind it are the next song's)
+                for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
             if (lane == 0) states[Tb - 1] = a.last_state[song];
         }
         int top = hi_c - 1 + a.warm;

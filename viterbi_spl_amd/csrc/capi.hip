@@ -849,6 +849,50 @@ PkLayout pk_layout(const vit_plan* p, int sd_floats, int64_t B, int64_t N) {
     return k;
 }
 
+
+// The plan's pinned staging buffer with room for `bytes` of host tables (vit_decode_packed, vit_decode_packed_checkpointed): waits for the
+// upload of the call before, which read it; pk_stage_sent() records the next one.
+int pk_stage(const vit_plan* plan, size_t bytes) {
+    std::lock_guard<std::mutex> g(plan->mu);
+    if (plan->pk_event) { hipError_t ew = hipEventSynchronize(plan->pk_event); if (ew != hipSuccess) return hip_fail(ew); }
+    else { hipError_t ec = hipEventCreateWithFlags(&plan->pk_event, hipEventDisableTiming); if (ec != hipSuccess) return hip_fail(ec); }
+    if (plan->pk_host_bytes < bytes) {
+        if (plan->pk_host) (void)hipHostFree(plan->pk_host);
+        plan->pk_host = nullptr;
+        plan->pk_host_bytes = 0;
+        hipError_t ea = hipHostMalloc(&plan->pk_host, bytes, hipHostMallocDefault);
+        if (ea != hipSuccess) return hip_fail(ea);
+        plan->pk_host_bytes = bytes;
+    }
+    return VIT_OK;
+}
+
+// forward slots of a packed batch: longest song first into the slot with the fewest frames (ties: fewest songs, lowest slot);
+// slot sl walks songs slot_songs[slot_begin[sl] .. slot_begin[sl+1]), longest first (the rule of sharded.shard_by_length)
+void pk_fill_slots(const int64_t* offsets, int64_t B, int64_t n_slots, int32_t* h_slot_begin, int32_t* h_slot_songs) {
+    std::vector<int32_t> order((size_t)B);
+    for (int64_t b = 0; b < B; ++b) order[(size_t)b] = (int32_t)b;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y]; });
+    typedef std::pair<std::pair<int64_t, int32_t>, int32_t> Load;       // ((frames, songs), slot)
+    std::priority_queue<Load, std::vector<Load>, std::greater<Load>> heap;
+    for (int32_t sl = 0; sl < (int32_t)n_slots; ++sl) heap.push(Load{{0, 0}, sl});
+    std::vector<int32_t> slot_of((size_t)B);
+    std::vector<int32_t> count((size_t)n_slots, 0);
+    for (int32_t sng : order) {
+        Load l = heap.top();
+        heap.pop();
+        slot_of[(size_t)sng] = l.second;
+        ++count[(size_t)l.second];
+        l.first.first += offsets[sng + 1] - offsets[sng];
+        ++l.first.second;
+        heap.push(l);
+    }
+    h_slot_begin[0] = 0;
+    for (int64_t sl = 0; sl < n_slots; ++sl) h_slot_begin[sl + 1] = h_slot_begin[sl] + count[(size_t)sl];
+    std::vector<int32_t> fill(h_slot_begin, h_slot_begin + n_slots);
+    for (int32_t sng : order) h_slot_songs[fill[(size_t)slot_of[(size_t)sng]]++] = sng;     // a slot walks its songs longest first
+}
+
 }  // namespace
 
 size_t vit_workspace_bytes_packed(const vit_plan* plan, int64_t B, int64_t total_frames) {
@@ -910,17 +954,8 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
 
     // ---- host tables in the plan's pinned staging buffer (the previous call's upload must have read it)
     {
-        std::lock_guard<std::mutex> g(plan->mu);
-        if (plan->pk_event) { hipError_t ew = hipEventSynchronize(plan->pk_event); if (ew != hipSuccess) return hip_fail(ew); }
-        else { hipError_t ec = hipEventCreateWithFlags(&plan->pk_event, hipEventDisableTiming); if (ec != hipSuccess) return hip_fail(ec); }
-        if (plan->pk_host_bytes < k.tables_bytes) {
-            if (plan->pk_host) (void)hipHostFree(plan->pk_host);
-            plan->pk_host = nullptr;
-            plan->pk_host_bytes = 0;
-            hipError_t ea = hipHostMalloc(&plan->pk_host, k.tables_bytes, hipHostMallocDefault);
-            if (ea != hipSuccess) return hip_fail(ea);
-            plan->pk_host_bytes = k.tables_bytes;
-        }
+        const int rs = pk_stage(plan, k.tables_bytes);
+        if (rs != VIT_OK) return rs;
     }
     uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
     std::memset(hb, 0, k.tables_bytes);
@@ -932,28 +967,7 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     std::memcpy(h_off, offsets, (size_t)(B + 1) * sizeof(int64_t));
     int64_t max_chunks = 1;
     try {
-        // forward slots: longest song first into the slot with the fewest frames (ties: fewest songs, lowest slot)
-        std::vector<int32_t> order((size_t)B);
-        for (int64_t b = 0; b < B; ++b) order[(size_t)b] = (int32_t)b;
-        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return offsets[x + 1] - offsets[x] > offsets[y + 1] - offsets[y]; });
-        typedef std::pair<std::pair<int64_t, int32_t>, int32_t> Load;       // ((frames, songs), slot)
-        std::priority_queue<Load, std::vector<Load>, std::greater<Load>> heap;
-        for (int32_t sl = 0; sl < (int32_t)k.n_slots; ++sl) heap.push(Load{{0, 0}, sl});
-        std::vector<int32_t> slot_of((size_t)B);
-        std::vector<int32_t> count((size_t)k.n_slots, 0);
-        for (int32_t sng : order) {
-            Load l = heap.top();
-            heap.pop();
-            slot_of[(size_t)sng] = l.second;
-            ++count[(size_t)l.second];
-            l.first.first += offsets[sng + 1] - offsets[sng];
-            ++l.first.second;
-            heap.push(l);
-        }
-        h_slot_begin[0] = 0;
-        for (int64_t sl = 0; sl < k.n_slots; ++sl) h_slot_begin[sl + 1] = h_slot_begin[sl] + count[(size_t)sl];
-        std::vector<int32_t> fill(h_slot_begin, h_slot_begin + k.n_slots);
-        for (int32_t sng : order) h_slot_songs[fill[(size_t)slot_of[(size_t)sng]]++] = sng;     // a slot walks its songs longest first
+        pk_fill_slots(offsets, B, k.n_slots, h_slot_begin, h_slot_songs);      // forward slots: greedy bins by frames, longest song first
         // back-trace streams (one per lane: backtrace_lane.hip): chunks of about (total frames / resident lanes) frames, never shorter
         // than four warm-ups, at most kLaneMaxChunks per song
         // (step plans, lazy back-trace: one WAVE per chunk -- about eight waves per CU, chunks no shorter than the 8 * kBtWarm frames
@@ -1052,6 +1066,189 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
     e = vit::launch_backtrace_lane(b, st);
     return e == hipSuccess ? VIT_OK : hip_fail(e);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Packed checkpointed decode (wave-form plans): the packed decode above under a workspace budget.  Segments are per song: song b
+// has n_b = ceil(T_b / K) of them.  Pass 1 is the packed forward pass (slots walking their song lists; wave.hip HM 9) that keeps
+// only the row in front of each segment 1 .. n_b - 1, packed into sum (n_b - 1) <= N / K checkpoint rows, and the terminal state
+// and log-likelihood per song.  Pass 2 works on (song, segment) UNITS, one wavefront each: the units of a song run from its last
+// segment to its first, units of different songs are independent, and the host lists the launches up front
+// (vit::packed_ckpt_schedule: up to n_units = min(8 x CUs, B) ready units per launch, at most one per song, most segments left
+// first).  A launch resumes the wave kernel from every unit's checkpoint row into that unit's K + 1 rows (HM 8), sets every unit's
+// length and start state (packed_segment_prep_kernel) and runs the sparse back-trace over the units, which writes the states at
+// offsets[b] + segment * K.  Exact by construction: the kernels and sums of vit_decode_packed's forward pass.
+namespace {
+
+// the ONE predicate behind vit_workspace_bytes_packed_checkpointed and vit_decode_packed_checkpointed (a size > 0 implies a decode that launches)
+bool pc_applies(const vit_plan* p) { return p->bp.ok && p->bp.wave_ok && ck_sparse_applies(p, 3); }
+
+struct PcLayout {
+    int64_t K, tmax, units, n_ckpt, n_units, n_slots;
+    size_t off_ckpt, off_seg, off_last, off_entry, off_slen, off_slast, off_sbase;
+    size_t off_offsets, off_ckpt_base, off_slot_begin, off_slot_songs, off_unit_song, off_unit_seg, bytes;
+    size_t tables_bytes;      // offsets .. unit_seg: one contiguous upload
+};
+// false: bad offsets (the rule of vit_decode_packed), or more units than an int32 counts
+bool pc_layout(const vit_plan* p, int64_t B, const int64_t* offsets, int64_t K, PcLayout& c) {
+    if (!offsets || offsets[0] != 0) return false;
+    c.tmax = 1;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t tb = offsets[b + 1] - offsets[b];
+        if (tb < 1 || tb > (int64_t)1 << 30) return false;
+        c.tmax = std::max(c.tmax, tb);
+    }
+    c.K = K > c.tmax ? c.tmax : K;                             // (a segment longer than every song: one segment per song)
+    c.units = vit::packed_ckpt_units(offsets, B, c.K);
+    if (c.units < 0 || c.units > 0x7fffffff) return false;
+    c.n_ckpt = c.units - B;
+    c.n_units = pk_slots(p, B);                                // units per launch: at most one per song, at most 8 waves per CU
+    c.n_slots = pk_slots(p, B);                                // pass 1's slots (an upper bound, as in pk_layout): one scratch row each
+    const size_t sd = (size_t)vit::wave_hist_stride(p->bp.wave_npl) * sizeof(float);
+    c.off_ckpt = 0;                                            // [n_ckpt] checkpoint rows, then [n_slots] scratch rows
+    c.off_seg = align256((size_t)(c.n_ckpt + c.n_slots) * sd); // [n_units][K + 1] rows of the segments being walked
+    c.off_last = c.off_seg + align256((size_t)c.n_units * (size_t)(c.K + 1) * sd);
+    c.off_entry = c.off_last + align256((size_t)B * sizeof(int32_t));
+    c.off_slen = c.off_entry + align256((size_t)c.n_units * vit::kBtMaxChunks * sizeof(int32_t));
+    c.off_slast = c.off_slen + align256((size_t)c.n_units * sizeof(int64_t));
+    c.off_sbase = c.off_slast + align256((size_t)c.n_units * sizeof(int32_t));
+    c.off_offsets = c.off_sbase + align256((size_t)c.n_units * sizeof(int64_t));
+    c.off_ckpt_base = c.off_offsets + align256((size_t)(B + 1) * sizeof(int64_t));
+    c.off_slot_begin = c.off_ckpt_base + align256((size_t)(B + 1) * sizeof(int64_t));
+    c.off_slot_songs = c.off_slot_begin + align256((size_t)(c.n_slots + 1) * sizeof(int32_t));
+    c.off_unit_song = c.off_slot_songs + align256((size_t)B * sizeof(int32_t));
+    c.off_unit_seg = c.off_unit_song + align256((size_t)c.units * sizeof(int32_t));
+    c.bytes = c.off_unit_seg + align256((size_t)c.units * sizeof(int32_t));
+    c.tables_bytes = c.bytes - c.off_offsets;
+    return true;
+}
+
+}  // namespace
+
+size_t vit_workspace_bytes_packed_checkpointed(const vit_plan* plan, int64_t B, const int64_t* offsets, int64_t segment_frames) {
+    if (!plan || !offsets || B < 0 || B > (int64_t)1 << 30 || !ck_segment_ok(segment_frames)) return 0;
+    if (!pc_applies(plan)) return 0;
+    PcLayout c;
+    return pc_layout(plan, B, offsets, segment_frames, c) ? c.bytes : 0;
+}
+
+int vit_decode_packed_checkpointed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
+                                   size_t workspace_bytes, int32_t* states, float* loglik, int64_t segment_frames, vit_stream stream) {
+    if (!plan || !workspace || !offsets) return VIT_EINVAL;
+    if (B < 0 || B > (int64_t)1 << 30) return VIT_EINVAL;
+    if (!plan->dev_image) return VIT_ENOTUPLOADED;
+    if (((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
+    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
+    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
+    if (!pc_applies(plan)) return VIT_EUNSUPPORTED;       // (everything that can refuse the plan is asked here, before anything is enqueued)
+    PcLayout c;
+    if (!pc_layout(plan, B, offsets, segment_frames, c)) return VIT_EINVAL;
+    if (B == 0) return VIT_OK;
+    if (!logE || !states) return VIT_EINVAL;
+    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
+    const int64_t N = offsets[B], K = c.K;
+    const bool f16 = emis_dtype == VIT_F16;
+    const int64_t n_slots = std::min<int64_t>(c.n_slots, std::max<int64_t>(1, N / c.tmax));     // the rule of vit_decode_packed
+    stamp_erase(plan, workspace);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    const int SDW = vit::wave_hist_stride(plan->bp.wave_npl);
+
+    // ---- host tables in the plan's pinned staging buffer, one upload
+    {
+        const int rs = pk_stage(plan, c.tables_bytes);
+        if (rs != VIT_OK) return rs;
+    }
+    uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
+    std::memset(hb, 0, c.tables_bytes);
+    vit::PackedCkptSchedule sc;
+    try {
+        pk_fill_slots(offsets, B, n_slots, reinterpret_cast<int32_t*>(hb + (c.off_slot_begin - c.off_offsets)),
+                      reinterpret_cast<int32_t*>(hb + (c.off_slot_songs - c.off_offsets)));
+        vit::packed_ckpt_schedule(offsets, B, K, c.n_units, sc);
+    } catch (const std::bad_alloc&) {
+        return VIT_ENOMEM;
+    }
+    if ((int64_t)sc.unit_song.size() != c.units) return VIT_EINVAL;      // (cannot happen: the layout counted the same segments)
+    std::memcpy(hb, offsets, (size_t)(B + 1) * sizeof(int64_t));
+    std::memcpy(hb + (c.off_ckpt_base - c.off_offsets), sc.ckpt_base.data(), (size_t)(B + 1) * sizeof(int64_t));
+    std::memcpy(hb + (c.off_unit_song - c.off_offsets), sc.unit_song.data(), (size_t)c.units * sizeof(int32_t));
+    std::memcpy(hb + (c.off_unit_seg - c.off_offsets), sc.unit_seg.data(), (size_t)c.units * sizeof(int32_t));
+    hipError_t e = hipMemcpyAsync(ws + c.off_offsets, hb, c.tables_bytes, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(e);
+    e = hipEventRecord(plan->pk_event, st);
+    if (e != hipSuccess) return hip_fail(e);
+
+    // ---- pass 1: checkpoint rows + terminal state, one wave per slot
+    vit::FwdArgs a{};
+    fwd_args_from_plan(plan, a);
+    a.logE = logE;
+    a.lengths = nullptr;
+    a.hist = reinterpret_cast<float*>(ws + c.off_ckpt);
+    a.fmax = nullptr;
+    a.last_state = reinterpret_cast<int32_t*>(ws + c.off_last);
+    a.loglik = loglik;
+    a.B = B;
+    a.T = 1;                      // (unused: a song's rows come from the offsets)
+    a.hist_rows = c.n_ckpt;       // the scratch row of slot w is row n_ckpt + w
+    a.ckpt_every = (int)K;
+    a.t_begin = 0;
+    a.t_end = 1;
+    a.offsets = reinterpret_cast<const int64_t*>(ws + c.off_offsets);
+    a.n_slots = (int)n_slots;
+    a.slot_begin = reinterpret_cast<const int32_t*>(ws + c.off_slot_begin);
+    a.slot_songs = reinterpret_cast<const int32_t*>(ws + c.off_slot_songs);
+    a.ckpt_base = reinterpret_cast<const int64_t*>(ws + c.off_ckpt_base);
+    a.unit_song = nullptr;
+    e = vit::launch_wave(a, f16, st);
+    if (e != hipSuccess) return hip_fail(e);
+
+    // ---- pass 2: the launches of the schedule; every unit's back-trace starts from what the launch before it wrote
+    vit::BtArgs b{};
+    bt_args_from_plan(plan, b);
+    b.SD = SDW;
+    b.col0 = SDW - plan->S;
+    b.mcol = 0;
+    b.xcol0 = 1;
+    b.aux_frames = 1;       // (a unit's sub-problem ends one frame behind the rows it decides from: every frame's scalars from its own row)
+    b.have_fmax = 1;
+    b.hist = reinterpret_cast<const float*>(ws + c.off_seg);
+    b.hist_rows = K + 1;
+    b.last_state = reinterpret_cast<const int32_t*>(ws + c.off_slast);
+    b.lengths = reinterpret_cast<const int64_t*>(ws + c.off_slen);
+    b.unit_states = reinterpret_cast<const int64_t*>(ws + c.off_sbase);
+    b.entry = reinterpret_cast<int32_t*>(ws + c.off_entry);
+    b.states = states;
+    b.states_stride = 0;
+    b.T = (int)(K + 1);
+    b.counters = nullptr;
+    b.bt_form = 0;
+    b.warm = vit::kBtWarmSparse;
+    vit::FwdArgs f = a;
+    f.hist = reinterpret_cast<float*>(ws + c.off_seg);
+    f.hist_rows = K + 1;
+    f.loglik = nullptr;
+    f.init_rows = reinterpret_cast<const float*>(ws + c.off_ckpt);
+    const int32_t* d_unit_song = reinterpret_cast<const int32_t*>(ws + c.off_unit_song);
+    const int32_t* d_unit_seg = reinterpret_cast<const int32_t*>(ws + c.off_unit_seg);
+    for (size_t l = 0; l + 1 < sc.launch_begin.size(); ++l) {
+        const int64_t u0 = sc.launch_begin[l], nu = sc.launch_begin[l + 1] - u0;
+        if (nu < 1 || nu > c.n_units) return VIT_EINVAL;                  // (cannot happen: the schedule takes at most n_units per launch)
+        f.B = nu;
+        f.unit_song = d_unit_song + u0;
+        f.unit_seg = d_unit_seg + u0;
+        e = vit::launch_wave(f, f16, st);
+        if (e != hipSuccess) return hip_fail(e);
+        e = vit::launch_packed_segment_prep(a.offsets, f.unit_song, f.unit_seg, (int)nu, (int)K, states, a.last_state,
+                                            reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast),
+                                            reinterpret_cast<int64_t*>(ws + c.off_sbase), st);
+        if (e != hipSuccess) return hip_fail(e);
+        b.B = nu;
+        b.chunks = vit::sparse_backtrace_chunks(nu, b.T, plan->n_cus);
+        e = vit::launch_backtrace_sparse(b, st);
+        if (e != hipSuccess) return hip_fail(e);
+    }
+    return VIT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

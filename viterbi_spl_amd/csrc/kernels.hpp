@@ -91,7 +91,15 @@ struct FwdArgs {
     int n_slots;
     const int32_t* slot_begin;   // device [n_slots + 1]
     const int32_t* slot_songs;   // device [B]
-    int win_shift;          // 0..3: delta is stored shifted by this many floats in LDS so that the window starts of a
+    // packed checkpointed decode (vit_decode_packed_checkpointed; wave form only).  Segments are per song: song b has
+    // ceil(T_b / ckpt_every) of them.  ckpt_base set, unit_song null = pass 1 (wave.hip HM 9): the slot walk of the packed batch, but
+    // the only rows kept are the ones in front of segments 1 .. n_b - 1, at rows ckpt_base[b] .. of hist; every other store goes to
+    // scratch row hist_rows + slot.  unit_song set = pass 2 (HM 8): wave u < B recomputes segment unit_seg[u] of song unit_song[u]
+    // from checkpoint row ckpt_base[song] + segment - 1 of init_rows (segment 0: from the prior) into rows u * hist_rows .. of hist
+    const int64_t* ckpt_base;    // device [songs]: checkpoint rows in front of song b's = sum of (n_b' - 1) over b' < b
+    const int32_t* unit_song;    // device [B units of this launch]
+    const int32_t* unit_seg;     // device [B units of this launch]
+    int win_shift;         // 0..3: delta is stored shifted by this many floats in LDS so that the window starts of a
                             // 16-lane group are 16-byte aligned in the SAME copy order (bank-conflict-free b128 reads)
 };
 
@@ -143,6 +151,9 @@ struct BtArgs {
     const int32_t* chunk_base;   // device [B+1]
     int n_waves;
     uint32_t* mask;         // [B][kLaneMaskWords] lane form: bit c = chunk c assumed the wrong state at its upper boundary (zeroed by vit_backtrace)
+    // sparse kernel over the segment units of a packed checkpointed decode: the states of sub-problem b start at states +
+    // unit_states[b] (not b * states_stride), and nothing is written behind its lengths[b] frames -- those belong to the next song
+    const int64_t* unit_states;  // device [B], or null
 };
 
 // fused.hip: emission builder + wave-form forward recursion in one workgroup (vit_decode_logits).  f: the forward pass's arguments
@@ -183,6 +194,11 @@ hipError_t launch_step_ckpt(const FwdArgs& a, bool f16, hipStream_t st);
 // its back-trace starts from (the state already decided at frame e0, or the song's terminal state)
 hipError_t launch_segment_prep(const int64_t* lengths, int64_t B, int T, int s0, int e0, const int32_t* states, const int32_t* last,
                                int64_t* seg_len, int32_t* seg_last, hipStream_t st);
+// the same per segment unit of a packed checkpointed decode (unit u = segment unit_seg[u] of K frames of song unit_song[u], whose
+// frames sit at offsets[song]); also the unit's first entry in the packed states (BtArgs::unit_states)
+hipError_t launch_packed_segment_prep(const int64_t* offsets, const int32_t* unit_song, const int32_t* unit_seg, int n_units, int K,
+                                      const int32_t* states, const int32_t* last, int64_t* seg_len, int32_t* seg_last, int64_t* unit_states,
+                                      hipStream_t st);
 // history layout of the wave form: row stride 64*npl floats, state i in column 64*npl - S + i, the frame maximum in column 0,
 // a copy of delta of extra column k in column 1 + k
 constexpr int wave_hist_stride(int npl) { return 64 * npl; }

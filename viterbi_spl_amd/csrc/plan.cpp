@@ -6,6 +6,8 @@
 #include <cstring>
 #include <limits>
 #include <map>
+#include <queue>
+#include <utility>
 
 namespace vit {
 
@@ -320,6 +322,46 @@ void fill_image(const float* A, const float* log_pi, const BandedPlan& bp, const
         for (int w = 0; w < L.W; ++w)
             for (int j = 0; j < SP; ++j)
                 tp[(size_t)w * SP + j] = j < S ? A[(size_t)j * S + bp.lo2[j / 2] + w] : ninf;
+    }
+}
+
+int64_t packed_ckpt_units(const int64_t* offsets, int64_t B, int64_t K) {
+    if (!offsets || B < 0 || K < 1 || offsets[0] != 0) return -1;
+    int64_t units = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t tb = offsets[b + 1] - offsets[b];
+        if (tb < 1 || tb > (int64_t)1 << 30) return -1;
+        units += (tb + K - 1) / K;
+    }
+    return units;
+}
+
+void packed_ckpt_schedule(const int64_t* offsets, int64_t B, int64_t K, int64_t max_units, PackedCkptSchedule& out) {
+    out.unit_song.clear();
+    out.unit_seg.clear();
+    out.launch_begin.assign(1, 0);
+    out.ckpt_base.assign((size_t)B + 1, 0);
+    typedef std::pair<int32_t, int32_t> Left;                  // (segments left, -song): the top has the most left, then the lowest song
+    std::priority_queue<Left> heap;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t nb = (offsets[b + 1] - offsets[b] + K - 1) / K;
+        out.ckpt_base[(size_t)b + 1] = out.ckpt_base[(size_t)b] + nb - 1;
+        heap.push(Left{(int32_t)nb, (int32_t)-b});
+    }
+    max_units = max_units < 1 ? 1 : max_units;
+    std::vector<Left> taken;
+    while (!heap.empty()) {
+        taken.clear();
+        while (!heap.empty() && (int64_t)taken.size() < max_units) {
+            taken.push_back(heap.top());
+            heap.pop();
+        }
+        for (const Left& l : taken) {
+            out.unit_song.push_back(-l.second);
+            out.unit_seg.push_back(l.first - 1);               // the last segment not yet walked
+            if (l.first > 1) heap.push(Left{l.first - 1, l.second});
+        }
+        out.launch_begin.push_back((int64_t)out.unit_song.size());
     }
 }
 

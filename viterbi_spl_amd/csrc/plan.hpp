@@ -115,6 +115,20 @@ struct ImageLayout {
     size_t bytes = 0;
 };
 
+// Launch schedule of pass 2 of the packed checkpointed decode (vit_decode_packed_checkpointed).  Song b (frames offsets[b] ..
+// offsets[b+1]-1) has n_b = ceil(T_b / K) segments; a unit is a (song, segment) pair.  The units of a song run from its last segment
+// to its first, one per launch at most (the back-trace of segment s starts from the state segment s + 1 decided); every launch
+// takes the songs with the most segments left first (ties: lowest song), up to max_units of them, so that the launch count is
+// about max(longest n_b, total units / max_units).  Units in launch order: launch l holds units launch_begin[l] ..
+// launch_begin[l+1]-1.  ckpt_base[b] = sum of (n_b' - 1) over b' < b: the first of song b's checkpoint rows ([B + 1]).
+struct PackedCkptSchedule {
+    std::vector<int32_t> unit_song, unit_seg;
+    std::vector<int64_t> launch_begin, ckpt_base;
+};
+// total units, or -1 when offsets are not strictly increasing from 0 or a song is longer than 2^30 frames
+int64_t packed_ckpt_units(const int64_t* offsets, int64_t B, int64_t K);
+void packed_ckpt_schedule(const int64_t* offsets, int64_t B, int64_t K, int64_t max_units, PackedCkptSchedule& out);
+
 ImageLayout make_layout(int S, const BandedPlan& bp);
 void fill_image(const float* logA_T, const float* log_pi, const BandedPlan& bp,
                 const ImageLayout& L, uint8_t* image);

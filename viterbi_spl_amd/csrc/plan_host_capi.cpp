@@ -47,4 +47,22 @@ void vph_wave(const vph_plan* p, long long* w) {
 }
 void vph_image(const vph_plan* p, unsigned char* out) { std::memcpy(out, p->image.data(), p->image.size()); }
 
+// Launch schedule of the packed checkpointed decode (vit::packed_ckpt_schedule), for the CPU tests.  Returns the number of launches,
+// or -1 for bad offsets / more than cap_units units / more than cap_launches launches.  unit_song / unit_seg: [cap_units], units in
+// launch order; launch_begin: [cap_launches + 1]; ckpt_base: [B + 1].
+long long vph_packed_ckpt_schedule(const long long* offsets, long long B, long long K, long long max_units, int* unit_song, int* unit_seg,
+                                   long long cap_units, long long* launch_begin, long long cap_launches, long long* ckpt_base) {
+    std::vector<int64_t> off(offsets, offsets + B + 1);
+    const int64_t units = vit::packed_ckpt_units(off.data(), B, K);
+    if (units < 0 || units > cap_units) return -1;
+    vit::PackedCkptSchedule sc;
+    vit::packed_ckpt_schedule(off.data(), B, K, max_units, sc);
+    const long long nl = (long long)sc.launch_begin.size() - 1;
+    if (nl > cap_launches) return -1;
+    for (size_t u = 0; u < sc.unit_song.size(); ++u) { unit_song[u] = sc.unit_song[u]; unit_seg[u] = sc.unit_seg[u]; }
+    for (size_t l = 0; l < sc.launch_begin.size(); ++l) launch_begin[l] = sc.launch_begin[l];
+    for (size_t b = 0; b < sc.ckpt_base.size(); ++b) ckpt_base[b] = sc.ckpt_base[b];
+    return nl;
+}
+
 }  // extern "C"

@@ -98,6 +98,12 @@ __device__ __forceinline__ void store_row(float* __restrict__ p, const float (&d
 // slot order (a checkpoint row; lane 0's scalar slots are idle slots and are reset to -inf), computes frames t_begin ..
 // min(t_end, T_b) - 1 and stores row t at t - t_begin; the terminal state is pass 1's business.
 //
+// 9 / 8: the two passes of the packed checkpointed decode (vit_decode_packed_checkpointed; FwdArgs::ckpt_base / unit_song).  9 = the slot walk
+// of HM 7 with the stores of HM 5: song b keeps the rows in front of its segments 1 .. n_b - 1 (frames t with (t + 1) % K == 0 and
+// t + 1 < T_b) at rows ckpt_base[b] .. of hist, every other store goes to scratch row hist_rows + slot.  8 = HM 6 per UNIT: wave u
+// recomputes the K frames of segment unit_seg[u] of song unit_song[u] from its checkpoint row (segment 0: from the prior) into rows
+// u * hist_rows .. of hist; the unit's song, segment and checkpoint row are loaded once per wave, in front of the frame loop.
+//
 // UV >= 1 (one extra column and it is the last state, S - 1 = slot 64*NPL - 1 whatever S): delta of the extra column is a plain
 // v_readlane of lane 63's last slot instead of a select chain over the lane's slots (which the compiler turned into an LDS round
 // trip per frame).  UV = 2 (plan-proven, FwdArgs::wave_u5; NPL = 6) in addition: the row constant and the extra-column weight are the
@@ -117,10 +123,12 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
     static_assert(UV == 0 || NX == 1, "last-state / uniform-lane forms: one extra column");
     static_assert(UV < 2 || NPL == 6, "uniform-lane forms: six states per lane");
     constexpr bool U5 = UV == 2, U3 = UV == 3;
-    constexpr bool PK = HM == 7;               // packed batch: this wave is a SLOT that walks a list of songs back to back
+    constexpr bool PK = HM == 7 || HM == 9;    // packed batch: this wave is a SLOT that walks a list of songs back to back
+    constexpr bool SG = HM == 6 || HM == 8;    // one segment, resumed from a checkpoint row
+    constexpr bool PO = PK || HM == 8;         // a song's rows come from the offsets
     // every row stored, one extra column: row t carries the scalars of frames t, t-1 and t-2 (columns 0 1 | 2 3 | 4 5 of lane 0), so that
     // the back-trace finds the scalars of three frames in ONE line (kernels.hpp wave_aux_frames / wave_aux_row)
-    constexpr bool A3 = (HM == 0 || HM == 6 || HM == 7) && NX == 1 && NPL >= 6;      // (and six idle slots: run time, l0a below)
+    constexpr bool A3 = (HM == 0 || HM == 6 || HM == 7 || HM == 8) && NX == 1 && NPL >= 6;      // (and six idle slots: run time, l0a below)
     const int S = a.S;
     const int lane = threadIdx.x & 63;
     const int wid = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -164,15 +172,19 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
     const int k_begin = PK ? a.slot_begin[wid] : 0, k_end = PK ? a.slot_begin[wid + 1] : 1;
     for (int kk = k_begin; kk < k_end; ++kk) {
     // ---------------- this song: emission rows, history rows, length
-    const int song = PK ? a.slot_songs[kk] : wid;
-    const long long off = PK ? a.offsets[song] : (long long)song * a.T;           // first emission row of the song in the tensor
-    const int T = PK ? (int)(a.offsets[song + 1] - off) : a.T;                     // rows the song owns (packed: its length)
-    const int t0 = HM == 6 ? a.t_begin : 0;                                    // first frame of this launch
-    const int Tl = PK ? T : song_length(a.lengths, song, T);
-    const int Tb = HM == 6 && a.t_end < Tl ? a.t_end : Tl;                     // one past the last frame of this launch
+    const int song = PK ? a.slot_songs[kk] : (HM == 8 ? a.unit_song[wid] : wid);
+    const long long off = PO ? a.offsets[song] : (long long)song * a.T;           // first emission row of the song in the tensor
+    const int T = PO ? (int)(a.offsets[song + 1] - off) : a.T;                     // rows the song owns (packed: its length)
+    const int useg = HM == 8 ? a.unit_seg[wid] : 0;                            // (HM 8) the segment this wave recomputes
+    const int t0 = HM == 6 ? a.t_begin : (HM == 8 ? useg * a.ckpt_every : 0);  // first frame of this launch
+    const int Tl = PO ? T : song_length(a.lengths, song, T);
+    const int te = HM == 8 ? t0 + a.ckpt_every : a.t_end;
+    const int Tb = SG && te < Tl ? te : Tl;                                    // one past the last frame of this launch
     if (Tb <= t0) continue;                                                    // (segments: the song ended before this one)
     const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)off * S;
-    float* __restrict__ hist = a.hist + (PK ? (size_t)off : (size_t)song * a.hist_rows) * SDW;     // hist_rows = T (HM 0), (T + 1) / 2 (HM 1), segments (HM 5), K + 1 (HM 6)
+    // hist_rows = T (HM 0), (T + 1) / 2 (HM 1), segments (HM 5), K + 1 (HM 6, 8: per song / per unit), all checkpoint rows (HM 9)
+    float* __restrict__ hist = a.hist + (HM == 9 ? (size_t)0 : (HM == 7 ? (size_t)off : (size_t)(HM == 8 ? wid : song) * a.hist_rows)) * SDW;
+    const long long ck0 = HM == 9 ? a.ckpt_base[song] : 0;                     // (HM 9) the song's first checkpoint row
     // emission columns of this lane in rows >= 1 (see above): the leading lanes reach back into the row in front -- of the same song,
     // or (packed, row 0 is never loaded this way) of the song before it in the tensor; the first row of the tensor has none
     const long ecol = (T > 1 || off > 0) ? (long)j0 : (long)(j0 < 0 ? 0 : j0);
@@ -208,6 +220,10 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
             const int q = (t + 1) / a.ckpt_every;
             row = (t + 1) - q * a.ckpt_every == 0 && q - 1 < a.hist_rows - 1 ? q - 1 : a.hist_rows - 1;     // checkpoint, else the scratch row
         }
+        if (HM == 9) {
+            const int q = (t + 1) / a.ckpt_every;
+            row = (t + 1) - q * a.ckpt_every == 0 && t + 1 < T ? (size_t)(ck0 + q - 1) : (size_t)(a.hist_rows + wid);   // checkpoint, else this slot's scratch row
+        }
         store_row<NPL>(hist + row * SDW + NPL * lane, v);
     };
     // delta of the extra columns, wave-uniform
@@ -232,7 +248,7 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
             d[k] = j >= 0 ? lpi[j] + load_e<ET>(E + j) : -INFINITY;
         }
     } else {
-        const float* __restrict__ ir = a.init_rows + (size_t)song * a.init_stride + NPL * lane;
+        const float* __restrict__ ir = a.init_rows + (HM == 8 ? (size_t)(a.ckpt_base[song] + useg - 1) * SDW : (size_t)song * a.init_stride) + NPL * lane;
 #pragma unroll
         for (int k = 0; k < NPL; ++k) d[k] = j0 + k >= 0 ? ir[k] : -INFINITY;
     }
@@ -288,7 +304,7 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
         }
 
     // ---------------- terminal state: lowest-index argmax of delta_{Tb-1} (not in a segment launch)
-    if (HM != 6 || a.t_end >= T) {
+    if (HM != 8 && (HM != 6 || a.t_end >= T)) {
 #include "wave_terminal.inc"
         if (lane == 63) {
             a.last_state[song] = bi == kBig ? 0 : bi;
@@ -296,6 +312,19 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
         }
     }
     }   // songs of this slot
+}
+
+// the instantiations of the packed batch (HM 7 below) for the two passes of the packed checkpointed decode: n waves
+template <int NPL, int D, int NX, int PF1, int PF2, int HM, typename ET>
+static hipError_t launch_wave_pk(const FwdArgs& a, int n, hipStream_t st) {
+    const int pgrid = (n + 3) / 4;
+    if (n <= 1024 && ((a.wave_flags & 2) || NX == 2)) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, HM, ET>), dim3(pgrid), dim3(256), 0, st, a);
+    else if (NX == 1 && NPL == 6 && a.wave_u5 == 2) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET, (NX == 1 && NPL == 6) ? 2 : 0>), dim3(pgrid), dim3(256), 0, st, a);
+    else if (NX == 1 && NPL == 6 && a.wave_u5 == 3) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET, (NX == 1 && NPL == 6) ? 3 : 0>), dim3(pgrid), dim3(256), 0, st, a);
+    // (the last-state form alone, UV 1 -- "wave_uniform" 2 -- only in pass 1: the fp16 instantiation of HM 8 takes 292 bytes of scratch, the general one none)
+    else if (NX == 1 && HM != 8 && a.wave_u5 >= 1) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET, (NX == 1 && HM != 8) ? 1 : 0>), dim3(pgrid), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET>), dim3(pgrid), dim3(256), 0, st, a);
+    return hipGetLastError();
 }
 
 template <int NPL, int D, int NX, typename ET>
@@ -322,6 +351,9 @@ static hipError_t launch_wave_x(const FwdArgs& a, hipStream_t st) {
         return hipGetLastError();
     }
 #endif
+    if (a.ckpt_base) {          // packed checkpointed decode: pass 2 (one wave per segment unit) / pass 1 (one wave per slot); the variants of the packed batch
+        return a.unit_song ? launch_wave_pk<NPL, D, NX, PF1, PF2, 8, ET>(a, (int)a.B, st) : launch_wave_pk<NPL, D, NX, PF1, PF2, 9, ET>(a, a.n_slots, st);
+    }
     if (a.offsets) {            // packed batch (vit_decode_packed): one wave per slot, full history, rows at the songs' offsets
         const int pgrid = (a.n_slots + 3) / 4;
         if (a.n_slots <= 1024 && ((a.wave_flags & 2) || NX == 2)) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, 7, ET>), dim3(pgrid), dim3(256), 0, st, a);
@@ -392,6 +424,33 @@ __global__ void segment_prep_kernel(const int64_t* __restrict__ lengths, int64_t
 hipError_t launch_segment_prep(const int64_t* lengths, int64_t B, int T, int s0, int e0, const int32_t* states, const int32_t* last,
                                int64_t* seg_len, int32_t* seg_last, hipStream_t st) {
     hipLaunchKernelGGL(segment_prep_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, lengths, B, T, s0, e0, states, last, seg_len, seg_last);
+    return hipGetLastError();
+}
+
+// segment_prep_kernel per unit of a packed checkpointed decode: the sub-problem of segment [s0, s0 + K) of a song of T_b frames holds
+// its frames and, where the song goes on, frame s0 + K, whose state the unit of the segment behind it decided in an earlier launch
+__global__ void packed_segment_prep_kernel(const int64_t* __restrict__ offsets, const int32_t* __restrict__ unit_song, const int32_t* __restrict__ unit_seg,
+                                           int n_units, int K, const int32_t* __restrict__ states, const int32_t* __restrict__ last,
+                                           int64_t* __restrict__ seg_len, int32_t* __restrict__ seg_last, int64_t* __restrict__ unit_states) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n_units) return;
+    const int b = unit_song[u];
+    const int64_t off = offsets[b], Tb = offsets[b + 1] - off, s0 = (int64_t)unit_seg[u] * K, e0 = s0 + K;
+    unit_states[u] = off + s0;
+    if (Tb > e0) {
+        seg_len[u] = K + 1;
+        seg_last[u] = states[off + e0];
+    } else {                          // the song's last segment: pass 1 left its terminal state
+        seg_len[u] = Tb - s0;
+        seg_last[u] = last[b];
+    }
+}
+
+hipError_t launch_packed_segment_prep(const int64_t* offsets, const int32_t* unit_song, const int32_t* unit_seg, int n_units, int K,
+                                      const int32_t* states, const int32_t* last, int64_t* seg_len, int32_t* seg_last, int64_t* unit_states,
+                                      hipStream_t st) {
+    hipLaunchKernelGGL(packed_segment_prep_kernel, dim3((unsigned)((n_units + 255) / 256)), dim3(256), 0, st, offsets, unit_song, unit_seg, n_units, K,
+                       states, last, seg_len, seg_last, unit_states);
     return hipGetLastError();
 }
 

@@ -344,15 +344,8 @@ class ViterbiDecoder:
         return (states[0], loglik[0]) if single else (states, loglik)
 
     # ------------------------------------------------------------------ packed (ragged) decode
-    def decode_packed(self, emission_logits: torch.Tensor, offsets, out_dtype: torch.dtype = torch.int64,
-                      workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Decode B recordings of different lengths without padding (``vit_decode_packed``): ``emission_logits`` is
-        ``[sum T_b, S]`` (the rows of recording b are ``offsets[b] : offsets[b+1]``), ``offsets`` a host sequence of B + 1
-        frame offsets starting at 0.  Returns ``(states [sum T_b], loglik [B])``, packed like the input -- what the reference
-        computes recording by recording (tonet/for_paper.py:2304-2309).  For plans with the wave form (S = 321 / 361), banded
-        plans whose floor form is proven (the 722-state jdc grids, one workgroup per forward slot) and step-structured plans (the
-        Durrieu matrix); any other plan (unstructured matrices, banded plans with only the scan form) raises ``ViterbiHipError``."""
-        lib = _lib.load()
+    def _check_packed(self, emission_logits: torch.Tensor, offsets) -> Tuple[int, np.ndarray]:
+        """The argument checks of the packed decodes -> (emission storage type, host int64 offsets)."""
         if not isinstance(emission_logits, torch.Tensor) or emission_logits.device != self.device:
             raise ValueError("emission_logits must be a torch tensor on the decoder's device")
         if emission_logits.dim() != 2 or emission_logits.shape[1] != self.S or not emission_logits.is_contiguous():
@@ -363,10 +356,38 @@ class ViterbiDecoder:
             dt = _lib.VIT_F16
         else:
             raise TypeError("emission_logits must be float32 or float16")
-        off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
-        if off.ndim != 1 or off.size < 1 or off[0] != 0 or (np.diff(off) < 1).any() or off[-1] != emission_logits.shape[0]:
+        off = self._host_offsets(offsets)
+        if off[-1] != emission_logits.shape[0]:
             raise ValueError("offsets must be B + 1 strictly increasing frame offsets from 0 to the number of emission rows")
+        return dt, off
+
+    @staticmethod
+    def _host_offsets(offsets) -> np.ndarray:
+        off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
+        if off.ndim != 1 or off.size < 1 or off[0] != 0 or (np.diff(off) < 1).any():
+            raise ValueError("offsets must be B + 1 strictly increasing frame offsets from 0 to the number of emission rows")
+        return off
+
+    def decode_packed(self, emission_logits: torch.Tensor, offsets, out_dtype: torch.dtype = torch.int64,
+                      workspace: Optional[torch.Tensor] = None, max_workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Decode B recordings of different lengths without padding (``vit_decode_packed``): ``emission_logits`` is
+        ``[sum T_b, S]`` (the rows of recording b are ``offsets[b] : offsets[b+1]``), ``offsets`` a host sequence of B + 1
+        frame offsets starting at 0.  Returns ``(states [sum T_b], loglik [B])``, packed like the input -- what the reference
+        computes recording by recording (tonet/for_paper.py:2304-2309).  For plans with the wave form (S = 321 / 361), banded
+        plans whose floor form is proven (the 722-state jdc grids, one workgroup per forward slot) and step-structured plans (the
+        Durrieu matrix); any other plan (unstructured matrices, banded plans with only the scan form) raises ``ViterbiHipError``.
+
+        ``max_workspace_bytes``: a budget for the workspace (``plan_workspace_packed``): where the full history does not fit, the
+        decode falls to ``decode_packed_checkpointed`` with the largest segment length that does -- the same states and
+        log-likelihoods -- and raises ``ViterbiHipError`` when nothing fits.  ``None``: the full history, whatever it takes."""
+        lib = _lib.load()
+        dt, off = self._check_packed(emission_logits, offsets)
         B, N = off.size - 1, int(off[-1])
+        if B > 0 and max_workspace_bytes is not None:
+            mode = self.plan_workspace_packed(off, int(max_workspace_bytes))
+            if mode["mode"] == "checkpointed":
+                return self.decode_packed_checkpointed(emission_logits, off, segment_frames=mode["segment_frames"], out_dtype=out_dtype,
+                                                       workspace=workspace)
         states = torch.empty((N,), dtype=torch.int32, device=self.device)
         loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
         if B > 0:
@@ -391,6 +412,78 @@ class ViterbiDecoder:
         """Workspace bytes of ``decode_packed`` for B recordings of ``total_frames`` frames together; 0 when the plan has none of
         the forms the packed decode runs (see ``decode_packed``)."""
         return int(_lib.load().vit_workspace_bytes_packed(self._plan, int(B), int(total_frames)))
+
+    # ------------------------------------------------------------------ packed decode under a workspace budget
+    def workspace_bytes_packed_checkpointed(self, offsets, segment_frames: int) -> int:
+        """Workspace bytes of ``decode_packed_checkpointed`` for the recordings ``offsets`` describes (B + 1 host frame offsets); raises
+        ViterbiHipError for a plan or a segment length it does not serve."""
+        off = self._host_offsets(offsets)
+        need = int(_lib.load().vit_workspace_bytes_packed_checkpointed(self._plan, off.size - 1, off.ctypes.data, int(segment_frames)))
+        if need == 0:
+            raise _lib.ViterbiHipError("the packed checkpointed decode needs 64 <= segment_frames <= 2**24 and a plan with the wave form "
+                                       "(S = 321 / 361; the 722-state grids: pad and use decode_checkpointed(lengths=), or split the "
+                                       "recordings into groups whose workspace_bytes_packed fits)")
+        return need
+
+    def decode_packed_checkpointed(self, emission_logits: torch.Tensor, offsets, segment_frames: int = 1024, out_dtype: torch.dtype = torch.int64,
+                                   workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_packed`` with a bounded workspace (``vit_decode_packed_checkpointed``): ``n_units * (K + 1)`` delta rows for the
+        segments being walked (``n_units = min(B, 8 x compute units)``, ``K = segment_frames``) plus one row per K frames, instead of
+        one row per frame.  Same arguments, same states, same log-likelihoods; about twice the forward work.  For plans with the
+        wave form (S = 321 / 361); any other plan raises ``ViterbiHipError`` before anything is enqueued.  ``workspace``: an optional
+        uint8 tensor of at least ``workspace_bytes_packed_checkpointed(...) + 256`` bytes to decode in (the caller then keeps it
+        alive until the stream has run the decode: the call does not synchronise)."""
+        lib = _lib.load()
+        dt, off = self._check_packed(emission_logits, offsets)
+        B, N = off.size - 1, int(off[-1])
+        states = torch.empty((N,), dtype=torch.int32, device=self.device)
+        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
+        if B > 0:
+            need = self.workspace_bytes_packed_checkpointed(off, segment_frames)
+            ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
+                raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
+            with torch.cuda.device(self.device):
+                rc = lib.vit_decode_packed_checkpointed(self._plan, emission_logits.data_ptr(), dt, B, off.ctypes.data, (ws.data_ptr() + 255) & ~255,
+                                                        ws.numel() - 256, states.data_ptr(), loglik.data_ptr(), int(segment_frames),
+                                                        torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(rc, "vit_decode_packed_checkpointed")
+            if workspace is None:
+                torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
+        if out_dtype != torch.int32:
+            states = states.to(out_dtype)
+        return states, loglik
+
+    def plan_workspace_packed(self, offsets, max_workspace_bytes: Optional[int] = None) -> dict:
+        """How the recordings ``offsets`` describes are decoded under a workspace budget (bytes; None = whatever it takes):
+
+        * ``{"mode": "full", "workspace_bytes": ...}`` -- ``decode_packed`` fits (one delta row per frame);
+        * ``{"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ...}`` -- ``decode_packed_checkpointed`` with the
+          largest K of 8192, 4096, ..., 64 that fits (fewest launches; the rule of ``plan_workspace``).
+
+        Raises ViterbiHipError naming the need when nothing fits or the plan is not served.  Both modes decode the same bits."""
+        off = self._host_offsets(offsets)
+        B, N = off.size - 1, int(off[-1])
+        need = self.workspace_bytes_packed(B, N)
+        if need == 0 and B > 0:
+            raise _lib.ViterbiHipError("the packed decode needs a plan with the wave form, the floor form or the step form "
+                                       "(unstructured matrices and scan-only banded plans: pad and use decode(lengths=))")
+        if max_workspace_bytes is None or need <= max_workspace_bytes:
+            return {"mode": "full", "workspace_bytes": need}
+        lib = _lib.load()
+        least, K = 0, 8192
+        while K >= 64:
+            ck = int(lib.vit_workspace_bytes_packed_checkpointed(self._plan, B, off.ctypes.data, K))
+            if 0 < ck <= max_workspace_bytes:           # the largest segment that fits: fewest launches
+                return {"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ck}
+            least = ck if least == 0 or 0 < ck < least else least
+            K //= 2
+        if least == 0:
+            raise _lib.ViterbiHipError(f"the packed decode of {B} recordings ({N} frames) needs a workspace of {need} bytes, the budget is "
+                                       f"{max_workspace_bytes}, and this plan has no packed checkpointed decode (wave-form plans only: "
+                                       "split the recordings into groups whose workspace_bytes_packed fits)")
+        raise _lib.ViterbiHipError(f"no packed decode of {B} recordings ({N} frames) fits a workspace of {max_workspace_bytes} bytes "
+                                   f"(the full history needs {need}, the checkpointed decode at least {least})")
 
     # ------------------------------------------------------------------ fused logits -> path decode
     @staticmethod
