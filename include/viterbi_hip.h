@@ -281,6 +281,35 @@ int vit_decode_packed_checkpointed(const vit_plan *plan, const void *logE, int e
                                    int64_t segment_frames, vit_stream stream);
 
 /*
+ * Packed decode under a workspace budget for EVERY plan with a packed decode: a superset of vit_decode_packed_checkpointed(), whose
+ * entry points keep their behaviour (size 0 / VIT_EUNSUPPORTED for plans without the wave form).  Arguments, argument rules, status
+ * codes, the staging of the tables and the thread-safety note are those of vit_decode_packed_checkpointed(): 64 <= K <= 2^24 (a
+ * value above the longest song acts like that length), offsets on the HOST from 0 with no empty song, a 256-byte aligned workspace,
+ * B = 0 is VIT_OK and enqueues nothing.  States and log-likelihoods are bit-identical to vit_decode_packed() on the same input.
+ * Which plans, and what runs:
+ *   - plans with the wave form: forwarded to vit_decode_packed_checkpointed() -- the same size, the same bits;
+ *   - banded plans without it whose floor form is proven (the 722- and 721-state grids of jdc and imm): the scheme above with a
+ *     WORKGROUP where it has a wavefront.  Pass 1 is vit_decode_packed's slot walk and keeps the row in front of every segment but a
+ *     song's first; pass 2 runs one workgroup per (song, segment) unit into K + 2 rows of its own and back-traces the units with the
+ *     sparse kernel.  Requires the sparse back-trace over the workgroup rows: a plan that only the lane form could back-trace
+ *     (vit_decode_checkpointed serves it) gets size 0 here;
+ *   - step plans (the Durrieu matrices, 705 .. 768 voiced states): the same with K + 1 rows per unit and the lazy back-trace;
+ *   - everything else (unstructured matrices, scan-only banded plans): size 0 and VIT_EUNSUPPORTED before anything is enqueued.
+ * A size > 0 means the decode launches.  vit_packed_bounded_units(): the units one pass-2 launch takes, min(B, u x compute units)
+ * with u = 8 (wave form), 1 (floor plans) or 2 (step plans); 0 for plans the decode does not serve.  Every unit owns its rows, so u
+ * is tuning, not correctness.  Compute units: of the device the plan was uploaded to, 256 before the upload.
+ * Workspace of the workgroup forms: units x (K + 2 | K + 1) segment rows + sum (n_b - 1) checkpoint rows + one scratch row per
+ * pass-1 slot (min(B, 8 x compute units) of them are provided for), (S + 5) / 4 * 4 floats each, + the tables of
+ * vit_decode_packed_checkpointed().  Honoured options: "bt_fast_rows", "bt_warm", "win_shift".
+ */
+size_t vit_workspace_bytes_packed_bounded(const vit_plan *plan, int64_t B, const int64_t *offsets /* HOST, [B+1] */,
+                                          int64_t segment_frames);
+int vit_decode_packed_bounded(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B, const int64_t *offsets,
+                              void *workspace, size_t workspace_bytes, int32_t *states, float *loglik,
+                              int64_t segment_frames, vit_stream stream);
+int64_t vit_packed_bounded_units(const vit_plan *plan, int64_t B);
+
+/*
  * Fused logits -> path decode: what callers of the reference run is Viterbi.__call__ (tonet/for_paper.py:1817-1831) -- pitch
  * logits -> observation log-probabilities -> Viterbi decode.  vit_obs_*() + vit_decode() do that with a [B,T,S] float32
  * emission tensor written to and read back from device memory (2 x 4 S bytes per frame, 44 GB for [1024, 30000, 361]); here the

@@ -24,6 +24,7 @@ EXPORTS = (
     "vit_backtrace_checked", "vit_forward_family", "vit_workspace_bytes_packed", "vit_decode_packed",
     "vit_workspace_bytes_logits", "vit_decode_logits", "vit_obs_activations",
     "vit_workspace_bytes_packed_checkpointed", "vit_decode_packed_checkpointed",
+    "vit_workspace_bytes_packed_bounded", "vit_decode_packed_bounded", "vit_packed_bounded_units",
 )
 ABI_VERSION = 4
 
@@ -114,6 +115,12 @@ def load() -> ctypes.CDLL:
     lib.vit_workspace_bytes_packed_checkpointed.argtypes = [vp, i64, vp, i64]
     lib.vit_decode_packed_checkpointed.restype = i32
     lib.vit_decode_packed_checkpointed.argtypes = [vp, vp, i32, i64, vp, vp, sz, vp, vp, i64, vp]
+    lib.vit_workspace_bytes_packed_bounded.restype = sz
+    lib.vit_workspace_bytes_packed_bounded.argtypes = [vp, i64, vp, i64]
+    lib.vit_decode_packed_bounded.restype = i32
+    lib.vit_decode_packed_bounded.argtypes = [vp, vp, i32, i64, vp, vp, sz, vp, vp, i64, vp]
+    lib.vit_packed_bounded_units.restype = i64
+    lib.vit_packed_bounded_units.argtypes = [vp, i64]
     lib.vit_workspace_bytes_logits.restype = sz
     lib.vit_workspace_bytes_logits.argtypes = [vp, ctypes.POINTER(ObsParams), i64, i64]
     lib.vit_decode_logits.restype = i32

@@ -289,7 +289,9 @@ constexpr int kBtWaves = 4;
 // SG: one segment of a checkpointed decode (vit_decode_checkpointed for step plans), in both passes what the sparse and lane kernels
 // do: the song's history rows start at row song * hist_rows (the segment buffer), its states at song * states_stride (the segment's
 // first frame within the whole song's row), and a song whose lengths[] entry is < 1 (skip_nonpositive: the segment does not reach it)
-// is skipped, not clamped to one frame.  PK = SG = false compiles to the code it was before the parameters existed.
+// is skipped, not clamped to one frame.  With a.unit_states the sub-problems are the segment units of a packed checkpointed decode
+// (vit_decode_packed_bounded): the states of sub-problem b start at states + unit_states[b], and nothing is written behind its
+// lengths[b] frames -- those entries belong to the next song.  PK = SG = false compiles to the code it was before the parameters existed.
 template <int NWT, int MODE, bool PK = false, bool SG = false>
 __global__ void __launch_bounds__(kBtWaves * 64) lazy_backtrace_kernel(BtArgs a) {
     static_assert(!(PK && SG), "a segment is a segment of a padded batch");
@@ -343,8 +345,8 @@ __global__ void __launch_bounds__(kBtWaves * 64) lazy_backtrace_kernel(BtArgs a)
     }
     const long long row0 = PK ? a.offsets[song] : (long long)song * T;  // first history row / state of the song
     const int Tb = PK ? (int)(a.offsets[song + 1] - row0) : song_length(a.lengths, song, T);
-    const int Tpad = PK ? Tb : T;                       // frames past the song's end are filled with -1 up to here
-    int32_t* __restrict__ states = a.states + (SG ? (size_t)song * (size_t)a.states_stride : (size_t)row0);
+    const int Tpad = PK || (SG && a.unit_states) ? Tb : T;   // frames past the song's end are filled with -1 up to here
+    int32_t* __restrict__ states = a.states + (SG ? (a.unit_states ? (size_t)a.unit_states[song] : (size_t)song * (size_t)a.states_stride) : (size_t)row0);
     const float* __restrict__ hist = a.hist + (SG ? (size_t)song * (size_t)a.hist_rows : (size_t)row0) * SD;
     int32_t* __restrict__ entry = a.entry + (PK ? (size_t)cbase : (size_t)song * C);   // [C] of this song
     const float* __restrict__ Arow = reinterpret_cast<const float*>(a.image + a.off_Arow);

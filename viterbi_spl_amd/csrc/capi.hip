@@ -72,6 +72,7 @@ struct vit_plan {
     mutable size_t pk_host_bytes = 0;
     mutable hipEvent_t pk_event = nullptr;
     mutable int pk_resident[2] = {0, 0};   // workgroups per CU of the packed workgroup-form kernel (fp32 / fp16 emissions), 0 = not asked yet
+    mutable int pb_resident[2] = {0, 0};   // the same for the packed-checkpoint variant (vit_decode_packed_bounded, pass 1's slots)
     ~vit_plan() {
         if (pk_event) (void)hipEventDestroy(pk_event);
         if (pk_host) (void)hipHostFree(pk_host);
@@ -1089,8 +1090,9 @@ struct PcLayout {
     size_t off_offsets, off_ckpt_base, off_slot_begin, off_slot_songs, off_unit_song, off_unit_seg, bytes;
     size_t tables_bytes;      // offsets .. unit_seg: one contiguous upload
 };
-// false: bad offsets (the rule of vit_decode_packed), or more units than an int32 counts
-bool pc_layout(const vit_plan* p, int64_t B, const int64_t* offsets, int64_t K, PcLayout& c) {
+// false: bad offsets (the rule of vit_decode_packed), or more units than an int32 counts.  sd_floats: the history row stride of the
+// form that runs; n_units: units per launch; extra_rows: rows a unit holds besides its K (1 wave form and step kernel, 2 floor kernel)
+bool pc_layout_rows(const vit_plan* p, int64_t B, const int64_t* offsets, int64_t K, int sd_floats, int64_t n_units, int extra_rows, PcLayout& c) {
     if (!offsets || offsets[0] != 0) return false;
     c.tmax = 1;
     for (int64_t b = 0; b < B; ++b) {
@@ -1102,12 +1104,12 @@ bool pc_layout(const vit_plan* p, int64_t B, const int64_t* offsets, int64_t K, 
     c.units = vit::packed_ckpt_units(offsets, B, c.K);
     if (c.units < 0 || c.units > 0x7fffffff) return false;
     c.n_ckpt = c.units - B;
-    c.n_units = pk_slots(p, B);                                // units per launch: at most one per song, at most 8 waves per CU
+    c.n_units = n_units;                                       // units per launch: at most one per song (wave form: at most 8 waves per CU)
     c.n_slots = pk_slots(p, B);                                // pass 1's slots (an upper bound, as in pk_layout): one scratch row each
-    const size_t sd = (size_t)vit::wave_hist_stride(p->bp.wave_npl) * sizeof(float);
+    const size_t sd = (size_t)sd_floats * sizeof(float);
     c.off_ckpt = 0;                                            // [n_ckpt] checkpoint rows, then [n_slots] scratch rows
-    c.off_seg = align256((size_t)(c.n_ckpt + c.n_slots) * sd); // [n_units][K + 1] rows of the segments being walked
-    c.off_last = c.off_seg + align256((size_t)c.n_units * (size_t)(c.K + 1) * sd);
+    c.off_seg = align256((size_t)(c.n_ckpt + c.n_slots) * sd); // [n_units][K + extra_rows] rows of the segments being walked
+    c.off_last = c.off_seg + align256((size_t)c.n_units * (size_t)(c.K + extra_rows) * sd);
     c.off_entry = c.off_last + align256((size_t)B * sizeof(int32_t));
     c.off_slen = c.off_entry + align256((size_t)c.n_units * vit::kBtMaxChunks * sizeof(int32_t));
     c.off_slast = c.off_slen + align256((size_t)c.n_units * sizeof(int64_t));
@@ -1121,6 +1123,10 @@ bool pc_layout(const vit_plan* p, int64_t B, const int64_t* offsets, int64_t K, 
     c.bytes = c.off_unit_seg + align256((size_t)c.units * sizeof(int32_t));
     c.tables_bytes = c.bytes - c.off_offsets;
     return true;
+}
+// the wave form's layout: at most 8 waves per CU, K + 1 rows per unit
+bool pc_layout(const vit_plan* p, int64_t B, const int64_t* offsets, int64_t K, PcLayout& c) {
+    return pc_layout_rows(p, B, offsets, K, vit::wave_hist_stride(p->bp.wave_npl), pk_slots(p, B), 1, c);
 }
 
 }  // namespace
@@ -1246,6 +1252,207 @@ int vit_decode_packed_checkpointed(const vit_plan* plan, const void* logE, int e
         b.B = nu;
         b.chunks = vit::sparse_backtrace_chunks(nu, b.T, plan->n_cus);
         e = vit::launch_backtrace_sparse(b, st);
+        if (e != hipSuccess) return hip_fail(e);
+    }
+    return VIT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Packed decode under a workspace budget for every plan with a packed decode (vit_decode_packed_bounded): a superset of the packed
+// checkpointed decode above.  Wave-form plans are forwarded to it.  Plans without the wave form run its scheme with a WORKGROUP where
+// it has a wavefront: pass 1 is the slot walk of vit_decode_packed's workgroup kernels with the stores of their checkpoint / resume
+// variants (banded_floor_forward_kernel / step4s_forward_kernel <.., PC>, a.unit_song null), pass 2 the launches of
+// vit::packed_ckpt_schedule with one workgroup per (song, segment) unit (the same kernels, a.unit_song set), packed_segment_prep_kernel,
+// and the back-trace over the units: the sparse kernel over the workgroup rows for banded plans, the lazy kernel's segment form for
+// step plans.  Every unit owns its rows (K + 2 for the floor kernel: one in front for the first frame's frame-maximum store, one behind
+// for the frame past the segment; K + 1 for the step kernel), so correctness does not depend on how many workgroups are resident; the
+// units per launch, min(B, u x CUs), are tuning: u = 1 for the floor kernel (W = 128 on twelve waves takes 148 KB of LDS and 3 x 168
+// registers per SIMD: one workgroup per CU) and u = 2 for the step kernel (62 KB of LDS, seven waves of 128 registers: two per CU).
+namespace {
+
+constexpr int kPbUnitsPerCuFloor = 1, kPbUnitsPerCuStep = 2;
+
+// The forward family a bounded packed decode of this plan runs (FwdStamp::family numbering), 0 = none: the ONE predicate behind
+// vit_workspace_bytes_packed_bounded, vit_packed_bounded_units and vit_decode_packed_bounded (a size > 0 implies a decode that launches).
+// Family 2 back-traces its units with the sparse kernel only: a plan that the lane form alone could back-trace gets 0.
+int pb_family(const vit_plan* p) {
+    if (p->bp.ok && p->bp.wave_ok) return pc_applies(p) ? 3 : 0;
+    if (p->bp.ok)
+        return vit::floor_pckpt_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && p->bp.W <= p->S && ck_sparse_applies(p, 2) ? 2 : 0;
+    if (p->bp.step_ok && vit::step_kernel_instantiated(p->S, p->bp.step_bw, p->bp.step_kb)) return 1;
+    return 0;
+}
+int64_t pb_units(const vit_plan* p, int family, int64_t B) {
+    if (family == 0) return 0;
+    const int64_t cap = family == 3 ? 8 * (int64_t)p->n_cus : (family == 2 ? kPbUnitsPerCuFloor : kPbUnitsPerCuStep) * (int64_t)p->n_cus;
+    return B < cap ? B : cap;
+}
+// families 1 and 2
+bool pb_layout(const vit_plan* p, int family, int64_t B, const int64_t* offsets, int64_t K, PcLayout& c) {
+    return pc_layout_rows(p, B, offsets, K, hist_stride(p->S), pb_units(p, family, B), family == 2 ? 2 : 1, c);
+}
+
+}  // namespace
+
+int64_t vit_packed_bounded_units(const vit_plan* plan, int64_t B) {
+    if (!plan || B < 0 || B > (int64_t)1 << 30) return 0;
+    return pb_units(plan, pb_family(plan), B);
+}
+
+size_t vit_workspace_bytes_packed_bounded(const vit_plan* plan, int64_t B, const int64_t* offsets, int64_t segment_frames) {
+    if (!plan || !offsets || B < 0 || B > (int64_t)1 << 30 || !ck_segment_ok(segment_frames)) return 0;
+    const int family = pb_family(plan);
+    if (family == 0) return 0;
+    if (family == 3) return vit_workspace_bytes_packed_checkpointed(plan, B, offsets, segment_frames);
+    PcLayout c;
+    return pb_layout(plan, family, B, offsets, segment_frames, c) ? c.bytes : 0;
+}
+
+int vit_decode_packed_bounded(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
+                              size_t workspace_bytes, int32_t* states, float* loglik, int64_t segment_frames, vit_stream stream) {
+    if (!plan || !workspace || !offsets) return VIT_EINVAL;
+    if (B < 0 || B > (int64_t)1 << 30) return VIT_EINVAL;
+    if (!plan->dev_image) return VIT_ENOTUPLOADED;
+    if (((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
+    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
+    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
+    const int family = pb_family(plan);                   // (everything that can refuse the plan is asked here, before anything is enqueued)
+    if (family == 0) return VIT_EUNSUPPORTED;
+    if (family == 3) return vit_decode_packed_checkpointed(plan, logE, emis_dtype, B, offsets, workspace, workspace_bytes, states, loglik, segment_frames, stream);
+    PcLayout c;
+    if (!pb_layout(plan, family, B, offsets, segment_frames, c)) return VIT_EINVAL;
+    if (B == 0) return VIT_OK;
+    if (!logE || !states) return VIT_EINVAL;
+    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
+    const int64_t N = offsets[B], K = c.K;
+    const bool f16 = emis_dtype == VIT_F16;
+    const Tuning& tn = plan->tune;
+    const int SDH = hist_stride(plan->S);
+    const int64_t seg_rows = K + (family == 2 ? 2 : 1);
+    auto forward = [&](const vit::FwdArgs& f) { return family == 2 ? vit::launch_banded_pckpt(f, f16, (hipStream_t)stream) : vit::launch_step_pckpt(f, f16, (hipStream_t)stream); };
+    vit::FwdArgs a{};
+    fwd_args_from_plan(plan, a);
+    // pass 1's slots, as vit_decode_packed chooses them: one per workgroup that is resident at once, no slot lighter than the longest song
+    int64_t n_slots = c.n_slots;
+    {
+        int per_cu;
+        {
+            std::lock_guard<std::mutex> g(plan->mu);
+            per_cu = plan->pb_resident[f16 ? 1 : 0];
+        }
+        if (per_cu < 1) {
+            hipError_t eq = family == 2 ? vit::banded_pckpt_resident(a, f16, &per_cu) : vit::step_pckpt_resident(a, f16, &per_cu);
+            if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: pb_family asked the same predicates)
+            if (eq != hipSuccess) return hip_fail(eq);
+            if (per_cu < 1) return VIT_EUNSUPPORTED;
+            std::lock_guard<std::mutex> g(plan->mu);
+            plan->pb_resident[f16 ? 1 : 0] = per_cu;
+        }
+        n_slots = std::min<int64_t>(n_slots, (int64_t)per_cu * plan->n_cus);
+        n_slots = std::min<int64_t>(n_slots, std::max<int64_t>(1, N / c.tmax));
+    }
+    stamp_erase(plan, workspace);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+
+    // ---- host tables in the plan's pinned staging buffer, one upload
+    {
+        const int rs = pk_stage(plan, c.tables_bytes);
+        if (rs != VIT_OK) return rs;
+    }
+    uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
+    std::memset(hb, 0, c.tables_bytes);
+    vit::PackedCkptSchedule sc;
+    try {
+        pk_fill_slots(offsets, B, n_slots, reinterpret_cast<int32_t*>(hb + (c.off_slot_begin - c.off_offsets)),
+                      reinterpret_cast<int32_t*>(hb + (c.off_slot_songs - c.off_offsets)));
+        vit::packed_ckpt_schedule(offsets, B, K, c.n_units, sc);
+    } catch (const std::bad_alloc&) {
+        return VIT_ENOMEM;
+    }
+    if ((int64_t)sc.unit_song.size() != c.units) return VIT_EINVAL;      // (cannot happen: the layout counted the same segments)
+    std::memcpy(hb, offsets, (size_t)(B + 1) * sizeof(int64_t));
+    std::memcpy(hb + (c.off_ckpt_base - c.off_offsets), sc.ckpt_base.data(), (size_t)(B + 1) * sizeof(int64_t));
+    std::memcpy(hb + (c.off_unit_song - c.off_offsets), sc.unit_song.data(), (size_t)c.units * sizeof(int32_t));
+    std::memcpy(hb + (c.off_unit_seg - c.off_offsets), sc.unit_seg.data(), (size_t)c.units * sizeof(int32_t));
+    hipError_t e = hipMemcpyAsync(ws + c.off_offsets, hb, c.tables_bytes, hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return hip_fail(e);
+    e = hipEventRecord(plan->pk_event, st);
+    if (e != hipSuccess) return hip_fail(e);
+
+    // ---- pass 1: checkpoint rows + terminal state, one workgroup per slot
+    a.logE = logE;
+    a.lengths = nullptr;
+    a.hist = reinterpret_cast<float*>(ws + c.off_ckpt);
+    a.fmax = nullptr;
+    a.last_state = reinterpret_cast<int32_t*>(ws + c.off_last);
+    a.loglik = loglik;
+    a.B = B;
+    a.T = 1;                      // (unused: a song's rows come from the offsets)
+    a.hist_rows = c.n_ckpt;       // the scratch row of slot w is row n_ckpt + w
+    a.ckpt_every = (int)K;
+    a.t_begin = 0;
+    a.t_end = 1;
+    a.offsets = reinterpret_cast<const int64_t*>(ws + c.off_offsets);
+    a.n_slots = (int)n_slots;
+    a.slot_begin = reinterpret_cast<const int32_t*>(ws + c.off_slot_begin);
+    a.slot_songs = reinterpret_cast<const int32_t*>(ws + c.off_slot_songs);
+    a.ckpt_base = reinterpret_cast<const int64_t*>(ws + c.off_ckpt_base);
+    a.unit_song = nullptr;
+    e = forward(a);
+    if (e != hipSuccess) return hip_fail(e);
+
+    // ---- pass 2: the launches of the schedule; every unit's back-trace starts from what the launch before it wrote
+    vit::BtArgs b{};
+    bt_args_from_plan(plan, b);
+    b.SD = SDH;
+    b.col0 = 0;             // the workgroup kernels' rows: state i in column i, the frame maximum (banded) in pad column S
+    b.mcol = plan->S;
+    b.xcol0 = -1;
+    b.aux_frames = 1;
+    b.have_fmax = family == 2 ? 1 : 0;
+    // family 2: a unit's row 0 is the second of its K + 2 rows
+    float* seg = reinterpret_cast<float*>(ws + c.off_seg) + (family == 2 ? SDH : 0);
+    b.hist = seg;
+    b.hist_rows = seg_rows;
+    b.last_state = reinterpret_cast<const int32_t*>(ws + c.off_slast);
+    b.lengths = reinterpret_cast<const int64_t*>(ws + c.off_slen);
+    b.unit_states = reinterpret_cast<const int64_t*>(ws + c.off_sbase);
+    b.entry = reinterpret_cast<int32_t*>(ws + c.off_entry);
+    b.states = states;
+    b.states_stride = 0;
+    b.T = (int)(K + 1);
+    b.counters = nullptr;
+    b.mask = nullptr;
+    b.bt_form = family == 1 ? 1 : 0;
+    b.warm = family == 1 ? (tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarm) : (tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarmSparse);
+    vit::FwdArgs f = a;
+    f.hist = seg;
+    f.hist_rows = seg_rows;
+    f.loglik = nullptr;
+    f.init_rows = reinterpret_cast<const float*>(ws + c.off_ckpt);
+    const int32_t* d_unit_song = reinterpret_cast<const int32_t*>(ws + c.off_unit_song);
+    const int32_t* d_unit_seg = reinterpret_cast<const int32_t*>(ws + c.off_unit_seg);
+    for (size_t l = 0; l + 1 < sc.launch_begin.size(); ++l) {
+        const int64_t u0 = sc.launch_begin[l], nu = sc.launch_begin[l + 1] - u0;
+        if (nu < 1 || nu > c.n_units) return VIT_EINVAL;                  // (cannot happen: the schedule takes at most n_units per launch)
+        f.B = nu;
+        f.unit_song = d_unit_song + u0;
+        f.unit_seg = d_unit_seg + u0;
+        e = forward(f);
+        if (e != hipSuccess) return hip_fail(e);
+        e = vit::launch_packed_segment_prep(a.offsets, f.unit_song, f.unit_seg, (int)nu, (int)K, states, a.last_state,
+                                            reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast),
+                                            reinterpret_cast<int64_t*>(ws + c.off_sbase), st);
+        if (e != hipSuccess) return hip_fail(e);
+        b.B = nu;
+        if (family == 1) {              // step plans: the lazy kernel, one wave per (unit, chunk)
+            b.chunks = vit::backtrace_chunks(nu, b.T);
+            e = vit::launch_backtrace_rows_segment(b, st);
+        } else {
+            b.chunks = vit::sparse_backtrace_chunks(nu, b.T, plan->n_cus);
+            e = vit::launch_backtrace_sparse(b, st);
+        }
         if (e != hipSuccess) return hip_fail(e);
     }
     return VIT_OK;

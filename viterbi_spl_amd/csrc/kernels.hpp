@@ -40,6 +40,9 @@ constexpr bool floor_ckpt_pair(int W, int nwt) { return W >= 64 || nwt >= 8; }
 constexpr bool floor_ckpt_applies(int S, int W, bool floor_ok, int n_dense) {
     return floor_packed_applies(S, W, floor_ok, n_dense) && floor_ckpt_pair(W, banded_waves_for(S));
 }
+// packed-checkpoint variant of the same kernel (banded_floor_forward_kernel<.., PC = true> in banded_pc.hip, vit_decode_packed_bounded
+// for plans without the wave form): every pair of the checkpoint / resume variant -- each of them compiles free of scratch
+constexpr bool floor_pckpt_applies(int S, int W, bool floor_ok, int n_dense) { return floor_ckpt_applies(S, W, floor_ok, n_dense); }
 // step-structured kernel (plan.step_ok): instantiated for the Durrieu geometry -- 20-bin bands, 9 near bands, 705..768 voiced states
 constexpr bool step_kernel_instantiated(int S, int bw, int kb) { return bw == 20 && kb == 9 && S - 1 > 704 && S - 1 <= 768; }
 // the dense kernel keeps NS running (best, arg) pairs per thread
@@ -91,7 +94,8 @@ struct FwdArgs {
     int n_slots;
     const int32_t* slot_begin;   // device [n_slots + 1]
     const int32_t* slot_songs;   // device [B]
-    // packed checkpointed decode (vit_decode_packed_checkpointed; wave form only).  Segments are per song: song b has
+    // packed checkpointed decode (vit_decode_packed_checkpointed, the wave form: described here; vit_decode_packed_bounded, the
+    // workgroup kernels: the same fields with a workgroup for a wave, see banded_floor.inc / step.hip PC).  Segments are per song: song b has
     // ceil(T_b / ckpt_every) of them.  ckpt_base set, unit_song null = pass 1 (wave.hip HM 9): the slot walk of the packed batch, but
     // the only rows kept are the ones in front of segments 1 .. n_b - 1, at rows ckpt_base[b] .. of hist; every other store goes to
     // scratch row hist_rows + slot.  unit_song set = pass 2 (HM 8): wave u < B recomputes segment unit_seg[u] of song unit_song[u]
@@ -151,7 +155,7 @@ struct BtArgs {
     const int32_t* chunk_base;   // device [B+1]
     int n_waves;
     uint32_t* mask;         // [B][kLaneMaskWords] lane form: bit c = chunk c assumed the wrong state at its upper boundary (zeroed by vit_backtrace)
-    // sparse kernel over the segment units of a packed checkpointed decode: the states of sub-problem b start at states +
+    // sparse kernel and the lazy kernel's segment form over the segment units of a packed checkpointed decode: the states of sub-problem b start at states +
     // unit_states[b] (not b * states_stride), and nothing is written behind its lengths[b] frames -- those belong to the next song
     const int64_t* unit_states;  // device [B], or null
 };
@@ -190,6 +194,17 @@ hipError_t step_packed_resident(const FwdArgs& a, bool f16, int* per_cu);
 // front of a.hist, see banded.hip)
 hipError_t launch_banded_ckpt(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_step_ckpt(const FwdArgs& a, bool f16, hipStream_t st);
+// packed checkpointed decode of plans without the wave form (vit_decode_packed_bounded; a.ckpt_base set, a.ckpt_every = K).  a.unit_song
+// null = pass 1: one workgroup per slot (a.n_slots) walks its songs, keeps the rows in front of segments 1 .. n_b - 1 at rows
+// ckpt_base[b] .. of a.hist and sends every other store to scratch row a.hist_rows + slot.  a.unit_song set = one workgroup per unit
+// (a.B of them): segment unit_seg[u] of song unit_song[u], resumed from row ckpt_base[song] + segment - 1 of a.init_rows, into rows
+// u * a.hist_rows .. of a.hist (the banded kernel also writes one pad column of the row in front of them and runs one frame past the
+// segment where the song goes on: K + 2 rows per unit, a.hist at the second; the step kernel: K + 1).
+// *_pckpt_resident: workgroups of that instantiation one compute unit holds at once.
+hipError_t launch_banded_pckpt(const FwdArgs& a, bool f16, hipStream_t st);
+hipError_t banded_pckpt_resident(const FwdArgs& a, bool f16, int* per_cu);
+hipError_t launch_step_pckpt(const FwdArgs& a, bool f16, hipStream_t st);
+hipError_t step_pckpt_resident(const FwdArgs& a, bool f16, int* per_cu);
 // per song, for the segment [s0, e0) of a checkpointed decode: the sub-problem's length (0: the song ends before s0) and the state
 // its back-trace starts from (the state already decided at frame e0, or the song's terminal state)
 hipError_t launch_segment_prep(const int64_t* lengths, int64_t B, int T, int s0, int e0, const int32_t* states, const int32_t* last,
@@ -217,7 +232,8 @@ hipError_t launch_backtrace_sparse(const BtArgs& a, hipStream_t st, int phases =
 bool half_backtrace_applies(const BtArgs& a);
 hipError_t launch_backtrace_half(const BtArgs& a, hipStream_t st, int phases = 3);
 // the lazy kernel over one segment of a checkpointed decode (plans that are not banded): song bases from hist_rows / states_stride,
-// songs with lengths[] < 1 skipped (skip_nonpositive), a.chunks from the segment length
+// songs with lengths[] < 1 skipped (skip_nonpositive), a.chunks from the segment length; with a.unit_states the sub-problems are the
+// units of a packed checkpointed decode: states at states + unit_states[b], nothing written behind a unit's lengths[b] frames
 hipError_t launch_backtrace_rows_segment(BtArgs a, hipStream_t st);
 int sparse_backtrace_chunks(int64_t B, int T, int n_cus);
 // backtrace_lane.hip: one (song, chunk) stream per LANE (banded plans, full history): ~130 wave instructions per 64 decisions

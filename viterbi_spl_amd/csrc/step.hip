@@ -304,10 +304,21 @@ __global__ void __launch_bounds__(256) step4_forward_kernel(FwdArgs a) {
 //     init_rows[song] = delta_{t_begin - 1} instead of forming log_pi + e_0.  A workgroup whose song ended before t_begin leaves
 //     without writing; the terminal state is pass 1's business.
 // CK = false compiles to the code it was before the parameter existed.
-template <int BW, int KB, int PF, typename ET, bool PK = false, bool CK = false>
+// PC = true is the packed-checkpoint variant (vit_decode_packed_bounded), the slot walk of PK joined with the stores of CK, in two modes
+// told apart by a.unit_song (uniform over the launch):
+//   pass 1 (unit_song null): the workgroup is a slot and walks its songs as in PK; of song b only the rows in front of its segments
+//     1 .. n_b - 1 are kept (frames t with (t + 1) % K == 0 and t + 1 < T_b, K = ckpt_every), at rows ckpt_base[b] .. of a.hist; every
+//     other store goes to the slot's scratch row hist_rows + slot; the terminal state and the log-likelihood are written per song;
+//   unit (unit_song set): CK's segment per workgroup: workgroup u runs the K frames of segment unit_seg[u] of song unit_song[u] (emission
+//     rows at offsets[song]) from row ckpt_base[song] + segment - 1 of init_rows (segment 0: from the prior) into rows u * hist_rows ..
+// PC = false compiles to the code it was before the parameter existed (PKx / CKx below are then PK / CK).
+template <int BW, int KB, int PF, typename ET, bool PK = false, bool CK = false, bool PC = false>
 __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     static_assert(BW == 20 && KB == 9 && PF % 2 == 0, "written for nine 20-bin bands");
     static_assert(!(PK && CK), "the checkpoint / resume variant is a variant of the unpacked kernel");
+    static_assert(!(PC && (PK || CK)), "the packed-checkpoint variant is a variant of its own");
+    constexpr bool PKx = PK || PC;                // the song loop and its per-song preamble
+    constexpr bool CKx = CK || PC;                // the row selection of the stores, the resumed first frame
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NQL = 192;                      // lanes per half: 192 x 4 states
     constexpr int NPV = 4 * NQL;                  // padded voiced states
@@ -334,16 +345,19 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     const int ql = tid - NQL * (half == 1 ? 1 : 0);                       // lane within the half (halves 0, 1)
     // the song being decoded: the workgroup's own, or (PK) the slot's songs one after the other
     int song = blockIdx.x;
-    int Tb = PK ? 1 : song_length(a.lengths, song, T);
-    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PK ? (size_t)0 : (size_t)song * T * S);
-    float* __restrict__ hist = a.hist + (PK ? (size_t)0 : (CK ? (size_t)song * (size_t)a.hist_rows * SD : (size_t)song * T * SD));
+    int Tb = PKx ? 1 : song_length(a.lengths, song, T);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PKx ? (size_t)0 : (size_t)song * T * S);
+    float* __restrict__ hist = a.hist + (PKx ? (size_t)0 : (CK ? (size_t)song * (size_t)a.hist_rows * SD : (size_t)song * T * SD));
     const float* __restrict__ lpi = reinterpret_cast<const float*>(a.image + a.off_logpi);
     // (CK) first frame of this launch, first frame the loop computes, pass 1's segment length and its row bookkeeping (all wave-uniform)
-    [[maybe_unused]] const int t0 = CK ? a.t_begin : 0;
-    [[maybe_unused]] const int t1 = CK && t0 > 0 ? t0 : 1;
-    [[maybe_unused]] const int ck_every = CK ? a.ckpt_every : 0;
-    [[maybe_unused]] const int ck_scratch = CK ? (int)a.hist_rows - 1 : 0;
+    // (PC: t0 and t1 belong to the unit; ck_every is K in pass 1 and 0 in a unit launch; the scratch row is the slot's)
+    [[maybe_unused]] const bool pc_unit = PC && a.unit_song != nullptr;
+    [[maybe_unused]] int t0 = CK ? a.t_begin : 0;
+    [[maybe_unused]] int t1 = CK && t0 > 0 ? t0 : 1;
+    [[maybe_unused]] const int ck_every = CK ? a.ckpt_every : (PC && !pc_unit ? a.ckpt_every : 0);
+    [[maybe_unused]] const int ck_scratch = CK ? (int)a.hist_rows - 1 : (PC ? (int)a.hist_rows + (int)blockIdx.x : 0);
     [[maybe_unused]] int ck_next = ck_every - 1, ck_row = 0;              // the next frame that is a checkpoint, and its row
+    [[maybe_unused]] const float* __restrict__ pc_init = nullptr;         // (PC, unit) the checkpoint row in front of the unit's segment
     if constexpr (CK) {
         const int stop = ck_every > 0 || a.t_end >= T ? T : a.t_end;
         Tb = Tb < stop ? Tb : stop;
@@ -362,6 +376,36 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
         si_end = a.slot_begin[blockIdx.x + 1];
         if (si >= si_end) return;                                         // an empty slot (the host makes none)
         take_song();
+    }
+    // (PC) pass 1: the next song of the slot, its emission rows and its first checkpoint row (a.hist is the checkpoint area)
+    auto take_song_pc = [&]() {
+        song = a.slot_songs[si];
+        const long long r0 = a.offsets[song];
+        Tb = (int)(a.offsets[song + 1] - r0);
+        E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
+        ck_next = ck_every - 1;
+        ck_row = (int)a.ckpt_base[song];
+    };
+    if constexpr (PC) {
+        hist = a.hist;
+        if (pc_unit) {                                                    // one unit: its song, segment, frames and rows
+            song = a.unit_song[blockIdx.x];
+            const int useg = a.unit_seg[blockIdx.x];
+            const long long r0 = a.offsets[song];
+            const int Ts = (int)(a.offsets[song + 1] - r0);
+            t0 = useg * a.ckpt_every;
+            t1 = t0 > 0 ? t0 : 1;
+            Tb = t0 + a.ckpt_every >= Ts ? Ts : t0 + a.ckpt_every;
+            E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
+            hist = a.hist + (size_t)blockIdx.x * (size_t)a.hist_rows * SD;
+            pc_init = a.init_rows + (size_t)(a.ckpt_base[song] + useg - 1) * SD;
+            if (Tb <= t0) return;                                         // (the host lists no such unit)
+        } else {
+            si = a.slot_begin[blockIdx.x];
+            si_end = a.slot_begin[blockIdx.x + 1];
+            if (si >= si_end) return;                                     // an empty slot (the host makes none)
+            take_song_pc();
+        }
     }
 
     for (int k = tid; k < KB * VLEN + KB * FLEN + DLEN + 8 * NQL + 8; k += 448) V[k] = -INFINITY;
@@ -424,9 +468,9 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     auto mx3 = [](float acc, float x, float y) { return fmaxf(fmaxf(acc, x), y); };
 
     f32x4 dn;                                                             // delta of the own states (unvoiced wave: .x = state n, every lane)
-    if constexpr (CK) {                                                   // frame 0 (pass 1: into the scratch row), or the checkpoint row
+    if constexpr (CKx) {                                                  // frame 0 (pass 1: into the scratch row), or the checkpoint row
         if (t0 > 0) {
-            const float* __restrict__ ir = a.init_rows + (size_t)song * a.init_stride;
+            const float* __restrict__ ir = PC ? pc_init : a.init_rows + (size_t)song * a.init_stride;
             dn = mask4(f32x4{ir[col[0]], ir[col[1]], ir[col[2]], ir[col[3]]});
         } else {
             const f32x4 e0 = load4(0);
@@ -440,10 +484,10 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     }
     f32x4 er[PF];
 #pragma unroll
-    for (int k = 0; k < PF; ++k) er[k] = load4((CK ? t1 : 1) + k < Tb ? (CK ? t1 : 1) + k : Tb - 1);
+    for (int k = 0; k < PF; ++k) er[k] = load4((CKx ? t1 : 1) + k < Tb ? (CKx ? t1 : 1) + k : Tb - 1);
 
 #ifdef VIT_TIMING_HOOKS
-    const bool prof = !PK && !CK && (a.debug & 256) != 0;      // phase stamps: publish | barrier | reads | exchange + store -> scratch[song][4*wave ..]
+    const bool prof = !PKx && !CKx && (a.debug & 256) != 0;      // phase stamps: publish | barrier | reads | exchange + store -> scratch[song][4*wave ..]
 #else
     constexpr bool prof = false;
 #endif
@@ -567,10 +611,11 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
         }
         dn = mask4(m + e_slot);
         const int tn = t + PF < Tb ? t + PF : Tb - 1;
-        if constexpr (CK) {         // a segment stores frame t at t - t0, pass 1 at the next checkpoint row or the scratch row (scalar selects)
+        if constexpr (CKx) {        // a segment stores frame t at t - t0, pass 1 at the next checkpoint row or the scratch row (scalar selects)
             int row = t - t0;
             if (ck_every > 0) {
-                const bool hit = t == ck_next;
+                // (PC: a song's last frame is no checkpoint -- the row behind its last one is the next song's first)
+                const bool hit = PC ? (t == ck_next && t + 1 < Tb) : t == ck_next;
                 row = hit ? ck_row : ck_scratch;
                 ck_next += hit ? ck_every : 0;
                 ck_row += hit ? 1 : 0;
@@ -587,7 +632,7 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     };
     // ---------------- one pass per song (PK: the songs of the slot, back to back)
     for (;;) {
-        int t = CK ? t1 : 1;
+        int t = CKx ? t1 : 1;
         for (; t + PF - 1 < Tb; t += PF) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) frame(t + k, er[k]);
@@ -604,7 +649,7 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
         // terminal state: lowest-index argmax over half A's lanes (four adjacent states each) and the unvoiced state
         // (CK: pass 1 only -- a uniform test, every thread reaches the barriers or none does)
         __syncthreads();
-        if (!CK || ck_every > 0) {
+        if (!CKx || ck_every > 0) {
             VI x = vi_identity();
             if (half == 0) {
                 if (val[0]) x = VI{dn.x, j0};
@@ -625,11 +670,11 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
                 if (a.loglik) a.loglik[song] = acc.v;
             }
         }
-        if constexpr (!PK) {
+        if constexpr (!PKx) {
             break;
         } else {
-            if (++si >= si_end) break;
-            take_song();
+            if (++si >= si_end) break;                                        // (PC, unit: si_end = 1)
+            if constexpr (PC) take_song_pc(); else take_song();
             // every wave is past its last read of the song before V, F, dl, X, wm and dun go back to -inf, and none publishes
             // frame 0 of the next song before they have
             __syncthreads();
@@ -640,7 +685,7 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
                 int cq[4] = {col[0], col[1], col[2], col[3]};             // (opaque: the prior's addresses are formed here, per song)
                 asm volatile("" : "+v"(cq[0]), "+v"(cq[1]), "+v"(cq[2]), "+v"(cq[3]));
                 dn = mask4(f32x4{lpi[cq[0]], lpi[cq[1]], lpi[cq[2]], lpi[cq[3]]} + e0);
-                store4(0, dn);
+                store4(PC ? ck_scratch : 0, dn);                          // (PC reaches here in pass 1 only)
             }
 #pragma unroll
             for (int k = 0; k < PF; ++k) er[k] = load4(1 + k < Tb ? 1 + k : Tb - 1);
@@ -674,6 +719,31 @@ hipError_t launch_step_ckpt(const FwdArgs& a, bool f16, hipStream_t st) {
         hipLaunchKernelGGL((step4s_forward_kernel<BW, KB, PF, float, false, true>), dim3((int)a.B), dim3(448), ldss, st, a);
     return hipGetLastError();
 }
+
+// packed-checkpoint variant of step4s_forward_kernel: one workgroup per slot (pass 1) or per unit; with `per_cu` the occupancy query
+static hipError_t step_pckpt(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu) {
+    constexpr int BW = 20, KB = 9, PF = 2;
+    if (!step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) return hipErrorInvalidConfiguration;
+    constexpr int VL4 = 768 + 2 * (KB * BW + BW);
+    const size_t ldss = sizeof(float) * (KB * VL4 + KB * (VL4 / 4) + (768 + 64) + 8 * 192 + 8) + sizeof(VI) * 16;
+    const int groups = a.unit_song ? (int)a.B : a.n_slots;
+    auto go = [&](auto kern) -> hipError_t {
+        if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, 448, ldss);
+        hipLaunchKernelGGL(kern, dim3(groups), dim3(448), ldss, st, a);
+        return hipGetLastError();
+    };
+    return f16 ? go(step4s_forward_kernel<BW, KB, PF, __half, false, false, true>) : go(step4s_forward_kernel<BW, KB, PF, float, false, false, true>);
+}
+
+hipError_t launch_step_pckpt(const FwdArgs& a, bool f16, hipStream_t st) {
+    if (!a.offsets || !a.ckpt_base || a.ckpt_every < 1 || a.hist_rows < 0) return hipErrorInvalidValue;
+    if (a.unit_song ? (!a.unit_seg || !a.init_rows || a.B < 1 || a.hist_rows < (int64_t)a.ckpt_every)
+                    : (!a.slot_begin || !a.slot_songs || a.n_slots < 1))
+        return hipErrorInvalidValue;
+    return step_pckpt(a, f16, st, nullptr);
+}
+
+hipError_t step_pckpt_resident(const FwdArgs& a, bool f16, int* per_cu) { return step_pckpt(a, f16, nullptr, per_cu); }
 
 hipError_t launch_step_packed(const FwdArgs& a, bool f16, hipStream_t st) {
     if (!a.offsets || !a.slot_begin || !a.slot_songs || a.n_slots < 1) return hipErrorInvalidValue;

@@ -377,17 +377,25 @@ class ViterbiDecoder:
         plans whose floor form is proven (the 722-state jdc grids, one workgroup per forward slot) and step-structured plans (the
         Durrieu matrix); any other plan (unstructured matrices, banded plans with only the scan form) raises ``ViterbiHipError``.
 
-        ``max_workspace_bytes``: a budget for the workspace (``plan_workspace_packed``): where the full history does not fit, the
-        decode falls to ``decode_packed_checkpointed`` with the largest segment length that does -- the same states and
-        log-likelihoods -- and raises ``ViterbiHipError`` when nothing fits.  ``None``: the full history, whatever it takes."""
+        ``max_workspace_bytes``: a budget for the workspace: where the full history does not fit, the decode falls to the
+        checkpointed form with the largest segment length that does -- the same states and log-likelihoods -- and raises
+        ``ViterbiHipError`` when nothing fits.  Plans with the wave form: ``plan_workspace_packed`` and
+        ``decode_packed_checkpointed``; the other plans (the 722-state grids): ``plan_workspace_packed_bounded`` and
+        ``decode_packed_bounded``.  ``None``: the full history, whatever it takes."""
         lib = _lib.load()
         dt, off = self._check_packed(emission_logits, offsets)
         B, N = off.size - 1, int(off[-1])
         if B > 0 and max_workspace_bytes is not None:
-            mode = self.plan_workspace_packed(off, int(max_workspace_bytes))
-            if mode["mode"] == "checkpointed":
-                return self.decode_packed_checkpointed(emission_logits, off, segment_frames=mode["segment_frames"], out_dtype=out_dtype,
-                                                       workspace=workspace)
+            if self.info["wave_ok"]:
+                mode = self.plan_workspace_packed(off, int(max_workspace_bytes))
+                if mode["mode"] == "checkpointed":
+                    return self.decode_packed_checkpointed(emission_logits, off, segment_frames=mode["segment_frames"], out_dtype=out_dtype,
+                                                           workspace=workspace)
+            else:
+                mode = self.plan_workspace_packed_bounded(off, int(max_workspace_bytes))
+                if mode["mode"] == "checkpointed":
+                    return self.decode_packed_bounded(emission_logits, off, segment_frames=mode["segment_frames"], out_dtype=out_dtype,
+                                                      workspace=workspace)
         states = torch.empty((N,), dtype=torch.int32, device=self.device)
         loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
         if B > 0:
@@ -484,6 +492,77 @@ class ViterbiDecoder:
                                        "split the recordings into groups whose workspace_bytes_packed fits)")
         raise _lib.ViterbiHipError(f"no packed decode of {B} recordings ({N} frames) fits a workspace of {max_workspace_bytes} bytes "
                                    f"(the full history needs {need}, the checkpointed decode at least {least})")
+
+    # ------------------------------------------------------------------ the same for every plan with a packed decode
+    def workspace_bytes_packed_bounded(self, offsets, segment_frames: int) -> int:
+        """Workspace bytes of ``decode_packed_bounded`` for the recordings ``offsets`` describes (B + 1 host frame offsets); raises
+        ViterbiHipError for a plan or a segment length it does not serve."""
+        off = self._host_offsets(offsets)
+        need = int(_lib.load().vit_workspace_bytes_packed_bounded(self._plan, off.size - 1, off.ctypes.data, int(segment_frames)))
+        if need == 0:
+            raise _lib.ViterbiHipError("the bounded packed decode needs 64 <= segment_frames <= 2**24 and a plan with the wave form, the floor "
+                                       "form with the sparse back-trace, or the step form (unstructured matrices and scan-only banded "
+                                       "plans: pad and use decode(lengths=))")
+        return need
+
+    def decode_packed_bounded(self, emission_logits: torch.Tensor, offsets, segment_frames: int = 1024, out_dtype: torch.dtype = torch.int64,
+                              workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_packed`` with a bounded workspace for every plan it serves (``vit_decode_packed_bounded``).  Plans with the wave form
+        run ``decode_packed_checkpointed`` (the same size, the same bits).  The 722-state floor and step plans run its scheme with one
+        workgroup per forward slot and per (recording, segment) unit: ``n_units * (K + 2)`` (step plans: ``K + 1``) delta rows for the
+        segments being walked (``n_units = min(B, u x compute units)``, u = 1 / 2, ``K = segment_frames``) plus one row per K frames.
+        Same arguments, same states, same log-likelihoods as ``decode_packed``; about twice the forward work.  Any other plan raises
+        ``ViterbiHipError`` before anything is enqueued.  ``workspace``: an optional uint8 tensor of at least
+        ``workspace_bytes_packed_bounded(...) + 256`` bytes to decode in (the caller then keeps it alive until the stream has run the
+        decode: the call does not synchronise)."""
+        lib = _lib.load()
+        dt, off = self._check_packed(emission_logits, offsets)
+        B, N = off.size - 1, int(off[-1])
+        states = torch.empty((N,), dtype=torch.int32, device=self.device)
+        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
+        if B > 0:
+            need = self.workspace_bytes_packed_bounded(off, segment_frames)
+            ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
+                raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
+            with torch.cuda.device(self.device):
+                rc = lib.vit_decode_packed_bounded(self._plan, emission_logits.data_ptr(), dt, B, off.ctypes.data, (ws.data_ptr() + 255) & ~255,
+                                                   ws.numel() - 256, states.data_ptr(), loglik.data_ptr(), int(segment_frames),
+                                                   torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(rc, "vit_decode_packed_bounded")
+            if workspace is None:
+                torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
+        if out_dtype != torch.int32:
+            states = states.to(out_dtype)
+        return states, loglik
+
+    def plan_workspace_packed_bounded(self, offsets, max_workspace_bytes: Optional[int] = None) -> dict:
+        """``plan_workspace_packed`` over ``decode_packed_bounded``: ``{"mode": "full", "workspace_bytes": ...}`` when ``decode_packed``
+        fits the budget, else ``{"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ...}`` with the largest K of 8192,
+        4096, ..., 64 whose ``workspace_bytes_packed_bounded`` fits.  Raises ViterbiHipError naming the least need when nothing fits
+        or the plan is not served."""
+        off = self._host_offsets(offsets)
+        B, N = off.size - 1, int(off[-1])
+        need = self.workspace_bytes_packed(B, N)
+        if need == 0 and B > 0:
+            raise _lib.ViterbiHipError("the packed decode needs a plan with the wave form, the floor form or the step form "
+                                       "(unstructured matrices and scan-only banded plans: pad and use decode(lengths=))")
+        if max_workspace_bytes is None or need <= max_workspace_bytes:
+            return {"mode": "full", "workspace_bytes": need}
+        lib = _lib.load()
+        least, K = 0, 8192
+        while K >= 64:
+            ck = int(lib.vit_workspace_bytes_packed_bounded(self._plan, B, off.ctypes.data, K))
+            if 0 < ck <= max_workspace_bytes:           # the largest segment that fits: fewest launches
+                return {"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ck}
+            least = ck if least == 0 or 0 < ck < least else least
+            K //= 2
+        if least == 0:
+            raise _lib.ViterbiHipError(f"the packed decode of {B} recordings ({N} frames) needs a workspace of {need} bytes, the budget is "
+                                       f"{max_workspace_bytes}, and this plan has no bounded packed decode (pad and use "
+                                       "decode_checkpointed(lengths=))")
+        raise _lib.ViterbiHipError(f"no packed decode of {B} recordings ({N} frames) fits a workspace of {max_workspace_bytes} bytes "
+                                   f"(the full history needs {need}, the bounded decode at least {least})")
 
     # ------------------------------------------------------------------ fused logits -> path decode
     @staticmethod

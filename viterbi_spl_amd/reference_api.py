@@ -422,13 +422,15 @@ class ImmViterbi:
         states, _ = self._decoder.decode(E, out_dtype=torch.int64)
         return states
 
-    def decode_activations_recordings(self, hf0_cat, offsets=None):
+    def decode_activations_recordings(self, hf0_cat, offsets=None, max_workspace_bytes=None):
         """Many recordings in one pass: ``hf0_cat [n_bins, sum T_b]`` holds them side by side along the frame axis, recording b in
         columns ``offsets[b] : offsets[b+1]`` (``offsets``: a host sequence of B + 1 frame offsets from 0).  One emission-builder
         call with per-recording statistics and one packed decode (``vit_decode_packed``; the step-structured plan of the Durrieu
         matrix is served there).  ``hf0_cat`` may also be a list of ``[n_bins, T_b]`` tensors or arrays, which are concatenated
         along frames first -- that is a copy of every recording; callers that can should fill one buffer.  Returns a list of
-        ``int64[T_b]`` state tensors on the GPU, each equal to ``decode_activations`` of that recording alone."""
+        ``int64[T_b]`` state tensors on the GPU, each equal to ``decode_activations`` of that recording alone.
+        ``max_workspace_bytes``: a budget for the decoder's workspace (``ViterbiDecoder.decode_packed``: the bounded packed decode
+        where the full delta history, 2896 bytes per frame at 722 states, does not fit; the same result).  ``None``: the full history."""
         from .emissions import activation_log_emissions
         if isinstance(hf0_cat, (list, tuple)):
             if offsets is not None:
@@ -443,7 +445,7 @@ class ImmViterbi:
         x = self._to_device(hf0_cat)
         off = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, dtype=np.int64)
         E = activation_log_emissions(x, offsets=off, dtype=self._torch_dtype())
-        states, _ = self._decoder.decode_packed(E, off, out_dtype=torch.int64)
+        states, _ = self._decoder.decode_packed(E, off, out_dtype=torch.int64, max_workspace_bytes=max_workspace_bytes)
         return [states[off[b]:off[b + 1]] for b in range(off.size - 1)]
 
     def __call__(self, HF0):
