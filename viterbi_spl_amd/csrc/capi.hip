@@ -18,9 +18,8 @@
 // Kernel-selection overrides (vit_plan_set_option).  Every combination decodes the same bits; they exist so that tests and
 // timing scripts can reach each kernel form.  `timing` carries the ablation / probe mask of a -DVIT_TIMING_HOOKS build and
 // is refused by a release build (those bits DO change results).
-// vit_decode_checkpointed of a plan without the wave form always runs the one-target floor kernel / the two-wave step kernel and picks
-// its back-trace from the plan: it does not consult forward_form, step_form, backtrace_form or bt_chunks (bt_fast_rows, bt_warm and
-// win_shift it does).
+// Which of them the checkpointed decodes consult is said once, at segment_backtrace and above vit_decode_checkpointed; in short: the
+// kernels are fixed by the plan's family, and bt_warm reaches the segment back-traces of the step and group families only.
 struct Tuning {
     int forward_form = 0;      // banded plans: 0 by batch size | 1 one target per lane | 2 two targets per lane | 3 scan form | 6 split windows
                                //               | 4 wave form (one song per wavefront) | 5 never the wave form
@@ -31,7 +30,7 @@ struct Tuning {
     int dense_form = 0;        // 0: matrix-resident dense kernel where it applies (64 < S <= 368) | 1: always the streaming kernel
     int step_form = 0;         // step-structured kernel, four targets per lane: 0 bands split over two waves | 3 one wave
     int bt_chunks = 0;         // time-parallel back-trace: chunks per song (0 = auto)
-    int bt_warm = -1;          //                            warm-up frames (-1 = default)
+    int bt_warm = -1;          //                            warm-up frames (-1 = default; NOT consulted by the wave family's segment back-traces)
     int win_shift = -1;        // LDS window shift of the floor kernels (-1 = from the plan)
     int wave_min_batch = 0;    // batch size from which banded plans take the wave form (0 = default)
     int wave_two = 0;          // wave kernel: 1 always the 256-register instantiation (the default but for two extra columns) | 2 the 512-register
@@ -44,13 +43,29 @@ struct Tuning {
     int timing = 0;
 };
 
+// Forward kernel families.  The values are public: vit_forward_family returns them and FwdStamp::family stores them.
+enum Family : int {
+    kFamNone = 0,              // (the answer of the *_family predicates for a plan an entry point does not serve)
+    kFamStep = 1,              // dense / step kernels: any matrix, or the step-structured one
+    kFamGroup = 2,             // banded, one song per workgroup
+    kFamWave = 3,              // banded, one song per wavefront
+};
+
+// Where a state's column, the frame maximum and the copies of the extra columns sit in a history row: hist_layout(plan, family).
+struct HistLayout {
+    int SD = 0;                // row stride, floats
+    int col0 = 0, mcol = 0;    // state i in column col0 + i, the frame maximum in column mcol
+    int xcol0 = -1;            // >= 0: column xcol0 + k holds a copy of delta of extra column k
+    int have_fmax = 0;         // column mcol of every history row holds a bound on max_i delta_t[i]
+};
+
 // What the last vit_forward left in a workspace: vit_backtrace reads the layout from here, not from its arguments.
 struct FwdStamp {
     const void* ws = nullptr;
     int64_t B = 0, T = 0;
-    int family = 0;            // 1 dense / step, 2 banded (one song per workgroup), 3 wave
-    int SD = 0, col0 = 0, mcol = 0, xcol0 = -1, aux_frames = 1;
-    int have_fmax = 0;         // column mcol of every history row holds a bound on max_i delta_t[i]
+    int family = 0;            // Family
+    HistLayout lay;            // the history rows the forward kernel wrote
+    int aux_frames = 1;        // frames whose scalars a row carries (BtArgs::aux_frames)
     int half = 0;              // wave form, even rows only: the back-trace re-reads the emissions
     const void* logE = nullptr;
     int e_f16 = 0;
@@ -71,8 +86,9 @@ struct vit_plan {
     mutable void* pk_host = nullptr;
     mutable size_t pk_host_bytes = 0;
     mutable hipEvent_t pk_event = nullptr;
-    mutable int pk_resident[2] = {0, 0};   // workgroups per CU of the packed workgroup-form kernel (fp32 / fp16 emissions), 0 = not asked yet
-    mutable int pb_resident[2] = {0, 0};   // the same for the packed-checkpoint variant (vit_decode_packed_bounded, pass 1's slots)
+    // workgroups per CU of the packed workgroup-form kernel [0] and of its packed-checkpoint variant [1] (vit_decode_packed_bounded, pass
+    // 1's slots), by emission type (fp32 / fp16); 0 = not asked yet (resident_per_cu)
+    mutable int resident[2][2] = {{0, 0}, {0, 0}};
     ~vit_plan() {
         if (pk_event) (void)hipEventDestroy(pk_event);
         if (pk_host) (void)hipHostFree(pk_host);
@@ -85,10 +101,37 @@ thread_local int g_last_hip_error = 0;
 
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 inline int hist_stride(int S) { return (S + 5) / 4 * 4; }   // rows 16-byte aligned, at least two pad columns (frame max, scratch)
-// widest history row any forward kernel of this plan writes (the wave form stores rows in slot order: 64 * npl floats)
+// The history row layout of one forward family: the ONE place that knows it.  Workgroup kernels (step, group): state i in column i,
+// the frame maximum (banded kernels only) in pad column S.  Wave form: rows in slot order, 64 * npl floats, the states at the end,
+// the frame maximum in column 0 and the extra columns' copies behind it.
+HistLayout hist_layout(const vit_plan* p, int family) {
+    HistLayout h;
+    if (family == kFamWave) {
+        h.SD = vit::wave_hist_stride(p->bp.wave_npl);
+        h.col0 = h.SD - p->S;
+        h.mcol = 0;
+        h.xcol0 = 1;
+        h.have_fmax = 1;
+    } else {
+        h.SD = hist_stride(p->S);
+        h.col0 = 0;
+        h.mcol = p->S;
+        h.xcol0 = -1;
+        h.have_fmax = family == kFamGroup ? 1 : 0;
+    }
+    return h;
+}
+void hist_layout_apply(const HistLayout& h, vit::BtArgs& b) {     // (aux_frames is the caller's: it depends on what was stored, not on the family)
+    b.SD = h.SD;
+    b.col0 = h.col0;
+    b.mcol = h.mcol;
+    b.xcol0 = h.xcol0;
+    b.have_fmax = h.have_fmax;
+}
+// widest history row any forward kernel of this plan writes
 inline int hist_stride_ws(const vit_plan* p) {
-    const int sd = hist_stride(p->S);
-    const int sw = (p->bp.ok && p->bp.wave_ok) ? vit::wave_hist_stride(p->bp.wave_npl) : 0;
+    const int sd = hist_layout(p, kFamStep).SD;
+    const int sw = (p->bp.ok && p->bp.wave_ok) ? hist_layout(p, kFamWave).SD : 0;
     return sd > sw ? sd : sw;
 }
 constexpr size_t kMaxStamps = 64;    // workspaces with a forward pass on record per plan (include/viterbi_hip.h, vit_forward)
@@ -119,6 +162,13 @@ int hip_fail(hipError_t e) {
     g_last_hip_error = (int)e;
     return VIT_EHIP;
 }
+inline int hip_status(hipError_t e) { return e == hipSuccess ? VIT_OK : hip_fail(e); }
+// a HIP call or launch in a function that returns a status: on failure record the error (vit_last_hip_error) and return VIT_EHIP
+#define VIT_TRY(expr)                                               \
+    do {                                                            \
+        const hipError_t vit_try_e_ = (expr);                       \
+        if (vit_try_e_ != hipSuccess) return hip_fail(vit_try_e_);  \
+    } while (0)
 
 struct WsLayout {
     size_t off_hist, off_fmax, off_cnt, off_mask, off_last, off_entry, bytes;
@@ -143,11 +193,10 @@ WsLayout ws_layout(const vit_plan* p, int64_t B, int64_t T) { return ws_layout_h
 // (backtrace_half.hip) is asked with the layout the forward kernel would write.
 bool wave_half_applies(const vit_plan* p, int64_t T) {
     if (!(p->bp.ok && p->bp.wave_ok) || p->tune.wave_history != 2 || T < 2) return false;
-    vit::BtArgs b{};
+    vit::BtArgs b{};                 // a probe: only what half_backtrace_applies reads, NOT bt_args_from_plan
+    hist_layout_apply(hist_layout(p, kFamWave), b);
     b.S = p->S;
     b.SP = p->L.SP;
-    b.SD = vit::wave_hist_stride(p->bp.wave_npl);
-    b.col0 = b.SD - p->S;
     b.W = p->bp.W;
     b.banded = 1;
     b.n_extras = p->bp.n_extras;
@@ -156,13 +205,10 @@ bool wave_half_applies(const vit_plan* p, int64_t T) {
     b.lo_off = p->bp.lo_off;
     return vit::half_backtrace_applies(b);
 }
-// the layout of one forward family (1 dense / step, 2 banded workgroup kernels, 3 wave)
+// the workspace of one forward family
 WsLayout ws_layout_family(const vit_plan* p, int family, int64_t B, int64_t T) {
-    if (family == 3) {
-        const size_t sd = (size_t)vit::wave_hist_stride(p->bp.wave_npl);
-        return wave_half_applies(p, T) ? ws_layout_hist(B, (size_t)((T + 1) / 2), sd) : ws_layout_hist(B, (size_t)T, sd);
-    }
-    return ws_layout_hist(B, (size_t)T, (size_t)hist_stride(p->S));
+    const bool half = family == kFamWave && wave_half_applies(p, T);
+    return ws_layout_hist(B, (size_t)(half ? (T + 1) / 2 : T), (size_t)hist_layout(p, family).SD);
 }
 
 int check_common(const vit_plan* plan, int64_t B, int64_t T, const void* ws) {
@@ -265,9 +311,7 @@ size_t vit_plan_image_bytes(const vit_plan* plan) { return plan ? plan->L.bytes 
 int vit_plan_upload(vit_plan* plan, void* device_image, size_t bytes, vit_stream stream) {
     if (!plan || !device_image) return VIT_EINVAL;
     if (bytes < plan->L.bytes || ((uintptr_t)device_image & 255) != 0) return VIT_EINVAL;
-    hipError_t e = hipMemcpyAsync(device_image, plan->host_image.data(), plan->L.bytes, hipMemcpyHostToDevice,
-                                  (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e);
+    VIT_TRY(hipMemcpyAsync(device_image, plan->host_image.data(), plan->L.bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
     plan->dev_image = static_cast<const uint8_t*>(device_image);
     int dev = 0, cus = 0;      // the thresholds below are "how many workgroups / waves fit the chip at once": from the device, not from "256"
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
@@ -307,7 +351,7 @@ int vit_plan_set_option(vit_plan* plan, const char* key, int64_t value) {
     return VIT_OK;
 }
 
-// forward kernel family for (plan, algo, batch): 1 dense / step, 2 banded one song per workgroup, 3 wave; < 0 = status
+// forward kernel family (Family) for (plan, algo, batch); < 0 = status
 static int resolve_family(const vit_plan* plan, int algo, int64_t B) {
     const int nwt = vit::banded_waves_for(plan->S);
     const bool group_ok = plan->bp.ok && (vit::scan_form_instantiated(plan->bp.W, nwt) ||
@@ -315,14 +359,14 @@ static int resolve_family(const vit_plan* plan, int algo, int64_t B) {
     const bool wave_ok = plan->bp.ok && plan->bp.wave_ok;
     const int ff = plan->tune.forward_form;
     const int64_t wmin = plan->tune.wave_min_batch > 0 ? plan->tune.wave_min_batch : wave_min_batch(plan);
-    if (algo == VIT_ALGO_DENSE) return 1;
-    if (algo == VIT_ALGO_WAVE) return wave_ok ? 3 : VIT_EUNSUPPORTED;
-    if (algo == VIT_ALGO_GROUP) return group_ok ? 2 : VIT_EUNSUPPORTED;
+    if (algo == VIT_ALGO_DENSE) return kFamStep;
+    if (algo == VIT_ALGO_WAVE) return wave_ok ? kFamWave : VIT_EUNSUPPORTED;
+    if (algo == VIT_ALGO_GROUP) return group_ok ? kFamGroup : VIT_EUNSUPPORTED;
     if (algo != VIT_ALGO_AUTO && algo != VIT_ALGO_BANDED) return VIT_EINVAL;
     const bool want_wave = wave_ok && ff != 5 && (ff == 4 || (ff == 0 && B >= wmin) || !group_ok);
-    if (want_wave) return 3;
-    if (group_ok) return 2;
-    return algo == VIT_ALGO_AUTO ? 1 : VIT_EUNSUPPORTED;
+    if (want_wave) return kFamWave;
+    if (group_ok) return kFamGroup;
+    return algo == VIT_ALGO_AUTO ? kFamStep : VIT_EUNSUPPORTED;
 }
 
 // the fields of FwdArgs that depend on the plan and its options only
@@ -389,8 +433,8 @@ int vit_forward(const vit_plan* plan, const void* logE, int emis_dtype, int64_t 
     const int family = resolve_family(plan, algo, B);
     if (family < 0) return family;
     const Tuning& tn = plan->tune;
-    const bool half = family == 3 && wave_half_applies(plan, T);
-    if (family == 3 && tn.wave_history == 2 && !half && T >= 2) return VIT_EUNSUPPORTED;
+    const bool half = family == kFamWave && wave_half_applies(plan, T);
+    if (family == kFamWave && tn.wave_history == 2 && !half && T >= 2) return VIT_EUNSUPPORTED;
     const WsLayout w = ws_layout_family(plan, family, B, T);
     if (workspace_bytes < w.bytes) return VIT_EWORKSPACE;
     if (B == 0) return VIT_OK;
@@ -417,23 +461,15 @@ int vit_forward(const vit_plan* plan, const void* logE, int emis_dtype, int64_t 
     st.B = B;
     st.T = T;
     st.family = family;
-    st.SD = a.SD;
-    st.col0 = 0;
-    st.mcol = plan->S;
-    st.have_fmax = family == 2 ? 1 : 0;
+    st.lay = hist_layout(plan, family);
     st.logE = logE;
     st.e_f16 = emis_dtype == VIT_F16 ? 1 : 0;
     hipError_t e;
-    if (family == 3) {
-        st.SD = vit::wave_hist_stride(plan->bp.wave_npl);
-        st.col0 = st.SD - plan->S;
-        st.mcol = 0;
-        st.xcol0 = 1;
+    if (family == kFamWave) {
         st.aux_frames = half || (a.wave_flags & 4) ? 1 : vit::wave_aux_frames(plan->bp.wave_npl, plan->S, a.n_extras);
-        st.have_fmax = 1;
         st.half = half ? 1 : 0;
         e = vit::launch_wave(a, emis_dtype == VIT_F16, (hipStream_t)stream);
-    } else if (family == 2) {
+    } else if (family == kFamGroup) {
         e = vit::launch_banded(a, emis_dtype == VIT_F16, (hipStream_t)stream);
     } else if (algo == VIT_ALGO_AUTO && a.step_ok && vit::step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) {
         // dense matrix with step structure (Durrieu): VIT_ALGO_DENSE still means the plain dense kernel
@@ -443,7 +479,7 @@ int vit_forward(const vit_plan* plan, const void* logE, int emis_dtype, int64_t 
         const int ns = tn.dense_songs > 0 ? tn.dense_songs : (B >= 512 ? 2 : 1);
         e = vit::launch_dense(a, ns, emis_dtype == VIT_F16, (hipStream_t)stream);
     }
-    if (e != hipSuccess) return hip_fail(e);
+    VIT_TRY(e);
     stamp_put(plan, st);
     return VIT_OK;
 }
@@ -516,7 +552,7 @@ static int backtrace_impl(const vit_plan* plan, const void* logE, int emis_dtype
     // the emission tensor must be the one the forward pass decoded (a half history reads it again through the recorded pointer)
     if (check_e && (st.logE != logE || st.e_f16 != (emis_dtype == VIT_F16 ? 1 : 0))) return VIT_EINVAL;
     const Tuning& tn = plan->tune;
-    const WsLayout w = st.half ? ws_layout_hist(B, (size_t)((T + 1) / 2), (size_t)st.SD) : ws_layout_hist(B, (size_t)T, (size_t)st.SD);
+    const WsLayout w = ws_layout_hist(B, (size_t)(st.half ? (T + 1) / 2 : T), (size_t)st.lay.SD);
     if (workspace_bytes < w.bytes) return VIT_EWORKSPACE;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
     vit::BtArgs b{};
@@ -528,21 +564,14 @@ static int backtrace_impl(const vit_plan* plan, const void* logE, int emis_dtype
     b.B = B;
     b.T = (int)T;
     bt_args_from_plan(plan, b);
-    b.SD = st.SD;
-    b.col0 = st.col0;
-    b.mcol = st.mcol;
-    b.xcol0 = st.xcol0;
+    hist_layout_apply(st.lay, b);
     b.aux_frames = st.aux_frames;
-    b.have_fmax = st.have_fmax;
     b.states_stride = T;
-    if (st.family == 3 && !(b.banded && b.n_dense == 0)) return VIT_EINVAL;   // (cannot happen: wave_ok implies both)
+    if (st.family == kFamWave && !(b.banded && b.n_dense == 0)) return VIT_EINVAL;   // (cannot happen: wave_ok implies both)
     b.hist_rows = T;
     b.counters = reinterpret_cast<int32_t*>(ws + w.off_cnt);          // event counts of this back-trace, chunk flags of the lane form
     b.mask = reinterpret_cast<uint32_t*>(ws + w.off_mask);
-    {
-        hipError_t ez = hipMemsetAsync(ws + w.off_cnt, 0, w.off_last - w.off_cnt, (hipStream_t)stream);
-        if (ez != hipSuccess) return hip_fail(ez);
-    }
+    VIT_TRY(hipMemsetAsync(ws + w.off_cnt, 0, w.off_last - w.off_cnt, (hipStream_t)stream));
     if (st.half) {
         b.hist_half = 1;
         b.hist_rows = (T + 1) / 2;
@@ -556,16 +585,14 @@ static int backtrace_impl(const vit_plan* plan, const void* logE, int emis_dtype
         b.warm = vit::kBtWarmSparse;
         if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kBtMaxChunks) b.chunks = tn.bt_chunks;
         if (tn.bt_warm >= 0) b.warm = tn.bt_warm;
-        hipError_t eh = vit::launch_backtrace_half(b, (hipStream_t)stream);
-        return eh == hipSuccess ? VIT_OK : hip_fail(eh);
+        return hip_status(vit::launch_backtrace_half(b, (hipStream_t)stream));
     }
     if (b.bt_form == 4) {                                             // one (song, chunk) stream per lane
         if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
         b.warm = tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarmSparse;
         b.chunks = vit::lane_backtrace_chunks(B, (int)T, plan->n_cus, b.warm);
         if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kLaneMaxChunks) b.chunks = tn.bt_chunks;
-        hipError_t el = vit::launch_backtrace_lane(b, (hipStream_t)stream);
-        return el == hipSuccess ? VIT_OK : hip_fail(el);
+        return hip_status(vit::launch_backtrace_lane(b, (hipStream_t)stream));
     }
     const bool sparse = b.bt_form == 0 && vit::sparse_backtrace_applies(b);
     b.chunks = sparse ? vit::sparse_backtrace_chunks(B, (int)T, plan->n_cus) : vit::backtrace_chunks(B, (int)T);
@@ -573,16 +600,14 @@ static int backtrace_impl(const vit_plan* plan, const void* logE, int emis_dtype
     // test hooks (vit_plan_set_option): force the chunking / warm-up so that the verify-and-repair pass is exercised
     if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kBtMaxChunks) b.chunks = tn.bt_chunks;
     if (tn.bt_warm >= 0) b.warm = tn.bt_warm;
-    hipError_t e = vit::launch_backtrace(b, (hipStream_t)stream);
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(vit::launch_backtrace(b, (hipStream_t)stream));
 }
 
 int vit_backtrace_counters(const vit_plan* plan, int64_t B, int64_t T, const void* workspace, size_t* offset, int32_t* n_per_song) {
     if (!plan || !workspace || !offset || !n_per_song) return VIT_EINVAL;
     FwdStamp st;
     if (!stamp_get(plan, workspace, &st) || st.B != B || st.T != T) return VIT_ENOFORWARD;
-    const WsLayout w = st.half ? ws_layout_hist(B, (size_t)((T + 1) / 2), (size_t)st.SD) : ws_layout_hist(B, (size_t)T, (size_t)st.SD);
-    *offset = w.off_cnt;
+    *offset = ws_layout_hist(B, (size_t)(st.half ? (T + 1) / 2 : T), (size_t)st.lay.SD).off_cnt;
     *n_per_song = vit::kBtCounters;
     return VIT_OK;
 }
@@ -604,37 +629,35 @@ int vit_decode(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B
 // (the row in front of the segment) plus the terminal state; pass 2 walks the segments from the last to the first, re-runs the
 // forward kernel over one segment from its checkpoint row into a buffer of about K rows and back-traces it from the state the
 // segment behind it decided at its first frame.  Exact by construction (the same kernels, the same sums); twice the forward work.
-// Three families (ck_family): plans with the wave form (wave.hip HM 5 / 6, the sparse back-trace); banded plans without it whose
+// Three families (ck_family, Family): plans with the wave form (wave.hip HM 5 / 6, the sparse back-trace); banded plans without it whose
 // floor form is proven (banded_floor_forward_kernel<.., CK>, the sparse back-trace over the workgroup layout, or the lane form);
 // step plans (step4s_forward_kernel<.., CK>, the lazy back-trace).  The workgroup families always run that one kernel:
 // forward_form, step_form, backtrace_form and bt_chunks are not consulted; bt_fast_rows, bt_warm and win_shift are.
 namespace {
 
-// the sparse back-trace serves the history layout a checkpointed decode of this plan writes (family 3: the wave layout, 2: workgroup rows)
+// the sparse back-trace serves the history layout a checkpointed decode of this plan writes (kFamWave: the wave layout, kFamGroup: workgroup rows)
 bool ck_sparse_applies(const vit_plan* p, int family) {
-    vit::BtArgs b{};
+    vit::BtArgs b{};                 // a probe: only what sparse_backtrace_applies reads, NOT bt_args_from_plan (lo_affine stays 0)
+    hist_layout_apply(hist_layout(p, family), b);
     b.S = p->S;
     b.SP = p->L.SP;
-    b.SD = family == 3 ? vit::wave_hist_stride(p->bp.wave_npl) : hist_stride(p->S);
-    b.col0 = family == 3 ? b.SD - p->S : 0;
     b.W = p->bp.W;
     b.banded = 1;
-    b.have_fmax = 1;
     b.n_extras = p->bp.n_extras;
     b.n_dense = p->bp.n_dense;
     return vit::sparse_backtrace_applies(b);
 }
 // the lane back-trace does (lane_backtrace_applies for the workgroup rows: width instantiated, W <= S, no dense rows)
 bool ck_lane_applies(const vit_plan* p) { return p->bp.n_dense == 0 && vit::banded_width_instantiated(p->bp.W) && p->bp.W <= p->S; }
+inline bool step_applies(const vit_plan* p) { return p->bp.step_ok && vit::step_kernel_instantiated(p->S, p->bp.step_bw, p->bp.step_kb); }
 
-// The forward family a checkpointed decode of this plan runs (FwdStamp::family numbering), 0 = none: the ONE predicate behind
+// The forward family a checkpointed decode of this plan runs, kFamNone = none: the ONE predicate behind
 // vit_workspace_bytes_checkpointed and vit_decode_checkpointed, so that a size > 0 implies a decode that launches.
 int ck_family(const vit_plan* p) {
-    if (p->bp.ok && p->bp.wave_ok) return ck_sparse_applies(p, 3) ? 3 : 0;
+    if (p->bp.ok && p->bp.wave_ok) return ck_sparse_applies(p, kFamWave) ? kFamWave : kFamNone;
     if (p->bp.ok)      // banded, no wave form: the floor form (no dense rows) and a back-trace over its rows
-        return vit::floor_ckpt_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && (ck_sparse_applies(p, 2) || ck_lane_applies(p)) ? 2 : 0;
-    if (p->bp.step_ok && vit::step_kernel_instantiated(p->S, p->bp.step_bw, p->bp.step_kb)) return 1;
-    return 0;
+        return vit::floor_ckpt_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && (ck_sparse_applies(p, kFamGroup) || ck_lane_applies(p)) ? kFamGroup : kFamNone;
+    return step_applies(p) ? kFamStep : kFamNone;
 }
 inline bool ck_segment_ok(int64_t K) { return K >= 64 && K <= (int64_t)1 << 24; }
 
@@ -642,27 +665,52 @@ struct CkLayout {
     int64_t nseg, seg_rows;
     size_t off_ckpt, off_seg, off_cnt, off_mask, off_last, off_entry, off_slen, off_slast, bytes;
 };
-// Family 3 keeps the byte counts it had when it was the only one.  Families 1 and 2: rows of hist_stride(S) floats; the segment
+// The wave family keeps the byte counts it had when it was the only one.  The workgroup families: the segment
 // buffer holds K + 2 rows per song -- one in FRONT of the segment (the banded kernel stores the frame maximum of frame t - 1 into row
 // t - 1 while it computes frame t: for a resumed segment's first frame that is the checkpoint's place) and one behind it (the
-// forward pass runs one frame past the segment where the song goes on, for the frame maximum of its last row).  Family 2 may
+// forward pass runs one frame past the segment where the song goes on, for the frame maximum of its last row).  kFamGroup may
 // back-trace with the lane form: its chunk flags and kLaneMaxChunks entries per song.
 CkLayout ck_layout(const vit_plan* p, int family, int64_t B, int64_t T, int64_t K) {
     CkLayout c;
     K = K > T ? T : K;                                                           // (a segment longer than the songs: one segment of T frames)
-    const size_t sd = (size_t)(family == 3 ? vit::wave_hist_stride(p->bp.wave_npl) : hist_stride(p->S)) * sizeof(float);
+    const size_t sd = (size_t)hist_layout(p, family).SD * sizeof(float);
     c.nseg = (T + K - 1) / K;
-    c.seg_rows = family == 3 ? K + 1 : K + 2;
+    c.seg_rows = family == kFamWave ? K + 1 : K + 2;
     c.off_ckpt = 0;                                                              // [B][nseg] rows: nseg - 1 checkpoints + the scratch row
     c.off_seg = align256((size_t)B * (size_t)c.nseg * sd);                       // [B][seg_rows] rows of the segment being walked
     c.off_cnt = c.off_seg + align256((size_t)B * (size_t)c.seg_rows * sd);
     c.off_mask = c.off_cnt + align256((size_t)B * 64 * sizeof(float));           // (counters; timing builds: the forward kernels' scratch)
-    c.off_last = c.off_mask + (family == 2 ? align256((size_t)B * vit::kLaneMaskWords * sizeof(uint32_t)) : 0);
+    c.off_last = c.off_mask + (family == kFamGroup ? align256((size_t)B * vit::kLaneMaskWords * sizeof(uint32_t)) : 0);
     c.off_entry = c.off_last + align256((size_t)B * sizeof(int32_t));
-    c.off_slen = c.off_entry + align256((size_t)B * (family == 2 ? vit::kLaneMaxChunks : vit::kBtMaxChunks) * sizeof(int32_t));
+    c.off_slen = c.off_entry + align256((size_t)B * (family == kFamGroup ? vit::kLaneMaxChunks : vit::kBtMaxChunks) * sizeof(int32_t));
     c.off_slast = c.off_slen + align256((size_t)B * sizeof(int64_t));
     c.bytes = c.off_slast + align256((size_t)B * sizeof(int32_t));
     return c;
+}
+
+// The back-trace of one segment of a checkpointed decode -- b.B sub-problems of b.T frames: the songs of vit_decode_checkpointed, the
+// units of one launch of the packed budgeted decode.  Step plans: the lazy kernel, one wave per (sub-problem, chunk); banded plans:
+// the sparse kernel, or the lane form where the caller found that the sparse one does not serve the rows (lane_bt; b.mask set).
+hipError_t segment_backtrace(const vit_plan* plan, int family, bool lane_bt, vit::BtArgs& b, hipStream_t st) {
+    const int bt_warm = plan->tune.bt_warm;
+    if (family == kFamStep) {
+        b.chunks = vit::backtrace_chunks(b.B, b.T);
+        b.warm = bt_warm >= 0 ? bt_warm : vit::kBtWarm;
+        return vit::launch_backtrace_rows_segment(b, st);
+    }
+    if (lane_bt) {
+        b.warm = bt_warm >= 0 ? bt_warm : vit::kBtWarmSparse;
+        b.chunks = vit::lane_backtrace_chunks(b.B, b.T, plan->n_cus, b.warm);
+        if (b.chunks > 1) {         // the chunk flags of this segment
+            const hipError_t e = hipMemsetAsync(b.mask, 0, (size_t)b.B * vit::kLaneMaskWords * sizeof(uint32_t), st);
+            if (e != hipSuccess) return e;
+        }
+        return vit::launch_backtrace_lane(b, st);
+    }
+    b.chunks = vit::sparse_backtrace_chunks(b.B, b.T, plan->n_cus);
+    // KNOWN ASYMMETRY, kept: the wave family always warms up kBtWarmSparse frames and does NOT consult bt_warm; kFamGroup does
+    b.warm = family == kFamWave || bt_warm < 0 ? vit::kBtWarmSparse : bt_warm;
+    return vit::launch_backtrace_sparse(b, st);
 }
 
 }  // namespace
@@ -670,7 +718,7 @@ CkLayout ck_layout(const vit_plan* p, int family, int64_t B, int64_t T, int64_t 
 size_t vit_workspace_bytes_checkpointed(const vit_plan* plan, int64_t B, int64_t T, int64_t segment_frames) {
     if (!plan || B < 0 || T < 1 || !ck_segment_ok(segment_frames)) return 0;
     const int family = ck_family(plan);
-    if (family == 0) return 0;
+    if (family == kFamNone) return 0;
     return ck_layout(plan, family, B, T, segment_frames).bytes;
 }
 
@@ -683,7 +731,7 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
     if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
     if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
     const int family = ck_family(plan);             // (everything that can refuse the plan is asked here, before anything is enqueued)
-    if (family == 0) return VIT_EUNSUPPORTED;
+    if (family == kFamNone) return VIT_EUNSUPPORTED;
     const int64_t K = segment_frames > T ? T : segment_frames;
     const CkLayout c = ck_layout(plan, family, B, T, K);
     if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
@@ -692,20 +740,15 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
     const bool f16 = emis_dtype == VIT_F16;
-    const Tuning& tn = plan->tune;
-    const int SDH = family == 3 ? vit::wave_hist_stride(plan->bp.wave_npl) : hist_stride(plan->S);    // row stride of the family's history layout
-    const bool lane_bt = family == 2 && !ck_sparse_applies(plan, 2);
+    const HistLayout lay = hist_layout(plan, family);
+    const bool lane_bt = family == kFamGroup && !ck_sparse_applies(plan, kFamGroup);
     auto forward = [&](const vit::FwdArgs& f) {
-        return family == 3 ? vit::launch_wave(f, f16, st) : (family == 2 ? vit::launch_banded_ckpt(f, f16, st) : vit::launch_step_ckpt(f, f16, st));
+        return family == kFamWave ? vit::launch_wave(f, f16, st) : (family == kFamGroup ? vit::launch_banded_ckpt(f, f16, st) : vit::launch_step_ckpt(f, f16, st));
     };
-    hipError_t e;
-    if (lengths) {     // frames past a song's end: -1 (segments a song does not reach are skipped, not written)
-        e = hipMemsetAsync(states, 0xff, (size_t)B * (size_t)T * sizeof(int32_t), st);
-        if (e != hipSuccess) return hip_fail(e);
-    }
+    if (lengths)       // frames past a song's end: -1 (segments a song does not reach are skipped, not written)
+        VIT_TRY(hipMemsetAsync(states, 0xff, (size_t)B * (size_t)T * sizeof(int32_t), st));
     int32_t* counters = reinterpret_cast<int32_t*>(ws + c.off_cnt);
-    e = hipMemsetAsync(counters, 0, (size_t)B * vit::kBtCounters * sizeof(int32_t), st);
-    if (e != hipSuccess) return hip_fail(e);
+    VIT_TRY(hipMemsetAsync(counters, 0, (size_t)B * vit::kBtCounters * sizeof(int32_t), st));
 
     // ---- pass 1: checkpoint rows + terminal state
     vit::FwdArgs a{};
@@ -722,26 +765,15 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
     a.ckpt_every = (int)K;
     a.t_begin = 0;
     a.t_end = (int)T;
-    e = forward(a);
-    if (e != hipSuccess) return hip_fail(e);
+    VIT_TRY(forward(a));
 
     // ---- pass 2: segments, last to first
     vit::BtArgs b{};
     bt_args_from_plan(plan, b);
-    b.SD = SDH;
-    if (family == 3) {
-        b.col0 = SDH - plan->S;
-        b.mcol = 0;
-        b.xcol0 = 1;
-    } else {                // the workgroup kernels' rows: state i in column i, the frame maximum (banded) in pad column S
-        b.col0 = 0;
-        b.mcol = plan->S;
-        b.xcol0 = -1;
-    }
+    hist_layout_apply(lay, b);
     b.aux_frames = 1;       // (a segment's sub-problem ends one frame behind the rows it decides from: every frame's scalars from its own row)
-    b.have_fmax = family == 1 ? 0 : 1;
-    // families 1, 2: the segment's row 0 is the buffer's second row (ck_layout)
-    float* seg = reinterpret_cast<float*>(ws + c.off_seg) + (family == 3 ? 0 : SDH);
+    // workgroup families: the segment's row 0 is the buffer's second row (ck_layout)
+    float* seg = reinterpret_cast<float*>(ws + c.off_seg) + (family == kFamWave ? 0 : lay.SD);
     b.hist = seg;
     b.hist_rows = c.seg_rows;
     b.last_state = reinterpret_cast<const int32_t*>(ws + c.off_slast);
@@ -751,8 +783,8 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
     b.states_stride = T;
     b.skip_nonpositive = 1;
     b.counters = counters;
-    b.mask = family == 2 ? reinterpret_cast<uint32_t*>(ws + c.off_mask) : nullptr;
-    b.bt_form = family == 1 ? 1 : (lane_bt ? 4 : 0);
+    b.mask = family == kFamGroup ? reinterpret_cast<uint32_t*>(ws + c.off_mask) : nullptr;
+    b.bt_form = family == kFamStep ? 1 : (lane_bt ? 4 : 0);
     if (lane_bt && !vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;      // (cannot happen: ck_family asked the same predicates)
     for (int64_t sgm = c.nseg - 1; sgm >= 0; --sgm) {
         const int64_t s0 = sgm * K, e0 = s0 + K < T ? s0 + K : T;
@@ -763,33 +795,14 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
         f.loglik = nullptr;
         f.t_begin = (int)s0;
         f.t_end = (int)e0;
-        f.init_rows = sgm > 0 ? reinterpret_cast<const float*>(ws + c.off_ckpt) + (size_t)(sgm - 1) * SDH : nullptr;
-        f.init_stride = (int64_t)c.nseg * SDH;
-        e = forward(f);
-        if (e != hipSuccess) return hip_fail(e);
-        e = vit::launch_segment_prep(lengths, B, (int)T, (int)s0, (int)e0, states, reinterpret_cast<const int32_t*>(ws + c.off_last),
-                                     reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast), st);
-        if (e != hipSuccess) return hip_fail(e);
+        f.init_rows = sgm > 0 ? reinterpret_cast<const float*>(ws + c.off_ckpt) + (size_t)(sgm - 1) * lay.SD : nullptr;
+        f.init_stride = (int64_t)c.nseg * lay.SD;
+        VIT_TRY(forward(f));
+        VIT_TRY(vit::launch_segment_prep(lengths, B, (int)T, (int)s0, (int)e0, states, reinterpret_cast<const int32_t*>(ws + c.off_last),
+                                         reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast), st));
         b.T = (int)(e0 < T ? e0 - s0 + 1 : e0 - s0);      // the frame behind the segment is the sub-problem's terminal frame
         b.states = states + s0;
-        if (family == 1) {              // step plans: the lazy kernel, one wave per (song, chunk)
-            b.chunks = vit::backtrace_chunks(B, b.T);
-            b.warm = tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarm;
-            e = vit::launch_backtrace_rows_segment(b, st);
-        } else if (lane_bt) {
-            b.warm = tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarmSparse;
-            b.chunks = vit::lane_backtrace_chunks(B, b.T, plan->n_cus, b.warm);
-            if (b.chunks > 1) {         // the chunk flags of this segment
-                e = hipMemsetAsync(ws + c.off_mask, 0, (size_t)B * vit::kLaneMaskWords * sizeof(uint32_t), st);
-                if (e != hipSuccess) return hip_fail(e);
-            }
-            e = vit::launch_backtrace_lane(b, st);
-        } else {
-            b.chunks = vit::sparse_backtrace_chunks(B, b.T, plan->n_cus);
-            b.warm = family == 3 || tn.bt_warm < 0 ? vit::kBtWarmSparse : tn.bt_warm;
-            e = vit::launch_backtrace_sparse(b, st);
-        }
-        if (e != hipSuccess) return hip_fail(e);
+        VIT_TRY(segment_backtrace(plan, family, lane_bt, b, st));
     }
     return VIT_OK;
 }
@@ -809,17 +822,35 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
 // step4s_forward_kernel<.., PK> and the lazy back-trace over per-song chunk lists.  Slots: as many workgroups as are resident at once.
 namespace {
 
-// The forward family a packed decode of this plan runs (FwdStamp::family numbering), 0 = none: the ONE predicate behind
+// The forward family a packed decode of this plan runs, kFamNone = none: the ONE predicate behind
 // vit_workspace_bytes_packed and vit_decode_packed, so that a size > 0 implies a decode that launches.
 int pk_family(const vit_plan* p) {
-    if (p->bp.ok && p->bp.wave_ok) return 3;
+    if (p->bp.ok && p->bp.wave_ok) return kFamWave;
     if (p->bp.ok)      // banded, no wave form: the floor form and the lane back-trace (lane_backtrace_applies: width instantiated, W <= S)
-        return vit::floor_packed_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && p->bp.W <= p->S ? 2 : 0;
-    if (p->bp.step_ok && vit::step_kernel_instantiated(p->S, p->bp.step_bw, p->bp.step_kb)) return 1;
-    return 0;
+        return vit::floor_packed_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && p->bp.W <= p->S ? kFamGroup : kFamNone;
+    return step_applies(p) ? kFamStep : kFamNone;
 }
-// history row stride of that family
-int pk_hist_stride(const vit_plan* p, int family) { return family == 3 ? vit::wave_hist_stride(p->bp.wave_npl) : hist_stride(p->S); }
+
+// The argument checks every packed decode starts with, in this order.
+int check_packed(const vit_plan* plan, int64_t B, const int64_t* offsets, const void* workspace, int emis_dtype) {
+    if (!plan || !workspace || !offsets) return VIT_EINVAL;
+    if (B < 0 || B > (int64_t)1 << 30) return VIT_EINVAL;
+    if (!plan->dev_image) return VIT_ENOTUPLOADED;
+    if (((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
+    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
+    return VIT_OK;
+}
+// B + 1 frame offsets from 0, every song with 1 .. 2^30 frames; *tmax: the longest song (1 for an empty batch)
+bool offsets_ok(const int64_t* offsets, int64_t B, int64_t* tmax) {
+    if (!offsets || offsets[0] != 0) return false;
+    *tmax = 1;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t tb = offsets[b + 1] - offsets[b];
+        if (tb < 1 || tb > (int64_t)1 << 30) return false;
+        *tmax = std::max(*tmax, tb);
+    }
+    return true;
+}
 
 struct PkLayout {
     int64_t n_slots, max_waves;
@@ -828,11 +859,10 @@ struct PkLayout {
 };
 inline int64_t pk_slots(const vit_plan* p, int64_t B) { const int64_t cap = 8 * (int64_t)p->n_cus; return B < cap ? B : cap; }
 inline int64_t pk_max_waves(const vit_plan* p, int64_t B) { return B + 16 * 64 * (int64_t)p->n_cus; }     // (song, chunk) streams of the back-trace: one per lane
-// sd_floats: the history row stride of the form that runs.  n_slots is an upper bound here (it sizes slot_begin): the decode
-// lowers it to the workgroups resident at once (workgroup forms: a device query) and to total frames / longest song.
-PkLayout pk_layout(const vit_plan* p, int sd_floats, int64_t B, int64_t N) {
+// n_slots is an upper bound here (it sizes slot_begin): the decode lowers it (pk_lower_slots)
+PkLayout pk_layout(const vit_plan* p, int family, int64_t B, int64_t N) {
     PkLayout k;
-    const size_t sd = (size_t)sd_floats * sizeof(float);
+    const size_t sd = (size_t)hist_layout(p, family).SD * sizeof(float);
     k.n_slots = pk_slots(p, B);
     k.max_waves = pk_max_waves(p, B);
     k.off_hist = 0;
@@ -850,21 +880,58 @@ PkLayout pk_layout(const vit_plan* p, int sd_floats, int64_t B, int64_t N) {
     return k;
 }
 
+// Workgroups one CU holds of the packed workgroup-form kernel (variant 0) or of its packed-checkpoint variant (1) -- the occupancy
+// of that instantiation, asked of the device once per emission type and remembered in the plan.
+int resident_per_cu(const vit_plan* plan, int family, int variant, const vit::FwdArgs& a, bool f16, int* per_cu) {
+    int& cached = plan->resident[variant][f16 ? 1 : 0];
+    {
+        std::lock_guard<std::mutex> g(plan->mu);
+        *per_cu = cached;
+    }
+    if (*per_cu >= 1) return VIT_OK;
+    const hipError_t eq = variant == 0 ? (family == kFamGroup ? vit::banded_packed_resident(a, f16, per_cu) : vit::step_packed_resident(a, f16, per_cu))
+                                       : (family == kFamGroup ? vit::banded_pckpt_resident(a, f16, per_cu) : vit::step_pckpt_resident(a, f16, per_cu));
+    if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: the *_family predicates asked the same)
+    VIT_TRY(eq);
+    if (*per_cu < 1) return VIT_EUNSUPPORTED;
+    std::lock_guard<std::mutex> g(plan->mu);
+    cached = *per_cu;
+    return VIT_OK;
+}
+// The forward slots of a packed batch of N frames whose longest song has tmax: at most `bound`; workgroup forms (variant as in
+// resident_per_cu): one per workgroup that is resident at once; and no more than N / tmax -- a slot's load should not fall below the
+// longest song, which bounds the launch anyway (1623 songs of 7500..30000 frames: 1024 slots of ~30000 frames, one wave per SIMD,
+// instead of 1623 waves of which the longest share their SIMDs to the end).
+int pk_lower_slots(const vit_plan* plan, int family, int variant, const vit::FwdArgs& a, bool f16, int64_t N, int64_t tmax, int64_t* n_slots) {
+    if (family != kFamWave) {   // the wave family takes min(pk_slots, max(1, N / tmax)) with no occupancy query
+        int per_cu;
+        const int rc = resident_per_cu(plan, family, variant, a, f16, &per_cu);
+        if (rc != VIT_OK) return rc;
+        *n_slots = std::min<int64_t>(*n_slots, (int64_t)per_cu * plan->n_cus);
+    }
+    *n_slots = std::min<int64_t>(*n_slots, std::max<int64_t>(1, N / tmax));
+    return VIT_OK;
+}
 
-// The plan's pinned staging buffer with room for `bytes` of host tables (vit_decode_packed, vit_decode_packed_checkpointed): waits for the
-// upload of the call before, which read it; pk_stage_sent() records the next one.
+// The plan's pinned staging buffer with room for `bytes` of host tables, zeroed (the packed decodes): waits for the upload of the call
+// before, which read it; pk_upload() sends it and records the next wait.
 int pk_stage(const vit_plan* plan, size_t bytes) {
     std::lock_guard<std::mutex> g(plan->mu);
-    if (plan->pk_event) { hipError_t ew = hipEventSynchronize(plan->pk_event); if (ew != hipSuccess) return hip_fail(ew); }
-    else { hipError_t ec = hipEventCreateWithFlags(&plan->pk_event, hipEventDisableTiming); if (ec != hipSuccess) return hip_fail(ec); }
+    if (plan->pk_event) VIT_TRY(hipEventSynchronize(plan->pk_event));
+    else VIT_TRY(hipEventCreateWithFlags(&plan->pk_event, hipEventDisableTiming));
     if (plan->pk_host_bytes < bytes) {
         if (plan->pk_host) (void)hipHostFree(plan->pk_host);
         plan->pk_host = nullptr;
         plan->pk_host_bytes = 0;
-        hipError_t ea = hipHostMalloc(&plan->pk_host, bytes, hipHostMallocDefault);
-        if (ea != hipSuccess) return hip_fail(ea);
+        VIT_TRY(hipHostMalloc(&plan->pk_host, bytes, hipHostMallocDefault));
         plan->pk_host_bytes = bytes;
     }
+    std::memset(plan->pk_host, 0, bytes);
+    return VIT_OK;
+}
+int pk_upload(const vit_plan* plan, void* dst, size_t bytes, hipStream_t st) {
+    VIT_TRY(hipMemcpyAsync(dst, plan->pk_host, bytes, hipMemcpyHostToDevice, st));
+    VIT_TRY(hipEventRecord(plan->pk_event, st));
     return VIT_OK;
 }
 
@@ -894,90 +961,72 @@ void pk_fill_slots(const int64_t* offsets, int64_t B, int64_t n_slots, int32_t* 
     for (int32_t sng : order) h_slot_songs[fill[(size_t)slot_of[(size_t)sng]]++] = sng;     // a slot walks its songs longest first
 }
 
+// the fields of a packed forward pass that do not depend on which packed decode runs it
+void fwd_args_packed(vit::FwdArgs& a, const void* logE, int64_t B, float* loglik) {
+    a.logE = logE;
+    a.lengths = nullptr;
+    a.fmax = nullptr;
+    a.loglik = loglik;
+    a.B = B;
+    a.T = 1;                      // (unused by the packed kernels: a song's rows come from the offsets)
+    a.t_begin = 0;
+    a.t_end = 1;
+}
+
 }  // namespace
 
 size_t vit_workspace_bytes_packed(const vit_plan* plan, int64_t B, int64_t total_frames) {
     if (!plan || B < 0 || total_frames < 0) return 0;
     const int family = pk_family(plan);
-    if (family == 0) return 0;
-    return pk_layout(plan, pk_hist_stride(plan, family), B, total_frames).bytes;
+    if (family == kFamNone) return 0;
+    return pk_layout(plan, family, B, total_frames).bytes;
 }
 
 int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
                       size_t workspace_bytes, int32_t* states, float* loglik, vit_stream stream) {
-    if (!plan || !workspace || !offsets) return VIT_EINVAL;
-    if (B < 0 || B > (int64_t)1 << 30) return VIT_EINVAL;
-    if (!plan->dev_image) return VIT_ENOTUPLOADED;
-    if (((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
-    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
+    int rc = check_packed(plan, B, offsets, workspace, emis_dtype);
+    if (rc != VIT_OK) return rc;
     const int family = pk_family(plan);
-    if (family == 0) return VIT_EUNSUPPORTED;
-    if (offsets[0] != 0) return VIT_EINVAL;
-    for (int64_t b = 0; b < B; ++b) {
-        const int64_t tb = offsets[b + 1] - offsets[b];
-        if (tb < 1 || tb > (int64_t)1 << 30) return VIT_EINVAL;      // every song holds at least one frame
-    }
+    if (family == kFamNone) return VIT_EUNSUPPORTED;
+    int64_t tmax;
+    if (!offsets_ok(offsets, B, &tmax)) return VIT_EINVAL;
     const int64_t N = offsets[B];
     if (B == 0) return VIT_OK;
     if (!logE || !states) return VIT_EINVAL;
-    PkLayout k = pk_layout(plan, pk_hist_stride(plan, family), B, N);
+    PkLayout k = pk_layout(plan, family, B, N);
     if (workspace_bytes < k.bytes) return VIT_EWORKSPACE;
     const bool f16 = emis_dtype == VIT_F16;
     vit::FwdArgs a{};
     fwd_args_from_plan(plan, a);
-    if (family != 3) {   // workgroup forms: one slot per workgroup that is resident at once (the occupancy of that instantiation x CUs)
-        int per_cu;
-        {
-            std::lock_guard<std::mutex> g(plan->mu);
-            per_cu = plan->pk_resident[f16 ? 1 : 0];
-        }
-        if (per_cu < 1) {
-            hipError_t eq = family == 2 ? vit::banded_packed_resident(a, f16, &per_cu) : vit::step_packed_resident(a, f16, &per_cu);
-            if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: pk_family asked the same predicates)
-            if (eq != hipSuccess) return hip_fail(eq);
-            if (per_cu < 1) return VIT_EUNSUPPORTED;
-            std::lock_guard<std::mutex> g(plan->mu);
-            plan->pk_resident[f16 ? 1 : 0] = per_cu;
-        }
-        k.n_slots = std::min<int64_t>(k.n_slots, (int64_t)per_cu * plan->n_cus);
-    }
-    {   // fewer slots than songs when the batch is short of frames: a slot's load should not fall below the longest song, which bounds
-        // the launch anyway (1623 songs of 7500..30000 frames: 1024 slots of ~30000 frames, one wave per SIMD, instead of 1623 waves
-        // of which the longest share their SIMDs to the end)
-        int64_t tmax = 1;
-        for (int64_t b = 0; b < B; ++b) tmax = std::max<int64_t>(tmax, offsets[b + 1] - offsets[b]);
-        const int64_t by_frames = std::max<int64_t>(1, N / tmax);
-        k.n_slots = std::min<int64_t>(k.n_slots, by_frames);
-    }
+    rc = pk_lower_slots(plan, family, 0, a, f16, N, tmax, &k.n_slots);
+    if (rc != VIT_OK) return rc;
     stamp_erase(plan, workspace);
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
 
     // ---- host tables in the plan's pinned staging buffer (the previous call's upload must have read it)
-    {
-        const int rs = pk_stage(plan, k.tables_bytes);
-        if (rs != VIT_OK) return rs;
-    }
+    rc = pk_stage(plan, k.tables_bytes);
+    if (rc != VIT_OK) return rc;
     uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
-    std::memset(hb, 0, k.tables_bytes);
-    int64_t* h_off = reinterpret_cast<int64_t*>(hb + (k.off_offsets - k.off_offsets));
-    int32_t* h_slot_begin = reinterpret_cast<int32_t*>(hb + (k.off_slot_begin - k.off_offsets));
-    int32_t* h_slot_songs = reinterpret_cast<int32_t*>(hb + (k.off_slot_songs - k.off_offsets));
     int32_t* h_wave_song = reinterpret_cast<int32_t*>(hb + (k.off_wave_song - k.off_offsets));
     int32_t* h_chunk_base = reinterpret_cast<int32_t*>(hb + (k.off_chunk_base - k.off_offsets));
-    std::memcpy(h_off, offsets, (size_t)(B + 1) * sizeof(int64_t));
+    std::memcpy(hb, offsets, (size_t)(B + 1) * sizeof(int64_t));
     int64_t max_chunks = 1;
     try {
-        pk_fill_slots(offsets, B, k.n_slots, h_slot_begin, h_slot_songs);      // forward slots: greedy bins by frames, longest song first
+        pk_fill_slots(offsets, B, k.n_slots, reinterpret_cast<int32_t*>(hb + (k.off_slot_begin - k.off_offsets)),
+                      reinterpret_cast<int32_t*>(hb + (k.off_slot_songs - k.off_offsets)));      // forward slots: greedy bins by frames
+    } catch (const std::bad_alloc&) {
+        return VIT_ENOMEM;
+    }
+    {
         // back-trace streams (one per lane: backtrace_lane.hip): chunks of about (total frames / resident lanes) frames, never shorter
         // than four warm-ups, at most kLaneMaxChunks per song
         // (step plans, lazy back-trace: one WAVE per chunk -- about eight waves per CU, chunks no shorter than the 8 * kBtWarm frames
         // of backtrace_chunks, at most kBtMaxChunks per song)
-        const bool lazy = family == 1;
+        const bool lazy = family == kFamStep;
         const int64_t resident = lazy ? 8 * (int64_t)plan->n_cus : 16 * 64 * (int64_t)plan->n_cus;
         const int64_t cmax = lazy ? vit::kBtMaxChunks : vit::kLaneMaxChunks;
-        int64_t cf = (N + resident - 1) / resident, tmax = 0;
-        for (int64_t b = 0; b < B; ++b) tmax = std::max<int64_t>(tmax, offsets[b + 1] - offsets[b]);
+        int64_t cf = (N + resident - 1) / resident;
         cf = std::max<int64_t>(cf, lazy ? 8 * vit::kBtWarm : 4 * vit::kBtWarmSparse);
         cf = std::max<int64_t>(cf, (tmax + cmax - 1) / cmax);
         int64_t w = 0;
@@ -992,54 +1041,28 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
         }
         h_chunk_base[B] = (int32_t)w;
         if (w > k.max_waves) return VIT_EINVAL;      // (cannot happen: sum of round(T_b / cf) <= B + N / cf <= B + 16 n_cus)
-    } catch (const std::bad_alloc&) {
-        return VIT_ENOMEM;
     }
     const int n_waves = h_chunk_base[B];
-    hipError_t e = hipMemcpyAsync(ws + k.off_offsets, hb, k.tables_bytes, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return hip_fail(e);
-    e = hipEventRecord(plan->pk_event, st);
-    if (e != hipSuccess) return hip_fail(e);
-    e = hipMemsetAsync(ws + k.off_cnt, 0, k.off_last - k.off_cnt, st);
-    if (e != hipSuccess) return hip_fail(e);
+    rc = pk_upload(plan, ws + k.off_offsets, k.tables_bytes, st);
+    if (rc != VIT_OK) return rc;
+    VIT_TRY(hipMemsetAsync(ws + k.off_cnt, 0, k.off_last - k.off_cnt, st));
 
     // ---- forward: one wave (wave form) or one workgroup per slot
-    a.logE = logE;
-    a.lengths = nullptr;
+    fwd_args_packed(a, logE, B, loglik);
     a.hist = reinterpret_cast<float*>(ws + k.off_hist);
-    a.fmax = nullptr;
     a.last_state = reinterpret_cast<int32_t*>(ws + k.off_last);
-    a.loglik = loglik;
-    a.B = B;
-    a.T = 1;                      // (unused by the packed kernel: a song's rows come from the offsets)
     a.hist_rows = 0;
-    a.t_begin = 0;
-    a.t_end = 1;
     a.offsets = reinterpret_cast<const int64_t*>(ws + k.off_offsets);
     a.n_slots = (int)k.n_slots;
     a.slot_begin = reinterpret_cast<const int32_t*>(ws + k.off_slot_begin);
     a.slot_songs = reinterpret_cast<const int32_t*>(ws + k.off_slot_songs);
-    e = family == 3 ? vit::launch_wave(a, f16, st) : (family == 2 ? vit::launch_banded_packed(a, f16, st) : vit::launch_step_packed(a, f16, st));
-    if (e != hipSuccess) return hip_fail(e);
+    VIT_TRY(family == kFamWave ? vit::launch_wave(a, f16, st) : (family == kFamGroup ? vit::launch_banded_packed(a, f16, st) : vit::launch_step_packed(a, f16, st)));
 
     // ---- back-trace: one lane (banded plans) or one wave (step plans) per (song, chunk)
     vit::BtArgs b{};
     bt_args_from_plan(plan, b);
-    if (family == 3) {
-        b.SD = vit::wave_hist_stride(plan->bp.wave_npl);
-        b.col0 = b.SD - plan->S;
-        b.mcol = 0;
-        b.xcol0 = 1;
-        b.aux_frames = (a.wave_flags & 4) ? 1 : vit::wave_aux_frames(plan->bp.wave_npl, plan->S, b.n_extras);
-        b.have_fmax = 1;
-    } else {             // the workgroup kernels' rows: state i in column i, the frame maximum (banded) in pad column S
-        b.SD = a.SD;
-        b.col0 = 0;
-        b.mcol = plan->S;
-        b.xcol0 = -1;
-        b.aux_frames = 1;
-        b.have_fmax = family == 2 ? 1 : 0;
-    }
+    hist_layout_apply(hist_layout(plan, family), b);
+    b.aux_frames = family != kFamWave || (a.wave_flags & 4) ? 1 : vit::wave_aux_frames(plan->bp.wave_npl, plan->S, b.n_extras);    // (a full wave history)
     b.hist = reinterpret_cast<const float*>(ws + k.off_hist);
     b.hist_rows = 0;
     b.last_state = reinterpret_cast<const int32_t*>(ws + k.off_last);
@@ -1056,33 +1079,65 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     b.chunk_base = reinterpret_cast<const int32_t*>(ws + k.off_chunk_base);
     b.n_waves = n_waves;
     b.chunks = (int)max_chunks;
-    if (family == 1) {
+    if (family == kFamStep) {
         b.warm = plan->tune.bt_warm >= 0 ? plan->tune.bt_warm : vit::kBtWarm;
         b.bt_form = 1;
-        e = vit::launch_backtrace_rows_packed(b, st);
-        return e == hipSuccess ? VIT_OK : hip_fail(e);
+        return hip_status(vit::launch_backtrace_rows_packed(b, st));
     }
     b.warm = plan->tune.bt_warm >= 0 ? plan->tune.bt_warm : vit::kBtWarmSparse;
     b.bt_form = 4;
     if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
-    e = vit::launch_backtrace_lane(b, st);
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(vit::launch_backtrace_lane(b, st));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Packed checkpointed decode (wave-form plans): the packed decode above under a workspace budget.  Segments are per song: song b
-// has n_b = ceil(T_b / K) of them.  Pass 1 is the packed forward pass (slots walking their song lists; wave.hip HM 9) that keeps
-// only the row in front of each segment 1 .. n_b - 1, packed into sum (n_b - 1) <= N / K checkpoint rows, and the terminal state
-// and log-likelihood per song.  Pass 2 works on (song, segment) UNITS, one wavefront each: the units of a song run from its last
-// segment to its first, units of different songs are independent, and the host lists the launches up front
-// (vit::packed_ckpt_schedule: up to n_units = min(8 x CUs, B) ready units per launch, at most one per song, most segments left
-// first).  A launch resumes the wave kernel from every unit's checkpoint row into that unit's K + 1 rows (HM 8), sets every unit's
-// length and start state (packed_segment_prep_kernel) and runs the sparse back-trace over the units, which writes the states at
-// offsets[b] + segment * K.  Exact by construction: the kernels and sums of vit_decode_packed's forward pass.
+// Packed decode under a workspace budget: vit_decode_packed_checkpointed (wave-form plans) and vit_decode_packed_bounded (every plan
+// with a packed decode; wave-form plans run the same code and get the same size) share ONE driver, decode_packed_budgeted.
+// Segments are per song: song b has n_b = ceil(T_b / K) of them.  Pass 1 is the packed forward pass (slots walking their song lists)
+// that keeps only the row in front of each segment 1 .. n_b - 1, packed into sum (n_b - 1) <= N / K checkpoint rows, and the terminal
+// state and log-likelihood per song.  Pass 2 works on (song, segment) UNITS: the units of a song run from its last segment to its
+// first, units of different songs are independent, and the host lists the launches up front (vit::packed_ckpt_schedule: up to n_units
+// ready units per launch, at most one per song, most segments left first).  A launch resumes the forward kernel from every unit's
+// checkpoint row into that unit's rows, sets every unit's length and start state (packed_segment_prep_kernel) and back-traces the
+// units, which writes the states at offsets[b] + segment * K.  Exact by construction: the kernels and sums of vit_decode_packed.
+// What differs by family (BudgetForm): the wave form runs a WAVEFRONT per slot and per unit (wave.hip HM 9 / HM 8, K + 1 rows per
+// unit, up to 8 units per CU and launch, the sparse back-trace); plans without it a WORKGROUP
+// (banded_floor_forward_kernel / step4s_forward_kernel <.., PC>; a.unit_song null = pass 1, set = pass 2).  The floor kernel's unit
+// holds K + 2 rows (one in front for the first frame's frame-maximum store, one behind for the frame past the segment), 1 unit per CU
+// (W = 128 on twelve waves takes 148 KB of LDS and 3 x 168 registers per SIMD), the sparse back-trace over the workgroup rows; the
+// step kernel's K + 1 rows, 2 per CU (62 KB of LDS, seven waves of 128 registers), the lazy kernel's segment form.  Every unit owns
+// its rows, so correctness does not depend on how many workgroups are resident; the units per launch are tuning.
 namespace {
 
 // the ONE predicate behind vit_workspace_bytes_packed_checkpointed and vit_decode_packed_checkpointed (a size > 0 implies a decode that launches)
-bool pc_applies(const vit_plan* p) { return p->bp.ok && p->bp.wave_ok && ck_sparse_applies(p, 3); }
+bool pc_applies(const vit_plan* p) { return p->bp.ok && p->bp.wave_ok && ck_sparse_applies(p, kFamWave); }
+int pc_family(const vit_plan* p) { return pc_applies(p) ? kFamWave : kFamNone; }
+// The same behind vit_workspace_bytes_packed_bounded, vit_packed_bounded_units and vit_decode_packed_bounded.  kFamGroup back-traces
+// its units with the sparse kernel only: a plan that the lane form alone could back-trace gets kFamNone.
+int pb_family(const vit_plan* p) {
+    if (p->bp.ok && p->bp.wave_ok) return pc_family(p);
+    if (p->bp.ok)
+        return vit::floor_pckpt_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && p->bp.W <= p->S && ck_sparse_applies(p, kFamGroup) ? kFamGroup : kFamNone;
+    return step_applies(p) ? kFamStep : kFamNone;
+}
+
+// the choices of the budgeted packed decode that depend on the family: data, read at the top of the driver
+struct BudgetForm {
+    hipError_t (*forward)(const vit::FwdArgs&, bool, hipStream_t);
+    int units_per_cu;         // units per launch: min(B, units_per_cu x CUs)
+    int extra_rows;           // rows a unit holds besides its K
+    int front_rows;           // of those, in front of the unit's row 0 (BtArgs::hist, FwdArgs::hist point behind them)
+};
+BudgetForm budget_form(int family) {
+    if (family == kFamWave) return {vit::launch_wave, 8, 1, 0};
+    if (family == kFamGroup) return {vit::launch_banded_pckpt, 1, 2, 1};
+    return {vit::launch_step_pckpt, 2, 1, 0};
+}
+int64_t pb_units(const vit_plan* p, int family, int64_t B) {
+    if (family == kFamNone) return 0;
+    const int64_t cap = budget_form(family).units_per_cu * (int64_t)p->n_cus;
+    return B < cap ? B : cap;
+}
 
 struct PcLayout {
     int64_t K, tmax, units, n_ckpt, n_units, n_slots;
@@ -1090,26 +1145,20 @@ struct PcLayout {
     size_t off_offsets, off_ckpt_base, off_slot_begin, off_slot_songs, off_unit_song, off_unit_seg, bytes;
     size_t tables_bytes;      // offsets .. unit_seg: one contiguous upload
 };
-// false: bad offsets (the rule of vit_decode_packed), or more units than an int32 counts.  sd_floats: the history row stride of the
-// form that runs; n_units: units per launch; extra_rows: rows a unit holds besides its K (1 wave form and step kernel, 2 floor kernel)
-bool pc_layout_rows(const vit_plan* p, int64_t B, const int64_t* offsets, int64_t K, int sd_floats, int64_t n_units, int extra_rows, PcLayout& c) {
-    if (!offsets || offsets[0] != 0) return false;
-    c.tmax = 1;
-    for (int64_t b = 0; b < B; ++b) {
-        const int64_t tb = offsets[b + 1] - offsets[b];
-        if (tb < 1 || tb > (int64_t)1 << 30) return false;
-        c.tmax = std::max(c.tmax, tb);
-    }
+// false: bad offsets (offsets_ok), or more units than an int32 counts.  One layout for the three families: for a wave plan
+// vit_workspace_bytes_packed_bounded IS vit_workspace_bytes_packed_checkpointed.
+bool pc_layout(const vit_plan* p, int family, int64_t B, const int64_t* offsets, int64_t K, PcLayout& c) {
+    if (!offsets_ok(offsets, B, &c.tmax)) return false;
     c.K = K > c.tmax ? c.tmax : K;                             // (a segment longer than every song: one segment per song)
     c.units = vit::packed_ckpt_units(offsets, B, c.K);
     if (c.units < 0 || c.units > 0x7fffffff) return false;
     c.n_ckpt = c.units - B;
-    c.n_units = n_units;                                       // units per launch: at most one per song (wave form: at most 8 waves per CU)
+    c.n_units = pb_units(p, family, B);                        // units per launch: at most one per song
     c.n_slots = pk_slots(p, B);                                // pass 1's slots (an upper bound, as in pk_layout): one scratch row each
-    const size_t sd = (size_t)sd_floats * sizeof(float);
+    const size_t sd = (size_t)hist_layout(p, family).SD * sizeof(float);
     c.off_ckpt = 0;                                            // [n_ckpt] checkpoint rows, then [n_slots] scratch rows
     c.off_seg = align256((size_t)(c.n_ckpt + c.n_slots) * sd); // [n_units][K + extra_rows] rows of the segments being walked
-    c.off_last = c.off_seg + align256((size_t)c.n_units * (size_t)(c.K + extra_rows) * sd);
+    c.off_last = c.off_seg + align256((size_t)c.n_units * (size_t)(c.K + budget_form(family).extra_rows) * sd);
     c.off_entry = c.off_last + align256((size_t)B * sizeof(int32_t));
     c.off_slen = c.off_entry + align256((size_t)c.n_units * vit::kBtMaxChunks * sizeof(int32_t));
     c.off_slast = c.off_slen + align256((size_t)c.n_units * sizeof(int64_t));
@@ -1124,54 +1173,24 @@ bool pc_layout_rows(const vit_plan* p, int64_t B, const int64_t* offsets, int64_
     c.tables_bytes = c.bytes - c.off_offsets;
     return true;
 }
-// the wave form's layout: at most 8 waves per CU, K + 1 rows per unit
-bool pc_layout(const vit_plan* p, int64_t B, const int64_t* offsets, int64_t K, PcLayout& c) {
-    return pc_layout_rows(p, B, offsets, K, vit::wave_hist_stride(p->bp.wave_npl), pk_slots(p, B), 1, c);
-}
-
-}  // namespace
-
-size_t vit_workspace_bytes_packed_checkpointed(const vit_plan* plan, int64_t B, const int64_t* offsets, int64_t segment_frames) {
+size_t budgeted_bytes(const vit_plan* plan, int (*family_of)(const vit_plan*), int64_t B, const int64_t* offsets, int64_t segment_frames) {
     if (!plan || !offsets || B < 0 || B > (int64_t)1 << 30 || !ck_segment_ok(segment_frames)) return 0;
-    if (!pc_applies(plan)) return 0;
+    const int family = family_of(plan);
     PcLayout c;
-    return pc_layout(plan, B, offsets, segment_frames, c) ? c.bytes : 0;
+    return family != kFamNone && pc_layout(plan, family, B, offsets, segment_frames, c) ? c.bytes : 0;
 }
 
-int vit_decode_packed_checkpointed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
-                                   size_t workspace_bytes, int32_t* states, float* loglik, int64_t segment_frames, vit_stream stream) {
-    if (!plan || !workspace || !offsets) return VIT_EINVAL;
-    if (B < 0 || B > (int64_t)1 << 30) return VIT_EINVAL;
-    if (!plan->dev_image) return VIT_ENOTUPLOADED;
-    if (((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
-    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
-    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
-    if (!pc_applies(plan)) return VIT_EUNSUPPORTED;       // (everything that can refuse the plan is asked here, before anything is enqueued)
-    PcLayout c;
-    if (!pc_layout(plan, B, offsets, segment_frames, c)) return VIT_EINVAL;
-    if (B == 0) return VIT_OK;
-    if (!logE || !states) return VIT_EINVAL;
-    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
-    const int64_t N = offsets[B], K = c.K;
-    const bool f16 = emis_dtype == VIT_F16;
-    const int64_t n_slots = std::min<int64_t>(c.n_slots, std::max<int64_t>(1, N / c.tmax));     // the rule of vit_decode_packed
-    stamp_erase(plan, workspace);
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-    const int SDW = vit::wave_hist_stride(plan->bp.wave_npl);
-
-    // ---- host tables in the plan's pinned staging buffer, one upload
-    {
-        const int rs = pk_stage(plan, c.tables_bytes);
-        if (rs != VIT_OK) return rs;
-    }
+// The host tables of a budgeted packed decode -- offsets, checkpoint bases, pass 1's slots, pass 2's units in launch order (sc) --
+// staged in the plan's pinned buffer and sent to the workspace in one upload.
+int pc_stage_tables(const vit_plan* plan, const PcLayout& c, const int64_t* offsets, int64_t B, int64_t n_slots, uint8_t* ws, hipStream_t st,
+                    vit::PackedCkptSchedule& sc) {
+    const int rs = pk_stage(plan, c.tables_bytes);
+    if (rs != VIT_OK) return rs;
     uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
-    std::memset(hb, 0, c.tables_bytes);
-    vit::PackedCkptSchedule sc;
     try {
         pk_fill_slots(offsets, B, n_slots, reinterpret_cast<int32_t*>(hb + (c.off_slot_begin - c.off_offsets)),
                       reinterpret_cast<int32_t*>(hb + (c.off_slot_songs - c.off_offsets)));
-        vit::packed_ckpt_schedule(offsets, B, K, c.n_units, sc);
+        vit::packed_ckpt_schedule(offsets, B, c.K, c.n_units, sc);
     } catch (const std::bad_alloc&) {
         return VIT_ENOMEM;
     }
@@ -1180,239 +1199,59 @@ int vit_decode_packed_checkpointed(const vit_plan* plan, const void* logE, int e
     std::memcpy(hb + (c.off_ckpt_base - c.off_offsets), sc.ckpt_base.data(), (size_t)(B + 1) * sizeof(int64_t));
     std::memcpy(hb + (c.off_unit_song - c.off_offsets), sc.unit_song.data(), (size_t)c.units * sizeof(int32_t));
     std::memcpy(hb + (c.off_unit_seg - c.off_offsets), sc.unit_seg.data(), (size_t)c.units * sizeof(int32_t));
-    hipError_t e = hipMemcpyAsync(ws + c.off_offsets, hb, c.tables_bytes, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return hip_fail(e);
-    e = hipEventRecord(plan->pk_event, st);
-    if (e != hipSuccess) return hip_fail(e);
+    return pk_upload(plan, ws + c.off_offsets, c.tables_bytes, st);
+}
 
-    // ---- pass 1: checkpoint rows + terminal state, one wave per slot
+// The driver behind both entry points; family_of is the entry point's predicate (pc_family / pb_family).
+int decode_packed_budgeted(const vit_plan* plan, int (*family_of)(const vit_plan*), const void* logE, int emis_dtype, int64_t B,
+                           const int64_t* offsets, void* workspace, size_t workspace_bytes, int32_t* states, float* loglik,
+                           int64_t segment_frames, vit_stream stream) {
+    int rc = check_packed(plan, B, offsets, workspace, emis_dtype);
+    if (rc != VIT_OK) return rc;
+    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
+    const int family = family_of(plan);                   // (everything that can refuse the plan is asked here, before anything is enqueued)
+    if (family == kFamNone) return VIT_EUNSUPPORTED;
+    PcLayout c;
+    if (!pc_layout(plan, family, B, offsets, segment_frames, c)) return VIT_EINVAL;
+    if (B == 0) return VIT_OK;
+    if (!logE || !states) return VIT_EINVAL;
+    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
+    const BudgetForm form = budget_form(family);
+    const HistLayout lay = hist_layout(plan, family);
+    const int64_t N = offsets[B], K = c.K, seg_rows = K + form.extra_rows;
+    const bool f16 = emis_dtype == VIT_F16;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
     vit::FwdArgs a{};
     fwd_args_from_plan(plan, a);
-    a.logE = logE;
-    a.lengths = nullptr;
+    int64_t n_slots = c.n_slots;                          // pass 1's slots, as vit_decode_packed chooses them (the packed-checkpoint kernels' occupancy)
+    rc = pk_lower_slots(plan, family, 1, a, f16, N, c.tmax, &n_slots);
+    if (rc != VIT_OK) return rc;
+    stamp_erase(plan, workspace);
+    vit::PackedCkptSchedule sc;
+    rc = pc_stage_tables(plan, c, offsets, B, n_slots, ws, st, sc);
+    if (rc != VIT_OK) return rc;
+
+    // ---- pass 1: checkpoint rows + terminal state, one wave / workgroup per slot
+    fwd_args_packed(a, logE, B, loglik);
     a.hist = reinterpret_cast<float*>(ws + c.off_ckpt);
-    a.fmax = nullptr;
     a.last_state = reinterpret_cast<int32_t*>(ws + c.off_last);
-    a.loglik = loglik;
-    a.B = B;
-    a.T = 1;                      // (unused: a song's rows come from the offsets)
     a.hist_rows = c.n_ckpt;       // the scratch row of slot w is row n_ckpt + w
     a.ckpt_every = (int)K;
-    a.t_begin = 0;
-    a.t_end = 1;
     a.offsets = reinterpret_cast<const int64_t*>(ws + c.off_offsets);
     a.n_slots = (int)n_slots;
     a.slot_begin = reinterpret_cast<const int32_t*>(ws + c.off_slot_begin);
     a.slot_songs = reinterpret_cast<const int32_t*>(ws + c.off_slot_songs);
     a.ckpt_base = reinterpret_cast<const int64_t*>(ws + c.off_ckpt_base);
     a.unit_song = nullptr;
-    e = vit::launch_wave(a, f16, st);
-    if (e != hipSuccess) return hip_fail(e);
+    VIT_TRY(form.forward(a, f16, st));
 
     // ---- pass 2: the launches of the schedule; every unit's back-trace starts from what the launch before it wrote
+    float* seg = reinterpret_cast<float*>(ws + c.off_seg) + (size_t)form.front_rows * lay.SD;
     vit::BtArgs b{};
     bt_args_from_plan(plan, b);
-    b.SD = SDW;
-    b.col0 = SDW - plan->S;
-    b.mcol = 0;
-    b.xcol0 = 1;
+    hist_layout_apply(lay, b);
     b.aux_frames = 1;       // (a unit's sub-problem ends one frame behind the rows it decides from: every frame's scalars from its own row)
-    b.have_fmax = 1;
-    b.hist = reinterpret_cast<const float*>(ws + c.off_seg);
-    b.hist_rows = K + 1;
-    b.last_state = reinterpret_cast<const int32_t*>(ws + c.off_slast);
-    b.lengths = reinterpret_cast<const int64_t*>(ws + c.off_slen);
-    b.unit_states = reinterpret_cast<const int64_t*>(ws + c.off_sbase);
-    b.entry = reinterpret_cast<int32_t*>(ws + c.off_entry);
-    b.states = states;
-    b.states_stride = 0;
-    b.T = (int)(K + 1);
-    b.counters = nullptr;
-    b.bt_form = 0;
-    b.warm = vit::kBtWarmSparse;
-    vit::FwdArgs f = a;
-    f.hist = reinterpret_cast<float*>(ws + c.off_seg);
-    f.hist_rows = K + 1;
-    f.loglik = nullptr;
-    f.init_rows = reinterpret_cast<const float*>(ws + c.off_ckpt);
-    const int32_t* d_unit_song = reinterpret_cast<const int32_t*>(ws + c.off_unit_song);
-    const int32_t* d_unit_seg = reinterpret_cast<const int32_t*>(ws + c.off_unit_seg);
-    for (size_t l = 0; l + 1 < sc.launch_begin.size(); ++l) {
-        const int64_t u0 = sc.launch_begin[l], nu = sc.launch_begin[l + 1] - u0;
-        if (nu < 1 || nu > c.n_units) return VIT_EINVAL;                  // (cannot happen: the schedule takes at most n_units per launch)
-        f.B = nu;
-        f.unit_song = d_unit_song + u0;
-        f.unit_seg = d_unit_seg + u0;
-        e = vit::launch_wave(f, f16, st);
-        if (e != hipSuccess) return hip_fail(e);
-        e = vit::launch_packed_segment_prep(a.offsets, f.unit_song, f.unit_seg, (int)nu, (int)K, states, a.last_state,
-                                            reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast),
-                                            reinterpret_cast<int64_t*>(ws + c.off_sbase), st);
-        if (e != hipSuccess) return hip_fail(e);
-        b.B = nu;
-        b.chunks = vit::sparse_backtrace_chunks(nu, b.T, plan->n_cus);
-        e = vit::launch_backtrace_sparse(b, st);
-        if (e != hipSuccess) return hip_fail(e);
-    }
-    return VIT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Packed decode under a workspace budget for every plan with a packed decode (vit_decode_packed_bounded): a superset of the packed
-// checkpointed decode above.  Wave-form plans are forwarded to it.  Plans without the wave form run its scheme with a WORKGROUP where
-// it has a wavefront: pass 1 is the slot walk of vit_decode_packed's workgroup kernels with the stores of their checkpoint / resume
-// variants (banded_floor_forward_kernel / step4s_forward_kernel <.., PC>, a.unit_song null), pass 2 the launches of
-// vit::packed_ckpt_schedule with one workgroup per (song, segment) unit (the same kernels, a.unit_song set), packed_segment_prep_kernel,
-// and the back-trace over the units: the sparse kernel over the workgroup rows for banded plans, the lazy kernel's segment form for
-// step plans.  Every unit owns its rows (K + 2 for the floor kernel: one in front for the first frame's frame-maximum store, one behind
-// for the frame past the segment; K + 1 for the step kernel), so correctness does not depend on how many workgroups are resident; the
-// units per launch, min(B, u x CUs), are tuning: u = 1 for the floor kernel (W = 128 on twelve waves takes 148 KB of LDS and 3 x 168
-// registers per SIMD: one workgroup per CU) and u = 2 for the step kernel (62 KB of LDS, seven waves of 128 registers: two per CU).
-namespace {
-
-constexpr int kPbUnitsPerCuFloor = 1, kPbUnitsPerCuStep = 2;
-
-// The forward family a bounded packed decode of this plan runs (FwdStamp::family numbering), 0 = none: the ONE predicate behind
-// vit_workspace_bytes_packed_bounded, vit_packed_bounded_units and vit_decode_packed_bounded (a size > 0 implies a decode that launches).
-// Family 2 back-traces its units with the sparse kernel only: a plan that the lane form alone could back-trace gets 0.
-int pb_family(const vit_plan* p) {
-    if (p->bp.ok && p->bp.wave_ok) return pc_applies(p) ? 3 : 0;
-    if (p->bp.ok)
-        return vit::floor_pckpt_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && p->bp.W <= p->S && ck_sparse_applies(p, 2) ? 2 : 0;
-    if (p->bp.step_ok && vit::step_kernel_instantiated(p->S, p->bp.step_bw, p->bp.step_kb)) return 1;
-    return 0;
-}
-int64_t pb_units(const vit_plan* p, int family, int64_t B) {
-    if (family == 0) return 0;
-    const int64_t cap = family == 3 ? 8 * (int64_t)p->n_cus : (family == 2 ? kPbUnitsPerCuFloor : kPbUnitsPerCuStep) * (int64_t)p->n_cus;
-    return B < cap ? B : cap;
-}
-// families 1 and 2
-bool pb_layout(const vit_plan* p, int family, int64_t B, const int64_t* offsets, int64_t K, PcLayout& c) {
-    return pc_layout_rows(p, B, offsets, K, hist_stride(p->S), pb_units(p, family, B), family == 2 ? 2 : 1, c);
-}
-
-}  // namespace
-
-int64_t vit_packed_bounded_units(const vit_plan* plan, int64_t B) {
-    if (!plan || B < 0 || B > (int64_t)1 << 30) return 0;
-    return pb_units(plan, pb_family(plan), B);
-}
-
-size_t vit_workspace_bytes_packed_bounded(const vit_plan* plan, int64_t B, const int64_t* offsets, int64_t segment_frames) {
-    if (!plan || !offsets || B < 0 || B > (int64_t)1 << 30 || !ck_segment_ok(segment_frames)) return 0;
-    const int family = pb_family(plan);
-    if (family == 0) return 0;
-    if (family == 3) return vit_workspace_bytes_packed_checkpointed(plan, B, offsets, segment_frames);
-    PcLayout c;
-    return pb_layout(plan, family, B, offsets, segment_frames, c) ? c.bytes : 0;
-}
-
-int vit_decode_packed_bounded(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
-                              size_t workspace_bytes, int32_t* states, float* loglik, int64_t segment_frames, vit_stream stream) {
-    if (!plan || !workspace || !offsets) return VIT_EINVAL;
-    if (B < 0 || B > (int64_t)1 << 30) return VIT_EINVAL;
-    if (!plan->dev_image) return VIT_ENOTUPLOADED;
-    if (((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
-    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
-    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
-    const int family = pb_family(plan);                   // (everything that can refuse the plan is asked here, before anything is enqueued)
-    if (family == 0) return VIT_EUNSUPPORTED;
-    if (family == 3) return vit_decode_packed_checkpointed(plan, logE, emis_dtype, B, offsets, workspace, workspace_bytes, states, loglik, segment_frames, stream);
-    PcLayout c;
-    if (!pb_layout(plan, family, B, offsets, segment_frames, c)) return VIT_EINVAL;
-    if (B == 0) return VIT_OK;
-    if (!logE || !states) return VIT_EINVAL;
-    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
-    const int64_t N = offsets[B], K = c.K;
-    const bool f16 = emis_dtype == VIT_F16;
-    const Tuning& tn = plan->tune;
-    const int SDH = hist_stride(plan->S);
-    const int64_t seg_rows = K + (family == 2 ? 2 : 1);
-    auto forward = [&](const vit::FwdArgs& f) { return family == 2 ? vit::launch_banded_pckpt(f, f16, (hipStream_t)stream) : vit::launch_step_pckpt(f, f16, (hipStream_t)stream); };
-    vit::FwdArgs a{};
-    fwd_args_from_plan(plan, a);
-    // pass 1's slots, as vit_decode_packed chooses them: one per workgroup that is resident at once, no slot lighter than the longest song
-    int64_t n_slots = c.n_slots;
-    {
-        int per_cu;
-        {
-            std::lock_guard<std::mutex> g(plan->mu);
-            per_cu = plan->pb_resident[f16 ? 1 : 0];
-        }
-        if (per_cu < 1) {
-            hipError_t eq = family == 2 ? vit::banded_pckpt_resident(a, f16, &per_cu) : vit::step_pckpt_resident(a, f16, &per_cu);
-            if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: pb_family asked the same predicates)
-            if (eq != hipSuccess) return hip_fail(eq);
-            if (per_cu < 1) return VIT_EUNSUPPORTED;
-            std::lock_guard<std::mutex> g(plan->mu);
-            plan->pb_resident[f16 ? 1 : 0] = per_cu;
-        }
-        n_slots = std::min<int64_t>(n_slots, (int64_t)per_cu * plan->n_cus);
-        n_slots = std::min<int64_t>(n_slots, std::max<int64_t>(1, N / c.tmax));
-    }
-    stamp_erase(plan, workspace);
-    hipStream_t st = (hipStream_t)stream;
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-
-    // ---- host tables in the plan's pinned staging buffer, one upload
-    {
-        const int rs = pk_stage(plan, c.tables_bytes);
-        if (rs != VIT_OK) return rs;
-    }
-    uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
-    std::memset(hb, 0, c.tables_bytes);
-    vit::PackedCkptSchedule sc;
-    try {
-        pk_fill_slots(offsets, B, n_slots, reinterpret_cast<int32_t*>(hb + (c.off_slot_begin - c.off_offsets)),
-                      reinterpret_cast<int32_t*>(hb + (c.off_slot_songs - c.off_offsets)));
-        vit::packed_ckpt_schedule(offsets, B, K, c.n_units, sc);
-    } catch (const std::bad_alloc&) {
-        return VIT_ENOMEM;
-    }
-    if ((int64_t)sc.unit_song.size() != c.units) return VIT_EINVAL;      // (cannot happen: the layout counted the same segments)
-    std::memcpy(hb, offsets, (size_t)(B + 1) * sizeof(int64_t));
-    std::memcpy(hb + (c.off_ckpt_base - c.off_offsets), sc.ckpt_base.data(), (size_t)(B + 1) * sizeof(int64_t));
-    std::memcpy(hb + (c.off_unit_song - c.off_offsets), sc.unit_song.data(), (size_t)c.units * sizeof(int32_t));
-    std::memcpy(hb + (c.off_unit_seg - c.off_offsets), sc.unit_seg.data(), (size_t)c.units * sizeof(int32_t));
-    hipError_t e = hipMemcpyAsync(ws + c.off_offsets, hb, c.tables_bytes, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return hip_fail(e);
-    e = hipEventRecord(plan->pk_event, st);
-    if (e != hipSuccess) return hip_fail(e);
-
-    // ---- pass 1: checkpoint rows + terminal state, one workgroup per slot
-    a.logE = logE;
-    a.lengths = nullptr;
-    a.hist = reinterpret_cast<float*>(ws + c.off_ckpt);
-    a.fmax = nullptr;
-    a.last_state = reinterpret_cast<int32_t*>(ws + c.off_last);
-    a.loglik = loglik;
-    a.B = B;
-    a.T = 1;                      // (unused: a song's rows come from the offsets)
-    a.hist_rows = c.n_ckpt;       // the scratch row of slot w is row n_ckpt + w
-    a.ckpt_every = (int)K;
-    a.t_begin = 0;
-    a.t_end = 1;
-    a.offsets = reinterpret_cast<const int64_t*>(ws + c.off_offsets);
-    a.n_slots = (int)n_slots;
-    a.slot_begin = reinterpret_cast<const int32_t*>(ws + c.off_slot_begin);
-    a.slot_songs = reinterpret_cast<const int32_t*>(ws + c.off_slot_songs);
-    a.ckpt_base = reinterpret_cast<const int64_t*>(ws + c.off_ckpt_base);
-    a.unit_song = nullptr;
-    e = forward(a);
-    if (e != hipSuccess) return hip_fail(e);
-
-    // ---- pass 2: the launches of the schedule; every unit's back-trace starts from what the launch before it wrote
-    vit::BtArgs b{};
-    bt_args_from_plan(plan, b);
-    b.SD = SDH;
-    b.col0 = 0;             // the workgroup kernels' rows: state i in column i, the frame maximum (banded) in pad column S
-    b.mcol = plan->S;
-    b.xcol0 = -1;
-    b.aux_frames = 1;
-    b.have_fmax = family == 2 ? 1 : 0;
-    // family 2: a unit's row 0 is the second of its K + 2 rows
-    float* seg = reinterpret_cast<float*>(ws + c.off_seg) + (family == 2 ? SDH : 0);
     b.hist = seg;
     b.hist_rows = seg_rows;
     b.last_state = reinterpret_cast<const int32_t*>(ws + c.off_slast);
@@ -1422,10 +1261,9 @@ int vit_decode_packed_bounded(const vit_plan* plan, const void* logE, int emis_d
     b.states = states;
     b.states_stride = 0;
     b.T = (int)(K + 1);
-    b.counters = nullptr;
+    b.counters = nullptr;   // no event counts and no chunk flags in pass 2: the layout has no room for them
     b.mask = nullptr;
-    b.bt_form = family == 1 ? 1 : 0;
-    b.warm = family == 1 ? (tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarm) : (tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarmSparse);
+    b.bt_form = family == kFamStep ? 1 : 0;
     vit::FwdArgs f = a;
     f.hist = seg;
     f.hist_rows = seg_rows;
@@ -1439,23 +1277,39 @@ int vit_decode_packed_bounded(const vit_plan* plan, const void* logE, int emis_d
         f.B = nu;
         f.unit_song = d_unit_song + u0;
         f.unit_seg = d_unit_seg + u0;
-        e = forward(f);
-        if (e != hipSuccess) return hip_fail(e);
-        e = vit::launch_packed_segment_prep(a.offsets, f.unit_song, f.unit_seg, (int)nu, (int)K, states, a.last_state,
-                                            reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast),
-                                            reinterpret_cast<int64_t*>(ws + c.off_sbase), st);
-        if (e != hipSuccess) return hip_fail(e);
+        VIT_TRY(form.forward(f, f16, st));
+        VIT_TRY(vit::launch_packed_segment_prep(a.offsets, f.unit_song, f.unit_seg, (int)nu, (int)K, states, a.last_state,
+                                                reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast),
+                                                reinterpret_cast<int64_t*>(ws + c.off_sbase), st));
         b.B = nu;
-        if (family == 1) {              // step plans: the lazy kernel, one wave per (unit, chunk)
-            b.chunks = vit::backtrace_chunks(nu, b.T);
-            e = vit::launch_backtrace_rows_segment(b, st);
-        } else {
-            b.chunks = vit::sparse_backtrace_chunks(nu, b.T, plan->n_cus);
-            e = vit::launch_backtrace_sparse(b, st);
-        }
-        if (e != hipSuccess) return hip_fail(e);
+        VIT_TRY(segment_backtrace(plan, family, false, b, st));
     }
     return VIT_OK;
+}
+
+}  // namespace
+
+size_t vit_workspace_bytes_packed_checkpointed(const vit_plan* plan, int64_t B, const int64_t* offsets, int64_t segment_frames) {
+    return budgeted_bytes(plan, pc_family, B, offsets, segment_frames);
+}
+
+int vit_decode_packed_checkpointed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
+                                   size_t workspace_bytes, int32_t* states, float* loglik, int64_t segment_frames, vit_stream stream) {
+    return decode_packed_budgeted(plan, pc_family, logE, emis_dtype, B, offsets, workspace, workspace_bytes, states, loglik, segment_frames, stream);
+}
+
+int64_t vit_packed_bounded_units(const vit_plan* plan, int64_t B) {
+    if (!plan || B < 0 || B > (int64_t)1 << 30) return 0;
+    return pb_units(plan, pb_family(plan), B);
+}
+
+size_t vit_workspace_bytes_packed_bounded(const vit_plan* plan, int64_t B, const int64_t* offsets, int64_t segment_frames) {
+    return budgeted_bytes(plan, pb_family, B, offsets, segment_frames);
+}
+
+int vit_decode_packed_bounded(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
+                              size_t workspace_bytes, int32_t* states, float* loglik, int64_t segment_frames, vit_stream stream) {
+    return decode_packed_budgeted(plan, pb_family, logE, emis_dtype, B, offsets, workspace, workspace_bytes, states, loglik, segment_frames, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1476,7 +1330,7 @@ bool lg_applies(const vit_plan* p, const vit_obs_params* obs) {
 size_t vit_workspace_bytes_logits(const vit_plan* plan, const vit_obs_params* obs, int64_t B, int64_t T) {
     if (!plan || !obs || B < 0 || T < 1) return 0;
     if (!lg_applies(plan, obs)) return 0;
-    return ws_layout_hist(B, (size_t)T, (size_t)vit::wave_hist_stride(plan->bp.wave_npl)).bytes;
+    return ws_layout_hist(B, (size_t)T, (size_t)hist_layout(plan, kFamWave).SD).bytes;
 }
 
 int vit_decode_logits(const vit_plan* plan, const float* logits, const vit_obs_params* obs, int64_t B, int64_t T, const int64_t* lengths,
@@ -1488,8 +1342,7 @@ int vit_decode_logits(const vit_plan* plan, const float* logits, const vit_obs_p
     if (obs->mode < 0 || obs->mode > 2 || obs->n_bins < 2 || (int64_t)obs->n_bins + 1 != plan->S) return VIT_EINVAL;
     if (!lg_applies(plan, obs)) return VIT_EUNSUPPORTED;      // (everything that can refuse the plan or the builder is asked here)
     if (B > 0 && (!logits || !states)) return VIT_EINVAL;
-    const int SDH = vit::wave_hist_stride(plan->bp.wave_npl);
-    const WsLayout w = ws_layout_hist(B, (size_t)T, (size_t)SDH);
+    const WsLayout w = ws_layout_hist(B, (size_t)T, (size_t)hist_layout(plan, kFamWave).SD);
     if (workspace_bytes < w.bytes) return VIT_EWORKSPACE;
     if (B == 0) return VIT_OK;
     stamp_erase(plan, workspace);
@@ -1519,19 +1372,15 @@ int vit_decode_logits(const vit_plan* plan, const float* logits, const vit_obs_p
     fa.prior = obs->mode == 2 ? obs->prior : nullptr;
     hipError_t e = vit::launch_fused_logits(fa, (hipStream_t)stream);
     if (e == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;     // (cannot happen: lg_applies asked the same predicate)
-    if (e != hipSuccess) return hip_fail(e);
+    VIT_TRY(e);
     // the back-trace of a full wave-layout history, through the record vit_backtrace reads; the record does not outlive the call
     FwdStamp st;
     st.ws = workspace;
     st.B = B;
     st.T = T;
-    st.family = 3;
-    st.SD = SDH;
-    st.col0 = SDH - plan->S;
-    st.mcol = 0;
-    st.xcol0 = 1;
+    st.family = kFamWave;
+    st.lay = hist_layout(plan, kFamWave);
     st.aux_frames = vit::wave_aux_frames(plan->bp.wave_npl, plan->S, fa.f.n_extras);
-    st.have_fmax = 1;
     st.half = 0;
     stamp_put(plan, st);
     rc = backtrace_impl(plan, nullptr, 0, false, B, T, lengths, workspace, workspace_bytes, states, stream);
@@ -1542,8 +1391,7 @@ int vit_decode_logits(const vit_plan* plan, const float* logits, const vit_obs_p
 int vit_voicing_map(const int32_t* states, int64_t n, int32_t n_bins, uint8_t* voiced, int32_t* bins,
                     vit_stream stream) {
     if (n < 0 || n_bins < 1 || (n > 0 && (!states || !voiced || !bins))) return VIT_EINVAL;
-    hipError_t e = vit::launch_voicing_map(states, n, n_bins, voiced, bins, (hipStream_t)stream);
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(vit::launch_voicing_map(states, n, n_bins, voiced, bins, (hipStream_t)stream));
 }
 
 int vit_obs_shaun(const float* logits, int64_t n_frames, int32_t n_bins, int32_t spw, double threshold_logit,
@@ -1551,14 +1399,14 @@ int vit_obs_shaun(const float* logits, int64_t n_frames, int32_t n_bins, int32_t
     if (n_frames < 0 || n_bins < 2 || (n_frames > 0 && (!logits || !logE))) return VIT_EINVAL;
     hipError_t e = vit::launch_obs_shaun(logits, n_frames, n_bins, spw, threshold_logit, offset, scale, logE, (hipStream_t)stream);
     if (e == hipErrorInvalidValue) return VIT_EUNSUPPORTED;
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(e);
 }
 
 int vit_obs_softmax(const float* logits, int64_t n_frames, int32_t n_bins, int32_t spw, float* logE, vit_stream stream) {
     if (n_frames < 0 || n_bins < 2 || (n_frames > 0 && (!logits || !logE))) return VIT_EINVAL;
     hipError_t e = vit::launch_obs_softmax(logits, n_frames, n_bins, spw, logE, (hipStream_t)stream);
     if (e == hipErrorInvalidValue) return VIT_EUNSUPPORTED;
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(e);
 }
 
 int vit_obs_softmax_scaled(const float* logits, int64_t n_frames, int32_t n_bins, int32_t spw, double unvoiced_logit,
@@ -1566,7 +1414,7 @@ int vit_obs_softmax_scaled(const float* logits, int64_t n_frames, int32_t n_bins
     if (n_frames < 0 || n_bins < 2 || (n_frames > 0 && (!logits || !logE))) return VIT_EINVAL;
     hipError_t e = vit::launch_obs_softmax_scaled(logits, n_frames, n_bins, spw, unvoiced_logit, prior, logE, (hipStream_t)stream);
     if (e == hipErrorInvalidValue) return VIT_EUNSUPPORTED;
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(e);
 }
 
 int vit_obs_activations(const float* hf0, int64_t ld, int32_t n_bins, int64_t B, const int64_t* offsets_dev, int64_t total_frames,
@@ -1577,9 +1425,8 @@ int vit_obs_activations(const float* hf0, int64_t ld, int32_t n_bins, int64_t B,
     if (out_dtype != VIT_F32 && out_dtype != VIT_F16) return VIT_EINVAL;
     uint32_t below_bits;
     memcpy(&below_bits, &clamp_below, sizeof(below_bits));
-    hipError_t e = vit::launch_activations(hf0, ld, n_bins, (int)B, offsets_dev, total_frames, below_bits, clamp_to, stats, logE,
-                                           out_dtype == VIT_F16, (hipStream_t)stream);
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(vit::launch_activations(hf0, ld, n_bins, (int)B, offsets_dev, total_frames, below_bits, clamp_to, stats, logE,
+                                           out_dtype == VIT_F16, (hipStream_t)stream));
 }
 
 int vit_snippets_append(const float* snippets, int32_t n_snippets, int32_t n_channels, int32_t n_frames, int32_t mode,
@@ -1587,22 +1434,19 @@ int vit_snippets_append(const float* snippets, int32_t n_snippets, int32_t n_cha
     if (n_snippets < 0 || n_channels < 2 || n_frames < 1 || (mode != 0 && mode != 1) || n_rows < 0 ||
         n_rows > (int64_t)n_snippets * n_frames || (n_rows > 0 && (!snippets || !rows_out)))
         return VIT_EINVAL;
-    hipError_t e = vit::launch_snippets_append(snippets, n_snippets, n_channels, n_frames, mode, rows_out, n_rows, (hipStream_t)stream);
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(vit::launch_snippets_append(snippets, n_snippets, n_channels, n_frames, mode, rows_out, n_rows, (hipStream_t)stream));
 }
 
 int vit_voicing_notes(const int32_t* states, int64_t n, int32_t n_bins, const float* note_range, uint8_t* voiced,
                       int32_t* bins, float* notes, float* notes_voiced, vit_stream stream) {
     if (n < 0 || n_bins < 1 || (n > 0 && (!states || !note_range))) return VIT_EINVAL;
-    hipError_t e = vit::launch_voicing_notes(states, n, n_bins, note_range, voiced, bins, notes, notes_voiced, (hipStream_t)stream);
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(vit::launch_voicing_notes(states, n, n_bins, note_range, voiced, bins, notes, notes_voiced, (hipStream_t)stream));
 }
 
 /* DPP scan self-test used by tests/test_gpu_parity.py */
 int vit_debug_scan(const float* vals, int n_waves, int mode, float* out_v, int32_t* out_i, vit_stream stream) {
     if (!vals || !out_v || !out_i || n_waves < 1) return VIT_EINVAL;
-    hipError_t e = vit::launch_scan_selftest(vals, n_waves, mode, out_v, out_i, (hipStream_t)stream);
-    return e == hipSuccess ? VIT_OK : hip_fail(e);
+    return hip_status(vit::launch_scan_selftest(vals, n_waves, mode, out_v, out_i, (hipStream_t)stream));
 }
 
 }  // extern "C"

@@ -27,6 +27,10 @@ import torch
 from . import _lib
 
 
+_NO_PACKED_DECODE = ("the packed decode needs a plan with the wave form, the floor form or the step form "
+                     "(unstructured matrices and scan-only banded plans: pad and use decode(lengths=))")
+
+
 def _as_host_f32(x, shape=None) -> np.ndarray:
     if isinstance(x, torch.Tensor):
         x = x.detach().cpu().numpy()
@@ -152,6 +156,15 @@ class ViterbiDecoder:
             else:
                 self._ws_slots[slot] = ws
         return (ws.data_ptr() + 255) & ~255, ws.numel() - 256
+
+    def _call_workspace(self, need: int, workspace: Optional[torch.Tensor]) -> Tuple[torch.Tensor, int, int, bool]:
+        """The workspace of ONE call of a bounded, packed or fused decode: the caller's tensor, or ``need + 256`` bytes allocated here
+        -> (tensor, its first 256-byte aligned address, the bytes usable from there, allocated here).  A buffer allocated here must
+        outlive the kernels: the decode synchronises the stream before it returns."""
+        ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
+            raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
+        return ws, (ws.data_ptr() + 255) & ~255, ws.numel() - 256, workspace is None
 
     # ------------------------------------------------------------------ checks
     def _check_emissions(self, logE: torch.Tensor) -> Tuple[torch.Tensor, bool, int]:
@@ -328,17 +341,14 @@ class ViterbiDecoder:
         if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
             raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
         if B > 0:
-            need = self.workspace_bytes_checkpointed(B, T, segment_frames)
-            ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
-                raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
+            ws, ws_ptr, ws_bytes, mine = self._call_workspace(self.workspace_bytes_checkpointed(B, T, segment_frames), workspace)
             with torch.cuda.device(self.device):
                 rc = lib.vit_decode_checkpointed(self._plan, logE.data_ptr(), dt, B, T, lengths.data_ptr() if lengths is not None else None,
-                                                 (ws.data_ptr() + 255) & ~255, ws.numel() - 256, states.data_ptr(), loglik.data_ptr(),
+                                                 ws_ptr, ws_bytes, states.data_ptr(), loglik.data_ptr(),
                                                  int(segment_frames), torch.cuda.current_stream(self.device).cuda_stream)
             _lib.check(rc, "vit_decode_checkpointed")
-            if workspace is None:
-                torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
+            if mine:
+                torch.cuda.current_stream(self.device).synchronize()
         if out_dtype != torch.int32:
             states = states.to(out_dtype)
         return (states[0], loglik[0]) if single else (states, loglik)
@@ -401,17 +411,14 @@ class ViterbiDecoder:
         if B > 0:
             need = int(lib.vit_workspace_bytes_packed(self._plan, B, N))
             if need == 0:
-                raise _lib.ViterbiHipError("the packed decode needs a plan with the wave form, the floor form or the step form "
-                                           "(unstructured matrices and scan-only banded plans: pad and use decode(lengths=))")
-            ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
-                raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
+                raise _lib.ViterbiHipError(_NO_PACKED_DECODE)
+            ws, ws_ptr, ws_bytes, mine = self._call_workspace(need, workspace)
             with torch.cuda.device(self.device):
-                rc = lib.vit_decode_packed(self._plan, emission_logits.data_ptr(), dt, B, off.ctypes.data, (ws.data_ptr() + 255) & ~255,
-                                           ws.numel() - 256, states.data_ptr(), loglik.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
+                rc = lib.vit_decode_packed(self._plan, emission_logits.data_ptr(), dt, B, off.ctypes.data, ws_ptr,
+                                           ws_bytes, states.data_ptr(), loglik.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
             _lib.check(rc, "vit_decode_packed")
-            if workspace is None:
-                torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
+            if mine:
+                torch.cuda.current_stream(self.device).synchronize()
         if out_dtype != torch.int32:
             states = states.to(out_dtype)
         return states, loglik
@@ -441,23 +448,25 @@ class ViterbiDecoder:
         wave form (S = 321 / 361); any other plan raises ``ViterbiHipError`` before anything is enqueued.  ``workspace``: an optional
         uint8 tensor of at least ``workspace_bytes_packed_checkpointed(...) + 256`` bytes to decode in (the caller then keeps it
         alive until the stream has run the decode: the call does not synchronise)."""
-        lib = _lib.load()
+        return self._decode_packed_segments("packed_checkpointed", emission_logits, offsets, segment_frames, out_dtype, workspace)
+
+    def _decode_packed_segments(self, entry: str, emission_logits: torch.Tensor, offsets, segment_frames: int, out_dtype: torch.dtype,
+                                workspace: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_packed_checkpointed`` / ``decode_packed_bounded``: `entry` names the pair ``workspace_bytes_<entry>`` (which
+        raises for a plan or a segment length that is not served) and ``vit_decode_<entry>``."""
         dt, off = self._check_packed(emission_logits, offsets)
         B, N = off.size - 1, int(off[-1])
         states = torch.empty((N,), dtype=torch.int32, device=self.device)
         loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
         if B > 0:
-            need = self.workspace_bytes_packed_checkpointed(off, segment_frames)
-            ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
-                raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
+            ws, ws_ptr, ws_bytes, mine = self._call_workspace(getattr(self, "workspace_bytes_" + entry)(off, segment_frames), workspace)
             with torch.cuda.device(self.device):
-                rc = lib.vit_decode_packed_checkpointed(self._plan, emission_logits.data_ptr(), dt, B, off.ctypes.data, (ws.data_ptr() + 255) & ~255,
-                                                        ws.numel() - 256, states.data_ptr(), loglik.data_ptr(), int(segment_frames),
-                                                        torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_packed_checkpointed")
-            if workspace is None:
-                torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
+                rc = getattr(_lib.load(), "vit_decode_" + entry)(self._plan, emission_logits.data_ptr(), dt, B, off.ctypes.data, ws_ptr, ws_bytes,
+                                                                 states.data_ptr(), loglik.data_ptr(), int(segment_frames),
+                                                                 torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(rc, "vit_decode_" + entry)
+            if mine:
+                torch.cuda.current_stream(self.device).synchronize()
         if out_dtype != torch.int32:
             states = states.to(out_dtype)
         return states, loglik
@@ -470,28 +479,32 @@ class ViterbiDecoder:
           largest K of 8192, 4096, ..., 64 that fits (fewest launches; the rule of ``plan_workspace``).
 
         Raises ViterbiHipError naming the need when nothing fits or the plan is not served.  Both modes decode the same bits."""
+        return self._plan_packed(offsets, max_workspace_bytes, _lib.load().vit_workspace_bytes_packed_checkpointed, "checkpointed",
+                                 "no packed checkpointed decode (wave-form plans only: split the recordings into groups whose "
+                                 "workspace_bytes_packed fits)")
+
+    def _plan_packed(self, offsets, max_workspace_bytes: Optional[int], size_of, kind: str, unserved: str) -> dict:
+        """``plan_workspace_packed`` / ``plan_workspace_packed_bounded``: `size_of` is the library's size query of the budgeted decode,
+        `kind` and `unserved` what the errors call it."""
         off = self._host_offsets(offsets)
         B, N = off.size - 1, int(off[-1])
         need = self.workspace_bytes_packed(B, N)
         if need == 0 and B > 0:
-            raise _lib.ViterbiHipError("the packed decode needs a plan with the wave form, the floor form or the step form "
-                                       "(unstructured matrices and scan-only banded plans: pad and use decode(lengths=))")
+            raise _lib.ViterbiHipError(_NO_PACKED_DECODE)
         if max_workspace_bytes is None or need <= max_workspace_bytes:
             return {"mode": "full", "workspace_bytes": need}
-        lib = _lib.load()
         least, K = 0, 8192
         while K >= 64:
-            ck = int(lib.vit_workspace_bytes_packed_checkpointed(self._plan, B, off.ctypes.data, K))
+            ck = int(size_of(self._plan, B, off.ctypes.data, K))
             if 0 < ck <= max_workspace_bytes:           # the largest segment that fits: fewest launches
                 return {"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ck}
             least = ck if least == 0 or 0 < ck < least else least
             K //= 2
         if least == 0:
             raise _lib.ViterbiHipError(f"the packed decode of {B} recordings ({N} frames) needs a workspace of {need} bytes, the budget is "
-                                       f"{max_workspace_bytes}, and this plan has no packed checkpointed decode (wave-form plans only: "
-                                       "split the recordings into groups whose workspace_bytes_packed fits)")
+                                       f"{max_workspace_bytes}, and this plan has {unserved}")
         raise _lib.ViterbiHipError(f"no packed decode of {B} recordings ({N} frames) fits a workspace of {max_workspace_bytes} bytes "
-                                   f"(the full history needs {need}, the checkpointed decode at least {least})")
+                                   f"(the full history needs {need}, the {kind} decode at least {least})")
 
     # ------------------------------------------------------------------ the same for every plan with a packed decode
     def workspace_bytes_packed_bounded(self, offsets, segment_frames: int) -> int:
@@ -515,54 +528,15 @@ class ViterbiDecoder:
         ``ViterbiHipError`` before anything is enqueued.  ``workspace``: an optional uint8 tensor of at least
         ``workspace_bytes_packed_bounded(...) + 256`` bytes to decode in (the caller then keeps it alive until the stream has run the
         decode: the call does not synchronise)."""
-        lib = _lib.load()
-        dt, off = self._check_packed(emission_logits, offsets)
-        B, N = off.size - 1, int(off[-1])
-        states = torch.empty((N,), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
-        if B > 0:
-            need = self.workspace_bytes_packed_bounded(off, segment_frames)
-            ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
-                raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
-            with torch.cuda.device(self.device):
-                rc = lib.vit_decode_packed_bounded(self._plan, emission_logits.data_ptr(), dt, B, off.ctypes.data, (ws.data_ptr() + 255) & ~255,
-                                                   ws.numel() - 256, states.data_ptr(), loglik.data_ptr(), int(segment_frames),
-                                                   torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_packed_bounded")
-            if workspace is None:
-                torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return states, loglik
+        return self._decode_packed_segments("packed_bounded", emission_logits, offsets, segment_frames, out_dtype, workspace)
 
     def plan_workspace_packed_bounded(self, offsets, max_workspace_bytes: Optional[int] = None) -> dict:
         """``plan_workspace_packed`` over ``decode_packed_bounded``: ``{"mode": "full", "workspace_bytes": ...}`` when ``decode_packed``
         fits the budget, else ``{"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ...}`` with the largest K of 8192,
         4096, ..., 64 whose ``workspace_bytes_packed_bounded`` fits.  Raises ViterbiHipError naming the least need when nothing fits
         or the plan is not served."""
-        off = self._host_offsets(offsets)
-        B, N = off.size - 1, int(off[-1])
-        need = self.workspace_bytes_packed(B, N)
-        if need == 0 and B > 0:
-            raise _lib.ViterbiHipError("the packed decode needs a plan with the wave form, the floor form or the step form "
-                                       "(unstructured matrices and scan-only banded plans: pad and use decode(lengths=))")
-        if max_workspace_bytes is None or need <= max_workspace_bytes:
-            return {"mode": "full", "workspace_bytes": need}
-        lib = _lib.load()
-        least, K = 0, 8192
-        while K >= 64:
-            ck = int(lib.vit_workspace_bytes_packed_bounded(self._plan, B, off.ctypes.data, K))
-            if 0 < ck <= max_workspace_bytes:           # the largest segment that fits: fewest launches
-                return {"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ck}
-            least = ck if least == 0 or 0 < ck < least else least
-            K //= 2
-        if least == 0:
-            raise _lib.ViterbiHipError(f"the packed decode of {B} recordings ({N} frames) needs a workspace of {need} bytes, the budget is "
-                                       f"{max_workspace_bytes}, and this plan has no bounded packed decode (pad and use "
-                                       "decode_checkpointed(lengths=))")
-        raise _lib.ViterbiHipError(f"no packed decode of {B} recordings ({N} frames) fits a workspace of {max_workspace_bytes} bytes "
-                                   f"(the full history needs {need}, the bounded decode at least {least})")
+        return self._plan_packed(offsets, max_workspace_bytes, _lib.load().vit_workspace_bytes_packed_bounded, "bounded",
+                                 "no bounded packed decode (pad and use decode_checkpointed(lengths=))")
 
     # ------------------------------------------------------------------ fused logits -> path decode
     @staticmethod
@@ -628,16 +602,14 @@ class ViterbiDecoder:
                 raise _lib.ViterbiHipError("the fused logits decode needs a plan with the wave form whose extra column is the last state "
                                            "(S = 321 / 361), n_bins = S - 1, and a builder geometry of the reference (shaun / scaled "
                                            "softmax with peak width 5, softmax with 15): build the emissions and use decode()")
-            ws = workspace if workspace is not None else torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
-                raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
+            ws, ws_ptr, ws_bytes, mine = self._call_workspace(need, workspace)
             with torch.cuda.device(self.device):
                 rc = lib.vit_decode_logits(self._plan, lg.data_ptr(), ctypes.byref(op), B, T, lengths.data_ptr() if lengths is not None else None,
-                                           (ws.data_ptr() + 255) & ~255, ws.numel() - 256, emissions_out.data_ptr() if emissions_out is not None else None,
+                                           ws_ptr, ws_bytes, emissions_out.data_ptr() if emissions_out is not None else None,
                                            states.data_ptr(), loglik.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
             _lib.check(rc, "vit_decode_logits")
-            if workspace is None:
-                torch.cuda.current_stream(self.device).synchronize()      # a workspace allocated here must outlive the kernels
+            if mine:
+                torch.cuda.current_stream(self.device).synchronize()
         if out_dtype != torch.int32:
             states = states.to(out_dtype)
         return (states[0], loglik[0]) if single else (states, loglik)
