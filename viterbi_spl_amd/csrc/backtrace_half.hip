@@ -17,9 +17,9 @@
 // first 8 floats of 9 rows (scalars), and 64 emission columns of 8 odd rows (2-3 lines each).  A window that leaves a
 // span drops the tile (re-fetched around the new state, starting at the frame that missed); a bound failure evaluates
 // the whole row -- from global memory at an even frame, rebuilt in full (361 x 35 candidates) at an odd one: rare (e.g.
-// a voiced -> unvoiced switch), exact either way.  Chunking, speculative warm-up and the verify-and-repair pass are
-// those of sparse_backtrace_kernel; a chunk's guess row is always an even frame.
-#include "device_common.hpp"
+// a voiced -> unvoiced switch), exact either way.  The chunk scheme around chase() is the shared bt_run_chunks
+// (backtrace_common.hpp) with its two half-history parameters: a chunk's guess row is always an even frame, stored as row f / 2.
+#include "backtrace_common.hpp"
 
 namespace vit {
 
@@ -78,16 +78,9 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
     const int tb = lane < WX1 ? lane : WX1 - 1;
     const unsigned long long cand_or_bound = (nx >= 64 - W ? ~0ull : ((1ull << (W + nx)) - 1ull)) | (1ull << CB);
     const int il = lane & 31, hh = lane >> 5;          // odd frames: source il of the window, half hh of ITS window
-    bool inS[EPL], xcol[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int i = e * 64 + lane;
-        inS[e] = i < S;
-        bool x = i >= S;
-#pragma unroll
-        for (int k = 0; k < kMaxExtras; ++k) x |= (k < nx && i == a.extras[k]);
-        xcol[e] = x;
-    }
+    const BtSourceFlags<EPL> src(a, lane);
+    const auto& inS = src.inS;
+    const auto& xcol = src.xcol;
     const int lo_max = S - W, lo_off = a.lo_off;
     const bool fast_rows = !a.no_fast_rows && (nx == 0 || (nx == 1 && a.extras[0] == S - 1));      // no index above the one extra column
     auto lo_of = [&](const int j) -> int { const int l = j - lo_off; return l < 0 ? 0 : (l > lo_max ? lo_max : l); };
@@ -129,7 +122,7 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
 #pragma unroll
         for (int r = 0; r < kHbR; ++r) te[r * kHbNE + lane] = tr.se[r];
     };
-    int n_tiles = 0, n_miss = 0, n_full = 0, n_reb = 0, n_rep = 0, n_repf = 0;      // event counts of this wave
+    int n_tiles = 0, n_miss = 0, n_full = 0, n_reb = 0, n_repf = 0;      // event counts of this wave
 
     // chase(top, bottom, cur, write): decide the states of frames top .. bottom (descending), starting from state `cur`
     // at frame top+1.
@@ -344,68 +337,9 @@ __global__ void __launch_bounds__(1024) half_backtrace_kernel(BtArgs a) {
         return cur;
     };
 
-    const int Lf = Tb - 1;
-    if (MODE == 0) {
-        const int lo_c = (int)((long long)Lf * chunk / C), hi_c = (int)((long long)Lf * (chunk + 1) / C);
-        if (chunk == C - 1) {
-            for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
-            if (lane == 0) states[Tb - 1] = a.last_state[song];
-        }
-        int top = hi_c - 1 + a.warm;
-        top += top & 1 ? 0 : 1;                   // the guess row top + 1 must be a stored (even) frame
-        int cur;
-        if (chunk == C - 1 || top >= Lf - 1) {
-            top = Lf - 1;
-            cur = __builtin_amdgcn_readfirstlane(a.last_state[song]);
-        } else {
-            // guess: lowest-index argmax of delta row top+1
-            const float* g = hist + (size_t)((top + 1) >> 1) * SD + a.col0;
-            float d[EPL];
-            float m = -INFINITY;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                d[e] = inS[e] ? g[e * 64 + lane] : -INFINITY;
-                m = fmaxf(m, d[e]);
-            }
-            m = wave_max_all(m);
-            unsigned idx = 0x7fffffffu;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                const unsigned long long mk = __ballot(d[e] == m && inS[e]);
-                if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
-            }
-            cur = idx == 0x7fffffffu ? 0 : (int)idx;
-        }
-        if (hi_c <= lo_c) {                       // empty chunk (very short song)
-            if (lane == 0) a.entry[(size_t)song * C + chunk] = cur;
-            return;
-        }
-        cur = chase(top, hi_c, cur, false);       // warm-up: frames top .. hi_c, nothing written
-        if (lane == 0) a.entry[(size_t)song * C + chunk] = cur;   // state this chunk assumed at frame hi_c
-        chase(hi_c - 1, lo_c, cur, true);
-    } else {
-        int truth = -1;                           // verified state at frame hi_c of the chunk being checked
-        for (int c = C - 2; c >= 0; --c) {
-            const int lo_c = (int)((long long)Lf * c / C), hi_c = (int)((long long)Lf * (c + 1) / C);
-            if (truth < 0) truth = __builtin_amdgcn_readfirstlane(states[hi_c]);
-            const int assumed = __builtin_amdgcn_readfirstlane(a.entry[(size_t)song * C + c]);
-            if (hi_c > lo_c && assumed != truth) {
-                ++n_rep;
-                truth = chase(hi_c - 1, lo_c, truth, true);   // re-chase from the true state; ends at frame lo_c
-            } else {
-                truth = -1;                       // chunk c stands: its frame lo_c is already in `states`
-            }
-        }
-    }
-    if (lane == 0 && a.counters) {
-        int32_t* ct = a.counters + (size_t)song * kBtCounters;
-        if (n_tiles) atomicAdd(ct + kCtTiles, n_tiles);
-        if (n_miss) atomicAdd(ct + kCtMisses, n_miss);
-        if (n_full) atomicAdd(ct + kCtFullRows, n_full);
-        if (n_reb) atomicAdd(ct + kCtRebuilt, n_reb);
-        if (n_rep) atomicAdd(ct + kCtRepairs, n_rep);
-        if (n_repf) atomicAdd(ct + kCtRepairFrames, n_repf);
-    }
+    const int n_rep = bt_run_chunks<MODE, EPL, true>(chase, [&](const int f) { return hist + (size_t)(f >> 1) * SD + a.col0; }, states,
+                                                     a.entry + (size_t)song * C, MODE == 0 ? a.last_state[song] : 0, Tb, T, chunk, C, a.warm, S, lane);
+    bt_flush_counters(a.counters, song, lane == 0, n_tiles, n_miss, n_full, n_reb, n_rep, n_repf);
 }
 
 static size_t half_lds_bytes(const BtArgs& a, int nwaves) {
@@ -440,16 +374,7 @@ static hipError_t launch_half_t(const BtArgs& a, hipStream_t st, int phases) {
     // 416 registers of every SIMD and cannot start on a CU whose SIMDs each hold a 256-register forward wave (1024 songs in flight); an
     // eight-wave workgroup (208 per SIMD) can, which is what puts this back-trace UNDER the next batch's forward pass (BtArgs::block_waves)
     const int nw = a.block_waves == 8 || a.block_waves == 4 ? a.block_waves : 16;
-    const size_t lds = half_lds_bytes(a, nw);
-    const long long waves0 = (long long)a.B * a.chunks;
-    hipError_t e = hipSuccess;
-    if (phases & 1) {
-        hipLaunchKernelGGL((half_backtrace_kernel<0, ET>), dim3((int)((waves0 + nw - 1) / nw)), dim3(nw * 64), lds, st, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess || a.chunks <= 1 || !(phases & 2)) return e;
-    hipLaunchKernelGGL((half_backtrace_kernel<1, ET>), dim3((int)((a.B + nw - 1) / nw)), dim3(nw * 64), lds, st, a);
-    return hipGetLastError();
+    return launch_two_pass(half_backtrace_kernel<0, ET>, half_backtrace_kernel<1, ET>, (long long)a.B * a.chunks, a.B, nw, half_lds_bytes(a, nw), st, a, phases);
 }
 
 hipError_t launch_backtrace_half(const BtArgs& a, hipStream_t st, int phases) {

@@ -20,8 +20,9 @@
 // Parallelism comes from chunks: every song is cut into C chunks (up to 256) chased speculatively from a warm-up point
 // above their upper boundary (lane_spec_kernel); lane_verify_kernel compares what every chunk assumed at its upper boundary
 // with what the chunk above it decided there, and lane_repair_kernel (one lane per song) re-chases the chunks whose guess was
-// wrong until the new path meets the stored one.  Exact whatever the guesses were (the scheme of banded_backtrace_kernel).
-#include "device_common.hpp"
+// wrong until the new path meets the stored one.  Exact whatever the guesses were (the chunk scheme of backtrace_common.hpp, one
+// lane per stream: the chunk bounds and the counter flush are the shared ones, the pad / verify / repair sequence is this file's).
+#include "backtrace_common.hpp"
 
 namespace vit {
 
@@ -34,10 +35,6 @@ __device__ __forceinline__ const float* ln_readlane_ptr(const float* p, int l) {
     const unsigned long long v = reinterpret_cast<unsigned long long>(p);
     const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)v, l), hi = __builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
     return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ void ln_chunk_bounds(int Lf, int c, int C, int& lo_c, int& hi_c) {
-    lo_c = (int)((long long)Lf * c / C);
-    hi_c = (int)((long long)Lf * (c + 1) / C);
 }
 
 // The decision of one frame for every lane of the wave: lane l holds the path state `cur` at frame t+1 of its stream and the
@@ -286,7 +283,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_spec_kernel(BtArgs a) {
     const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows) * SD;
     int32_t* __restrict__ entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
     int lo_c, hi_c;
-    ln_chunk_bounds(Lf, chunk, C, lo_c, hi_c);
+    bt_chunk_bounds(Lf, chunk, C, lo_c, hi_c);
     if (valid && chunk == C - 1) states[Tb - 1] = a.last_state[song];
     bool act = valid && hi_c > lo_c;
     int top = hi_c - 1 + a.warm;
@@ -366,7 +363,7 @@ __global__ void lane_verify_kernel(BtArgs a, uint32_t* __restrict__ mask) {
     const long long off = packed ? a.offsets[song] : 0;
     const int Lf = (packed ? (int)(a.offsets[song + 1] - off) : song_length(a, song)) - 1;
     int lo_c, hi_c;
-    ln_chunk_bounds(Lf, c, C, lo_c, hi_c);
+    bt_chunk_bounds(Lf, c, C, lo_c, hi_c);
     if (hi_c <= lo_c) return;
     const int truth = a.states[(packed ? (size_t)off : (size_t)song * a.states_stride) + hi_c];
     const int32_t* entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
@@ -426,7 +423,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_repair_kernel(BtArgs a, const
             int c;
             if (take_bit(c)) {
                 int hi_c;
-                ln_chunk_bounds(Lf, c, C, lo_cc, hi_c);
+                bt_chunk_bounds(Lf, c, C, lo_cc, hi_c);
                 cc = c;
                 cur = states[hi_c];
                 t = hi_c - 1;
@@ -453,7 +450,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_repair_kernel(BtArgs a, const
                 // frame lo_cc = the upper boundary of the next chunk below that holds frames (chunks in between are empty)
                 int c2 = cc - 1, lo2 = 0, hi2 = 0;
                 for (; c2 >= 0; --c2) {
-                    ln_chunk_bounds(Lf, c2, C, lo2, hi2);
+                    bt_chunk_bounds(Lf, c2, C, lo2, hi2);
                     if (hi2 > lo2) break;
                 }
                 if (c2 < 0) {
@@ -473,12 +470,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_repair_kernel(BtArgs a, const
             }
         }
     }
-    if (valid && a.counters) {
-        int32_t* ct = a.counters + (size_t)song * kBtCounters;
-        if (n_rep) atomicAdd(ct + kCtRepairs, n_rep);
-        if (n_repf) atomicAdd(ct + kCtRepairFrames, n_repf);
-        if (decide.n_full) atomicAdd(ct + kCtFullRows, decide.n_full);
-    }
+    bt_flush_counters(a.counters, song, valid, 0, 0, decide.n_full, 0, n_rep, n_repf);
 }
 
 static size_t lane_lds_bytes(const BtArgs& a, bool table_in_lds) {
@@ -517,13 +509,7 @@ static hipError_t launch_lane_w(const BtArgs& a, hipStream_t st, int phases) {
 }
 template <int WQ>
 static hipError_t launch_lane_s(const BtArgs& a, hipStream_t st, int phases) {
-    const int nwt = (a.S + 63) / 64;
-    if (nwt <= 2) return launch_lane_w<WQ, 2>(a, st, phases);
-    if (nwt <= 4) return launch_lane_w<WQ, 4>(a, st, phases);
-    if (nwt <= 6) return launch_lane_w<WQ, 6>(a, st, phases);
-    if (nwt <= 8) return launch_lane_w<WQ, 8>(a, st, phases);
-    if (nwt <= 12) return launch_lane_w<WQ, 12>(a, st, phases);
-    return launch_lane_w<WQ, 16>(a, st, phases);
+    return bt_dispatch_upto<2, 4, 6, 8, 12, 16>((a.S + 63) / 64, [&](auto nwt) { return launch_lane_w<WQ, decltype(nwt)::value>(a, st, phases); });
 }
 
 hipError_t launch_backtrace_lane(const BtArgs& a, hipStream_t st, int phases) {

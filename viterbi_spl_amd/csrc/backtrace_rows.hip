@@ -1,6 +1,8 @@
 // backtrace_rows.hip -- back-trace kernels that stage whole history rows through LDS: the lean banded form and the
-// generic (lazy) form for any matrix.
-#include "device_common.hpp"
+// generic (lazy) form for any matrix.  Each kernel is its chase() over LDS tiles; the chunk scheme around it is the shared
+// bt_run_chunks (backtrace_common.hpp), and the lean kernel takes its candidate slots, lowest_candidate and full evaluation
+// from there too (the lazy kernel's full evaluation -- dense rows, step and unstructured matrices -- is its own).
+#include "backtrace_common.hpp"
 
 namespace vit {
 
@@ -37,7 +39,6 @@ __global__ void __launch_bounds__(512) banded_backtrace_kernel(BtArgs a) {
     constexpr int EPL = NWT;               // sources per lane in the full evaluation, strided: i = e*64 + lane
     constexpr int TF = kBtVec * 256;       // floats per wave tile
     const int S = a.S, SP = a.SP, SD = a.SD, T = a.T, W = a.W, K = a.K;
-    const int nx = a.n_extras;
     const int WX1 = W + kMaxExtras + 1;    // candidate-table row: window, extras, row constant
     const int CB = W + kMaxExtras;         // candidate index of the bound
     const int nwaves = blockDim.x >> 6;
@@ -70,34 +71,16 @@ __global__ void __launch_bounds__(512) banded_backtrace_kernel(BtArgs a) {
     const int tile_off = wv * TF;
 
     // ---- per-lane constants, per candidate slot
-    bool isw[KC], cand[KC];
-    int pb[KC], tb[KC];
-    unsigned long long wmask[KC];                                           // lanes of slot k that hold window candidates
+    const BtSlots<KC> sl(a, lane);
+    const auto& isw = sl.isw;
+    const auto& cand = sl.cand;
+    const auto& tb = sl.tb;
+    int pb[KC];                                                              // row entry read (window candidates: + lo)
 #pragma unroll
-    for (int k = 0; k < KC; ++k) {
-        const int c = 64 * k + lane;
-        isw[k] = c < W;
-        cand[k] = c < W + nx;
-        const int xs = (c >= W && c < W + nx) ? a.extras[(c - W) & (kMaxExtras - 1)] : 0;
-        pb[k] = c == CB ? a.mcol : a.col0 + (isw[k] ? c : xs);               // row entry read (window candidates: + lo)
-        tb[k] = c < WX1 ? c : WX1 - 1;                                       // entry of the target's table row
-        const int nwin = W - 64 * k;
-        wmask[k] = nwin >= 64 ? ~0ull : (nwin <= 0 ? 0ull : ((1ull << nwin) - 1ull));
-    }
+    for (int k = 0; k < KC; ++k) pb[k] = 64 * k + lane == CB ? a.mcol : a.col0 + (isw[k] ? 64 * k + lane : sl.xs[k]);
     const int kb = CB >> 6, lb = CB & 63;                                    // slot / lane of the bound candidate
     const int tabX_off = (int)(tabX - tiles);
-    int ic[EPL];
-    bool isx[EPL], inS[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int i = e * 64 + lane;
-        ic[e] = i < S ? a.col0 + i : a.col0;
-        inS[e] = i < S;
-        bool x = i >= S;
-#pragma unroll
-        for (int k = 0; k < kMaxExtras; ++k) x |= (k < nx && i == a.extras[k]);
-        isx[e] = x;
-    }
+    const BtSourceFlags<EPL> src(a, lane);
     const int rv = SD / 4;  // float4 per row
 
     // chase(top, bottom, cur, write): decide the states of frames top .. bottom (descending) from the delta rows
@@ -156,56 +139,11 @@ __global__ void __launch_bounds__(512) banded_backtrace_kernel(BtArgs a) {
                     mloc = fmaxf(mloc, v[k]);
                 }
                 const float m = wave_max_all(mloc);
-                // lowest source index among the window / extra-column candidates equal to `mm`
-                auto lowest_candidate = [&](const float mm) -> unsigned {
-                    unsigned best = 0x7fffffffu;
-                    bool have_w = false;
-#pragma unroll
-                    for (int k = 0; k < KC; ++k) {
-                        const unsigned long long mk = __ballot(v[k] == mm && cand[k]);
-                        const unsigned long long mw = mk & wmask[k];
-                        if (mw && !have_w) {                                 // window candidates ascend with the source index
-                            const unsigned c = lo + 64 * k + __builtin_ctzll(mw);
-                            best = c < best ? c : best;
-                            have_w = true;
-                        }
-                        unsigned long long mx = mk & ~wmask[k];              // extra-column candidates: arbitrary indices
-                        while (mx) {
-                            const unsigned c = __builtin_amdgcn_readlane(pb[k], __builtin_ctzll(mx)) - a.col0;   // column -> state
-                            best = c < best ? c : best;
-                            mx &= mx - 1;
-                        }
-                    }
-                    return best;
-                };
-                unsigned idx = 0x7fffffffu;
-                if (mf < m) {
-                    // ---- common case: no row-constant candidate can tie or win
-                    idx = lowest_candidate(m);
-                } else {
-                    // ---- full evaluation: every source outside the window / extras contributes fl(delta_t[i] + c_cur)
-                    float vf[EPL];
-                    float m2 = -INFINITY;
-#pragma unroll
-                    for (int e = 0; e < EPL; ++e) {
-                        const int i = e * 64 + lane;
-                        const float d = L[row_off + ic[e]];
-                        const bool excl = isx[e] || (unsigned)(i - lo) < (unsigned)W;
-                        vf[e] = excl ? -INFINITY : d + cj;
-                        m2 = fmaxf(m2, vf[e]);
-                    }
-                    const float mm = fmaxf(m, wave_max_all(m2));
-                    // lowest index among the candidates equal to the max (an all -inf frame resolves to index 0
-                    // like np.argmax: every in-range source then matches)
-#pragma unroll
-                    for (int e = 0; e < EPL; ++e) {
-                        const unsigned long long mk = __ballot(vf[e] == mm && inS[e]);
-                        if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
-                    }
-                    const unsigned c = lowest_candidate(mm);
-                    idx = c < idx ? c : idx;
-                    if (idx == 0x7fffffffu) idx = 0;
-                }
+                // common case: no row-constant candidate can tie or win; else the full evaluation
+                // (pb, col0: the extra-column lanes of the row entries are col0 + the candidate's state)
+                auto row = [&](const int e) { return src.inS[e] ? L[row_off + a.col0 + e * 64 + lane] : -INFINITY; };
+                const unsigned idx = mf < m ? bt_lowest_candidate<KC>(sl, v, m, lo, 0.f, 0ull, pb, a.col0)
+                                            : bt_full_row<EPL, KC>(src, sl, v, row, cj, m, lo, W, lane, 0ull, pb, a.col0);
                 cur = (int)idx;
                 outv = lane == r ? cur : outv;
                 if (MODE == 1 && cur == __builtin_amdgcn_readlane(oldv, r)) { rstop = r; break; }
@@ -217,58 +155,8 @@ __global__ void __launch_bounds__(512) banded_backtrace_kernel(BtArgs a) {
         return cur;
     };
 
-    // Chunking, speculative warm-up and verification exactly as in lazy_backtrace_kernel.
-    const int Lf = Tb - 1;
-    if (MODE == 0) {
-        const int lo_c = (int)((long long)Lf * chunk / C), hi_c = (int)((long long)Lf * (chunk + 1) / C);
-        if (chunk == C - 1) {
-            for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
-            if (lane == 0) states[Tb - 1] = a.last_state[song];
-        }
-        int top = hi_c - 1 + a.warm;
-        int cur;
-        if (chunk == C - 1 || top >= Lf - 1) {
-            top = Lf - 1;
-            cur = __builtin_amdgcn_readfirstlane(a.last_state[song]);
-        } else {
-            // guess: lowest-index argmax of delta row top+1
-            const float* g = hist + (size_t)(top + 1) * SD + a.col0;
-            float d[EPL];
-            float m = -INFINITY;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                d[e] = inS[e] ? g[e * 64 + lane] : -INFINITY;
-                m = fmaxf(m, d[e]);
-            }
-            m = wave_max_all(m);
-            unsigned idx = 0x7fffffffu;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                const unsigned long long mk = __ballot(d[e] == m && inS[e]);
-                if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
-            }
-            cur = idx == 0x7fffffffu ? 0 : (int)idx;
-        }
-        if (hi_c <= lo_c) {                       // empty chunk (very short song)
-            if (lane == 0) a.entry[(size_t)song * C + chunk] = cur;
-            return;
-        }
-        cur = chase(top, hi_c, cur, false);       // warm-up: frames top .. hi_c, nothing written
-        if (lane == 0) a.entry[(size_t)song * C + chunk] = cur;   // state this chunk assumed at frame hi_c
-        chase(hi_c - 1, lo_c, cur, true);
-    } else {
-        int truth = -1;                           // verified state at frame hi_c of the chunk being checked
-        for (int c = C - 2; c >= 0; --c) {
-            const int lo_c = (int)((long long)Lf * c / C), hi_c = (int)((long long)Lf * (c + 1) / C);
-            if (truth < 0) truth = __builtin_amdgcn_readfirstlane(states[hi_c]);
-            const int assumed = __builtin_amdgcn_readfirstlane(a.entry[(size_t)song * C + c]);
-            if (hi_c > lo_c && assumed != truth) {
-                truth = chase(hi_c - 1, lo_c, truth, true);   // re-chase from the true state; ends at frame lo_c
-            } else {
-                truth = -1;                       // chunk c stands: its frame lo_c is already in `states`
-            }
-        }
-    }
+    bt_run_chunks<MODE, EPL>(chase, [&](const int f) { return hist + (size_t)f * SD + a.col0; }, states, a.entry + (size_t)song * C,
+                             MODE == 0 ? a.last_state[song] : 0, Tb, T, chunk, C, a.warm, S, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -529,63 +417,9 @@ __global__ void __launch_bounds__(kBtWaves * 64) lazy_backtrace_kernel(BtArgs a)
     return cur;
     };
 
-    // Frames 0 .. Tb-2 are decided (frame Tb-1 is the terminal state).  They are split into C chunks
-    // [lo_c, hi_c); chunk c is chased from a warm-up point `a.warm` frames above hi_c, starting from
-    // the best state of that frame (a guess); survivor paths coalesce, and MODE 1 verifies that the
-    // state chunk c reached at frame hi_c equals what chunk c+1 (already verified) decided there --
-    // if not, the chunk is chased again from the true state.  The result is exact either way.
-    const int L = Tb - 1;
-    if (MODE == 0) {
-        const int lo_c = (int)((long long)L * chunk / C), hi_c = (int)((long long)L * (chunk + 1) / C);
-        if (chunk == C - 1) {
-            for (int t = Tb + lane; t < Tpad; t += 64) states[t] = -1;
-            if (lane == 0) states[Tb - 1] = a.last_state[song];
-        }
-        int top = hi_c - 1 + a.warm;
-        int cur;
-        if (chunk == C - 1 || top >= L - 1) {
-            top = L - 1;
-            cur = __builtin_amdgcn_readfirstlane(a.last_state[song]);
-        } else {
-            // guess: lowest-index argmax of delta row top+1
-            const float* g = hist + (size_t)(top + 1) * SD + a.col0;
-            float d[EPL];
-            float m = -INFINITY;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                const int i = e * 64 + lane;
-                d[e] = i < S ? g[i] : -INFINITY;
-                m = fmaxf(m, d[e]);
-            }
-            m = wave_max_all(m);
-            unsigned idx = 0x7fffffffu;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                const unsigned long long mk = __ballot(d[e] == m && e * 64 + lane < S);
-                if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
-            }
-            cur = idx == 0x7fffffffu ? 0 : (int)idx;
-        }
-        if (hi_c <= lo_c) {                       // empty chunk (very short song)
-            if (lane == 0) entry[chunk] = cur;
-            return;
-        }
-        cur = chase(top, hi_c, cur, false);       // warm-up: frames top .. hi_c, nothing written
-        if (lane == 0) entry[chunk] = cur;   // state this chunk assumed at frame hi_c
-        chase(hi_c - 1, lo_c, cur, true);
-    } else {
-        int truth = -1;                           // verified state at frame hi_c of the chunk being checked
-        for (int c = C - 2; c >= 0; --c) {
-            const int lo_c = (int)((long long)L * c / C), hi_c = (int)((long long)L * (c + 1) / C);
-            if (truth < 0) truth = __builtin_amdgcn_readfirstlane(states[hi_c]);
-            const int assumed = __builtin_amdgcn_readfirstlane(entry[c]);
-            if (hi_c > lo_c && assumed != truth) {
-                truth = chase(hi_c - 1, lo_c, truth, true);   // re-chase from the true state; ends at frame lo_c
-            } else {
-                truth = -1;                       // chunk c stands: its frame lo_c is already in `states`
-            }
-        }
-    }
+    // (PK / SG only decide which pointers and limits the chunk scheme gets)
+    bt_run_chunks<MODE, EPL>(chase, [&](const int f) { return hist + (size_t)f * SD + a.col0; }, states, entry,
+                             MODE == 0 ? a.last_state[song] : 0, Tb, Tpad, chunk, C, a.warm, S, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -595,27 +429,30 @@ int backtrace_tile_rows(int SD) {
     int k = (kBtVec * 256) / SD;
     return k > 64 ? 64 : (k < 1 ? 1 : k);
 }
-template <int NWT, bool AFF, int KC, bool GT>
-static hipError_t launch_bt_lean(const BtArgs& a, int nwaves, size_t lds, hipStream_t st) {
-    const long long waves0 = (long long)a.B * a.chunks;
-    hipLaunchKernelGGL((banded_backtrace_kernel<NWT, AFF, 0, KC, GT>), dim3((int)((waves0 + nwaves - 1) / nwaves)), dim3(nwaves * 64), lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || a.chunks <= 1) return e;
-    hipLaunchKernelGGL((banded_backtrace_kernel<NWT, AFF, 1, KC, GT>), dim3((int)((a.B + nwaves - 1) / nwaves)), dim3(nwaves * 64), lds, st, a);
-    return hipGetLastError();
-}
-
 template <int NWT, int KC, bool GT>
 static hipError_t launch_bt_lean_a(const BtArgs& a, int nwaves, size_t lds, hipStream_t st) {
-    return a.lo_affine ? launch_bt_lean<NWT, true, KC, GT>(a, nwaves, lds, st) : launch_bt_lean<NWT, false, KC, GT>(a, nwaves, lds, st);
+    return bt_dispatch_bool(a.lo_affine != 0, [&](auto aff) {
+        return launch_two_pass(banded_backtrace_kernel<NWT, decltype(aff)::value, 0, KC, GT>, banded_backtrace_kernel<NWT, decltype(aff)::value, 1, KC, GT>,
+                               (long long)a.B * a.chunks, a.B, nwaves, lds, st, a);
+    });
+}
+
+// LDS bytes of the lazy kernel: tiles and decided states of its waves, the step table of a step plan, and (tables) the row
+// tables of a banded plan
+static size_t lazy_lds_bytes(const BtArgs& a, bool tables) {
+    size_t lds = sizeof(f32x4) * kBtWaves * kBtVec * 64 + sizeof(int32_t) * kBtWaves * 64;
+    if (!a.banded && a.step_ok) lds += sizeof(float) * (a.step_kb + 1) * a.SP;
+    if (tables) lds += sizeof(int32_t) * 2 * a.SP + sizeof(float) * (1 + kMaxExtras + a.W) * a.SP;
+    return lds;
 }
 
 template <int NWT>
 static hipError_t launch_bt_t(BtArgs a, hipStream_t st) {
-    // lean kernel: banded plan, no dense rows, frame maxima stored by the forward pass
+    // lean kernel: banded plan, no dense rows, frame maxima stored by the forward pass, at most three candidates per lane
+    // (W <= 128 gives kc <= 3 with today's kMaxExtras; anything wider falls through to the lazy kernel)
     if constexpr (NWT <= 12) {
-        if (a.banded && a.have_fmax && a.n_dense == 0 && a.W <= 128 && a.bt_form != 1) {
-            const int kc = (a.W + kMaxExtras + 1 + 63) / 64;
+        const int kc = (a.W + kMaxExtras + 1 + 63) / 64;
+        if (a.banded && a.have_fmax && a.n_dense == 0 && a.W <= 128 && kc <= 3 && a.bt_form != 1) {
             const size_t tile = sizeof(f32x4) * kBtVec * 64, lo_tab = sizeof(int32_t) * a.SP;
             const size_t table = sizeof(float) * (size_t)a.SP * (a.W + kMaxExtras + 1);
             // candidate table in LDS when it leaves room for at least four waves, else read from the image (L2)
@@ -623,70 +460,46 @@ static hipError_t launch_bt_t(BtArgs a, hipStream_t st) {
                 const int nw = 8 * tile + lo_tab + table + 1024 <= kLdsBytes ? 8 : 4;
                 return launch_bt_lean_a<NWT, 1, false>(a, nw, nw * tile + lo_tab + table, st);
             }
-            const size_t lds = 8 * tile + lo_tab;
-            if (kc == 1) return launch_bt_lean_a<NWT, 1, true>(a, 8, lds, st);
-            if (kc == 2) return launch_bt_lean_a<NWT, 2, true>(a, 8, lds, st);
-            if (kc == 3) return launch_bt_lean_a<NWT, 3, true>(a, 8, lds, st);
+            return bt_dispatch_upto<1, 2, 3>(kc, [&](auto k) { return launch_bt_lean_a<NWT, decltype(k)::value, true>(a, 8, 8 * tile + lo_tab, st); });
         }
     }
-    size_t lds = sizeof(f32x4) * kBtWaves * kBtVec * 64 + sizeof(int32_t) * kBtWaves * 64;
-    if (!a.banded && a.step_ok) lds += sizeof(float) * (a.step_kb + 1) * a.SP;
+    size_t lds = lazy_lds_bytes(a, false);
     if (a.banded) {
-        const size_t tables = sizeof(int32_t) * 2 * a.SP + sizeof(float) * (1 + kMaxExtras + a.W) * a.SP;
-        if (lds + tables + 1024 > kLdsBytes) {   // tables do not fit: evaluate full matrix rows instead (exact, slower)
+        if (lazy_lds_bytes(a, true) + 1024 > kLdsBytes) {   // tables do not fit: evaluate full matrix rows instead (exact, slower)
             a.banded = 0;
             a.have_fmax = 0;
         } else {
-            lds += tables;
+            lds = lazy_lds_bytes(a, true);
         }
     }
-    const long long waves0 = (long long)a.B * a.chunks;
-    hipLaunchKernelGGL((lazy_backtrace_kernel<NWT, 0>), dim3((int)((waves0 + kBtWaves - 1) / kBtWaves)), dim3(kBtWaves * 64),
-                       lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || a.chunks <= 1) return e;
-    hipLaunchKernelGGL((lazy_backtrace_kernel<NWT, 1>), dim3((int)((a.B + kBtWaves - 1) / kBtWaves)), dim3(kBtWaves * 64),
-                       lds, st, a);
-    return hipGetLastError();
+    return launch_two_pass(lazy_backtrace_kernel<NWT, 0>, lazy_backtrace_kernel<NWT, 1>, (long long)a.B * a.chunks, a.B, kBtWaves, lds, st, a);
+}
+
+// the lazy kernel over a packed batch (PK) or over one segment of a checkpointed decode (!PK): plans that are not banded
+template <bool PK>
+static hipError_t launch_rows_lazy(BtArgs a, hipStream_t st) {
+    a.K = backtrace_tile_rows(a.SD);
+    a.have_fmax = 0;
+    const size_t lds = lazy_lds_bytes(a, false);
+    const int nwt = (a.S + 63) / 64;
+    if (nwt > 16) return hipErrorInvalidConfiguration;
+    const long long waves0 = PK ? (long long)a.n_waves : (long long)a.B * a.chunks;
+    return bt_dispatch_upto<12, 16>(nwt, [&](auto n) {
+        return launch_two_pass(lazy_backtrace_kernel<decltype(n)::value, 0, PK, !PK>, lazy_backtrace_kernel<decltype(n)::value, 1, PK, !PK>, waves0, a.B,
+                               kBtWaves, lds, st, a);
+    });
 }
 
 hipError_t launch_backtrace_rows_packed(BtArgs a, hipStream_t st) {
     if (!a.offsets || !a.wave_song || !a.chunk_base || a.n_waves < 1 || a.chunks < 1 || a.chunks > kBtMaxChunks) return hipErrorInvalidValue;
     if (a.banded) return hipErrorInvalidConfiguration;         // (banded plans take the lane form)
-    a.K = backtrace_tile_rows(a.SD);
-    a.have_fmax = 0;
-    size_t lds = sizeof(f32x4) * kBtWaves * kBtVec * 64 + sizeof(int32_t) * kBtWaves * 64;
-    if (a.step_ok) lds += sizeof(float) * (a.step_kb + 1) * a.SP;
-    const int nwt = (a.S + 63) / 64;
-    const dim3 g0((unsigned)((a.n_waves + kBtWaves - 1) / kBtWaves)), g1((unsigned)((a.B + kBtWaves - 1) / kBtWaves)), blk(kBtWaves * 64);
-    if (nwt > 16) return hipErrorInvalidConfiguration;
-    if (nwt <= 12) hipLaunchKernelGGL((lazy_backtrace_kernel<12, 0, true>), g0, blk, lds, st, a);
-    else hipLaunchKernelGGL((lazy_backtrace_kernel<16, 0, true>), g0, blk, lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || a.chunks <= 1) return e;
-    if (nwt <= 12) hipLaunchKernelGGL((lazy_backtrace_kernel<12, 1, true>), g1, blk, lds, st, a);
-    else hipLaunchKernelGGL((lazy_backtrace_kernel<16, 1, true>), g1, blk, lds, st, a);
-    return hipGetLastError();
+    return launch_rows_lazy<true>(a, st);
 }
 
 hipError_t launch_backtrace_rows_segment(BtArgs a, hipStream_t st) {
     if (!a.lengths || a.offsets || a.hist_rows < a.T || a.chunks < 1 || a.chunks > kBtMaxChunks) return hipErrorInvalidValue;
     if (a.banded) return hipErrorInvalidConfiguration;         // (banded plans take the sparse or the lane form)
-    a.K = backtrace_tile_rows(a.SD);
-    a.have_fmax = 0;
-    size_t lds = sizeof(f32x4) * kBtWaves * kBtVec * 64 + sizeof(int32_t) * kBtWaves * 64;
-    if (a.step_ok) lds += sizeof(float) * (a.step_kb + 1) * a.SP;
-    const int nwt = (a.S + 63) / 64;
-    const long long waves0 = (long long)a.B * a.chunks;
-    const dim3 g0((unsigned)((waves0 + kBtWaves - 1) / kBtWaves)), g1((unsigned)((a.B + kBtWaves - 1) / kBtWaves)), blk(kBtWaves * 64);
-    if (nwt > 16) return hipErrorInvalidConfiguration;
-    if (nwt <= 12) hipLaunchKernelGGL((lazy_backtrace_kernel<12, 0, false, true>), g0, blk, lds, st, a);
-    else hipLaunchKernelGGL((lazy_backtrace_kernel<16, 0, false, true>), g0, blk, lds, st, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || a.chunks <= 1) return e;
-    if (nwt <= 12) hipLaunchKernelGGL((lazy_backtrace_kernel<12, 1, false, true>), g1, blk, lds, st, a);
-    else hipLaunchKernelGGL((lazy_backtrace_kernel<16, 1, false, true>), g1, blk, lds, st, a);
-    return hipGetLastError();
+    return launch_rows_lazy<false>(a, st);
 }
 
 int backtrace_chunks(int64_t B, int T) {
@@ -701,13 +514,7 @@ int backtrace_chunks(int64_t B, int T) {
 hipError_t launch_backtrace(BtArgs a, hipStream_t st) {
     if (a.bt_form == 0 && sparse_backtrace_applies(a)) return launch_backtrace_sparse(a, st);
     a.K = backtrace_tile_rows(a.SD);
-    const int nwt = (a.S + 63) / 64;
-    if (nwt <= 2) return launch_bt_t<2>(a, st);
-    if (nwt <= 4) return launch_bt_t<4>(a, st);
-    if (nwt <= 6) return launch_bt_t<6>(a, st);
-    if (nwt <= 8) return launch_bt_t<8>(a, st);
-    if (nwt <= 12) return launch_bt_t<12>(a, st);
-    return launch_bt_t<16>(a, st);
+    return bt_dispatch_upto<2, 4, 6, 8, 12, 16>((a.S + 63) / 64, [&](auto nwt) { return launch_bt_t<decltype(nwt)::value>(a, st); });
 }
 
 }  // namespace vit

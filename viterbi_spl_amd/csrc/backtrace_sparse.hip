@@ -13,8 +13,10 @@
 // a voiced -> unvoiced switch, whose best source can be any voiced state) the whole row is evaluated straight from
 // global memory -- exact either way.  When the path leaves the span (a jump through the floor or an extra column, or
 // accumulated drift) the tile is dropped and re-fetched around the new state, starting at the frame that missed.
-// Chunking, speculative warm-up and the verify-and-repair pass are those of banded_backtrace_kernel.
-#include "device_common.hpp"
+// This file holds the kernel's chase() -- tiles, fast rows, the general row -- and its launcher.  The chunk scheme around it
+// (bt_run_chunks), the candidate slots, lowest_candidate, the full evaluation and the counter flush are the shared ones of
+// backtrace_common.hpp.
+#include "backtrace_common.hpp"
 
 namespace vit {
 
@@ -72,35 +74,20 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
     float* tile = tiles + wv * kSpK * kSpRS;
 
     // ---- per-lane constants, per candidate slot: candidates 0 .. W-1 the window, W .. W+nx-1 the extra columns, CB the bound
-    bool isw[KC], cand[KC];
-    int xs[KC], auxi[KC], tb[KC];
-    unsigned long long wmask[KC];                                          // lanes of slot k that hold window candidates
+    const BtSlots<KC> sl(a, lane);
+    const auto& isw = sl.isw;
+    const auto& cand = sl.cand;
+    const auto& tb = sl.tb;
+    const auto& wmask = sl.wmask;
+    int auxi[KC];                                                          // aux entry read by a non-window candidate
 #pragma unroll
-    for (int k = 0; k < KC; ++k) {
-        const int c = 64 * k + lane;
-        isw[k] = c < W;
-        cand[k] = c < W + nx;
-        xs[k] = (c >= W && c < W + nx) ? a.extras[(c - W) & (kMaxExtras - 1)] : 0;     // state of an extra-column candidate
-        auxi[k] = c == CB ? 0 : 1 + ((c - W) & (kMaxExtras - 1));                      // aux entry read by a non-window candidate
-        tb[k] = c < WX1 ? c : WX1 - 1;
-        const int nwin = W - 64 * k;
-        wmask[k] = nwin >= 64 ? ~0ull : (nwin <= 0 ? 0ull : ((1ull << nwin) - 1ull));
-    }
+    for (int k = 0; k < KC; ++k) auxi[k] = 64 * k + lane == CB ? 0 : 1 + ((64 * k + lane - W) & (kMaxExtras - 1));
     const int kb = CB >> 6, lb = CB & 63;                                  // slot / lane of the bound candidate
     const unsigned long long cand_or_bound = (W + nx >= 64 ? ~0ull : ((1ull << (W + nx)) - 1ull)) | (1ull << (CB & 63));   // (KC == 1)
     // aux loads: entry e of row r by lane r * 8 + e (two halves of eight rows)
     const int aux_e = lane & 7;
     const int aux_col = aux_e == 0 ? a.mcol : (aux_e <= nx ? (a.xcol0 >= 0 ? a.xcol0 + aux_e - 1 : a.col0 + a.extras[(aux_e - 1) & (kMaxExtras - 1)]) : a.mcol);
-    bool inS[EPL], xcol[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const int i = e * 64 + lane;
-        inS[e] = i < S;
-        bool x = i >= S;
-#pragma unroll
-        for (int k = 0; k < kMaxExtras; ++k) x |= (k < nx && i == a.extras[k]);
-        xcol[e] = x;
-    }
+    const BtSourceFlags<EPL> src(a, lane);
     const int lo_max = S - W;
     // at most one extra column and it is the last state (the unvoiced state of the reference's matrices): no index is above it
     const bool fast_rows = KC == 1 && !a.no_fast_rows && (nx == 0 || (nx == 1 && a.extras[0] == S - 1));
@@ -108,7 +95,7 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
     const unsigned fr_mul = isw[0] ? 4u : 0u, fr_off = 4u * (unsigned)(isw[0] ? lane : kSpNS + auxi[0]);
     const int c0_max = (SD - kSpNS) & ~3;    // (rows are 16-byte aligned; the clamp may leave the last span 16-byte aligned only)
 
-    int n_tiles = 0, n_miss = 0, n_full = 0, n_rep = 0, n_repf = 0;      // event counts of this wave (vit_backtrace_counters)
+    int n_tiles = 0, n_miss = 0, n_full = 0, n_repf = 0;      // event counts of this wave (vit_backtrace_counters)
 
     // chase(top, bottom, cur, write): decide the states of frames top .. bottom (descending) from the delta rows
     // top .. bottom, starting from state `cur` at frame top+1.
@@ -236,58 +223,19 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
                     m = wave_max_all(mloc);
                     fail = !(mf < m);
                 }
-                auto lowest_candidate = [&](const float mm) -> unsigned {
-                    unsigned best = 0x7fffffffu;
-                    bool have_w = false;
-#pragma unroll
-                    for (int k = 0; k < KC; ++k) {
-                        const unsigned long long mk = (kLean && mm == m) ? (ge & ~(1ull << CB)) : __ballot(v[k] == mm && cand[k]);
-                        const unsigned long long mw = mk & wmask[k];
-                        if (mw && !have_w) {                                 // window candidates ascend with the source index
-                            const unsigned c = lo + 64 * k + __builtin_ctzll(mw);
-                            best = c < best ? c : best;
-                            have_w = true;
-                        }
-                        unsigned long long mx = mk & ~wmask[k];              // extra columns: arbitrary indices
-                        while (mx) {
-                            const unsigned c = __builtin_amdgcn_readlane(xs[k], __builtin_ctzll(mx));
-                            best = c < best ? c : best;
-                            mx &= mx - 1;
-                        }
-                    }
-                    return best;
-                };
-                unsigned idx = 0x7fffffffu;
+                unsigned idx;
                 if (!fail) {
-                    idx = lowest_candidate(m);
+                    idx = bt_lowest_candidate<KC, kLean>(sl, v, m, lo, m, ge & ~(1ull << CB));
                 } else {
                     float cj = 0.f;                                         // c_cur, from the bound candidate's table entry
 #pragma unroll
                     for (int k = 0; k < KC; ++k)
                         if (KC == 1 || k == kb) cj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(av[k]), lb));
                     ++n_full;
-                    // ---- full evaluation, straight from the history row in global memory: every source outside the
-                    //      window / extra columns contributes fl(delta_t[i] + c_cur)
+                    // ---- full evaluation, straight from the history row in global memory
                     const float* __restrict__ grow = hist + (size_t)(first + r) * SD + a.col0;
-                    float vf[EPL];
-                    float m2 = -INFINITY;
-#pragma unroll
-                    for (int e = 0; e < EPL; ++e) {
-                        const int i = e * 64 + lane;
-                        const float d = inS[e] ? grow[i] : -INFINITY;
-                        const bool excl = xcol[e] || (unsigned)(i - lo) < (unsigned)W;
-                        vf[e] = excl ? -INFINITY : d + cj;
-                        m2 = fmaxf(m2, vf[e]);
-                    }
-                    const float mm = fmaxf(m, wave_max_all(m2));
-#pragma unroll
-                    for (int e = 0; e < EPL; ++e) {
-                        const unsigned long long mk = __ballot(vf[e] == mm && inS[e]);
-                        if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
-                    }
-                    const unsigned c = lowest_candidate(mm);
-                    idx = c < idx ? c : idx;
-                    if (idx == 0x7fffffffu) idx = 0;        // an all -inf frame resolves to index 0 like np.argmax
+                    idx = bt_full_row<EPL, KC, kLean>(src, sl, v, [&](const int e) { return src.inS[e] ? grow[e * 64 + lane] : -INFINITY; },
+                                                      cj, m, lo, W, lane, ge & ~(1ull << CB));
                 }
                 cur = (int)idx;
                 outv = lane == r ? cur : outv;
@@ -302,67 +250,11 @@ __global__ void __launch_bounds__(1024) sparse_backtrace_kernel(BtArgs a) {
         return cur;
     };
 
-    const int Lf = Tb - 1;
-    if (MODE == 0) {
-        const int lo_c = (int)((long long)Lf * chunk / C), hi_c = (int)((long long)Lf * (chunk + 1) / C);
-        if (chunk == C - 1) {
-            if (!a.unit_states)          // (a unit of a packed decode: the entries behind it are the next song's)
-                for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
-            if (lane == 0) states[Tb - 1] = a.last_state[song];
-        }
-        int top = hi_c - 1 + a.warm;
-        int cur;
-        if (chunk == C - 1 || top >= Lf - 1) {
-            top = Lf - 1;
-            cur = __builtin_amdgcn_readfirstlane(a.last_state[song]);
-        } else {
-            // guess: lowest-index argmax of delta row top+1
-            const float* g = hist + (size_t)(top + 1) * SD + a.col0;
-            float d[EPL];
-            float m = -INFINITY;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                d[e] = inS[e] ? g[e * 64 + lane] : -INFINITY;
-                m = fmaxf(m, d[e]);
-            }
-            m = wave_max_all(m);
-            unsigned idx = 0x7fffffffu;
-#pragma unroll
-            for (int e = 0; e < EPL; ++e) {
-                const unsigned long long mk = __ballot(d[e] == m && inS[e]);
-                if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
-            }
-            cur = idx == 0x7fffffffu ? 0 : (int)idx;
-        }
-        if (hi_c <= lo_c) {                       // empty chunk (very short song)
-            if (lane == 0) a.entry[(size_t)song * C + chunk] = cur;
-            return;
-        }
-        cur = chase(top, hi_c, cur, false);       // warm-up: frames top .. hi_c, nothing written
-        if (lane == 0) a.entry[(size_t)song * C + chunk] = cur;   // state this chunk assumed at frame hi_c
-        chase(hi_c - 1, lo_c, cur, true);
-    } else {
-        int truth = -1;                           // verified state at frame hi_c of the chunk being checked
-        for (int c = C - 2; c >= 0; --c) {
-            const int lo_c = (int)((long long)Lf * c / C), hi_c = (int)((long long)Lf * (c + 1) / C);
-            if (truth < 0) truth = __builtin_amdgcn_readfirstlane(states[hi_c]);
-            const int assumed = __builtin_amdgcn_readfirstlane(a.entry[(size_t)song * C + c]);
-            if (hi_c > lo_c && assumed != truth) {
-                ++n_rep;
-                truth = chase(hi_c - 1, lo_c, truth, true);   // re-chase from the true state; ends at frame lo_c
-            } else {
-                truth = -1;                       // chunk c stands: its frame lo_c is already in `states`
-            }
-        }
-    }
-    if (lane == 0 && a.counters) {
-        int32_t* ct = a.counters + (size_t)song * kBtCounters;
-        if (n_tiles) atomicAdd(ct + kCtTiles, n_tiles);
-        if (n_miss) atomicAdd(ct + kCtMisses, n_miss);
-        if (n_full) atomicAdd(ct + kCtFullRows, n_full);
-        if (n_rep) atomicAdd(ct + kCtRepairs, n_rep);
-        if (n_repf) atomicAdd(ct + kCtRepairFrames, n_repf);
-    }
+    // (a unit of a packed decode: the entries behind it are the next song's -- nothing is written there)
+    const int n_rep = bt_run_chunks<MODE, EPL>(chase, [&](const int f) { return hist + (size_t)f * SD + a.col0; }, states,
+                                               a.entry + (size_t)song * C, MODE == 0 ? a.last_state[song] : 0, Tb, a.unit_states ? Tb : T,
+                                               chunk, C, a.warm, S, lane);
+    bt_flush_counters(a.counters, song, lane == 0, n_tiles, n_miss, n_full, 0, n_rep, n_repf);
 }
 
 static int sparse_kc(const BtArgs& a) { return (a.W + kMaxExtras + 1 + 63) / 64; }
@@ -386,40 +278,20 @@ template <int NWT, bool AFF, int KC, bool GT>
 static hipError_t launch_sparse_t(const BtArgs& a, hipStream_t st, int phases) {
     int nw = 16;
     while (nw > 4 && sparse_lds_bytes(a, nw, !GT) + 1024 > kLdsBytes) nw >>= 1;
-    const size_t lds = sparse_lds_bytes(a, nw, !GT);
-    const long long waves0 = (long long)a.B * a.chunks;
-    hipError_t e = hipSuccess;
-    if (phases & 1) {
-        hipLaunchKernelGGL((sparse_backtrace_kernel<NWT, AFF, 0, KC, GT>), dim3((int)((waves0 + nw - 1) / nw)), dim3(nw * 64), lds, st, a);
-        e = hipGetLastError();
-    }
-    if (e != hipSuccess || a.chunks <= 1 || !(phases & 2)) return e;
-    hipLaunchKernelGGL((sparse_backtrace_kernel<NWT, AFF, 1, KC, GT>), dim3((int)((a.B + nw - 1) / nw)), dim3(nw * 64), lds, st, a);
-    return hipGetLastError();
-}
-
-template <int NWT>
-static hipError_t launch_sparse_a(const BtArgs& a, hipStream_t st, int phases) {
-    const bool gt = !sparse_table_fits(a);
-    if (sparse_kc(a) == 1) {
-        if (gt) return a.lo_affine ? launch_sparse_t<NWT, true, 1, true>(a, st, phases) : launch_sparse_t<NWT, false, 1, true>(a, st, phases);
-        return a.lo_affine ? launch_sparse_t<NWT, true, 1, false>(a, st, phases) : launch_sparse_t<NWT, false, 1, false>(a, st, phases);
-    }
-    if (sparse_kc(a) == 2) {
-        if (gt) return a.lo_affine ? launch_sparse_t<NWT, true, 2, true>(a, st, phases) : launch_sparse_t<NWT, false, 2, true>(a, st, phases);
-        return a.lo_affine ? launch_sparse_t<NWT, true, 2, false>(a, st, phases) : launch_sparse_t<NWT, false, 2, false>(a, st, phases);
-    }
-    if (gt) return a.lo_affine ? launch_sparse_t<NWT, true, 3, true>(a, st, phases) : launch_sparse_t<NWT, false, 3, true>(a, st, phases);
-    return a.lo_affine ? launch_sparse_t<NWT, true, 3, false>(a, st, phases) : launch_sparse_t<NWT, false, 3, false>(a, st, phases);
+    return launch_two_pass(sparse_backtrace_kernel<NWT, AFF, 0, KC, GT>, sparse_backtrace_kernel<NWT, AFF, 1, KC, GT>,
+                           (long long)a.B * a.chunks, a.B, nw, sparse_lds_bytes(a, nw, !GT), st, a, phases);
 }
 
 hipError_t launch_backtrace_sparse(const BtArgs& a, hipStream_t st, int phases) {
-    const int nwt = (a.S + 63) / 64;
-    if (nwt <= 2) return launch_sparse_a<2>(a, st, phases);
-    if (nwt <= 4) return launch_sparse_a<4>(a, st, phases);
-    if (nwt <= 6) return launch_sparse_a<6>(a, st, phases);
-    if (nwt <= 8) return launch_sparse_a<8>(a, st, phases);
-    return launch_sparse_a<12>(a, st, phases);
+    return bt_dispatch_upto<2, 4, 6, 8, 12>((a.S + 63) / 64, [&](auto nwt) {
+        return bt_dispatch_upto<1, 2, 3>(sparse_kc(a), [&](auto kc) {
+            return bt_dispatch_bool(a.lo_affine != 0, [&](auto aff) {
+                return bt_dispatch_bool(!sparse_table_fits(a), [&](auto gt) {
+                    return launch_sparse_t<decltype(nwt)::value, decltype(aff)::value, decltype(kc)::value, decltype(gt)::value>(a, st, phases);
+                });
+            });
+        });
+    });
 }
 
 // more, shorter chunks than the whole-row kernels: the sparse kernel hides its fetch latency with waves, not with a

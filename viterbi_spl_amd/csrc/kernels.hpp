@@ -1,5 +1,6 @@
 // kernels.hpp -- launch interface between the C ABI (capi.hip) and the kernel files (dense, step, banded, wave, emission, activations, fused,
-// backtrace_rows / _sparse / _half / _lane .hip).
+// backtrace_rows / _sparse / _half / _lane .hip; those four share backtrace_common.hpp: the chunk scheme, the pieces of a decision and
+// the launch helpers).
 #pragma once
 #include <hip/hip_runtime.h>
 
