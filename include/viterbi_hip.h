@@ -29,7 +29,10 @@
  *   - the terminal log-likelihood delta_{T-1}[s_{T-1}] is returned as well
  *     (the unused `p` at dcnet/tf_viterbi_decoding.py:255).
  *
- * NaN inputs are outside the contract.  -inf entries are accepted.
+ * NaN inputs are outside the contract.  -inf entries are accepted.  A candidate of -inf never beats the running best
+ * (the comparison is strict), so a frame whose delta row is all -inf resolves every back-pointer to state 0, and a song
+ * that reaches such a frame returns state 0 from that frame on and log-likelihood -inf -- what the oracle
+ * (oracle/viterbi_oracle.c) and np.argmax do.
  */
 #ifndef VITERBI_HIP_H_
 #define VITERBI_HIP_H_

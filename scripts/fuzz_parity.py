@@ -1,5 +1,5 @@
 """Randomised parity run (test infrastructure; run on the GPU box): random state counts, band half-widths, matrix families,
-batch shapes, ragged lengths, emission kinds and storage types; every kernel family the plan allows and both back-trace forms, the wave
+batch shapes, ragged lengths, emission kinds ("edges": -inf entries, the float16 edge values, dead songs) and storage types; every kernel family the plan allows and both back-trace forms, the wave
 form's half history, the checkpointed decode (wave-form plans and the workgroup-form plans of the 722-state grids, random segment
 lengths), the lane form of the back-trace (chunk counts up to 256) and the packed decode against the C
 restatement in oracle/.  argv: seconds to run (default 240), seed (default 1)."""
@@ -20,6 +20,26 @@ rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
 dev = torch.device("cuda:0")
 GOLDEN_722 = ["jdc722", "jdc721", "imm722w", "durrieu722", "durrieu721"]      # the reference's 722-state grids (tests/golden/params.npz)
 GEN = {"peaks": synth.emissions_peaks, "dense": synth.emissions_dense, "ties": synth.emissions_ties, "scaled": synth.emissions_scaled}
+# +0, -0, +-2^-24, +-largest subnormal, +-2^-14, -65504, -inf (tests/common.py FP16_EDGE_BITS)
+FP16_EDGE_BITS = np.asarray([0x0000, 0x8000, 0x0001, 0x8001, 0x03FF, 0x83FF, 0x0400, 0x8400, 0xFBFF, 0xFC00], np.uint16)
+
+
+def emissions_edges(B, T, S, f16):
+    """Emission kind "edges": a coarse grid sprinkled with -inf (float16 storage: with the float16 edge values), and with
+    probability 1/4 one song killed by a whole -inf frame at a random position.  A dead song decodes to state 0 from that frame
+    on and to log-likelihood -inf."""
+    e = (-(rng.integers(0, 96, (B, T, S)) / 8)).astype(np.float16)
+    if f16:
+        u = e.view(np.uint16).copy()
+        pick = rng.random((B, T, S)) < 0.3
+        u[pick] = FP16_EDGE_BITS[rng.integers(0, len(FP16_EDGE_BITS), int(pick.sum()))]
+        e = u.view(np.float16)
+    else:
+        e = e.astype(np.float32)
+        e[rng.random((B, T, S)) < 0.2] = -np.inf
+    if rng.random() < 0.25:
+        e[int(rng.integers(B)), int(rng.integers(T)), :] = -np.inf
+    return torch.from_numpy(np.ascontiguousarray(e)).to(dev)
 
 
 def random_matrix():
@@ -70,9 +90,12 @@ while time.time() - t0 < budget:
     for _ in range(3):
         B = int(rng.choice([1, 2, 3, 5, 9, 17]))
         T = int(rng.choice([1, 2, 3, 17, 64, 65, 129, 300, 601, 1100]))
-        kind = str(rng.choice(list(GEN) if S >= 8 else ["dense", "ties"]))
+        kind = str(rng.choice(list(GEN) + ["edges"] if S >= 8 else ["dense", "ties", "edges"]))
         f16 = bool(rng.integers(2))
-        E = GEN[kind](B, T, S, seed=int(rng.integers(1 << 20)), device=dev, dtype=torch.float16 if f16 else torch.float32)
+        if kind == "edges":
+            E = emissions_edges(B, T, S, f16)
+        else:
+            E = GEN[kind](B, T, S, seed=int(rng.integers(1 << 20)), device=dev, dtype=torch.float16 if f16 else torch.float32)
         lens_np = np.where(rng.random(B) < 0.5, T, rng.integers(1, T + 1, B)).astype(np.int64)
         lens = torch.from_numpy(lens_np).to(dev)
         ref_s, ref_l = vo.decode_c(la, lp, E.float().cpu().numpy(), lengths=lens_np)
@@ -126,7 +149,7 @@ while time.time() - t0 < budget:
             n_runs += 1
             st = st.cpu().numpy()
             okp = all(np.array_equal(st[b, :lens_np[b]], ref_s[b, :lens_np[b]]) for b in range(B))
-            okl = np.array_equal(ll.cpu().numpy(), ref_l)
+            okl = np.array_equal(ll.cpu().numpy(), ref_l) and not np.isnan(ll.cpu().numpy()).any()
             if not (okp and okl):
                 fails.append((name, dec.info, B, T, kind, f16, algo, btf, chunks, warm, okp, okl))
                 print("FAIL", name, B, T, kind, f16, algo, btf, chunks, warm, "paths", okp, "loglik", okl, flush=True)
