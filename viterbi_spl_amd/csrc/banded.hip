@@ -319,17 +319,18 @@ __global__ void __launch_bounds__((NWT + (DW ? 3 : 2)) * 64) banded_forward_kern
 // ---------------------------------------------------------------------------------------
 inline constexpr int kSplitFullWaves = 4, kSplitHalfWaves = 4;
 inline constexpr int kSplitStates = 64 * kSplitFullWaves + 32 * kSplitHalfWaves;   // 384 target slots
+using FloorSplitLds = FloorLds<32, kSplitStates / 64>;   // the six-wave kernel's LDS, byte for byte
 
 template <int NXT, int PF, typename ET, bool WPR = false>
 __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) banded_floor_split_forward_kernel(FwdArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int W = 32;
     constexpr int NWF = kSplitFullWaves, NW = kSplitFullWaves + kSplitHalfWaves;
-    constexpr int DC = kSplitStates + 16;         // copy stride: from the state slots, not from the thread count
-    constexpr int BUF = 4 * DC;                   // floats per delta buffer
-    float* dls = reinterpret_cast<float*>(smem);  // [2][4][DC]
-    float* fmg = dls + 2 * BUF;                   // [kFmGroups][kFmGroupFloats] frame-maximum slot groups
-    VI* tot = reinterpret_cast<VI*>(fmg + kFmGroups * kFmGroupFloats);
+    using L = FloorSplitLds;                      // the copy stride comes from the state slots, not from the thread count
+    constexpr int DC = L::DC, BUF = L::BUF;
+    float* dls = reinterpret_cast<float*>(smem) + L::dls;
+    float* fmg = dls + L::fmg;
+    VI* tot = reinterpret_cast<VI*>(dls + L::tot);
     const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
     constexpr bool GEN = NXT < 0;
     constexpr int NXL = GEN ? kMaxExtras : NXT;
@@ -370,7 +371,7 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
     const float* rp = dls + 4 + (lov & 3) * DC + (lov & ~3) + 16 * hh;    // (half of the) window in the copy that aligns it
     float* fmp = fmg + fm_slot(lane);
 
-    for (int k = tid; k < 2 * BUF + kFmGroups * kFmGroupFloats; k += NW * 64) dls[k] = -INFINITY;
+    for (int k = tid; k < L::reset; k += NW * 64) dls[k] = -INFINITY;
     __syncthreads();
 
 #ifdef VIT_TIMING_HOOKS
@@ -518,17 +519,32 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
 // max3 per target.  Everything else is as in banded_floor_forward_kernel, except that M is still published through the
 // six-step wave scan and the history / emission rows are addressed with 64-bit per-lane pointers.
 // ---------------------------------------------------------------------------------------
+// LDS of the pair kernel, in floats: what the kernel carves and what its launcher asks for
+template <int NPW>
+struct FloorPairLds {
+    static constexpr int NP = NPW * 128;                 // padded state count
+    static constexpr int DC = NP + 16;                   // copy stride (see banded_forward_kernel)
+    static constexpr int BUF = 4 * DC;                   // floats per delta buffer
+    static constexpr int NWM = (NPW + 3) / 4 * 4;        // wave maxima per buffer, whole float4s (slots >= NPW hold -inf)
+    static constexpr int dls = 0;                        // [2][4][DC]
+    static constexpr int wm = dls + 2 * BUF;             // [2][NWM]
+    static constexpr int reset = wm + 2 * NWM;           // floats that go to -inf before the song: everything up to here
+    static constexpr int dump = reset;                   // [64 + NWM]
+    static constexpr int tot = dump + 64 + NWM;          // [16] VI
+    static constexpr int end = tot + 16 * (int)(sizeof(VI) / sizeof(float));
+    static_assert(sizeof(float) * end <= kLdsBytes, "one workgroup's LDS");
+    static constexpr size_t bytes() { return sizeof(float) * end; }
+};
+
 template <int W, int NPW, int NXT, int PF, typename ET>
 __global__ void __launch_bounds__(NPW * 64) banded_floor_pair_forward_kernel(FwdArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int NP = NPW * 128;                 // padded state count
-    constexpr int DC = NP + 16;                   // copy stride (see banded_forward_kernel)
-    constexpr int BUF = 4 * DC;                   // floats per delta buffer
-    constexpr int NWM = (NPW + 3) / 4 * 4;        // wave maxima per buffer, whole float4s (slots >= NPW hold -inf)
-    float* dls = reinterpret_cast<float*>(smem);  // [2][4][DC]
-    float* wm = dls + 2 * BUF;                    // [2][NWM]
-    float* dump = wm + 2 * NWM;                   // [64 + NWM]
-    VI* tot = reinterpret_cast<VI*>(dump + 64 + NWM);
+    using L = FloorPairLds<NPW>;
+    constexpr int DC = L::DC, BUF = L::BUF, NWM = L::NWM;
+    float* dls = reinterpret_cast<float*>(smem) + L::dls;
+    float* wm = dls + L::wm;
+    float* dump = dls + L::dump;
+    VI* tot = reinterpret_cast<VI*>(dls + L::tot);
     const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
     constexpr bool GEN = NXT < 0;
     constexpr int NXL = GEN ? kMaxExtras : NXT;
@@ -583,7 +599,7 @@ __global__ void __launch_bounds__(NPW * 64) banded_floor_pair_forward_kernel(Fwd
     float* wp = dls + 4 + sh + j0;                                        // slot 0 of copy 0 (copy c: + c*DC - c), slot 1 follows
     float* wmp = lane == 63 ? wm + wv : dump + lane;
 
-    for (int k = tid; k < 2 * BUF + 2 * NWM; k += NPW * 64) dls[k] = -INFINITY;
+    for (int k = tid; k < L::reset; k += NPW * 64) dls[k] = -INFINITY;
     __syncthreads();
 
     auto produce = [&](const f32x2 dn, const int WB) {
@@ -727,8 +743,7 @@ __global__ void scan_selftest_kernel(const float* __restrict__ vals, int mode, f
 // floor-max forms (plan.floor_ok; idle slot S stores the frame maximum: needs S < 64 * NWT)
 template <int W, int NWT, typename ET>
 static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
-    constexpr int NP = NWT * 64;
-    constexpr int PF = W <= 32 ? 12 : 4;   // emission rows in flight: a row is requested PF frames (0.34 us each) before its use; under the overlapped
+    constexpr int PF = floor_pf<W>();      // emission rows in flight: a row is requested PF frames (0.34 us each) before its use; under the overlapped
                                             // back-trace 4 left ~2 % on the table (B = 128: 4 -> 10.35, 8 -> 10.20, 12 -> 10.12, 16 -> 10.14 ms per forward pass)
     // Up to two songs per CU the one-target-per-lane kernel is (slightly) faster; beyond that the two-targets-per-lane
     // kernel wins because it moves half the window bytes through LDS (B = 512: 14.5 vs 15.5 ms).
@@ -739,9 +754,9 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
     // (S = 361: 10.28 -> 15.67 ms, S = 321: 10.27 -> 15.51 ms: its loops convert the 16-bit emission right behind the
     // prefetch load and wait for it every frame), so the default leaves those to the one-target kernel (profiles/r06_logs/floor_split_ab.log).
     if constexpr (W == 32 && NWT == 6) {
-        static_assert(kSplitStates == NP, "the split kernel keeps the six-wave kernel's LDS and history layout");
+        static_assert(kSplitStates == NWT * 64, "the split kernel keeps the six-wave kernel's LDS and history layout");
         if (a.fwd_form == 6 || (a.fwd_form == 0 && a.B <= 256 && std::is_same_v<ET, float>)) {
-            const size_t ldss = sizeof(float) * (8 * (kSplitStates + 16) + kFmGroups * kFmGroupFloats) + sizeof(VI) * 16;
+            constexpr size_t ldss = FloorSplitLds::bytes();
             constexpr int NWS = kSplitFullWaves + kSplitHalfWaves;
 #ifdef VIT_TIMING_HOOKS
             if ((a.debug & 64) && a.n_extras == 1)
@@ -761,8 +776,7 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
         if (pair) {
             constexpr int NPW = (NWT + 1) / 2;
             constexpr int PFP = 4;             // (two workgroups share a CU here and cover each other's waits: 12 rows in flight measured 9 % slower)
-            constexpr int NWMP = (NPW + 3) / 4 * 4;
-            const size_t ldsp = sizeof(float) * (8 * (NPW * 128 + 16) + 2 * NWMP + 64 + NWMP) + sizeof(VI) * 16;
+            constexpr size_t ldsp = FloorPairLds<NPW>::bytes();
             if (W == 32 && a.n_extras == 1)
                 hipLaunchKernelGGL((banded_floor_pair_forward_kernel<W, NPW, (W == 32 ? 1 : -1), PFP, ET>), dim3((int)a.B), dim3(NPW * 64), ldsp, st, a);
             else
@@ -770,109 +784,19 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
             return hipGetLastError();
         }
     }
-    const size_t ldsf = sizeof(float) * (8 * (NP + 16) + kFmGroups * kFmGroupFloats) + sizeof(VI) * 16 +
-                        ((W == 128 && NWT > 8) ? sizeof(f32x4) * 8 * NP : 0);
+    constexpr size_t ldsf = FloorLds<W, NWT>::bytes();
 #ifdef VIT_TIMING_HOOKS
     if constexpr (W == 32 && NWT == 6) {
         if ((a.debug & 64) && a.n_extras == 1) {
-            hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, 1, PF, ET, true>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
+            hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, 1, PF, ET, WgVariant::Plain, true>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
             return hipGetLastError();
         }
     }
 #endif
-    if ((W == 32 || W >= 84) && a.n_extras == 1)   // the reference's matrices: band + unvoiced column (compile-time extras count)
-        hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, ((W == 32 || W >= 84) ? 1 : -1), PF, ET>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
-    else
-        hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, -1, PF, ET>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
-    return hipGetLastError();
-}
-
-// The packed variant of the one-target floor kernel: one workgroup per slot (vit_decode_packed).  NXT and PF as above.  With
-// `per_cu` the launch is replaced by the occupancy query of that instantiation at its dynamic LDS size.
-template <int W, int NWT, typename ET>
-static hipError_t packed_floor_t(const FwdArgs& a, hipStream_t st, int* per_cu) {
-    constexpr int NP = NWT * 64;
-    constexpr int PF = W <= 32 ? 12 : 4;
-    const size_t ldsf = sizeof(float) * (8 * (NP + 16) + kFmGroups * kFmGroupFloats) + sizeof(VI) * 16 +
-                        ((W == 128 && NWT > 8) ? sizeof(f32x4) * 10 * NP : 0);      // (88 register-resident weights, 40 in LDS)
-    auto go = [&](auto kern) -> hipError_t {
-        if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, NWT * 64, ldsf);
-        hipLaunchKernelGGL(kern, dim3(a.n_slots), dim3(NWT * 64), ldsf, st, a);
+    return with_nxt<W>(a.n_extras, [&](auto nxt) {
+        hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, decltype(nxt)::value, PF, ET>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
         return hipGetLastError();
-    };
-    if ((W == 32 || W >= 84) && a.n_extras == 1)
-        return go(banded_floor_forward_kernel<W, NWT, ((W == 32 || W >= 84) ? 1 : -1), PF, ET, false, true>);
-    return go(banded_floor_forward_kernel<W, NWT, -1, PF, ET, false, true>);
-}
-
-// The checkpoint / resume variant of the one-target floor kernel (vit_decode_checkpointed): one workgroup per song.
-template <int W, int NWT, typename ET>
-static hipError_t ckpt_floor_t(const FwdArgs& a, hipStream_t st) {
-    constexpr int NP = NWT * 64;
-    constexpr int PF = W <= 32 ? 12 : 4;
-    const size_t ldsf = sizeof(float) * (8 * (NP + 16) + kFmGroups * kFmGroupFloats) + sizeof(VI) * 16 +
-                        ((W == 128 && NWT > 8) ? sizeof(f32x4) * 10 * NP : 0);      // (88 register-resident weights, 40 in LDS)
-    if ((W == 32 || W >= 84) && a.n_extras == 1)
-        hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, ((W == 32 || W >= 84) ? 1 : -1), PF, ET, false, false, true>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
-    else
-        hipLaunchKernelGGL((banded_floor_forward_kernel<W, NWT, -1, PF, ET, false, false, true>), dim3((int)a.B), dim3(NWT * 64), ldsf, st, a);
-    return hipGetLastError();
-}
-
-template <int W, typename ET>
-static hipError_t ckpt_floor_w(const FwdArgs& a, hipStream_t st) {
-    if (!floor_ckpt_applies(a.S, a.W, a.floor_ok != 0, a.n_dense)) return hipErrorInvalidConfiguration;
-    switch (banded_waves_for(a.S)) {
-        case 2: if constexpr (floor_ckpt_pair(W, 2)) return ckpt_floor_t<W, 2, ET>(a, st); break;
-        case 4: if constexpr (floor_ckpt_pair(W, 4)) return ckpt_floor_t<W, 4, ET>(a, st); break;
-        case 6: if constexpr (floor_ckpt_pair(W, 6)) return ckpt_floor_t<W, 6, ET>(a, st); break;
-        case 8: if constexpr (floor_ckpt_pair(W, 8)) return ckpt_floor_t<W, 8, ET>(a, st); break;
-        case 12: if constexpr (floor_ckpt_pair(W, 12)) return ckpt_floor_t<W, 12, ET>(a, st); break;
-        default: break;
-    }
-    return hipErrorInvalidConfiguration;
-}
-
-template <typename ET>
-static hipError_t ckpt_floor_e(const FwdArgs& a, hipStream_t st) {
-    static_assert(sizeof(kBandedWidths) / sizeof(int) == 6, "one case per instantiated window width");
-    switch (a.W) {
-        case 16: return ckpt_floor_w<16, ET>(a, st);
-        case 32: return ckpt_floor_w<32, ET>(a, st);
-        case 64: return ckpt_floor_w<64, ET>(a, st);
-        case 84: return ckpt_floor_w<84, ET>(a, st);
-        case 96: return ckpt_floor_w<96, ET>(a, st);
-        case 128: return ckpt_floor_w<128, ET>(a, st);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-
-template <int W, typename ET>
-static hipError_t packed_floor_w(const FwdArgs& a, hipStream_t st, int* per_cu) {
-    const int nwt = banded_waves_for(a.S);
-    if (!floor_packed_applies(a.S, a.W, a.floor_ok != 0, a.n_dense)) return hipErrorInvalidConfiguration;
-    switch (nwt) {
-        case 2: return packed_floor_t<W, 2, ET>(a, st, per_cu);
-        case 4: return packed_floor_t<W, 4, ET>(a, st, per_cu);
-        case 6: return packed_floor_t<W, 6, ET>(a, st, per_cu);
-        case 8: return packed_floor_t<W, 8, ET>(a, st, per_cu);
-        case 12: return packed_floor_t<W, 12, ET>(a, st, per_cu);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-
-template <typename ET>
-static hipError_t packed_floor_e(const FwdArgs& a, hipStream_t st, int* per_cu) {
-    static_assert(sizeof(kBandedWidths) / sizeof(int) == 6, "one case per instantiated window width");
-    switch (a.W) {
-        case 16: return packed_floor_w<16, ET>(a, st, per_cu);
-        case 32: return packed_floor_w<32, ET>(a, st, per_cu);
-        case 64: return packed_floor_w<64, ET>(a, st, per_cu);
-        case 84: return packed_floor_w<84, ET>(a, st, per_cu);
-        case 96: return packed_floor_w<96, ET>(a, st, per_cu);
-        case 128: return packed_floor_w<128, ET>(a, st, per_cu);
-        default: return hipErrorInvalidConfiguration;
-    }
+    });
 }
 
 // general (scan) form
@@ -910,49 +834,32 @@ static hipError_t launch_banded_t(const FwdArgs& a, hipStream_t st) {
     return hipErrorInvalidConfiguration;
 }
 
-template <int W, typename ET>
-static hipError_t launch_banded_w(const FwdArgs& a, hipStream_t st) {
-    switch (banded_waves_for(a.S)) {
-        case 2: return launch_banded_t<W, 2, ET>(a, st);
-        case 4: return launch_banded_t<W, 4, ET>(a, st);
-        case 6: return launch_banded_t<W, 6, ET>(a, st);
-        case 8: return launch_banded_t<W, 8, ET>(a, st);
-        case 12: return launch_banded_t<W, 12, ET>(a, st);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-
-template <typename ET>
-static hipError_t launch_banded_e(const FwdArgs& a, hipStream_t st) {
-    static_assert(sizeof(kBandedWidths) / sizeof(int) == 6, "one case per instantiated window width");
-    switch (a.W) {
-        case 16: return launch_banded_w<16, ET>(a, st);
-        case 32: return launch_banded_w<32, ET>(a, st);
-        case 64: return launch_banded_w<64, ET>(a, st);
-        case 84: return launch_banded_w<84, ET>(a, st);
-        case 96: return launch_banded_w<96, ET>(a, st);
-        case 128: return launch_banded_w<128, ET>(a, st);
-        default: return hipErrorInvalidConfiguration;
-    }
-}
-
 hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st) {
-    return f16 ? launch_banded_e<__half>(a, st) : launch_banded_e<float>(a, st);
+    auto go = [&](auto et) {
+        using ET = decltype(et);
+        return dispatch_width(a.W, [&](auto w) {
+            return dispatch_waves(a.S, [&](auto n) { return launch_banded_t<decltype(w)::value, decltype(n)::value, ET>(a, st); });
+        });
+    };
+    return f16 ? go(__half{}) : go(float{});
 }
 
-hipError_t launch_banded_packed(const FwdArgs& a, bool f16, hipStream_t st) {
-    if (!a.offsets || !a.slot_begin || !a.slot_songs || a.n_slots < 1) return hipErrorInvalidValue;
-    return f16 ? packed_floor_e<__half>(a, st, nullptr) : packed_floor_e<float>(a, st, nullptr);
+// the variants of the one-target floor kernel
+static hipError_t floor_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st, int* per_cu) {
+    switch (v) {
+        case WgVariant::Packed: return f16 ? floor_variant_e<__half, WgVariant::Packed>(a, st, per_cu) : floor_variant_e<float, WgVariant::Packed>(a, st, per_cu);
+        case WgVariant::Ckpt: return f16 ? floor_variant_e<__half, WgVariant::Ckpt>(a, st, per_cu) : floor_variant_e<float, WgVariant::Ckpt>(a, st, per_cu);
+        case WgVariant::PackedCkpt: return floor_pckpt(a, f16, st, per_cu);
+        default: return hipErrorInvalidValue;   // (Plain is launch_banded's)
+    }
 }
 
-hipError_t launch_banded_ckpt(const FwdArgs& a, bool f16, hipStream_t st) {
-    if (a.offsets || a.hist_rows < 1 || (a.t_begin > 0 && !a.init_rows) || (a.ckpt_every > 0 && a.t_begin > 0)) return hipErrorInvalidValue;
-    return f16 ? ckpt_floor_e<__half>(a, st) : ckpt_floor_e<float>(a, st);
+hipError_t launch_banded_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st) {
+    if (!wg_variant_args_ok(a, v, 2)) return hipErrorInvalidValue;
+    return floor_variant(a, v, f16, st, nullptr);
 }
 
-hipError_t banded_packed_resident(const FwdArgs& a, bool f16, int* per_cu) {
-    return f16 ? packed_floor_e<__half>(a, nullptr, per_cu) : packed_floor_e<float>(a, nullptr, per_cu);
-}
+hipError_t banded_variant_resident(const FwdArgs& a, WgVariant v, bool f16, int* per_cu) { return floor_variant(a, v, f16, nullptr, per_cu); }
 
 hipError_t launch_scan_selftest(const float* vals, int n_waves, int mode, float* out_v, int32_t* out_i,
                                 hipStream_t st) {

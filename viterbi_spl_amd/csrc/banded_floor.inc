@@ -1,6 +1,7 @@
-// banded_floor.inc -- the one-target floor-max forward kernel (banded_floor_forward_kernel) and its device helpers, shared by the
-// translation units that instantiate it: banded.hip (plain, packed and checkpoint / resume variants) and banded_pc.hip (the
-// packed-checkpoint variant).  Included inside namespace vit, after device_common.hpp.  The scheme is described in banded.hip.
+// banded_floor.inc -- the one-target floor-max forward kernel (banded_floor_forward_kernel), its device helpers, its LDS layout and the
+// launch of its variants, shared by the translation units that instantiate it: banded.hip (plain, packed and checkpoint / resume
+// variants) and banded_pc.hip (the packed-checkpoint variant).  Included inside namespace vit, after device_common.hpp.  The scheme is
+// described in banded.hip.
 // Global row access with a wave-uniform row base: a raw buffer descriptor (stride 0, no range limit) built on the SALU and
 // the lane's 32-bit byte offset -- no 64-bit per-lane address arithmetic on the VALU.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* row) {
@@ -69,13 +70,34 @@ struct WaveProbe {
 };
 #endif
 
-// PK = true is the packed variant (vit_decode_packed, plans without the wave form): the workgroup is a SLOT and decodes the
+// LDS of the one-target floor kernel (and, with the copy stride of its 384 state slots, of the split kernel), in floats from the start
+// of the dynamic segment: what the kernel carves and what its launchers ask for.
+// W = 128 with twelve waves (S > 512) leaves 168 registers per thread: the last W - WR window weights then live in LDS
+// ([(W - WR) / 4][NP] float4-interleaved, read with conflict-free 16-byte reads next to the delta window)
+// (variants: WR = 88 -- the song loop / the row selection keep a few more values alive, and 168 registers leave nothing to spill into)
+template <int W, int NWT, WgVariant V = WgVariant::Plain>
+struct FloorLds {
+    static constexpr int NP = NWT * 64;
+    static constexpr int DC = NP + 16;                   // copy stride (see banded_forward_kernel)
+    static constexpr int BUF = 4 * DC;                   // floats per delta buffer
+    static constexpr int WR = (W == 128 && NWT > 8) ? (V != WgVariant::Plain ? 88 : 96) : W;   // register-resident window weights
+    static constexpr int dls = 0;                        // [2][4][DC] delta buffers
+    static constexpr int fmg = dls + 2 * BUF;            // [kFmGroups][kFmGroupFloats] frame-maximum slot groups
+    static constexpr int reset = fmg + kFmGroups * kFmGroupFloats;   // floats that go to -inf before a song: everything up to here
+    static constexpr int tot = reset;                    // [16] VI: terminal argmax scratch
+    static constexpr int awl = tot + 16 * (int)(sizeof(VI) / sizeof(float));   // [(W - WR) / 4][NP] f32x4: window weights WR .. W - 1
+    static constexpr int end = awl + (W - WR) / 4 * 4 * NP;
+    static_assert(sizeof(float) * end <= kLdsBytes, "one workgroup's LDS");
+    static constexpr size_t bytes() { return sizeof(float) * end; }
+};
+
+// V = Packed is the packed variant (vit_decode_packed, plans without the wave form): the workgroup is a SLOT and decodes the
 // songs slot_songs[slot_begin[w] .. slot_begin[w+1]) back to back, as a wave does in wave.hip.  Emission and history rows of
 // a song start at row offsets[song] of the packed buffers (row strides S and SD; T plays no role).  The per-lane tables and
 // the LDS-resident weights are loaded once; between two songs both delta buffers and every slot group go back to -inf behind
 // a barrier.  The history layout is the unpacked one (the frame maximum of row t in pad column S of row t), so a song
-// writes its own rows only.  PK = false compiles to the code it was before the parameter existed.
-// CK = true is the checkpoint / resume variant (vit_decode_checkpointed, plans without the wave form), driven by the FwdArgs fields
+// writes its own rows only.
+// V = Ckpt is the checkpoint / resume variant (vit_decode_checkpointed, plans without the wave form), driven by the FwdArgs fields
 // the wave form uses:
 //   pass 1 (ckpt_every = K > 0): every frame of the song; frame mK - 1 goes to row m - 1 of the song's hist_rows rows, every other
 //     frame to its last row (scratch).  The store stays unconditional, only its row base is selected (on the SALU).  The frame maximum
@@ -86,37 +108,31 @@ struct WaveProbe {
 //     log_pi + e_0; row t is stored at t - t_begin.  Lane S stores M of frame t - 1 into row t - 1 - t_begin: for the first frame
 //     that is the row IN FRONT of a.hist, which the caller must own (the segment buffer starts one row before a.hist).  A workgroup
 //     whose song ended before t_begin leaves without writing; the terminal state is pass 1's business.
-// CK = false compiles to the code it was before the parameter existed.
-// PC = true is the packed-checkpoint variant (vit_decode_packed_bounded, plans without the wave form; instantiated in banded_pc.hip):
-// the slot walk of PK joined with the stores of CK, in two modes told apart by a.unit_song (uniform over the launch):
-//   pass 1 (unit_song null): the workgroup is a slot and walks its songs as in PK; of song b only the rows in front of its segments
+// V = PackedCkpt is the packed-checkpoint variant (vit_decode_packed_bounded, plans without the wave form; instantiated in banded_pc.hip):
+// the slot walk of Packed joined with the stores of Ckpt, in two modes told apart by a.unit_song (uniform over the launch):
+//   pass 1 (unit_song null): the workgroup is a slot and walks its songs as in Packed; of song b only the rows in front of its segments
 //     1 .. n_b - 1 are kept (frames t with (t + 1) % K == 0 and t + 1 < T_b, K = ckpt_every), at rows ckpt_base[b] .. of a.hist; every
-//     other store goes to the slot's scratch row hist_rows + slot.  Stores, lane S and the frame maximum as in CK's pass 1; the
+//     other store goes to the slot's scratch row hist_rows + slot.  Stores, lane S and the frame maximum as in Ckpt's pass 1; the
 //     terminal state and the log-likelihood are written per song.
-//   unit (unit_song set): CK's segment with the song, the segment and the rows taken per workgroup: workgroup u runs frames
+//   unit (unit_song set): Ckpt's segment with the song, the segment and the rows taken per workgroup: workgroup u runs frames
 //     unit_seg[u] * K .. of song unit_song[u] (emission rows at offsets[song]) from row ckpt_base[song] + segment - 1 of init_rows
 //     (segment 0: from the prior) into rows u * hist_rows .. of a.hist, one frame past the segment where the song goes on; the row in
 //     front of those rows takes the first frame's frame-maximum store (the caller passes a.hist one row into the unit's K + 2 rows).
-// PC = false compiles to the code it was before the parameter existed (PKx / CKx below are then PK / CK).
-template <int W, int NWT, int NXT, int PF, typename ET, bool WPR = false, bool PK = false, bool CK = false, bool PC = false>
+// V = Plain compiles to the code it was before the variants existed.  (PK / CK / PC below: V is that variant; PKx / CKx: what the
+// packed-checkpoint variant shares with the packed and with the checkpoint / resume variant.)
+template <int W, int NWT, int NXT, int PF, typename ET, WgVariant V = WgVariant::Plain, bool WPR = false>
 __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs a) {
-    static_assert(!(PK && WPR), "the per-wave probe exists for the unpacked kernel only");
-    static_assert(!(CK && (PK || WPR)), "the checkpoint / resume variant is a variant of the plain unpacked kernel");
-    static_assert(!(PC && (PK || CK || WPR)), "the packed-checkpoint variant is a variant of its own");
+    static_assert(!WPR || V == WgVariant::Plain, "the per-wave probe exists for the plain kernel only");
+    using L = FloorLds<W, NWT, V>;
+    constexpr bool PK = V == WgVariant::Packed, CK = V == WgVariant::Ckpt, PC = V == WgVariant::PackedCkpt;
     constexpr bool PKx = PK || PC;                // the song loop and its per-song preamble
     constexpr bool CKx = CK || PC;                // the row selection of the stores, the resumed first frame
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int NP = NWT * 64;
-    constexpr int DC = NP + 16;                   // copy stride (see banded_forward_kernel)
-    constexpr int BUF = 4 * DC;                   // floats per delta buffer
-    float* dls = reinterpret_cast<float*>(smem);  // [2][4][DC]
-    float* fmg = dls + 2 * BUF;                   // [kFmGroups][kFmGroupFloats] frame-maximum slot groups
-    VI* tot = reinterpret_cast<VI*>(fmg + kFmGroups * kFmGroupFloats);
-    // W = 128 with twelve waves (S > 512) leaves 168 registers per thread: the last 32 window weights then live in LDS
-    // ([8][NP] float4-interleaved, read with conflict-free 16-byte reads next to the delta window)
-    // (PK, CK: 88 -- the song loop / the row selection keep a few more values alive, and 168 registers leave nothing to spill into)
-    constexpr int WR = (W == 128 && NWT > 8) ? ((PK || CK || PC) ? 88 : 96) : W;     // register-resident window weights
-    f32x4* awl = reinterpret_cast<f32x4*>(tot + 16);       // [(W - WR) / 4][NP]
+    constexpr int NP = L::NP, DC = L::DC, BUF = L::BUF, WR = L::WR;
+    float* dls = reinterpret_cast<float*>(smem) + L::dls;
+    float* fmg = dls + L::fmg;
+    VI* tot = reinterpret_cast<VI*>(dls + L::tot);
+    f32x4* awl = reinterpret_cast<f32x4*>(dls + L::awl);
     const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
     constexpr bool GEN = NXT < 0;
     constexpr int NXL = GEN ? kMaxExtras : NXT;
@@ -125,69 +141,11 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // the song being decoded: the workgroup's own, or (PK) the slot's songs one after the other
-    int song = blockIdx.x;
-    int Tb = PKx ? 1 : song_length(a.lengths, song, T);
-    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PKx ? (size_t)0 : (size_t)song * T * S);
-    float* __restrict__ hist = a.hist + (PKx ? (size_t)0 : (CK ? (size_t)song * (size_t)a.hist_rows * SD : (size_t)song * T * SD));
-    int si = 0, si_end = 1;                                               // (PK) position in slot_songs, end of the slot's list
-    auto take_song = [&]() {                                              // (PK) wave-uniform: scalar loads
-        song = a.slot_songs[si];
-        const long long r0 = a.offsets[song];
-        Tb = (int)(a.offsets[song + 1] - r0);
-        E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
-        hist = a.hist + (size_t)r0 * SD;
-    };
-    if constexpr (PK) {
-        si = a.slot_begin[blockIdx.x];
-        si_end = a.slot_begin[blockIdx.x + 1];
-        if (si >= si_end) return;                                         // an empty slot (the host makes none)
-        take_song();
-    }
-    // (CK) first frame of this launch, first frame the loop computes, pass 1's segment length and its row bookkeeping (all wave-uniform)
-    // (PC: t0 and t1 belong to the unit; ck_every is K in pass 1 and 0 in a unit launch; the scratch row is the slot's)
-    [[maybe_unused]] const bool pc_unit = PC && a.unit_song != nullptr;
-    [[maybe_unused]] int t0 = CK ? a.t_begin : 0;
-    [[maybe_unused]] int t1 = CK && t0 > 0 ? t0 : 1;
-    [[maybe_unused]] const int ck_every = CK ? a.ckpt_every : (PC && !pc_unit ? a.ckpt_every : 0);
-    [[maybe_unused]] const int ck_scratch = CK ? (int)a.hist_rows - 1 : (PC ? (int)a.hist_rows + (int)blockIdx.x : 0);
-    [[maybe_unused]] int ck_next = ck_every - 1, ck_row = 0;              // the next frame that is a checkpoint, and its row
-    [[maybe_unused]] const float* __restrict__ pc_init = nullptr;         // (PC, unit) the checkpoint row in front of the unit's segment
-    // (PC) pass 1: the next song of the slot, its emission rows and its first checkpoint row (a.hist is the checkpoint area)
-    auto take_song_pc = [&]() {
-        song = a.slot_songs[si];
-        const long long r0 = a.offsets[song];
-        Tb = (int)(a.offsets[song + 1] - r0);
-        E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
-        ck_next = ck_every - 1;
-        ck_row = (int)a.ckpt_base[song];
-    };
-    if constexpr (PC) {
-        hist = a.hist;
-        if (pc_unit) {                                                    // one unit: its song, segment, frames and rows
-            song = a.unit_song[blockIdx.x];
-            const int useg = a.unit_seg[blockIdx.x];
-            const long long r0 = a.offsets[song];
-            const int Ts = (int)(a.offsets[song + 1] - r0);
-            t0 = useg * a.ckpt_every;
-            t1 = t0 > 0 ? t0 : 1;
-            Tb = t0 + a.ckpt_every >= Ts ? Ts : t0 + a.ckpt_every + 1;    // one frame past the segment where the song goes on
-            E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
-            hist = a.hist + (size_t)blockIdx.x * (size_t)a.hist_rows * SD;
-            pc_init = a.init_rows + (size_t)(a.ckpt_base[song] + useg - 1) * SD;
-            if (Tb <= t0) return;                                         // (the host lists no such unit)
-        } else {
-            si = a.slot_begin[blockIdx.x];
-            si_end = a.slot_begin[blockIdx.x + 1];
-            if (si >= si_end) return;                                     // an empty slot (the host makes none)
-            take_song_pc();
-        }
-    }
-    if constexpr (CK) {
-        const int stop = ck_every > 0 || a.t_end >= T ? T : a.t_end + 1;
-        Tb = Tb < stop ? Tb : stop;
-        if (Tb <= t0) return;                                             // (segments: the song ended before this one)
-    }
+    constexpr int kPast = 1, kRowBias = 1;        // a segment runs one frame on; the lanes' row offsets are relative to row t - 1
+#define VIT_WG_CURSOR 1
+#include "wg_cursor.inc"
+#define VIT_WG_CURSOR 2
+#include "wg_cursor.inc"
 
     // ---------------- per-lane constants.  Idle lanes (j >= S) carry -inf tables: their delta stays -inf.
     const int j = tid;
@@ -237,7 +195,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     float* wp = dls + 4 + sh + j;                                         // own entry of copy 0 (copy c: + c*DC - c)
     float* fmp = fmg + fm_slot(lane);                                     // own frame-maximum slot in group 0 (group g: + g*kFmGroupFloats)
 
-    for (int k = tid; k < 2 * BUF + kFmGroups * kFmGroupFloats; k += NWT * 64) dls[k] = -INFINITY;
+    for (int k = tid; k < L::reset; k += NWT * 64) dls[k] = -INFINITY;
     __syncthreads();
 
     // produce(): publish a new delta value -- four shifted copies into buffer WB and the lane's share of M into slot group G --
@@ -389,15 +347,10 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
             if constexpr (CKx) {
                 // the row in front of the one this frame's delta goes to (the lanes' offsets are relative to row t - 1): a segment
                 // stores frame t at t - t0, pass 1 at the next checkpoint row or the scratch row.  Scalar selects, the store as ever.
-                long long rb = (long long)t - 1 - t0;
-                if (ck_every > 0) {
-                    // (PC: a song's last frame is no checkpoint -- the row behind its last one is the next song's first)
-                    const bool hit = PC ? (t == ck_next && t + 1 < Tb) : t == ck_next;
-                    rb = (hit ? ck_row : ck_scratch) - 1;
-                    ck_next += hit ? ck_every : 0;
-                    ck_row += hit ? 1 : 0;
-                }
-                row_store_f32(hist + rb * SD, hoffb, is_fm ? M : dn);
+                long long row = (long long)t - 1 - t0;
+#define VIT_WG_CURSOR 3
+#include "wg_cursor.inc"
+                row_store_f32(hist + row * SD, hoffb, is_fm ? M : dn);
             } else {
                 row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, is_fm ? M : dn);
             }
@@ -444,12 +397,81 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
             break;
         } else {
             if (++si >= si_end) break;                                        // (PC, unit: si_end = 1)
-            if constexpr (PC) take_song_pc(); else take_song();
+            take_song();
             // every wave has read the last delta row (terminal_argmax) before both buffers and all slot groups go back to -inf,
             // and no wave starts frame 0 of the next song before they have
             __syncthreads();
-            for (int k = tid; k < 2 * BUF + kFmGroups * kFmGroupFloats; k += NWT * 64) dls[k] = -INFINITY;
+            for (int k = tid; k < L::reset; k += NWT * 64) dls[k] = -INFINITY;
             __syncthreads();
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------
+// launch helpers of the floor form (host)
+// ---------------------------------------------------------------------------------------
+// f(std::integral_constant<int, W>) for the instantiated window width W / for the target waves of S states
+template <typename F>
+static hipError_t dispatch_width(int W, F&& f) {
+    static_assert(sizeof(kBandedWidths) / sizeof(int) == 6, "one case per instantiated window width");
+    switch (W) {
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 84: return f(std::integral_constant<int, 84>{});
+        case 96: return f(std::integral_constant<int, 96>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+template <typename F>
+static hipError_t dispatch_waves(int S, F&& f) {
+    switch (banded_waves_for(S)) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+// emission rows in flight (see launch_floor_t)
+template <int W>
+constexpr int floor_pf() { return W <= 32 ? 12 : 4; }
+// f(std::integral_constant<int, NXT>): the compile-time extras count of the one-target kernel -- 1 for the reference's matrices (band +
+// unvoiced column) at the widths they come in, else the run-time count
+template <int W, typename F>
+static hipError_t with_nxt(int n_extras, F&& f) {
+    if constexpr (W == 32 || W >= 84) {
+        if (n_extras == 1) return f(std::integral_constant<int, 1>{});
+    }
+    return f(std::integral_constant<int, -1>{});
+}
+
+// A variant of the one-target floor kernel: one workgroup per slot (Packed, PackedCkpt pass 1), per song (Ckpt) or per unit (PackedCkpt,
+// a.unit_song set).  With `per_cu` the launch is replaced by the occupancy query of that instantiation at its dynamic LDS size.
+template <int W, int NWT, typename ET, WgVariant V>
+static hipError_t floor_variant_t(const FwdArgs& a, hipStream_t st, int* per_cu) {
+    constexpr size_t ldsf = FloorLds<W, NWT, V>::bytes();
+    const int groups = V == WgVariant::Ckpt || (V == WgVariant::PackedCkpt && a.unit_song) ? (int)a.B : a.n_slots;
+    return with_nxt<W>(a.n_extras, [&](auto nxt) -> hipError_t {
+        auto kern = banded_floor_forward_kernel<W, NWT, decltype(nxt)::value, floor_pf<W>(), ET, V>;
+        if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, NWT * 64, ldsf);
+        hipLaunchKernelGGL(kern, dim3(groups), dim3(NWT * 64), ldsf, st, a);
+        return hipGetLastError();
+    });
+}
+// the (W, NWT) pairs a variant is instantiated for: Packed every pair of the floor form, the checkpoint variants floor_ckpt_pair's
+template <typename ET, WgVariant V>
+static hipError_t floor_variant_e(const FwdArgs& a, hipStream_t st, int* per_cu) {
+    constexpr bool packed = V == WgVariant::Packed;
+    if (!(packed ? floor_packed_applies(a.S, a.W, a.floor_ok != 0, a.n_dense) : floor_ckpt_applies(a.S, a.W, a.floor_ok != 0, a.n_dense)))
+        return hipErrorInvalidConfiguration;
+    return dispatch_width(a.W, [&](auto w) {
+        return dispatch_waves(a.S, [&](auto n) -> hipError_t {
+            constexpr int W = decltype(w)::value, NWT = decltype(n)::value;
+            if constexpr (packed || floor_ckpt_pair(W, NWT)) return floor_variant_t<W, NWT, ET, V>(a, st, per_cu);
+            return hipErrorInvalidConfiguration;
+        });
+    });
 }

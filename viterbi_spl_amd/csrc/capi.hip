@@ -50,6 +50,12 @@ enum Family : int {
     kFamGroup = 2,             // banded, one song per workgroup
     kFamWave = 3,              // banded, one song per wavefront
 };
+// the forward launch of a packed / checkpointed decode: the workgroup kernels take a variant; the wave form ignores it and reads its
+// mode from the arguments (launch_wave: ckpt_every / t_begin / t_end, offsets, ckpt_base, unit_song)
+inline hipError_t launch_family(int family, vit::WgVariant v, const vit::FwdArgs& a, bool f16, hipStream_t st) {
+    if (family == kFamWave) return vit::launch_wave(a, f16, st);
+    return family == kFamGroup ? vit::launch_banded_variant(a, v, f16, st) : vit::launch_step_variant(a, v, f16, st);
+}
 
 // Where a state's column, the frame maximum and the copies of the extra columns sit in a history row: hist_layout(plan, family).
 struct HistLayout {
@@ -630,8 +636,8 @@ int vit_decode(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B
 // forward kernel over one segment from its checkpoint row into a buffer of about K rows and back-traces it from the state the
 // segment behind it decided at its first frame.  Exact by construction (the same kernels, the same sums); twice the forward work.
 // Three families (ck_family, Family): plans with the wave form (wave.hip HM 5 / 6, the sparse back-trace); banded plans without it whose
-// floor form is proven (banded_floor_forward_kernel<.., CK>, the sparse back-trace over the workgroup layout, or the lane form);
-// step plans (step4s_forward_kernel<.., CK>, the lazy back-trace).  The workgroup families always run that one kernel:
+// floor form is proven (banded_floor_forward_kernel<.., WgVariant::Ckpt>, the sparse back-trace over the workgroup layout, or the lane form);
+// step plans (step4s_forward_kernel<.., WgVariant::Ckpt>, the lazy back-trace).  The workgroup families always run that one kernel:
 // forward_form, step_form, backtrace_form and bt_chunks are not consulted; bt_fast_rows, bt_warm and win_shift are.
 namespace {
 
@@ -743,7 +749,7 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
     const HistLayout lay = hist_layout(plan, family);
     const bool lane_bt = family == kFamGroup && !ck_sparse_applies(plan, kFamGroup);
     auto forward = [&](const vit::FwdArgs& f) {
-        return family == kFamWave ? vit::launch_wave(f, f16, st) : (family == kFamGroup ? vit::launch_banded_ckpt(f, f16, st) : vit::launch_step_ckpt(f, f16, st));
+        return launch_family(family, vit::WgVariant::Ckpt, f, f16, st);
     };
     if (lengths)       // frames past a song's end: -1 (segments a song does not reach are skipped, not written)
         VIT_TRY(hipMemsetAsync(states, 0xff, (size_t)B * (size_t)T * sizeof(int32_t), st));
@@ -818,8 +824,8 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
 // chunk -- the one-stream-per-wavefront kernels hold 16 streams per CU, fewer than a ragged batch of thousands of songs needs
 // (3250 songs: a second round of waves, 14 instead of 6 ms).
 // Plans without the wave form (the 722-state grids) run the same scheme with a WORKGROUP per slot: banded plans with the floor
-// form proven take banded_floor_forward_kernel<.., PK> and the lane back-trace over the workgroup history layout, step plans take
-// step4s_forward_kernel<.., PK> and the lazy back-trace over per-song chunk lists.  Slots: as many workgroups as are resident at once.
+// form proven take banded_floor_forward_kernel<.., WgVariant::Packed> and the lane back-trace over the workgroup history layout, step plans take
+// step4s_forward_kernel<.., WgVariant::Packed> and the lazy back-trace over per-song chunk lists.  Slots: as many workgroups as are resident at once.
 namespace {
 
 // The forward family a packed decode of this plan runs, kFamNone = none: the ONE predicate behind
@@ -880,17 +886,16 @@ PkLayout pk_layout(const vit_plan* p, int family, int64_t B, int64_t N) {
     return k;
 }
 
-// Workgroups one CU holds of the packed workgroup-form kernel (variant 0) or of its packed-checkpoint variant (1) -- the occupancy
+// Workgroups one CU holds of the packed workgroup-form kernel (variant Packed) or of its packed-checkpoint variant -- the occupancy
 // of that instantiation, asked of the device once per emission type and remembered in the plan.
-int resident_per_cu(const vit_plan* plan, int family, int variant, const vit::FwdArgs& a, bool f16, int* per_cu) {
-    int& cached = plan->resident[variant][f16 ? 1 : 0];
+int resident_per_cu(const vit_plan* plan, int family, vit::WgVariant variant, const vit::FwdArgs& a, bool f16, int* per_cu) {
+    int& cached = plan->resident[variant == vit::WgVariant::PackedCkpt ? 1 : 0][f16 ? 1 : 0];
     {
         std::lock_guard<std::mutex> g(plan->mu);
         *per_cu = cached;
     }
     if (*per_cu >= 1) return VIT_OK;
-    const hipError_t eq = variant == 0 ? (family == kFamGroup ? vit::banded_packed_resident(a, f16, per_cu) : vit::step_packed_resident(a, f16, per_cu))
-                                       : (family == kFamGroup ? vit::banded_pckpt_resident(a, f16, per_cu) : vit::step_pckpt_resident(a, f16, per_cu));
+    const hipError_t eq = family == kFamGroup ? vit::banded_variant_resident(a, variant, f16, per_cu) : vit::step_variant_resident(a, variant, f16, per_cu);
     if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: the *_family predicates asked the same)
     VIT_TRY(eq);
     if (*per_cu < 1) return VIT_EUNSUPPORTED;
@@ -902,7 +907,7 @@ int resident_per_cu(const vit_plan* plan, int family, int variant, const vit::Fw
 // resident_per_cu): one per workgroup that is resident at once; and no more than N / tmax -- a slot's load should not fall below the
 // longest song, which bounds the launch anyway (1623 songs of 7500..30000 frames: 1024 slots of ~30000 frames, one wave per SIMD,
 // instead of 1623 waves of which the longest share their SIMDs to the end).
-int pk_lower_slots(const vit_plan* plan, int family, int variant, const vit::FwdArgs& a, bool f16, int64_t N, int64_t tmax, int64_t* n_slots) {
+int pk_lower_slots(const vit_plan* plan, int family, vit::WgVariant variant, const vit::FwdArgs& a, bool f16, int64_t N, int64_t tmax, int64_t* n_slots) {
     if (family != kFamWave) {   // the wave family takes min(pk_slots, max(1, N / tmax)) with no occupancy query
         int per_cu;
         const int rc = resident_per_cu(plan, family, variant, a, f16, &per_cu);
@@ -998,7 +1003,7 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     const bool f16 = emis_dtype == VIT_F16;
     vit::FwdArgs a{};
     fwd_args_from_plan(plan, a);
-    rc = pk_lower_slots(plan, family, 0, a, f16, N, tmax, &k.n_slots);
+    rc = pk_lower_slots(plan, family, vit::WgVariant::Packed, a, f16, N, tmax, &k.n_slots);
     if (rc != VIT_OK) return rc;
     stamp_erase(plan, workspace);
     hipStream_t st = (hipStream_t)stream;
@@ -1056,7 +1061,7 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     a.n_slots = (int)k.n_slots;
     a.slot_begin = reinterpret_cast<const int32_t*>(ws + k.off_slot_begin);
     a.slot_songs = reinterpret_cast<const int32_t*>(ws + k.off_slot_songs);
-    VIT_TRY(family == kFamWave ? vit::launch_wave(a, f16, st) : (family == kFamGroup ? vit::launch_banded_packed(a, f16, st) : vit::launch_step_packed(a, f16, st)));
+    VIT_TRY(launch_family(family, vit::WgVariant::Packed, a, f16, st));
 
     // ---- back-trace: one lane (banded plans) or one wave (step plans) per (song, chunk)
     vit::BtArgs b{};
@@ -1102,7 +1107,7 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
 // units, which writes the states at offsets[b] + segment * K.  Exact by construction: the kernels and sums of vit_decode_packed.
 // What differs by family (BudgetForm): the wave form runs a WAVEFRONT per slot and per unit (wave.hip HM 9 / HM 8, K + 1 rows per
 // unit, up to 8 units per CU and launch, the sparse back-trace); plans without it a WORKGROUP
-// (banded_floor_forward_kernel / step4s_forward_kernel <.., PC>; a.unit_song null = pass 1, set = pass 2).  The floor kernel's unit
+// (banded_floor_forward_kernel / step4s_forward_kernel <.., WgVariant::PackedCkpt>; a.unit_song null = pass 1, set = pass 2).  The floor kernel's unit
 // holds K + 2 rows (one in front for the first frame's frame-maximum store, one behind for the frame past the segment), 1 unit per CU
 // (W = 128 on twelve waves takes 148 KB of LDS and 3 x 168 registers per SIMD), the sparse back-trace over the workgroup rows; the
 // step kernel's K + 1 rows, 2 per CU (62 KB of LDS, seven waves of 128 registers), the lazy kernel's segment form.  Every unit owns
@@ -1123,15 +1128,14 @@ int pb_family(const vit_plan* p) {
 
 // the choices of the budgeted packed decode that depend on the family: data, read at the top of the driver
 struct BudgetForm {
-    hipError_t (*forward)(const vit::FwdArgs&, bool, hipStream_t);
     int units_per_cu;         // units per launch: min(B, units_per_cu x CUs)
     int extra_rows;           // rows a unit holds besides its K
     int front_rows;           // of those, in front of the unit's row 0 (BtArgs::hist, FwdArgs::hist point behind them)
 };
 BudgetForm budget_form(int family) {
-    if (family == kFamWave) return {vit::launch_wave, 8, 1, 0};
-    if (family == kFamGroup) return {vit::launch_banded_pckpt, 1, 2, 1};
-    return {vit::launch_step_pckpt, 2, 1, 0};
+    if (family == kFamWave) return {8, 1, 0};
+    if (family == kFamGroup) return {1, 2, 1};
+    return {2, 1, 0};
 }
 int64_t pb_units(const vit_plan* p, int family, int64_t B) {
     if (family == kFamNone) return 0;
@@ -1225,7 +1229,7 @@ int decode_packed_budgeted(const vit_plan* plan, int (*family_of)(const vit_plan
     vit::FwdArgs a{};
     fwd_args_from_plan(plan, a);
     int64_t n_slots = c.n_slots;                          // pass 1's slots, as vit_decode_packed chooses them (the packed-checkpoint kernels' occupancy)
-    rc = pk_lower_slots(plan, family, 1, a, f16, N, c.tmax, &n_slots);
+    rc = pk_lower_slots(plan, family, vit::WgVariant::PackedCkpt, a, f16, N, c.tmax, &n_slots);
     if (rc != VIT_OK) return rc;
     stamp_erase(plan, workspace);
     vit::PackedCkptSchedule sc;
@@ -1244,7 +1248,7 @@ int decode_packed_budgeted(const vit_plan* plan, int (*family_of)(const vit_plan
     a.slot_songs = reinterpret_cast<const int32_t*>(ws + c.off_slot_songs);
     a.ckpt_base = reinterpret_cast<const int64_t*>(ws + c.off_ckpt_base);
     a.unit_song = nullptr;
-    VIT_TRY(form.forward(a, f16, st));
+    VIT_TRY(launch_family(family, vit::WgVariant::PackedCkpt, a, f16, st));
 
     // ---- pass 2: the launches of the schedule; every unit's back-trace starts from what the launch before it wrote
     float* seg = reinterpret_cast<float*>(ws + c.off_seg) + (size_t)form.front_rows * lay.SD;
@@ -1277,7 +1281,7 @@ int decode_packed_budgeted(const vit_plan* plan, int (*family_of)(const vit_plan
         f.B = nu;
         f.unit_song = d_unit_song + u0;
         f.unit_seg = d_unit_seg + u0;
-        VIT_TRY(form.forward(f, f16, st));
+        VIT_TRY(launch_family(family, vit::WgVariant::PackedCkpt, f, f16, st));
         VIT_TRY(vit::launch_packed_segment_prep(a.offsets, f.unit_song, f.unit_seg, (int)nu, (int)K, states, a.last_state,
                                                 reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast),
                                                 reinterpret_cast<int64_t*>(ws + c.off_sbase), st));

@@ -1,6 +1,8 @@
 // kernels.hpp -- launch interface between the C ABI (capi.hip) and the kernel files (dense, step, banded, wave, emission, activations, fused,
 // backtrace_rows / _sparse / _half / _lane .hip; those four share backtrace_common.hpp: the chunk scheme, the pieces of a decision and
-// the launch helpers).
+// the launch helpers).  The two workgroup forward kernels that have variants -- banded_floor_forward_kernel (banded.hip, banded_pc.hip)
+// and step4s_forward_kernel (step.hip) -- take one WgVariant, share their song / segment bookkeeping as text (wg_cursor.inc) and are
+// reached through one launch and one occupancy entry point per family (launch_*_variant, *_variant_resident).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,20 +30,26 @@ constexpr int banded_target_waves(int S, int W) {
     const int nwt = banded_waves_for(S);
     return scan_form_instantiated(W, nwt) ? nwt : 0;
 }
-// packed variant of the one-target floor kernel (banded_floor_forward_kernel<.., PK = true>, vit_decode_packed for plans without
+// What a workgroup of banded_floor_forward_kernel / step4s_forward_kernel decodes (described at the kernels):
+//   Plain       its own song, every row kept                                     (vit_decode)
+//   Packed      the songs of its slot, back to back, rows at offsets[song]       (vit_decode_packed)
+//   Ckpt        its own song: pass 1 (checkpoint rows only) or one segment       (vit_decode_checkpointed)
+//   PackedCkpt  pass 1 over the songs of its slot, or one segment unit           (vit_decode_packed_bounded)
+enum class WgVariant { Plain, Packed, Ckpt, PackedCkpt };
+// packed variant of the one-target floor kernel (banded_floor_forward_kernel<.., WgVariant::Packed>, vit_decode_packed for plans without
 // the wave form): every instantiated (W, NWT) pair of the floor form; idle slot S stores the frame maximum, so S < 64 * NWT
 constexpr bool floor_packed_applies(int S, int W, bool floor_ok, int n_dense) {
     const int nwt = banded_waves_for(S);
     return floor_ok && n_dense == 0 && nwt > 0 && S < nwt * 64 && banded_width_instantiated(W) && floor_form_instantiated(W, nwt);
 }
-// checkpoint / resume variant of the same kernel (banded_floor_forward_kernel<.., CK = true>, vit_decode_checkpointed for plans without
+// checkpoint / resume variant of the same kernel (banded_floor_forward_kernel<.., WgVariant::Ckpt>, vit_decode_checkpointed for plans without
 // the wave form): the packed variant's pairs but the narrow windows on few waves (W <= 32, S <= 384) -- plans that narrow take the
 // wave form, but for the odd one with three extra columns or S = 64 * npl, and banded.hip is the longest compile as it is
 constexpr bool floor_ckpt_pair(int W, int nwt) { return W >= 64 || nwt >= 8; }
 constexpr bool floor_ckpt_applies(int S, int W, bool floor_ok, int n_dense) {
     return floor_packed_applies(S, W, floor_ok, n_dense) && floor_ckpt_pair(W, banded_waves_for(S));
 }
-// packed-checkpoint variant of the same kernel (banded_floor_forward_kernel<.., PC = true> in banded_pc.hip, vit_decode_packed_bounded
+// packed-checkpoint variant of the same kernel (banded_floor_forward_kernel<.., WgVariant::PackedCkpt> in banded_pc.hip, vit_decode_packed_bounded
 // for plans without the wave form): every pair of the checkpoint / resume variant -- each of them compiles free of scratch
 constexpr bool floor_pckpt_applies(int S, int W, bool floor_ok, int n_dense) { return floor_ckpt_applies(S, W, floor_ok, n_dense); }
 // step-structured kernel (plan.step_ok): instantiated for the Durrieu geometry -- 20-bin bands, 9 near bands, 705..768 voiced states
@@ -82,7 +90,7 @@ struct FwdArgs {
     int wave_flags;         // bit 0: force the 256-register (two waves per SIMD) instantiation, bit 1: the 512-register one up to 1024 songs
     int hist_half;          // wave form: 1 = only the delta rows of even frames are stored (wave.hip, HM 1)
     int64_t hist_rows;      // history rows per song: T, or (T + 1) / 2 with hist_half; checkpoint pass: segments + 1
-    // vit_decode_checkpointed: ckpt_every > 0 = pass 1 (checkpoint rows only; wave.hip HM 5, the CK variants of the floor and step
+    // vit_decode_checkpointed: ckpt_every > 0 = pass 1 (checkpoint rows only; wave.hip HM 5, the Ckpt variants of the floor and step
     // kernels); t_begin > 0 / t_end < T = a segment resumed from init_rows (one row per song in the history layout of the form that
     // runs; row t stored at t - t_begin)
     int ckpt_every, t_begin, t_end;
@@ -96,7 +104,7 @@ struct FwdArgs {
     const int32_t* slot_begin;   // device [n_slots + 1]
     const int32_t* slot_songs;   // device [B]
     // packed checkpointed decode (vit_decode_packed_checkpointed, the wave form: described here; vit_decode_packed_bounded, the
-    // workgroup kernels: the same fields with a workgroup for a wave, see banded_floor.inc / step.hip PC).  Segments are per song: song b has
+    // workgroup kernels: the same fields with a workgroup for a wave, see banded_floor.inc / step.hip, WgVariant::PackedCkpt).  Segments are per song: song b has
     // ceil(T_b / ckpt_every) of them.  ckpt_base set, unit_song null = pass 1 (wave.hip HM 9): the slot walk of the packed batch, but
     // the only rows kept are the ones in front of segments 1 .. n_b - 1, at rows ckpt_base[b] .. of hist; every other store goes to
     // scratch row hist_rows + slot.  unit_song set = pass 2 (HM 8): wave u < B recomputes segment unit_seg[u] of song unit_song[u]
@@ -184,28 +192,36 @@ hipError_t launch_dense(const FwdArgs& a, int songs_per_group, bool f16, hipStre
 hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_wave(const FwdArgs& a, bool f16, hipStream_t st);   // wave.hip: one song per wavefront
-// packed decode of plans without the wave form: one workgroup per slot (a.n_slots, a.offsets, a.slot_begin, a.slot_songs).
-// *_packed_resident: workgroups of that instantiation one compute unit holds at once (the occupancy query at its LDS size).
-hipError_t launch_banded_packed(const FwdArgs& a, bool f16, hipStream_t st);
-hipError_t banded_packed_resident(const FwdArgs& a, bool f16, int* per_cu);
-hipError_t launch_step_packed(const FwdArgs& a, bool f16, hipStream_t st);
-hipError_t step_packed_resident(const FwdArgs& a, bool f16, int* per_cu);
-// checkpointed decode of plans without the wave form, one workgroup per song: pass 1 (a.ckpt_every > 0: checkpoint rows + terminal
-// state) or one segment (a.t_begin / a.t_end, resumed from a.init_rows; the banded kernel also writes one pad column of the row in
-// front of a.hist, see banded.hip)
-hipError_t launch_banded_ckpt(const FwdArgs& a, bool f16, hipStream_t st);
-hipError_t launch_step_ckpt(const FwdArgs& a, bool f16, hipStream_t st);
-// packed checkpointed decode of plans without the wave form (vit_decode_packed_bounded; a.ckpt_base set, a.ckpt_every = K).  a.unit_song
-// null = pass 1: one workgroup per slot (a.n_slots) walks its songs, keeps the rows in front of segments 1 .. n_b - 1 at rows
-// ckpt_base[b] .. of a.hist and sends every other store to scratch row a.hist_rows + slot.  a.unit_song set = one workgroup per unit
-// (a.B of them): segment unit_seg[u] of song unit_song[u], resumed from row ckpt_base[song] + segment - 1 of a.init_rows, into rows
-// u * a.hist_rows .. of a.hist (the banded kernel also writes one pad column of the row in front of them and runs one frame past the
-// segment where the song goes on: K + 2 rows per unit, a.hist at the second; the step kernel: K + 1).
-// *_pckpt_resident: workgroups of that instantiation one compute unit holds at once.
-hipError_t launch_banded_pckpt(const FwdArgs& a, bool f16, hipStream_t st);
-hipError_t banded_pckpt_resident(const FwdArgs& a, bool f16, int* per_cu);
-hipError_t launch_step_pckpt(const FwdArgs& a, bool f16, hipStream_t st);
-hipError_t step_pckpt_resident(const FwdArgs& a, bool f16, int* per_cu);
+// The variants of the workgroup kernels, for plans without the wave form (Plain is not one: launch_banded / launch_step; hipErrorInvalidValue here):
+//   Packed      one workgroup per slot (a.n_slots, a.offsets, a.slot_begin, a.slot_songs)
+//   Ckpt        one workgroup per song: pass 1 (a.ckpt_every > 0: checkpoint rows + terminal state) or one segment (a.t_begin / a.t_end,
+//               resumed from a.init_rows; the banded kernel also writes one pad column of the row in front of a.hist, see banded_floor.inc)
+//   PackedCkpt  a.ckpt_base set, a.ckpt_every = K.  a.unit_song null = pass 1: one workgroup per slot (a.n_slots) walks its songs, keeps
+//               the rows in front of segments 1 .. n_b - 1 at rows ckpt_base[b] .. of a.hist and sends every other store to scratch row
+//               a.hist_rows + slot.  a.unit_song set = one workgroup per unit (a.B of them): segment unit_seg[u] of song unit_song[u],
+//               resumed from row ckpt_base[song] + segment - 1 of a.init_rows, into rows u * a.hist_rows .. of a.hist (the banded kernel
+//               also writes one pad column of the row in front of them and runs one frame past the segment where the song goes on:
+//               K + 2 rows per unit, a.hist at the second; the step kernel: K + 1).
+// *_variant_resident: workgroups of that instantiation one compute unit holds at once (the occupancy query at its LDS size; Packed and
+// PackedCkpt, whose launches are sized by it).
+hipError_t launch_banded_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st);
+hipError_t banded_variant_resident(const FwdArgs& a, WgVariant v, bool f16, int* per_cu);
+// banded.hip -> banded_pc.hip: the PackedCkpt instantiations of the floor kernel build in a translation unit of their own
+hipError_t floor_pckpt(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu);
+hipError_t launch_step_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st);
+hipError_t step_variant_resident(const FwdArgs& a, WgVariant v, bool f16, int* per_cu);
+// what a variant launch needs of FwdArgs; rows_in_front: extra rows the check demands of a unit's hist_rows beyond K (as before: banded 2, step 0)
+inline bool wg_variant_args_ok(const FwdArgs& a, WgVariant v, int rows_in_front) {
+    const bool slots = a.slot_begin && a.slot_songs && a.n_slots >= 1;
+    switch (v) {
+        case WgVariant::Packed: return a.offsets && slots;
+        case WgVariant::Ckpt: return !a.offsets && a.hist_rows >= 1 && (a.t_begin <= 0 || a.init_rows) && (a.ckpt_every <= 0 || a.t_begin <= 0);
+        case WgVariant::PackedCkpt:
+            if (!a.offsets || !a.ckpt_base || a.ckpt_every < 1 || a.hist_rows < 0) return false;
+            return a.unit_song ? (a.unit_seg && a.init_rows && a.B >= 1 && a.hist_rows >= (int64_t)a.ckpt_every + rows_in_front) : slots;
+        default: return false;   // (Plain has no variant launch)
+    }
+}
 // per song, for the segment [s0, e0) of a checkpointed decode: the sub-problem's length (0: the song ends before s0) and the state
 // its back-trace starts from (the state already decided at frame e0, or the song's terminal state)
 hipError_t launch_segment_prep(const int64_t* lengths, int64_t B, int T, int s0, int e0, const int32_t* states, const int32_t* last,

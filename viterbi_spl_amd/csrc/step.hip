@@ -292,49 +292,65 @@ __global__ void __launch_bounds__(256) step4_forward_kernel(FwdArgs a) {
 // delta_t.  Two waves per SIMD issue alternately (2 cycles per instruction), each half moves half the bytes through the LDS
 // store path, and with a barrier on either side of the reads V needs no second buffer: 60 KB of LDS instead of 112.
 // ---------------------------------------------------------------------------------------
-// PK = true is the packed variant (vit_decode_packed): the workgroup is a slot and decodes the songs
+// LDS of step4s_forward_kernel, in floats: what the kernel carves and what its launchers ask for
+template <int BW, int KB>
+struct Step4sLds {
+    static constexpr int NQL = 192;                      // lanes per half: 192 x 4 states
+    static constexpr int NPV = 4 * NQL;                  // padded voiced states
+    static constexpr int PAD = KB * BW + BW;             // -inf margin on both sides of every V_k (multiple of 4)
+    static constexpr int VLEN = NPV + 2 * PAD;
+    static constexpr int FLEN = VLEN / 4;
+    static constexpr int DLEN = NPV + 64;
+    static constexpr int V = 0;                          // [KB][VLEN]
+    static constexpr int F = V + KB * VLEN;              // [KB][FLEN]  F_k[u] = max of the quad V_k[4u .. 4u+3]
+    static constexpr int dl = F + KB * FLEN;             // [DLEN]      delta of the voiced states (for the unvoiced target's row)
+    static constexpr int X = dl + DLEN;                  // [2][NQL] f32x4: partial maxima of the two halves
+    static constexpr int wm = X + 2 * NQL * 4;           // [4]  wave maxima of V_KB (half B), slot 3 = the unvoiced source's candidate
+    static constexpr int dun = wm + 4;                   // [1 (+3)]    delta of the unvoiced state
+    static constexpr int reset = dun + 4;                // floats that go to -inf before a song: everything up to here
+    static constexpr int tot = reset;                    // [16] VI
+    static constexpr int end = tot + 16 * (int)(sizeof(VI) / sizeof(float));
+    static_assert(sizeof(float) * end <= kLdsBytes, "one workgroup's LDS");
+    static constexpr size_t bytes() { return sizeof(float) * end; }
+};
+
+// WV = Packed is the packed variant (vit_decode_packed): the workgroup is a slot and decodes the songs
 // slot_songs[slot_begin[w] .. slot_begin[w+1]) back to back, rows of a song at offsets[song] of the packed buffers.  The band
 // tables c[] and rown[] stay in registers; V, F, dl, X, wm and dun go back to -inf between two songs, behind a barrier.
-// PK = false compiles to the code it was before the parameter existed.
-// CK = true is the checkpoint / resume variant (vit_decode_checkpointed), driven by the FwdArgs fields the wave form uses.  The only
+// WV = Ckpt is the checkpoint / resume variant (vit_decode_checkpointed), driven by the FwdArgs fields the wave form uses.  The only
 // state this kernel carries from frame to frame is dn (V, F, dl, X, wm and dun are published anew every frame), so
 //   pass 1 (ckpt_every = K > 0): every frame; frame mK - 1 is stored to row m - 1 of the song's hist_rows rows, every other frame to
 //     its last row (scratch);
 //   segment (ckpt_every = 0): frames t_begin .. min(length, t_end) - 1, row t stored at t - t_begin; t_begin > 0 loads dn from
 //     init_rows[song] = delta_{t_begin - 1} instead of forming log_pi + e_0.  A workgroup whose song ended before t_begin leaves
 //     without writing; the terminal state is pass 1's business.
-// CK = false compiles to the code it was before the parameter existed.
-// PC = true is the packed-checkpoint variant (vit_decode_packed_bounded), the slot walk of PK joined with the stores of CK, in two modes
+// WV = PackedCkpt is the packed-checkpoint variant (vit_decode_packed_bounded), the slot walk of Packed joined with the stores of Ckpt, in two modes
 // told apart by a.unit_song (uniform over the launch):
-//   pass 1 (unit_song null): the workgroup is a slot and walks its songs as in PK; of song b only the rows in front of its segments
+//   pass 1 (unit_song null): the workgroup is a slot and walks its songs as in Packed; of song b only the rows in front of its segments
 //     1 .. n_b - 1 are kept (frames t with (t + 1) % K == 0 and t + 1 < T_b, K = ckpt_every), at rows ckpt_base[b] .. of a.hist; every
 //     other store goes to the slot's scratch row hist_rows + slot; the terminal state and the log-likelihood are written per song;
-//   unit (unit_song set): CK's segment per workgroup: workgroup u runs the K frames of segment unit_seg[u] of song unit_song[u] (emission
+//   unit (unit_song set): Ckpt's segment per workgroup: workgroup u runs the K frames of segment unit_seg[u] of song unit_song[u] (emission
 //     rows at offsets[song]) from row ckpt_base[song] + segment - 1 of init_rows (segment 0: from the prior) into rows u * hist_rows ..
-// PC = false compiles to the code it was before the parameter existed (PKx / CKx below are then PK / CK).
-template <int BW, int KB, int PF, typename ET, bool PK = false, bool CK = false, bool PC = false>
+// WV = Plain compiles to the code it was before the variants existed.  (PK / CK / PC below: WV is that variant; PKx / CKx: what the
+// packed-checkpoint variant shares with the packed and with the checkpoint / resume variant.)
+template <int BW, int KB, int PF, typename ET, WgVariant WV = WgVariant::Plain>
 __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     static_assert(BW == 20 && KB == 9 && PF % 2 == 0, "written for nine 20-bin bands");
-    static_assert(!(PK && CK), "the checkpoint / resume variant is a variant of the unpacked kernel");
-    static_assert(!(PC && (PK || CK)), "the packed-checkpoint variant is a variant of its own");
+    using L = Step4sLds<BW, KB>;
+    constexpr bool PK = WV == WgVariant::Packed, CK = WV == WgVariant::Ckpt, PC = WV == WgVariant::PackedCkpt;
     constexpr bool PKx = PK || PC;                // the song loop and its per-song preamble
     constexpr bool CKx = CK || PC;                // the row selection of the stores, the resumed first frame
     extern __shared__ __align__(16) unsigned char smem[];
-    constexpr int NQL = 192;                      // lanes per half: 192 x 4 states
-    constexpr int NPV = 4 * NQL;                  // padded voiced states
-    constexpr int PAD = KB * BW + BW;             // -inf margin on both sides of every V_k (multiple of 4)
-    constexpr int VLEN = NPV + 2 * PAD;
-    constexpr int FLEN = VLEN / 4;
-    constexpr int DLEN = NPV + 64;
+    constexpr int NQL = L::NQL, PAD = L::PAD, VLEN = L::VLEN, FLEN = L::FLEN;
     constexpr int KA = 5;                         // half A: bands 0 .. KA-1; half B: KA .. KB-1 and the far band KB
     constexpr int NST = 2 * KB, STA = 10;         // read stages; half A takes 0 .. STA-1 (half B also reduces the far band and scans)
-    float* V = reinterpret_cast<float*>(smem);    // [KB][VLEN]
-    float* F = V + KB * VLEN;                     // [KB][FLEN]  F_k[u] = max of the quad V_k[4u .. 4u+3]
-    float* dl = F + KB * FLEN;                    // [DLEN]      delta of the voiced states (for the unvoiced target's row)
-    f32x4* X = reinterpret_cast<f32x4*>(dl + DLEN);   // [2][NQL]    partial maxima of the two halves
-    float* wm = reinterpret_cast<float*>(X + 2 * NQL);   // [4]  wave maxima of V_KB (half B), slot 3 = the unvoiced source's candidate
-    float* dun = wm + 4;                          // [1 (+3)]    delta of the unvoiced state
-    VI* tot = reinterpret_cast<VI*>(dun + 4);
+    float* V = reinterpret_cast<float*>(smem) + L::V;
+    float* F = V + L::F;
+    float* dl = V + L::dl;
+    f32x4* X = reinterpret_cast<f32x4*>(V + L::X);
+    float* wm = V + L::wm;
+    float* dun = V + L::dun;
+    VI* tot = reinterpret_cast<VI*>(V + L::tot);
     const int S = a.S, SP = a.SP, T = a.T, SD = a.SD;
     const int n = S - 1;
 
@@ -343,72 +359,14 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = wv < 3 ? 0 : (wv < 6 ? 1 : 2);                        // 2: the unvoiced state's wave
     const int ql = tid - NQL * (half == 1 ? 1 : 0);                       // lane within the half (halves 0, 1)
-    // the song being decoded: the workgroup's own, or (PK) the slot's songs one after the other
-    int song = blockIdx.x;
-    int Tb = PKx ? 1 : song_length(a.lengths, song, T);
-    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PKx ? (size_t)0 : (size_t)song * T * S);
-    float* __restrict__ hist = a.hist + (PKx ? (size_t)0 : (CK ? (size_t)song * (size_t)a.hist_rows * SD : (size_t)song * T * SD));
+    constexpr int kPast = 0, kRowBias = 0;        // a segment ends with its last frame; rows are stored at their own index
+#define VIT_WG_CURSOR 1
+#include "wg_cursor.inc"
     const float* __restrict__ lpi = reinterpret_cast<const float*>(a.image + a.off_logpi);
-    // (CK) first frame of this launch, first frame the loop computes, pass 1's segment length and its row bookkeeping (all wave-uniform)
-    // (PC: t0 and t1 belong to the unit; ck_every is K in pass 1 and 0 in a unit launch; the scratch row is the slot's)
-    [[maybe_unused]] const bool pc_unit = PC && a.unit_song != nullptr;
-    [[maybe_unused]] int t0 = CK ? a.t_begin : 0;
-    [[maybe_unused]] int t1 = CK && t0 > 0 ? t0 : 1;
-    [[maybe_unused]] const int ck_every = CK ? a.ckpt_every : (PC && !pc_unit ? a.ckpt_every : 0);
-    [[maybe_unused]] const int ck_scratch = CK ? (int)a.hist_rows - 1 : (PC ? (int)a.hist_rows + (int)blockIdx.x : 0);
-    [[maybe_unused]] int ck_next = ck_every - 1, ck_row = 0;              // the next frame that is a checkpoint, and its row
-    [[maybe_unused]] const float* __restrict__ pc_init = nullptr;         // (PC, unit) the checkpoint row in front of the unit's segment
-    if constexpr (CK) {
-        const int stop = ck_every > 0 || a.t_end >= T ? T : a.t_end;
-        Tb = Tb < stop ? Tb : stop;
-        if (Tb <= t0) return;                                             // (segments: the song ended before this one)
-    }
-    int si = 0, si_end = 1;                                               // (PK) position in slot_songs, end of the slot's list
-    auto take_song = [&]() {                                              // (PK) wave-uniform: scalar loads
-        song = a.slot_songs[si];
-        const long long r0 = a.offsets[song];
-        Tb = (int)(a.offsets[song + 1] - r0);
-        E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
-        hist = a.hist + (size_t)r0 * SD;
-    };
-    if constexpr (PK) {
-        si = a.slot_begin[blockIdx.x];
-        si_end = a.slot_begin[blockIdx.x + 1];
-        if (si >= si_end) return;                                         // an empty slot (the host makes none)
-        take_song();
-    }
-    // (PC) pass 1: the next song of the slot, its emission rows and its first checkpoint row (a.hist is the checkpoint area)
-    auto take_song_pc = [&]() {
-        song = a.slot_songs[si];
-        const long long r0 = a.offsets[song];
-        Tb = (int)(a.offsets[song + 1] - r0);
-        E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
-        ck_next = ck_every - 1;
-        ck_row = (int)a.ckpt_base[song];
-    };
-    if constexpr (PC) {
-        hist = a.hist;
-        if (pc_unit) {                                                    // one unit: its song, segment, frames and rows
-            song = a.unit_song[blockIdx.x];
-            const int useg = a.unit_seg[blockIdx.x];
-            const long long r0 = a.offsets[song];
-            const int Ts = (int)(a.offsets[song + 1] - r0);
-            t0 = useg * a.ckpt_every;
-            t1 = t0 > 0 ? t0 : 1;
-            Tb = t0 + a.ckpt_every >= Ts ? Ts : t0 + a.ckpt_every;
-            E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
-            hist = a.hist + (size_t)blockIdx.x * (size_t)a.hist_rows * SD;
-            pc_init = a.init_rows + (size_t)(a.ckpt_base[song] + useg - 1) * SD;
-            if (Tb <= t0) return;                                         // (the host lists no such unit)
-        } else {
-            si = a.slot_begin[blockIdx.x];
-            si_end = a.slot_begin[blockIdx.x + 1];
-            if (si >= si_end) return;                                     // an empty slot (the host makes none)
-            take_song_pc();
-        }
-    }
+#define VIT_WG_CURSOR 2
+#include "wg_cursor.inc"
 
-    for (int k = tid; k < KB * VLEN + KB * FLEN + DLEN + 8 * NQL + 8; k += 448) V[k] = -INFINITY;
+    for (int k = tid; k < L::reset; k += 448) V[k] = -INFINITY;
     __syncthreads();
 
     const bool voiced_wave = half < 2;
@@ -613,13 +571,8 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
         const int tn = t + PF < Tb ? t + PF : Tb - 1;
         if constexpr (CKx) {        // a segment stores frame t at t - t0, pass 1 at the next checkpoint row or the scratch row (scalar selects)
             int row = t - t0;
-            if (ck_every > 0) {
-                // (PC: a song's last frame is no checkpoint -- the row behind its last one is the next song's first)
-                const bool hit = PC ? (t == ck_next && t + 1 < Tb) : t == ck_next;
-                row = hit ? ck_row : ck_scratch;
-                ck_next += hit ? ck_every : 0;
-                ck_row += hit ? 1 : 0;
-            }
+#define VIT_WG_CURSOR 3
+#include "wg_cursor.inc"
             store4(row, dn);
         } else {
             store4(t, dn);
@@ -674,11 +627,11 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
             break;
         } else {
             if (++si >= si_end) break;                                        // (PC, unit: si_end = 1)
-            if constexpr (PC) take_song_pc(); else take_song();
+            take_song();
             // every wave is past its last read of the song before V, F, dl, X, wm and dun go back to -inf, and none publishes
             // frame 0 of the next song before they have
             __syncthreads();
-            for (int k = tid; k < KB * VLEN + KB * FLEN + DLEN + 8 * NQL + 8; k += 448) V[k] = -INFINITY;
+            for (int k = tid; k < L::reset; k += 448) V[k] = -INFINITY;
             __syncthreads();
             {                                                             // frame 0 and the first PF emission rows, as above
                 const f32x4 e0 = load4(0);
@@ -693,77 +646,45 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     }
 }
 
-// packed variant of step4s_forward_kernel: one workgroup per slot; with `per_cu` the occupancy query instead of the launch
-static hipError_t step_packed(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu) {
+// step4s_forward_kernel<.., WV = V>: one workgroup per song (Plain, Ckpt), per slot (Packed, PackedCkpt pass 1) or per unit (PackedCkpt,
+// a.unit_song set); with `per_cu` the occupancy query of that instantiation instead of the launch
+template <WgVariant V>
+static hipError_t step4s_launch(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu) {
     constexpr int BW = 20, KB = 9, PF = 2;
-    if (!step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) return hipErrorInvalidConfiguration;
-    constexpr int VL4 = 768 + 2 * (KB * BW + BW);
-    const size_t ldss = sizeof(float) * (KB * VL4 + KB * (VL4 / 4) + (768 + 64) + 8 * 192 + 8) + sizeof(VI) * 16;
+    constexpr size_t ldss = Step4sLds<BW, KB>::bytes();
+    const bool per_song = V == WgVariant::Plain || V == WgVariant::Ckpt || (V == WgVariant::PackedCkpt && a.unit_song);
     auto go = [&](auto kern) -> hipError_t {
         if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, 448, ldss);
-        hipLaunchKernelGGL(kern, dim3(a.n_slots), dim3(448), ldss, st, a);
+        hipLaunchKernelGGL(kern, dim3(per_song ? (int)a.B : a.n_slots), dim3(448), ldss, st, a);
         return hipGetLastError();
     };
-    return f16 ? go(step4s_forward_kernel<BW, KB, PF, __half, true>) : go(step4s_forward_kernel<BW, KB, PF, float, true>);
+    return f16 ? go(step4s_forward_kernel<BW, KB, PF, __half, V>) : go(step4s_forward_kernel<BW, KB, PF, float, V>);
 }
-
-hipError_t launch_step_ckpt(const FwdArgs& a, bool f16, hipStream_t st) {
-    constexpr int BW = 20, KB = 9, PF = 2;
+static hipError_t step_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st, int* per_cu) {
     if (!step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) return hipErrorInvalidConfiguration;
-    if (a.offsets || a.hist_rows < 1 || (a.t_begin > 0 && !a.init_rows) || (a.ckpt_every > 0 && a.t_begin > 0)) return hipErrorInvalidValue;
-    constexpr int VL4 = 768 + 2 * (KB * BW + BW);
-    const size_t ldss = sizeof(float) * (KB * VL4 + KB * (VL4 / 4) + (768 + 64) + 8 * 192 + 8) + sizeof(VI) * 16;
-    if (f16)
-        hipLaunchKernelGGL((step4s_forward_kernel<BW, KB, PF, __half, false, true>), dim3((int)a.B), dim3(448), ldss, st, a);
-    else
-        hipLaunchKernelGGL((step4s_forward_kernel<BW, KB, PF, float, false, true>), dim3((int)a.B), dim3(448), ldss, st, a);
-    return hipGetLastError();
+    switch (v) {
+        case WgVariant::Packed: return step4s_launch<WgVariant::Packed>(a, f16, st, per_cu);
+        case WgVariant::Ckpt: return step4s_launch<WgVariant::Ckpt>(a, f16, st, per_cu);
+        case WgVariant::PackedCkpt: return step4s_launch<WgVariant::PackedCkpt>(a, f16, st, per_cu);
+        default: return hipErrorInvalidValue;   // (Plain is launch_step's)
+    }
 }
 
-// packed-checkpoint variant of step4s_forward_kernel: one workgroup per slot (pass 1) or per unit; with `per_cu` the occupancy query
-static hipError_t step_pckpt(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu) {
-    constexpr int BW = 20, KB = 9, PF = 2;
-    if (!step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) return hipErrorInvalidConfiguration;
-    constexpr int VL4 = 768 + 2 * (KB * BW + BW);
-    const size_t ldss = sizeof(float) * (KB * VL4 + KB * (VL4 / 4) + (768 + 64) + 8 * 192 + 8) + sizeof(VI) * 16;
-    const int groups = a.unit_song ? (int)a.B : a.n_slots;
-    auto go = [&](auto kern) -> hipError_t {
-        if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, 448, ldss);
-        hipLaunchKernelGGL(kern, dim3(groups), dim3(448), ldss, st, a);
-        return hipGetLastError();
-    };
-    return f16 ? go(step4s_forward_kernel<BW, KB, PF, __half, false, false, true>) : go(step4s_forward_kernel<BW, KB, PF, float, false, false, true>);
+hipError_t launch_step_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st) {
+    // (the checkpoint / resume entry has always asked for the instantiation first, the packed ones for their arguments)
+    if (v == WgVariant::Ckpt && !step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) return hipErrorInvalidConfiguration;
+    if (!wg_variant_args_ok(a, v, 0)) return hipErrorInvalidValue;
+    return step_variant(a, v, f16, st, nullptr);
 }
 
-hipError_t launch_step_pckpt(const FwdArgs& a, bool f16, hipStream_t st) {
-    if (!a.offsets || !a.ckpt_base || a.ckpt_every < 1 || a.hist_rows < 0) return hipErrorInvalidValue;
-    if (a.unit_song ? (!a.unit_seg || !a.init_rows || a.B < 1 || a.hist_rows < (int64_t)a.ckpt_every)
-                    : (!a.slot_begin || !a.slot_songs || a.n_slots < 1))
-        return hipErrorInvalidValue;
-    return step_pckpt(a, f16, st, nullptr);
-}
-
-hipError_t step_pckpt_resident(const FwdArgs& a, bool f16, int* per_cu) { return step_pckpt(a, f16, nullptr, per_cu); }
-
-hipError_t launch_step_packed(const FwdArgs& a, bool f16, hipStream_t st) {
-    if (!a.offsets || !a.slot_begin || !a.slot_songs || a.n_slots < 1) return hipErrorInvalidValue;
-    return step_packed(a, f16, st, nullptr);
-}
-
-hipError_t step_packed_resident(const FwdArgs& a, bool f16, int* per_cu) { return step_packed(a, f16, nullptr, per_cu); }
+hipError_t step_variant_resident(const FwdArgs& a, WgVariant v, bool f16, int* per_cu) { return step_variant(a, v, f16, nullptr, per_cu); }
 
 hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st) {
     constexpr int BW = 20, KB = 9, PF = 2;
     if (!step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) return hipErrorInvalidConfiguration;
+    // four targets per lane, bands split over two waves (step_form 3: one wave)
+    if (a.step_form != 3) return step4s_launch<WgVariant::Plain>(a, f16, st, nullptr);
     constexpr int VL4 = 768 + 2 * (KB * BW + BW);
-    if (a.step_form != 3) {     // four targets per lane, bands split over two waves (step_form 3: one wave)
-        const size_t ldss = sizeof(float) * (KB * VL4 + KB * (VL4 / 4) + (768 + 64) + 8 * 192 + 8) + sizeof(VI) * 16;
-        if (f16)
-            hipLaunchKernelGGL((step4s_forward_kernel<BW, KB, PF, __half>), dim3((int)a.B), dim3(448), ldss, st, a);
-        else
-            hipLaunchKernelGGL((step4s_forward_kernel<BW, KB, PF, float>), dim3((int)a.B), dim3(448), ldss, st, a);
-        return hipGetLastError();
-    }
     const size_t lds4 = sizeof(float) * (2 * KB * VL4 + 2 * KB * (VL4 / 4) + 2 * (768 + 64) + 2 * 4 + 4) + sizeof(VI) * 16;
     if (f16)
         hipLaunchKernelGGL((step4_forward_kernel<BW, KB, PF, __half>), dim3((int)a.B), dim3(256), lds4, st, a);
