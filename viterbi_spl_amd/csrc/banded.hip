@@ -315,12 +315,11 @@ __global__ void __launch_bounds__((NWT + (DW ? 3 : 2)) * 64) banded_forward_kern
 // same address), and the two lanes of idle slot S play the one-target kernel's "lane S" (M into pad column S of the previous
 // row); the other idle slots hit pad column S + 1 with -inf as they do there.  LDS layout (copy stride from the 384 state slots), barrier, read order, pinning, prefetch depth
 // and the history rows, pad columns included, are those of banded_floor_forward_kernel<32, 6, ...>, byte for byte.
-// The wave role is a scalar test outside the frame loop: two loop bodies with the same barriers.
+// The wave role is a scalar test outside the frame loop: three loop bodies with the same barriers (full wave, half wave, and the
+// last half wave, which also resets the slot group of the frame after next -- a role, not a wave test per frame).  The history and
+// emission rows of a round of twelve frames hang off one buffer descriptor each; a frame's row is the instruction's scalar offset.
 // ---------------------------------------------------------------------------------------
-inline constexpr int kSplitFullWaves = 4, kSplitHalfWaves = 4;
-inline constexpr int kSplitStates = 64 * kSplitFullWaves + 32 * kSplitHalfWaves;   // 384 target slots
-using FloorSplitLds = FloorLds<32, kSplitStates / 64>;   // the six-wave kernel's LDS, byte for byte
-
+// (kSplitFullWaves, kSplitHalfWaves, kSplitStates and FloorSplitLds: banded_floor.inc, next to FloorLds)
 template <int NXT, int PF, typename ET, bool WPR = false>
 __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) banded_floor_split_forward_kernel(FwdArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -384,8 +383,9 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
     unsigned long long clk0 = 0ull, rt0 = 0ull;
 
     // one role's share of the song: HALF = false the full-window waves, true the half-window waves
-    auto body = [&](auto role) {
-        constexpr bool HALF = decltype(role)::value;
+    // (resets: the last half wave, which also sends the slot group of the frame after next back to -inf)
+    auto body = [&](auto role, auto resets) {
+        constexpr bool HALF = decltype(role)::value, RESETS = decltype(resets)::value;
         constexpr int WL = HALF ? W / 2 : W;                              // window sources per lane
         const float cj = own ? reinterpret_cast<const float*>(a.image + a.off_rowc)[jc] : -INFINITY;   // (upper half: -inf)
         float aw[WL];
@@ -400,17 +400,22 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
                 xa[k] = (tvalid && k < nx && (!HALF || hh == 1)) ? xaT[(size_t)k * SP + jc] : -INFINITY;   // (lower half: -inf)
         }
         // own entry of copy 0 (copy c: + c*DC - c); an upper lane starts at copy 2
-        float* wp = dls + 4 + sh + j + (HALF ? hh * (2 * DC - 2) : 0);
+        float* wp = dls + 4 + sh + j + (HALF ? hh * split_upper_off(DC) : 0);
+        // the extra columns' positions in copy 0, kept in a vector register: they are wave-uniform, and from a scalar register every
+        // frame's ds_read_b32 needed a v_mov first
+        int xo[NXL > 0 ? NXL : 1];
+#pragma unroll
+        for (int k = 0; k < NXL; ++k) {
+            xo[k] = 4 + sh + xcol[k];
+            asm volatile("" : "+v"(xo[k]));
+        }
 
         auto produce = [&](const float dn, const int WB, const int G, const int Z) {
 #pragma unroll
-            for (int c = 0; c < (HALF ? 2 : 4); ++c) wp[WB * BUF + c * DC - c] = dn;
+            for (int c = 0; c < (HALF ? 2 : 4); ++c) wp[WB * BUF + floor_copy_off(DC, c)] = dn;
             fm_publish(fmp + G * kFmGroupFloats, (NXL > 0 && is_x) ? -INFINITY : dn);
-            if constexpr (HALF) {
-                int w = wv;
-                asm volatile("" : "+s"(w));   // (see banded_floor_forward_kernel)
-                if (w == NW - 1) fmg[Z * kFmGroupFloats + lane] = -INFINITY;
-            }
+            // (the resetting wave is a role of its own: no wave test per frame, the one-target kernel's costs three SALU slots)
+            if constexpr (RESETS) fmg[Z * kFmGroupFloats + lane] = -INFINITY;
         };
 
         // ---------------- frame 0 (both lanes of a split target hold it)
@@ -429,7 +434,23 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
         asm volatile("" ::"v"(cj));
         __syncthreads();
 
-        auto frame = [&](const int t, float& e_slot, const int u) {
+        // Row bases of a round of up to PF frames that starts at frame t: history row t - 1 and emission row min(t + PF, Tb - 1), one
+        // descriptor each for the whole round.  Frame t + u reaches its rows through the buffer instructions' scalar offset: u history
+        // rows on (u * rowH, a constant per unrolled frame), and min(u, Tb - 1 - (t + PF)) emission rows on, i.e. row
+        // min(t + u + PF, Tb - 1) as ever (elim: that bound in bytes, at most PF rows; 0 once the round's base row is the last row).
+        // Per frame that is one s_min_u32 where the row bases took two 64-bit multiply-adds, a clamp and two descriptor rebuilds.
+        const unsigned rowH = 4u * (unsigned)SD, rowE = (unsigned)sizeof(ET) * (unsigned)S;
+        float* hb = hist;
+        const ET* eb = E;
+        unsigned elim = 0;
+        auto round_bases = [&](const int t) {
+            const int r = t + PF < Tb ? t + PF : Tb - 1;
+            const int ahead = Tb - 1 - r < PF ? Tb - 1 - r : PF;
+            hb = hist + (size_t)(t - 1) * SD;
+            eb = E + (size_t)r * S;
+            elim = (unsigned)ahead * rowE;
+        };
+        auto frame = [&](float& e_slot, const int u) {
             const int RB = u & 1, WB = RB ^ 1;
             const int GR = u % kFmGroups, GW = (u + 1) % kFmGroups, GZ = (u + 2) % kFmGroups;
             const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
@@ -438,7 +459,7 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             float m0, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
             // small reads first, the window right behind them, then M (see banded_floor_forward_kernel)
 #pragma unroll
-            for (int k = 0; k < NXL; ++k) xd[k] = dls[4 + sh + RB * BUF + xcol[k]];
+            for (int k = 0; k < NXL; ++k) xd[k] = dls[xo[k] + RB * BUF];
             fq = reinterpret_cast<const f32x4*>(fmg + GR * kFmGroupFloats)[0];
             asm volatile("" ::: "memory");
             f32x4 dw[WL / 4];
@@ -471,9 +492,11 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
 #endif
             produce(dn, WB, GW, GZ);
             asm volatile("" ::: "memory");   // the global store / prefetch fill the wait for the LDS write acknowledgement
-            const int tn = t + PF < Tb ? t + PF : Tb - 1;
-            row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, (HALF && is_fm) ? M : dn);   // (full waves hold live targets only)
-            e_slot = row_load_e<ET>(E + (size_t)tn * S, eoffb);
+            const unsigned eso = (unsigned)u * rowE < elim ? (unsigned)u * rowE : elim;
+            // KEEP THIS STORE SINGLE-DWORD: with a register soffset a store wider than 64 bits needs wait states in front of the next write
+            // of its data registers that the compiler does not insert -- wrong rows, not reproducibly
+            row_store_f32(hb, hoffb, (HALF && is_fm) ? M : dn, (unsigned)u * rowH);   // (full waves hold live targets only)
+            e_slot = row_load_e<ET>(eb, eoffb, eso);
 #ifdef VIT_TIMING_HOOKS
             if constexpr (wprobe) wp_.barrier(); else
 #endif
@@ -486,15 +509,19 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
         rt0 = probe ? __builtin_amdgcn_s_memrealtime() : 0ull;
         int t = 1;
         for (; t + PF - 1 < Tb; t += PF) {
+            round_bases(t);
 #pragma unroll
-            for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
+            for (int k = 0; k < PF; ++k) frame(er[k], k);
         }
+        round_bases(t);
 #pragma unroll
         for (int k = 0; k < PF - 1; ++k)
-            if (t + k < Tb) frame(t + k, er[k], k);
+            if (t + k < Tb) frame(er[k], k);
     };
     static_assert(PF % 2 == 0 && PF % kFmGroups == 0, "the unrolled frames must cycle through whole buffer and slot-group rounds");
-    if (half) body(std::true_type{}); else body(std::false_type{});
+    if (!half) body(std::false_type{}, std::false_type{});
+    else if (wv == NW - 1) body(std::true_type{}, std::true_type{});
+    else body(std::true_type{}, std::false_type{});
 
     const int fb = (Tb - 1) & 1;                                          // buffer holding delta_{Tb-1}
     terminal_argmax(own ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, own, tot, NW, a.last_state, a.loglik, song);

@@ -7,18 +7,20 @@
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const void* row) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(row), (short)0, -1, 0x00020000);
 }
-__device__ __forceinline__ void row_store_f32(float* row, unsigned off, float v) {
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), row_rsrc(row), off, 0, 0);
+// `soff` is the instruction's scalar byte offset (wave-uniform): a kernel that keeps one descriptor for a round of frames passes the
+// frame's row distance here instead of rebuilding the descriptor per frame (the split kernel, banded.hip).
+__device__ __forceinline__ void row_store_f32(float* row, unsigned off, float v, unsigned soff = 0) {
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), row_rsrc(row), off, soff, 0);
 }
 template <typename ET>
-__device__ __forceinline__ float row_load_e(const ET* row, unsigned off);
+__device__ __forceinline__ float row_load_e(const ET* row, unsigned off, unsigned soff = 0);
 template <>
-__device__ __forceinline__ float row_load_e<float>(const float* row, unsigned off) {
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(row_rsrc(row), off, 0, 0));
+__device__ __forceinline__ float row_load_e<float>(const float* row, unsigned off, unsigned soff) {
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(row_rsrc(row), off, soff, 0));
 }
 template <>
-__device__ __forceinline__ float row_load_e<__half>(const __half* row, unsigned off) {
-    return __half2float(__ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(row_rsrc(row), off, 0, 0)));
+__device__ __forceinline__ float row_load_e<__half>(const __half* row, unsigned off, unsigned soff) {
+    return __half2float(__ushort_as_half(__builtin_amdgcn_raw_buffer_load_b16(row_rsrc(row), off, soff, 0)));
 }
 
 // Frame-maximum slots of the floor-max kernel: a two-step DPP max over each quad of lanes, then lane l adds into slot
@@ -90,6 +92,15 @@ struct FloorLds {
     static_assert(sizeof(float) * end <= kLdsBytes, "one workgroup's LDS");
     static constexpr size_t bytes() { return sizeof(float) * end; }
 };
+// Where a lane writes: from its own entry of copy 0 (wp = dls + 4 + sh + j), copy c's entry lies floor_copy_off(DC, c) floats on; an
+// upper lane of the split kernel's half waves writes copies 2 and 3, so its wp starts split_upper_off(DC) floats further on.  (Shared
+// with floor_lds_check.hip, which holds them against where the readers look.)
+constexpr int floor_copy_off(int DC, int c) { return c * DC - c; }
+constexpr int split_upper_off(int DC) { return floor_copy_off(DC, 2); }
+// the split kernel (banded.hip): four full waves and four half-window waves over 384 target slots, in the six-wave kernel's LDS
+inline constexpr int kSplitFullWaves = 4, kSplitHalfWaves = 4;
+inline constexpr int kSplitStates = 64 * kSplitFullWaves + 32 * kSplitHalfWaves;   // 384 target slots
+using FloorSplitLds = FloorLds<32, kSplitStates / 64>;   // the six-wave kernel's LDS, byte for byte
 
 // V = Packed is the packed variant (vit_decode_packed, plans without the wave form): the workgroup is a SLOT and decodes the
 // songs slot_songs[slot_begin[w] .. slot_begin[w+1]) back to back, as a wave does in wave.hip.  Emission and history rows of
@@ -202,7 +213,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     // and reset slot group Z for the frame after next
     auto produce = [&](const float dn, const int WB, const int G, const int Z) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) wp[WB * BUF + c * DC - c] = dn;
+        for (int c = 0; c < 4; ++c) wp[WB * BUF + floor_copy_off(DC, c)] = dn;
         fm_publish(fmp + G * kFmGroupFloats, (NXL > 0 && is_x) ? -INFINITY : dn);
         int w = wv;
         asm volatile("" : "+s"(w));   // a fresh SGPR test per frame: hoisted, the wave test became two VALU instructions a frame
