@@ -1,4 +1,4 @@
-"""Half-history wave form (wave.hip HM 1 + backtrace_half.hip): parity against the CPU oracle on small ragged batches (every
+"""Half-history wave form (wave.hip WaveHist::Half + backtrace_half.hip): parity against the CPU oracle on small ragged batches (every
 emission kind, storage type, chunking, forced bad guesses), then forward / back-trace timing against the full history at
 large batch sizes (test infrastructure; run on the GPU box).  argv: batch sizes to time (default 1024 2048); "peaks" /
 "dense" selects the emission kind; "notime" skips the timing."""

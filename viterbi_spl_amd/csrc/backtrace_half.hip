@@ -1,7 +1,7 @@
-// backtrace_half.hip -- exact, time-parallel back-trace over a HALF history (wave form, wave.hip HM 1).
+// backtrace_half.hip -- exact, time-parallel back-trace over a HALF history (wave form, wave.hip WaveHist::Half).
 //
 // The wave form is HBM-bound and the float32 delta row it stores per frame (1536 B) is more than the emission row it
-// reads (1444 B).  With HM 1 it stores the rows of even frames only.  This kernel decides an even frame exactly like
+// reads (1444 B).  With WaveHist::Half it stores the rows of even frames only.  This kernel decides an even frame exactly like
 // sparse_backtrace_kernel (candidates fl(delta_t[i] + logA_T[j][i]) over the window and the extra columns of the path
 // state j at t+1, wave max, the bound fl(M_t + c_j), lowest matching index) and REBUILDS what it needs of an odd frame
 // t: the path state's window holds 32 sources i, and

@@ -51,7 +51,7 @@ enum Family : int {
     kFamWave = 3,              // banded, one song per wavefront
 };
 // the forward launch of a packed / checkpointed decode: the workgroup kernels take a variant; the wave form ignores it and reads its
-// mode from the arguments (launch_wave: ckpt_every / t_begin / t_end, offsets, ckpt_base, unit_song)
+// mode from the arguments (wave_hist_of, wave_common.hpp: which of ckpt_base / unit_song, offsets, ckpt_every, t_begin / t_end, hist_half mean which mode)
 inline hipError_t launch_family(int family, vit::WgVariant v, const vit::FwdArgs& a, bool f16, hipStream_t st) {
     if (family == kFamWave) return vit::launch_wave(a, f16, st);
     return family == kFamGroup ? vit::launch_banded_variant(a, v, f16, st) : vit::launch_step_variant(a, v, f16, st);
@@ -635,7 +635,7 @@ int vit_decode(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B
 // (the row in front of the segment) plus the terminal state; pass 2 walks the segments from the last to the first, re-runs the
 // forward kernel over one segment from its checkpoint row into a buffer of about K rows and back-traces it from the state the
 // segment behind it decided at its first frame.  Exact by construction (the same kernels, the same sums); twice the forward work.
-// Three families (ck_family, Family): plans with the wave form (wave.hip HM 5 / 6, the sparse back-trace); banded plans without it whose
+// Three families (ck_family, Family): plans with the wave form (wave.hip WaveHist::CkptPass / Segment, the sparse back-trace); banded plans without it whose
 // floor form is proven (banded_floor_forward_kernel<.., WgVariant::Ckpt>, the sparse back-trace over the workgroup layout, or the lane form);
 // step plans (step4s_forward_kernel<.., WgVariant::Ckpt>, the lazy back-trace).  The workgroup families always run that one kernel:
 // forward_form, step_form, backtrace_form and bt_chunks are not consulted; bt_fast_rows, bt_warm and win_shift are.
@@ -1105,7 +1105,7 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
 // ready units per launch, at most one per song, most segments left first).  A launch resumes the forward kernel from every unit's
 // checkpoint row into that unit's rows, sets every unit's length and start state (packed_segment_prep_kernel) and back-traces the
 // units, which writes the states at offsets[b] + segment * K.  Exact by construction: the kernels and sums of vit_decode_packed.
-// What differs by family (BudgetForm): the wave form runs a WAVEFRONT per slot and per unit (wave.hip HM 9 / HM 8, K + 1 rows per
+// What differs by family (BudgetForm): the wave form runs a WAVEFRONT per slot and per unit (wave.hip WaveHist::PackedCkptPass / PackedSegment, K + 1 rows per
 // unit, up to 8 units per CU and launch, the sparse back-trace); plans without it a WORKGROUP
 // (banded_floor_forward_kernel / step4s_forward_kernel <.., WgVariant::PackedCkpt>; a.unit_song null = pass 1, set = pass 2).  The floor kernel's unit
 // holds K + 2 rows (one in front for the first frame's frame-maximum store, one behind for the frame past the segment), 1 unit per CU

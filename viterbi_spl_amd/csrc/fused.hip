@@ -1,8 +1,8 @@
 // fused.hip -- pitch logits -> path in ONE forward launch (gfx950): the emission builder and the wave-form forward recursion
 // in the same workgroup, the emission rows handed over through LDS instead of HBM.
 //
-// One workgroup = eight waves = four songs.  Waves 0-3 are CONSUMERS (the forward recursion of wave_forward_kernel: full history,
-// HM 0 row layout, its frame arithmetic included as text -- wave_frame_body.inc), waves 4-7 are PRODUCERS (the frame body of
+// One workgroup = eight waves = four songs.  Waves 0-3 are CONSUMERS (the forward recursion of wave_forward_kernel: the rows of
+// WaveHist::Full, its frame arithmetic included as text -- wave_frame_body.inc --, its per-lane setup from wave_common.hpp), waves 4-7 are PRODUCERS (the frame body of
 // observation_reg_kernel -- obs_frame_body.inc), producer p building the emission rows of consumer p's song.  512 threads at 256
 // registers are exactly one workgroup per CU: four songs per CU resident, larger batches run as further rounds of workgroups.
 //
@@ -17,8 +17,8 @@
 // owns bins NPLP*l ..) and writes its values one by one, the recursion is right-aligned with six slots per lane (slot 6l + k =
 // state 6l + k - o) and reads floats 6l .. 6l + 5 as three 8-byte pieces, one frame ahead of their use.  The o leading floats of a row
 // feed idle slots whose delta is -inf + e: they are zeroed once before the first barrier (they must be finite).
-#include "device_common.hpp"
 #include "obs_frame.hpp"
+#include "wave_common.hpp"
 
 namespace vit {
 
@@ -134,18 +134,8 @@ __device__ __forceinline__ void fused_consume(const FwdArgs& a, const float* __r
     const int o = SDW - S;                                 // idle leading slots
     const int j0 = NPL * lane - o;                         // state of slot 0 of this lane (negative: idle)
     const bool l0a = lane == 0 && wave_aux_frames(NPL, S, NX) == 3;    // this lane's slots 2 .. 5 carry the scalars of frames t-1, t-2
-    // per-lane constants: wave_forward_kernel's (wave.hip)
-    f32x2 aw[NPL][NPM];
-    {
-        const float* __restrict__ tv = reinterpret_cast<const float*>(a.image + a.off_tabV);
-#pragma unroll
-        for (int k = 0; k < NPL; ++k)
-#pragma unroll
-            for (int m = 0; m < NPM; ++m) {
-                aw[k][m].x = tv[(((size_t)k * NPM + m) * 2 + 0) * 64 + lane];
-                aw[k][m].y = tv[(((size_t)k * NPM + m) * 2 + 1) * 64 + lane];
-            }
-    }
+    constexpr bool A3 = true;                  // WaveHist::Full's rows: the scalars of three frames in lane 0's leading slots
+#include "wave_lane_weights.inc"
     float cj[NPL];
     float xa[1][NPL];
     float lp[NPL];
@@ -162,35 +152,10 @@ __device__ __forceinline__ void fused_consume(const FwdArgs& a, const float* __r
         }
     }
     float* __restrict__ hist = a.hist + (size_t)(Tl > 0 ? song : 0) * a.hist_rows * SDW;
-    // history row t in slot order; lane 0's leading slots carry M_t, delta_t of the extra column and the same two scalars of frames
-    // t-1 and t-2 (wave.hip, store_hist with A3)
-    auto store_hist = [&](const int t, const float (&dd)[NPL], const float Mt, const float xt, const float Mp, const float xp, const float Mq,
+    auto store_hist = [&](const int t, const float (&d)[NPL], const float M, const float (&xd)[1], const float Mp, const float (&xp)[1], const float Mq,
                           const float xq) {
-        float v[NPL];
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) v[k] = dd[k];
-        v[0] = lane == 0 ? Mt : v[0];
-        v[1] = lane == 0 ? xt : v[1];
-        v[2] = l0a ? Mp : v[2];
-        v[3] = l0a ? xp : v[3];
-        v[4] = l0a ? Mq : v[4];
-        v[5] = l0a ? xq : v[5];
-        float* __restrict__ p = hist + (size_t)t * SDW + NPL * lane;
-        f32x4_u w4;
-        w4.x = v[0]; w4.y = v[1]; w4.z = v[2]; w4.w = v[3];
-        *reinterpret_cast<f32x4_u*>(p) = w4;
-        f32x2_u w2;
-        w2.x = v[4]; w2.y = v[5];
-        *reinterpret_cast<f32x2_u*>(p + 4) = w2;
-    };
-    auto frame_max = [&](const float (&v)[NPL]) -> float {
-        float loc = v[0];
-#pragma unroll
-        for (int k = 1; k < NPL; ++k) loc = fmaxf(loc, v[k]);
-        return wave_max_all(loc);
-    };
-    auto last_delta = [&](const float (&v)[NPL]) -> float {      // delta of the extra column = state S-1 = lane 63, last slot
-        return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v[NPL - 1]), 63));
+#include "wave_hist_row.inc"
+        store_row<NPL>(hist + (size_t)t * SDW + NPL * lane, v);
     };
     // this lane's six values of a ring row: floats 6l .. 6l + 5, 8-byte aligned
     auto load_ring = [&](const float* __restrict__ row, float (&e)[NPL]) {
@@ -211,20 +176,20 @@ __device__ __forceinline__ void fused_consume(const FwdArgs& a, const float* __r
     auto frame0 = [&](const float (&e)[NPL]) {             // delta_0 = log_pi + e_0
 #pragma unroll
         for (int k = 0; k < NPL; ++k) d[k] = j0 + k >= 0 ? lp[k] + e[k] : -INFINITY;
-        M = frame_max(d);
-        xd[0] = last_delta(d);
-        store_hist(0, d, M, xd[0], M, xd[0], M, xd[0]);
+        M = wave_frame_max<NPL>(d);
+        xd[0] = wave_last_delta<NPL>(d);
+        store_hist(0, d, M, xd, M, xd, M, xd[0]);
         Mb = M;
         xb = xd[0];
     };
     auto frame = [&](const int t, const float (&e)[NPL]) {
 #include "wave_frame_body.inc"
-        const float Mp = M, xp = xd[0];    // the previous frame's scalars (wave-uniform: scalar registers)
-        M = frame_max(d);
-        xd[0] = last_delta(d);             // for the next frame's candidates, and for the history row
-        store_hist(t, d, M, xd[0], Mp, xp, Mb, xb);
+        const float Mp = M, xp[1] = {xd[0]};   // the previous frame's scalars (wave-uniform: scalar registers)
+        M = wave_frame_max<NPL>(d);
+        xd[0] = wave_last_delta<NPL>(d);   // for the next frame's candidates, and for the history row
+        store_hist(t, d, M, xd, Mp, xp, Mb, xb);
         Mb = Mp;
-        xb = xp;
+        xb = xp[0];
     };
     for (int i = 0; i < nph; ++i) {
         const int tb = FH * (i - 1);

@@ -88,9 +88,9 @@ struct FwdArgs {
     int wave_u5;            // wave.hip UV: 1 = the one extra column is state S-1; 2 = also: row constant and extra-column weight uniform over a
                             // lane's slots 0..4; 3 = uniform over slots {0,1,2} and {3,4}
     int wave_flags;         // bit 0: force the 256-register (two waves per SIMD) instantiation, bit 1: the 512-register one up to 1024 songs
-    int hist_half;          // wave form: 1 = only the delta rows of even frames are stored (wave.hip, HM 1)
+    int hist_half;          // wave form: 1 = only the delta rows of even frames are stored (wave.hip, WaveHist::Half)
     int64_t hist_rows;      // history rows per song: T, or (T + 1) / 2 with hist_half; checkpoint pass: segments + 1
-    // vit_decode_checkpointed: ckpt_every > 0 = pass 1 (checkpoint rows only; wave.hip HM 5, the Ckpt variants of the floor and step
+    // vit_decode_checkpointed: ckpt_every > 0 = pass 1 (checkpoint rows only; wave.hip WaveHist::CkptPass, the Ckpt variants of the floor and step
     // kernels); t_begin > 0 / t_end < T = a segment resumed from init_rows (one row per song in the history layout of the form that
     // runs; row t stored at t - t_begin)
     int ckpt_every, t_begin, t_end;
@@ -105,9 +105,9 @@ struct FwdArgs {
     const int32_t* slot_songs;   // device [B]
     // packed checkpointed decode (vit_decode_packed_checkpointed, the wave form: described here; vit_decode_packed_bounded, the
     // workgroup kernels: the same fields with a workgroup for a wave, see banded_floor.inc / step.hip, WgVariant::PackedCkpt).  Segments are per song: song b has
-    // ceil(T_b / ckpt_every) of them.  ckpt_base set, unit_song null = pass 1 (wave.hip HM 9): the slot walk of the packed batch, but
+    // ceil(T_b / ckpt_every) of them.  ckpt_base set, unit_song null = pass 1 (wave.hip WaveHist::PackedCkptPass): the slot walk of the packed batch, but
     // the only rows kept are the ones in front of segments 1 .. n_b - 1, at rows ckpt_base[b] .. of hist; every other store goes to
-    // scratch row hist_rows + slot.  unit_song set = pass 2 (HM 8): wave u < B recomputes segment unit_seg[u] of song unit_song[u]
+    // scratch row hist_rows + slot.  unit_song set = pass 2 (WaveHist::PackedSegment): wave u < B recomputes segment unit_seg[u] of song unit_song[u]
     // from checkpoint row ckpt_base[song] + segment - 1 of init_rows (segment 0: from the prior) into rows u * hist_rows .. of hist
     const int64_t* ckpt_base;    // device [songs]: checkpoint rows in front of song b's = sum of (n_b' - 1) over b' < b
     const int32_t* unit_song;    // device [B units of this launch]
@@ -142,7 +142,7 @@ struct BtArgs {
     size_t off_lo, off_kind, off_tabA, off_extraA, off_denseA, off_Arow, off_rowc, off_tabX, off_stepC;
     int step_ok, step_kb, step_mult;   // step-structured dense matrix: band = min((dist * step_mult) >> 16, step_kb)
     float step_cn;
-    // half history (wave form, HM 1): row r of a song holds frame 2r; its aux slots mcol / xcol0 + k carry the frame maximum and the
+    // half history (wave form, WaveHist::Half): row r of a song holds frame 2r; its aux slots mcol / xcol0 + k carry the frame maximum and the
     // extra-column deltas of frame 2r, slots mcol_odd / xcol0_odd + k those of frame 2r - 1.  The back-trace reads the emissions again.
     int hist_half;
     int64_t hist_rows;
@@ -191,7 +191,7 @@ hipError_t launch_fused_logits(const FusedArgs& fa, hipStream_t st);
 hipError_t launch_dense(const FwdArgs& a, int songs_per_group, bool f16, hipStream_t st);
 hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st);
-hipError_t launch_wave(const FwdArgs& a, bool f16, hipStream_t st);   // wave.hip: one song per wavefront
+hipError_t launch_wave(const FwdArgs& a, bool f16, hipStream_t st);   // wave.hip: one song per wavefront; the mode: wave_hist_of (wave_common.hpp)
 // The variants of the workgroup kernels, for plans without the wave form (Plain is not one: launch_banded / launch_step; hipErrorInvalidValue here):
 //   Packed      one workgroup per slot (a.n_slots, a.offsets, a.slot_begin, a.slot_songs)
 //   Ckpt        one workgroup per song: pass 1 (a.ckpt_every > 0: checkpoint rows + terminal state) or one segment (a.t_begin / a.t_end,

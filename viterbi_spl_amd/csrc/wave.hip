@@ -20,56 +20,14 @@
 // Every value compared is one the dense recursion forms, so delta is bit-identical (CPU replay: tests/plan_replay.py
 // replay_wave).  Per frame and wave 253 VALU instructions (272 in all) and nothing to wait for but the emission prefetch;
 // songs of different lengths simply finish at different times.  The history rows are written in slot order (row stride
-// 64*NPL floats; layout at the kernel below) and vit_forward records that layout for the back-trace kernels.
+// 64*NPL floats; layout at the kernel below) and vit_forward records that layout for the back-trace kernels.  Which rows a launch
+// keeps is the history mode, a WaveHist; launch_wave takes it from the arguments (wave_hist_of) and picks the instantiation from the
+// mode's row of the launch table (wave_launch_of), both in wave_common.hpp.
 // Measured (S = 361, fp32, T = 30000): 19.9 ms for 1024 songs, 35.7 ms for 2048 -- HBM-bound at 4.5-5 TB/s of real
 // traffic.
-#include <type_traits>
-
-#include "device_common.hpp"
+#include "wave_common.hpp"
 
 namespace vit {
-
-namespace {
-
-template <int NPL, typename ET>
-struct RowIO;
-
-// float32 emissions: NPL consecutive columns as 16- and 8-byte pieces
-template <int NPL>
-struct RowIO<NPL, float> {
-    static __device__ __forceinline__ void load(const float* __restrict__ p, float (&e)[NPL]) {
-        int k = 0;
-#pragma unroll
-        for (; k + 3 < NPL; k += 4) { const f32x4_u v = *reinterpret_cast<const f32x4_u*>(p + k); e[k] = v.x; e[k + 1] = v.y; e[k + 2] = v.z; e[k + 3] = v.w; }
-#pragma unroll
-        for (; k + 1 < NPL; k += 2) { const f32x2_u v = *reinterpret_cast<const f32x2_u*>(p + k); e[k] = v.x; e[k + 1] = v.y; }
-        if (k < NPL) e[k] = p[k];
-    }
-};
-template <int NPL>
-struct RowIO<NPL, __half> {
-    static __device__ __forceinline__ void load(const __half* __restrict__ ph, float (&e)[NPL]) {
-        const _Float16* p = reinterpret_cast<const _Float16*>(ph);
-        int k = 0;
-#pragma unroll
-        for (; k + 3 < NPL; k += 4) { const f16x4_u v = *reinterpret_cast<const f16x4_u*>(p + k); e[k] = (float)v.x; e[k + 1] = (float)v.y; e[k + 2] = (float)v.z; e[k + 3] = (float)v.w; }
-#pragma unroll
-        for (; k + 1 < NPL; k += 2) { const f16x2_u v = *reinterpret_cast<const f16x2_u*>(p + k); e[k] = (float)v.x; e[k + 1] = (float)v.y; }
-        if (k < NPL) e[k] = (float)p[k];
-    }
-};
-
-template <int NPL>
-__device__ __forceinline__ void store_row(float* __restrict__ p, const float (&d)[NPL]) {
-    int k = 0;
-#pragma unroll
-    for (; k + 3 < NPL; k += 4) { f32x4_u v; v.x = d[k]; v.y = d[k + 1]; v.z = d[k + 2]; v.w = d[k + 3]; *reinterpret_cast<f32x4_u*>(p + k) = v; }
-#pragma unroll
-    for (; k + 1 < NPL; k += 2) { f32x2_u v; v.x = d[k]; v.y = d[k + 1]; *reinterpret_cast<f32x2_u*>(p + k) = v; }
-    if (k < NPL) p[k] = d[k];
-}
-
-}  // namespace
 
 // NPL states per lane, D window half-width, NX extra columns, PF emission rows in flight, WPS minimum waves per SIMD the
 // register budget must allow.
@@ -84,25 +42,18 @@ __device__ __forceinline__ void store_row(float* __restrict__ p, const float (&d
 // and the back-trace kernels then find the scalars of three frames in ONE line (the carrier row t - t % 3 + 2; B = 2048: -8 % / -13 %).  No branch surrounds a memory instruction, so the in-order vmcnt
 // of the emission prefetch is exact.  The back-trace is told the column offset and the column of M (BtArgs::col0, mcol).
 //
-// HM (history mode).  0: every delta row is stored (row t of a song at hist + t * 64*NPL).  1: only the rows of EVEN frames are
-// stored (row t/2); lane 0's idle slots of row t carry, behind M_t and delta_t of the extra columns, the same scalars of the odd
-// frame t-1 -- they are still in scalar registers when row t is stored, so the odd frames cost no store at all.  The back-trace
-// (backtrace_half.hip) rebuilds the 32 delta values of an odd frame that it needs from the stored row before it and the
-// emission row, with the very sums and maxima of this kernel's recursion: 768 instead of 1536 history bytes per frame.
-// 5: checkpoints only (vit_decode_checkpointed, pass 1): row (t + 1) / K - 1 for the frames t with (t + 1) % K == 0 -- the row
-// in front of every segment of K frames; every other frame's store goes to one scratch row per song (the same address over
-// and over: it stays in L2), so that no branch surrounds a store.
-//
-// 6: a segment (vit_decode_checkpointed pass 2; a mode of its own so that the t_begin arithmetic stays out of HM 0 -- folded into
-// HM 0 it cost the full-history kernel 25 %: 19.9 -> 25.1 ms at B = 1024): every row like HM 0, but FwdArgs::t_begin > 0 resumes from init_rows[song] = delta_{t_begin - 1} in
-// slot order (a checkpoint row; lane 0's scalar slots are idle slots and are reset to -inf), computes frames t_begin ..
-// min(t_end, T_b) - 1 and stores row t at t - t_begin; the terminal state is pass 1's business.
-//
-// 9 / 8: the two passes of the packed checkpointed decode (vit_decode_packed_checkpointed; FwdArgs::ckpt_base / unit_song).  9 = the slot walk
-// of HM 7 with the stores of HM 5: song b keeps the rows in front of its segments 1 .. n_b - 1 (frames t with (t + 1) % K == 0 and
-// t + 1 < T_b) at rows ckpt_base[b] .. of hist, every other store goes to scratch row hist_rows + slot.  8 = HM 6 per UNIT: wave u
-// recomputes the K frames of segment unit_seg[u] of song unit_song[u] from its checkpoint row (segment 0: from the prior) into rows
-// u * hist_rows .. of hist; the unit's song, segment and checkpoint row are loaded once per wave, in front of the frame loop.
+// HM, the history mode (WaveHist, wave_common.hpp: its members, the properties the kernel reads -- WaveHistTraits --, the function
+// from FwdArgs to the mode and the table of what each mode instantiates).  Full: every row.  Half: row t/2 of the EVEN frames; lane 0's
+// idle slots carry, behind M_t and delta_t of the extra columns, the same scalars of the odd frame t-1 -- still in scalar registers
+// when row t is stored, so the odd frames cost no store at all -- and the back-trace (backtrace_half.hip) rebuilds the 32 delta values
+// of an odd frame that it needs with the very sums and maxima of this recursion: 768 instead of 1536 history bytes per frame.
+// CkptPass: row (t + 1) / K - 1 for the frames t with (t + 1) % K == 0, the row in front of every segment of K frames; every other
+// store goes to one scratch row per song (the same address over and over: it stays in L2), so that no branch surrounds a store.
+// Segment: resumes from init_rows[song] = delta_{t_begin - 1} in slot order (a checkpoint row; lane 0's scalar slots are idle slots and
+// are reset to -inf), computes frames t_begin .. min(t_end, T_b) - 1 and stores row t at t - t_begin.  A mode of its own so that the
+// t_begin arithmetic stays out of Full: folded in, it cost the full-history kernel 25 % (19.9 -> 25.1 ms at B = 1024).
+// PackedCkptPass / PackedSegment: the same two per slot / per unit (FwdArgs::ckpt_base, unit_song in kernels.hpp); a unit's song,
+// segment and checkpoint row are loaded once per wave, in front of the frame loop.
 //
 // UV >= 1 (one extra column and it is the last state, S - 1 = slot 64*NPL - 1 whatever S): delta of the extra column is a plain
 // v_readlane of lane 63's last slot instead of a select chain over the lane's slots (which the compiler turned into an LDS round
@@ -112,23 +63,23 @@ __device__ __forceinline__ void store_row(float* __restrict__ p, const float (&d
 // their maximum are formed ONCE per lane and once for slot 5 (4 adds + 2 max instead of 12 adds, and six two-operand maxima
 // instead of six max3), and delta of the extra column is a plain v_readlane of lane 63's slot 5.  UV = 3: the same with three groups of
 // slots, {0,1,2} {3,4} {5} -- S = 321 (msnet / dcnet / ftanet), whose idle slots end in the middle of lane 10 (6 adds + 3 max).
-template <int NPL, int D, int NX, int PF, int WPS, int HM, typename ET, int UV = 0>
+template <int NPL, int D, int NX, int PF, int WPS, WaveHist HM, typename ET, int UV = 0>
 __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
     constexpr int H = wave_halo(NPL, D);
     constexpr int NG = 2 * H + 1;              // lane groups of the neighbourhood
     constexpr int NPM = wave_pairs(D);
     constexpr int SDW = 64 * NPL;              // history row stride of this form
     static_assert(NPL <= 8 && NPL % 2 == 0 && NX <= kWaveMaxExtras && NX + 1 <= NPL && PF >= 1, "geometry (source pairs never straddle two lanes)");
-    static_assert(HM != 1 || 2 * (NX + 1) <= NPL, "half history: lane 0 carries the scalars of two frames");
+    constexpr WaveHistTraits HT = wave_hist_traits(HM);
+    constexpr bool HALF = HT.rows == WaveRows::Even, CKPT = HT.rows == WaveRows::Checkpoints;
+    static_assert(!HALF || 2 * (NX + 1) <= NPL, "half history: lane 0 carries the scalars of two frames");
     static_assert(UV == 0 || NX == 1, "last-state / uniform-lane forms: one extra column");
     static_assert(UV < 2 || NPL == 6, "uniform-lane forms: six states per lane");
     constexpr bool U5 = UV == 2, U3 = UV == 3;
-    constexpr bool PK = HM == 7 || HM == 9;    // packed batch: this wave is a SLOT that walks a list of songs back to back
-    constexpr bool SG = HM == 6 || HM == 8;    // one segment, resumed from a checkpoint row
-    constexpr bool PO = PK || HM == 8;         // a song's rows come from the offsets
-    // every row stored, one extra column: row t carries the scalars of frames t, t-1 and t-2 (columns 0 1 | 2 3 | 4 5 of lane 0), so that
-    // the back-trace finds the scalars of three frames in ONE line (kernels.hpp wave_aux_frames / wave_aux_row)
-    constexpr bool A3 = (HM == 0 || HM == 6 || HM == 7 || HM == 8) && NX == 1 && NPL >= 6;      // (and six idle slots: run time, l0a below)
+    constexpr bool PK = HT.slot_walk;          // packed batch: this wave is a SLOT that walks a list of songs back to back
+    constexpr bool SG = HT.segment;            // one segment, resumed from a checkpoint row
+    constexpr bool PO = HT.offsets;            // a song's rows come from the offsets
+    constexpr bool A3 = HT.aux3 && NX == 1 && NPL >= 6;      // rows carry the scalars of three frames (and six idle slots: run time, l0a below; kernels.hpp wave_aux_row)
     const int S = a.S;
     const int lane = threadIdx.x & 63;
     const int wid = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -137,17 +88,7 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
     const int o = SDW - S;                                 // idle leading slots (>= 1)
     const int j0 = NPL * lane - o;                         // state of slot 0 of this lane (negative: idle)
     const bool l0a = A3 && lane == 0 && wave_aux_frames(NPL, S, NX) == 3 && !(a.wave_flags & 4);   // this lane's slots 2 .. 5 carry the scalars of frames t-1, t-2
-    f32x2 aw[NPL][NPM];
-    {
-        const float* __restrict__ tv = reinterpret_cast<const float*>(a.image + a.off_tabV);
-#pragma unroll
-        for (int k = 0; k < NPL; ++k)
-#pragma unroll
-            for (int m = 0; m < NPM; ++m) {
-                aw[k][m].x = tv[(((size_t)k * NPM + m) * 2 + 0) * 64 + lane];
-                aw[k][m].y = tv[(((size_t)k * NPM + m) * 2 + 1) * 64 + lane];
-            }
-    }
+#include "wave_lane_weights.inc"
     float cj[NPL];
     float xa[NX > 0 ? NX : 1][NPL];
     int xl[NX > 0 ? NX : 1];                               // lane that owns extra column x
@@ -172,55 +113,42 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
     const int k_begin = PK ? a.slot_begin[wid] : 0, k_end = PK ? a.slot_begin[wid + 1] : 1;
     for (int kk = k_begin; kk < k_end; ++kk) {
     // ---------------- this song: emission rows, history rows, length
-    const int song = PK ? a.slot_songs[kk] : (HM == 8 ? a.unit_song[wid] : wid);
+    const int song = PK ? a.slot_songs[kk] : (HT.unit ? a.unit_song[wid] : wid);
     const long long off = PO ? a.offsets[song] : (long long)song * a.T;           // first emission row of the song in the tensor
     const int T = PO ? (int)(a.offsets[song + 1] - off) : a.T;                     // rows the song owns (packed: its length)
-    const int useg = HM == 8 ? a.unit_seg[wid] : 0;                            // (HM 8) the segment this wave recomputes
-    const int t0 = HM == 6 ? a.t_begin : (HM == 8 ? useg * a.ckpt_every : 0);  // first frame of this launch
+    const int useg = HT.unit ? a.unit_seg[wid] : 0;                            // (units) the segment this wave recomputes
+    const int t0 = !SG ? 0 : (HT.unit ? useg * a.ckpt_every : a.t_begin);      // first frame of this launch
     const int Tl = PO ? T : song_length(a.lengths, song, T);
-    const int te = HM == 8 ? t0 + a.ckpt_every : a.t_end;
+    const int te = HT.unit ? t0 + a.ckpt_every : a.t_end;
     const int Tb = SG && te < Tl ? te : Tl;                                    // one past the last frame of this launch
     if (Tb <= t0) continue;                                                    // (segments: the song ended before this one)
     const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)off * S;
-    // hist_rows = T (HM 0), (T + 1) / 2 (HM 1), segments (HM 5), K + 1 (HM 6, 8: per song / per unit), all checkpoint rows (HM 9)
-    float* __restrict__ hist = a.hist + (HM == 9 ? (size_t)0 : (HM == 7 ? (size_t)off : (size_t)(HM == 8 ? wid : song) * a.hist_rows)) * SDW;
-    const long long ck0 = HM == 9 ? a.ckpt_base[song] : 0;                     // (HM 9) the song's first checkpoint row
+    // hist_rows = T (Full), (T + 1) / 2 (Half), segments (CkptPass), K + 1 (Segment, PackedSegment: per song / per unit), all checkpoint rows (PackedCkptPass)
+    float* __restrict__ hist = a.hist + (HT.base == WaveBase::Shared ? (size_t)0 : (HT.base == WaveBase::Offset ? (size_t)off : (size_t)(HT.base == WaveBase::Unit ? wid : song) * a.hist_rows)) * SDW;
+    const long long ck0 = HT.base == WaveBase::Shared ? a.ckpt_base[song] : 0; // (PackedCkptPass) the song's first checkpoint row
     // emission columns of this lane in rows >= 1 (see above): the leading lanes reach back into the row in front -- of the same song,
     // or (packed, row 0 is never loaded this way) of the song before it in the tensor; the first row of the tensor has none
     const long ecol = (T > 1 || off > 0) ? (long)j0 : (long)(j0 < 0 ? 0 : j0);
     const int row_min = T > 1 ? 1 : 0;
     auto load_row = [&](int row, float (&e)[NPL]) {
         row = row < row_min ? row_min : row;
-        RowIO<NPL, ET>::load(E + (size_t)row * S + ecol, e);
+        load_cols<NPL>(E + (size_t)row * S + ecol, e);
     };
-    // history row t in slot order; lane 0's leading slots (always idle: o > NX is checked by the plan) carry M_t and a
-    // copy of delta_t of the extra columns, so that the sparse back-trace finds its per-row scalars in ONE cache line
-    // (HM 1: row t/2 of an even frame t; Mp / xp = the scalars of frame t-1, slots 1+NX .. 1+2*NX)
+    // history row t in slot order (Half: row t/2 of an even frame t; Mp / xp = the scalars of frame t-1, slots 1+NX .. 1+2*NX)
     auto store_hist = [&](const int t, const float (&d)[NPL], const float M, const float (&xd)[NX > 0 ? NX : 1], const float Mp,
                           const float (&xp)[NX > 0 ? NX : 1], const float Mq, const float xq) {
-        float v[NPL];
-#pragma unroll
-        for (int k = 0; k < NPL; ++k) v[k] = d[k];
-        v[0] = lane == 0 ? M : v[0];
-#pragma unroll
-        for (int x = 0; x < NX; ++x) v[1 + x] = lane == 0 ? xd[x] : v[1 + x];
-        if (A3) {
-            v[2] = l0a ? Mp : v[2];
-            v[3] = l0a ? xp[0] : v[3];
-            v[4] = l0a ? Mq : v[4];
-            v[5] = l0a ? xq : v[5];
-        }
-        if (HM == 1) {
+#include "wave_hist_row.inc"
+        if (HALF) {
             v[1 + NX] = lane == 0 ? Mp : v[1 + NX];
 #pragma unroll
             for (int x = 0; x < NX; ++x) v[2 + NX + x] = lane == 0 ? xp[x] : v[2 + NX + x];
         }
-        size_t row = HM == 1 ? t >> 1 : t - t0;
-        if (HM == 5) {
+        size_t row = HALF ? t >> 1 : t - t0;
+        if (CKPT && !PK) {
             const int q = (t + 1) / a.ckpt_every;
             row = (t + 1) - q * a.ckpt_every == 0 && q - 1 < a.hist_rows - 1 ? q - 1 : a.hist_rows - 1;     // checkpoint, else the scratch row
         }
-        if (HM == 9) {
+        if (CKPT && PK) {
             const int q = (t + 1) / a.ckpt_every;
             row = (t + 1) - q * a.ckpt_every == 0 && t + 1 < T ? (size_t)(ck0 + q - 1) : (size_t)(a.hist_rows + wid);   // checkpoint, else this slot's scratch row
         }
@@ -228,7 +156,7 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
     };
     // delta of the extra columns, wave-uniform
     auto extra_deltas = [&](const float (&d)[NPL], float (&xd)[NX > 0 ? NX : 1]) {
-        if (UV >= 1) { xd[0] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d[NPL - 1]), 63)); return; }   // state S-1 = lane 63, last slot
+        if (UV >= 1) { xd[0] = wave_last_delta<NPL>(d); return; }
 #pragma unroll
         for (int x = 0; x < NX; ++x) {
             float v = d[0];
@@ -248,17 +176,11 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
             d[k] = j >= 0 ? lpi[j] + load_e<ET>(E + j) : -INFINITY;
         }
     } else {
-        const float* __restrict__ ir = a.init_rows + (HM == 8 ? (size_t)(a.ckpt_base[song] + useg - 1) * SDW : (size_t)song * a.init_stride) + NPL * lane;
+        const float* __restrict__ ir = a.init_rows + (HT.unit ? (size_t)(a.ckpt_base[song] + useg - 1) * SDW : (size_t)song * a.init_stride) + NPL * lane;
 #pragma unroll
         for (int k = 0; k < NPL; ++k) d[k] = j0 + k >= 0 ? ir[k] : -INFINITY;
     }
-    auto frame_max = [&](const float (&v)[NPL]) -> float {
-        float loc = v[0];
-#pragma unroll
-        for (int k = 1; k < NPL; ++k) loc = fmaxf(loc, v[k]);
-        return wave_max_all(loc);
-    };
-    float M = frame_max(d);
+    float M = wave_frame_max<NPL>(d);
     float xd[NX > 0 ? NX : 1] = {};
     extra_deltas(d, xd);
     if (t0 == 0) store_hist(0, d, M, xd, M, xd, M, xd[0]);
@@ -279,32 +201,32 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
         float xp[NX > 0 ? NX : 1];
 #pragma unroll
         for (int x = 0; x < (NX > 0 ? NX : 1); ++x) xp[x] = xd[x];
-        M = frame_max(d);
+        M = wave_frame_max<NPL>(d);
         extra_deltas(d, xd);               // for the next frame's candidates, and for the history row
-        if (decltype(stored)::value && HM != 2 && HM != 4) store_hist(t, d, M, xd, Mp, xp, Mb, xb);
+        if (decltype(stored)::value && HT.stores) store_hist(t, d, M, xd, Mp, xp, Mb, xb);
         if (A3) { Mb = Mp; xb = xp[0]; }
-        if (HM != 3 && HM != 4) load_row(t + PF < Tb ? t + PF : Tb - 1, e);     // (HM 2 / 3 / 4: timing builds only -- no stores / no loads / neither)
+        if (HT.loads) load_row(t + PF < Tb ? t + PF : Tb - 1, e);                // (no stores / no loads: the timing-only modes)
     };
     // The loop body is a whole number of frame pairs when only even frames are stored: t is odd at its top, frame t + q is
     // even for odd q, and "store or not" is a compile-time property of each unrolled frame (no branch around a store).
-    constexpr int UN = (HM == 1 && (PF & 1)) ? 2 * PF : PF;
+    constexpr int UN = (HALF && (PF & 1)) ? 2 * PF : PF;
     int t = t1;
     for (; t + UN - 1 < Tb; t += UN) {
 #pragma unroll
         for (int q = 0; q < UN; ++q) {
-            if (HM != 1 || (q & 1)) frame(t + q, er[q % PF], std::true_type{});
+            if (!HALF || (q & 1)) frame(t + q, er[q % PF], std::true_type{});
             else frame(t + q, er[q % PF], std::false_type{});
         }
     }
 #pragma unroll
     for (int q = 0; q < UN - 1; ++q)
         if (t + q < Tb) {
-            if (HM != 1 || (q & 1)) frame(t + q, er[q % PF], std::true_type{});
+            if (!HALF || (q & 1)) frame(t + q, er[q % PF], std::true_type{});
             else frame(t + q, er[q % PF], std::false_type{});
         }
 
     // ---------------- terminal state: lowest-index argmax of delta_{Tb-1} (not in a segment launch)
-    if (HM != 8 && (HM != 6 || a.t_end >= T)) {
+    if (!HT.unit && (!SG || a.t_end >= T)) {
 #include "wave_terminal.inc"
         if (lane == 63) {
             a.last_state[song] = bi == kBig ? 0 : bi;
@@ -314,92 +236,48 @@ __global__ void __launch_bounds__(256, WPS) wave_forward_kernel(FwdArgs a) {
     }   // songs of this slot
 }
 
-// the instantiations of the packed batch (HM 7 below) for the two passes of the packed checkpointed decode: n waves
-template <int NPL, int D, int NX, int PF1, int PF2, int HM, typename ET>
-static hipError_t launch_wave_pk(const FwdArgs& a, int n, hipStream_t st) {
-    const int pgrid = (n + 3) / 4;
-    if (n <= 1024 && ((a.wave_flags & 2) || NX == 2)) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, HM, ET>), dim3(pgrid), dim3(256), 0, st, a);
-    else if (NX == 1 && NPL == 6 && a.wave_u5 == 2) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET, (NX == 1 && NPL == 6) ? 2 : 0>), dim3(pgrid), dim3(256), 0, st, a);
-    else if (NX == 1 && NPL == 6 && a.wave_u5 == 3) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET, (NX == 1 && NPL == 6) ? 3 : 0>), dim3(pgrid), dim3(256), 0, st, a);
-    // (the last-state form alone, UV 1 -- "wave_uniform" 2 -- only in pass 1: the fp16 instantiation of HM 8 takes 292 bytes of scratch, the general one none)
-    else if (NX == 1 && HM != 8 && a.wave_u5 >= 1) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET, (NX == 1 && HM != 8) ? 1 : 0>), dim3(pgrid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET>), dim3(pgrid), dim3(256), 0, st, a);
+// One mode's launch: the register form and the UV form, chosen once from the mode's row of the table (wave_launch_of, wave_common.hpp).
+// 512 registers (one wave per SIMD, PF1 emission rows in flight: full history, B = 1024, PF 2 / 3 / 4 / 6 / 8 -> 24.6 / 21.4 / 19.9 / 21.5 /
+// 33.8 ms) against 256 registers (two waves per SIMD, PF2 rows).  With the half history the kernel no longer waits for memory and the
+// 256-register code is the faster one even with a single wave on each SIMD (B = 1024, full / half history: 512-register form 19.9 /
+// 21.3 ms, 256-register form 19.7 / 16.5 ms), so it runs at every batch size unless a second extra column pushes it into scratch.
+template <int NPL, int D, int NX, WaveHist HM, typename ET>
+static hipError_t launch_wave_mode(const FwdArgs& a, hipStream_t st) {
+    constexpr WaveLaunch L = wave_launch_of(HM);
+    constexpr int PF1 = NX == 2 ? 3 : 4, PF2 = NX == 2 ? 2 : 3;
+    constexpr int U1 = L.uv1 && NX == 1 ? 1 : 0, U2 = L.uv23 && NX == 1 && NPL == 6 ? 2 : 0, U3 = U2 ? 3 : 0;   // 0: the mode or the geometry has no such form
+    const int n = L.by_slots ? a.n_slots : (int)a.B;
+    const dim3 grid((n + 3) / 4), block(256);
+    if (n <= 1024 && !(L.flag0 && (a.wave_flags & 1)) && ((a.wave_flags & 2) || NX == 2))
+        hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, HM, ET>), grid, block, 0, st, a);
+    else if (U2 && a.wave_u5 == 2) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET, U2>), grid, block, 0, st, a);
+    else if (U3 && a.wave_u5 == 3) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET, U3>), grid, block, 0, st, a);
+    else if (U1 && a.wave_u5 >= 1) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET, U1>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, HM, ET>), grid, block, 0, st, a);
     return hipGetLastError();
 }
 
 template <int NPL, int D, int NX, typename ET>
 static hipError_t launch_wave_x(const FwdArgs& a, hipStream_t st) {
-    const int grid = (int)((a.B + 3) / 4);
-    // Two instantiations: 512 registers (one wave per SIMD, PF1 emission rows in flight) and 256 registers (two waves per
-    // SIMD, PF2 rows).  Round 2 took the first one up to 1024 songs (full history, B = 1024: PF 2 / 3 / 4 / 6 / 8 -> 24.6 /
-    // 21.4 / 19.9 / 21.5 / 33.8 ms).  With the half history the kernel no longer waits for memory and the 256-register
-    // code is the faster one even with a single wave on each SIMD (B = 1024, gpurun_out/r3a/wave_ablate.log: 512-register
-    // form full / half history 19.9 / 21.3 ms, 256-register form 19.7 / 16.5 ms; without any load or store 16.0 ms), so it
-    // runs at every batch size unless a second extra column pushes it into scratch.
-    constexpr int PF1 = NX == 2 ? 3 : 4, PF2 = NX == 2 ? 2 : 3;
-    const bool one = a.B <= 1024 && !(a.wave_flags & 1) && ((a.wave_flags & 2) || NX == 2);
+    switch (wave_hist_of(a)) {
+#define VIT_WAVE_MODE(M) case WaveHist::M: return launch_wave_mode<NPL, D, NX, WaveHist::M, ET>(a, st);
+        VIT_WAVE_MODE(Full) VIT_WAVE_MODE(Half) VIT_WAVE_MODE(CkptPass) VIT_WAVE_MODE(Segment)
+        VIT_WAVE_MODE(Packed) VIT_WAVE_MODE(PackedSegment) VIT_WAVE_MODE(PackedCkptPass)
 #ifdef VIT_TIMING_HOOKS
-    // result-breaking ablations (make TIMING=1 only): bits 0 / 1 of the timing mask drop the history stores / the emission loads
-    if (a.debug & 3) {
-        const int hm = (a.debug & 3) + 1;
-        if (hm == 2) { if (one) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, 2, ET>), dim3(grid), dim3(256), 0, st, a);
-                       else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 2, ET>), dim3(grid), dim3(256), 0, st, a); }
-        else if (hm == 3) { if (one) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, 3, ET>), dim3(grid), dim3(256), 0, st, a);
-                            else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 3, ET>), dim3(grid), dim3(256), 0, st, a); }
-        else { if (one) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, 4, ET>), dim3(grid), dim3(256), 0, st, a);
-               else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 4, ET>), dim3(grid), dim3(256), 0, st, a); }
-        return hipGetLastError();
-    }
+        VIT_WAVE_MODE(NoStores) VIT_WAVE_MODE(NoLoads) VIT_WAVE_MODE(NoLoadsNoStores)
 #endif
-    if (a.ckpt_base) {          // packed checkpointed decode: pass 2 (one wave per segment unit) / pass 1 (one wave per slot); the variants of the packed batch
-        return a.unit_song ? launch_wave_pk<NPL, D, NX, PF1, PF2, 8, ET>(a, (int)a.B, st) : launch_wave_pk<NPL, D, NX, PF1, PF2, 9, ET>(a, a.n_slots, st);
-    }
-    if (a.offsets) {            // packed batch (vit_decode_packed): one wave per slot, full history, rows at the songs' offsets
-        const int pgrid = (a.n_slots + 3) / 4;
-        if (a.n_slots <= 1024 && ((a.wave_flags & 2) || NX == 2)) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, 7, ET>), dim3(pgrid), dim3(256), 0, st, a);
-        else if (NX == 1 && NPL == 6 && a.wave_u5 == 2) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 7, ET, (NX == 1 && NPL == 6) ? 2 : 0>), dim3(pgrid), dim3(256), 0, st, a);
-        else if (NX == 1 && NPL == 6 && a.wave_u5 == 3) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 7, ET, (NX == 1 && NPL == 6) ? 3 : 0>), dim3(pgrid), dim3(256), 0, st, a);
-        else if (NX == 1 && a.wave_u5 >= 1) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 7, ET, NX == 1 ? 1 : 0>), dim3(pgrid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 7, ET>), dim3(pgrid), dim3(256), 0, st, a);
-        return hipGetLastError();
-    }
-    if (a.ckpt_every > 0) {
-        if (one) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, 5, ET>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 5, ET>), dim3(grid), dim3(256), 0, st, a);
-    } else if (a.t_begin > 0 || a.t_end < a.T) {
-        if (one) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, 6, ET>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 6, ET>), dim3(grid), dim3(256), 0, st, a);
-    } else if (a.hist_half) {
-        if (one) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, 1, ET>), dim3(grid), dim3(256), 0, st, a);
-        else if (NX == 1 && NPL == 6 && a.wave_u5 == 2) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 1, ET, (NX == 1 && NPL == 6) ? 2 : 0>), dim3(grid), dim3(256), 0, st, a);
-        else if (NX == 1 && NPL == 6 && a.wave_u5 == 3) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 1, ET, (NX == 1 && NPL == 6) ? 3 : 0>), dim3(grid), dim3(256), 0, st, a);
-        else if (NX == 1 && a.wave_u5 >= 1) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 1, ET, NX == 1 ? 1 : 0>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 1, ET>), dim3(grid), dim3(256), 0, st, a);
-    } else {
-        if (one) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF1, 1, 0, ET>), dim3(grid), dim3(256), 0, st, a);
-        else if (NX == 1 && NPL == 6 && a.wave_u5 == 2) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 0, ET, (NX == 1 && NPL == 6) ? 2 : 0>), dim3(grid), dim3(256), 0, st, a);
-        else if (NX == 1 && NPL == 6 && a.wave_u5 == 3) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 0, ET, (NX == 1 && NPL == 6) ? 3 : 0>), dim3(grid), dim3(256), 0, st, a);
-        else if (NX == 1 && a.wave_u5 >= 1) hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 0, ET, NX == 1 ? 1 : 0>), dim3(grid), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((wave_forward_kernel<NPL, D, NX, PF2, 2, 0, ET>), dim3(grid), dim3(256), 0, st, a);
-    }
-    return hipGetLastError();
-}
-
-template <int NPL, int D, typename ET>
-static hipError_t launch_wave_n(const FwdArgs& a, hipStream_t st) {
-    switch (a.n_extras) {
-        case 0: return launch_wave_x<NPL, D, 0, ET>(a, st);
-        case 1: return launch_wave_x<NPL, D, 1, ET>(a, st);
-        case 2: return launch_wave_x<NPL, D, 2, ET>(a, st);
+#undef VIT_WAVE_MODE
         default: return hipErrorInvalidConfiguration;
     }
 }
 
 template <typename ET>
 static hipError_t launch_wave_e(const FwdArgs& a, hipStream_t st) {
-    if (a.wave_dk != 14) return hipErrorInvalidConfiguration;
-    switch (a.wave_npl) {
-        case 6: return launch_wave_n<6, 14, ET>(a, st);
+    if (a.wave_dk != 14 || a.wave_npl != 6) return hipErrorInvalidConfiguration;   // the one instantiated geometry
+    switch (a.n_extras) {
+        case 0: return launch_wave_x<6, 14, 0, ET>(a, st);
+        case 1: return launch_wave_x<6, 14, 1, ET>(a, st);
+        case 2: return launch_wave_x<6, 14, 2, ET>(a, st);
         default: return hipErrorInvalidConfiguration;
     }
 }
