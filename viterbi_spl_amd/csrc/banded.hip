@@ -320,7 +320,14 @@ __global__ void __launch_bounds__((NWT + (DW ? 3 : 2)) * 64) banded_forward_kern
 // emission rows of a round of twelve frames hang off one buffer descriptor each; a frame's row is the instruction's scalar offset.
 // ---------------------------------------------------------------------------------------
 // (kSplitFullWaves, kSplitHalfWaves, kSplitStates and FloorSplitLds: banded_floor.inc, next to FloorLds)
-template <int NXT, int PF, typename ET, bool WPR = false>
+// s_waitcnt immediate of gfx9: vmcnt in bits 3:0 and 15:14, expcnt (left open) in 6:4, lgkmcnt in 11:8
+constexpr int split_waitcnt(int vm, int lgkm) { return (vm & 15) | ((vm >> 4) << 14) | (7 << 4) | (lgkm << 8); }
+constexpr int kNoVmWait = 63;
+// f(std::integral_constant<int, K>) for K = 0, 1, ...: the unrolled frames and window groups need their index as a constant
+// (the s_waitcnt immediate is derived from it)
+template <int... K, typename F>
+__device__ __forceinline__ void split_frames(std::integer_sequence<int, K...>, F&& f) { (f(std::integral_constant<int, K>{}), ...); }
+template <int NXT, int PF, typename ET, bool WPR = false, bool XQ = false>
 __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) banded_floor_split_forward_kernel(FwdArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int W = 32;
@@ -368,7 +375,8 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
     const int sh = a.win_shift;                                           // (see banded_floor_forward_kernel)
     const int lov = (tvalid ? lo : 0) + sh;
     const float* rp = dls + 4 + (lov & 3) * DC + (lov & ~3) + 16 * hh;    // (half of the) window in the copy that aligns it
-    float* fmp = fmg + fm_slot(lane);
+    float* fmp = fmg + fm_slot((XQ && is_x) ? (lane | 1) : lane);
+    static_assert(!XQ || NXT == 1, "the extra column leaves M by address only where the launcher proved its quad idle");
 
     for (int k = tid; k < L::reset; k += NW * 64) dls[k] = -INFINITY;
     __syncthreads();
@@ -413,7 +421,8 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
         auto produce = [&](const float dn, const int WB, const int G, const int Z) {
 #pragma unroll
             for (int c = 0; c < (HALF ? 2 : 4); ++c) wp[WB * BUF + floor_copy_off(DC, c)] = dn;
-            fm_publish(fmp + G * kFmGroupFloats, (NXL > 0 && is_x) ? -INFINITY : dn);
+            // XQ: the extra column's lanes publish into a slot nobody reads (fmp above), every other plan keeps the select
+            fm_publish(fmp + G * kFmGroupFloats, (!XQ && NXL > 0 && is_x) ? -INFINITY : dn);
             // (the resetting wave is a role of its own: no wave test per frame, the one-target kernel's costs three SALU slots)
             if constexpr (RESETS) fmg[Z * kFmGroupFloats + lane] = -INFINITY;
         };
@@ -450,14 +459,18 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             eb = E + (size_t)r * S;
             elim = (unsigned)ahead * rowE;
         };
-        auto frame = [&](float& e_slot, const int u) {
+        auto frame = [&](float& e_slot, auto uc) {
+            constexpr int u = decltype(uc)::value;
             const int RB = u & 1, WB = RB ^ 1;
             const int GR = u % kFmGroups, GW = (u + 1) % kFmGroups, GZ = (u + 2) % kFmGroups;
             const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
             float xd[NXL > 0 ? NXL : 1];
             f32x4 fq;
             float m0, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
-            // small reads first, the window right behind them, then M (see banded_floor_forward_kernel)
+            // The small reads first (extra columns, then the M slots), the window quads right behind them and nothing after: the window
+            // quads are the LAST LDS operations of the frame's read burst (the two quads of a pair in either order).  The paired waits below count on that
+            // (lgkmcnt(2) = "all but the last two quads"); a read moved behind the window would turn them into waits for less than they
+            // name, and the compiler would add its own wait again.
 #pragma unroll
             for (int k = 0; k < NXL; ++k) xd[k] = dls[xo[k] + RB * BUF];
             fq = reinterpret_cast<const f32x4*>(fmg + GR * kFmGroupFloats)[0];
@@ -468,10 +481,27 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             __builtin_amdgcn_sched_barrier(0);
             const float M = fmaxf(fmaxf(fq.x, fq.y), fmaxf(fq.z, fq.w));
             m0 = M + cj;
+            asm volatile("" ::"v"(m0));   // M + c_j stays in front of the window sums (with the explicit waits below the add otherwise sinks behind them)
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int w = 0; w < WL; w += 8) {
-                const f32x4 da = dw[w / 4], db = dw[w / 4 + 1];
+            split_frames(std::make_integer_sequence<int, WL / 8>{}, [&](auto gc) {
+                constexpr int w = 8 * decltype(gc)::value;
+                constexpr bool last = w + 8 == WL;
+                // The emission of this frame was requested PF frames ago: behind it stand the PF - 1 younger prefetch loads and one row
+                // store per frame since (u in the first round, where the prologue issued the loads back to back; 2 (PF - 1) >= PF - 1 + u
+                // operations in every later round and in the tails), and vmcnt retires in order.  Stating that bound together with the
+                // frame's last window wait saves the s_waitcnt vmcnt the compiler otherwise puts in front of "+ e".
+                constexpr int vmw = PF - 1 + u;
+                // Counted on this kernel's frame: ONE store (row_store_f32) and ONE load (row_load_e) per frame and role.  More VMEM per
+                // frame (the probe instantiations) only makes the bound wait longer than needed; fewer would make it too weak.
+                static_assert(vmw <= 2 * (PF - 1) && 2 * (PF - 1) < kNoVmWait, "vmcnt bound: one store and one load per frame, 6-bit field");
+                // The late window quads are waited for in pairs: the last four of the full waves' eight, the last two of the half waves'
+                // four.  M and the first quads keep the compiler's stepped waits, which buy the early first max3.
+                constexpr bool pairw = w + 16 >= WL && w >= 8;
+                f32x4 da = dw[w / 4], db = dw[w / 4 + 1];
+                if constexpr (pairw) {
+                    __builtin_amdgcn_s_waitcnt(split_waitcnt(last ? vmw : kNoVmWait, last ? 0 : 2));
+                    asm volatile("" : "+v"(da), "+v"(db));
+                }
                 f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[w + 0], aw[w + 1]};
                 f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[w + 2], aw[w + 3]};
                 f32x2 c2_ = f32x2{db.x, db.y} + f32x2{aw[w + 4], aw[w + 5]};
@@ -481,7 +511,7 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
                 m1 = fmaxf(fmaxf(m1, c1_.x), c1_.y);
                 m2 = fmaxf(fmaxf(m2, c2_.x), c2_.y);
                 m3 = fmaxf(fmaxf(m3, c3_.x), c3_.y);
-            }
+            });
 #pragma unroll
             for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
             float mx = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
@@ -490,12 +520,14 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
 #ifdef VIT_TIMING_HOOKS
             if constexpr (wprobe) wp_.before_publish(dn);
 #endif
+            // (the stored value and the emission offset are formed in front of the publication: the order the measured builds have)
+            const float sv = (HALF && is_fm) ? M : dn;                    // (full waves hold live targets only)
+            const unsigned eso = (unsigned)u * rowE < elim ? (unsigned)u * rowE : elim;
             produce(dn, WB, GW, GZ);
             asm volatile("" ::: "memory");   // the global store / prefetch fill the wait for the LDS write acknowledgement
-            const unsigned eso = (unsigned)u * rowE < elim ? (unsigned)u * rowE : elim;
             // KEEP THIS STORE SINGLE-DWORD: with a register soffset a store wider than 64 bits needs wait states in front of the next write
             // of its data registers that the compiler does not insert -- wrong rows, not reproducibly
-            row_store_f32(hb, hoffb, (HALF && is_fm) ? M : dn, (unsigned)u * rowH);   // (full waves hold live targets only)
+            row_store_f32(hb, hoffb, sv, (unsigned)u * rowH);
             e_slot = row_load_e<ET>(eb, eoffb, eso);
 #ifdef VIT_TIMING_HOOKS
             if constexpr (wprobe) wp_.barrier(); else
@@ -507,16 +539,19 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
 #endif
         clk0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
         rt0 = probe ? __builtin_amdgcn_s_memrealtime() : 0ull;
+        // The half waves are the younger wave of each SIMD and lost the arbitration to the full wave in every frame; with static priority 1
+        // they publish first and the full waves, which have fewer instructions left per frame than the half waves' lag cost, close the frame.
+        // Once per song, in the half-wave roles only (the role is a scalar branch, see below); nothing in the loop.
+        if constexpr (HALF) __builtin_amdgcn_s_setprio(1);
         int t = 1;
         for (; t + PF - 1 < Tb; t += PF) {
             round_bases(t);
-#pragma unroll
-            for (int k = 0; k < PF; ++k) frame(er[k], k);
+            split_frames(std::make_integer_sequence<int, PF>{}, [&](auto k) { frame(er[k], k); });
         }
         round_bases(t);
-#pragma unroll
-        for (int k = 0; k < PF - 1; ++k)
+        split_frames(std::make_integer_sequence<int, PF - 1>{}, [&](auto k) {
             if (t + k < Tb) frame(er[k], k);
+        });
     };
     static_assert(PF % 2 == 0 && PF % kFmGroups == 0, "the unrolled frames must cycle through whole buffer and slot-group rounds");
     if (!half) body(std::false_type{}, std::false_type{});
@@ -785,12 +820,21 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
         if (a.fwd_form == 6 || (a.fwd_form == 0 && a.B <= 256 && std::is_same_v<ET, float>)) {
             constexpr size_t ldss = FloorSplitLds::bytes();
             constexpr int NWS = kSplitFullWaves + kSplitHalfWaves;
+            // The extra column leaves M by address only where its whole quad is otherwise idle: the quad maximum is formed before the
+            // slot is chosen, so the column can only be dropped together with its quad.  One extra column x = S - 1 with x % 4 == 0 is
+            // the publishing lane of its quad and states x + 1 .. x + 3 are idle slots (-inf for the whole song); any other plan
+            // (generic extras, an extra column elsewhere, x % 4 != 0 with live states in the quad) keeps the select.
+            const bool xq = a.n_extras == 1 && a.extras[0] == a.S - 1 && (a.S - 1) % 4 == 0;
 #ifdef VIT_TIMING_HOOKS
-            if ((a.debug & 64) && a.n_extras == 1)
+            if ((a.debug & 64) && xq)
+                hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET, true, true>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
+            else if ((a.debug & 64) && a.n_extras == 1)
                 hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET, true>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
             else
 #endif
-            if (a.n_extras == 1)
+            if (xq)
+                hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET, false, true>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
+            else if (a.n_extras == 1)
                 hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
             else
                 hipLaunchKernelGGL((banded_floor_split_forward_kernel<-1, PF, ET>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
