@@ -80,7 +80,10 @@ typedef struct vit_plan_info {
     int32_t n_extras;       /* extra exception columns shared by most rows */
     int32_t max_window;     /* widest per-row exception window */
     int32_t group_window;   /* window width the banded kernel evaluates per target */
-    int32_t reserved[3];    /* [0] dense rows, [1] one-maximum ("floor") form proven, [2] bit 0: window start affine in the target, bit 1: pair windows proven, bit 2: step structure (dense matrix, piecewise-constant columns), bit 3: wave form (one song per wavefront) available */
+    int32_t reserved[3];    /* [0] dense rows, [1] one-maximum ("floor") form proven, [2] bit 0: window start affine in the target, bit 1: pair windows proven, bit 2: step structure (dense matrix, piecewise-constant columns), bit 3: wave form (one song per wavefront) available.
+                             * Bit 2 means "step structure proven AND the forward step kernel is instantiated for it" (20-bin bands, 9 near bands,
+                             * 705..768 voiced states); a step-structured plan without it (another band width or count, another state count)
+                             * runs the dense forward kernel and still reads the band table, not the matrix rows, in its back-trace. */
     float consts[4];
     int32_t extras[4];
 } vit_plan_info;

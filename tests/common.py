@@ -380,3 +380,84 @@ def edge_cases(seed, A, pi, T, half=None, f16=False, only=None):
         deaths, dl = _dead_batches(T)[0]
         E, E16 = fp16_edges(rng, B, T, S, deaths=deaths)
         yield ("fp16_edges_dead", A, pi, E, E16, dl, lambda s, l, d=deaths, n=dl: premise_dead(s, l, n, d), False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Step-structured matrices (tests/test_step_plan_host.py, tests/test_gpu_step_geometries.py): what analyze_step (csrc/plan.cpp)
+# accepts beyond the one Durrieu geometry the forward step kernels are instantiated for.
+# ---------------------------------------------------------------------------------------------------------------------
+def step_matrix(n, bw, kb, rng, zero_top=False, return_table=False):
+    """logA_T [n + 1, n + 1] float32 with step structure: n voiced states and the unvoiced state n.  For voiced target j and voiced
+    source i  A[j][i] = C[min(|i - j| // bw, kb)][i]: column i is constant in distance bands of bw bins and holds its far value
+    C[kb][i] from distance kb * bw on.  Everything lies on the half-integer grid, so that sums tie exactly and the lowest-index rule
+    decides: the far values are drawn per column from -15 .. -24.5 (ten or more different values in every row: no row constant, so
+    the banded analysis refuses the matrix), each nearer band adds 0, 0.5 or 1 to the next one (a band may equal its neighbour, never
+    lie below it) -- except in source column 0, where it adds 0.5 or 1: consecutive bands differ there, which is how the plan measures
+    bw and kb.  The unvoiced source column is one value for every voiced target, the unvoiced target's row is arbitrary.
+    zero_top=True shifts every column so that its nearest band is exactly +0.  return_table=True: (A, C [kb + 1, n])."""
+    far = -(rng.integers(30, 50, n) / 2)
+    inc = rng.integers(0, 3, (kb, n)) / 2
+    inc[:, 0] = np.maximum(inc[:, 0], 0.5)
+    C = np.empty((kb + 1, n), np.float64)
+    C[kb] = far
+    for k in range(kb - 1, -1, -1):
+        C[k] = C[k + 1] + inc[k]
+    if zero_top:
+        C = C - C[0][None, :]
+        C[C == 0] = 0.0                                                      # (+0, never -0)
+    C = C.astype(np.float32)
+    idx = np.arange(n)
+    band = np.minimum(np.abs(idx[None, :] - idx[:, None]) // bw, kb)         # [target j, source i]
+    A = np.empty((n + 1, n + 1), np.float32)
+    A[:n, :n] = C[band, idx[None, :]]
+    A[:n, n] = np.float32(-(int(rng.integers(8, 40)) / 2))
+    A[n, :] = -(rng.integers(0, 40, n + 1) / 2)
+    return (A, C) if return_table else A
+
+
+def durrieu_log_params(n, bps):
+    """(logA_T, log_pi) of imm's decoder at n voiced states and bps bins per semitone, with the uniform prior."""
+    return synth.log_params(synth.durrieu_transition(n, bps), synth.uniform_prior(n + 1))
+
+
+def emissions_jumps(B, T, S, seed, bw, peaks=6, spread=12):
+    """Emissions [B, T, S] float32 that make the best path jump: every frame has `peaks` states with values 0 .. -spread on the
+    half-integer grid (exact in float16) and -60 everywhere else, so the path hops from peak to peak, and with `spread` about the
+    span of a column's band values the predecessors of a state compete across all distance bands.  Half of the peaks are drawn uniformly over the voiced
+    states, half from the bw // 2 states at either end (end-to-end hops land in the far band whenever (kb + 1) * bw < n); one frame
+    in eight also offers the unvoiced state.  The i.i.d. kinds of synth ("dense", "ties") keep their paths in the nearest bands."""
+    rng = np.random.default_rng(seed)
+    n = S - 1
+    E = np.full((B, T, S), -60.0, np.float32)
+    ends = np.concatenate([np.arange(max(bw // 2, 1)), n - 1 - np.arange(max(bw // 2, 1))])
+    for b in range(B):
+        for t in range(T):
+            pos = np.where(rng.random(peaks) < 0.5, rng.integers(0, n, peaks), ends[rng.integers(0, len(ends), peaks)])
+            E[b, t, pos] = -(rng.integers(0, 2 * spread + 1, peaks) / 2)
+            if rng.integers(0, 8) == 0:
+                E[b, t, n] = -(int(rng.integers(0, 6)) / 2)
+    return E
+
+
+def path_bands(states, lens, n, bw, kb):
+    """The distance band min(|i - j| // bw, kb) of every voiced-to-voiced step of the paths `states` [B, T] -> sorted unique bands."""
+    out = set()
+    for b in range(states.shape[0]):
+        s = np.asarray(states[b, :int(lens[b])], np.int64)
+        i, j = s[:-1], s[1:]
+        v = (i < n) & (j < n)
+        out |= set(np.minimum(np.abs(i - j)[v] // bw, kb).tolist())
+    return sorted(out)
+
+
+# seed index of emissions_jumps per (kind, n, bw, kb) for the [6, T, n + 1] ragged batches of tests/test_gpu_step_geometries.py
+# (T = 150, 100 above 800 states): the lowest k of 0 .. 11 for which the oracle's paths use every distance band 0 .. kb -- each
+# test asserts that premise -- and a back-trace that clamps the band index to kb - 1 decodes another path (checked once on the
+# host with tests/plan_replay.py: replay_step)
+JUMP_K = {("durrieu", 367, 5, 9): 4, ("durrieu", 500, 7, 9): 1, ("durrieu", 1023, 64, 9): 3, ("generated", 128, 4, 15): 6,
+          ("generated", 199, 12, 15): 7, ("generated", 1023, 63, 15): 1, ("durrieu", 705, 20, 9): 2, ("durrieu", 706, 20, 9): 3,
+          ("durrieu", 707, 20, 9): 1, ("durrieu", 708, 20, 9): 1, ("durrieu", 768, 20, 9): 1}
+
+
+def jump_seed(kind, n, bw, kb):
+    return 100 * JUMP_K.get((kind, n, bw, kb), 0) + n

@@ -10,6 +10,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "viterbi_spl_amd", "libviterbi_plan_host.so")
 BIG = 0x7FFFFFFF
+STEP_ROWS = 16           # kMaxStepBands + 1 (plan.hpp)
 
 
 def _lib():
@@ -23,6 +24,7 @@ def _lib():
     lib.vph_offsets.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.vph_image.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
     lib.vph_wave.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    lib.vph_step.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     return lib
 
 
@@ -42,6 +44,9 @@ class HostPlan:
         lib.vph_image(h, img.ctypes.data)
         wv = np.zeros(6, np.int64)
         lib.vph_wave(h, wv.ctypes.data)
+        stp = np.zeros(4, np.int64)
+        cn = np.zeros(1, np.float32)
+        lib.vph_step(h, stp.ctypes.data, cn.ctypes.data)
         lib.vph_destroy(h)
         self.wave_ok, self.wave_npl, self.wave_d, self.wave_dk = bool(wv[0]), int(wv[1]), int(wv[2]), int(wv[3])
         self.floor_all_ok = bool(wv[4])
@@ -74,6 +79,11 @@ class HostPlan:
         if self.wave_ok:   # [own state k][pair m][half h][lane]
             n = self.wave_npl * (self.wave_dk + 1) * 2 * 64
             self.tabV = img[int(wv[5]): int(wv[5]) + 4 * n].view(np.float32).reshape(self.wave_npl, self.wave_dk + 1, 2, 64)
+        assert (bool(stp[0]), int(stp[1]), int(stp[2])) == (self.step_ok, self.step_bw, self.step_kb)
+        self.step_cn = np.float32(cn[0])
+        # [kMaxStepBands + 1][SP] band table of a step plan (all zero bytes otherwise): stepC[k][i] = the value of source column i
+        # at distance band k
+        self.stepC = img[int(stp[3]): int(stp[3]) + 4 * STEP_ROWS * SP].view(np.float32).reshape(STEP_ROWS, SP)
 
 
 def replay_banded(plan: HostPlan, logE, floor=False, pair=False):
@@ -214,6 +224,70 @@ def replay_wave(plan: HostPlan, logE):
             for e, x in enumerate(plan.extras):                                    # copies of the extra columns' delta
                 hist[t, 1 + e] = d[o + x]
     return hist, d[valid].copy()
+
+
+def step_multiplier(bw):
+    """The multiplier of the back-trace's multiply-shift division (bt_args_from_plan, capi.hip): dist // bw == (dist * mult) >> 16."""
+    return (65536 + bw - 1) // bw
+
+
+def step_backtrace_weights(plan: HostPlan, j):
+    """The transition weights [S] the lazy back-trace kernel adds to a delta row for the path state j (backtrace_rows.hip): for a
+    voiced target stepC[min((|i - j| * mult) >> 16, kb)][i] in the kernel's integer arithmetic and step_cn for the unvoiced source,
+    for the unvoiced target its matrix row."""
+    S, n, bw, kb = plan.S, plan.S - 1, plan.step_bw, plan.step_kb
+    if j >= n:
+        return plan.Arow[n, :S]
+    src = np.arange(n)
+    mult = step_multiplier(bw)
+    band = np.minimum((np.abs(src - j) * mult) >> 16, kb)
+    return np.append(plan.stepC[band, src], plan.step_cn).astype(np.float32)
+
+
+def replay_step(plan: HostPlan, logE):
+    """Follows the step-structured kernels on the host, driven by the plan's own band width, band count and band table.
+
+    Forward (step.hip): every voiced source i publishes V_k[i] = fl(delta_i + stepC[k][i]) for k = 0 .. kb; a voiced target j takes
+    the max of the band windows V_k[j + k*bw .. j + k*bw + bw) and V_k(j - k*bw - bw .. j - k*bw] for k < kb and of ONE far maximum
+    M = max(max_i V_kb[i], fl(delta_n + step_cn)) -- the unvoiced source n joins M; the unvoiced target takes the max over its own
+    matrix row.  Back-trace (lazy_backtrace_kernel, backtrace_rows.hip): for the path state j at t+1 every candidate
+    fl(delta_t[i] + stepC[min((|i-j| * mult) >> 16, kb)][i]) in the kernel's integer arithmetic, fl(delta_t[n] + step_cn) for the
+    unvoiced source, the matrix row for the unvoiced target; the LOWEST index attaining the max.
+    Returns (states int64[T], loglik, delta rows [T, S])."""
+    assert plan.step_ok and not plan.ok
+    S, n, bw, kb = plan.S, plan.S - 1, plan.step_bw, plan.step_kb
+    C = plan.stepC[:kb + 1, :n]
+    cn = plan.step_cn
+    row_n = plan.Arow[n, :S]
+    logE = np.ascontiguousarray(logE, np.float32)
+    T = logE.shape[0]
+    ninf = np.float32(-np.inf)
+    pad = kb * bw + bw
+    jj = np.arange(n)
+
+    hist = np.empty((T, S), np.float32)
+    delta = (plan.log_pi[:S] + logE[0]).astype(np.float32)
+    hist[0] = delta
+    for t in range(1, T):
+        V = (delta[None, :n] + C).astype(np.float32)                               # [kb+1, n]
+        M = max(np.max(V[kb]), np.float32(delta[n] + cn))
+        m = np.full(S, M, np.float32)
+        for k in range(kb):
+            Vp = np.concatenate([np.full(pad, ninf, np.float32), V[k], np.full(pad, ninf, np.float32)])
+            R = np.max(np.lib.stride_tricks.sliding_window_view(Vp, bw), axis=1)   # R[u] = max Vp[u .. u + bw)
+            m[:n] = np.maximum(m[:n], R[pad + jj + k * bw])                        # sources j + k*bw .. j + k*bw + bw - 1
+            m[:n] = np.maximum(m[:n], R[pad + jj - k * bw - bw + 1])               # sources j - k*bw - bw + 1 .. j - k*bw
+        m[n] = np.max((delta + row_n).astype(np.float32))
+        delta = (m + logE[t]).astype(np.float32)
+        hist[t] = delta
+
+    s = int(np.argmax(delta))
+    path = np.empty(T, np.int64)
+    path[-1] = s
+    for t in range(T - 2, -1, -1):
+        s = int(np.argmax((hist[t] + step_backtrace_weights(plan, s)).astype(np.float32)))
+        path[t] = s
+    return path, delta[path[-1]], hist
 
 
 def replay_dense_image(plan: HostPlan, logE):

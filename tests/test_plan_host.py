@@ -3,7 +3,7 @@ import numpy as np
 import pytest
 
 from oracle import viterbi_oracle as vo
-from tests.plan_replay import HostPlan, replay_banded, replay_dense_image, replay_wave
+from tests.plan_replay import HostPlan, replay_banded, replay_dense_image, replay_step, replay_wave
 from viterbi_spl_amd import synth
 
 
@@ -171,29 +171,12 @@ def test_step_structure_of_the_durrieu_matrix(golden):
     B[300, 310] = np.nextafter(B[300, 310], np.float32(0))          # one entry one ulp off: not a step matrix any more
     assert not HostPlan(B, pi).step_ok
     assert not HostPlan(p["dense361_logA_T"], p["dense361_log_pi"]).step_ok
-    # host replay of the step kernels' arithmetic
-    S, n, BW, KB = 722, 721, 20, 9
-    E = synth.emissions_dense(1, 40, S, seed=12)[0].numpy()
+    # host replay of the step kernels' arithmetic (tests/plan_replay.py: replay_step, shared with tests/test_step_plan_host.py)
+    E = synth.emissions_dense(1, 40, 722, seed=12)[0].numpy()
     ref, rl, rdelta = vo.decode_c(A, pi, E, return_delta=True)
-    C = np.stack([A[np.minimum(np.arange(n) + k * BW, n - 1), np.arange(n)] if k * BW < n else None for k in range(KB + 1)])
-    for i in range(n):                                               # band value of source i at distance k*BW (either side)
-        for k in range(KB + 1):
-            j = i + k * BW if i + k * BW < n else i - k * BW
-            C[k, i] = A[j, i]
-    delta = (pi + E[0]).astype(np.float32)
-    ninf = np.float32(-np.inf)
-    for t in range(1, E.shape[0]):
-        V = (delta[None, :n] + C).astype(np.float32)                 # [KB+1, n]
-        M = max(np.max(V[KB]), np.float32(delta[n] + A[0, n]))
-        m = np.full(S, ninf, np.float32)
-        for j in range(n):
-            best = M
-            for i in range(max(0, j - KB * BW + 1), min(n, j + KB * BW)):
-                best = max(best, V[abs(i - j) // BW, i])
-            m[j] = best
-        m[n] = np.max((delta + A[n]).astype(np.float32))
-        delta = (m + E[t]).astype(np.float32)
-    assert delta.tobytes() == rdelta.tobytes()
+    st, ll, rows = replay_step(plan, E)
+    assert rows[-1].tobytes() == rdelta.tobytes()
+    assert np.array_equal(st, ref) and np.float32(ll) == np.float32(rl)
 
 
 # ------------------------------------------------------------------ wave form (wave_forward_kernel: one song per wavefront)

@@ -63,7 +63,8 @@ struct BandedPlan {
     // fl(delta_i + logA_T[j][i]) takes only step_kb+1 values per source and the far sources reduce to ONE maximum.
     bool step_ok = false;
     int step_bw = 0, step_kb = 0;
-    std::vector<float> stepC;   // [(kMaxStepBands+1)][SP], rows > step_kb unused, -inf for i >= n
+    std::vector<float> stepC;   // [(kMaxStepBands+1)][SP]; -inf in the rows > step_kb (unused), in the columns i >= n, and where no voiced
+                                // target lies in band k of source i (n < 2 * step_kb * step_bw: a middle source has no far band)
     float step_cn = 0.f;
 
     // "Wave" form (wave_forward_kernel: one song per wavefront, no LDS, no barrier).  Lane l owns the wave_npl =

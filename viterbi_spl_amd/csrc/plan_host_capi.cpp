@@ -45,6 +45,13 @@ void vph_wave(const vph_plan* p, long long* w) {
     w[0] = p->bp.wave_ok; w[1] = p->bp.wave_npl; w[2] = p->bp.wave_d; w[3] = p->bp.wave_dk;
     w[4] = p->bp.floor_all_ok; w[5] = (long long)p->L.off_tabV;
 }
+// step structure: s[0..3] = step_ok, band width, near bands, offset of the band table stepC [kMaxStepBands + 1][SP]; *cn = the
+// unvoiced source's one value
+void vph_step(const vph_plan* p, long long* s, float* cn) {
+    s[0] = p->bp.step_ok; s[1] = p->bp.step_ok ? p->bp.step_bw : 0; s[2] = p->bp.step_ok ? p->bp.step_kb : 0;
+    s[3] = (long long)p->L.off_stepC;
+    *cn = p->bp.step_ok ? p->bp.step_cn : 0.f;
+}
 void vph_image(const vph_plan* p, unsigned char* out) { std::memcpy(out, p->image.data(), p->image.size()); }
 
 // Launch schedule of the packed checkpointed decode (vit::packed_ckpt_schedule), for the CPU tests.  Returns the number of launches,
