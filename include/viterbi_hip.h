@@ -134,6 +134,10 @@ int vit_plan_query(const vit_plan *plan, vit_plan_info *info);
  *                      matrix the reference builds), and a lane's slots 0..4 share the row constant and the extra-column weight
  *                      (its 361-state matrices; for its 321-state ones three groups of slots do) | 1 = neither | 2 = the first only |
  *                      3 = the three-group form also where two groups would do
+ *   "floor_live_window"   split-window floor kernel (what "forward_form" 6 forces): 0 = its full-window waves evaluate only the window
+ *                      entries the plan proves live for their targets (rows 0 .. 255: the trailing entries that equal the row constant or
+ *                      are an extra column are covered by the frame-maximum candidate and the extra-column path; 29 of 32 on the
+ *                      reference's 361-state grid, 25 on its 321-state grids) | 1 = always the whole window
  *   "timing"           ablation / probe mask: accepted only by a -DVIT_TIMING_HOOKS build (VIT_EUNSUPPORTED otherwise;
  *                      those bits change results)
  *   "reset"            back to the defaults

@@ -323,14 +323,23 @@ __global__ void __launch_bounds__((NWT + (DW ? 3 : 2)) * 64) banded_forward_kern
 // s_waitcnt immediate of gfx9: vmcnt in bits 3:0 and 15:14, expcnt (left open) in 6:4, lgkmcnt in 11:8
 constexpr int split_waitcnt(int vm, int lgkm) { return (vm & 15) | ((vm >> 4) << 14) | (7 << 4) | (lgkm << 8); }
 constexpr int kNoVmWait = 63;
+// A trimmed full-wave window is read as NQ quads, in order, and one float behind them, the last LDS reads of the frame's burst: the
+// reads still behind quad pair g (quads 2g, 2g + 1), i.e. the lgkmcnt that waits for that pair and everything in front of it
+constexpr int split_reads_behind(int NQ, int g) { return (NQ + 1) - 2 * (g + 1); }
 // f(std::integral_constant<int, K>) for K = 0, 1, ...: the unrolled frames and window groups need their index as a constant
 // (the s_waitcnt immediate is derived from it)
 template <int... K, typename F>
 __device__ __forceinline__ void split_frames(std::integer_sequence<int, K...>, F&& f) { (f(std::integral_constant<int, K>{}), ...); }
-template <int NXT, int PF, typename ET, bool WPR = false, bool XQ = false>
+// WF: the window entries a full wave evaluates (FwdArgs::floor_live, proven by the plan: floor_live_width).  WF = W is the whole window.
+// WF = 4 n + 1 < W reads n quads and position WF - 1 as one float, loads no weight beyond it, and reduces its WF + 2 candidates
+// (window, floor, extra column) in (WF + 1) / 2 v_max3_f32 (15 at WF = 29): two chains seeded with fl(M + c_j) and with the extra-column
+// sum, one pair of sums per step, and the single entry joins the two chains in the last one.  M's four slots take one v_max3_f32 and one
+// v_max_f32 more, as ever: 16 + 1 per frame at WF = 29, 37 VALU in all.  The half waves always take W / 2 each.
+template <int NXT, int PF, typename ET, bool WPR = false, bool XQ = false, int WF = 32>
 __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) banded_floor_split_forward_kernel(FwdArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int W = 32;
+    static_assert(WF == W || (WF % 4 == 1 && WF >= 9 && WF < W && NXT == 1), "a trimmed window: whole quads and one float, one extra column");
     constexpr int NWF = kSplitFullWaves, NW = kSplitFullWaves + kSplitHalfWaves;
     using L = FloorSplitLds;                      // the copy stride comes from the state slots, not from the thread count
     constexpr int DC = L::DC, BUF = L::BUF;
@@ -394,7 +403,8 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
     // (resets: the last half wave, which also sends the slot group of the frame after next back to -inf)
     auto body = [&](auto role, auto resets) {
         constexpr bool HALF = decltype(role)::value, RESETS = decltype(resets)::value;
-        constexpr int WL = HALF ? W / 2 : W;                              // window sources per lane
+        constexpr int WL = HALF ? W / 2 : WF;                             // window sources per lane
+        constexpr bool TRIM = WL % 4 != 0;                                // (full waves with WF < W: WL / 4 quads and one float)
         const float cj = own ? reinterpret_cast<const float*>(a.image + a.off_rowc)[jc] : -INFINITY;   // (upper half: -inf)
         float aw[WL];
         float xa[NXL > 0 ? NXL : 1];
@@ -466,7 +476,7 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
             float xd[NXL > 0 ? NXL : 1];
             f32x4 fq;
-            float m0, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
+            [[maybe_unused]] float m0, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
             // The small reads first (extra columns, then the M slots), the window quads right behind them and nothing after: the window
             // quads are the LAST LDS operations of the frame's read burst (the two quads of a pair in either order).  The paired waits below count on that
             // (lgkmcnt(2) = "all but the last two quads"); a read moved behind the window would turn them into waits for less than they
@@ -478,43 +488,107 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             f32x4 dw[WL / 4];
 #pragma unroll
             for (int q = 0; q < WL / 4; ++q) dw[q] = win[q];
+            [[maybe_unused]] float ds = 0.f;                              // (TRIM) position WL - 1: the last LDS read of the burst
+            if constexpr (TRIM) ds = (rp + RB * BUF)[WL - 1];
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (TRIM) {
+                // one wait for M and the first pair of quads: everything but the WL / 4 - 2 quads and the float behind them
+                static_assert(split_reads_behind(WL / 4, 0) == WL / 4 + 1 - 2, "behind the first pair: every other window read of the burst");
+                __builtin_amdgcn_s_waitcnt(split_waitcnt(kNoVmWait, split_reads_behind(WL / 4, 0)));
+                asm volatile("" : "+v"(fq), "+v"(dw[0]), "+v"(dw[1]));
+            }
             const float M = fmaxf(fmaxf(fq.x, fq.y), fmaxf(fq.z, fq.w));
             m0 = M + cj;
             asm volatile("" ::"v"(m0));   // M + c_j stays in front of the window sums (with the explicit waits below the add otherwise sinks behind them)
             __builtin_amdgcn_sched_barrier(0);
-            split_frames(std::make_integer_sequence<int, WL / 8>{}, [&](auto gc) {
-                constexpr int w = 8 * decltype(gc)::value;
-                constexpr bool last = w + 8 == WL;
-                // The emission of this frame was requested PF frames ago: behind it stand the PF - 1 younger prefetch loads and one row
-                // store per frame since (u in the first round, where the prologue issued the loads back to back; 2 (PF - 1) >= PF - 1 + u
-                // operations in every later round and in the tails), and vmcnt retires in order.  Stating that bound together with the
-                // frame's last window wait saves the s_waitcnt vmcnt the compiler otherwise puts in front of "+ e".
-                constexpr int vmw = PF - 1 + u;
-                // Counted on this kernel's frame: ONE store (row_store_f32) and ONE load (row_load_e) per frame and role.  More VMEM per
-                // frame (the probe instantiations) only makes the bound wait longer than needed; fewer would make it too weak.
-                static_assert(vmw <= 2 * (PF - 1) && 2 * (PF - 1) < kNoVmWait, "vmcnt bound: one store and one load per frame, 6-bit field");
-                // The late window quads are waited for in pairs: the last four of the full waves' eight, the last two of the half waves'
-                // four.  M and the first quads keep the compiler's stepped waits, which buy the early first max3.
-                constexpr bool pairw = w + 16 >= WL && w >= 8;
-                f32x4 da = dw[w / 4], db = dw[w / 4 + 1];
-                if constexpr (pairw) {
-                    __builtin_amdgcn_s_waitcnt(split_waitcnt(last ? vmw : kNoVmWait, last ? 0 : 2));
-                    asm volatile("" : "+v"(da), "+v"(db));
+            float mx;
+            // The emission of this frame was requested PF frames ago: behind it stand the PF - 1 younger prefetch loads and one row
+            // store per frame since (u in the first round, where the prologue issued the loads back to back; 2 (PF - 1) >= PF - 1 + u
+            // operations in every later round and in the tails), and vmcnt retires in order.  Stating that bound together with the
+            // frame's last window wait saves the s_waitcnt vmcnt the compiler otherwise puts in front of "+ e".
+            // Counted on this kernel's frame: ONE store (row_store_f32) and ONE load (row_load_e) per frame and role.  More VMEM per
+            // frame (the probe instantiations) only makes the bound wait longer than needed; fewer would make it too weak.
+            constexpr int vmw = PF - 1 + u;
+            static_assert(vmw <= 2 * (PF - 1) && 2 * (PF - 1) < kNoVmWait, "vmcnt bound: one store and one load per frame, 6-bit field");
+            if constexpr (TRIM) {
+                // NQ quads and the single float behind them.  The tail -- the last quad of an odd count, the last two of an even one, and
+                // the float -- is waited for at once, together with the emission (lgkmcnt(0), the frame's last wait); every pair of quads
+                // in front of it waits once, for all but the reads behind it (the first pair together with M, above).
+                constexpr int NQ = WL / 4, TQ = NQ % 2 ? 1 : 2, NPB = (NQ - TQ) / 2;
+                static_assert(NXL == 1 && NQ >= 3 && 2 * NPB + TQ == NQ && 4 * NQ + 1 == WL, "pairs of quads, then the tail: one or two quads and one float");
+                static_assert(split_reads_behind(NQ, 0) <= 15, "lgkmcnt is a four-bit field");
+                static_assert(split_reads_behind(NQ, NPB - 1) == TQ + 1, "behind the last pair stand the tail's reads -- TQ quads and the float -- and nothing else");
+                static_assert(split_reads_behind(NQ, NPB) + 2 == TQ + 1 && TQ <= 2, "the tail's wait, lgkmcnt(0), leaves no window read out");
+                float mb = xd[0] + xa[0];                                 // the second chain starts from the extra-column sum (the burst's first read)
+                asm volatile("" ::"v"(mb));
+                split_frames(std::make_integer_sequence<int, NPB>{}, [&](auto gc) {
+                    constexpr int w = 8 * decltype(gc)::value;
+                    f32x4 da = dw[w / 4], db = dw[w / 4 + 1];
+                    if constexpr (decltype(gc)::value >= 1) {
+                        constexpr int behind = split_reads_behind(NQ, decltype(gc)::value);   // the quads and the float behind this pair
+                        static_assert(behind >= TQ + 1 && behind + 2 == split_reads_behind(NQ, decltype(gc)::value - 1), "two reads fewer than the pair before");
+                        __builtin_amdgcn_s_waitcnt(split_waitcnt(kNoVmWait, behind));
+                        asm volatile("" : "+v"(da), "+v"(db));
+                    }
+                    f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[w + 0], aw[w + 1]};
+                    f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[w + 2], aw[w + 3]};
+                    f32x2 c2_ = f32x2{db.x, db.y} + f32x2{aw[w + 4], aw[w + 5]};
+                    f32x2 c3_ = f32x2{db.z, db.w} + f32x2{aw[w + 6], aw[w + 7]};
+                    asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_));   // a group's sums before its maxima: no hazard s_nop
+                    m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
+                    mb = fmaxf(fmaxf(mb, c1_.x), c1_.y);
+                    m0 = fmaxf(fmaxf(m0, c2_.x), c2_.y);
+                    mb = fmaxf(fmaxf(mb, c3_.x), c3_.y);
+                });
+                {
+                    constexpr int w = 8 * NPB;
+                    f32x4 da = dw[w / 4], db = dw[NQ - 1];                // (TQ == 1: db is da again and unused)
+                    __builtin_amdgcn_s_waitcnt(split_waitcnt(vmw, 0));
+                    if constexpr (TQ == 2) asm volatile("" : "+v"(da), "+v"(db), "+v"(ds)); else asm volatile("" : "+v"(da), "+v"(ds));
+                    f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[w + 0], aw[w + 1]};
+                    f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[w + 2], aw[w + 3]};
+                    float cs = ds + aw[WL - 1];
+                    if constexpr (TQ == 2) {
+                        f32x2 c2_ = f32x2{db.x, db.y} + f32x2{aw[w + 4], aw[w + 5]};
+                        f32x2 c3_ = f32x2{db.z, db.w} + f32x2{aw[w + 6], aw[w + 7]};
+                        asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_), "+v"(cs));
+                        m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
+                        mb = fmaxf(fmaxf(mb, c1_.x), c1_.y);
+                        m0 = fmaxf(fmaxf(m0, c2_.x), c2_.y);
+                        mb = fmaxf(fmaxf(mb, c3_.x), c3_.y);
+                    } else {
+                        asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(cs));
+                        m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
+                        mb = fmaxf(fmaxf(mb, c1_.x), c1_.y);
+                    }
+                    mx = fmaxf(fmaxf(m0, mb), cs);                        // the single entry joins the two chains
                 }
-                f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[w + 0], aw[w + 1]};
-                f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[w + 2], aw[w + 3]};
-                f32x2 c2_ = f32x2{db.x, db.y} + f32x2{aw[w + 4], aw[w + 5]};
-                f32x2 c3_ = f32x2{db.z, db.w} + f32x2{aw[w + 6], aw[w + 7]};
-                asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_));   // a group's sums before its maxima: no hazard s_nop
-                m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
-                m1 = fmaxf(fmaxf(m1, c1_.x), c1_.y);
-                m2 = fmaxf(fmaxf(m2, c2_.x), c2_.y);
-                m3 = fmaxf(fmaxf(m3, c3_.x), c3_.y);
-            });
+            } else {
+                split_frames(std::make_integer_sequence<int, WL / 8>{}, [&](auto gc) {
+                    constexpr int w = 8 * decltype(gc)::value;
+                    constexpr bool last = w + 8 == WL;
+                    // The late window quads are waited for in pairs: the last four of the full waves' eight, the last two of the half waves'
+                    // four.  M and the first quads keep the compiler's stepped waits, which buy the early first max3.
+                    constexpr bool pairw = w + 16 >= WL && w >= 8;
+                    f32x4 da = dw[w / 4], db = dw[w / 4 + 1];
+                    if constexpr (pairw) {
+                        __builtin_amdgcn_s_waitcnt(split_waitcnt(last ? vmw : kNoVmWait, last ? 0 : 2));
+                        asm volatile("" : "+v"(da), "+v"(db));
+                    }
+                    f32x2 c0_ = f32x2{da.x, da.y} + f32x2{aw[w + 0], aw[w + 1]};
+                    f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[w + 2], aw[w + 3]};
+                    f32x2 c2_ = f32x2{db.x, db.y} + f32x2{aw[w + 4], aw[w + 5]};
+                    f32x2 c3_ = f32x2{db.z, db.w} + f32x2{aw[w + 6], aw[w + 7]};
+                    asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_));   // a group's sums before its maxima: no hazard s_nop
+                    m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
+                    m1 = fmaxf(fmaxf(m1, c1_.x), c1_.y);
+                    m2 = fmaxf(fmaxf(m2, c2_.x), c2_.y);
+                    m3 = fmaxf(fmaxf(m3, c3_.x), c3_.y);
+                });
 #pragma unroll
-            for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
-            float mx = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+                for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
+                mx = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+            }
             if constexpr (HALF) mx = max_other_half(mx);                  // join the two halves of the window
             const float dn = mx + e_slot;
 #ifdef VIT_TIMING_HOOKS
@@ -817,6 +891,7 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
     // prefetch load and wait for it every frame), so the default leaves those to the one-target kernel (profiles/r06_logs/floor_split_ab.log).
     if constexpr (W == 32 && NWT == 6) {
         static_assert(kSplitStates == NWT * 64, "the split kernel keeps the six-wave kernel's LDS and history layout");
+        static_assert(kSplitFullRows == 64 * kSplitFullWaves, "FwdArgs::floor_live speaks for the full waves' targets");
         if (a.fwd_form == 6 || (a.fwd_form == 0 && a.B <= 256 && std::is_same_v<ET, float>)) {
             constexpr size_t ldss = FloorSplitLds::bytes();
             constexpr int NWS = kSplitFullWaves + kSplitHalfWaves;
@@ -825,17 +900,30 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
             // the publishing lane of its quad and states x + 1 .. x + 3 are idle slots (-inf for the whole song); any other plan
             // (generic extras, an extra column elsewhere, x % 4 != 0 with live states in the quad) keeps the select.
             const bool xq = a.n_extras == 1 && a.extras[0] == a.S - 1 && (a.S - 1) % 4 == 0;
+            // The full waves evaluate the window entries the plan proves live for their targets (a.floor_live, floor_live_width): the
+            // smallest instantiated width that covers them -- 29 for the reference's 361-state grid, 25 for its 321-state grids.  Generic
+            // extras, fp16 emissions (forward form 6 only) and a plan whose first rows are clamped to the end of the grid take the whole window.
+            const int wf = split_full_width(a.floor_live, W, a.S, a.n_extras, !std::is_same_v<ET, float>);
+            auto go = [&](auto xqc, auto wfc) {
+                constexpr bool XQ = decltype(xqc)::value;
+                constexpr int WF = decltype(wfc)::value;
 #ifdef VIT_TIMING_HOOKS
-            if ((a.debug & 64) && xq)
-                hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET, true, true>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
-            else if ((a.debug & 64) && a.n_extras == 1)
-                hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET, true>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
-            else
+                if (a.debug & 64)
+                    hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET, true, XQ, WF>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
+                else
 #endif
-            if (xq)
-                hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET, false, true>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
-            else if (a.n_extras == 1)
-                hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
+                hipLaunchKernelGGL((banded_floor_split_forward_kernel<1, PF, ET, false, XQ, WF>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
+            };
+            auto go_w = [&](auto xqc) {
+                if constexpr (std::is_same_v<ET, float>) {
+                    static_assert(sizeof(kSplitLiveWidths) / sizeof(int) == 2, "one case per instantiated live width");
+                    if (wf == 25) return go(xqc, std::integral_constant<int, 25>{});
+                    if (wf == 29) return go(xqc, std::integral_constant<int, 29>{});
+                }
+                return go(xqc, std::integral_constant<int, W>{});
+            };
+            if (xq) go_w(std::true_type{});
+            else if (a.n_extras == 1) go_w(std::false_type{});
             else
                 hipLaunchKernelGGL((banded_floor_split_forward_kernel<-1, PF, ET>), dim3((int)a.B), dim3(NWS * 64), ldss, st, a);
             return hipGetLastError();

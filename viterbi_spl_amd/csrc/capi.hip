@@ -39,6 +39,7 @@ struct Tuning {
                                // 2 = the last-state variant only | 3 = the three-group form where the two-group one would run (it is valid there too)
     int bt_fast_rows = 0;      // sparse / half back-trace: 0 = the unexceptional rows in their own loop | 1 = every row through the general code
     int bt_block_waves = 0;    // half back-trace: waves per workgroup, 0 = 16 | 8 | 4 (to start beside the next batch's resident forward waves)
+    int floor_live_window = 0; // split floor kernel: 0 = the full waves evaluate the window entries the plan proves live | 1 = always the whole window
     int wave_history = 0;      // wave form: 0 / 1 every delta row | 2 the rows of even frames only (VIT_EUNSUPPORTED where the plan does not allow it)
     int timing = 0;
 };
@@ -338,7 +339,7 @@ static int* tuning_field(Tuning& t, const char* key) {
         {"step_form", &Tuning::step_form}, {"bt_chunks", &Tuning::bt_chunks}, {"bt_warm", &Tuning::bt_warm},
         {"win_shift", &Tuning::win_shift}, {"wave_min_batch", &Tuning::wave_min_batch}, {"wave_two", &Tuning::wave_two},
         {"bt_fast_rows", &Tuning::bt_fast_rows}, {"bt_block_waves", &Tuning::bt_block_waves}, {"wave_history", &Tuning::wave_history}, {"wave_uniform", &Tuning::wave_uniform},
-        {"timing", &Tuning::timing},
+        {"floor_live_window", &Tuning::floor_live_window}, {"timing", &Tuning::timing},
     };
     for (const auto& e : tab)
         if (std::strcmp(e.k, key) == 0) return &(t.*(e.f));
@@ -420,6 +421,7 @@ static void fwd_args_from_plan(const vit_plan* plan, vit::FwdArgs& a) {
     a.win_shift = (plan->bp.ok && plan->bp.lo_affine) ? (plan->bp.lo_off & 3) : 0;
     a.win_shift2 = (plan->bp.ok && plan->bp.pair_ok && plan->bp.lo2_affine) ? (plan->bp.lo2_off & 3) : 0;
     if (tn.win_shift >= 0) a.win_shift = a.win_shift2 = tn.win_shift & 3;   // every value is functionally correct
+    a.floor_live = tn.floor_live_window == 0 ? vit::floor_live_width(plan->bp, vit::kSplitFullRows) : plan->bp.W;
 }
 
 size_t vit_workspace_bytes_for(const vit_plan* plan, int64_t B, int64_t T, int algo) {

@@ -114,6 +114,8 @@ struct FwdArgs {
     const int32_t* unit_seg;     // device [B units of this launch]
     int win_shift;         // 0..3: delta is stored shifted by this many floats in LDS so that the window starts of a
                             // 16-lane group are 16-byte aligned in the SAME copy order (bank-conflict-free b128 reads)
+    int floor_live;         // split floor kernel (host side only): window entries the full waves' targets [0, 64 * kSplitFullWaves) must evaluate
+                            // (floor_live_width; W = no trim, also with vit_plan_set_option "floor_live_window" 1)
 };
 
 struct BtArgs {

@@ -152,6 +152,13 @@ BandedPlan analyze_banded(const float* A, int S) {
             }
         }
         bp.floor_ok = ok;
+        // the last window position of each row that the floor form must still evaluate (floor_live_width)
+        bp.live_last.assign(S, W - 1);
+        for (int j = 0; j < S && ok; ++j) {
+            int w = W - 1;
+            while (w >= 0 && (is_extra(bp.lo[j] + w) || f2u(A[(size_t)j * S + bp.lo[j] + w]) == row_mode[j])) --w;
+            bp.live_last[j] = w;
+        }
     }
     // "wave" form: the frame maximum over ALL sources needs the extra-column entries to dominate the row constant as
     // well; the half-width bounds how many neighbouring lanes a lane must see
@@ -171,6 +178,13 @@ BandedPlan analyze_banded(const float* A, int S) {
     }
     bp.ok = true;
     return bp;
+}
+
+int floor_live_width(const BandedPlan& bp, int n_rows) {
+    if (!bp.ok || !bp.floor_ok || bp.n_dense != 0 || (int)bp.live_last.size() < bp.S) return bp.W;
+    int last = 0;                                      // (a range with nothing live still evaluates position 0)
+    for (int j = 0; j < n_rows && j < bp.S; ++j) last = std::max(last, (int)bp.live_last[j]);
+    return last + 1;
 }
 
 void analyze_step(const float* A, int S, BandedPlan& bp) {

@@ -50,6 +50,9 @@ struct BandedPlan {
     bool lo_affine = false;   // lo[j] == clamp(j - lo_off, 0, S - W) for every banded row
     bool floor_ok = false;    // every non-extra window entry of every banded row is >= that row's constant, and no dense rows:
                               // then max_{i outside window} fl(delta_i + c_j) can be replaced by fl(max_{all non-extra i} delta_i + c_j)
+    std::vector<int32_t> live_last;   // [S] floor_ok plans: the last window position of banded row j that is neither an extra column nor, in bits,
+                              // the row constant (-1: none).  Behind it the window holds only candidates that fl(M + c_j) or the
+                              // extra-column path already cover (floor_live_width)
     bool pair_ok = false;     // targets (2p, 2p+1) share one window [lo2[p], lo2[p]+W) that covers both exception spans
     std::vector<int32_t> lo2; // [SP/2]
     bool lo2_affine = false;  // lo2[p] == clamp(2p - lo2_off, 0, S - W)
@@ -94,6 +97,25 @@ void analyze_step(const float* logA_T, int S, BandedPlan& bp);
 
 // Analyse logA_T ([S,S] row-major, row j = into target j).
 BandedPlan analyze_banded(const float* logA_T, int S);
+// Live window width of the targets [0, n_rows) under the floor-max form: 1 + the last window position any of them must still evaluate.
+// A trailing position w of row j is droppable when source lo_j + w is an extra column (the extra-column path forms that candidate anyway)
+// or A[j][lo_j + w] is, in bits, the row constant c_j: then fl(delta_i + c_j) <= fl(M + c_j), which the floor form carries (rounding is
+// monotone; M is the maximum over every non-extra source).  Only the trailing run is trimmed.  W where the plan does not prove the floor
+// form (floor_ok, no dense rows): nothing may be dropped there.
+int floor_live_width(const BandedPlan& bp, int n_rows);
+// The split floor kernel (banded.hip): its full-window waves own targets [0, kSplitFullRows) and are instantiated for the whole window and
+// for the live widths of the reference's grids (25: the 321-state grids, 29: the 361-state grid); a proven live width takes the
+// narrowest instantiated one that covers it, anything else the whole window.
+constexpr int kSplitFullRows = 256;
+inline constexpr int kSplitLiveWidths[] = {25, 29};
+// Everything the choice depends on, for the launcher (launch_floor_t, banded.hip) and the host library alike: the split kernel exists
+// for W = 32 on the six-wave grids (256 < S < 384), and its trimmed instantiations for one extra column and fp32 emissions.
+constexpr int split_full_width(int live, int W, int S, int n_extras, bool f16) {
+    if (W != 32 || S <= kSplitFullRows || S >= 384 || n_extras != 1 || f16) return W;
+    for (int w : kSplitLiveWidths)
+        if (live >= 1 && live <= w && w < W) return w;
+    return W;
+}
 
 // Byte layout of the device image (all offsets in bytes from the image base,
 // every section 256-byte aligned).

@@ -52,6 +52,12 @@ void vph_step(const vph_plan* p, long long* s, float* cn) {
     s[3] = (long long)p->L.off_stepC;
     *cn = p->bp.step_ok ? p->bp.step_cn : 0.f;
 }
+// live window width of targets [0, n_rows) under the floor-max form (vit::floor_live_width): what the split kernel's full waves evaluate
+int vph_live_width(const vph_plan* p, int n_rows) { return vit::floor_live_width(p->bp, n_rows); }
+// ... and the width the kernel then runs them at for fp32 (f16 = 0) or fp16 emissions: the launcher's own choice (vit::split_full_width)
+int vph_split_full_width(const vph_plan* p, int f16) {
+    return vit::split_full_width(vit::floor_live_width(p->bp, vit::kSplitFullRows), p->bp.W, p->bp.S, p->bp.ok ? p->bp.n_extras : 0, f16 != 0);
+}
 void vph_image(const vph_plan* p, unsigned char* out) { std::memcpy(out, p->image.data(), p->image.size()); }
 
 // Launch schedule of the packed checkpointed decode (vit::packed_ckpt_schedule), for the CPU tests.  Returns the number of launches,
