@@ -320,6 +320,32 @@ int vit_decode_packed_bounded(const vit_plan *plan, const void *logE, int emis_d
 int64_t vit_packed_bounded_units(const vit_plan *plan, int64_t B);
 
 /*
+ * Float64-accumulating decode: the reference's float64 Viterbi variant, dcnet/tf_viterbi_decoding.py:209-263 (viterbi_librosa_fn
+ * there; its parameters and emissions are float32, only T1 is float64; the unused `p` at :255 is the log-likelihood returned here).
+ * Inputs are the library's: the plan's float32 logA_T and log_pi, float32 or float16 log-emissions (float16 is widened to float32
+ * first; every widening below is exact), lengths.  Bit for bit, with A[j][i] = logA_T[j][i]:
+ *   d_0[j]  = f64( fl32(log_pi[j] + E_0[j]) )            the reference adds two float32 arrays, THEN stores into its float64 T1
+ *   m_j     = max_i fl64( d_{t-1}[i] + f64(A[j][i]) )     psi_t[j] = LOWEST i attaining m_j
+ *   d_t[j]  = fl64( m_j + f64(E_t[j]) )
+ *   s_{T-1} = lowest argmax_j d_{T-1}[j];   s_t = psi_{t+1}[s_{t+1}];   loglik = d_{T-1}[s_{T-1}]   (a double)
+ * -inf follows the rules of vit_decode(): the compare is strict, a dead song yields state 0 and a log-likelihood of -inf; NaN is
+ * outside the contract.  On long inputs the path differs from vit_decode()'s in a few frames out of thousands (the float32 running
+ * sum drifts); this one is the better-scoring path.
+ * Plans served: banded plans whose one-maximum ("floor") form is proven, without dense rows, at an instantiated window width
+ * (16 / 32 / 64 / 84 / 96 / 128) and at most 768 states -- every banded matrix the reference builds (321, 361, the 721- / 722-state
+ * bands of jdc and imm).  Unstructured matrices, the Durrieu (step) matrices and scan-only or dense-row plans get size 0 and
+ * VIT_EUNSUPPORTED before anything is enqueued; a size > 0 means the decode launches.
+ * Argument checks, status codes and their order, the 256-byte workspace alignment, lengths clamped to [1, T] and states[b, t] = -1
+ * past a song's end are vit_decode()'s; B = 0 is VIT_OK.  The call does not synchronise the host and allocates nothing.  It
+ * overwrites the workspace: the record an earlier vit_forward() left for it is dropped and none is written, so a vit_backtrace()
+ * on that workspace afterwards is VIT_ENOFORWARD.  Workspace: B x T rows of (S + 3) / 2 * 2 doubles (every d row and the frame maximum) + tables.
+ * Honoured options: "bt_chunks", "bt_warm"; every other option is ignored.
+ */
+size_t vit_workspace_bytes_f64(const vit_plan *plan, int64_t B, int64_t T);
+int vit_decode_f64(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B, int64_t T, const int64_t *lengths,
+                   void *workspace, size_t workspace_bytes, int32_t *states, double *loglik /* [B] or NULL */, vit_stream stream);
+
+/*
  * Fused logits -> path decode: what callers of the reference run is Viterbi.__call__ (tonet/for_paper.py:1817-1831) -- pitch
  * logits -> observation log-probabilities -> Viterbi decode.  vit_obs_*() + vit_decode() do that with a [B,T,S] float32
  * emission tensor written to and read back from device memory (2 x 4 S bytes per frame, 44 GB for [1024, 30000, 361]); here the

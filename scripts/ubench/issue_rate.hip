@@ -15,6 +15,7 @@ __global__ void k(float* out, unsigned long long* cyc, int iters) {
     const int lane = threadIdx.x & 63;
     float a0 = lane, a1 = lane + 1, a2 = lane + 2, a3 = lane + 3, a4 = 1.f, a5 = 2.f, a6 = 3.f, a7 = 4.f;
     f32x2 p0{a0, a1}, p1{a2, a3}, p2{a4, a5}, p3{a6, a7};
+    double d0 = lane, d1 = lane + 1, d2 = lane + 2, d3 = lane + 3, d4 = 1.0;
     const float* lp = lds + (threadIdx.x & 255);
     unsigned long long t0 = __builtin_amdgcn_s_memtime();
     for (int it = 0; it < iters; ++it) {
@@ -47,11 +48,20 @@ __global__ void k(float* out, unsigned long long* cyc, int iters) {
             } else if (OP == 8) {  // v_cmp + v_cndmask pairs
                 asm volatile("v_cmp_gt_f32 vcc, %0, %1\n\tv_cndmask_b32 %2, %2, %3, vcc\n\tv_cmp_gt_f32 vcc, %1, %0\n\tv_cndmask_b32 %3, %3, %2, vcc"
                              : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) :: "vcc");
+            } else if (OP == 9) {  // 4 independent v_add_f64 (the float64 decode, csrc/f64.hip)
+                asm volatile("v_add_f64 %0, %0, %4\n\tv_add_f64 %1, %1, %4\n\tv_add_f64 %2, %2, %4\n\tv_add_f64 %3, %3, %4"
+                             : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3) : "v"(d4));
+            } else if (OP == 10) {  // 4 independent v_max_f64
+                asm volatile("v_max_f64 %0, %0, %4\n\tv_max_f64 %1, %1, %4\n\tv_max_f64 %2, %2, %4\n\tv_max_f64 %3, %3, %4"
+                             : "+v"(d0), "+v"(d1), "+v"(d2), "+v"(d3) : "v"(d4));
+            } else if (OP == 11) {  // 4 independent v_cvt_f64_f32
+                asm volatile("v_cvt_f64_f32 %0, %4\n\tv_cvt_f64_f32 %1, %5\n\tv_cvt_f64_f32 %2, %6\n\tv_cvt_f64_f32 %3, %7"
+                             : "=v"(d0), "=v"(d1), "=v"(d2), "=v"(d3) : "v"(a0), "v"(a1), "v"(a2), "v"(a3));
             }
         }
     }
     unsigned long long t1 = __builtin_amdgcn_s_memtime();
-    out[threadIdx.x + blockIdx.x * blockDim.x] = a0 + a1 + a2 + a3 + p0.x + p1.x + p2.x + p3.y;
+    out[threadIdx.x + blockIdx.x * blockDim.x] = a0 + a1 + a2 + a3 + p0.x + p1.x + p2.x + p3.y + (float)(d0 + d1 + d2 + d3);
     if (lane == 0) cyc[(blockIdx.x * blockDim.x + threadIdx.x) >> 6] = t1 - t0;
 }
 
@@ -83,5 +93,8 @@ int main() {
     run<6>("s_nop 0", 4);
     run<7>("pk_add -> max3 (2 chains)", 4);
     run<8>("v_cmp + v_cndmask", 4);
+    run<9>("v_add_f64 (indep)", 4);
+    run<10>("v_max_f64 (indep)", 4);
+    run<11>("v_cvt_f64_f32 (indep)", 4);
     return 0;
 }

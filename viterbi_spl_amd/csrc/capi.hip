@@ -629,6 +629,79 @@ int vit_decode(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B
     return vit_backtrace(plan, B, T, lengths, workspace, workspace_bytes, states, algo, stream);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Float64-accumulating decode (f64.hip): the reference's float64 variant, dcnet/tf_viterbi_decoding.py:209-263.  The forward and the
+// back-trace kernel of that file, nothing else: of the plan's options only bt_chunks and bt_warm are consulted.  No forward pass is
+// put on record and the record an earlier vit_forward left for the workspace is dropped (vit_backtrace knows nothing of this history).
+namespace {
+
+inline bool f64_applies(const vit_plan* p) {
+    return vit::f64_decode_applies(p->S, p->bp.W, p->bp.ok, p->bp.ok && p->bp.floor_ok, p->bp.ok ? p->bp.n_dense : 0);
+}
+struct F64Layout {
+    size_t off_hist, off_last, off_entry, bytes;
+};
+F64Layout f64_layout(const vit_plan* p, int64_t B, int64_t T) {
+    F64Layout w;
+    w.off_hist = 0;
+    w.off_last = align256((size_t)B * (size_t)T * (size_t)vit::f64_hist_stride(p->S) * sizeof(double));
+    w.off_entry = w.off_last + align256((size_t)B * sizeof(int32_t));
+    w.bytes = w.off_entry + align256((size_t)B * vit::kBtMaxChunks * sizeof(int32_t));
+    return w;
+}
+
+}  // namespace
+
+size_t vit_workspace_bytes_f64(const vit_plan* plan, int64_t B, int64_t T) {
+    if (!plan || B < 0 || T < 1 || T > (int64_t)1 << 30 || B > (int64_t)1 << 30 || !f64_applies(plan)) return 0;
+    return f64_layout(plan, B, T).bytes;
+}
+
+int vit_decode_f64(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T, const int64_t* lengths, void* workspace,
+                   size_t workspace_bytes, int32_t* states, double* loglik, vit_stream stream) {
+    if (!states) return VIT_EINVAL;
+    int rc = check_common(plan, B, T, workspace);
+    if (rc != VIT_OK) return rc;
+    if (!logE) return VIT_EINVAL;
+    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
+    if (!f64_applies(plan)) return VIT_EUNSUPPORTED;
+    const F64Layout w = f64_layout(plan, B, T);
+    if (workspace_bytes < w.bytes) return VIT_EWORKSPACE;
+    if (B == 0) return VIT_OK;
+    stamp_erase(plan, workspace);      // whatever vit_forward left in this workspace is gone once the kernels below start: vit_backtrace must not find it
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    vit::F64Args a{};
+    a.image = plan->dev_image;
+    a.logE = logE;
+    a.lengths = lengths;
+    a.hist = reinterpret_cast<double*>(ws + w.off_hist);
+    a.last_state = reinterpret_cast<int32_t*>(ws + w.off_last);
+    a.loglik = loglik;
+    a.states = states;
+    a.entry = reinterpret_cast<int32_t*>(ws + w.off_entry);
+    a.B = B;
+    a.T = (int)T;
+    a.S = plan->S;
+    a.SP = plan->L.SP;
+    a.SD64 = vit::f64_hist_stride(plan->S);
+    a.W = plan->bp.W;
+    a.n_extras = plan->bp.n_extras;
+    for (int k = 0; k < vit::kMaxExtras; ++k) a.extras[k] = plan->bp.extras[k];
+    a.off_logpi = plan->L.off_logpi;
+    a.off_lo = plan->L.off_lo;
+    a.off_tabA = plan->L.off_tabA;
+    a.off_extraA = plan->L.off_extraA;
+    a.off_rowc = plan->L.off_rowc;
+    a.off_tabX = plan->L.off_tabX;
+    const Tuning& tn = plan->tune;
+    a.chunks = vit::backtrace_chunks(B, (int)T);
+    a.warm = vit::kBtWarm;
+    if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kBtMaxChunks) a.chunks = tn.bt_chunks;
+    if (tn.bt_warm >= 0) a.warm = tn.bt_warm;
+    VIT_TRY(vit::launch_f64_forward(a, emis_dtype == VIT_F16, (hipStream_t)stream));
+    return hip_status(vit::launch_f64_backtrace(a, (hipStream_t)stream));
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Bounded-workspace decode.  The reference keeps T1 / T2 for ONE song (tonet/for_paper.py:1852-1853); the

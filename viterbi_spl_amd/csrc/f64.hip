@@ -1,0 +1,490 @@
+// f64.hip -- the float64-accumulating decode (vit_decode_f64): the reference's float64 Viterbi variant
+// (dcnet/tf_viterbi_decoding.py:209-263), whose T1 is float64 while its parameters and emissions are float32.
+//
+//   d_0[j]  = f64( fl32(log_pi[j] + E_0[j]) )              (the reference adds two float32 arrays, then stores into T1)
+//   m_j     = max_i fl64( d_{t-1}[i] + f64(A[j][i]) );      psi_t[j] = LOWEST i attaining m_j
+//   d_t[j]  = fl64( m_j + f64(E_t[j]) )
+//   s_{T-1} = lowest argmax_j d_{T-1}[j];  s_t = psi_{t+1}[s_{t+1}];  loglik = d_{T-1}[s_{T-1}]
+//
+// Forward (f64_floor_forward_kernel): the floor form of banded.hip in double.  Rounding to float64 is monotone as rounding to
+// float32 is, so with M = max of d_{t-1} over the non-extra sources
+//   m_j = max( window candidates, fl64(M + c_j), extra-column candidates )
+// is the dense value for every plan whose floor form is proven (plan.floor_ok): the plan image is read as it is.  One song per
+// workgroup, one target per lane, value-only; the history keeps every d row and M_t ([B, T, SD64] doubles, state i in column i,
+// M_t in column S).
+// Back-trace (f64_backtrace_kernel): lazy_backtrace_kernel's banded case in double under the chunk scheme of backtrace_common.hpp
+// (a speculative pass per (song, chunk), a verify / repair pass per song).
+#include "backtrace_common.hpp"
+
+namespace vit {
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+// ---- wave primitives on doubles: the two halves travel through DPP moves, the max is one v_max_f64 per step
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_max_step_f64(const double x) {
+    const long long b = __double_as_longlong(x);
+    const int lo = (int)(unsigned)(b & 0xffffffffll), hi = (int)(b >> 32);
+    // a lane without a source (or in a masked row) keeps its own value: max(x, x) = x
+    const int slo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
+    const int shi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
+    const double s = __longlong_as_double(((long long)shi << 32) | (long long)(unsigned)slo);
+    return fmax(x, s);
+}
+// inclusive prefix max over lanes 0 .. lane (the row_shr / row_bcast ladder of wave_scan_max): lane 63 holds the wave's maximum
+__device__ __forceinline__ double wave_scan_max_f64(double x) {
+    x = dpp_max_step_f64<0x111, 0xf>(x);
+    x = dpp_max_step_f64<0x112, 0xf>(x);
+    x = dpp_max_step_f64<0x114, 0xf>(x);
+    x = dpp_max_step_f64<0x118, 0xf>(x);
+    x = dpp_max_step_f64<0x142, 0xa>(x);
+    x = dpp_max_step_f64<0x143, 0xc>(x);
+    return x;
+}
+__device__ __forceinline__ double readlane_f64(const double x, const int l) {
+    const long long b = __double_as_longlong(x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffll), l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ double wave_max_all_f64(const double x) { return readlane_f64(wave_scan_max_f64(x), 63); }
+
+// Lowest-index argmax of one d row (row[i] = d of state i; LDS or global), sources strided: lane l holds i = 64 e + l.  An all -inf
+// row resolves to index 0 like np.argmax.  Wave-uniform; *mout = the maximum.  (The double analogue of bt_row_argmax.)
+template <int EPL>
+__device__ __forceinline__ int row_argmax_f64(const double* row, const int S, const int lane, double* mout = nullptr) {
+    double d[EPL];
+    double m = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        d[e] = e * 64 + lane < S ? row[e * 64 + lane] : -INFINITY;
+        m = fmax(m, d[e]);
+    }
+    m = wave_max_all_f64(m);
+    unsigned idx = 0x7fffffffu;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        const unsigned long long mk = __ballot(d[e] == m && e * 64 + lane < S);
+        if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
+    }
+    if (mout) *mout = m;
+    return idx == 0x7fffffffu ? 0 : (int)idx;
+}
+
+// ---------------------------------------------------------------------------------------
+// Forward kernel
+// ---------------------------------------------------------------------------------------
+// LDS, in doubles from the start of the dynamic segment.  d lives in two copies per buffer: copy c holds d[i] at index i + c, so a lane
+// whose window starts at source lo reads it from copy lo & 1 at the even index lo + (lo & 1) -- 16-byte reads throughout.  The copy
+// stride DC = 14 mod 32 puts the two copies 128 bytes (mod 256) apart: the eight lanes of a 16-lane read group that read copy 0 and the
+// eight that read copy 1 (consecutive targets, consecutive window starts) cover all 64 banks once.
+// W > 64 on twelve waves (three waves per SIMD: 168 registers) keeps its last W - WR window weights in LDS, float4-interleaved as the
+// float32 kernel does (W = 128: 44 of them, which with the d buffers fills the 160 KB).
+template <int W, int NWT>
+struct F64Lds {
+    static constexpr int NP = NWT * 64;
+    static constexpr int DC = NP + 14;                   // doubles per copy
+    static constexpr int BUF = 2 * DC;                   // doubles per d buffer
+    static constexpr int WR = (W > 64 && NWT > 8) ? (W == 128 ? 84 : 64) : W;   // register-resident window weights (floats)
+    static constexpr int dls = 0;                        // [2][2][DC] d buffers
+    static constexpr int pm = dls + 2 * BUF;             // [2][16] per-wave partial maxima of M, one set per buffer
+    static constexpr int awl = pm + 2 * 16;              // [(W - WR) / 4][NP] f32x4: window weights WR .. W - 1
+    static constexpr size_t bytes() { return sizeof(double) * awl + sizeof(float) * (size_t)(W - WR) * NP; }
+    static_assert(DC % 2 == 0 && BUF % 2 == 0 && pm % 2 == 0 && awl % 2 == 0, "16-byte aligned sections");
+    static_assert(NWT <= 16 && bytes() <= kLdsBytes, "one workgroup's LDS");
+};
+
+constexpr int kF64Prefetch = 4;    // emission rows in flight (frames ahead)
+
+template <int W, int NWT, typename ET>
+__global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) {
+    using L = F64Lds<W, NWT>;
+    constexpr int NP = L::NP, DC = L::DC, BUF = L::BUF, WR = L::WR, PF = kF64Prefetch;
+    constexpr int CH = (W > 64 && NWT > 8) ? 8 : 16;        // window sources in flight
+    constexpr bool WD = W <= 32 || (W == 64 && NWT <= 8);   // the window weights live in registers as doubles (two waves per SIMD at W = 64)
+    static_assert(W % 4 == 0 && WR % 4 == 0 && PF % 2 == 0, "whole quads; the unrolled frames cycle through both buffers");
+    extern __shared__ __align__(16) unsigned char smem[];
+    double* dls = reinterpret_cast<double*>(smem) + L::dls;
+    double* pm = reinterpret_cast<double*>(smem) + L::pm;
+    f32x4* awl = reinterpret_cast<f32x4*>(reinterpret_cast<double*>(smem) + L::awl);
+    const int S = a.S, SP = a.SP, T = a.T, SD = a.SD64, nx = a.n_extras;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int song = blockIdx.x;
+    const int Tb = song_length(a.lengths, song, T);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
+    double* __restrict__ hist = a.hist + (size_t)song * T * SD;
+
+    // ---------------- per-lane constants.  Idle lanes (j >= S) publish -inf.
+    const int j = tid;
+    const bool tvalid = j < S;
+    const int jc = tvalid ? j : 0;
+    const int lo = tvalid ? reinterpret_cast<const int32_t*>(a.image + a.off_lo)[jc] : 0;
+    const double cj = tvalid ? (double)reinterpret_cast<const float*>(a.image + a.off_rowc)[jc] : -INFINITY;
+    float aw[WR];
+    float xa[kMaxExtras];
+    int xcol[kMaxExtras];
+    bool is_x = false;                                   // this lane's state is an extra column: not part of M
+    {
+        const float* __restrict__ tab = reinterpret_cast<const float*>(a.image + a.off_tabA);
+        const float* __restrict__ xaT = reinterpret_cast<const float*>(a.image + a.off_extraA);
+#pragma unroll
+        for (int w = 0; w < WR; ++w) aw[w] = tvalid ? tab[(size_t)w * SP + jc] : -INFINITY;
+#pragma unroll
+        for (int q = 0; q < (W - WR) / 4; ++q) {
+            f32x4 w4;
+            w4.x = tvalid ? tab[(size_t)(WR + 4 * q + 0) * SP + jc] : -INFINITY;
+            w4.y = tvalid ? tab[(size_t)(WR + 4 * q + 1) * SP + jc] : -INFINITY;
+            w4.z = tvalid ? tab[(size_t)(WR + 4 * q + 2) * SP + jc] : -INFINITY;
+            w4.w = tvalid ? tab[(size_t)(WR + 4 * q + 3) * SP + jc] : -INFINITY;
+            awl[q * NP + j] = w4;
+        }
+#pragma unroll
+        for (int k = 0; k < kMaxExtras; ++k) {
+            xcol[k] = k < nx ? a.extras[k] : 0;
+            xa[k] = (tvalid && k < nx) ? xaT[(size_t)k * SP + jc] : -INFINITY;
+            is_x |= (k < nx && j == xcol[k]);
+        }
+    }
+    const int cp = lo & 1;
+    const double* rp = dls + cp * DC + lo + cp;           // window start in the copy that aligns it (an even index)
+    double* wp = dls + j;                                 // own entry of copy 0 (copy 1: + DC + 1)
+
+    // produce(): publish a new d value -- both copies of buffer WB -- and the wave's share of M
+    auto produce = [&](const double dn, const int WB) {
+        wp[WB * BUF] = dn;
+        wp[WB * BUF + DC + 1] = dn;
+        const double part = wave_scan_max_f64(is_x ? -INFINITY : dn);
+        if (lane == 63) pm[WB * 16 + wv] = part;
+    };
+
+    // ---------------- frame 0: the reference forms log_pi + E_0 in float32 and stores it into the float64 T1
+    {
+        const float d0f = tvalid ? reinterpret_cast<const float*>(a.image + a.off_logpi)[jc] + load_e<ET>(E + jc) : -INFINITY;
+        const double d0 = (double)d0f;
+        if (tvalid) hist[j] = d0;
+        produce(d0, 0);
+    }
+    float er[PF];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S + jc);
+    __syncthreads();
+
+    // frame t = 1 + PF n + u reads buffer u & 1 and writes the other one; one barrier per frame
+    auto frame = [&](const int t, float& e_slot, const int u) {
+        const int RB = u & 1, WB = RB ^ 1;
+        const f64x2* __restrict__ win = reinterpret_cast<const f64x2*>(rp + RB * BUF);
+        double xd[kMaxExtras];
+#pragma unroll
+        for (int k = 0; k < kMaxExtras; ++k) xd[k] = dls[RB * BUF + xcol[k]];
+        f64x2 pq[NWT / 2];
+#pragma unroll
+        for (int q = 0; q < NWT / 2; ++q) pq[q] = reinterpret_cast<const f64x2*>(pm + RB * 16)[q];
+        // M = max of d_{t-1} over the non-extra sources
+        double M = fmax(pq[0].x, pq[0].y);
+#pragma unroll
+        for (int q = 1; q < NWT / 2; ++q) M = fmax(fmax(M, pq[q].x), pq[q].y);
+        double m0 = M + cj, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
+        // the window in chunks of CH sources (CH / 2 reads): wide windows must not hold all their data at once
+#pragma unroll
+        for (int w0 = 0; w0 < W; w0 += CH) {
+            f64x2 dw[CH / 2];
+#pragma unroll
+            for (int q = 0; q < CH / 2; ++q)
+                if (w0 + 2 * q < W) dw[q] = win[w0 / 2 + q];
+#pragma unroll
+            for (int w = w0; w < W && w < w0 + CH; w += 4) {
+                f32x4 wa;
+                if (w < WR) {
+                    // (wide windows: the weights stay float32 in registers and are widened at use -- exact; left alone the compiler
+                    // hoists the conversions out of the frame loop and keeps W doubles)
+                    if constexpr (!WD) asm volatile("" : "+v"(aw[w < WR ? w : 0]), "+v"(aw[w < WR ? w + 1 : 0]), "+v"(aw[w < WR ? w + 2 : 0]), "+v"(aw[w < WR ? w + 3 : 0]));
+                    wa = f32x4{aw[w < WR ? w : 0], aw[w < WR ? w + 1 : 0], aw[w < WR ? w + 2 : 0], aw[w < WR ? w + 3 : 0]};
+                } else {
+                    wa = awl[((w - WR) / 4) * NP + j];
+                }
+                const f64x2 da = dw[(w - w0) / 2], db = dw[(w - w0) / 2 + 1];
+                m0 = fmax(m0, da.x + (double)wa.x);
+                m1 = fmax(m1, da.y + (double)wa.y);
+                m2 = fmax(m2, db.x + (double)wa.z);
+                m3 = fmax(m3, db.y + (double)wa.w);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kMaxExtras; ++k) m1 = fmax(m1, xd[k] + (double)xa[k]);   // (-inf weights beyond the plan's extra columns)
+        double dn = fmax(fmax(m0, m1), fmax(m2, m3)) + (double)e_slot;
+        dn = tvalid ? dn : -INFINITY;
+        produce(dn, WB);
+        if (tvalid) hist[(size_t)t * SD + j] = dn;
+        if (wv == 0 && lane == 0) hist[(size_t)(t - 1) * SD + S] = M;   // M_{t-1}, next to the row it was taken over
+        const int tn = t + PF < Tb ? t + PF : Tb - 1;
+        e_slot = load_e<ET>(E + (size_t)tn * S + jc);
+        __syncthreads();
+    };
+    int t = 1;
+    for (; t + PF - 1 < Tb; t += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
+    }
+#pragma unroll
+    for (int k = 0; k < PF - 1; ++k)
+        if (t + k < Tb) frame(t + k, er[k], k);
+
+    // ---------------- the terminal state: lowest-index argmax of d_{Tb-1}, and its value
+    if (wv == 0) {
+        const int fb = (Tb - 1) & 1;                      // buffer holding d_{Tb-1}
+        double best;
+        const int s = row_argmax_f64<NWT>(dls + fb * BUF, S, lane, &best);
+        if (lane == 0) {
+            a.last_state[song] = s;
+            if (a.loglik) a.loglik[song] = best;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// Back-trace kernel
+// ---------------------------------------------------------------------------------------
+// One wave per (song, chunk) in MODE 0, per song in MODE 1; kF64BtWaves waves per workgroup.  A wave keeps the d row of the frame it
+// decides in its own LDS row and the next row (one frame down) in flight in registers: the row a step reads does not depend on the
+// path, only the columns do.  For the path state j at t + 1:
+//   * candidate c = 64 k + lane: c < W window source lo_j + c, W <= c < W + n_extras an extra column; its weight is entry c of the
+//     plan's per-target candidate row (tabX[j]: window, extra columns, row constant), read from the image (L2-resident);
+//   * fl64(M_t + c_j) bounds every row-constant candidate: below the candidates' maximum, the lowest matching source wins;
+//   * otherwise all S candidates are evaluated and the lowest index attaining the maximum wins (an all -inf frame: state 0).
+constexpr int kF64BtWaves = 4;
+constexpr int kF64BtSlots = 3;     // candidate slots per lane: W + kMaxExtras <= 192
+
+template <int NWT, int MODE>
+__global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args a) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    constexpr int EPL = NWT, NP = NWT * 64, KC = kF64BtSlots;
+    const int S = a.S, SD = a.SD64, T = a.T, W = a.W, nx = a.n_extras;
+    const int WX1 = W + kMaxExtras + 1;                   // candidate-table row: window, extras, row constant
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    double* rowL = reinterpret_cast<double*>(smem) + (size_t)wv * NP;   // this wave's d row
+    const int C = a.chunks;
+    const long long gw = (long long)blockIdx.x * kF64BtWaves + wv;
+    const long long song_l = MODE == 0 ? gw / C : gw;
+    if (song_l >= a.B) return;
+    const int song = (int)song_l;
+    const int chunk = MODE == 0 ? (int)(gw % C) : 0;
+    const int Tb = song_length(a.lengths, song, T);
+    int32_t* states = a.states + (size_t)song * T;       // (no __restrict__: MODE 1 reads what chase() stored)
+    int32_t* entry = a.entry + (size_t)song * C;
+    const double* __restrict__ hist = a.hist + (size_t)song * T * SD;
+    const float* __restrict__ tabX = reinterpret_cast<const float*>(a.image + a.off_tabX);
+    const int32_t* __restrict__ loT = reinterpret_cast<const int32_t*>(a.image + a.off_lo);
+
+    // per-lane constants of the candidate slots and of the strided sources
+    bool isw[KC], cand[KC];
+    int xs[KC];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+        const int c = 64 * k + lane;
+        isw[k] = c < W;
+        cand[k] = c < W + nx;
+        xs[k] = (c >= W && c < W + nx) ? a.extras[(c - W) & (kMaxExtras - 1)] : 0;
+    }
+    int xk[EPL];                                          // strided source i = 64 e + lane: -1 ordinary, k = extra column k, -2 none
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        const int i = e * 64 + lane;
+        int x = i < S ? -1 : -2;
+#pragma unroll
+        for (int k = 0; k < kMaxExtras; ++k) x = (k < nx && i == a.extras[k]) ? k : x;
+        xk[e] = x;
+    }
+
+    auto fetch = [&](double (&stage)[EPL], double& Mrow, int& old, const int t) {
+        const double* __restrict__ r = hist + (size_t)t * SD;
+#pragma unroll
+        for (int e = 0; e < EPL; ++e) stage[e] = e * 64 + lane < S ? r[e * 64 + lane] : -INFINITY;
+        Mrow = r[S];
+        old = MODE == 1 ? states[t] : -1;
+    };
+
+    // chase(top, bottom, cur, write): decide the states of frames top .. bottom (descending) from the d rows top .. bottom, starting
+    // from state `cur` at frame top + 1; returns the state at frame `bottom`
+    auto chase = [&](const int top, const int bottom, int cur, const bool write) -> int {
+        if (top < bottom) return cur;
+        double stage[EPL], Mn;
+        int oldn;
+        fetch(stage, Mn, oldn, top);
+        for (int t = top; t >= bottom; --t) {
+            cur = __builtin_amdgcn_readfirstlane(cur);
+            // the weights of target cur: issued first, they are the step's only dependent global reads
+            const int lo = __builtin_amdgcn_readfirstlane(loT[cur]);
+            const float* __restrict__ tx = tabX + (size_t)cur * WX1;
+            float av[KC];
+#pragma unroll
+            for (int k = 0; k < KC; ++k) av[k] = (64 * k < W + nx && cand[k]) ? tx[64 * k + lane] : -INFINITY;
+            const double cj = (double)tx[W + kMaxExtras];
+#pragma unroll
+            for (int e = 0; e < EPL; ++e) rowL[e * 64 + lane] = stage[e];
+            const double Mt = Mn;
+            const int old = oldn;
+            if (t > bottom) fetch(stage, Mn, oldn, t - 1);
+            // the row is this wave's own: every lane's stores above before any lane's reads below (LDS runs a wave's accesses in
+            // order; the fence and the wave barrier keep the compiler from moving the reads up, and cost no instruction)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            double v[KC];
+            double m = -INFINITY;
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                v[k] = -INFINITY;
+                if (64 * k < W + nx) {
+                    const double dv = cand[k] ? rowL[isw[k] ? lo + 64 * k + lane : xs[k]] : -INFINITY;
+                    v[k] = cand[k] ? dv + (double)av[k] : -INFINITY;
+                }
+                m = fmax(m, v[k]);
+            }
+            m = wave_max_all_f64(m);
+            const double bound = Mt + cj;                  // fl64(M_t + c_j): every row-constant candidate is at most this
+            unsigned idx = 0x7fffffffu;
+            double mm = m;
+            if (!(bound < m)) {
+                // full evaluation: a row-constant candidate may tie or win
+                double vf[EPL];
+                double m2 = -INFINITY;
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) {
+                    const int i = e * 64 + lane;
+                    const bool excl = xk[e] != -1 || (unsigned)(i - lo) < (unsigned)W;   // covered by v[] (or no source at all)
+                    vf[e] = excl ? -INFINITY : rowL[i] + cj;
+                    m2 = fmax(m2, vf[e]);
+                }
+                mm = fmax(m, wave_max_all_f64(m2));
+#pragma unroll
+                for (int e = 0; e < EPL; ++e) {
+                    const int i = e * 64 + lane;
+                    const bool excl = xk[e] != -1 || (unsigned)(i - lo) < (unsigned)W;
+                    const unsigned long long mk = __ballot(vf[e] == mm && !excl);
+                    if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
+                }
+            }
+            // lowest source among the window / extra-column candidates that attain the maximum
+            bool have_w = false;
+#pragma unroll
+            for (int k = 0; k < KC; ++k) {
+                if (64 * k >= W + nx) continue;
+                const unsigned long long mk = __ballot(v[k] == mm && cand[k]);
+                const unsigned long long mw = mk & __ballot(isw[k]);
+                if (mw && !have_w) {                           // window candidates ascend with the source index
+                    const unsigned c = lo + 64 * k + __builtin_ctzll(mw);
+                    idx = c < idx ? c : idx;
+                    have_w = true;
+                }
+                unsigned long long mx = mk & ~__ballot(isw[k]);   // extra columns: arbitrary indices
+                while (mx) {
+                    const unsigned c = (unsigned)__builtin_amdgcn_readlane(xs[k], __builtin_ctzll(mx));
+                    idx = c < idx ? c : idx;
+                    mx &= mx - 1;
+                }
+            }
+            cur = idx == 0x7fffffffu ? 0 : (int)idx;       // (an all -inf frame resolves to state 0 like np.argmax)
+            // MODE 1 re-chases a chunk whose assumed entry state was wrong: as soon as the new path meets the stored one the rest of
+            // the chunk is already right (the step below a state depends on that state only)
+            if (MODE == 1 && cur == __builtin_amdgcn_readfirstlane(old)) return __builtin_amdgcn_readfirstlane(states[bottom]);
+            if (write && lane == 0) states[t] = cur;
+        }
+        return cur;
+    };
+
+    // ---- the chunk scheme (bt_run_chunks of backtrace_common.hpp, with the guess taken from a row of doubles)
+    const int Lf = Tb - 1;
+    if (MODE == 0) {
+        const int last = __builtin_amdgcn_readfirstlane(a.last_state[song]);
+        int lo_c, hi_c;
+        bt_chunk_bounds(Lf, chunk, C, lo_c, hi_c);
+        if (chunk == C - 1) {
+            for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
+            if (lane == 0) states[Tb - 1] = last;
+        }
+        int top = hi_c - 1 + a.warm;
+        int cur;
+        if (chunk == C - 1 || top >= Lf - 1) {
+            top = Lf - 1;
+            cur = last;
+        } else {
+            cur = row_argmax_f64<EPL>(hist + (size_t)(top + 1) * SD, S, lane);   // guess: lowest-index argmax of d row top + 1
+        }
+        if (hi_c <= lo_c) {                               // empty chunk (very short song)
+            if (lane == 0) entry[chunk] = cur;
+            return;
+        }
+        cur = chase(top, hi_c, cur, false);               // warm-up: frames top .. hi_c, nothing written
+        if (lane == 0) entry[chunk] = cur;                // state this chunk assumed at frame hi_c
+        chase(hi_c - 1, lo_c, cur, true);
+    } else {
+        int truth = -1;                                   // verified state at frame hi_c of the chunk being checked
+        for (int c = C - 2; c >= 0; --c) {
+            int lo_c, hi_c;
+            bt_chunk_bounds(Lf, c, C, lo_c, hi_c);
+            if (truth < 0) truth = __builtin_amdgcn_readfirstlane(states[hi_c]);
+            const int assumed = __builtin_amdgcn_readfirstlane(entry[c]);
+            if (hi_c > lo_c && assumed != truth) truth = chase(hi_c - 1, lo_c, truth, true);   // re-chase from the true state; ends at frame lo_c
+            else truth = -1;                              // chunk c stands: its frame lo_c is already in `states`
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// launchers
+// ---------------------------------------------------------------------------------------
+template <typename F>
+static hipError_t f64_dispatch_width(int W, F&& f) {
+    static_assert(sizeof(kBandedWidths) / sizeof(int) == 6, "one case per instantiated window width");
+    switch (W) {
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        case 64: return f(std::integral_constant<int, 64>{});
+        case 84: return f(std::integral_constant<int, 84>{});
+        case 96: return f(std::integral_constant<int, 96>{});
+        case 128: return f(std::integral_constant<int, 128>{});
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+template <typename F>
+static hipError_t f64_dispatch_waves(int S, F&& f) {
+    switch (banded_waves_for(S)) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        default: return hipErrorInvalidConfiguration;
+    }
+}
+
+hipError_t launch_f64_forward(const F64Args& a, bool f16, hipStream_t st) {
+    if (a.B < 1 || a.T < 1 || a.W > a.S) return hipErrorInvalidValue;
+    return f64_dispatch_width(a.W, [&](auto w) {
+        return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
+            constexpr int W = decltype(w)::value, NWT = decltype(n)::value;
+            constexpr size_t lds = F64Lds<W, NWT>::bytes();
+            if (f16) hipLaunchKernelGGL((f64_floor_forward_kernel<W, NWT, __half>), dim3((unsigned)a.B), dim3(NWT * 64), lds, st, a);
+            else hipLaunchKernelGGL((f64_floor_forward_kernel<W, NWT, float>), dim3((unsigned)a.B), dim3(NWT * 64), lds, st, a);
+            return hipGetLastError();
+        });
+    });
+}
+
+hipError_t launch_f64_backtrace(const F64Args& a, hipStream_t st) {
+    if (a.B < 1 || a.chunks < 1 || a.chunks > kBtMaxChunks || a.W + kMaxExtras > 64 * kF64BtSlots) return hipErrorInvalidValue;
+    return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
+        constexpr int NWT = decltype(n)::value;
+        constexpr size_t lds = sizeof(double) * kF64BtWaves * NWT * 64;
+        const long long waves0 = (long long)a.B * a.chunks;
+        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 0>), dim3((unsigned)((waves0 + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess || a.chunks <= 1) return e;
+        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 1>), dim3((unsigned)((a.B + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
+        return hipGetLastError();
+    });
+}
+
+}  // namespace vit

@@ -1,4 +1,4 @@
-// kernels.hpp -- launch interface between the C ABI (capi.hip) and the kernel files (dense, step, banded, wave, emission, activations, fused,
+// kernels.hpp -- launch interface between the C ABI (capi.hip) and the kernel files (dense, step, banded, wave, emission, activations, fused, f64,
 // backtrace_rows / _sparse / _half / _lane .hip; those four share backtrace_common.hpp: the chunk scheme, the pieces of a decision and
 // the launch helpers).  The two workgroup forward kernels that have variants -- banded_floor_forward_kernel (banded.hip, banded_pc.hip)
 // and step4s_forward_kernel (step.hip) -- take one WgVariant, share their song / segment bookkeeping as text (wg_cursor.inc) and are
@@ -190,6 +190,33 @@ constexpr bool fused_logits_applies(int S, int wave_ok, int wave_npl, int wave_d
            ((mode == 0 && spw == 5) || (mode == 1 && spw == 15) || (mode == 2 && spw == 5));
 }
 hipError_t launch_fused_logits(const FusedArgs& fa, hipStream_t st);
+
+// f64.hip: the float64-accumulating decode (vit_decode_f64): float32 parameters and emissions, d (the reference's float64 T1) in double.
+// The floor form in double, so what it serves is what the floor form is proven and instantiated for: banded plans with floor_ok, no
+// dense rows, an instantiated window width and a target-wave count.  Unstructured, step and dense-row plans are refused.
+constexpr bool f64_decode_applies(int S, int W, bool banded_ok, bool floor_ok, int n_dense) {
+    return banded_ok && floor_ok && n_dense == 0 && banded_width_instantiated(W) && W <= S && banded_waves_for(S) > 0;
+}
+// history row stride in doubles: state i in column i, the frame maximum M_t (over the non-extra sources) in column S; rows 16-byte aligned
+constexpr int f64_hist_stride(int S) { return (S + 3) / 2 * 2; }
+struct F64Args {
+    const uint8_t* image;   // device plan image, read as it is: tabA, lo, rowc, extraA, log_pi, tabX
+    const void* logE;       // [B,T,S] f32 or f16
+    const int64_t* lengths; // [B] or null
+    double* hist;           // [B,T,SD64]
+    int32_t* last_state;    // [B]
+    double* loglik;         // [B] or null
+    int32_t* states;        // [B,T]
+    int32_t* entry;         // [B,chunks] state each chunk assumed at its upper boundary
+    int64_t B;
+    int T, S, SP, SD64, W;
+    int n_extras;
+    int extras[kMaxExtras];
+    int chunks, warm;       // time-parallel back-trace: chunks per song (<= kBtMaxChunks), warm-up frames
+    size_t off_logpi, off_lo, off_tabA, off_extraA, off_rowc, off_tabX;
+};
+hipError_t launch_f64_forward(const F64Args& a, bool f16, hipStream_t st);
+hipError_t launch_f64_backtrace(const F64Args& a, hipStream_t st);
 hipError_t launch_dense(const FwdArgs& a, int songs_per_group, bool f16, hipStream_t st);
 hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st);

@@ -310,6 +310,48 @@ class ViterbiDecoder:
             states = states.to(out_dtype)
         return (states[0], loglik[0]) if single else (states, loglik)
 
+    # ------------------------------------------------------------------ float64-accumulating decode
+    def workspace_bytes_f64(self, B: int, T: int) -> int:
+        """Workspace bytes of ``decode_f64``; raises ViterbiHipError for a plan it does not serve."""
+        need = int(_lib.load().vit_workspace_bytes_f64(self._plan, B, T))
+        if need == 0 and B > 0:
+            raise _lib.ViterbiHipError("the float64 decode needs a banded plan whose floor form is proven, without dense rows (unstructured "
+                                       "matrices, the Durrieu step matrices and scan-only plans are not served)")
+        return need
+
+    def decode_f64(self, emission_logits: torch.Tensor, lengths: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.int64,
+                   workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The reference's float64 Viterbi variant (dcnet/tf_viterbi_decoding.py:209-263) on float32 / float16 emissions
+        (``vit_decode_f64``): the running score is kept in float64, bit for bit what that NumPy loop computes on float32 parameters.
+        Returns (states [B,T] or [T] of ``out_dtype``, loglik float64 [B] or scalar).  On long inputs the path differs from
+        ``decode``'s in a few frames out of thousands; this one scores better.  ``workspace``: a uint8 tensor of at least
+        ``workspace_bytes_f64(B, T) + 256`` bytes on the decoder's device (the caller keeps it alive until the stream has run the
+        decode), else the decoder's own buffer, the one ``decode`` uses (twice that decode's bytes: rows of doubles; it stays that
+        large until the decoder goes).  The call does not synchronise."""
+        lib = _lib.load()
+        logE, single, dt = self._check_emissions(emission_logits)
+        B, T, _ = logE.shape
+        if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
+            raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
+        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
+        loglik = torch.empty((B,), dtype=torch.float64, device=self.device)
+        if B > 0:
+            need = self.workspace_bytes_f64(B, T)
+            if workspace is None:                            # the decoder's slot-0 buffer, shared with decode() and grown like it: no synchronisation
+                if self._ws is None or self._ws.numel() < need + 256:
+                    self._ws = None
+                    self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                workspace = self._ws
+            _, ws_ptr, ws_bytes, _ = self._call_workspace(need, workspace)
+            with torch.cuda.device(self.device):
+                rc = lib.vit_decode_f64(self._plan, logE.data_ptr(), dt, B, T, lengths.data_ptr() if lengths is not None else None,
+                                        ws_ptr, ws_bytes, states.data_ptr(), loglik.data_ptr(),
+                                        torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(rc, "vit_decode_f64")
+        if out_dtype != torch.int32:
+            states = states.to(out_dtype)
+        return (states[0], loglik[0]) if single else (states, loglik)
+
     # ------------------------------------------------------------------ bounded-workspace decode
     def workspace_bytes_checkpointed(self, B: int, T: int, segment_frames: int) -> int:
         """Workspace bytes of ``decode_checkpointed``; raises ViterbiHipError for a plan or a segment length it does not serve."""

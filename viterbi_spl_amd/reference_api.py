@@ -8,6 +8,7 @@ last bit a GPU cannot be trusted to reproduce.
 
   family A  viterbi_librosa_c_fn / viterbi_numba_fn(*, transition_matrix, prob_init, probs_st)
             dcnet/tf_viterbi_decoding.py:119-207, dcnet/main.py:2417-2468 (+10 copies)
+  float64   viterbi_librosa_f64_fn(*, transition_matrix, prob_init, probs_st)    dcnet/tf_viterbi_decoding.py:209-263
   family D  viterbi_librosa_fn(*, log_transition_matrix_T, log_prob_init, log_probs_st)
             imm/tf_viterbi.py:75-109
   AOT core  viterbi_numba_core(B, prob_init, probs)   dcnet/aot_viterbi_core.py:8-54
@@ -71,6 +72,21 @@ def viterbi_librosa_c_fn(*, transition_matrix, prob_init, probs_st):
     log_pi = np.log(prob_init + tinyp).astype(np.float32)
     logE = np.require(np.log(probs_st.T + tinyp), np.float32, ['C'])
     return _run(logA_T, log_pi, logE)
+
+
+def viterbi_librosa_f64_fn(*, transition_matrix, prob_init, probs_st):
+    """dcnet's float64 function, ``viterbi_librosa_fn`` at dcnet/tf_viterbi_decoding.py:209-263 (that name is imm's log-domain
+    function here, hence the suffix): float32 probabilities in, the log taken on the host, the running score T1 in float64
+    (``ViterbiDecoder.decode_f64``); int64[T] out.  float64 parameters stay refused as in the other adapters."""
+    S = _check_probs(transition_matrix, prob_init, probs_st)
+    assert probs_st.shape == (S, probs_st.shape[1])
+    tinyp = np.finfo(probs_st.dtype).tiny
+    logA_T = np.require(np.log(transition_matrix.T + tinyp), np.float32, ['C'])
+    log_pi = np.log(prob_init + tinyp).astype(np.float32)
+    logE = np.require(np.log(probs_st.T + tinyp), np.float32, ['C'])
+    dec = get_decoder(logA_T, log_pi)
+    states, _ = dec.decode_f64(torch.from_numpy(logE).to(dec.device), out_dtype=torch.int64)
+    return states.cpu().numpy()
 
 
 def viterbi_numba_fn(*, transition_matrix, prob_init, probs_st):
