@@ -304,11 +304,11 @@ __global__ void __launch_bounds__((NWT + (DW ? 3 : 2)) * 64) banded_forward_kern
 //
 // Six waves on four SIMDs put two waves on SIMD 0 and 1 and one on SIMD 2 and 3, and the frame waits for the full ones.
 // Here every SIMD carries one FULL wave (waves 0-3: one target per lane, the whole window, exactly the frame body of
-// banded_floor_forward_kernel) and one HALF-WINDOW wave (waves 4-7): lane l < 32 of wave w evaluates sources 0-15 of target
-// 256 + 32 (w - 4) + l, lane l + 32 sources 16-31 of the same target (4 reads, 8 packed adds, 8 max3 each).  The lower half
-// also carries the floor candidate fl(M + c_j), the upper half the extra columns; the other half holds -inf for them, so one
-// instruction stream serves both.  The two partial maxima are joined in registers (v_permlane32_swap + v_max_f32) and only
-// then is the emission added: max is exact and order-free, every candidate still gets exactly one rounded add, so the
+// banded_floor_forward_kernel) and one HALF-WINDOW wave (waves 4-7): the lanes l and l ^ 8 of wave w share target
+// 256 + 32 (w - 4) + split_half_target(l); the one with bit 3 clear evaluates its sources 0-15, the other its sources 16-31 (4 reads,
+// 8 packed adds, 8 max3 each).  The lower half also carries the floor candidate fl(M + c_j), the upper half the extra columns; the other half holds -inf for them, so one
+// instruction stream serves both.  The two partial maxima are joined in registers (one v_max_f32_dpp: the partner lanes
+// are half a DPP row apart, row_ror:8) and only then is the emission added: max is exact and order-free, every candidate still gets exactly one rounded add, so the
 // result is the float the one-target kernel forms.  After the join both lanes of a target hold its new delta; the lower
 // lane writes copies 0 and 1 of it, the upper lane copies 2 and 3 (two ds_write each, nothing dead), and both add it into
 // the frame-maximum slots (a duplicate changes no maximum).  Both lanes store the history column (the same bits to the
@@ -333,8 +333,8 @@ __device__ __forceinline__ void split_frames(std::integer_sequence<int, K...>, F
 // WF: the window entries a full wave evaluates (FwdArgs::floor_live, proven by the plan: floor_live_width).  WF = W is the whole window.
 // WF = 4 n + 1 < W reads n quads and position WF - 1 as one float, loads no weight beyond it, and reduces its WF + 2 candidates
 // (window, floor, extra column) in (WF + 1) / 2 v_max3_f32 (15 at WF = 29): two chains seeded with fl(M + c_j) and with the extra-column
-// sum, one pair of sums per step, and the single entry joins the two chains in the last one.  M's four slots take one v_max3_f32 and one
-// v_max_f32 more, as ever: 16 + 1 per frame at WF = 29, 37 VALU in all.  The half waves always take W / 2 each.
+// sum, one pair of sums per step, and the single entry joins the two chains in the last one.  M takes one v_max3_f32 more (XQ: three
+// slots; else four slots and a v_max_f32 on top): 16 per frame at WF = 29, 36 VALU in all.  The half waves always take W / 2 each.
 template <int NXT, int PF, typename ET, bool WPR = false, bool XQ = false, int WF = 32>
 __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) banded_floor_split_forward_kernel(FwdArgs a) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -355,14 +355,14 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool half = wv >= NWF;                                          // wave-uniform role
-    const int hh = half ? lane >> 5 : 0;                                  // which half of the window (half waves)
+    const int hh = half ? split_half_of(lane) : 0;                        // which half of the window (half waves: lanes l and l ^ 8 share a target)
     const int song = blockIdx.x;
     const int Tb = song_length(a.lengths, song, T);
     const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
     float* __restrict__ hist = a.hist + (size_t)song * T * SD;
 
     // ---------------- per-lane constants.  Idle targets (j >= S) carry -inf tables: their delta stays -inf.
-    const int j = half ? 64 * NWF + 32 * (wv - NWF) + (lane & 31) : tid;
+    const int j = half ? 64 * NWF + 32 * (wv - NWF) + split_half_target(lane) : tid;
     const bool tvalid = j < S;
     const bool own = tvalid && hh == 0;                                   // the lane that answers for its target (frame 0, terminal state)
     const int jc = tvalid ? j : 0;
@@ -382,9 +382,14 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
         is_x |= (k < nx && j == xcol[k]);
     }
     const int sh = a.win_shift;                                           // (see banded_floor_forward_kernel)
-    const int lov = (tvalid ? lo : 0) + sh;
+    // (an idle target reads the last window, where the clamped rows next to it read: one address for all of them, no bank shared with
+    // a live partner lane -- from window 0 the lanes of target S - 1 and the idle lanes of its read group met on one bank, floor_lds_check.hip)
+    const int lov = (tvalid ? lo : S - W) + sh;
     const float* rp = dls + 4 + (lov & 3) * DC + (lov & ~3) + 16 * hh;    // (half of the) window in the copy that aligns it
-    float* fmp = fmg + fm_slot((XQ && is_x) ? (lane | 1) : lane);
+    // XQ: M lives in slots 0 .. 2 and both lanes of the extra column add into slot 3 of the same quad of floats (split_fm_slot), so the
+    // frame's one 16-byte read of the group brings M's three slots and delta[x]; every other plan keeps the four slots and its own read of x
+    constexpr bool XS = XQ;                                               // the extra column in M's slot quad
+    float* fmp = fmg + (XS ? split_fm_slot(lane, is_x) : fm_slot(lane));
     static_assert(!XQ || NXT == 1, "the extra column leaves M by address only where the launcher proved its quad idle");
 
     for (int k = tid; k < L::reset; k += NW * 64) dls[k] = -INFINITY;
@@ -420,12 +425,14 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
         // own entry of copy 0 (copy c: + c*DC - c); an upper lane starts at copy 2
         float* wp = dls + 4 + sh + j + (HALF ? hh * split_upper_off(DC) : 0);
         // the extra columns' positions in copy 0, kept in a vector register: they are wave-uniform, and from a scalar register every
-        // frame's ds_read_b32 needed a v_mov first
-        int xo[NXL > 0 ? NXL : 1];
+        // frame's ds_read_b32 needed a v_mov first  (XS: delta[x] comes with the M slots, no read and no register)
+        [[maybe_unused]] int xo[NXL > 0 ? NXL : 1];
+        if constexpr (!XS) {
 #pragma unroll
-        for (int k = 0; k < NXL; ++k) {
-            xo[k] = 4 + sh + xcol[k];
-            asm volatile("" : "+v"(xo[k]));
+            for (int k = 0; k < NXL; ++k) {
+                xo[k] = 4 + sh + xcol[k];
+                asm volatile("" : "+v"(xo[k]));
+            }
         }
 
         auto produce = [&](const float dn, const int WB, const int G, const int Z) {
@@ -477,12 +484,16 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             float xd[NXL > 0 ? NXL : 1];
             f32x4 fq;
             [[maybe_unused]] float m0, m1 = -INFINITY, m2 = -INFINITY, m3 = -INFINITY;
-            // The small reads first (extra columns, then the M slots), the window quads right behind them and nothing after: the window
+            // The small reads first (extra columns -- none of their own under XS --, then the M slots), the window quads right behind them and nothing after: the window
             // quads are the LAST LDS operations of the frame's read burst (the two quads of a pair in either order).  The paired waits below count on that
             // (lgkmcnt(2) = "all but the last two quads"); a read moved behind the window would turn them into waits for less than they
-            // name, and the compiler would add its own wait again.
+            // name, and the compiler would add its own wait again.  Every stated lgkmcnt counts the reads BEHIND the one it waits for
+            // (split_reads_behind), so the extra column's read, the first of the burst, does not appear in any of them: with or without
+            // it (XS) the immediates are the same, and the first wait covers the M slots, hence delta[x], either way.
+            if constexpr (!XS) {
 #pragma unroll
-            for (int k = 0; k < NXL; ++k) xd[k] = dls[xo[k] + RB * BUF];
+                for (int k = 0; k < NXL; ++k) xd[k] = dls[xo[k] + RB * BUF];
+            }
             fq = reinterpret_cast<const f32x4*>(fmg + GR * kFmGroupFloats)[0];
             asm volatile("" ::: "memory");
             f32x4 dw[WL / 4];
@@ -497,7 +508,8 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
                 __builtin_amdgcn_s_waitcnt(split_waitcnt(kNoVmWait, split_reads_behind(WL / 4, 0)));
                 asm volatile("" : "+v"(fq), "+v"(dw[0]), "+v"(dw[1]));
             }
-            const float M = fmaxf(fmaxf(fq.x, fq.y), fmaxf(fq.z, fq.w));
+            const float M = XS ? fmaxf(fmaxf(fq.x, fq.y), fq.z) : fmaxf(fmaxf(fq.x, fq.y), fmaxf(fq.z, fq.w));
+            if constexpr (XS) xd[0] = fq.w;                               // delta[x] of this frame, bit for bit (split_fm_slot)
             m0 = M + cj;
             asm volatile("" ::"v"(m0));   // M + c_j stays in front of the window sums (with the explicit waits below the add otherwise sinks behind them)
             __builtin_amdgcn_sched_barrier(0);
@@ -589,7 +601,7 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
                 for (int k = 0; k < NXL; ++k) m1 = fmaxf(m1, xd[k] + xa[k]);
                 mx = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
             }
-            if constexpr (HALF) mx = max_other_half(mx);                  // join the two halves of the window
+            if constexpr (HALF) mx = max_lane_xor8(mx);                   // join the two halves of the window (partner lanes, one DPP maximum)
             const float dn = mx + e_slot;
 #ifdef VIT_TIMING_HOOKS
             if constexpr (wprobe) wp_.before_publish(dn);

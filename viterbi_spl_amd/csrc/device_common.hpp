@@ -94,6 +94,12 @@ __device__ __forceinline__ float max_other_half(float x) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
+// max(x[l], x[l ^ 8]) in every lane: row_ror:8 turns each row of sixteen lanes by half a row, and the compiler folds the move into
+// the maximum (one v_max_f32_dpp).  Every lane has a source, so the old value is never taken.
+inline constexpr int kDppRowRor8 = 0x128;
+__device__ __forceinline__ float max_lane_xor8(float x) {
+    return fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), kDppRowRor8, 0xf, 0xf, false)));
+}
 // lane l <- x[l-1], lane 0 <- fill   (wave_shr:1)
 __device__ __forceinline__ float wave_shift_up(float x, float fill) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(x), 0x138, 0xf, 0xf, false));

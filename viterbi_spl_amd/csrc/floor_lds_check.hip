@@ -5,6 +5,9 @@
 //   * the four shifted delta copies of a buffer, the two buffers, the slot groups and the tail of the segment do not overlap;
 //   * every lane's window read is 16-byte aligned and stays inside the copy it reads, and reads the delta values it means to;
 //   * every lane's four (split kernel, half waves: two) copy writes land inside their copies;
+//   * the half waves' lane map (split_half_of, split_half_target): partner lanes l and l ^ 8, 32 targets in ascending lane order, and
+//     the LDS cycles of a half wave's four ds_read_b128 under the hardware's lane groups, against the map with the halves 32 lanes apart;
+//   * the split kernel's frame-maximum slots with the extra column in M's quad (split_fm_slot);
 //   * which pairs of copy writes one ds_write2_b32 / ds_write2st64_b32 could encode (two 8-bit offsets in units of 1 / 64 dwords
 //     from one address): printed per layout, and checked against the argument in DESIGN.md 7 for why none exists from NP = 256 on.
 #include <cstdio>
@@ -89,7 +92,7 @@ static void replay(const char* name, int NWT, bool split) {
         for (int sh = 0; sh < 4; ++sh)
             for (int wv = kSplitFullWaves; wv < kSplitFullWaves + kSplitHalfWaves; ++wv)
                 for (int lane = 0; lane < 64; ++lane) {
-                    const int hh = lane >> 5, j = 64 * kSplitFullWaves + 32 * (wv - kSplitFullWaves) + (lane & 31);
+                    const int hh = split_half_of(lane), j = 64 * kSplitFullWaves + 32 * (wv - kSplitFullWaves) + split_half_target(lane);
                     CHECK(j >= 64 * kSplitFullWaves && j < kSplitStates, "split target %d", j);
                     const int wp = L::dls + 4 + sh + j + hh * split_upper_off(DC);
                     for (int c = 0; c < 2; ++c) {
@@ -113,6 +116,130 @@ static void replay(const char* name, int NWT, bool split) {
     CHECK(plain == (NP + 15 <= 255), "%s: plain pair iff a copy fits 255 dwords", name);
     std::printf("%-28s NP %4d DC %4d bytes %6zu  copy stride %4d dwords: ds_write2_b32 %s, ds_write2st64_b32 no\n", name, NP, DC, L::bytes(),
                 stride, plain ? "pairs (0,1) and (2,3)" : "no");
+}
+
+// ---- the half waves' lane map
+// the map this one replaced: lane l and lane l + 32 share target l & 31
+static int old_half_of(int lane) { return lane >> 5; }
+static int old_half_target(int lane) { return lane & 31; }
+static void replay_lane_map() {
+    int next = 0;                                                         // lower lanes, in lane order, take targets 0, 1, 2, ...
+    for (int lane = 0; lane < 64; ++lane) {
+        const int hh = split_half_of(lane), k = split_half_target(lane), p = lane ^ 8;
+        CHECK(hh == 0 || hh == 1, "lane %d: half %d", lane, hh);
+        CHECK(k >= 0 && k < 32, "lane %d: target %d", lane, k);
+        CHECK(split_half_target(p) == k && split_half_of(p) == 1 - hh, "lane %d: partner %d holds target %d half %d", lane, p, split_half_target(p), split_half_of(p));
+        CHECK((lane >> 4) == (p >> 4), "lane %d: partner %d in another DPP row", lane, p);
+        CHECK((k & 3) == (lane & 3), "lane %d: target %d sits elsewhere in its quad", lane, k);
+        if (hh == 0) { CHECK(k == next, "lower lane %d takes target %d, not %d", lane, k, next); ++next; }
+    }
+    CHECK(next == 32, "%d lower lanes", next);
+    std::printf("split lane map: partner l ^ 8 (row_ror:8), 32 lower lanes in ascending target order: ok\n");
+}
+
+// LDS cycles of one ds_read_b128 of a wave: the hardware serves it in four groups of sixteen lanes; a group takes one cycle, and one more
+// for every further distinct address on its busiest bank (64 banks of 4 bytes, a lane covers four of them).
+static int read_b128_cycles(const int* addr /* float positions, 64 lanes */) {
+    static const int groups[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
+                                      {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
+                                      {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
+                                      {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
+    int cycles = 0;
+    for (int g = 0; g < 4; ++g) {
+        int worst = 1;
+        for (int bank = 0; bank < 64; bank += 4) {                        // aligned 16-byte reads: whole 4-bank groups
+            int seen[16], n = 0;
+            for (int i = 0; i < 16; ++i) {
+                const int a = addr[groups[g][i]];
+                if (a % 64 != bank) continue;
+                bool dup = false;
+                for (int q = 0; q < n; ++q) dup |= seen[q] == a;
+                if (!dup) seen[n++] = a;
+            }
+            if (n > worst) worst = n;
+        }
+        cycles += worst;
+    }
+    return cycles;
+}
+// The four window reads of half wave hw at S states, window starts lo_j = clamp(j - off, 0, S - W) (the affine plans; idle targets
+// read the last window, S - W, as the kernel has them do)
+template <typename HF, typename TF>
+static int half_wave_read_cycles(int S, int off, int sh, int hw, HF half_of, TF target_of) {
+    using L = FloorSplitLds;
+    constexpr int W = 32;
+    int cycles = 0;
+    for (int q = 0; q < W / 2 / 4; ++q) {
+        int addr[64];
+        for (int lane = 0; lane < 64; ++lane) {
+            const int j = 64 * kSplitFullWaves + 32 * hw + target_of(lane);
+            int lo = j - off;
+            lo = lo < 0 ? 0 : (lo > S - W ? S - W : lo);
+            const int lov = (j < S ? lo : S - W) + sh;
+            addr[lane] = L::dls + 4 + (lov & 3) * L::DC + (lov & ~3) + 16 * half_of(lane) + 4 * q;
+        }
+        cycles += read_b128_cycles(addr);
+    }
+    return cycles;
+}
+static void replay_read_cycles(int S, int off) {
+    for (int sh = 0; sh < 4; ++sh) {
+        int was[kSplitHalfWaves], now[kSplitHalfWaves];
+        for (int hw = 0; hw < kSplitHalfWaves; ++hw) {
+            was[hw] = half_wave_read_cycles(S, off, sh, hw, old_half_of, old_half_target);
+            now[hw] = half_wave_read_cycles(S, off, sh, hw, split_half_of, split_half_target);
+            // (only the plan's own shift, off mod 4, ever runs: the others are printed for the record)
+            if (sh == off % 4) CHECK(now[hw] <= was[hw], "S %d sh %d half wave %d: %d LDS cycles for its window reads, %d with the halves 32 lanes apart", S, sh, hw, now[hw], was[hw]);
+        }
+        std::printf("split window reads S %d off %d sh %d%s: ds_read_b128 cycles per half wave, halves 32 lanes apart %d / %d / %d / %d, partner l ^ 8 %d / %d / %d / %d\n",
+                    S, off, sh, sh == off % 4 ? " (the plan's)" : "", was[0], was[1], was[2], was[3], now[0], now[1], now[2], now[3]);
+    }
+}
+
+// ---- frame-maximum slots of the split kernel with the extra column in M's quad: one extra column x = S - 1, x % 4 == 0 (the launcher's test)
+static void replay_slot_map() {
+    int cases = 0;
+    for (int S = 64 * kSplitFullWaves + 1; S < kSplitStates; S += 4) {
+        const int x = S - 1;
+        CHECK(x % 4 == 0, "x %d", x);
+        bool x_reached = false;
+        for (int wv = 0; wv < kSplitFullWaves + kSplitHalfWaves; ++wv) {
+            bool quad_in_m[16] = {};
+            for (int lane = 0; lane < 64; ++lane) {
+                const bool half = wv >= kSplitFullWaves;
+                const int j = half ? 64 * kSplitFullWaves + 32 * (wv - kSplitFullWaves) + split_half_target(lane) : 64 * wv + lane;
+                const int slot = split_fm_slot(lane, j == x);
+                CHECK(slot >= 0 && slot < 16, "slot %d", slot);
+                // the quad of this lane holds x after the quad maximum iff one of its lanes is x's
+                bool quad_has_x = false;
+                for (int m = 0; m < 4; ++m) {
+                    const int lm = (lane & ~3) | m;
+                    const int jm = half ? 64 * kSplitFullWaves + 32 * (wv - kSplitFullWaves) + split_half_target(lm) : 64 * wv + lm;
+                    quad_has_x |= jm == x;
+                    if (quad_has_x && jm != x) CHECK(jm >= S, "S %d: state %d shares a quad with x and is live", S, jm);
+                }
+                if (slot < kSplitXSlot) {
+                    CHECK(!quad_has_x, "S %d wave %d lane %d: a quad that holds x adds into M slot %d", S, wv, lane, slot);
+                    quad_in_m[lane >> 2] = true;
+                }
+                if (slot == kSplitXSlot) {
+                    CHECK(j == x, "S %d wave %d lane %d (state %d) adds into the extra column's slot", S, wv, lane, j);
+                    x_reached = true;
+                }
+            }
+            for (int q = 0; q < 16; ++q) {
+                bool has_x = false;
+                for (int m = 0; m < 4; ++m) {
+                    const int lm = 4 * q + m;
+                    has_x |= (wv >= kSplitFullWaves ? 64 * kSplitFullWaves + 32 * (wv - kSplitFullWaves) + split_half_target(lm) : 64 * wv + lm) == x;
+                }
+                CHECK(quad_in_m[q] != has_x, "S %d wave %d quad %d: %s", S, wv, q, has_x ? "holds x and reaches M" : "reaches none of slots 0 .. 2");
+            }
+        }
+        CHECK(x_reached, "S %d: no lane adds x into slot %d", S, kSplitXSlot);
+        ++cases;
+    }
+    std::printf("split slot map: every quad without x reaches one of slots 0 .. 2, x reaches slot %d alone: ok (%d state counts)\n", kSplitXSlot, cases);
 }
 
 template <int W, int NWT>
@@ -143,6 +270,10 @@ int main() {
     replay_width<96>();
     replay_width<128>();
     replay<FloorSplitLds, 32>("FloorSplitLds (split kernel)", kSplitStates / 64, true);
+    replay_lane_map();
+    replay_slot_map();
+    replay_read_cycles(361, 15);                                          // the reference's 361-state grid: rows 344 .. 359 are clamped to S - W
+    replay_read_cycles(321, 13);
     // two workgroups per CU up to B = 512 at the production shape
     static_assert(2 * FloorSplitLds::bytes() <= kLdsBytes && 2 * FloorLds<32, 6>::bytes() <= kLdsBytes, "two workgroups share a CU's LDS");
     if (failures) { std::printf("%d check(s) failed\n", failures); return 1; }
