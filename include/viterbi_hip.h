@@ -346,6 +346,36 @@ int vit_decode_f64(const vit_plan *plan, const void *logE, int emis_dtype, int64
                    void *workspace, size_t workspace_bytes, int32_t *states, double *loglik /* [B] or NULL */, vit_stream stream);
 
 /*
+ * The same over recordings of different lengths without padding: vit_decode_packed()'s buffers (logE [offsets[B], S], states
+ * [offsets[B]], recording b in rows offsets[b] .. offsets[b+1] - 1; offsets on the HOST) with vit_decode_f64()'s recursion.  States
+ * and log-likelihoods are bit for bit those of vit_decode_f64() of each recording alone.  The reference decodes recording by
+ * recording, each with its own length (tonet/for_paper.py:2304-2309).
+ * Plans served: exactly those of vit_decode_f64() (one predicate behind both); every other plan gets size 0 and VIT_EUNSUPPORTED
+ * before anything is enqueued, and a size > 0 means the decode launches.
+ * Argument rules, status codes and their order are vit_decode_packed()'s: null plan / offsets / workspace, B out of range,
+ * a misaligned workspace or a bad dtype VIT_EINVAL (VIT_ENOTUPLOADED in its place); then VIT_EUNSUPPORTED; then bad offsets
+ * (offsets[0] != 0, a recording with fewer than 1 or more than 2^30 frames) VIT_EINVAL; B = 0 VIT_OK; null logE / states VIT_EINVAL;
+ * a workspace below vit_workspace_bytes_f64_packed(plan, B, offsets[B]) VIT_EWORKSPACE.
+ * Forward: one workgroup per slot, min(B, resident workgroups of the packed kernel x compute units, max(1, total frames /
+ * longest recording)) slots, each walking its recordings back to back; recordings go longest first into the lightest slot.  The
+ * occupancy answer is asked of the device once per plan and emission type.
+ * Back-trace: one wave per (recording, chunk).  With N = total frames and tmax = the longest recording,
+ *   cf = max(ceil(N / (8 x compute units)), 8 * 128, ceil(tmax / 32))
+ * and recording b gets clamp(T_b / cf, 1, 32) chunks (the division rounds down: no chunk is shorter than cf frames); a second pass
+ * per recording verifies every chunk's entry state and repairs what was guessed wrong.  The chunk rule is tuning: the states do not
+ * depend on it.
+ * The slot and chunk tables go through the plan's pinned staging buffer with one upload: like vit_decode_packed() the call is not
+ * thread-safe against other packed decodes on the same plan, may wait for the previous packed call's upload, does no other host
+ * synchronisation and no device allocation.  It drops the workspace's vit_forward() record as vit_decode_f64() does.
+ * Workspace: offsets[B] rows of (S + 3) / 2 * 2 doubles + per-recording terminal states + chunk entries + the tables.
+ * Honoured options: "bt_warm"; "bt_chunks" and every other option are ignored.
+ */
+size_t vit_workspace_bytes_f64_packed(const vit_plan *plan, int64_t B, int64_t total_frames);
+int vit_decode_f64_packed(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B, const int64_t *offsets /* HOST, [B+1] */,
+                          void *workspace, size_t workspace_bytes, int32_t *states /* [offsets[B]] */,
+                          double *loglik /* [B] or NULL */, vit_stream stream);
+
+/*
  * Fused logits -> path decode: what callers of the reference run is Viterbi.__call__ (tonet/for_paper.py:1817-1831) -- pitch
  * logits -> observation log-probabilities -> Viterbi decode.  vit_obs_*() + vit_decode() do that with a [B,T,S] float32
  * emission tensor written to and read back from device memory (2 x 4 S bytes per frame, 44 GB for [1024, 30000, 361]); here the

@@ -9,5 +9,5 @@ from .decoder import ViterbiDecoder, decode, get_decoder  # noqa: F401
 from .emissions import activation_log_emissions  # noqa: F401
 from .reference_api import (  # noqa: F401
     ImmViterbi, RecordingAccumulator, ScaledSoftMaxViterbi, SoftMaxViterbi, Viterbi, tf_viterbi_librosa_fn, viterbi_librosa_c_fn,
-    viterbi_librosa_f64_fn, viterbi_librosa_fn, viterbi_numba_core, viterbi_numba_fn, viterbi_tf_fn,
+    viterbi_librosa_f64_fn, viterbi_librosa_f64_recordings_fn, viterbi_librosa_fn, viterbi_numba_core, viterbi_numba_fn, viterbi_tf_fn,
 )

@@ -96,6 +96,8 @@ struct vit_plan {
     // workgroups per CU of the packed workgroup-form kernel [0] and of its packed-checkpoint variant [1] (vit_decode_packed_bounded, pass
     // 1's slots), by emission type (fp32 / fp16); 0 = not asked yet (resident_per_cu)
     mutable int resident[2][2] = {{0, 0}, {0, 0}};
+    // the same of the packed float64 forward kernel (vit_decode_f64_packed), by emission type
+    mutable int resident_f64[2] = {0, 0};
     ~vit_plan() {
         if (pk_event) (void)hipEventDestroy(pk_event);
         if (pk_host) (void)hipHostFree(pk_host);
@@ -649,6 +651,22 @@ F64Layout f64_layout(const vit_plan* p, int64_t B, int64_t T) {
     w.bytes = w.off_entry + align256((size_t)B * vit::kBtMaxChunks * sizeof(int32_t));
     return w;
 }
+// what the float64 kernels read of the plan (vit_decode_f64, vit_decode_f64_packed)
+void f64_args_from_plan(const vit_plan* plan, vit::F64Args& a) {
+    a.image = plan->dev_image;
+    a.S = plan->S;
+    a.SP = plan->L.SP;
+    a.SD64 = vit::f64_hist_stride(plan->S);
+    a.W = plan->bp.W;
+    a.n_extras = plan->bp.n_extras;
+    for (int k = 0; k < vit::kMaxExtras; ++k) a.extras[k] = plan->bp.extras[k];
+    a.off_logpi = plan->L.off_logpi;
+    a.off_lo = plan->L.off_lo;
+    a.off_tabA = plan->L.off_tabA;
+    a.off_extraA = plan->L.off_extraA;
+    a.off_rowc = plan->L.off_rowc;
+    a.off_tabX = plan->L.off_tabX;
+}
 
 }  // namespace
 
@@ -671,7 +689,7 @@ int vit_decode_f64(const vit_plan* plan, const void* logE, int emis_dtype, int64
     stamp_erase(plan, workspace);      // whatever vit_forward left in this workspace is gone once the kernels below start: vit_backtrace must not find it
     uint8_t* ws = static_cast<uint8_t*>(workspace);
     vit::F64Args a{};
-    a.image = plan->dev_image;
+    f64_args_from_plan(plan, a);
     a.logE = logE;
     a.lengths = lengths;
     a.hist = reinterpret_cast<double*>(ws + w.off_hist);
@@ -681,18 +699,6 @@ int vit_decode_f64(const vit_plan* plan, const void* logE, int emis_dtype, int64
     a.entry = reinterpret_cast<int32_t*>(ws + w.off_entry);
     a.B = B;
     a.T = (int)T;
-    a.S = plan->S;
-    a.SP = plan->L.SP;
-    a.SD64 = vit::f64_hist_stride(plan->S);
-    a.W = plan->bp.W;
-    a.n_extras = plan->bp.n_extras;
-    for (int k = 0; k < vit::kMaxExtras; ++k) a.extras[k] = plan->bp.extras[k];
-    a.off_logpi = plan->L.off_logpi;
-    a.off_lo = plan->L.off_lo;
-    a.off_tabA = plan->L.off_tabA;
-    a.off_extraA = plan->L.off_extraA;
-    a.off_rowc = plan->L.off_rowc;
-    a.off_tabX = plan->L.off_tabX;
     const Tuning& tn = plan->tune;
     a.chunks = vit::backtrace_chunks(B, (int)T);
     a.warm = vit::kBtWarm;
@@ -1168,6 +1174,149 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     b.bt_form = 4;
     if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
     return hip_status(vit::launch_backtrace_lane(b, st));
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Packed float64-accumulating decode: vit_decode_f64's kernels (f64.hip, their PK case) over vit_decode_packed's buffers.  A WORKGROUP
+// per forward slot walks its songs back to back; the back-trace runs one wave per (song, chunk) over per-song chunk lists, the scheme
+// of the step plans' lazy back-trace above.  The plans served are vit_decode_f64's (f64_applies).
+namespace {
+
+// Tables first, the history behind them: the size less the N history rows does not depend on N.
+struct F64PkLayout {
+    int64_t n_slots, max_waves;
+    size_t off_last, off_entry, off_offsets, off_slot_begin, off_slot_songs, off_wave_song, off_chunk_base, off_hist, bytes;
+    size_t tables_bytes;      // offsets .. chunk_base: one contiguous upload
+};
+// back-trace waves wanted at once: about eight per CU (tuning, as for the step plans of vit_decode_packed)
+inline int64_t f64_pk_resident_waves(const vit_plan* p) { return 8 * (int64_t)p->n_cus; }
+// n_slots is an upper bound here (it sizes slot_begin): the decode lowers it
+F64PkLayout f64_pk_layout(const vit_plan* p, int64_t B, int64_t N) {
+    F64PkLayout k;
+    k.n_slots = pk_slots(p, B);
+    k.max_waves = B + f64_pk_resident_waves(p);      // sum of max(1, T_b / cf) <= B + N / cf, cf >= N / resident waves
+    k.off_last = 0;
+    k.off_entry = k.off_last + align256((size_t)B * sizeof(int32_t));
+    k.off_offsets = k.off_entry + align256((size_t)k.max_waves * sizeof(int32_t));
+    k.off_slot_begin = k.off_offsets + align256((size_t)(B + 1) * sizeof(int64_t));
+    k.off_slot_songs = k.off_slot_begin + align256((size_t)(k.n_slots + 1) * sizeof(int32_t));
+    k.off_wave_song = k.off_slot_songs + align256((size_t)B * sizeof(int32_t));
+    k.off_chunk_base = k.off_wave_song + align256((size_t)k.max_waves * sizeof(int32_t));
+    k.off_hist = k.off_chunk_base + align256((size_t)(B + 1) * sizeof(int32_t));
+    k.tables_bytes = k.off_hist - k.off_offsets;
+    k.bytes = k.off_hist + (size_t)N * (size_t)vit::f64_hist_stride(p->S) * sizeof(double);
+    return k;
+}
+// workgroups one CU holds of the packed float64 forward kernel: asked of the device once per emission type (as resident_per_cu)
+int f64_resident_per_cu(const vit_plan* plan, const vit::F64Args& a, bool f16, int* per_cu) {
+    int& cached = plan->resident_f64[f16 ? 1 : 0];
+    {
+        std::lock_guard<std::mutex> g(plan->mu);
+        *per_cu = cached;
+    }
+    if (*per_cu >= 1) return VIT_OK;
+    const hipError_t eq = vit::f64_forward_packed_resident(a, f16, per_cu);
+    if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: f64_applies asked the same)
+    VIT_TRY(eq);
+    if (*per_cu < 1) return VIT_EUNSUPPORTED;
+    std::lock_guard<std::mutex> g(plan->mu);
+    cached = *per_cu;
+    return VIT_OK;
+}
+
+}  // namespace
+
+size_t vit_workspace_bytes_f64_packed(const vit_plan* plan, int64_t B, int64_t total_frames) {
+    if (!plan || B < 0 || B > (int64_t)1 << 30 || total_frames < 0 || !f64_applies(plan)) return 0;
+    return f64_pk_layout(plan, B, total_frames).bytes;
+}
+
+int vit_decode_f64_packed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
+                          size_t workspace_bytes, int32_t* states, double* loglik, vit_stream stream) {
+    int rc = check_packed(plan, B, offsets, workspace, emis_dtype);
+    if (rc != VIT_OK) return rc;
+    if (!f64_applies(plan)) return VIT_EUNSUPPORTED;
+    int64_t tmax;
+    if (!offsets_ok(offsets, B, &tmax)) return VIT_EINVAL;
+    const int64_t N = offsets[B];
+    if (B == 0) return VIT_OK;
+    if (!logE || !states) return VIT_EINVAL;
+    F64PkLayout k = f64_pk_layout(plan, B, N);
+    if (workspace_bytes < k.bytes) return VIT_EWORKSPACE;
+    const bool f16 = emis_dtype == VIT_F16;
+    vit::F64Args a{};
+    f64_args_from_plan(plan, a);
+    {
+        // forward slots: min(B, workgroups resident at once, max(1, N / tmax)) -- a slot's load should not fall below the longest song
+        int per_cu;
+        rc = f64_resident_per_cu(plan, a, f16, &per_cu);
+        if (rc != VIT_OK) return rc;
+        k.n_slots = std::min<int64_t>(k.n_slots, (int64_t)per_cu * plan->n_cus);
+        k.n_slots = std::min<int64_t>(k.n_slots, std::max<int64_t>(1, N / tmax));
+    }
+    stamp_erase(plan, workspace);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+
+    // ---- host tables in the plan's pinned staging buffer (the previous call's upload must have read it)
+    rc = pk_stage(plan, k.tables_bytes);
+    if (rc != VIT_OK) return rc;
+    uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
+    int32_t* h_wave_song = reinterpret_cast<int32_t*>(hb + (k.off_wave_song - k.off_offsets));
+    int32_t* h_chunk_base = reinterpret_cast<int32_t*>(hb + (k.off_chunk_base - k.off_offsets));
+    std::memcpy(hb, offsets, (size_t)(B + 1) * sizeof(int64_t));
+    try {
+        pk_fill_slots(offsets, B, k.n_slots, reinterpret_cast<int32_t*>(hb + (k.off_slot_begin - k.off_offsets)),
+                      reinterpret_cast<int32_t*>(hb + (k.off_slot_songs - k.off_offsets)));      // greedy bins by frames
+    } catch (const std::bad_alloc&) {
+        return VIT_ENOMEM;
+    }
+    int64_t max_chunks = 1;
+    {
+        // back-trace waves, one per (song, chunk): cf = max(ceil(N / resident waves), 8 * kBtWarm, ceil(tmax / kBtMaxChunks)) frames per
+        // chunk, song b gets clamp(T_b / cf, 1, kBtMaxChunks) of them (rounded down: no chunk shorter than cf) -- the step plans' rule
+        // of vit_decode_packed
+        const int64_t resident = f64_pk_resident_waves(plan), cmax = vit::kBtMaxChunks;
+        int64_t cf = (N + resident - 1) / resident;
+        cf = std::max<int64_t>(cf, 8 * vit::kBtWarm);
+        cf = std::max<int64_t>(cf, (tmax + cmax - 1) / cmax);
+        int64_t w = 0;
+        for (int64_t b = 0; b < B; ++b) {
+            const int64_t tb = offsets[b + 1] - offsets[b];
+            int64_t c = tb / cf;
+            c = c < 1 ? 1 : (c > cmax ? cmax : c);
+            if (w + c > k.max_waves) return VIT_EINVAL;      // (cannot happen: sum of max(1, T_b / cf) <= B + N / cf <= B + resident)
+            h_chunk_base[b] = (int32_t)w;
+            for (int64_t q = 0; q < c; ++q) h_wave_song[w + q] = (int32_t)b;
+            w += c;
+            max_chunks = c > max_chunks ? c : max_chunks;
+        }
+        h_chunk_base[B] = (int32_t)w;
+    }
+    const int n_waves = h_chunk_base[B];
+    rc = pk_upload(plan, ws + k.off_offsets, k.tables_bytes, st);
+    if (rc != VIT_OK) return rc;
+
+    a.logE = logE;
+    a.lengths = nullptr;
+    a.hist = reinterpret_cast<double*>(ws + k.off_hist);
+    a.last_state = reinterpret_cast<int32_t*>(ws + k.off_last);
+    a.loglik = loglik;
+    a.states = states;
+    a.entry = reinterpret_cast<int32_t*>(ws + k.off_entry);
+    a.B = B;
+    a.T = 1;                      // (unused by the packed kernels: a song's rows come from the offsets)
+    a.offsets = reinterpret_cast<const int64_t*>(ws + k.off_offsets);
+    a.n_slots = (int)k.n_slots;
+    a.slot_begin = reinterpret_cast<const int32_t*>(ws + k.off_slot_begin);
+    a.slot_songs = reinterpret_cast<const int32_t*>(ws + k.off_slot_songs);
+    a.wave_song = reinterpret_cast<const int32_t*>(ws + k.off_wave_song);
+    a.chunk_base = reinterpret_cast<const int32_t*>(ws + k.off_chunk_base);
+    a.n_waves = n_waves;
+    a.chunks = (int)max_chunks;
+    a.warm = plan->tune.bt_warm >= 0 ? plan->tune.bt_warm : vit::kBtWarm;
+    VIT_TRY(vit::launch_f64_forward_packed(a, f16, st));
+    return hip_status(vit::launch_f64_backtrace_packed(a, st));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

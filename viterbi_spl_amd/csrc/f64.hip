@@ -14,6 +14,8 @@
 // M_t in column S).
 // Back-trace (f64_backtrace_kernel): lazy_backtrace_kernel's banded case in double under the chunk scheme of backtrace_common.hpp
 // (a speculative pass per (song, chunk), a verify / repair pass per song).
+// Both kernels have a packed case (PK: vit_decode_f64_packed), described at each: a workgroup per forward slot that walks its songs
+// back to back, back-trace waves over per-song chunk lists, rows at offsets[b] of the packed buffers.
 #include "backtrace_common.hpp"
 
 namespace vit {
@@ -96,7 +98,16 @@ struct F64Lds {
 
 constexpr int kF64Prefetch = 4;    // emission rows in flight (frames ahead)
 
-template <int W, int NWT, typename ET>
+// PK: packed batch (vit_decode_f64_packed).  One workgroup per forward slot: it walks the songs slot_songs[slot_begin[sl] ..
+// slot_begin[sl + 1]) back to back (the scheme of wg_cursor.inc's take_song()); the emission and history rows of song b start at row
+// offsets[b] of the packed buffers (64-bit row offsets).  The per-lane plan constants are loaded once; frame 0, the emission
+// prefetch (clamped to the song's own last row) and the terminal argmax are per song.  Between two songs stands one barrier of its
+// own, behind the terminal read: wave 0 reads d_{Tb-1} out of buffer (Tb - 1) & 1 after the song's last barrier, and without it
+// the other waves would already publish the next song's frame 0 into buffer 0 and its partial maxima into pm[0] -- the buffer
+// being read when Tb is odd (a one-frame song included).  Behind that barrier nothing of the finished song is read any more (the
+// frame loop's reads all sit before its last barrier), so one barrier is enough for every parity.  PK = false compiles to the
+// code it was before the parameter existed.
+template <int W, int NWT, typename ET, bool PK = false>
 __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) {
     using L = F64Lds<W, NWT>;
     constexpr int NP = L::NP, DC = L::DC, BUF = L::BUF, WR = L::WR, PF = kF64Prefetch;
@@ -111,10 +122,27 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int song = blockIdx.x;
-    const int Tb = song_length(a.lengths, song, T);
-    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (size_t)song * T * S;
-    double* __restrict__ hist = a.hist + (size_t)song * T * SD;
+    int song = blockIdx.x;
+    int Tb = PK ? 1 : song_length(a.lengths, song, T);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PK ? (size_t)0 : (size_t)song * T * S);
+    double* __restrict__ hist = a.hist + (PK ? (size_t)0 : (size_t)song * T * SD);
+    // (PK) position in slot_songs and the end of the slot's list; the song at si: its length, emission rows and history rows.
+    // Wave-uniform: scalar loads.
+    [[maybe_unused]] int si = 0, si_end = 1;
+    [[maybe_unused]] auto take_song = [&]() {
+        song = a.slot_songs[si];
+        const long long r0 = a.offsets[song];
+        Tb = (int)(a.offsets[song + 1] - r0);
+        E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
+        hist = a.hist + (size_t)r0 * SD;
+    };
+    if constexpr (PK) {
+        if ((int)blockIdx.x >= a.n_slots) return;
+        si = a.slot_begin[blockIdx.x];
+        si_end = a.slot_begin[blockIdx.x + 1];
+        if (si >= si_end) return;                         // an empty slot (the host makes none)
+        take_song();
+    }
 
     // ---------------- per-lane constants.  Idle lanes (j >= S) publish -inf.
     const int j = tid;
@@ -158,18 +186,6 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
         const double part = wave_scan_max_f64(is_x ? -INFINITY : dn);
         if (lane == 63) pm[WB * 16 + wv] = part;
     };
-
-    // ---------------- frame 0: the reference forms log_pi + E_0 in float32 and stores it into the float64 T1
-    {
-        const float d0f = tvalid ? reinterpret_cast<const float*>(a.image + a.off_logpi)[jc] + load_e<ET>(E + jc) : -INFINITY;
-        const double d0 = (double)d0f;
-        if (tvalid) hist[j] = d0;
-        produce(d0, 0);
-    }
-    float er[PF];
-#pragma unroll
-    for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S + jc);
-    __syncthreads();
 
     // frame t = 1 + PF n + u reads buffer u & 1 and writes the other one; one barrier per frame
     auto frame = [&](const int t, float& e_slot, const int u) {
@@ -222,23 +238,50 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
         e_slot = load_e<ET>(E + (size_t)tn * S + jc);
         __syncthreads();
     };
-    int t = 1;
-    for (; t + PF - 1 < Tb; t += PF) {
-#pragma unroll
-        for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
-    }
-#pragma unroll
-    for (int k = 0; k < PF - 1; ++k)
-        if (t + k < Tb) frame(t + k, er[k], k);
 
-    // ---------------- the terminal state: lowest-index argmax of d_{Tb-1}, and its value
-    if (wv == 0) {
-        const int fb = (Tb - 1) & 1;                      // buffer holding d_{Tb-1}
-        double best;
-        const int s = row_argmax_f64<NWT>(dls + fb * BUF, S, lane, &best);
-        if (lane == 0) {
-            a.last_state[song] = s;
-            if (a.loglik) a.loglik[song] = best;
+    // one song per pass (PK: the slot's songs one after the other)
+    for (;;) {
+        // ---------------- frame 0: the reference forms log_pi + E_0 in float32 and stores it into the float64 T1
+        {
+            const float d0f = tvalid ? reinterpret_cast<const float*>(a.image + a.off_logpi)[jc] + load_e<ET>(E + jc) : -INFINITY;
+            const double d0 = (double)d0f;
+            if (tvalid) hist[j] = d0;
+            produce(d0, 0);
+        }
+        float er[PF];
+#pragma unroll
+        for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S + jc);
+        __syncthreads();
+
+        int t = 1;
+        for (; t + PF - 1 < Tb; t += PF) {
+#pragma unroll
+            for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
+        }
+#pragma unroll
+        for (int k = 0; k < PF - 1; ++k)
+            if (t + k < Tb) frame(t + k, er[k], k);
+
+        // ---------------- the terminal state: lowest-index argmax of d_{Tb-1}, and its value
+        if (wv == 0) {
+            const int fb = (Tb - 1) & 1;                  // buffer holding d_{Tb-1}
+            double best;
+            int ln = lane;
+            // (PK: left alone the compiler hoists the argmax's NWT row masks out of the song loop and keeps them in scalar registers
+            // through the frames: twelve waves at W = 128 then spill)
+            if constexpr (PK) asm volatile("" : "+v"(ln));
+            const int s = row_argmax_f64<NWT>(dls + fb * BUF, S, ln, &best);
+            if (lane == 0) {
+                a.last_state[song] = s;
+                if (a.loglik) a.loglik[song] = best;
+            }
+        }
+        if constexpr (!PK) {
+            break;
+        } else {
+            if (++si >= si_end) break;
+            take_song();
+            __syncthreads();                              // the hand-over: the terminal read above before the next song's frame 0
         }
     }
 }
@@ -253,10 +296,14 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
 //     plan's per-target candidate row (tabX[j]: window, extra columns, row constant), read from the image (L2-resident);
 //   * fl64(M_t + c_j) bounds every row-constant candidate: below the candidates' maximum, the lowest matching source wins;
 //   * otherwise all S candidates are evaluated and the lowest index attaining the maximum wins (an all -inf frame: state 0).
+// PK: packed batch (vit_decode_f64_packed; lazy_backtrace_kernel's PK case).  MODE 0 runs one wave per entry of wave_song; song b owns
+// the waves and the chunk entries chunk_base[b] .. chunk_base[b + 1] - 1, so its chunk count grows with its length; MODE 1 one wave
+// per song over that song's own chunk count.  Its history rows and states sit at row offsets[b] of the packed buffers and there are
+// no frames past its end to fill.  PK = false compiles to the code it was before the parameter existed.
 constexpr int kF64BtWaves = 4;
 constexpr int kF64BtSlots = 3;     // candidate slots per lane: W + kMaxExtras <= 192
 
-template <int NWT, int MODE>
+template <int NWT, int MODE, bool PK = false>
 __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args a) {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int EPL = NWT, NP = NWT * 64, KC = kF64BtSlots;
@@ -265,16 +312,21 @@ __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     double* rowL = reinterpret_cast<double*>(smem) + (size_t)wv * NP;   // this wave's d row
-    const int C = a.chunks;
+    // which song and chunk this wave serves, the song's length and its rows (PK: from the tables)
+    const int C0 = PK ? 1 : a.chunks;
     const long long gw = (long long)blockIdx.x * kF64BtWaves + wv;
-    const long long song_l = MODE == 0 ? gw / C : gw;
+    if (PK && MODE == 0 && gw >= a.n_waves) return;
+    const long long song_l = PK ? (MODE == 0 ? (long long)a.wave_song[gw] : gw) : (MODE == 0 ? gw / C0 : gw);
     if (song_l >= a.B) return;
     const int song = (int)song_l;
-    const int chunk = MODE == 0 ? (int)(gw % C) : 0;
-    const int Tb = song_length(a.lengths, song, T);
-    int32_t* states = a.states + (size_t)song * T;       // (no __restrict__: MODE 1 reads what chase() stored)
-    int32_t* entry = a.entry + (size_t)song * C;
-    const double* __restrict__ hist = a.hist + (size_t)song * T * SD;
+    const int cbase = PK ? a.chunk_base[song] : 0;
+    const int C = PK ? a.chunk_base[song + 1] - cbase : C0;
+    const int chunk = MODE == 0 ? (PK ? (int)(gw - cbase) : (int)(gw % C)) : 0;
+    const long long row0 = PK ? (long long)a.offsets[song] : 0;   // (PK) first history row / state of the song
+    const int Tb = PK ? (int)(a.offsets[song + 1] - row0) : song_length(a.lengths, song, T);
+    int32_t* states = a.states + (PK ? (size_t)row0 : (size_t)song * T);       // (no __restrict__: MODE 1 reads what chase() stored)
+    int32_t* entry = a.entry + (PK ? (size_t)cbase : (size_t)song * C);
+    const double* __restrict__ hist = a.hist + (PK ? (size_t)row0 * SD : (size_t)song * T * SD);
     const float* __restrict__ tabX = reinterpret_cast<const float*>(a.image + a.off_tabX);
     const int32_t* __restrict__ loT = reinterpret_cast<const int32_t*>(a.image + a.off_lo);
 
@@ -401,7 +453,8 @@ __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args
         int lo_c, hi_c;
         bt_chunk_bounds(Lf, chunk, C, lo_c, hi_c);
         if (chunk == C - 1) {
-            for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
+            if constexpr (!PK)
+                for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
             if (lane == 0) states[Tb - 1] = last;
         }
         int top = hi_c - 1 + a.warm;
@@ -473,6 +526,29 @@ hipError_t launch_f64_forward(const F64Args& a, bool f16, hipStream_t st) {
     });
 }
 
+// the packed forward instantiation of the plan: launched over a.n_slots workgroups, or (per_cu set) asked how many of its workgroups
+// one compute unit holds at once (the occupancy query at its LDS size)
+static hipError_t f64_forward_packed(const F64Args& a, bool f16, hipStream_t st, int* per_cu) {
+    if (a.W > a.S) return hipErrorInvalidValue;
+    return f64_dispatch_width(a.W, [&](auto w) {
+        return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
+            constexpr int W = decltype(w)::value, NWT = decltype(n)::value;
+            constexpr size_t lds = F64Lds<W, NWT>::bytes();
+            auto go = [&](auto kern) -> hipError_t {
+                if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, NWT * 64, lds);
+                hipLaunchKernelGGL(kern, dim3((unsigned)a.n_slots), dim3(NWT * 64), lds, st, a);
+                return hipGetLastError();
+            };
+            return f16 ? go(f64_floor_forward_kernel<W, NWT, __half, true>) : go(f64_floor_forward_kernel<W, NWT, float, true>);
+        });
+    });
+}
+hipError_t launch_f64_forward_packed(const F64Args& a, bool f16, hipStream_t st) {
+    if (a.B < 1 || !a.offsets || !a.slot_begin || !a.slot_songs || a.n_slots < 1) return hipErrorInvalidValue;
+    return f64_forward_packed(a, f16, st, nullptr);
+}
+hipError_t f64_forward_packed_resident(const F64Args& a, bool f16, int* per_cu) { return f64_forward_packed(a, f16, nullptr, per_cu); }
+
 hipError_t launch_f64_backtrace(const F64Args& a, hipStream_t st) {
     if (a.B < 1 || a.chunks < 1 || a.chunks > kBtMaxChunks || a.W + kMaxExtras > 64 * kF64BtSlots) return hipErrorInvalidValue;
     return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
@@ -483,6 +559,21 @@ hipError_t launch_f64_backtrace(const F64Args& a, hipStream_t st) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || a.chunks <= 1) return e;
         hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 1>), dim3((unsigned)((a.B + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_f64_backtrace_packed(const F64Args& a, hipStream_t st) {
+    if (a.B < 1 || !a.offsets || !a.wave_song || !a.chunk_base || a.n_waves < 1 || a.chunks < 1 || a.chunks > kBtMaxChunks ||
+        a.W + kMaxExtras > 64 * kF64BtSlots)
+        return hipErrorInvalidValue;
+    return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
+        constexpr int NWT = decltype(n)::value;
+        constexpr size_t lds = sizeof(double) * kF64BtWaves * NWT * 64;
+        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 0, true>), dim3((unsigned)((a.n_waves + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess || a.chunks <= 1) return e;      // (a.chunks: the largest chunk count of any song)
+        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 1, true>), dim3((unsigned)((a.B + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
         return hipGetLastError();
     });
 }

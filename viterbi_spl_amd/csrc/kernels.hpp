@@ -214,9 +214,23 @@ struct F64Args {
     int extras[kMaxExtras];
     int chunks, warm;       // time-parallel back-trace: chunks per song (<= kBtMaxChunks), warm-up frames
     size_t off_logpi, off_lo, off_tabA, off_extraA, off_rowc, off_tabX;
+    // packed batch (vit_decode_f64_packed; behind the fields above, whose places the plain kernels keep): logE, hist and states are
+    // [sum T_b, ..], the rows of song b start at row offsets[b]; entry is [n_waves]
+    const int64_t* offsets;     // [B+1] frame offsets
+    int n_slots;                // forward slots: one workgroup each
+    const int32_t* slot_begin;  // [n_slots+1]
+    const int32_t* slot_songs;  // [B] song ids grouped by slot
+    const int32_t* wave_song;   // [n_waves] song of each back-trace wave (speculative pass)
+    const int32_t* chunk_base;  // [B+1] first wave / chunk entry of each song; chunks = the largest chunk count of any song
+    int n_waves;
 };
 hipError_t launch_f64_forward(const F64Args& a, bool f16, hipStream_t st);
 hipError_t launch_f64_backtrace(const F64Args& a, hipStream_t st);
+// the same over a packed batch, and the workgroups of the packed forward instantiation one compute unit holds at once (as
+// banded_variant_resident)
+hipError_t launch_f64_forward_packed(const F64Args& a, bool f16, hipStream_t st);
+hipError_t launch_f64_backtrace_packed(const F64Args& a, hipStream_t st);
+hipError_t f64_forward_packed_resident(const F64Args& a, bool f16, int* per_cu);
 hipError_t launch_dense(const FwdArgs& a, int songs_per_group, bool f16, hipStream_t st);
 hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st);

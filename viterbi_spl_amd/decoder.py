@@ -352,6 +352,81 @@ class ViterbiDecoder:
             states = states.to(out_dtype)
         return (states[0], loglik[0]) if single else (states, loglik)
 
+    # ------------------------------------------------------------------ the same over a packed (ragged) batch
+    def workspace_bytes_f64_packed(self, B: int, total_frames: int) -> int:
+        """Workspace bytes of ``decode_f64_packed`` for B recordings of ``total_frames`` frames together; raises ViterbiHipError for
+        a plan it does not serve (the plans of ``decode_f64``)."""
+        need = int(_lib.load().vit_workspace_bytes_f64_packed(self._plan, int(B), int(total_frames)))
+        if need == 0:
+            raise _lib.ViterbiHipError("the packed float64 decode needs a banded plan whose floor form is proven, without dense rows "
+                                       "(unstructured matrices, the Durrieu step matrices and scan-only plans are not served)")
+        return need
+
+    @staticmethod
+    def _greedy_groups(offsets, size_of, budget: int) -> list:
+        """Consecutive groups ``[(b0, b1), ...]`` of the recordings ``offsets`` describes: each takes recordings in order while
+        ``size_of(recordings, frames)`` of the group fits ``budget``.  ValueError (naming the recording) when one alone does not."""
+        off = [int(x) for x in offsets]
+        groups, b0, B = [], 0, len(off) - 1
+        while b0 < B:
+            b1 = b0
+            while b1 < B and size_of(b1 + 1 - b0, off[b1 + 1] - off[b0]) <= budget:
+                b1 += 1
+            if b1 == b0:
+                raise ValueError(f"recording {b0} ({off[b0 + 1] - off[b0]} frames) alone needs {size_of(1, off[b0 + 1] - off[b0])} bytes")
+            groups.append((b0, b1))
+            b0 = b1
+        return groups
+
+    def plan_workspace_f64_packed(self, offsets, max_workspace_bytes: Optional[int] = None) -> dict:
+        """How ``decode_f64_packed`` meets a workspace budget (bytes; None = whatever it takes): there is no checkpointed float64
+        decode, so the recordings are decoded in consecutive groups, each taking recordings in order while its
+        ``workspace_bytes_f64_packed`` fits.  Returns ``{"groups": [(b0, b1), ...], "bytes": the largest group's need}``; raises
+        ViterbiHipError when one recording alone does not fit, or for a plan that is not served."""
+        off = self._host_offsets(offsets)
+        B = off.size - 1
+        if B == 0:
+            return {"groups": [], "bytes": 0}
+        if max_workspace_bytes is None:
+            return {"groups": [(0, B)], "bytes": self.workspace_bytes_f64_packed(B, int(off[-1]))}
+        try:
+            groups = self._greedy_groups(off, self.workspace_bytes_f64_packed, int(max_workspace_bytes))
+        except ValueError as e:
+            raise _lib.ViterbiHipError(f"no packed float64 decode fits a workspace of {max_workspace_bytes} bytes: {e}") from None
+        return {"groups": groups, "bytes": max(self.workspace_bytes_f64_packed(b1 - b0, int(off[b1] - off[b0])) for b0, b1 in groups)}
+
+    def decode_f64_packed(self, emission_logits: torch.Tensor, offsets, out_dtype: torch.dtype = torch.int64,
+                          workspace: Optional[torch.Tensor] = None, max_workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_f64`` of B recordings of different lengths without padding (``vit_decode_f64_packed``): the arguments of
+        ``decode_packed`` -- ``emission_logits [sum T_b, S]``, ``offsets`` a host sequence of B + 1 frame offsets from 0 -- and the
+        recursion of ``decode_f64``.  Returns ``(states [sum T_b], loglik float64 [B])``, bit for bit ``decode_f64`` of each
+        recording alone.  Plans: those of ``decode_f64``; any other raises ``ViterbiHipError`` before anything is enqueued.
+
+        ``max_workspace_bytes``: a budget for the workspace, met by decoding consecutive groups of recordings one after the other
+        in one workspace (``plan_workspace_f64_packed``) -- the same bytes out; ``ViterbiHipError`` before anything is enqueued when
+        one recording alone does not fit.  ``workspace``: an optional uint8 tensor of at least the need + 256 bytes (the caller
+        then keeps it alive until the stream has run the decode: the call does not synchronise)."""
+        lib = _lib.load()
+        dt, off = self._check_packed(emission_logits, offsets)
+        B, N = off.size - 1, int(off[-1])
+        states = torch.empty((N,), dtype=torch.int32, device=self.device)
+        loglik = torch.empty((B,), dtype=torch.float64, device=self.device)
+        if B > 0:
+            mode = self.plan_workspace_f64_packed(off, max_workspace_bytes)
+            ws, ws_ptr, ws_bytes, mine = self._call_workspace(mode["bytes"], workspace)
+            stream = torch.cuda.current_stream(self.device)
+            for b0, b1 in mode["groups"]:                   # (a group: the same entry point on a row slice with rebased offsets)
+                goff = np.ascontiguousarray(off[b0:b1 + 1] - off[b0])
+                with torch.cuda.device(self.device):
+                    rc = lib.vit_decode_f64_packed(self._plan, emission_logits[int(off[b0]):].data_ptr(), dt, b1 - b0, goff.ctypes.data, ws_ptr,
+                                                   ws_bytes, states[int(off[b0]):].data_ptr(), loglik[b0:].data_ptr(), stream.cuda_stream)
+                _lib.check(rc, "vit_decode_f64_packed")
+            if mine:
+                stream.synchronize()
+        if out_dtype != torch.int32:
+            states = states.to(out_dtype)
+        return states, loglik
+
     # ------------------------------------------------------------------ bounded-workspace decode
     def workspace_bytes_checkpointed(self, B: int, T: int, segment_frames: int) -> int:
         """Workspace bytes of ``decode_checkpointed``; raises ViterbiHipError for a plan or a segment length it does not serve."""

@@ -9,6 +9,7 @@ last bit a GPU cannot be trusted to reproduce.
   family A  viterbi_librosa_c_fn / viterbi_numba_fn(*, transition_matrix, prob_init, probs_st)
             dcnet/tf_viterbi_decoding.py:119-207, dcnet/main.py:2417-2468 (+10 copies)
   float64   viterbi_librosa_f64_fn(*, transition_matrix, prob_init, probs_st)    dcnet/tf_viterbi_decoding.py:209-263
+            viterbi_librosa_f64_recordings_fn(*, transition_matrix, prob_init, probs_st_list)   the same, many recordings in one call
   family D  viterbi_librosa_fn(*, log_transition_matrix_T, log_prob_init, log_probs_st)
             imm/tf_viterbi.py:75-109
   AOT core  viterbi_numba_core(B, prob_init, probs)   dcnet/aot_viterbi_core.py:8-54
@@ -87,6 +88,29 @@ def viterbi_librosa_f64_fn(*, transition_matrix, prob_init, probs_st):
     dec = get_decoder(logA_T, log_pi)
     states, _ = dec.decode_f64(torch.from_numpy(logE).to(dec.device), out_dtype=torch.int64)
     return states.cpu().numpy()
+
+
+def viterbi_librosa_f64_recordings_fn(*, transition_matrix, prob_init, probs_st_list):
+    """``viterbi_librosa_f64_fn`` over many recordings of different lengths in ONE packed decode
+    (``ViterbiDecoder.decode_f64_packed``; the reference calls its function once per recording, as at tonet/for_paper.py:2304-2309):
+    ``probs_st_list`` holds one float32 ``[S, T_b]`` array per recording; a list of ``int64[T_b]`` comes back, entry b equal to
+    ``viterbi_librosa_f64_fn`` of recording b alone.  The asserts and the host ``np.log`` step are that function's, per recording."""
+    probs_st_list = list(probs_st_list)
+    if not probs_st_list:
+        return []
+    parts = []
+    for probs_st in probs_st_list:
+        S = _check_probs(transition_matrix, prob_init, probs_st)
+        assert probs_st.shape == (S, probs_st.shape[1])
+        parts.append(np.require(np.log(probs_st.T + np.finfo(probs_st.dtype).tiny), np.float32, ['C']))
+    tinyp = np.finfo(np.float32).tiny
+    logA_T = np.require(np.log(transition_matrix.T + tinyp), np.float32, ['C'])
+    log_pi = np.log(prob_init + tinyp).astype(np.float32)
+    offsets = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
+    dec = get_decoder(logA_T, log_pi)
+    states, _ = dec.decode_f64_packed(torch.from_numpy(np.concatenate(parts, axis=0)).to(dec.device), offsets, out_dtype=torch.int64)
+    states = states.cpu().numpy()
+    return [states[offsets[b]:offsets[b + 1]] for b in range(len(parts))]
 
 
 def viterbi_numba_fn(*, transition_matrix, prob_init, probs_st):
