@@ -197,7 +197,11 @@ class ViterbiDecoder:
         history (``set_option("wave_history", 2)``) the back-trace reads 32 emission values of every odd frame again.  The
         back-trace phase hands the pointer to the library (``vit_backtrace_checked``), which refuses a tensor other than the one
         its forward pass decoded ("invalid argument"); a caller that double-buffers its emissions must keep a batch's buffer
-        untouched until that batch's back-trace has run."""
+        untouched until that batch's back-trace has run.
+
+        A slot must not grow while a batch that uses it is in flight: ``_workspace`` replaces a buffer that is too small, so
+        allocate every slot at the size it will need (``_workspace(B, T, slot, None)`` serves any form) before anything is
+        enqueued, as ``bench.py`` and tests/test_gpu_two_streams.py do."""
         lib = _lib.load()
         logE, _, dt = self._check_emissions(logE)
         B, T, _ = logE.shape
