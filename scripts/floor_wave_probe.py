@@ -1,7 +1,8 @@
 """Per-wave probe of the floor forward kernels (hooks build only: make -C viterbi_spl_amd/csrc TIMING=1).
 For each forward_form given: forward time without a probe, cycles per frame (timing option 16) and, per wave, the SIMD it
-ran on, the mean cycles from the barrier release to "last max3 done" and the mean cycles from its s_waitcnt lgkmcnt(0) to
-the next barrier release (timing option 64), mean over the songs of a [B, 30000, 361] batch.
+ran on, the mean cycles from the barrier release to the return of the frame's first s_waitcnt (the split kernel) and to "last
+max3 done", and the mean cycles from its s_waitcnt lgkmcnt(0) to the next barrier release (timing option 64), mean over the songs
+of a [B, 30000, 361] batch.
 usage: floor_wave_probe.py [B] [forward_form ...]   (default 128, forms 1)"""
 import os
 import sys
@@ -64,5 +65,7 @@ for form in forms:
         if w * 4 + 3 >= 63 or not (q[:, 3] == T - 1).all():
             break
         simd = q[:, 0].astype(np.int64)
-        print(f"  wave {w}: SIMD {np.bincount(simd, minlength=4).tolist()} (songs by SIMD_ID)  barrier -> last max3 {q[:,1].mean():6.1f}"
+        d = sc[:, 48 + w]      # barrier release -> behind the frame's first s_waitcnt (the split kernel only; 0 elsewhere)
+        print(f"  wave {w}: SIMD {np.bincount(simd, minlength=4).tolist()} (songs by SIMD_ID)  barrier -> first data {d.mean():6.1f}"
+              f" (min {d.min():.1f} max {d.max():.1f})  barrier -> last max3 {q[:,1].mean():6.1f}"
               f" (min {q[:,1].min():.1f} max {q[:,1].max():.1f})  lgkmcnt(0) -> barrier release {q[:,2].mean():6.1f} cycles")

@@ -464,20 +464,28 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
         // descriptor each for the whole round.  Frame t + u reaches its rows through the buffer instructions' scalar offset: u history
         // rows on (u * rowH, a constant per unrolled frame), and min(u, Tb - 1 - (t + PF)) emission rows on, i.e. row
         // min(t + u + PF, Tb - 1) as ever (elim: that bound in bytes, at most PF rows; 0 once the round's base row is the last row).
-        // Per frame that is one s_min_u32 where the row bases took two 64-bit multiply-adds, a clamp and two descriptor rebuilds.
+        // Per frame that is one s_min_u32 where the row bases took two 64-bit multiply-adds, a clamp and two descriptor rebuilds -- and
+        // only in the last full round and the tail: the rounds in front of them (interior_bases) cannot reach the bound and go without it.
         const unsigned rowH = 4u * (unsigned)SD, rowE = (unsigned)sizeof(ET) * (unsigned)S;
         float* hb = hist;
         const ET* eb = E;
         unsigned elim = 0;
         auto round_bases = [&](const int t) {
-            const int r = t + PF < Tb ? t + PF : Tb - 1;
+            const int r = split_prefetch_row(t, 0, PF, Tb, false);
             const int ahead = Tb - 1 - r < PF ? Tb - 1 - r : PF;
             hb = hist + (size_t)(t - 1) * SD;
             eb = E + (size_t)r * S;
             elim = (unsigned)ahead * rowE;
         };
-        auto frame = [&](float& e_slot, auto uc) {
+        // An interior round (split_round_interior, plan.hpp): every request t + u + PF, u < PF, lies inside the song, so frame t + u
+        // takes the constant offset u * rowE and the round needs no bound
+        auto interior_bases = [&](const int t) {
+            hb = hist + (size_t)(t - 1) * SD;
+            eb = E + (size_t)split_prefetch_row(t, 0, PF, Tb, true) * S;
+        };
+        auto frame = [&](float& e_slot, auto uc, auto ic) {
             constexpr int u = decltype(uc)::value;
+            constexpr bool INTERIOR = decltype(ic)::value;
             const int RB = u & 1, WB = RB ^ 1;
             const int GR = u % kFmGroups, GW = (u + 1) % kFmGroups, GZ = (u + 2) % kFmGroups;
             const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
@@ -502,11 +510,17 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             [[maybe_unused]] float ds = 0.f;                              // (TRIM) position WL - 1: the last LDS read of the burst
             if constexpr (TRIM) ds = (rp + RB * BUF)[WL - 1];
             __builtin_amdgcn_sched_barrier(0);
+#ifdef VIT_TIMING_HOOKS
+            if constexpr (wprobe && !TRIM) wp_.first_data(fq);
+#endif
             if constexpr (TRIM) {
                 // one wait for M and the first pair of quads: everything but the WL / 4 - 2 quads and the float behind them
                 static_assert(split_reads_behind(WL / 4, 0) == WL / 4 + 1 - 2, "behind the first pair: every other window read of the burst");
                 __builtin_amdgcn_s_waitcnt(split_waitcnt(kNoVmWait, split_reads_behind(WL / 4, 0)));
                 asm volatile("" : "+v"(fq), "+v"(dw[0]), "+v"(dw[1]));
+#ifdef VIT_TIMING_HOOKS
+                if constexpr (wprobe) wp_.first_data(fq);
+#endif
             }
             const float M = XS ? fmaxf(fmaxf(fq.x, fq.y), fq.z) : fmaxf(fmaxf(fq.x, fq.y), fmaxf(fq.z, fq.w));
             if constexpr (XS) xd[0] = fq.w;                               // delta[x] of this frame, bit for bit (split_fm_slot)
@@ -608,7 +622,7 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
 #endif
             // (the stored value and the emission offset are formed in front of the publication: the order the measured builds have)
             const float sv = (HALF && is_fm) ? M : dn;                    // (full waves hold live targets only)
-            const unsigned eso = (unsigned)u * rowE < elim ? (unsigned)u * rowE : elim;
+            const unsigned eso = INTERIOR ? (unsigned)u * rowE : ((unsigned)u * rowE < elim ? (unsigned)u * rowE : elim);
             produce(dn, WB, GW, GZ);
             asm volatile("" ::: "memory");   // the global store / prefetch fill the wait for the LDS write acknowledgement
             // KEEP THIS STORE SINGLE-DWORD: with a register soffset a store wider than 64 bits needs wait states in front of the next write
@@ -628,15 +642,23 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
         // The half waves are the younger wave of each SIMD and lost the arbitration to the full wave in every frame; with static priority 1
         // they publish first and the full waves, which have fewer instructions left per frame than the half waves' lag cost, close the frame.
         // Once per song, in the half-wave roles only (the role is a scalar branch, see below); nothing in the loop.
+        // (per frame it was tried and lost: priority 0 for the half waves' read burst, so that the full waves' reads go first, gets the full
+        // waves their first data ~105 cycles earlier and makes the frame 50 cycles LONGER -- DESIGN.md 7)
         if constexpr (HALF) __builtin_amdgcn_s_setprio(1);
+        // Interior rounds (no request is held at the song's last row: constant row offsets, no clamp), then the last full round and the
+        // tail with the clamp.  At T = 30000 that is 2498 rounds without it and one with.
         int t = 1;
-        for (; t + PF - 1 < Tb; t += PF) {
+        for (; split_round_interior(t, PF, Tb); t += PF) {
+            interior_bases(t);
+            split_frames(std::make_integer_sequence<int, PF>{}, [&](auto k) { frame(er[k], k, std::true_type{}); });
+        }
+        for (; split_round_full(t, PF, Tb); t += PF) {
             round_bases(t);
-            split_frames(std::make_integer_sequence<int, PF>{}, [&](auto k) { frame(er[k], k); });
+            split_frames(std::make_integer_sequence<int, PF>{}, [&](auto k) { frame(er[k], k, std::false_type{}); });
         }
         round_bases(t);
         split_frames(std::make_integer_sequence<int, PF - 1>{}, [&](auto k) {
-            if (t + k < Tb) frame(er[k], k);
+            if (t + k < Tb) frame(er[k], k, std::false_type{});
         });
     };
     static_assert(PF % 2 == 0 && PF % kFmGroups == 0, "the unrolled frames must cycle through whole buffer and slot-group rounds");
@@ -904,6 +926,7 @@ static hipError_t launch_floor_t(const FwdArgs& a, hipStream_t st) {
     if constexpr (W == 32 && NWT == 6) {
         static_assert(kSplitStates == NWT * 64, "the split kernel keeps the six-wave kernel's LDS and history layout");
         static_assert(kSplitFullRows == 64 * kSplitFullWaves, "FwdArgs::floor_live speaks for the full waves' targets");
+        static_assert(PF == kSplitPrefetch, "the host library replays the split kernel's rounds at this depth");
         if (a.fwd_form == 6 || (a.fwd_form == 0 && a.B <= 256 && std::is_same_v<ET, float>)) {
             constexpr size_t ldss = FloorSplitLds::bytes();
             constexpr int NWS = kSplitFullWaves + kSplitHalfWaves;

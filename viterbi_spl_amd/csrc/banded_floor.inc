@@ -41,12 +41,24 @@ __device__ __forceinline__ void fm_publish(float* slot, float v) {
 // S = 361 production shape).  Every wave accumulates over its frames
 //   work = s_memtime at "last max3 done" (just before the publication) - s_memtime right after the preceding barrier
 //   wait = s_memtime after the barrier release - s_memtime after the s_waitcnt lgkmcnt(0) in front of the barrier
-// and lane 0 of wave w leaves {SIMD_ID of HW_REG_HW_ID, mean work, mean wait, frames} in scratch floats 4w .. 4w+3 of its song.
+//   data = s_memtime behind the frame's first s_waitcnt (M's slot quad, in the trimmed full waves together with the first pair of window
+//          quads) - s_memtime right after the preceding barrier: barrier release to first usable data (the split kernel only)
+// and lane 0 of wave w leaves {SIMD_ID of HW_REG_HW_ID, mean work, mean wait, frames} in scratch floats 4w .. 4w+3 of its song and
+// mean data in float 48 + w.  A frame is then data | work - data (first data to last max3) | wait (publication, stores and barrier).
 // The two s_memtime around the barrier return behind it (one more s_waitcnt per frame, the same for every wave): compare
-// waves with each other, and take the frame time from a run without the probe.
+// waves with each other, and take the frame time from a run without the probe.  (With the data stamp's scalar load in flight the
+// compiler makes the next stated lgkmcnt of the frame a wait for everything: the probed full wave's second pair waits as the last one.)
 struct WaveProbe {
-    unsigned long long t_rel = 0, t_pub = 0, work = 0, wait = 0;
-    __device__ __forceinline__ void start() { t_rel = __builtin_amdgcn_s_memtime(); }
+    unsigned long long t_rel = 0, t_pub = 0, t_dat = 0, work = 0, wait = 0, data = 0;
+    __device__ __forceinline__ void start() { t_rel = t_dat = __builtin_amdgcn_s_memtime(); }   // (a kernel without the data stamp reports 0)
+    // behind the frame's first wait: `first` is a value that wait delivered
+    template <typename V>
+    __device__ __forceinline__ void first_data(V& first) {
+        asm volatile("" : "+v"(first));
+        __builtin_amdgcn_sched_barrier(0);
+        t_dat = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+    }
     __device__ __forceinline__ void before_publish(float dn) {
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("" ::"v"(dn));
@@ -56,10 +68,11 @@ struct WaveProbe {
     __device__ __forceinline__ void barrier() {
         unsigned long long t_in, t_out;
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_memtime %0\n\ts_barrier\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&s"(t_in), "=&s"(t_out) : "s"(t_pub) : "memory");
+                     : "=&s"(t_in), "=&s"(t_out) : "s"(t_pub), "s"(t_dat) : "memory");
         work += t_pub - t_rel;
+        data += t_dat - t_rel;
         wait += t_out - t_in;
-        t_rel = t_out;
+        t_rel = t_dat = t_out;
     }
     __device__ __forceinline__ void finish(float* scratch, int wv, int lane, int frames) const {
         if (lane != 0) return;
@@ -68,6 +81,7 @@ struct WaveProbe {
         scratch[4 * wv + 1] = (float)work / n;
         scratch[4 * wv + 2] = (float)wait / n;
         scratch[4 * wv + 3] = n;
+        scratch[48 + wv] = (float)data / n;
     }
 };
 #endif

@@ -116,6 +116,23 @@ constexpr int split_full_width(int live, int W, int S, int n_extras, bool f16) {
         if (live >= 1 && live <= w && w < W) return w;
     return W;
 }
+// Rounds of the split kernel's frame loop.  Frames 1 .. Tb - 1 of a song run in rounds of PF unrolled frames that start at
+// t = 1, 1 + PF, ..., and a tail of up to PF - 1 frames behind the last full round; frame t + u of a round that starts at t requests the
+// emission row of frame t + u + PF, held at the song's last row.  A round is
+//   full      when all its PF frames exist (its last frame t + PF - 1 <= Tb - 1);
+//   interior  when none of its requests is held back (its last request t + 2 PF - 1 <= Tb - 1): the row offset of frame t + u is the
+//             constant u and the loop body has no clamp.  Every full round but the last is interior.
+// split_prefetch_row is the row frame t + u requests: in an interior round the unclamped sum, which the two conditions above keep
+// inside the song; anywhere else the clamped one.  The kernel's loops and the host library's replay (vph_split_rounds) are both
+// written with these three.
+constexpr bool split_round_full(int t, int PF, int Tb) { return t + PF - 1 <= Tb - 1; }
+constexpr bool split_round_interior(int t, int PF, int Tb) { return t + 2 * PF - 1 <= Tb - 1; }
+constexpr int split_prefetch_row(int t, int u, int PF, int Tb, bool interior) {
+    const int r = t + u + PF;
+    return interior || r < Tb - 1 ? r : Tb - 1;
+}
+// the prefetch depth the split kernel is instantiated with (floor_pf<32>(), banded_floor.inc)
+inline constexpr int kSplitPrefetch = 12;
 
 // Byte layout of the device image (all offsets in bytes from the image base,
 // every section 256-byte aligned).

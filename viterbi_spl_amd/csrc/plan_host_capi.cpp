@@ -58,6 +58,28 @@ int vph_live_width(const vph_plan* p, int n_rows) { return vit::floor_live_width
 int vph_split_full_width(const vph_plan* p, int f16) {
     return vit::split_full_width(vit::floor_live_width(p->bp, vit::kSplitFullRows), p->bp.W, p->bp.S, p->bp.ok ? p->bp.n_extras : 0, f16 != 0);
 }
+// The split kernel's frame loop for a song of Tb frames at prefetch depth pf (pf = 0: the depth it is instantiated with), replayed with
+// the kernel's own predicates (vit::split_round_interior / split_round_full / split_prefetch_row): the interior rounds, the remaining
+// full rounds, the tail.  Per frame, in loop order: its index, the emission row it requests and its round's class (2 interior round,
+// 1 clamped full round, 0 tail).  Returns the number of frames, or -1 when they exceed cap or pf is no whole number of buffer rounds.
+int vph_split_rounds(int Tb, int pf, int* frame, int* row, int* cls, int cap) {
+    const int PF = pf > 0 ? pf : vit::kSplitPrefetch;
+    if (Tb < 1 || PF % 2 != 0) return -1;
+    int n = 0;
+    auto emit = [&](int t, int u, int c) {
+        if (n < cap) { frame[n] = t + u; row[n] = vit::split_prefetch_row(t, u, PF, Tb, c == 2); cls[n] = c; }
+        ++n;
+    };
+    int t = 1;
+    for (; vit::split_round_interior(t, PF, Tb); t += PF)
+        for (int u = 0; u < PF; ++u) emit(t, u, 2);
+    for (; vit::split_round_full(t, PF, Tb); t += PF)
+        for (int u = 0; u < PF; ++u) emit(t, u, 1);
+    for (int u = 0; u < PF - 1; ++u)
+        if (t + u < Tb) emit(t, u, 0);
+    return n <= cap ? n : -1;
+}
+int vph_split_prefetch(void) { return vit::kSplitPrefetch; }
 void vph_image(const vph_plan* p, unsigned char* out) { std::memcpy(out, p->image.data(), p->image.size()); }
 
 // Launch schedule of the packed checkpointed decode (vit::packed_ckpt_schedule), for the CPU tests.  Returns the number of launches,
