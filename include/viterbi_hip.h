@@ -376,6 +376,37 @@ int vit_decode_f64_packed(const vit_plan *plan, const void *logE, int emis_dtype
                           double *loglik /* [B] or NULL */, vit_stream stream);
 
 /*
+ * vit_decode_f64() under a workspace budget: the scheme of vit_decode_checkpointed() with the float64 kernels.  States and
+ * log-likelihoods are bit for bit those of vit_decode_f64() on the same arguments (-1 past a song's length, lengths clamped to
+ * [1, T], the -inf rules and the float16 widening included).  The reference keeps T1 / T2 for one recording at a time.
+ * Plans served: exactly those of vit_decode_f64() (one predicate behind all float64 entry points); every other plan gets size 0
+ * and VIT_EUNSUPPORTED before anything is enqueued, and a size > 0 means the decode launches.
+ * segment_frames = K: 64 <= K <= 2^24, a value above T acts like T; out of range VIT_EINVAL and size 0.
+ * Argument checks, status codes and their order are vit_decode_f64()'s, with the K check behind the dtype check and in front of
+ * VIT_EUNSUPPORTED (where vit_decode_checkpointed() has it); B = 0 is VIT_OK; a workspace one byte below the size function's answer
+ * is VIT_EWORKSPACE and nothing is written.  No host synchronisation, no device allocation, O(T / K) launches on `stream`.  It
+ * drops the workspace's vit_forward() record and writes none.
+ * Pass 1 runs the forward recursion over all T frames, one workgroup per song, and keeps the d row of the frame in front of every
+ * segment but a song's first, plus every song's terminal state and log-likelihood.  Pass 2 walks the segments from the last to the
+ * first: the forward kernel resumed from the checkpoint row into the song's segment rows, then the segment's back-trace from the
+ * state decided just behind it (a song's last segment: from the terminal state); a song that ends before a segment starts is
+ * skipped in it.  About twice the forward work.
+ * Workspace, with K = min(segment_frames, T), nseg = ceil(T / K), SD = (S + 3) / 2 * 2 and r(x) = x rounded up to 256:
+ *   r(B * nseg * SD * 8)        checkpoint rows: nseg - 1 per song and one more (where K divides T, pass 1 stores frame T - 1)
+ * + r(B * (K + 1) * SD * 8)     segment rows: ONE IN FRONT of the segment, which receives the frame maximum M of the checkpoint
+ *                               frame (written, never read), and the K of the segment.  M of the segment's last row is formed behind
+ *                               the segment's last frame from what that frame published: no frame past the segment is run.
+ * + r(4 B) + r(128 B) + r(8 B) + r(4 B)   terminal states, chunk entries, the sub-problems' lengths and start states.
+ * A segment's back-trace runs min(32, ceil(2048 / B), frames / max(2 * warm, 64)) chunks per song (at least one) with a warm-up of
+ * 64 frames, and the verify / repair pass of vit_decode_f64(); the chunk rule is tuning: the states do not depend on it.
+ * Honoured options: "bt_chunks", "bt_warm" (per segment); every other option is ignored.
+ */
+size_t vit_workspace_bytes_f64_checkpointed(const vit_plan *plan, int64_t B, int64_t T, int64_t segment_frames);
+int vit_decode_f64_checkpointed(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B, int64_t T, const int64_t *lengths,
+                                void *workspace, size_t workspace_bytes, int32_t *states, double *loglik /* [B] or NULL */,
+                                int64_t segment_frames, vit_stream stream);
+
+/*
  * Fused logits -> path decode: what callers of the reference run is Viterbi.__call__ (tonet/for_paper.py:1817-1831) -- pitch
  * logits -> observation log-probabilities -> Viterbi decode.  vit_obs_*() + vit_decode() do that with a [B,T,S] float32
  * emission tensor written to and read back from device memory (2 x 4 S bytes per frame, 44 GB for [1024, 30000, 361]); here the

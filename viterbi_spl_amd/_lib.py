@@ -26,6 +26,7 @@ EXPORTS = (
     "vit_workspace_bytes_packed_checkpointed", "vit_decode_packed_checkpointed",
     "vit_workspace_bytes_packed_bounded", "vit_decode_packed_bounded", "vit_packed_bounded_units",
     "vit_workspace_bytes_f64", "vit_decode_f64", "vit_workspace_bytes_f64_packed", "vit_decode_f64_packed",
+    "vit_workspace_bytes_f64_checkpointed", "vit_decode_f64_checkpointed",
 )
 ABI_VERSION = 4
 
@@ -130,6 +131,10 @@ def load() -> ctypes.CDLL:
     lib.vit_workspace_bytes_f64_packed.argtypes = [vp, i64, i64]
     lib.vit_decode_f64_packed.restype = i32
     lib.vit_decode_f64_packed.argtypes = [vp, vp, i32, i64, vp, vp, sz, vp, vp, vp]
+    lib.vit_workspace_bytes_f64_checkpointed.restype = sz
+    lib.vit_workspace_bytes_f64_checkpointed.argtypes = [vp, i64, i64, i64]
+    lib.vit_decode_f64_checkpointed.restype = i32
+    lib.vit_decode_f64_checkpointed.argtypes = [vp, vp, i32, i64, i64, vp, vp, sz, vp, vp, i64, vp]
     lib.vit_workspace_bytes_logits.restype = sz
     lib.vit_workspace_bytes_logits.argtypes = [vp, ctypes.POINTER(ObsParams), i64, i64]
     lib.vit_decode_logits.restype = i32

@@ -896,6 +896,123 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
 
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Bounded-workspace float64 decode: the scheme above with vit_decode_f64's kernels in their CK case (f64.hip).  Pass 1 keeps the d
+// row in front of every segment but a song's first and the terminal state and log-likelihood; pass 2 walks the segments from the
+// last to the first: the forward kernel resumed from the checkpoint row into K + 1 rows per song, segment_prep_kernel, the
+// back-trace of the sub-problems.  The plans are vit_decode_f64's (f64_applies); bt_chunks and bt_warm are honoured per segment.
+namespace {
+
+struct F64CkLayout {
+    int64_t nseg, seg_rows;
+    size_t off_ckpt, off_seg, off_last, off_entry, off_slen, off_slast, bytes;
+};
+// Checkpoint rows: nseg per song -- the rows in front of segments 1 .. nseg - 1 and, where K divides T, the place pass 1 stores frame
+// T - 1 at.  Segment rows: K + 1 per song -- one in FRONT of the segment (the forward kernel stores the frame maximum of frame t - 1
+// next to row t - 1 while it computes frame t: for a resumed segment's first frame that is the checkpoint's place) and the K of the
+// segment; M of the segment's last row is formed from what the last frame published, so no frame past the segment is run.
+F64CkLayout f64_ck_layout(const vit_plan* p, int64_t B, int64_t T, int64_t K) {
+    F64CkLayout c;
+    K = K > T ? T : K;
+    const size_t sd = (size_t)vit::f64_hist_stride(p->S) * sizeof(double);
+    c.nseg = (T + K - 1) / K;
+    c.seg_rows = K + 1;
+    c.off_ckpt = 0;
+    c.off_seg = align256((size_t)B * (size_t)c.nseg * sd);
+    c.off_last = c.off_seg + align256((size_t)B * (size_t)c.seg_rows * sd);
+    c.off_entry = c.off_last + align256((size_t)B * sizeof(int32_t));
+    c.off_slen = c.off_entry + align256((size_t)B * vit::kBtMaxChunks * sizeof(int32_t));
+    c.off_slast = c.off_slen + align256((size_t)B * sizeof(int64_t));
+    c.bytes = c.off_slast + align256((size_t)B * sizeof(int32_t));
+    return c;
+}
+// Chunks of one segment's back-trace.  backtrace_chunks() keeps a chunk at eight warm-ups of 128 frames and so gives a segment of
+// 1024 frames ONE chunk: every song then walks its K frames step by step in every segment, T dependent steps in all where the
+// whole-history decode walks T / 32.  Here: enough (song, chunk) waves to cover the chip twice over, chunks no shorter than two
+// warm-ups of kBtWarmSparse frames (a wrong guess costs a repair that ends where the paths meet).  Tuning: the states do not depend on it.
+int f64_segment_chunks(int64_t B, int frames, int warm) {
+    const int shortest = 2 * warm > 64 ? 2 * warm : 64;
+    long long c = (2 * 1024 + B - 1) / B;
+    c = c > frames / shortest ? frames / shortest : c;
+    c = c > vit::kBtMaxChunks ? vit::kBtMaxChunks : c;
+    return c < 1 ? 1 : (int)c;
+}
+
+}  // namespace
+
+size_t vit_workspace_bytes_f64_checkpointed(const vit_plan* plan, int64_t B, int64_t T, int64_t segment_frames) {
+    if (!plan || B < 0 || T < 1 || T > (int64_t)1 << 30 || B > (int64_t)1 << 30 || !ck_segment_ok(segment_frames) || !f64_applies(plan)) return 0;
+    return f64_ck_layout(plan, B, T, segment_frames).bytes;
+}
+
+int vit_decode_f64_checkpointed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T, const int64_t* lengths,
+                                void* workspace, size_t workspace_bytes, int32_t* states, double* loglik, int64_t segment_frames,
+                                vit_stream stream) {
+    if (!states) return VIT_EINVAL;
+    int rc = check_common(plan, B, T, workspace);
+    if (rc != VIT_OK) return rc;
+    if (!logE) return VIT_EINVAL;
+    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
+    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
+    if (!f64_applies(plan)) return VIT_EUNSUPPORTED;
+    const int64_t K = segment_frames > T ? T : segment_frames;
+    const F64CkLayout c = f64_ck_layout(plan, B, T, K);
+    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
+    if (B == 0) return VIT_OK;
+    stamp_erase(plan, workspace);
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    const bool f16 = emis_dtype == VIT_F16;
+    if (lengths)       // frames past a song's end: -1 (segments a song does not reach are skipped, not written)
+        VIT_TRY(hipMemsetAsync(states, 0xff, (size_t)B * (size_t)T * sizeof(int32_t), st));
+
+    // ---- pass 1: checkpoint rows + terminal state and log-likelihood
+    vit::F64Args a{};
+    f64_args_from_plan(plan, a);
+    a.logE = logE;
+    a.lengths = lengths;
+    a.hist = reinterpret_cast<double*>(ws + c.off_ckpt);
+    a.hist_song_stride = c.nseg * (int64_t)a.SD64;
+    a.last_state = reinterpret_cast<int32_t*>(ws + c.off_last);
+    a.loglik = loglik;
+    a.entry = reinterpret_cast<int32_t*>(ws + c.off_entry);
+    a.B = B;
+    a.T = (int)T;
+    a.ckpt_every = (int)K;
+    a.t_begin = 0;
+    a.t_end = (int)T;
+    VIT_TRY(vit::launch_f64_forward_ckpt(a, f16, st));
+
+    // ---- pass 2: segments, last to first
+    int64_t* seg_len = reinterpret_cast<int64_t*>(ws + c.off_slen);
+    int32_t* seg_last = reinterpret_cast<int32_t*>(ws + c.off_slast);
+    const Tuning& tn = plan->tune;
+    for (int64_t sgm = c.nseg - 1; sgm >= 0; --sgm) {
+        const int64_t s0 = sgm * K, e0 = s0 + K < T ? s0 + K : T;
+        vit::F64Args f = a;
+        f.ckpt_every = 0;
+        f.hist = reinterpret_cast<double*>(ws + c.off_seg) + a.SD64;      // the segment's row 0 is the buffer's second row
+        f.hist_song_stride = c.seg_rows * (int64_t)a.SD64;
+        f.loglik = nullptr;
+        f.t_begin = (int)s0;
+        f.t_end = (int)e0;
+        f.init_rows = sgm > 0 ? reinterpret_cast<const double*>(ws + c.off_ckpt) + (size_t)(sgm - 1) * a.SD64 : nullptr;
+        f.init_stride = a.hist_song_stride;
+        VIT_TRY(vit::launch_f64_forward_ckpt(f, f16, st));
+        VIT_TRY(vit::launch_segment_prep(lengths, B, (int)T, (int)s0, (int)e0, states, a.last_state, seg_len, seg_last, st));
+        const int sub_T = (int)(e0 < T ? e0 - s0 + 1 : e0 - s0);           // the frame behind the segment is the sub-problem's terminal frame
+        f.seg_len = seg_len;
+        f.seg_last = seg_last;
+        f.states = states + s0;
+        f.warm = tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarmSparse;
+        f.chunks = f64_segment_chunks(B, sub_T, f.warm);
+        if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kBtMaxChunks) f.chunks = tn.bt_chunks;
+        VIT_TRY(vit::launch_f64_backtrace_segment(f, st));
+    }
+    return VIT_OK;
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Packed (ragged) decode.  The reference decodes every recording whole with its own T (tonet/for_paper.py:2304-2309); a padded
 // [B, T_max, S] tensor wastes memory on the padding and a launch with one wavefront per song costs its LONGEST song.  Here the
 // emissions of B songs are one [sum T_b, S] buffer, the history and the states are packed the same way, and the forward pass

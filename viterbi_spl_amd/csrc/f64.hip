@@ -16,6 +16,8 @@
 // (a speculative pass per (song, chunk), a verify / repair pass per song).
 // Both kernels have a packed case (PK: vit_decode_f64_packed), described at each: a workgroup per forward slot that walks its songs
 // back to back, back-trace waves over per-song chunk lists, rows at offsets[b] of the packed buffers.
+// And a checkpointed case (CK: vit_decode_f64_checkpointed): the forward kernel as pass 1 (checkpoint rows only) or over one segment
+// resumed from a checkpoint row, the back-trace over one segment's sub-problems.
 #include "backtrace_common.hpp"
 
 namespace vit {
@@ -107,8 +109,24 @@ constexpr int kF64Prefetch = 4;    // emission rows in flight (frames ahead)
 // being read when Tb is odd (a one-frame song included).  Behind that barrier nothing of the finished song is read any more (the
 // frame loop's reads all sit before its last barrier), so one barrier is enough for every parity.  PK = false compiles to the
 // code it was before the parameter existed.
-template <int W, int NWT, typename ET, bool PK = false>
+// CK: checkpointed decode (vit_decode_f64_checkpointed), one workgroup per song, in one of two wave-uniform runtime modes.
+//   pass 1 (ckpt_every = K > 0): every frame of the song.  Of the history only the d rows of frames mK - 1 are kept, at rows m - 1 of
+//     the song's own rows of hist (m = 1 ..; the host provides ceil(T / K) rows, so the row of frame T - 1 has a place when K divides
+//     T); every other frame skips its stores by a wave-uniform branch, M is not stored at all.  Terminal state and log-likelihood
+//     as ever.
+//   one segment (ckpt_every = 0): frames t_begin .. min(length, t_end) - 1; a song that ends before t_begin leaves at once.  With
+//     t_begin > 0 the checkpoint row init_rows[song] = d_{t_begin - 1} stands where frame 0 stands: published into buffer 0 in both
+//     copies, with the per-wave partial maxima taken the same way.  Frames are counted from that row: local frame n is frame
+//     base + n, base = max(t_begin - 1, 0); the buffer parity, the emission prefetch (clamped to the last frame this launch
+//     computes) and the unrolled loop all run on n.  Row t is stored at t - t_begin; M_{t-1} goes next to its row as ever, which
+//     for the first frame of a resumed segment is the row in FRONT of hist (the checkpoint's place: written, never read).  M of
+//     the segment's last row, which no frame of this launch takes, is formed behind the loop from the partial maxima of the last
+//     buffer (where the song goes on: the back-trace of the segment decides that row's frame).  No terminal.
+// Both modes share one store: the next frame to keep (`keep`) and its row (`hrow`) advance by K frames / one row in pass 1 and by
+// one frame / one row in a segment.  CK = false compiles to the code it was before the parameter existed.
+template <int W, int NWT, typename ET, bool PK = false, bool CK = false>
 __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) {
+    static_assert(!(PK && CK), "the packed and the checkpointed case are separate kernels");
     using L = F64Lds<W, NWT>;
     constexpr int NP = L::NP, DC = L::DC, BUF = L::BUF, WR = L::WR, PF = kF64Prefetch;
     constexpr int CH = (W > 64 && NWT > 8) ? 8 : 16;        // window sources in flight
@@ -125,7 +143,26 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
     int song = blockIdx.x;
     int Tb = PK ? 1 : song_length(a.lengths, song, T);
     const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PK ? (size_t)0 : (size_t)song * T * S);
-    double* __restrict__ hist = a.hist + (PK ? (size_t)0 : (size_t)song * T * SD);
+    double* __restrict__ hist = a.hist + (PK ? (size_t)0 : CK ? (size_t)song * a.hist_song_stride : (size_t)song * T * SD);
+    // (CK) wave-uniform: pass 1 or a segment, whether the song goes on behind this launch's last frame, the next frame whose row
+    // is kept, the frames between two kept rows, and the kept row's place.  From here on Tb counts LOCAL frames and E starts at
+    // local frame 0.
+    [[maybe_unused]] const bool pass1 = CK && a.ckpt_every > 0;
+    [[maybe_unused]] const bool resumed = CK && a.t_begin > 0;
+    [[maybe_unused]] bool goes_on = false;
+    [[maybe_unused]] int keep = 0, keep_step = 1;
+    [[maybe_unused]] double* hrow = hist;
+    if constexpr (CK) {
+        const int t_last = Tb < a.t_end ? Tb : a.t_end;   // one past the last frame this launch computes
+        if (t_last <= a.t_begin) return;                  // the song ended before this segment
+        goes_on = !pass1 && Tb > t_last;
+        const int base = resumed ? a.t_begin - 1 : 0;
+        Tb = t_last - base;
+        E += (size_t)base * S;
+        keep = pass1 ? a.ckpt_every - 1 : 1;
+        keep_step = pass1 ? a.ckpt_every : 1;
+        hrow = pass1 || resumed ? hist : hist + SD;       // (local frame 1 of a segment from the prior is row 1)
+    }
     // (PK) position in slot_songs and the end of the slot's list; the song at si: its length, emission rows and history rows.
     // Wave-uniform: scalar loads.
     [[maybe_unused]] int si = 0, si_end = 1;
@@ -232,8 +269,15 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
         double dn = fmax(fmax(m0, m1), fmax(m2, m3)) + (double)e_slot;
         dn = tvalid ? dn : -INFINITY;
         produce(dn, WB);
-        if (tvalid) hist[(size_t)t * SD + j] = dn;
-        if (wv == 0 && lane == 0) hist[(size_t)(t - 1) * SD + S] = M;   // M_{t-1}, next to the row it was taken over
+        if constexpr (!CK) {
+            if (tvalid) hist[(size_t)t * SD + j] = dn;
+            if (wv == 0 && lane == 0) hist[(size_t)(t - 1) * SD + S] = M;   // M_{t-1}, next to the row it was taken over
+        } else if (t == keep) {
+            if (tvalid) hrow[j] = dn;
+            if (wv == 0 && lane == 0 && !pass1) hrow[S - SD] = M;           // (a resumed segment's first frame: the row in front)
+            hrow += SD;
+            keep += keep_step;
+        }
         const int tn = t + PF < Tb ? t + PF : Tb - 1;
         e_slot = load_e<ET>(E + (size_t)tn * S + jc);
         __syncthreads();
@@ -244,8 +288,13 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
         // ---------------- frame 0: the reference forms log_pi + E_0 in float32 and stores it into the float64 T1
         {
             const float d0f = tvalid ? reinterpret_cast<const float*>(a.image + a.off_logpi)[jc] + load_e<ET>(E + jc) : -INFINITY;
-            const double d0 = (double)d0f;
-            if (tvalid) hist[j] = d0;
+            double d0 = (double)d0f;
+            if constexpr (!CK) {
+                if (tvalid) hist[j] = d0;
+            } else {
+                if (resumed) d0 = tvalid ? a.init_rows[(size_t)song * a.init_stride + jc] : -INFINITY;   // the checkpoint row: d_{t_begin - 1}
+                else if (tvalid && !pass1) hist[j] = d0;
+            }
             produce(d0, 0);
         }
         float er[PF];
@@ -262,6 +311,19 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
         for (int k = 0; k < PF - 1; ++k)
             if (t + k < Tb) frame(t + k, er[k], k);
 
+        if constexpr (CK) {
+            if (!pass1) {
+                // M of the segment's last row (buffer (Tb - 1) & 1, complete behind the last barrier), in frame()'s order
+                if (goes_on && wv == 0 && lane == 0) {
+                    const f64x2* __restrict__ pl = reinterpret_cast<const f64x2*>(pm + ((Tb - 1) & 1) * 16);
+                    double M = fmax(pl[0].x, pl[0].y);
+#pragma unroll
+                    for (int q = 1; q < NWT / 2; ++q) M = fmax(fmax(M, pl[q].x), pl[q].y);
+                    hrow[S - SD] = M;
+                }
+                return;
+            }
+        }
         // ---------------- the terminal state: lowest-index argmax of d_{Tb-1}, and its value
         if (wv == 0) {
             const int fb = (Tb - 1) & 1;                  // buffer holding d_{Tb-1}
@@ -300,11 +362,16 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
 // the waves and the chunk entries chunk_base[b] .. chunk_base[b + 1] - 1, so its chunk count grows with its length; MODE 1 one wave
 // per song over that song's own chunk count.  Its history rows and states sit at row offsets[b] of the packed buffers and there are
 // no frames past its end to fill.  PK = false compiles to the code it was before the parameter existed.
+// CK: one segment of a checkpointed decode (vit_decode_f64_checkpointed).  Song b is a sub-problem of seg_len[b] frames (0: the song
+// ended before the segment; its waves leave) whose last frame already has its state, seg_last[b]; its rows start at
+// hist_song_stride * b and its states at states + b * T, a.states being advanced to the segment's first frame.  Nothing is filled
+// past a song's end: the host fills the whole buffer once.  CK = false compiles to the code it was before the parameter existed.
 constexpr int kF64BtWaves = 4;
 constexpr int kF64BtSlots = 3;     // candidate slots per lane: W + kMaxExtras <= 192
 
-template <int NWT, int MODE, bool PK = false>
+template <int NWT, int MODE, bool PK = false, bool CK = false>
 __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args a) {
+    static_assert(!(PK && CK), "the packed and the checkpointed case are separate kernels");
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int EPL = NWT, NP = NWT * 64, KC = kF64BtSlots;
     const int S = a.S, SD = a.SD64, T = a.T, W = a.W, nx = a.n_extras;
@@ -323,10 +390,11 @@ __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args
     const int C = PK ? a.chunk_base[song + 1] - cbase : C0;
     const int chunk = MODE == 0 ? (PK ? (int)(gw - cbase) : (int)(gw % C)) : 0;
     const long long row0 = PK ? (long long)a.offsets[song] : 0;   // (PK) first history row / state of the song
-    const int Tb = PK ? (int)(a.offsets[song + 1] - row0) : song_length(a.lengths, song, T);
+    const int Tb = PK ? (int)(a.offsets[song + 1] - row0) : CK ? (int)a.seg_len[song] : song_length(a.lengths, song, T);
+    if (CK && Tb < 1) return;
     int32_t* states = a.states + (PK ? (size_t)row0 : (size_t)song * T);       // (no __restrict__: MODE 1 reads what chase() stored)
     int32_t* entry = a.entry + (PK ? (size_t)cbase : (size_t)song * C);
-    const double* __restrict__ hist = a.hist + (PK ? (size_t)row0 * SD : (size_t)song * T * SD);
+    const double* __restrict__ hist = a.hist + (PK ? (size_t)row0 * SD : CK ? (size_t)song * a.hist_song_stride : (size_t)song * T * SD);
     const float* __restrict__ tabX = reinterpret_cast<const float*>(a.image + a.off_tabX);
     const int32_t* __restrict__ loT = reinterpret_cast<const int32_t*>(a.image + a.off_lo);
 
@@ -449,11 +517,11 @@ __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args
     // ---- the chunk scheme (bt_run_chunks of backtrace_common.hpp, with the guess taken from a row of doubles)
     const int Lf = Tb - 1;
     if (MODE == 0) {
-        const int last = __builtin_amdgcn_readfirstlane(a.last_state[song]);
+        const int last = __builtin_amdgcn_readfirstlane(CK ? a.seg_last[song] : a.last_state[song]);
         int lo_c, hi_c;
         bt_chunk_bounds(Lf, chunk, C, lo_c, hi_c);
         if (chunk == C - 1) {
-            if constexpr (!PK)
+            if constexpr (!PK && !CK)
                 for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
             if (lane == 0) states[Tb - 1] = last;
         }
@@ -526,6 +594,22 @@ hipError_t launch_f64_forward(const F64Args& a, bool f16, hipStream_t st) {
     });
 }
 
+// pass 1 (a.ckpt_every > 0, from frame 0) or one segment (resumed from a.init_rows where a.t_begin > 0) of a checkpointed decode
+hipError_t launch_f64_forward_ckpt(const F64Args& a, bool f16, hipStream_t st) {
+    if (a.B < 1 || a.T < 1 || a.W > a.S || a.offsets || a.t_begin < 0 || a.t_end > a.T || a.t_begin >= a.t_end || (a.t_begin > 0 && !a.init_rows) ||
+        (a.ckpt_every > 0 && a.t_begin > 0) || a.ckpt_every < 0)
+        return hipErrorInvalidValue;
+    return f64_dispatch_width(a.W, [&](auto w) {
+        return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
+            constexpr int W = decltype(w)::value, NWT = decltype(n)::value;
+            constexpr size_t lds = F64Lds<W, NWT>::bytes();
+            if (f16) hipLaunchKernelGGL((f64_floor_forward_kernel<W, NWT, __half, false, true>), dim3((unsigned)a.B), dim3(NWT * 64), lds, st, a);
+            else hipLaunchKernelGGL((f64_floor_forward_kernel<W, NWT, float, false, true>), dim3((unsigned)a.B), dim3(NWT * 64), lds, st, a);
+            return hipGetLastError();
+        });
+    });
+}
+
 // the packed forward instantiation of the plan: launched over a.n_slots workgroups, or (per_cu set) asked how many of its workgroups
 // one compute unit holds at once (the occupancy query at its LDS size)
 static hipError_t f64_forward_packed(const F64Args& a, bool f16, hipStream_t st, int* per_cu) {
@@ -559,6 +643,22 @@ hipError_t launch_f64_backtrace(const F64Args& a, hipStream_t st) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess || a.chunks <= 1) return e;
         hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 1>), dim3((unsigned)((a.B + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
+        return hipGetLastError();
+    });
+}
+
+// the sub-problems of one segment: a.chunks chunks each, whatever their lengths (an empty chunk stands by itself)
+hipError_t launch_f64_backtrace_segment(const F64Args& a, hipStream_t st) {
+    if (a.B < 1 || !a.seg_len || !a.seg_last || a.offsets || a.chunks < 1 || a.chunks > kBtMaxChunks || a.W + kMaxExtras > 64 * kF64BtSlots)
+        return hipErrorInvalidValue;
+    return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
+        constexpr int NWT = decltype(n)::value;
+        constexpr size_t lds = sizeof(double) * kF64BtWaves * NWT * 64;
+        const long long waves0 = (long long)a.B * a.chunks;
+        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 0, false, true>), dim3((unsigned)((waves0 + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess || a.chunks <= 1) return e;
+        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 1, false, true>), dim3((unsigned)((a.B + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
         return hipGetLastError();
     });
 }

@@ -223,9 +223,24 @@ struct F64Args {
     const int32_t* wave_song;   // [n_waves] song of each back-trace wave (speculative pass)
     const int32_t* chunk_base;  // [B+1] first wave / chunk entry of each song; chunks = the largest chunk count of any song
     int n_waves;
+    // checkpointed decode (vit_decode_f64_checkpointed; the CK case of both kernels).  Forward: ckpt_every = K > 0 is pass 1 -- every
+    // frame of the song, the d row of frame mK - 1 kept at row m - 1 of the song's rows of hist, nothing else stored but the terminal
+    // state and log-likelihood; ckpt_every = 0 is one segment -- frames t_begin .. min(length, t_end) - 1, resumed from
+    // init_rows[song] = d_{t_begin - 1} where t_begin > 0, row t stored at t - t_begin (and M of frame t_begin - 1 in the row in
+    // front of hist).  A song's rows start hist_song_stride doubles after the one before.  Back-trace: song b is a sub-problem of
+    // seg_len[b] frames (0: skipped) that starts from state seg_last[b]; states is advanced to the segment's first frame.
+    int ckpt_every, t_begin, t_end;
+    const double* init_rows;
+    int64_t init_stride;        // doubles from one song's init row to the next
+    int64_t hist_song_stride;
+    const int64_t* seg_len;     // [B]
+    const int32_t* seg_last;    // [B]
 };
 hipError_t launch_f64_forward(const F64Args& a, bool f16, hipStream_t st);
 hipError_t launch_f64_backtrace(const F64Args& a, hipStream_t st);
+// the CK instantiations: pass 1 or one segment of the forward kernel; the back-trace of one segment's sub-problems
+hipError_t launch_f64_forward_ckpt(const F64Args& a, bool f16, hipStream_t st);
+hipError_t launch_f64_backtrace_segment(const F64Args& a, hipStream_t st);
 // the same over a packed batch, and the workgroups of the packed forward instantiation one compute unit holds at once (as
 // banded_variant_resident)
 hipError_t launch_f64_forward_packed(const F64Args& a, bool f16, hipStream_t st);

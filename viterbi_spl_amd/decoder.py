@@ -323,20 +323,94 @@ class ViterbiDecoder:
                                        "matrices, the Durrieu step matrices and scan-only plans are not served)")
         return need
 
+    def workspace_bytes_f64_checkpointed(self, B: int, T: int, segment_frames: int) -> int:
+        """Workspace bytes of ``decode_f64_checkpointed``; raises ViterbiHipError for a plan or a segment length it does not serve."""
+        need = int(_lib.load().vit_workspace_bytes_f64_checkpointed(self._plan, int(B), int(T), int(segment_frames)))
+        if need == 0 and B > 0:
+            raise _lib.ViterbiHipError("the checkpointed float64 decode needs 64 <= segment_frames <= 2**24 and a plan decode_f64 serves: "
+                                       "banded, its floor form proven, without dense rows (unstructured matrices, the Durrieu step "
+                                       "matrices and scan-only plans are not served)")
+        return need
+
+    @staticmethod
+    def _plan_segments(full_need: int, size_of, budget: Optional[int], what: str = "decode") -> dict:
+        """The budget policy of the checkpointed decodes as a pure function: ``full_need`` bytes of the whole history, ``size_of(K)``
+        the bytes at segment length K (0 = not served), ``budget`` bytes or None.  ``{"mode": "full", ...}`` when the whole history
+        fits, else the largest K of 8192, 4096, ..., 64 that fits (the fewest launches); ViterbiHipError when none does."""
+        if budget is None or full_need <= budget:
+            return {"mode": "full", "workspace_bytes": int(full_need)}
+        K = 8192
+        while K >= 64:
+            ck = int(size_of(K))
+            if 0 < ck <= budget:
+                return {"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ck}
+            K //= 2
+        raise _lib.ViterbiHipError(f"no {what} fits a workspace of {budget} bytes (the whole history needs {full_need})")
+
+    def plan_workspace_f64(self, B: int, T: int, max_workspace_bytes: Optional[int] = None) -> dict:
+        """How ``decode_f64`` decodes a [B, T, S] batch under a workspace budget (bytes; None = whatever it takes):
+        ``{"mode": "full", "workspace_bytes": n}`` -- ``vit_decode_f64`` fits -- or ``{"mode": "checkpointed", "segment_frames": K,
+        "workspace_bytes": n}`` -- ``vit_decode_f64_checkpointed`` with the largest K of 8192, 4096, ..., 64 that fits.  Raises
+        ViterbiHipError when nothing fits or the plan is not served.  Both modes decode the same bits."""
+        lib = _lib.load()
+        return self._plan_segments(self.workspace_bytes_f64(B, T), lambda K: lib.vit_workspace_bytes_f64_checkpointed(self._plan, B, T, K),
+                                   None if max_workspace_bytes is None else int(max_workspace_bytes), f"float64 decode of a [{B}, {T}, {self.S}] batch")
+
+    def decode_f64_checkpointed(self, emission_logits: torch.Tensor, segment_frames: int = 1024, lengths: Optional[torch.Tensor] = None,
+                                out_dtype: torch.dtype = torch.int64, workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_f64`` with a bounded workspace (``vit_decode_f64_checkpointed``): about ``T / segment_frames + segment_frames``
+        rows of doubles per song instead of ``T``.  Same states, same float64 log-likelihood, bit for bit; about twice the forward
+        work.  Plans: those of ``decode_f64``; any other raises ``ViterbiHipError`` before anything is enqueued.  ``workspace``: an
+        optional uint8 tensor of at least ``workspace_bytes_f64_checkpointed(...) + 256`` bytes to decode in (the caller then keeps it
+        alive until the stream has run the decode: the call does not synchronise); without one the call allocates its own and
+        synchronises the stream before it returns."""
+        lib = _lib.load()
+        logE, single, dt = self._check_emissions(emission_logits)
+        B, T, _ = logE.shape
+        if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
+            raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
+        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
+        loglik = torch.empty((B,), dtype=torch.float64, device=self.device)
+        if B > 0:
+            ws, ws_ptr, ws_bytes, mine = self._call_workspace(self.workspace_bytes_f64_checkpointed(B, T, segment_frames), workspace)
+            with torch.cuda.device(self.device):
+                rc = lib.vit_decode_f64_checkpointed(self._plan, logE.data_ptr(), dt, B, T, lengths.data_ptr() if lengths is not None else None,
+                                                     ws_ptr, ws_bytes, states.data_ptr(), loglik.data_ptr(), int(segment_frames),
+                                                     torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(rc, "vit_decode_f64_checkpointed")
+            if mine:
+                torch.cuda.current_stream(self.device).synchronize()
+        if out_dtype != torch.int32:
+            states = states.to(out_dtype)
+        return (states[0], loglik[0]) if single else (states, loglik)
+
     def decode_f64(self, emission_logits: torch.Tensor, lengths: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.int64,
-                   workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                   workspace: Optional[torch.Tensor] = None, max_workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The reference's float64 Viterbi variant (dcnet/tf_viterbi_decoding.py:209-263) on float32 / float16 emissions
         (``vit_decode_f64``): the running score is kept in float64, bit for bit what that NumPy loop computes on float32 parameters.
         Returns (states [B,T] or [T] of ``out_dtype``, loglik float64 [B] or scalar).  On long inputs the path differs from
         ``decode``'s in a few frames out of thousands; this one scores better.  ``workspace``: a uint8 tensor of at least
         ``workspace_bytes_f64(B, T) + 256`` bytes on the decoder's device (the caller keeps it alive until the stream has run the
         decode), else the decoder's own buffer, the one ``decode`` uses (twice that decode's bytes: rows of doubles; it stays that
-        large until the decoder goes).  The call does not synchronise."""
+        large until the decoder goes).  The call does not synchronise.
+
+        ``max_workspace_bytes``: a budget for the workspace (``plan_workspace_f64``).  Where the whole history does not fit, the call
+        goes through ``decode_f64_checkpointed`` with the largest segment length that does -- the same bits -- and raises
+        ``ViterbiHipError`` before anything is enqueued when none does.  Under a budget the decoder's own buffer is not used where
+        it is larger than the budget: it is dropped and allocated anew at the size needed."""
         lib = _lib.load()
         logE, single, dt = self._check_emissions(emission_logits)
         B, T, _ = logE.shape
         if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
             raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
+        if B > 0 and max_workspace_bytes is not None:
+            mode = self.plan_workspace_f64(B, T, int(max_workspace_bytes))
+            if mode["mode"] == "checkpointed":
+                st, ll = self.decode_f64_checkpointed(logE, segment_frames=mode["segment_frames"], lengths=lengths, out_dtype=out_dtype,
+                                                      workspace=workspace)
+                return (st[0], ll[0]) if single else (st, ll)
+            if workspace is None and self._ws is not None and self._ws.numel() > int(max_workspace_bytes) + 256:
+                self._ws = None                              # (a larger buffer kept from an earlier decode would defeat the budget)
         states = torch.empty((B, T), dtype=torch.int32, device=self.device)
         loglik = torch.empty((B,), dtype=torch.float64, device=self.device)
         if B > 0:
@@ -383,8 +457,8 @@ class ViterbiDecoder:
         return groups
 
     def plan_workspace_f64_packed(self, offsets, max_workspace_bytes: Optional[int] = None) -> dict:
-        """How ``decode_f64_packed`` meets a workspace budget (bytes; None = whatever it takes): there is no checkpointed float64
-        decode, so the recordings are decoded in consecutive groups, each taking recordings in order while its
+        """How ``decode_f64_packed`` meets a workspace budget (bytes; None = whatever it takes): the checkpointed float64 decode
+        (``decode_f64_checkpointed``) takes padded batches only, so the recordings are decoded in consecutive groups, each taking recordings in order while its
         ``workspace_bytes_f64_packed`` fits.  Returns ``{"groups": [(b0, b1), ...], "bytes": the largest group's need}``; raises
         ViterbiHipError when one recording alone does not fit, or for a plan that is not served."""
         off = self._host_offsets(offsets)
