@@ -22,7 +22,7 @@ def kind(op):
         return "barrier"
     if op.startswith("v_"):
         return "valu"
-    if op.startswith("ds_"):
+    if op.startswith("ds_"):          # (inline asm included: ds_write_addtid_b32 between ;;#ASMSTART / ;;#ASMEND is an LDS instruction like any other)
         return "lds"
     if op.startswith(("buffer_", "global_", "flat_", "scratch_")):
         return "vmem"

@@ -422,8 +422,21 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             for (int k = 0; k < NXL; ++k)
                 xa[k] = (tvalid && k < nx && (!HALF || hh == 1)) ? xaT[(size_t)k * SP + jc] : -INFINITY;   // (lower half: -inf)
         }
-        // own entry of copy 0 (copy c: + c*DC - c); an upper lane starts at copy 2
-        float* wp = dls + 4 + sh + j + (HALF ? hh * split_upper_off(DC) : 0);
+        // Half waves: own entry of copy 0 (copy c: + c*DC - c); an upper lane starts at copy 2.
+        // Full waves: no address register.  Lane l of wave wv writes float 4 + sh + 64 wv + l of copy 0 and the same entry of the other
+        // copies a constant further on, so the store is ds_write_addtid_b32 (lds_store_addtid): M0 holds the wave's part, set here once
+        // for the whole song (frame 0 included; nothing in this role writes M0 again -- checked in the .s), the instruction's immediate
+        // the buffer's and the copy's, and the hardware adds 4 * lane.  Half the issue time of ds_write_b32 for the sixteen stores per
+        // CU that end every frame (scripts/ubench/lds_store_tail.hip: 64 -> 32 cycles).  The half waves' targets are not
+        // linear in the lane (split_half_target) and their stores do not close the frame: they keep ds_write_b32.
+        [[maybe_unused]] float* wp = nullptr;
+        if constexpr (HALF) wp = dls + 4 + sh + j + hh * split_upper_off(DC);
+        else {
+            static_assert(L::dls == 0 && DC == kSplitCopyStride && BUF == 4 * DC, "split_addtid_base / split_addtid_imm (plan.hpp) speak of this layout");
+            static_assert(split_addtid_imm(1, 3) + split_addtid_base(3, NWF - 1) + 4 * 64 <= (int)L::bytes() && L::bytes() < 65536,
+                          "the largest immediate, the largest base and their sum with the lane term: inside the segment, hence 16 bits each");
+            lds_addtid_base(reinterpret_cast<const float*>(smem + split_addtid_base(sh, wv)));
+        }
         // the extra columns' positions in copy 0, kept in a vector register: they are wave-uniform, and from a scalar register every
         // frame's ds_read_b32 needed a v_mov first  (XS: delta[x] comes with the M slots, no read and no register)
         [[maybe_unused]] int xo[NXL > 0 ? NXL : 1];
@@ -435,9 +448,17 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             }
         }
 
-        auto produce = [&](const float dn, const int WB, const int G, const int Z) {
+        auto produce = [&](const float dn, auto wbc, const int G, const int Z) {
+            constexpr int WB = decltype(wbc)::value;                      // (a constant: the add-tid stores carry it in their immediate)
+            if constexpr (HALF) {
 #pragma unroll
-            for (int c = 0; c < (HALF ? 2 : 4); ++c) wp[WB * BUF + floor_copy_off(DC, c)] = dn;
+                for (int c = 0; c < 2; ++c) wp[WB * BUF + floor_copy_off(DC, c)] = dn;
+            } else {
+                split_frames(std::make_integer_sequence<int, 4>{}, [&](auto cc) {
+                    static_assert(split_addtid_imm(WB, decltype(cc)::value) == 4 * (WB * BUF + floor_copy_off(DC, decltype(cc)::value)), "the ds_write_b32 form's offset");
+                    lds_store_addtid<split_addtid_imm(WB, decltype(cc)::value)>(dn);
+                });
+            }
             // XQ: the extra column's lanes publish into a slot nobody reads (fmp above), every other plan keeps the select
             fm_publish(fmp + G * kFmGroupFloats, (!XQ && NXL > 0 && is_x) ? -INFINITY : dn);
             // (the resetting wave is a role of its own: no wave test per frame, the one-target kernel's costs three SALU slots)
@@ -448,8 +469,14 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
         {
             const float d0 = tvalid ? reinterpret_cast<const float*>(a.image + a.off_logpi)[j] + load_e<ET>(E + j) : -INFINITY;
             if (own) hist[j] = d0;
-            produce(d0, 0, 0, 1);
+            produce(d0, std::integral_constant<int, 0>{}, 0, 1);
         }
+        // The full waves' copy writes are inline asm the compiler counts no lgkmcnt for: in front of EVERY barrier of this role the wait
+        // for them is stated, not left to the one the compiler derives from the ds_max_f32.  A missing one is a silent race, not a fault.
+        auto frame_barrier = [&] {
+            if constexpr (!HALF) __builtin_amdgcn_s_waitcnt(split_waitcnt(kNoVmWait, 0));
+            __syncthreads();
+        };
         float er[PF];
 #pragma unroll
         for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)(1 + k < Tb ? 1 + k : Tb - 1) * S + jld);
@@ -458,7 +485,7 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
 #pragma unroll
         for (int k = 0; k < NXL; ++k) asm volatile("" ::"v"(xa[k]));
         asm volatile("" ::"v"(cj));
-        __syncthreads();
+        frame_barrier();
 
         // Row bases of a round of up to PF frames that starts at frame t: history row t - 1 and emission row min(t + PF, Tb - 1), one
         // descriptor each for the whole round.  Frame t + u reaches its rows through the buffer instructions' scalar offset: u history
@@ -486,7 +513,7 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
         auto frame = [&](float& e_slot, auto uc, auto ic) {
             constexpr int u = decltype(uc)::value;
             constexpr bool INTERIOR = decltype(ic)::value;
-            const int RB = u & 1, WB = RB ^ 1;
+            constexpr int RB = u & 1, WB = RB ^ 1;
             const int GR = u % kFmGroups, GW = (u + 1) % kFmGroups, GZ = (u + 2) % kFmGroups;
             const f32x4* __restrict__ win = reinterpret_cast<const f32x4*>(rp + RB * BUF);
             float xd[NXL > 0 ? NXL : 1];
@@ -623,16 +650,16 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             // (the stored value and the emission offset are formed in front of the publication: the order the measured builds have)
             const float sv = (HALF && is_fm) ? M : dn;                    // (full waves hold live targets only)
             const unsigned eso = INTERIOR ? (unsigned)u * rowE : ((unsigned)u * rowE < elim ? (unsigned)u * rowE : elim);
-            produce(dn, WB, GW, GZ);
+            produce(dn, std::integral_constant<int, WB>{}, GW, GZ);
             asm volatile("" ::: "memory");   // the global store / prefetch fill the wait for the LDS write acknowledgement
             // KEEP THIS STORE SINGLE-DWORD: with a register soffset a store wider than 64 bits needs wait states in front of the next write
             // of its data registers that the compiler does not insert -- wrong rows, not reproducibly
             row_store_f32(hb, hoffb, sv, (unsigned)u * rowH);
             e_slot = row_load_e<ET>(eb, eoffb, eso);
 #ifdef VIT_TIMING_HOOKS
-            if constexpr (wprobe) wp_.barrier(); else
+            if constexpr (wprobe) wp_.barrier(); else   // (the probe's barrier states the same wait)
 #endif
-            __syncthreads();
+            frame_barrier();
         };
 #ifdef VIT_TIMING_HOOKS
         if constexpr (wprobe) wp_.start();

@@ -100,6 +100,22 @@ inline constexpr int kDppRowRor8 = 0x128;
 __device__ __forceinline__ float max_lane_xor8(float x) {
     return fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), kDppRowRor8, 0xf, 0xf, false)));
 }
+// ---- LDS stores without an address register (ds_write_addtid_b32): lane l stores its dword at byte M0[15:0] + BYTE_OFF + 4 * l.
+// The instruction hands the LDS one register instead of two and takes half the issue time of ds_write_b32 (measured:
+// scripts/ubench/lds_store_tail.hip).  M0 is set by lds_addtid_base, ONCE in front of a loop of stores -- as an input operand of the
+// store the compiler re-issued the s_mov in every iteration.  The compiler does not know either asm as an LDS operation: the "memory"
+// clobber keeps its own LDS accesses on their side of the store, but it counts no lgkmcnt for it, so whoever needs the store
+// to have landed (a barrier) states s_waitcnt lgkmcnt(0) himself.  Nothing else between base and stores may write M0 (check the .s).
+// `p` points into LDS; the base is its 32-bit LDS address (wave-uniform), which must fit 16 bits together with every BYTE_OFF used.
+__device__ __forceinline__ void lds_addtid_base(const float* p) {
+    const unsigned base = (unsigned)(unsigned long)(__attribute__((address_space(3))) const float*)p;
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" ::"s"(base) : "memory");   // (one wait state between an M0 write and an add-tid store)
+}
+template <int BYTE_OFF>
+__device__ __forceinline__ void lds_store_addtid(float v) {
+    static_assert(BYTE_OFF >= 0 && BYTE_OFF < 65536 && BYTE_OFF % 4 == 0, "the instruction's 16-bit offset field");
+    asm volatile("ds_write_addtid_b32 %0 offset:%1" ::"v"(v), "n"(BYTE_OFF) : "memory");
+}
 // lane l <- x[l-1], lane 0 <- fill   (wave_shr:1)
 __device__ __forceinline__ float wave_shift_up(float x, float fill) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(x), 0x138, 0xf, 0xf, false));

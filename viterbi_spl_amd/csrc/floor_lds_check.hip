@@ -101,6 +101,28 @@ static void replay(const char* name, int NWT, bool split) {
                     }
                 }
     }
+    // ---- the split kernel's full waves store by ds_write_addtid_b32: byte address = base (M0) + immediate + 4 * lane, from the start
+    // of the segment (plan.hpp).  For every wave, lane, buffer, copy and shift that must be the byte address of the float the
+    // ds_write_b32 form writes (the position claimed above, wp = dls + 4 + sh + j with j = 64 wave + lane), and base and immediate
+    // must each fit the instruction's 16-bit field -- as must their sum with the lane term, the address the LDS sees.
+    if (split) {
+        static_assert(!std::is_same_v<L, FloorSplitLds> || (kSplitCopyStride == DC && L::dls == 0 && BUF == 4 * DC), "plan.hpp's address rule speaks of this layout");
+        CHECK((std::is_same_v<L, FloorSplitLds>), "%s: the split kernel runs in FloorSplitLds", name);
+        for (int sh = 0; sh < 4; ++sh)
+            for (int wv = 0; wv < kSplitFullWaves; ++wv)
+                for (int b = 0; b < 2; ++b)
+                    for (int c = 0; c < 4; ++c) {
+                        const int base = split_addtid_base(sh, wv), imm = split_addtid_imm(b, c);
+                        CHECK(base >= 0 && base < 65536 && imm >= 0 && imm < 65536, "add-tid base %d / immediate %d outside 16 bits", base, imm);
+                        for (int lane = 0; lane < 64; ++lane) {
+                            const int j = 64 * wv + lane, pos = L::dls + 4 + sh + j + b * BUF + floor_copy_off(DC, c);
+                            CHECK(pos == split_copy_pos(sh, j, b, c), "split_copy_pos(%d, %d, %d, %d) = %d, the kernel's offsets give %d", sh, j, b, c, split_copy_pos(sh, j, b, c), pos);
+                            CHECK(base + imm + 4 * lane == 4 * pos, "add-tid store of wave %d lane %d, buffer %d copy %d, sh %d: byte %d, not %d", wv, lane, b, c, sh, base + imm + 4 * lane, 4 * pos);
+                            CHECK(base + imm + 4 * lane + 4 <= 65536 && 4 * pos + 4 <= (int)L::bytes(), "add-tid store at byte %d leaves the segment", base + imm + 4 * lane);
+                        }
+                    }
+        std::printf("split full waves: ds_write_addtid_b32 base + immediate + 4 * lane is the ds_write_b32 address for every wave, lane, buffer, copy and shift: ok\n");
+    }
     // ---- paired writes.  The lane's four writes are `stride` = DC - 1 dwords apart.  The copies must sit at four different residues
     // mod 4 (each lane reads the one that aligns its window), so the distance between any two copies is not a multiple of 4, let alone
     // of 64: the st64 form can never pair two copies; the plain form needs a whole copy (> NP floats) within 255 dwords.

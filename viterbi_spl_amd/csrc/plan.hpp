@@ -133,6 +133,17 @@ constexpr int split_prefetch_row(int t, int u, int PF, int Tb, bool interior) {
 }
 // the prefetch depth the split kernel is instantiated with (floor_pf<32>(), banded_floor.inc)
 inline constexpr int kSplitPrefetch = 12;
+// Copy writes of the split kernel's full-window waves (waves 0 .. 3, target j = 64 wave + lane).  delta[j] of buffer b goes to copy c
+// at float split_copy_pos(sh, j, b, c) of the LDS segment (sh = win_shift; the four copies lie kSplitCopyStride floats apart, each
+// shifted one float down against the one before, two buffers of four copies: FloorSplitLds, banded_floor.inc).  The kernel stores it
+// with ds_write_addtid_b32, whose byte address is M0 + immediate + 4 * lane:
+//   M0        = split_addtid_base(sh, wave), set once per wave (plus the LDS address of the segment, which the kernel takes from the pointer)
+//   immediate = split_addtid_imm(b, c), a constant of the unrolled frame and copy
+// Both are 16-bit fields.  The kernel, floor_lds_check.hip and the host library (vph_split_addtid) are written with these.
+inline constexpr int kSplitCopyStride = 384 + 16;
+constexpr int split_copy_pos(int sh, int j, int b, int c) { return 4 + sh + j + b * 4 * kSplitCopyStride + c * kSplitCopyStride - c; }
+constexpr int split_addtid_base(int sh, int wave) { return 4 * (4 + sh + 64 * wave); }
+constexpr int split_addtid_imm(int b, int c) { return 4 * (b * 4 * kSplitCopyStride + c * kSplitCopyStride - c); }
 
 // Byte layout of the device image (all offsets in bytes from the image base,
 // every section 256-byte aligned).

@@ -80,6 +80,16 @@ int vph_split_rounds(int Tb, int pf, int* frame, int* row, int* cls, int cap) {
     return n <= cap ? n : -1;
 }
 int vph_split_prefetch(void) { return vit::kSplitPrefetch; }
+// The copy write of lane `lane` of full wave `wave` (0 .. 3) into copy c of buffer b at win_shift sh, in both forms: out[0] = the
+// ds_write_addtid_b32 base (M0, from the start of the LDS segment), out[1] = its immediate, out[2] = the float position the ds_write_b32
+// form writes (wp[b * BUF + floor_copy_off(DC, c)], wp = dls + 4 + sh + j).  Returns 0, or -1 for an argument out of range.
+int vph_split_addtid(int sh, int wave, int lane, int b, int c, int* out) {
+    if (sh < 0 || sh > 3 || wave < 0 || wave >= vit::kSplitFullRows / 64 || lane < 0 || lane > 63 || b < 0 || b > 1 || c < 0 || c > 3) return -1;
+    out[0] = vit::split_addtid_base(sh, wave);
+    out[1] = vit::split_addtid_imm(b, c);
+    out[2] = vit::split_copy_pos(sh, 64 * wave + lane, b, c);
+    return 0;
+}
 void vph_image(const vph_plan* p, unsigned char* out) { std::memcpy(out, p->image.data(), p->image.size()); }
 
 // Launch schedule of the packed checkpointed decode (vit::packed_ckpt_schedule), for the CPU tests.  Returns the number of launches,
