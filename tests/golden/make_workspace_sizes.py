@@ -53,8 +53,10 @@ def plan_sizes(lib, A, pi):
             for algo in ALGOS:
                 out[f"for|{B}|{T}|algo{algo}|wave_history{wh}"] = int(lib.vit_workspace_bytes_for(plan, B, T, algo))
         assert lib.vit_plan_set_option(plan, b"reset", 0) == 0
+        out[f"f64|{B}|{T}"] = int(lib.vit_workspace_bytes_f64(plan, B, T))
         for K in SEGMENTS:
             out[f"checkpointed|{B}|{T}|{K}"] = int(lib.vit_workspace_bytes_checkpointed(plan, B, T, K))
+            out[f"f64_checkpointed|{B}|{T}|{K}"] = int(lib.vit_workspace_bytes_f64_checkpointed(plan, B, T, K))
         for mode, spw in BUILDERS:
             obs = _lib.ObsParams(mode, S - 1, spw, 0.0, 1.0, 2.0, None)
             out[f"logits|{B}|{T}|mode{mode}|spw{spw}"] = int(lib.vit_workspace_bytes_logits(plan, ctypes.byref(obs), B, T))
@@ -63,6 +65,7 @@ def plan_sizes(lib, A, pi):
         off = np.concatenate([[0], np.cumsum(np.asarray(lens, np.int64))]).astype(np.int64)
         B, tag = len(lens), ",".join(str(n) for n in lens)
         out[f"packed|{tag}"] = int(lib.vit_workspace_bytes_packed(plan, B, int(off[-1])))
+        out[f"f64_packed|{tag}"] = int(lib.vit_workspace_bytes_f64_packed(plan, B, int(off[-1])))
         out[f"units|{B}"] = int(lib.vit_packed_bounded_units(plan, B))
         for K in SEGMENTS:
             out[f"packed_checkpointed|{tag}|{K}"] = int(lib.vit_workspace_bytes_packed_checkpointed(plan, B, off.ctypes.data, K))

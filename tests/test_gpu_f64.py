@@ -215,6 +215,42 @@ def test_backtrace_chunking(golden, dev, name):
     dec.set_option("reset", 0)
 
 
+def test_empty_chunks_and_warmups_on_the_terminal_frame(dev):
+    """The branches of the chunk scheme (bt_run_chunks) that the chunking tests above, of the packed and of the checkpointed decode do
+    not reach with their songs of hundreds of frames: 32 chunks on songs of 1, 2, 65 and 130 frames (most chunks empty, some songs
+    with fewer frames than chunks) and no warm-up (every warm-up point of a short song falls on its terminal frame).  The plan is
+    f64_ref.band_params(100, 6) as it stands (S = 100, W = 16: the W16-S100 plan of GRID, not the -inf-floor sibling of EDGE_PLANS),
+    fp32 emissions.  decode_f64 and decode_f64_checkpointed at K = 64 (three segments,
+    the last of two frames) on [4, 130, 100]; decode_f64_packed on recordings of 1, 2, 3 and 65 frames (its chunk counts come from
+    its table: one each).  States equal and log-likelihoods bit-equal to the restatement."""
+    A, pi = f64_ref.band_params(100, 6)
+    dec = ViterbiDecoder(A, pi, dev)
+    assert dec.info["group_window"] == 16 and dec.info["floor_ok"]
+    lens, plens = [1, 2, 65, 130], [1, 2, 3, 65]
+    E = synth.emissions_peaks(4, 130, 100, seed=100, device=dev)
+    ref = f64_ref.decode_f64_batch(A, pi, E.cpu().numpy(), lens)
+    pref = f64_ref.decode_f64_batch(A, pi, E[:, :65].cpu().numpy(), plens)
+    ln = torch.as_tensor(np.asarray(lens, np.int64), device=dev)
+    Ep = torch.cat([E[b, :n] for b, n in enumerate(plens)], dim=0).contiguous()
+    off = np.concatenate([[0], np.cumsum(plens)]).astype(np.int64)
+    dec.set_option("bt_chunks", 32)
+    dec.set_option("bt_warm", 0)
+    try:
+        st, ll = _decode(dec, E, lens)
+        _assert_same(st, ll, ref[0], ref[1], "decode_f64")
+        s, l = dec.decode_f64_checkpointed(E, segment_frames=64, lengths=ln)
+        torch.cuda.synchronize()
+        _assert_same(s.cpu().numpy(), l.cpu().numpy(), ref[0], ref[1], "decode_f64_checkpointed")
+        s, l = dec.decode_f64_packed(Ep, off)
+        torch.cuda.synchronize()
+        s, l = s.cpu().numpy(), l.cpu().numpy()
+        for b, n in enumerate(plens):
+            assert np.array_equal(s[off[b]:off[b + 1]], pref[0][b, :n]), ("decode_f64_packed", b)
+        assert np.array_equal(f64_ref.bits64(l), f64_ref.bits64(pref[1])), ("decode_f64_packed", l, pref[1])
+    finally:
+        dec.set_option("reset", 0)
+
+
 # ----------------------------------------------------------------------------------------------------------------------------------
 # 4. workspace and status codes, through the C ABI
 # ----------------------------------------------------------------------------------------------------------------------------------

@@ -28,10 +28,12 @@ def recorded():
 def test_every_plan_is_recorded(golden, recorded):
     assert sorted(recorded) == sorted(mk.plan_names(golden["params"]) + [mk.SCAN_ONLY])
     n = len(mk.SHAPES) * (1 + 2 * len(mk.ALGOS) + len(mk.SEGMENTS) + len(mk.BUILDERS)) + len(mk.LENGTHS) * (1 + 2 * len(mk.SEGMENTS))
+    n += len(mk.SHAPES) * (1 + len(mk.SEGMENTS)) + len(mk.LENGTHS)                   # the float64 decodes: padded, checkpointed, packed
     n += len({B for B, _ in mk.SHAPES} | {len(lens) for lens in mk.LENGTHS})          # vit_packed_bounded_units
     assert all(len(v) == n for v in recorded.values())
     # the record is not a list of zeros: every family of queries answers for some plan, and refuses for some
-    for prefix in ("bytes", "for", "checkpointed", "logits", "units", "packed", "packed_checkpointed", "packed_bounded"):
+    for prefix in ("bytes", "for", "checkpointed", "logits", "units", "packed", "packed_checkpointed", "packed_bounded", "f64", "f64_checkpointed",
+                   "f64_packed"):
         vals = [v for plan in recorded.values() for k, v in plan.items() if k.split("|")[0] == prefix]
         assert any(v > 0 for v in vals), prefix
         assert prefix == "bytes" or any(v == 0 for v in vals), prefix

@@ -1,4 +1,4 @@
-// backtrace_common.hpp -- what the back-trace kernel files (backtrace_sparse / _half / _rows / _lane .hip) share: the ONE copy of
+// backtrace_common.hpp -- what the back-trace kernel files (backtrace_sparse / _half / _rows / _lane .hip, f64.hip) share: the ONE copy of
 // the time-parallel chunk scheme of the wave-per-chunk kernels, the pieces of a frame's decision that the sparse and the lean
 // whole-row kernel have in common, the counter flush, and the host-side launch helpers.
 //
@@ -45,11 +45,32 @@ __device__ __forceinline__ int bt_row_argmax(const float* __restrict__ row, cons
     }
     return idx == 0x7fffffffu ? 0 : (int)idx;
 }
+// The same of a row of doubles (f64.hip: the d rows of its history, or of LDS); *mout = the maximum.  An overload, declared in
+// front of bt_run_chunks: the call in there is resolved where the template is defined (a pointer to double has no namespace of its own).
+template <int EPL>
+__device__ __forceinline__ int bt_row_argmax(const double* row, const int S, const int lane, double* mout = nullptr) {
+    double d[EPL];
+    double m = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        d[e] = e * 64 + lane < S ? row[e * 64 + lane] : -INFINITY;
+        m = fmax(m, d[e]);
+    }
+    m = wave_max_all_f64(m);
+    unsigned idx = 0x7fffffffu;
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+        const unsigned long long mk = __ballot(d[e] == m && e * 64 + lane < S);
+        if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
+    }
+    if (mout) *mout = m;
+    return idx == 0x7fffffffu ? 0 : (int)idx;
+}
 
 // The chunk scheme of one wave.
 //   chase(top, bottom, cur, write) -> int: decide frames top .. bottom (descending) starting from state `cur` at frame top + 1,
 //       store them if `write`; returns the state at frame `bottom`
-//   guess_row(f) -> const float*: the stored delta row of frame f, at the column of state 0
+//   guess_row(f) -> const float* (f64.hip: const double*): the stored delta row of frame f, at the column of state 0
 //   states, entry: the song's (states is the array chase() writes: no __restrict__ here, MODE 1 reads what chase() stored);
 //       last: its terminal state; Tb: its frames; Tpad: -1 is written to states[Tb .. Tpad)
 //   EVEN_GUESS: only even frames have a stored row (half history): the warm-up point is moved up to an odd frame
@@ -219,9 +240,10 @@ __device__ __forceinline__ void bt_flush_counters(int32_t* counters, const int s
 // ---------------------------------------------------------------------------------------
 // The two passes of a wave-per-chunk back-trace, nw waves per workgroup: kern0 (MODE 0) over waves0 waves if phases & 1, then --
 // unless that failed, there is one chunk per song, or !(phases & 2) -- kern1 (MODE 1) over one wave per song.
-template <typename Kern>
+// (Args: BtArgs, or F64Args of f64.hip -- a.chunks is all that is read of it)
+template <typename Kern, typename Args>
 static inline hipError_t launch_two_pass(Kern kern0, Kern kern1, const long long waves0, const long long songs, const int nw, const size_t lds,
-                                         hipStream_t st, const BtArgs& a, const int phases = 3) {
+                                         hipStream_t st, const Args& a, const int phases = 3) {
     hipError_t e = hipSuccess;
     if (phases & 1) {
         hipLaunchKernelGGL(kern0, dim3((unsigned)((waves0 + nw - 1) / nw)), dim3(nw * 64), lds, st, a);

@@ -43,6 +43,10 @@ struct Tuning {
     int wave_history = 0;      // wave form: 0 / 1 every delta row | 2 the rows of even frames only (VIT_EUNSUPPORTED where the plan does not allow it)
     int timing = 0;
 };
+// The bt_chunks / bt_warm overrides applied to a default (test hooks: they force the chunking / warm-up so that the verify-and-repair
+// pass is exercised).  cap: the most chunks per song the kernel that runs takes (kLaneMaxChunks for the lane form).
+inline int tuned_chunks(const Tuning& tn, int chunks, int cap = vit::kBtMaxChunks) { return tn.bt_chunks >= 1 && tn.bt_chunks <= cap ? tn.bt_chunks : chunks; }
+inline int tuned_warm(const Tuning& tn, int warm) { return tn.bt_warm >= 0 ? tn.bt_warm : warm; }
 
 // Forward kernel families.  The values are public: vit_forward_family returns them and FwdStamp::family stores them.
 enum Family : int {
@@ -57,6 +61,13 @@ inline hipError_t launch_family(int family, vit::WgVariant v, const vit::FwdArgs
     if (family == kFamWave) return vit::launch_wave(a, f16, st);
     return family == kFamGroup ? vit::launch_banded_variant(a, v, f16, st) : vit::launch_step_variant(a, v, f16, st);
 }
+// ... and the occupancy query of a workgroup family's variant
+inline hipError_t family_resident(int family, vit::WgVariant v, const vit::FwdArgs& a, bool f16, int* per_cu) {
+    return family == kFamGroup ? vit::banded_variant_resident(a, v, f16, per_cu) : vit::step_variant_resident(a, v, f16, per_cu);
+}
+// The packed forward kernels whose launches are sized by their occupancy (vit_plan::resident): the Packed and the PackedCkpt variant of
+// the plan's workgroup family, the Packed variant of the float64 kernel.  kResNone: nothing to ask (the wave family).
+enum ResidentKey : int { kResNone = -1, kResPacked = 0, kResPackedCkpt = 1, kResF64Packed = 2, kResKeys = 3 };
 
 // Where a state's column, the frame maximum and the copies of the extra columns sit in a history row: hist_layout(plan, family).
 struct HistLayout {
@@ -93,11 +104,9 @@ struct vit_plan {
     mutable void* pk_host = nullptr;
     mutable size_t pk_host_bytes = 0;
     mutable hipEvent_t pk_event = nullptr;
-    // workgroups per CU of the packed workgroup-form kernel [0] and of its packed-checkpoint variant [1] (vit_decode_packed_bounded, pass
-    // 1's slots), by emission type (fp32 / fp16); 0 = not asked yet (resident_per_cu)
-    mutable int resident[2][2] = {{0, 0}, {0, 0}};
-    // the same of the packed float64 forward kernel (vit_decode_f64_packed), by emission type
-    mutable int resident_f64[2] = {0, 0};
+    // workgroups per CU of the packed forward kernels, by kernel (ResidentKey) and emission type (fp32 / fp16); 0 = not asked yet
+    // (resident_per_cu)
+    mutable int resident[kResKeys][2] = {};
     ~vit_plan() {
         if (pk_event) (void)hipEventDestroy(pk_event);
         if (pk_host) (void)hipHostFree(pk_host);
@@ -227,6 +236,8 @@ int check_common(const vit_plan* plan, int64_t B, int64_t T, const void* ws) {
     if (((uintptr_t)ws & 255) != 0) return VIT_EINVAL;
     return VIT_OK;
 }
+// the segment lengths the checkpointed decodes take
+inline bool ck_segment_ok(int64_t K) { return K >= 64 && K <= (int64_t)1 << 24; }
 
 }  // namespace
 
@@ -591,25 +602,19 @@ static int backtrace_impl(const vit_plan* plan, const void* logE, int emis_dtype
         b.e_f16 = st.e_f16;
     }
     if (st.half) {
-        b.chunks = vit::sparse_backtrace_chunks(B, (int)T, plan->n_cus);
-        b.warm = vit::kBtWarmSparse;
-        if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kBtMaxChunks) b.chunks = tn.bt_chunks;
-        if (tn.bt_warm >= 0) b.warm = tn.bt_warm;
+        b.chunks = tuned_chunks(tn, vit::sparse_backtrace_chunks(B, (int)T, plan->n_cus));
+        b.warm = tuned_warm(tn, vit::kBtWarmSparse);
         return hip_status(vit::launch_backtrace_half(b, (hipStream_t)stream));
     }
     if (b.bt_form == 4) {                                             // one (song, chunk) stream per lane
         if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
-        b.warm = tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarmSparse;
-        b.chunks = vit::lane_backtrace_chunks(B, (int)T, plan->n_cus, b.warm);
-        if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kLaneMaxChunks) b.chunks = tn.bt_chunks;
+        b.warm = tuned_warm(tn, vit::kBtWarmSparse);
+        b.chunks = tuned_chunks(tn, vit::lane_backtrace_chunks(B, (int)T, plan->n_cus, b.warm), vit::kLaneMaxChunks);   // (one stream per lane: its own cap)
         return hip_status(vit::launch_backtrace_lane(b, (hipStream_t)stream));
     }
     const bool sparse = b.bt_form == 0 && vit::sparse_backtrace_applies(b);
-    b.chunks = sparse ? vit::sparse_backtrace_chunks(B, (int)T, plan->n_cus) : vit::backtrace_chunks(B, (int)T);
-    b.warm = sparse ? vit::kBtWarmSparse : vit::kBtWarm;
-    // test hooks (vit_plan_set_option): force the chunking / warm-up so that the verify-and-repair pass is exercised
-    if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kBtMaxChunks) b.chunks = tn.bt_chunks;
-    if (tn.bt_warm >= 0) b.warm = tn.bt_warm;
+    b.chunks = tuned_chunks(tn, sparse ? vit::sparse_backtrace_chunks(B, (int)T, plan->n_cus) : vit::backtrace_chunks(B, (int)T));
+    b.warm = tuned_warm(tn, sparse ? vit::kBtWarmSparse : vit::kBtWarm);
     return hip_status(vit::launch_backtrace(b, (hipStream_t)stream));
 }
 
@@ -651,6 +656,17 @@ F64Layout f64_layout(const vit_plan* p, int64_t B, int64_t T) {
     w.bytes = w.off_entry + align256((size_t)B * vit::kBtMaxChunks * sizeof(int32_t));
     return w;
 }
+// The argument checks the two padded float64 decodes start with, in this order (segment_frames: null for vit_decode_f64).
+int check_f64(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T, const void* ws, const int32_t* states,
+              const int64_t* segment_frames = nullptr) {
+    if (!states) return VIT_EINVAL;
+    const int rc = check_common(plan, B, T, ws);
+    if (rc != VIT_OK) return rc;
+    if (!logE) return VIT_EINVAL;
+    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
+    if (segment_frames && !ck_segment_ok(*segment_frames)) return VIT_EINVAL;
+    return f64_applies(plan) ? VIT_OK : VIT_EUNSUPPORTED;
+}
 // what the float64 kernels read of the plan (vit_decode_f64, vit_decode_f64_packed)
 void f64_args_from_plan(const vit_plan* plan, vit::F64Args& a) {
     a.image = plan->dev_image;
@@ -677,12 +693,8 @@ size_t vit_workspace_bytes_f64(const vit_plan* plan, int64_t B, int64_t T) {
 
 int vit_decode_f64(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T, const int64_t* lengths, void* workspace,
                    size_t workspace_bytes, int32_t* states, double* loglik, vit_stream stream) {
-    if (!states) return VIT_EINVAL;
-    int rc = check_common(plan, B, T, workspace);
+    const int rc = check_f64(plan, logE, emis_dtype, B, T, workspace, states);
     if (rc != VIT_OK) return rc;
-    if (!logE) return VIT_EINVAL;
-    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
-    if (!f64_applies(plan)) return VIT_EUNSUPPORTED;
     const F64Layout w = f64_layout(plan, B, T);
     if (workspace_bytes < w.bytes) return VIT_EWORKSPACE;
     if (B == 0) return VIT_OK;
@@ -699,15 +711,11 @@ int vit_decode_f64(const vit_plan* plan, const void* logE, int emis_dtype, int64
     a.entry = reinterpret_cast<int32_t*>(ws + w.off_entry);
     a.B = B;
     a.T = (int)T;
-    const Tuning& tn = plan->tune;
-    a.chunks = vit::backtrace_chunks(B, (int)T);
-    a.warm = vit::kBtWarm;
-    if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kBtMaxChunks) a.chunks = tn.bt_chunks;
-    if (tn.bt_warm >= 0) a.warm = tn.bt_warm;
-    VIT_TRY(vit::launch_f64_forward(a, emis_dtype == VIT_F16, (hipStream_t)stream));
-    return hip_status(vit::launch_f64_backtrace(a, (hipStream_t)stream));
+    a.chunks = tuned_chunks(plan->tune, vit::backtrace_chunks(B, (int)T));
+    a.warm = tuned_warm(plan->tune, vit::kBtWarm);
+    VIT_TRY(vit::launch_f64_forward(a, vit::F64Variant::Plain, emis_dtype == VIT_F16, (hipStream_t)stream));
+    return hip_status(vit::launch_f64_backtrace(a, vit::F64Variant::Plain, (hipStream_t)stream));
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Bounded-workspace decode.  The reference keeps T1 / T2 for ONE song (tonet/for_paper.py:1852-1853); the
@@ -746,7 +754,6 @@ int ck_family(const vit_plan* p) {
         return vit::floor_ckpt_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && (ck_sparse_applies(p, kFamGroup) || ck_lane_applies(p)) ? kFamGroup : kFamNone;
     return step_applies(p) ? kFamStep : kFamNone;
 }
-inline bool ck_segment_ok(int64_t K) { return K >= 64 && K <= (int64_t)1 << 24; }
 
 struct CkLayout {
     int64_t nseg, seg_rows;
@@ -779,14 +786,14 @@ CkLayout ck_layout(const vit_plan* p, int family, int64_t B, int64_t T, int64_t 
 // units of one launch of the packed budgeted decode.  Step plans: the lazy kernel, one wave per (sub-problem, chunk); banded plans:
 // the sparse kernel, or the lane form where the caller found that the sparse one does not serve the rows (lane_bt; b.mask set).
 hipError_t segment_backtrace(const vit_plan* plan, int family, bool lane_bt, vit::BtArgs& b, hipStream_t st) {
-    const int bt_warm = plan->tune.bt_warm;
+    const Tuning& tn = plan->tune;      // (bt_chunks is not consulted here)
     if (family == kFamStep) {
         b.chunks = vit::backtrace_chunks(b.B, b.T);
-        b.warm = bt_warm >= 0 ? bt_warm : vit::kBtWarm;
+        b.warm = tuned_warm(tn, vit::kBtWarm);
         return vit::launch_backtrace_rows_segment(b, st);
     }
     if (lane_bt) {
-        b.warm = bt_warm >= 0 ? bt_warm : vit::kBtWarmSparse;
+        b.warm = tuned_warm(tn, vit::kBtWarmSparse);
         b.chunks = vit::lane_backtrace_chunks(b.B, b.T, plan->n_cus, b.warm);
         if (b.chunks > 1) {         // the chunk flags of this segment
             const hipError_t e = hipMemsetAsync(b.mask, 0, (size_t)b.B * vit::kLaneMaskWords * sizeof(uint32_t), st);
@@ -796,7 +803,7 @@ hipError_t segment_backtrace(const vit_plan* plan, int family, bool lane_bt, vit
     }
     b.chunks = vit::sparse_backtrace_chunks(b.B, b.T, plan->n_cus);
     // KNOWN ASYMMETRY, kept: the wave family always warms up kBtWarmSparse frames and does NOT consult bt_warm; kFamGroup does
-    b.warm = family == kFamWave || bt_warm < 0 ? vit::kBtWarmSparse : bt_warm;
+    b.warm = family == kFamWave ? vit::kBtWarmSparse : tuned_warm(tn, vit::kBtWarmSparse);
     return vit::launch_backtrace_sparse(b, st);
 }
 
@@ -896,7 +903,7 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Bounded-workspace float64 decode: the scheme above with vit_decode_f64's kernels in their CK case (f64.hip).  Pass 1 keeps the d
+// Bounded-workspace float64 decode: the scheme above with vit_decode_f64's kernels in their Ckpt variant (f64.hip).  Pass 1 keeps the d
 // row in front of every segment but a song's first and the terminal state and log-likelihood; pass 2 walks the segments from the
 // last to the first: the forward kernel resumed from the checkpoint row into K + 1 rows per song, segment_prep_kernel, the
 // back-trace of the sub-problems.  The plans are vit_decode_f64's (f64_applies); bt_chunks and bt_warm are honoured per segment.
@@ -947,13 +954,8 @@ size_t vit_workspace_bytes_f64_checkpointed(const vit_plan* plan, int64_t B, int
 int vit_decode_f64_checkpointed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T, const int64_t* lengths,
                                 void* workspace, size_t workspace_bytes, int32_t* states, double* loglik, int64_t segment_frames,
                                 vit_stream stream) {
-    if (!states) return VIT_EINVAL;
-    int rc = check_common(plan, B, T, workspace);
+    const int rc = check_f64(plan, logE, emis_dtype, B, T, workspace, states, &segment_frames);
     if (rc != VIT_OK) return rc;
-    if (!logE) return VIT_EINVAL;
-    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
-    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
-    if (!f64_applies(plan)) return VIT_EUNSUPPORTED;
     const int64_t K = segment_frames > T ? T : segment_frames;
     const F64CkLayout c = f64_ck_layout(plan, B, T, K);
     if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
@@ -980,7 +982,7 @@ int vit_decode_f64_checkpointed(const vit_plan* plan, const void* logE, int emis
     a.ckpt_every = (int)K;
     a.t_begin = 0;
     a.t_end = (int)T;
-    VIT_TRY(vit::launch_f64_forward_ckpt(a, f16, st));
+    VIT_TRY(vit::launch_f64_forward(a, vit::F64Variant::Ckpt, f16, st));
 
     // ---- pass 2: segments, last to first
     int64_t* seg_len = reinterpret_cast<int64_t*>(ws + c.off_slen);
@@ -997,16 +999,15 @@ int vit_decode_f64_checkpointed(const vit_plan* plan, const void* logE, int emis
         f.t_end = (int)e0;
         f.init_rows = sgm > 0 ? reinterpret_cast<const double*>(ws + c.off_ckpt) + (size_t)(sgm - 1) * a.SD64 : nullptr;
         f.init_stride = a.hist_song_stride;
-        VIT_TRY(vit::launch_f64_forward_ckpt(f, f16, st));
+        VIT_TRY(vit::launch_f64_forward(f, vit::F64Variant::Ckpt, f16, st));
         VIT_TRY(vit::launch_segment_prep(lengths, B, (int)T, (int)s0, (int)e0, states, a.last_state, seg_len, seg_last, st));
         const int sub_T = (int)(e0 < T ? e0 - s0 + 1 : e0 - s0);           // the frame behind the segment is the sub-problem's terminal frame
         f.seg_len = seg_len;
         f.seg_last = seg_last;
         f.states = states + s0;
-        f.warm = tn.bt_warm >= 0 ? tn.bt_warm : vit::kBtWarmSparse;
-        f.chunks = f64_segment_chunks(B, sub_T, f.warm);
-        if (tn.bt_chunks >= 1 && tn.bt_chunks <= vit::kBtMaxChunks) f.chunks = tn.bt_chunks;
-        VIT_TRY(vit::launch_f64_backtrace_segment(f, st));
+        f.warm = tuned_warm(tn, vit::kBtWarmSparse);
+        f.chunks = tuned_chunks(tn, f64_segment_chunks(B, sub_T, f.warm));
+        VIT_TRY(vit::launch_f64_backtrace(f, vit::F64Variant::Ckpt, st));
     }
     return VIT_OK;
 }
@@ -1056,6 +1057,16 @@ bool offsets_ok(const int64_t* offsets, int64_t B, int64_t* tmax) {
     return true;
 }
 
+// The chunk table (vit::packed_chunk_table) of the packed back-traces that run one WAVE per chunk -- the lazy kernel over step plans,
+// the float64 kernel: about eight waves per CU (tuning), chunks no shorter than the 8 * kBtWarm frames of backtrace_chunks, at most
+// kBtMaxChunks per song, counts rounded down (no chunk shorter than that).  At most B + pk_wave_streams entries: sum of
+// max(1, T_b / cf) <= B + N / cf, cf >= N / streams.
+inline int64_t pk_wave_streams(const vit_plan* p) { return 8 * (int64_t)p->n_cus; }
+inline bool pk_wave_chunk_table(const vit_plan* p, const int64_t* offsets, int64_t B, int64_t capacity, int32_t* chunk_base, int32_t* wave_song,
+                                int64_t* largest) {
+    return vit::packed_chunk_table(offsets, B, pk_wave_streams(p), vit::kBtMaxChunks, 8 * vit::kBtWarm, false, capacity, chunk_base, wave_song, largest);
+}
+
 struct PkLayout {
     int64_t n_slots, max_waves;
     size_t off_hist, off_cnt, off_mask, off_last, off_entry, off_offsets, off_slot_begin, off_slot_songs, off_wave_song, off_chunk_base, bytes;
@@ -1084,37 +1095,41 @@ PkLayout pk_layout(const vit_plan* p, int family, int64_t B, int64_t N) {
     return k;
 }
 
-// Workgroups one CU holds of the packed workgroup-form kernel (variant Packed) or of its packed-checkpoint variant -- the occupancy
-// of that instantiation, asked of the device once per emission type and remembered in the plan.
-int resident_per_cu(const vit_plan* plan, int family, vit::WgVariant variant, const vit::FwdArgs& a, bool f16, int* per_cu) {
-    int& cached = plan->resident[variant == vit::WgVariant::PackedCkpt ? 1 : 0][f16 ? 1 : 0];
+extern "C++" {      // (two templates over the query callable: no C linkage)
+// Workgroups one CU holds of a packed forward kernel (key: which; not kResNone) -- the occupancy of that instantiation, asked of the
+// device once per emission type (query(&per_cu) -> hipError_t) and remembered in the plan.
+template <typename Query>
+int resident_per_cu(const vit_plan* plan, int key, bool f16, Query&& query, int* per_cu) {
+    int& cached = plan->resident[key][f16 ? 1 : 0];
     {
         std::lock_guard<std::mutex> g(plan->mu);
         *per_cu = cached;
     }
     if (*per_cu >= 1) return VIT_OK;
-    const hipError_t eq = family == kFamGroup ? vit::banded_variant_resident(a, variant, f16, per_cu) : vit::step_variant_resident(a, variant, f16, per_cu);
-    if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: the *_family predicates asked the same)
+    const hipError_t eq = query(per_cu);
+    if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: the predicate of the entry point asked the same)
     VIT_TRY(eq);
     if (*per_cu < 1) return VIT_EUNSUPPORTED;
     std::lock_guard<std::mutex> g(plan->mu);
     cached = *per_cu;
     return VIT_OK;
 }
-// The forward slots of a packed batch of N frames whose longest song has tmax: at most `bound`; workgroup forms (variant as in
-// resident_per_cu): one per workgroup that is resident at once; and no more than N / tmax -- a slot's load should not fall below the
-// longest song, which bounds the launch anyway (1623 songs of 7500..30000 frames: 1024 slots of ~30000 frames, one wave per SIMD,
-// instead of 1623 waves of which the longest share their SIMDs to the end).
-int pk_lower_slots(const vit_plan* plan, int family, vit::WgVariant variant, const vit::FwdArgs& a, bool f16, int64_t N, int64_t tmax, int64_t* n_slots) {
-    if (family != kFamWave) {   // the wave family takes min(pk_slots, max(1, N / tmax)) with no occupancy query
+// The forward slots of a packed batch of N frames whose longest song has tmax: at most `bound` (*n_slots on entry); workgroup forms
+// (key, query: as in resident_per_cu): one per workgroup that is resident at once; and no more than N / tmax -- a slot's load should
+// not fall below the longest song, which bounds the launch anyway (1623 songs of 7500..30000 frames: 1024 slots of ~30000 frames, one
+// wave per SIMD, instead of 1623 waves of which the longest share their SIMDs to the end).
+template <typename Query>
+int pk_lower_slots(const vit_plan* plan, int key, bool f16, Query&& query, int64_t N, int64_t tmax, int64_t* n_slots) {
+    if (key != kResNone) {      // (kResNone, the wave family: min(pk_slots, max(1, N / tmax)) with no occupancy query)
         int per_cu;
-        const int rc = resident_per_cu(plan, family, variant, a, f16, &per_cu);
+        const int rc = resident_per_cu(plan, key, f16, query, &per_cu);
         if (rc != VIT_OK) return rc;
         *n_slots = std::min<int64_t>(*n_slots, (int64_t)per_cu * plan->n_cus);
     }
     *n_slots = std::min<int64_t>(*n_slots, std::max<int64_t>(1, N / tmax));
     return VIT_OK;
 }
+}  // extern "C++"
 
 // The plan's pinned staging buffer with room for `bytes` of host tables, zeroed (the packed decodes): waits for the upload of the call
 // before, which read it; pk_upload() sends it and records the next wait.
@@ -1164,6 +1179,22 @@ void pk_fill_slots(const int64_t* offsets, int64_t B, int64_t n_slots, int32_t* 
     for (int32_t sng : order) h_slot_songs[fill[(size_t)slot_of[(size_t)sng]]++] = sng;     // a slot walks its songs longest first
 }
 
+// The tables every packed decode starts with, in the plan's pinned staging buffer (pk_stage: `bytes` of it, zeroed): the offsets at
+// its start, the forward slots at rel_slot_begin / rel_slot_songs (the tables' workspace offsets less that of the offsets).  *hb: the buffer.
+int pk_stage_common(const vit_plan* plan, size_t bytes, const int64_t* offsets, int64_t B, int64_t n_slots, size_t rel_slot_begin,
+                    size_t rel_slot_songs, uint8_t** hb) {
+    const int rc = pk_stage(plan, bytes);
+    if (rc != VIT_OK) return rc;
+    *hb = static_cast<uint8_t*>(plan->pk_host);
+    std::memcpy(*hb, offsets, (size_t)(B + 1) * sizeof(int64_t));
+    try {
+        pk_fill_slots(offsets, B, n_slots, reinterpret_cast<int32_t*>(*hb + rel_slot_begin), reinterpret_cast<int32_t*>(*hb + rel_slot_songs));
+    } catch (const std::bad_alloc&) {
+        return VIT_ENOMEM;
+    }
+    return VIT_OK;
+}
+
 // the fields of a packed forward pass that do not depend on which packed decode runs it
 void fwd_args_packed(vit::FwdArgs& a, const void* logE, int64_t B, float* loglik) {
     a.logE = logE;
@@ -1201,50 +1232,27 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     const bool f16 = emis_dtype == VIT_F16;
     vit::FwdArgs a{};
     fwd_args_from_plan(plan, a);
-    rc = pk_lower_slots(plan, family, vit::WgVariant::Packed, a, f16, N, tmax, &k.n_slots);
+    rc = pk_lower_slots(plan, family == kFamWave ? kResNone : kResPacked, f16,
+                        [&](int* n) { return family_resident(family, vit::WgVariant::Packed, a, f16, n); }, N, tmax, &k.n_slots);
     if (rc != VIT_OK) return rc;
     stamp_erase(plan, workspace);
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
 
-    // ---- host tables in the plan's pinned staging buffer (the previous call's upload must have read it)
-    rc = pk_stage(plan, k.tables_bytes);
+    // ---- host tables in the plan's pinned staging buffer (the previous call's upload must have read it): offsets, forward slots
+    // (greedy bins by frames) and the back-trace's chunk table.  Banded plans: one stream per LANE (backtrace_lane.hip) -- chunks of
+    // about (total frames / resident lanes) frames, never shorter than four warm-ups, at most kLaneMaxChunks per song, counts rounded
+    // to nearest.  Step plans, lazy back-trace: one WAVE per chunk (pk_wave_chunk_table).
+    uint8_t* hb;
+    rc = pk_stage_common(plan, k.tables_bytes, offsets, B, k.n_slots, k.off_slot_begin - k.off_offsets, k.off_slot_songs - k.off_offsets, &hb);
     if (rc != VIT_OK) return rc;
-    uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
-    int32_t* h_wave_song = reinterpret_cast<int32_t*>(hb + (k.off_wave_song - k.off_offsets));
     int32_t* h_chunk_base = reinterpret_cast<int32_t*>(hb + (k.off_chunk_base - k.off_offsets));
-    std::memcpy(hb, offsets, (size_t)(B + 1) * sizeof(int64_t));
-    int64_t max_chunks = 1;
-    try {
-        pk_fill_slots(offsets, B, k.n_slots, reinterpret_cast<int32_t*>(hb + (k.off_slot_begin - k.off_offsets)),
-                      reinterpret_cast<int32_t*>(hb + (k.off_slot_songs - k.off_offsets)));      // forward slots: greedy bins by frames
-    } catch (const std::bad_alloc&) {
-        return VIT_ENOMEM;
-    }
-    {
-        // back-trace streams (one per lane: backtrace_lane.hip): chunks of about (total frames / resident lanes) frames, never shorter
-        // than four warm-ups, at most kLaneMaxChunks per song
-        // (step plans, lazy back-trace: one WAVE per chunk -- about eight waves per CU, chunks no shorter than the 8 * kBtWarm frames
-        // of backtrace_chunks, at most kBtMaxChunks per song)
-        const bool lazy = family == kFamStep;
-        const int64_t resident = lazy ? 8 * (int64_t)plan->n_cus : 16 * 64 * (int64_t)plan->n_cus;
-        const int64_t cmax = lazy ? vit::kBtMaxChunks : vit::kLaneMaxChunks;
-        int64_t cf = (N + resident - 1) / resident;
-        cf = std::max<int64_t>(cf, lazy ? 8 * vit::kBtWarm : 4 * vit::kBtWarmSparse);
-        cf = std::max<int64_t>(cf, (tmax + cmax - 1) / cmax);
-        int64_t w = 0;
-        for (int64_t b = 0; b < B; ++b) {
-            const int64_t tb = offsets[b + 1] - offsets[b];
-            int64_t c = lazy ? tb / cf : (tb + cf / 2) / cf;      // (lazy: rounded down, no chunk shorter than cf)
-            c = c < 1 ? 1 : (c > cmax ? cmax : c);
-            h_chunk_base[b] = (int32_t)w;
-            for (int64_t q = 0; q < c; ++q) h_wave_song[w + q] = (int32_t)b;
-            w += c;
-            max_chunks = c > max_chunks ? c : max_chunks;
-        }
-        h_chunk_base[B] = (int32_t)w;
-        if (w > k.max_waves) return VIT_EINVAL;      // (cannot happen: sum of round(T_b / cf) <= B + N / cf <= B + 16 n_cus)
-    }
+    int32_t* h_wave_song = reinterpret_cast<int32_t*>(hb + (k.off_wave_song - k.off_offsets));
+    int64_t max_chunks;
+    if (!(family == kFamStep ? pk_wave_chunk_table(plan, offsets, B, k.max_waves, h_chunk_base, h_wave_song, &max_chunks)
+                             : vit::packed_chunk_table(offsets, B, 16 * 64 * (int64_t)plan->n_cus, vit::kLaneMaxChunks, 4 * vit::kBtWarmSparse, true,
+                                                       k.max_waves, h_chunk_base, h_wave_song, &max_chunks)))
+        return VIT_EINVAL;      // (cannot happen: sum of round(T_b / cf) <= B + N / cf <= B + 16 * 64 n_cus)
     const int n_waves = h_chunk_base[B];
     rc = pk_upload(plan, ws + k.off_offsets, k.tables_bytes, st);
     if (rc != VIT_OK) return rc;
@@ -1283,18 +1291,18 @@ int vit_decode_packed(const vit_plan* plan, const void* logE, int emis_dtype, in
     b.n_waves = n_waves;
     b.chunks = (int)max_chunks;
     if (family == kFamStep) {
-        b.warm = plan->tune.bt_warm >= 0 ? plan->tune.bt_warm : vit::kBtWarm;
+        b.warm = tuned_warm(plan->tune, vit::kBtWarm);
         b.bt_form = 1;
         return hip_status(vit::launch_backtrace_rows_packed(b, st));
     }
-    b.warm = plan->tune.bt_warm >= 0 ? plan->tune.bt_warm : vit::kBtWarmSparse;
+    b.warm = tuned_warm(plan->tune, vit::kBtWarmSparse);
     b.bt_form = 4;
     if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
     return hip_status(vit::launch_backtrace_lane(b, st));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Packed float64-accumulating decode: vit_decode_f64's kernels (f64.hip, their PK case) over vit_decode_packed's buffers.  A WORKGROUP
+// Packed float64-accumulating decode: vit_decode_f64's kernels (f64.hip, their Packed variant) over vit_decode_packed's buffers.  A WORKGROUP
 // per forward slot walks its songs back to back; the back-trace runs one wave per (song, chunk) over per-song chunk lists, the scheme
 // of the step plans' lazy back-trace above.  The plans served are vit_decode_f64's (f64_applies).
 namespace {
@@ -1305,13 +1313,11 @@ struct F64PkLayout {
     size_t off_last, off_entry, off_offsets, off_slot_begin, off_slot_songs, off_wave_song, off_chunk_base, off_hist, bytes;
     size_t tables_bytes;      // offsets .. chunk_base: one contiguous upload
 };
-// back-trace waves wanted at once: about eight per CU (tuning, as for the step plans of vit_decode_packed)
-inline int64_t f64_pk_resident_waves(const vit_plan* p) { return 8 * (int64_t)p->n_cus; }
 // n_slots is an upper bound here (it sizes slot_begin): the decode lowers it
 F64PkLayout f64_pk_layout(const vit_plan* p, int64_t B, int64_t N) {
     F64PkLayout k;
     k.n_slots = pk_slots(p, B);
-    k.max_waves = B + f64_pk_resident_waves(p);      // sum of max(1, T_b / cf) <= B + N / cf, cf >= N / resident waves
+    k.max_waves = B + pk_wave_streams(p);            // (pk_wave_chunk_table)
     k.off_last = 0;
     k.off_entry = k.off_last + align256((size_t)B * sizeof(int32_t));
     k.off_offsets = k.off_entry + align256((size_t)k.max_waves * sizeof(int32_t));
@@ -1323,22 +1329,6 @@ F64PkLayout f64_pk_layout(const vit_plan* p, int64_t B, int64_t N) {
     k.tables_bytes = k.off_hist - k.off_offsets;
     k.bytes = k.off_hist + (size_t)N * (size_t)vit::f64_hist_stride(p->S) * sizeof(double);
     return k;
-}
-// workgroups one CU holds of the packed float64 forward kernel: asked of the device once per emission type (as resident_per_cu)
-int f64_resident_per_cu(const vit_plan* plan, const vit::F64Args& a, bool f16, int* per_cu) {
-    int& cached = plan->resident_f64[f16 ? 1 : 0];
-    {
-        std::lock_guard<std::mutex> g(plan->mu);
-        *per_cu = cached;
-    }
-    if (*per_cu >= 1) return VIT_OK;
-    const hipError_t eq = vit::f64_forward_packed_resident(a, f16, per_cu);
-    if (eq == hipErrorInvalidConfiguration) return VIT_EUNSUPPORTED;    // (cannot happen: f64_applies asked the same)
-    VIT_TRY(eq);
-    if (*per_cu < 1) return VIT_EUNSUPPORTED;
-    std::lock_guard<std::mutex> g(plan->mu);
-    cached = *per_cu;
-    return VIT_OK;
 }
 
 }  // namespace
@@ -1363,53 +1353,23 @@ int vit_decode_f64_packed(const vit_plan* plan, const void* logE, int emis_dtype
     const bool f16 = emis_dtype == VIT_F16;
     vit::F64Args a{};
     f64_args_from_plan(plan, a);
-    {
-        // forward slots: min(B, workgroups resident at once, max(1, N / tmax)) -- a slot's load should not fall below the longest song
-        int per_cu;
-        rc = f64_resident_per_cu(plan, a, f16, &per_cu);
-        if (rc != VIT_OK) return rc;
-        k.n_slots = std::min<int64_t>(k.n_slots, (int64_t)per_cu * plan->n_cus);
-        k.n_slots = std::min<int64_t>(k.n_slots, std::max<int64_t>(1, N / tmax));
-    }
+    // forward slots: min(B, workgroups resident at once, max(1, N / tmax))
+    rc = pk_lower_slots(plan, kResF64Packed, f16, [&](int* n) { return vit::f64_forward_resident(a, vit::F64Variant::Packed, f16, n); }, N, tmax,
+                        &k.n_slots);
+    if (rc != VIT_OK) return rc;
     stamp_erase(plan, workspace);
     hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
 
-    // ---- host tables in the plan's pinned staging buffer (the previous call's upload must have read it)
-    rc = pk_stage(plan, k.tables_bytes);
+    // ---- host tables in the plan's pinned staging buffer (the previous call's upload must have read it): offsets, forward slots
+    // (greedy bins by frames), and the back-trace's chunk table: one wave per (song, chunk), the step plans' rule of vit_decode_packed
+    uint8_t* hb;
+    rc = pk_stage_common(plan, k.tables_bytes, offsets, B, k.n_slots, k.off_slot_begin - k.off_offsets, k.off_slot_songs - k.off_offsets, &hb);
     if (rc != VIT_OK) return rc;
-    uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
-    int32_t* h_wave_song = reinterpret_cast<int32_t*>(hb + (k.off_wave_song - k.off_offsets));
     int32_t* h_chunk_base = reinterpret_cast<int32_t*>(hb + (k.off_chunk_base - k.off_offsets));
-    std::memcpy(hb, offsets, (size_t)(B + 1) * sizeof(int64_t));
-    try {
-        pk_fill_slots(offsets, B, k.n_slots, reinterpret_cast<int32_t*>(hb + (k.off_slot_begin - k.off_offsets)),
-                      reinterpret_cast<int32_t*>(hb + (k.off_slot_songs - k.off_offsets)));      // greedy bins by frames
-    } catch (const std::bad_alloc&) {
-        return VIT_ENOMEM;
-    }
-    int64_t max_chunks = 1;
-    {
-        // back-trace waves, one per (song, chunk): cf = max(ceil(N / resident waves), 8 * kBtWarm, ceil(tmax / kBtMaxChunks)) frames per
-        // chunk, song b gets clamp(T_b / cf, 1, kBtMaxChunks) of them (rounded down: no chunk shorter than cf) -- the step plans' rule
-        // of vit_decode_packed
-        const int64_t resident = f64_pk_resident_waves(plan), cmax = vit::kBtMaxChunks;
-        int64_t cf = (N + resident - 1) / resident;
-        cf = std::max<int64_t>(cf, 8 * vit::kBtWarm);
-        cf = std::max<int64_t>(cf, (tmax + cmax - 1) / cmax);
-        int64_t w = 0;
-        for (int64_t b = 0; b < B; ++b) {
-            const int64_t tb = offsets[b + 1] - offsets[b];
-            int64_t c = tb / cf;
-            c = c < 1 ? 1 : (c > cmax ? cmax : c);
-            if (w + c > k.max_waves) return VIT_EINVAL;      // (cannot happen: sum of max(1, T_b / cf) <= B + N / cf <= B + resident)
-            h_chunk_base[b] = (int32_t)w;
-            for (int64_t q = 0; q < c; ++q) h_wave_song[w + q] = (int32_t)b;
-            w += c;
-            max_chunks = c > max_chunks ? c : max_chunks;
-        }
-        h_chunk_base[B] = (int32_t)w;
-    }
+    int64_t max_chunks;
+    if (!pk_wave_chunk_table(plan, offsets, B, k.max_waves, h_chunk_base, reinterpret_cast<int32_t*>(hb + (k.off_wave_song - k.off_offsets)), &max_chunks))
+        return VIT_EINVAL;      // (cannot happen: see pk_wave_chunk_table)
     const int n_waves = h_chunk_base[B];
     rc = pk_upload(plan, ws + k.off_offsets, k.tables_bytes, st);
     if (rc != VIT_OK) return rc;
@@ -1431,9 +1391,9 @@ int vit_decode_f64_packed(const vit_plan* plan, const void* logE, int emis_dtype
     a.chunk_base = reinterpret_cast<const int32_t*>(ws + k.off_chunk_base);
     a.n_waves = n_waves;
     a.chunks = (int)max_chunks;
-    a.warm = plan->tune.bt_warm >= 0 ? plan->tune.bt_warm : vit::kBtWarm;
-    VIT_TRY(vit::launch_f64_forward_packed(a, f16, st));
-    return hip_status(vit::launch_f64_backtrace_packed(a, st));
+    a.warm = tuned_warm(plan->tune, vit::kBtWarm);
+    VIT_TRY(vit::launch_f64_forward(a, vit::F64Variant::Packed, f16, st));
+    return hip_status(vit::launch_f64_backtrace(a, vit::F64Variant::Packed, st));
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1529,18 +1489,15 @@ size_t budgeted_bytes(const vit_plan* plan, int (*family_of)(const vit_plan*), i
 // staged in the plan's pinned buffer and sent to the workspace in one upload.
 int pc_stage_tables(const vit_plan* plan, const PcLayout& c, const int64_t* offsets, int64_t B, int64_t n_slots, uint8_t* ws, hipStream_t st,
                     vit::PackedCkptSchedule& sc) {
-    const int rs = pk_stage(plan, c.tables_bytes);
+    uint8_t* hb;
+    const int rs = pk_stage_common(plan, c.tables_bytes, offsets, B, n_slots, c.off_slot_begin - c.off_offsets, c.off_slot_songs - c.off_offsets, &hb);
     if (rs != VIT_OK) return rs;
-    uint8_t* hb = static_cast<uint8_t*>(plan->pk_host);
     try {
-        pk_fill_slots(offsets, B, n_slots, reinterpret_cast<int32_t*>(hb + (c.off_slot_begin - c.off_offsets)),
-                      reinterpret_cast<int32_t*>(hb + (c.off_slot_songs - c.off_offsets)));
         vit::packed_ckpt_schedule(offsets, B, c.K, c.n_units, sc);
     } catch (const std::bad_alloc&) {
         return VIT_ENOMEM;
     }
     if ((int64_t)sc.unit_song.size() != c.units) return VIT_EINVAL;      // (cannot happen: the layout counted the same segments)
-    std::memcpy(hb, offsets, (size_t)(B + 1) * sizeof(int64_t));
     std::memcpy(hb + (c.off_ckpt_base - c.off_offsets), sc.ckpt_base.data(), (size_t)(B + 1) * sizeof(int64_t));
     std::memcpy(hb + (c.off_unit_song - c.off_offsets), sc.unit_song.data(), (size_t)c.units * sizeof(int32_t));
     std::memcpy(hb + (c.off_unit_seg - c.off_offsets), sc.unit_seg.data(), (size_t)c.units * sizeof(int32_t));
@@ -1570,7 +1527,8 @@ int decode_packed_budgeted(const vit_plan* plan, int (*family_of)(const vit_plan
     vit::FwdArgs a{};
     fwd_args_from_plan(plan, a);
     int64_t n_slots = c.n_slots;                          // pass 1's slots, as vit_decode_packed chooses them (the packed-checkpoint kernels' occupancy)
-    rc = pk_lower_slots(plan, family, vit::WgVariant::PackedCkpt, a, f16, N, c.tmax, &n_slots);
+    rc = pk_lower_slots(plan, family == kFamWave ? kResNone : kResPackedCkpt, f16,
+                        [&](int* n) { return family_resident(family, vit::WgVariant::PackedCkpt, a, f16, n); }, N, c.tmax, &n_slots);
     if (rc != VIT_OK) return rc;
     stamp_erase(plan, workspace);
     vit::PackedCkptSchedule sc;

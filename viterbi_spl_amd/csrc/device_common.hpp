@@ -88,6 +88,34 @@ __device__ __forceinline__ float wave_scan_max(float x) {
 __device__ __forceinline__ float wave_max_all(float x) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_scan_max(x)), 63));
 }
+// ---- the same on doubles (f64.hip): the two halves travel through DPP moves, the max is one v_max_f64 per step
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_max_step_f64(const double x) {
+    const long long b = __double_as_longlong(x);
+    const int lo = (int)(unsigned)(b & 0xffffffffll), hi = (int)(b >> 32);
+    // a lane without a source (or in a masked row) keeps its own value: max(x, x) = x
+    const int slo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
+    const int shi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
+    const double s = __longlong_as_double(((long long)shi << 32) | (long long)(unsigned)slo);
+    return fmax(x, s);
+}
+// inclusive prefix max over lanes 0 .. lane (the row_shr / row_bcast ladder of wave_scan_max): lane 63 holds the wave's maximum
+__device__ __forceinline__ double wave_scan_max_f64(double x) {
+    x = dpp_max_step_f64<0x111, 0xf>(x);
+    x = dpp_max_step_f64<0x112, 0xf>(x);
+    x = dpp_max_step_f64<0x114, 0xf>(x);
+    x = dpp_max_step_f64<0x118, 0xf>(x);
+    x = dpp_max_step_f64<0x142, 0xa>(x);
+    x = dpp_max_step_f64<0x143, 0xc>(x);
+    return x;
+}
+__device__ __forceinline__ double readlane_f64(const double x, const int l) {
+    const long long b = __double_as_longlong(x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffll), l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ double wave_max_all_f64(const double x) { return readlane_f64(wave_scan_max_f64(x), 63); }
 // max(x[l], x[l ^ 32]) in every lane: v_permlane32_swap exchanges the upper 32 lanes of its first operand with the lower 32
 // of its second; fed two copies of x it leaves {x.lo, x.lo} and {x.hi, x.hi}
 __device__ __forceinline__ float max_other_half(float x) {

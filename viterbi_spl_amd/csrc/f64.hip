@@ -13,67 +13,18 @@
 // workgroup, one target per lane, value-only; the history keeps every d row and M_t ([B, T, SD64] doubles, state i in column i,
 // M_t in column S).
 // Back-trace (f64_backtrace_kernel): lazy_backtrace_kernel's banded case in double under the chunk scheme of backtrace_common.hpp
-// (a speculative pass per (song, chunk), a verify / repair pass per song).
-// Both kernels have a packed case (PK: vit_decode_f64_packed), described at each: a workgroup per forward slot that walks its songs
-// back to back, back-trace waves over per-song chunk lists, rows at offsets[b] of the packed buffers.
-// And a checkpointed case (CK: vit_decode_f64_checkpointed): the forward kernel as pass 1 (checkpoint rows only) or over one segment
-// resumed from a checkpoint row, the back-trace over one segment's sub-problems.
+// (bt_run_chunks: a speculative pass per (song, chunk), a verify / repair pass per song).
+// Both kernels take one F64Variant (kernels.hpp), described at each.  Packed (vit_decode_f64_packed): a workgroup per forward slot
+// that walks its songs back to back, back-trace waves over per-song chunk lists, rows at offsets[b] of the packed buffers.
+// Ckpt (vit_decode_f64_checkpointed): the forward kernel as pass 1 (checkpoint rows only) or over one segment resumed from a
+// checkpoint row, the back-trace over one segment's sub-problems.
+// The wave primitives on doubles are device_common.hpp's (wave_scan_max_f64, wave_max_all_f64), the lowest-index argmax of a d row is
+// the double overload of bt_row_argmax (backtrace_common.hpp).
 #include "backtrace_common.hpp"
 
 namespace vit {
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-// ---- wave primitives on doubles: the two halves travel through DPP moves, the max is one v_max_f64 per step
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_max_step_f64(const double x) {
-    const long long b = __double_as_longlong(x);
-    const int lo = (int)(unsigned)(b & 0xffffffffll), hi = (int)(b >> 32);
-    // a lane without a source (or in a masked row) keeps its own value: max(x, x) = x
-    const int slo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-    const int shi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    const double s = __longlong_as_double(((long long)shi << 32) | (long long)(unsigned)slo);
-    return fmax(x, s);
-}
-// inclusive prefix max over lanes 0 .. lane (the row_shr / row_bcast ladder of wave_scan_max): lane 63 holds the wave's maximum
-__device__ __forceinline__ double wave_scan_max_f64(double x) {
-    x = dpp_max_step_f64<0x111, 0xf>(x);
-    x = dpp_max_step_f64<0x112, 0xf>(x);
-    x = dpp_max_step_f64<0x114, 0xf>(x);
-    x = dpp_max_step_f64<0x118, 0xf>(x);
-    x = dpp_max_step_f64<0x142, 0xa>(x);
-    x = dpp_max_step_f64<0x143, 0xc>(x);
-    return x;
-}
-__device__ __forceinline__ double readlane_f64(const double x, const int l) {
-    const long long b = __double_as_longlong(x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffll), l);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ double wave_max_all_f64(const double x) { return readlane_f64(wave_scan_max_f64(x), 63); }
-
-// Lowest-index argmax of one d row (row[i] = d of state i; LDS or global), sources strided: lane l holds i = 64 e + l.  An all -inf
-// row resolves to index 0 like np.argmax.  Wave-uniform; *mout = the maximum.  (The double analogue of bt_row_argmax.)
-template <int EPL>
-__device__ __forceinline__ int row_argmax_f64(const double* row, const int S, const int lane, double* mout = nullptr) {
-    double d[EPL];
-    double m = -INFINITY;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        d[e] = e * 64 + lane < S ? row[e * 64 + lane] : -INFINITY;
-        m = fmax(m, d[e]);
-    }
-    m = wave_max_all_f64(m);
-    unsigned idx = 0x7fffffffu;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-        const unsigned long long mk = __ballot(d[e] == m && e * 64 + lane < S);
-        if (mk) { const unsigned c = e * 64 + __builtin_ctzll(mk); idx = c < idx ? c : idx; }
-    }
-    if (mout) *mout = m;
-    return idx == 0x7fffffffu ? 0 : (int)idx;
-}
 
 // ---------------------------------------------------------------------------------------
 // Forward kernel
@@ -100,16 +51,15 @@ struct F64Lds {
 
 constexpr int kF64Prefetch = 4;    // emission rows in flight (frames ahead)
 
-// PK: packed batch (vit_decode_f64_packed).  One workgroup per forward slot: it walks the songs slot_songs[slot_begin[sl] ..
+// Packed: packed batch (vit_decode_f64_packed).  One workgroup per forward slot: it walks the songs slot_songs[slot_begin[sl] ..
 // slot_begin[sl + 1]) back to back (the scheme of wg_cursor.inc's take_song()); the emission and history rows of song b start at row
 // offsets[b] of the packed buffers (64-bit row offsets).  The per-lane plan constants are loaded once; frame 0, the emission
 // prefetch (clamped to the song's own last row) and the terminal argmax are per song.  Between two songs stands one barrier of its
 // own, behind the terminal read: wave 0 reads d_{Tb-1} out of buffer (Tb - 1) & 1 after the song's last barrier, and without it
 // the other waves would already publish the next song's frame 0 into buffer 0 and its partial maxima into pm[0] -- the buffer
 // being read when Tb is odd (a one-frame song included).  Behind that barrier nothing of the finished song is read any more (the
-// frame loop's reads all sit before its last barrier), so one barrier is enough for every parity.  PK = false compiles to the
-// code it was before the parameter existed.
-// CK: checkpointed decode (vit_decode_f64_checkpointed), one workgroup per song, in one of two wave-uniform runtime modes.
+// frame loop's reads all sit before its last barrier), so one barrier is enough for every parity.
+// Ckpt: checkpointed decode (vit_decode_f64_checkpointed), one workgroup per song, in one of two wave-uniform runtime modes.
 //   pass 1 (ckpt_every = K > 0): every frame of the song.  Of the history only the d rows of frames mK - 1 are kept, at rows m - 1 of
 //     the song's own rows of hist (m = 1 ..; the host provides ceil(T / K) rows, so the row of frame T - 1 has a place when K divides
 //     T); every other frame skips its stores by a wave-uniform branch, M is not stored at all.  Terminal state and log-likelihood
@@ -123,10 +73,11 @@ constexpr int kF64Prefetch = 4;    // emission rows in flight (frames ahead)
 //     the segment's last row, which no frame of this launch takes, is formed behind the loop from the partial maxima of the last
 //     buffer (where the song goes on: the back-trace of the segment decides that row's frame).  No terminal.
 // Both modes share one store: the next frame to keep (`keep`) and its row (`hrow`) advance by K frames / one row in pass 1 and by
-// one frame / one row in a segment.  CK = false compiles to the code it was before the parameter existed.
-template <int W, int NWT, typename ET, bool PK = false, bool CK = false>
+// one frame / one row in a segment.
+// Plain compiles to the code it was before the variants existed (PK / CK below: the variant as two flags).
+template <int W, int NWT, typename ET, F64Variant V = F64Variant::Plain>
 __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) {
-    static_assert(!(PK && CK), "the packed and the checkpointed case are separate kernels");
+    constexpr bool PK = V == F64Variant::Packed, CK = V == F64Variant::Ckpt;
     using L = F64Lds<W, NWT>;
     constexpr int NP = L::NP, DC = L::DC, BUF = L::BUF, WR = L::WR, PF = kF64Prefetch;
     constexpr int CH = (W > 64 && NWT > 8) ? 8 : 16;        // window sources in flight
@@ -332,7 +283,7 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
             // (PK: left alone the compiler hoists the argmax's NWT row masks out of the song loop and keeps them in scalar registers
             // through the frames: twelve waves at W = 128 then spill)
             if constexpr (PK) asm volatile("" : "+v"(ln));
-            const int s = row_argmax_f64<NWT>(dls + fb * BUF, S, ln, &best);
+            const int s = bt_row_argmax<NWT>(dls + fb * BUF, S, ln, &best);
             if (lane == 0) {
                 a.last_state[song] = s;
                 if (a.loglik) a.loglik[song] = best;
@@ -358,20 +309,20 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
 //     plan's per-target candidate row (tabX[j]: window, extra columns, row constant), read from the image (L2-resident);
 //   * fl64(M_t + c_j) bounds every row-constant candidate: below the candidates' maximum, the lowest matching source wins;
 //   * otherwise all S candidates are evaluated and the lowest index attaining the maximum wins (an all -inf frame: state 0).
-// PK: packed batch (vit_decode_f64_packed; lazy_backtrace_kernel's PK case).  MODE 0 runs one wave per entry of wave_song; song b owns
+// Packed: packed batch (vit_decode_f64_packed; lazy_backtrace_kernel's PK case).  MODE 0 runs one wave per entry of wave_song; song b owns
 // the waves and the chunk entries chunk_base[b] .. chunk_base[b + 1] - 1, so its chunk count grows with its length; MODE 1 one wave
 // per song over that song's own chunk count.  Its history rows and states sit at row offsets[b] of the packed buffers and there are
-// no frames past its end to fill.  PK = false compiles to the code it was before the parameter existed.
-// CK: one segment of a checkpointed decode (vit_decode_f64_checkpointed).  Song b is a sub-problem of seg_len[b] frames (0: the song
+// no frames past its end to fill.
+// Ckpt: one segment of a checkpointed decode (vit_decode_f64_checkpointed).  Song b is a sub-problem of seg_len[b] frames (0: the song
 // ended before the segment; its waves leave) whose last frame already has its state, seg_last[b]; its rows start at
 // hist_song_stride * b and its states at states + b * T, a.states being advanced to the segment's first frame.  Nothing is filled
-// past a song's end: the host fills the whole buffer once.  CK = false compiles to the code it was before the parameter existed.
+// past a song's end: the host fills the whole buffer once.
 constexpr int kF64BtWaves = 4;
 constexpr int kF64BtSlots = 3;     // candidate slots per lane: W + kMaxExtras <= 192
 
-template <int NWT, int MODE, bool PK = false, bool CK = false>
+template <int NWT, int MODE, F64Variant V = F64Variant::Plain>
 __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args a) {
-    static_assert(!(PK && CK), "the packed and the checkpointed case are separate kernels");
+    constexpr bool PK = V == F64Variant::Packed, CK = V == F64Variant::Ckpt;
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int EPL = NWT, NP = NWT * 64, KC = kF64BtSlots;
     const int S = a.S, SD = a.SD64, T = a.T, W = a.W, nx = a.n_extras;
@@ -514,43 +465,9 @@ __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args
         return cur;
     };
 
-    // ---- the chunk scheme (bt_run_chunks of backtrace_common.hpp, with the guess taken from a row of doubles)
-    const int Lf = Tb - 1;
-    if (MODE == 0) {
-        const int last = __builtin_amdgcn_readfirstlane(CK ? a.seg_last[song] : a.last_state[song]);
-        int lo_c, hi_c;
-        bt_chunk_bounds(Lf, chunk, C, lo_c, hi_c);
-        if (chunk == C - 1) {
-            if constexpr (!PK && !CK)
-                for (int t = Tb + lane; t < T; t += 64) states[t] = -1;
-            if (lane == 0) states[Tb - 1] = last;
-        }
-        int top = hi_c - 1 + a.warm;
-        int cur;
-        if (chunk == C - 1 || top >= Lf - 1) {
-            top = Lf - 1;
-            cur = last;
-        } else {
-            cur = row_argmax_f64<EPL>(hist + (size_t)(top + 1) * SD, S, lane);   // guess: lowest-index argmax of d row top + 1
-        }
-        if (hi_c <= lo_c) {                               // empty chunk (very short song)
-            if (lane == 0) entry[chunk] = cur;
-            return;
-        }
-        cur = chase(top, hi_c, cur, false);               // warm-up: frames top .. hi_c, nothing written
-        if (lane == 0) entry[chunk] = cur;                // state this chunk assumed at frame hi_c
-        chase(hi_c - 1, lo_c, cur, true);
-    } else {
-        int truth = -1;                                   // verified state at frame hi_c of the chunk being checked
-        for (int c = C - 2; c >= 0; --c) {
-            int lo_c, hi_c;
-            bt_chunk_bounds(Lf, c, C, lo_c, hi_c);
-            if (truth < 0) truth = __builtin_amdgcn_readfirstlane(states[hi_c]);
-            const int assumed = __builtin_amdgcn_readfirstlane(entry[c]);
-            if (hi_c > lo_c && assumed != truth) truth = chase(hi_c - 1, lo_c, truth, true);   // re-chase from the true state; ends at frame lo_c
-            else truth = -1;                              // chunk c stands: its frame lo_c is already in `states`
-        }
-    }
+    // (the variant only decides which pointers and limits the chunk scheme gets: Plain alone has frames past a song's end to fill)
+    bt_run_chunks<MODE, EPL>(chase, [&](const int f) { return hist + (size_t)f * SD; }, states, entry,
+                             MODE == 0 ? (CK ? a.seg_last[song] : a.last_state[song]) : 0, Tb, PK || CK ? Tb : T, chunk, C, a.warm, S, lane);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -581,101 +498,80 @@ static hipError_t f64_dispatch_waves(int S, F&& f) {
     }
 }
 
-hipError_t launch_f64_forward(const F64Args& a, bool f16, hipStream_t st) {
-    if (a.B < 1 || a.T < 1 || a.W > a.S) return hipErrorInvalidValue;
-    return f64_dispatch_width(a.W, [&](auto w) {
-        return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
-            constexpr int W = decltype(w)::value, NWT = decltype(n)::value;
-            constexpr size_t lds = F64Lds<W, NWT>::bytes();
-            if (f16) hipLaunchKernelGGL((f64_floor_forward_kernel<W, NWT, __half>), dim3((unsigned)a.B), dim3(NWT * 64), lds, st, a);
-            else hipLaunchKernelGGL((f64_floor_forward_kernel<W, NWT, float>), dim3((unsigned)a.B), dim3(NWT * 64), lds, st, a);
-            return hipGetLastError();
-        });
-    });
+// what a launch of variant v needs of F64Args (the sibling of wg_variant_args_ok); bt: the back-trace's launch
+static bool f64_variant_args_ok(const F64Args& a, F64Variant v, bool bt) {
+    if (a.B < 1) return false;
+    if (bt ? a.chunks < 1 || a.chunks > kBtMaxChunks || a.W + kMaxExtras > 64 * kF64BtSlots : a.W > a.S) return false;
+    switch (v) {
+        case F64Variant::Plain: return bt || a.T >= 1;
+        case F64Variant::Packed:
+            if (!a.offsets) return false;
+            return bt ? a.wave_song && a.chunk_base && a.n_waves >= 1 : a.slot_begin && a.slot_songs && a.n_slots >= 1;
+        case F64Variant::Ckpt:
+            if (a.offsets) return false;
+            if (bt) return a.seg_len && a.seg_last;
+            // pass 1 (a.ckpt_every > 0, from frame 0) or one segment (resumed from a.init_rows where a.t_begin > 0)
+            return a.T >= 1 && a.t_begin >= 0 && a.t_end <= a.T && a.t_begin < a.t_end && (a.t_begin <= 0 || a.init_rows) &&
+                   (a.ckpt_every <= 0 || a.t_begin <= 0) && a.ckpt_every >= 0;
+    }
+    return false;
 }
 
-// pass 1 (a.ckpt_every > 0, from frame 0) or one segment (resumed from a.init_rows where a.t_begin > 0) of a checkpointed decode
-hipError_t launch_f64_forward_ckpt(const F64Args& a, bool f16, hipStream_t st) {
-    if (a.B < 1 || a.T < 1 || a.W > a.S || a.offsets || a.t_begin < 0 || a.t_end > a.T || a.t_begin >= a.t_end || (a.t_begin > 0 && !a.init_rows) ||
-        (a.ckpt_every > 0 && a.t_begin > 0) || a.ckpt_every < 0)
-        return hipErrorInvalidValue;
-    return f64_dispatch_width(a.W, [&](auto w) {
-        return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
-            constexpr int W = decltype(w)::value, NWT = decltype(n)::value;
-            constexpr size_t lds = F64Lds<W, NWT>::bytes();
-            if (f16) hipLaunchKernelGGL((f64_floor_forward_kernel<W, NWT, __half, false, true>), dim3((unsigned)a.B), dim3(NWT * 64), lds, st, a);
-            else hipLaunchKernelGGL((f64_floor_forward_kernel<W, NWT, float, false, true>), dim3((unsigned)a.B), dim3(NWT * 64), lds, st, a);
-            return hipGetLastError();
-        });
-    });
-}
-
-// the packed forward instantiation of the plan: launched over a.n_slots workgroups, or (per_cu set) asked how many of its workgroups
-// one compute unit holds at once (the occupancy query at its LDS size)
-static hipError_t f64_forward_packed(const F64Args& a, bool f16, hipStream_t st, int* per_cu) {
-    if (a.W > a.S) return hipErrorInvalidValue;
+// The forward instantiation of the plan for variant V: launched over one workgroup per song (Packed: per slot), or (per_cu set) asked
+// how many of its workgroups one compute unit holds at once (the occupancy query at its LDS size)
+template <F64Variant V>
+static hipError_t f64_forward_v(const F64Args& a, bool f16, hipStream_t st, int* per_cu) {
     return f64_dispatch_width(a.W, [&](auto w) {
         return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
             constexpr int W = decltype(w)::value, NWT = decltype(n)::value;
             constexpr size_t lds = F64Lds<W, NWT>::bytes();
             auto go = [&](auto kern) -> hipError_t {
                 if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, NWT * 64, lds);
-                hipLaunchKernelGGL(kern, dim3((unsigned)a.n_slots), dim3(NWT * 64), lds, st, a);
+                hipLaunchKernelGGL(kern, dim3((unsigned)(V == F64Variant::Packed ? a.n_slots : a.B)), dim3(NWT * 64), lds, st, a);
                 return hipGetLastError();
             };
-            return f16 ? go(f64_floor_forward_kernel<W, NWT, __half, true>) : go(f64_floor_forward_kernel<W, NWT, float, true>);
+            return f16 ? go(f64_floor_forward_kernel<W, NWT, __half, V>) : go(f64_floor_forward_kernel<W, NWT, float, V>);
         });
     });
 }
-hipError_t launch_f64_forward_packed(const F64Args& a, bool f16, hipStream_t st) {
-    if (a.B < 1 || !a.offsets || !a.slot_begin || !a.slot_songs || a.n_slots < 1) return hipErrorInvalidValue;
-    return f64_forward_packed(a, f16, st, nullptr);
-}
-hipError_t f64_forward_packed_resident(const F64Args& a, bool f16, int* per_cu) { return f64_forward_packed(a, f16, nullptr, per_cu); }
-
-hipError_t launch_f64_backtrace(const F64Args& a, hipStream_t st) {
-    if (a.B < 1 || a.chunks < 1 || a.chunks > kBtMaxChunks || a.W + kMaxExtras > 64 * kF64BtSlots) return hipErrorInvalidValue;
-    return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
-        constexpr int NWT = decltype(n)::value;
-        constexpr size_t lds = sizeof(double) * kF64BtWaves * NWT * 64;
-        const long long waves0 = (long long)a.B * a.chunks;
-        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 0>), dim3((unsigned)((waves0 + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess || a.chunks <= 1) return e;
-        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 1>), dim3((unsigned)((a.B + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
-        return hipGetLastError();
-    });
+static hipError_t f64_forward(const F64Args& a, F64Variant v, bool f16, hipStream_t st, int* per_cu) {
+    switch (v) {
+        case F64Variant::Plain: return f64_forward_v<F64Variant::Plain>(a, f16, st, per_cu);
+        case F64Variant::Packed: return f64_forward_v<F64Variant::Packed>(a, f16, st, per_cu);
+        case F64Variant::Ckpt: return f64_forward_v<F64Variant::Ckpt>(a, f16, st, per_cu);
+    }
+    return hipErrorInvalidValue;
 }
 
-// the sub-problems of one segment: a.chunks chunks each, whatever their lengths (an empty chunk stands by itself)
-hipError_t launch_f64_backtrace_segment(const F64Args& a, hipStream_t st) {
-    if (a.B < 1 || !a.seg_len || !a.seg_last || a.offsets || a.chunks < 1 || a.chunks > kBtMaxChunks || a.W + kMaxExtras > 64 * kF64BtSlots)
-        return hipErrorInvalidValue;
-    return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
-        constexpr int NWT = decltype(n)::value;
-        constexpr size_t lds = sizeof(double) * kF64BtWaves * NWT * 64;
-        const long long waves0 = (long long)a.B * a.chunks;
-        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 0, false, true>), dim3((unsigned)((waves0 + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess || a.chunks <= 1) return e;
-        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 1, false, true>), dim3((unsigned)((a.B + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
-        return hipGetLastError();
-    });
+hipError_t launch_f64_forward(const F64Args& a, F64Variant v, bool f16, hipStream_t st) {
+    if (!f64_variant_args_ok(a, v, false)) return hipErrorInvalidValue;
+    return f64_forward(a, v, f16, st, nullptr);
 }
 
-hipError_t launch_f64_backtrace_packed(const F64Args& a, hipStream_t st) {
-    if (a.B < 1 || !a.offsets || !a.wave_song || !a.chunk_base || a.n_waves < 1 || a.chunks < 1 || a.chunks > kBtMaxChunks ||
-        a.W + kMaxExtras > 64 * kF64BtSlots)
-        return hipErrorInvalidValue;
+hipError_t f64_forward_resident(const F64Args& a, F64Variant v, bool f16, int* per_cu) {
+    if (v != F64Variant::Packed || a.W > a.S) return hipErrorInvalidValue;   // (the one variant whose launch is sized by it)
+    return f64_forward(a, v, f16, nullptr, per_cu);
+}
+
+// The two passes (launch_two_pass): one wave per (song, chunk) -- Packed: per entry of wave_song, a.chunks the largest chunk count of
+// any song; Ckpt: a.chunks chunks per sub-problem whatever its length, an empty chunk stands by itself -- then one wave per song.
+template <F64Variant V>
+static hipError_t f64_backtrace_v(const F64Args& a, hipStream_t st) {
     return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
         constexpr int NWT = decltype(n)::value;
-        constexpr size_t lds = sizeof(double) * kF64BtWaves * NWT * 64;
-        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 0, true>), dim3((unsigned)((a.n_waves + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess || a.chunks <= 1) return e;      // (a.chunks: the largest chunk count of any song)
-        hipLaunchKernelGGL((f64_backtrace_kernel<NWT, 1, true>), dim3((unsigned)((a.B + kF64BtWaves - 1) / kF64BtWaves)), dim3(kF64BtWaves * 64), lds, st, a);
-        return hipGetLastError();
+        const long long waves0 = V == F64Variant::Packed ? (long long)a.n_waves : (long long)a.B * a.chunks;
+        return launch_two_pass(f64_backtrace_kernel<NWT, 0, V>, f64_backtrace_kernel<NWT, 1, V>, waves0, a.B, kF64BtWaves,
+                               sizeof(double) * kF64BtWaves * NWT * 64, st, a);
     });
+}
+hipError_t launch_f64_backtrace(const F64Args& a, F64Variant v, hipStream_t st) {
+    if (!f64_variant_args_ok(a, v, true)) return hipErrorInvalidValue;
+    switch (v) {
+        case F64Variant::Plain: return f64_backtrace_v<F64Variant::Plain>(a, st);
+        case F64Variant::Packed: return f64_backtrace_v<F64Variant::Packed>(a, st);
+        case F64Variant::Ckpt: return f64_backtrace_v<F64Variant::Ckpt>(a, st);
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace vit

@@ -2,7 +2,11 @@
 // backtrace_rows / _sparse / _half / _lane .hip; those four share backtrace_common.hpp: the chunk scheme, the pieces of a decision and
 // the launch helpers).  The two workgroup forward kernels that have variants -- banded_floor_forward_kernel (banded.hip, banded_pc.hip)
 // and step4s_forward_kernel (step.hip) -- take one WgVariant, share their song / segment bookkeeping as text (wg_cursor.inc) and are
-// reached through one launch and one occupancy entry point per family (launch_*_variant, *_variant_resident).
+// reached through one launch and one occupancy entry point per family (launch_*_variant, *_variant_resident).  The float64 family
+// (f64.hip) is built the same way: both of its kernels take one F64Variant and are reached through launch_f64_forward,
+// f64_forward_resident and launch_f64_backtrace; its back-trace runs under the chunk scheme and the two-pass launch of
+// backtrace_common.hpp, and its wave maximum and row argmax on doubles stand next to the float32 ones (device_common.hpp,
+// backtrace_common.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -223,7 +227,7 @@ struct F64Args {
     const int32_t* wave_song;   // [n_waves] song of each back-trace wave (speculative pass)
     const int32_t* chunk_base;  // [B+1] first wave / chunk entry of each song; chunks = the largest chunk count of any song
     int n_waves;
-    // checkpointed decode (vit_decode_f64_checkpointed; the CK case of both kernels).  Forward: ckpt_every = K > 0 is pass 1 -- every
+    // checkpointed decode (vit_decode_f64_checkpointed; the Ckpt variant of both kernels).  Forward: ckpt_every = K > 0 is pass 1 -- every
     // frame of the song, the d row of frame mK - 1 kept at row m - 1 of the song's rows of hist, nothing else stored but the terminal
     // state and log-likelihood; ckpt_every = 0 is one segment -- frames t_begin .. min(length, t_end) - 1, resumed from
     // init_rows[song] = d_{t_begin - 1} where t_begin > 0, row t stored at t - t_begin (and M of frame t_begin - 1 in the row in
@@ -236,16 +240,18 @@ struct F64Args {
     const int64_t* seg_len;     // [B]
     const int32_t* seg_last;    // [B]
 };
-hipError_t launch_f64_forward(const F64Args& a, bool f16, hipStream_t st);
-hipError_t launch_f64_backtrace(const F64Args& a, hipStream_t st);
-// the CK instantiations: pass 1 or one segment of the forward kernel; the back-trace of one segment's sub-problems
-hipError_t launch_f64_forward_ckpt(const F64Args& a, bool f16, hipStream_t st);
-hipError_t launch_f64_backtrace_segment(const F64Args& a, hipStream_t st);
-// the same over a packed batch, and the workgroups of the packed forward instantiation one compute unit holds at once (as
-// banded_variant_resident)
-hipError_t launch_f64_forward_packed(const F64Args& a, bool f16, hipStream_t st);
-hipError_t launch_f64_backtrace_packed(const F64Args& a, hipStream_t st);
-hipError_t f64_forward_packed_resident(const F64Args& a, bool f16, int* per_cu);
+// What a workgroup of f64_floor_forward_kernel decodes and what the waves of f64_backtrace_kernel walk (described at the kernels):
+//   Plain   a song each, every row kept; a.chunks chunks per song                                   (vit_decode_f64)
+//   Packed  forward: the songs of a slot (a.n_slots workgroups); back-trace: one wave per entry of
+//           a.wave_song, rows at offsets[song]                                                      (vit_decode_f64_packed)
+//   Ckpt    forward: pass 1 (a.ckpt_every > 0) or one segment (a.t_begin / a.t_end, resumed from
+//           a.init_rows); back-trace: the sub-problems a.seg_len / a.seg_last of one segment         (vit_decode_f64_checkpointed)
+// f64_forward_resident: workgroups of the forward instantiation one compute unit holds at once (Packed, whose launch is sized by it;
+// hipErrorInvalidValue for the others, as *_variant_resident).
+enum class F64Variant { Plain, Packed, Ckpt };
+hipError_t launch_f64_forward(const F64Args& a, F64Variant v, bool f16, hipStream_t st);
+hipError_t f64_forward_resident(const F64Args& a, F64Variant v, bool f16, int* per_cu);
+hipError_t launch_f64_backtrace(const F64Args& a, F64Variant v, hipStream_t st);
 hipError_t launch_dense(const FwdArgs& a, int songs_per_group, bool f16, hipStream_t st);
 hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st);
 hipError_t launch_banded(const FwdArgs& a, bool f16, hipStream_t st);

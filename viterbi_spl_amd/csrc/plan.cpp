@@ -379,4 +379,27 @@ void packed_ckpt_schedule(const int64_t* offsets, int64_t B, int64_t K, int64_t 
     }
 }
 
+bool packed_chunk_table(const int64_t* offsets, int64_t B, int64_t streams, int64_t max_chunks, int64_t min_frames, bool round_nearest,
+                        int64_t capacity, int32_t* chunk_base, int32_t* wave_song, int64_t* largest) {
+    int64_t tmax = 1;
+    for (int64_t b = 0; b < B; ++b) tmax = std::max(tmax, offsets[b + 1] - offsets[b]);
+    int64_t cf = (offsets[B] + streams - 1) / streams;
+    cf = std::max(cf, min_frames);
+    cf = std::max(cf, (tmax + max_chunks - 1) / max_chunks);
+    int64_t w = 0;
+    *largest = 1;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t tb = offsets[b + 1] - offsets[b];
+        int64_t c = round_nearest ? (tb + cf / 2) / cf : tb / cf;
+        c = c < 1 ? 1 : (c > max_chunks ? max_chunks : c);
+        if (w + c > capacity) return false;
+        chunk_base[b] = (int32_t)w;
+        for (int64_t q = 0; q < c; ++q) wave_song[w + q] = (int32_t)b;
+        w += c;
+        *largest = std::max(*largest, c);
+    }
+    chunk_base[B] = (int32_t)w;
+    return true;
+}
+
 }  // namespace vit

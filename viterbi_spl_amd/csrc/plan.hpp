@@ -180,6 +180,15 @@ struct PackedCkptSchedule {
 int64_t packed_ckpt_units(const int64_t* offsets, int64_t B, int64_t K);
 void packed_ckpt_schedule(const int64_t* offsets, int64_t B, int64_t K, int64_t max_units, PackedCkptSchedule& out);
 
+// Per-song chunk table of a packed back-trace (vit_decode_packed, vit_decode_f64_packed): song b is walked in
+//   clamp(T_b / cf rounded down, or to nearest with round_nearest, 1, max_chunks)
+// chunks of about cf = max(ceil(total frames / streams), min_frames, ceil(longest song / max_chunks)) frames -- `streams` (song, chunk)
+// streams wanted at once, no chunk much shorter than min_frames, no song with more than max_chunks.  chunk_base[B + 1]: the first
+// stream / chunk entry of each song; wave_song[chunk_base[b] .. chunk_base[b + 1]) = b; *largest: the largest per-song count.
+// false, with nothing written at or past wave_song[capacity], when the table needs more than `capacity` entries.
+bool packed_chunk_table(const int64_t* offsets, int64_t B, int64_t streams, int64_t max_chunks, int64_t min_frames, bool round_nearest,
+                        int64_t capacity, int32_t* chunk_base, int32_t* wave_song, int64_t* largest);
+
 ImageLayout make_layout(int S, const BandedPlan& bp);
 void fill_image(const float* logA_T, const float* log_pi, const BandedPlan& bp,
                 const ImageLayout& L, uint8_t* image);

@@ -110,4 +110,14 @@ long long vph_packed_ckpt_schedule(const long long* offsets, long long B, long l
     return nl;
 }
 
+// Chunk table of a packed back-trace (vit::packed_chunk_table), for the CPU tests: 1 and *largest, or 0 when `capacity` is exceeded.
+int vph_packed_chunk_table(const long long* offsets, long long B, long long streams, long long max_chunks, long long min_frames, int round_nearest,
+                           long long capacity, int* chunk_base, int* wave_song, long long* largest) {
+    std::vector<int64_t> off(offsets, offsets + B + 1);
+    int64_t big = 0;
+    const bool ok = vit::packed_chunk_table(off.data(), B, streams, max_chunks, min_frames, round_nearest != 0, capacity, chunk_base, wave_song, &big);
+    *largest = big;
+    return ok ? 1 : 0;
+}
+
 }  // extern "C"

@@ -172,12 +172,7 @@ class ViterbiDecoder:
             raise TypeError("emission_logits must be a torch tensor on the GPU")
         if logE.device != self.device:
             raise ValueError(f"emission_logits is on {logE.device}, decoder is on {self.device}")
-        if logE.dtype == torch.float32:
-            dt = _lib.VIT_F32
-        elif logE.dtype == torch.float16:
-            dt = _lib.VIT_F16
-        else:
-            raise TypeError("emission_logits must be float32 or float16")
+        dt = self._emission_dtype(logE)
         single = logE.dim() == 2
         if single:
             logE = logE.unsqueeze(0)
@@ -186,6 +181,19 @@ class ViterbiDecoder:
         if not logE.is_contiguous():
             raise ValueError("emission_logits must be C-contiguous (the reference requires it too)")
         return logE, single, dt
+
+    @staticmethod
+    def _emission_dtype(logE: torch.Tensor) -> int:
+        """The library's storage type of an emission tensor (``VIT_F32`` / ``VIT_F16``)."""
+        if logE.dtype == torch.float32:
+            return _lib.VIT_F32
+        if logE.dtype == torch.float16:
+            return _lib.VIT_F16
+        raise TypeError("emission_logits must be float32 or float16")
+
+    def _check_lengths(self, lengths: Optional[torch.Tensor], B: int) -> None:
+        if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
+            raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
 
     # ------------------------------------------------------------------ decode
     def decode_into(self, logE: torch.Tensor, states: torch.Tensor, loglik: Optional[torch.Tensor] = None,
@@ -209,9 +217,7 @@ class ViterbiDecoder:
             raise ValueError("states must be a contiguous int32 [B,T] tensor")
         if loglik is not None and (loglik.dtype != torch.float32 or tuple(loglik.shape) != (B,)):
             raise ValueError("loglik must be float32 [B]")
-        if lengths is not None:
-            if lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device:
-                raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
+        self._check_lengths(lengths, B)
         ws_ptr, ws_bytes = self._workspace(B, T, slot, algo)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -272,15 +278,11 @@ class ViterbiDecoder:
             _lib.check(lib.vit_plan_set_option(self._plan, b"wave_history", prev), "vit_plan_set_option(wave_history)")
             if 0 < half <= max_workspace_bytes:
                 return {"mode": "half", "workspace_bytes": half}
-        if wave or group:
-            K = 8192
-            while K >= 64:
-                ck = int(lib.vit_workspace_bytes_checkpointed(self._plan, B, T, K))
-                if 0 < ck <= max_workspace_bytes:       # the largest segment that fits: fewest launches
-                    return {"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ck}
-                K //= 2
-        raise _lib.ViterbiHipError(f"no decode of a [{B}, {T}, {self.S}] batch fits a workspace of {max_workspace_bytes} bytes "
-                                   f"(the normal decode needs {need})")
+        def checkpointed(K):                                # (0: an `algo` the checkpointed decode does not stand in for)
+            return lib.vit_workspace_bytes_checkpointed(self._plan, B, T, K) if wave or group else 0
+        return self._plan_segments(need, checkpointed, max_workspace_bytes,
+                                   lambda _: f"no decode of a [{B}, {T}, {self.S}] batch fits a workspace of {max_workspace_bytes} bytes "
+                                             f"(the normal decode needs {need})")
 
     def decode(self, emission_logits: torch.Tensor, lengths: Optional[torch.Tensor] = None, algo: str = "auto",
                out_dtype: torch.dtype = torch.int64, max_workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -314,6 +316,39 @@ class ViterbiDecoder:
             states = states.to(out_dtype)
         return (states[0], loglik[0]) if single else (states, loglik)
 
+    def _decode_padded(self, entry: str, emission_logits: torch.Tensor, lengths: Optional[torch.Tensor], out_dtype: torch.dtype,
+                       loglik_dtype: torch.dtype, workspace: Optional[torch.Tensor], extra: tuple = (), own_buffer: bool = False
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_checkpointed`` / ``decode_f64_checkpointed`` / the unbudgeted ``decode_f64``: `entry` names the pair
+        ``workspace_bytes_<entry>`` (which raises for what is not served) and ``vit_decode_<entry>``, `extra` the arguments both take
+        behind the shape (the segment length).  The workspace is the caller's tensor, else one allocated for this call, which is
+        followed by a stream synchronise; `own_buffer` (``decode_f64``): else the decoder's slot-0 buffer, shared with ``decode`` and
+        grown like it, and no synchronisation."""
+        logE, single, dt = self._check_emissions(emission_logits)
+        B, T, _ = logE.shape
+        self._check_lengths(lengths, B)
+        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
+        loglik = torch.empty((B,), dtype=loglik_dtype, device=self.device)
+        if B > 0:
+            need = getattr(self, "workspace_bytes_" + entry)(B, T, *extra)
+            if own_buffer and workspace is None:
+                if self._ws is None or self._ws.numel() < need + 256:
+                    self._ws = None
+                    self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                workspace = self._ws
+            ws_keep, ws_ptr, ws_bytes, mine = self._call_workspace(need, workspace)   # (ws_keep: a buffer allocated here lives until the synchronise below)
+            with torch.cuda.device(self.device):
+                rc = getattr(_lib.load(), "vit_decode_" + entry)(self._plan, logE.data_ptr(), dt, B, T, lengths.data_ptr() if lengths is not None else None,
+                                                                 ws_ptr, ws_bytes, states.data_ptr(), loglik.data_ptr(), *extra,
+                                                                 torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(rc, "vit_decode_" + entry)
+            if mine:
+                torch.cuda.current_stream(self.device).synchronize()
+            del ws_keep
+        if out_dtype != torch.int32:
+            states = states.to(out_dtype)
+        return (states[0], loglik[0]) if single else (states, loglik)
+
     # ------------------------------------------------------------------ float64-accumulating decode
     def workspace_bytes_f64(self, B: int, T: int) -> int:
         """Workspace bytes of ``decode_f64``; raises ViterbiHipError for a plan it does not serve."""
@@ -333,19 +368,21 @@ class ViterbiDecoder:
         return need
 
     @staticmethod
-    def _plan_segments(full_need: int, size_of, budget: Optional[int], what: str = "decode") -> dict:
+    def _plan_segments(full_need: int, size_of, budget: Optional[int], no_fit=None) -> dict:
         """The budget policy of the checkpointed decodes as a pure function: ``full_need`` bytes of the whole history, ``size_of(K)``
         the bytes at segment length K (0 = not served), ``budget`` bytes or None.  ``{"mode": "full", ...}`` when the whole history
-        fits, else the largest K of 8192, 4096, ..., 64 that fits (the fewest launches); ViterbiHipError when none does."""
+        fits, else the largest K of 8192, 4096, ..., 64 that fits (the fewest launches); ViterbiHipError when none does, with the
+        caller's text ``no_fit(least)`` (``least``: the smallest need any K had, 0 when none is served)."""
         if budget is None or full_need <= budget:
             return {"mode": "full", "workspace_bytes": int(full_need)}
-        K = 8192
+        least, K = 0, 8192
         while K >= 64:
             ck = int(size_of(K))
             if 0 < ck <= budget:
                 return {"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ck}
+            least = ck if least == 0 or 0 < ck < least else least
             K //= 2
-        raise _lib.ViterbiHipError(f"no {what} fits a workspace of {budget} bytes (the whole history needs {full_need})")
+        raise _lib.ViterbiHipError(no_fit(least) if no_fit else f"no decode fits a workspace of {budget} bytes (the whole history needs {full_need})")
 
     def plan_workspace_f64(self, B: int, T: int, max_workspace_bytes: Optional[int] = None) -> dict:
         """How ``decode_f64`` decodes a [B, T, S] batch under a workspace budget (bytes; None = whatever it takes):
@@ -353,8 +390,10 @@ class ViterbiDecoder:
         "workspace_bytes": n}`` -- ``vit_decode_f64_checkpointed`` with the largest K of 8192, 4096, ..., 64 that fits.  Raises
         ViterbiHipError when nothing fits or the plan is not served.  Both modes decode the same bits."""
         lib = _lib.load()
-        return self._plan_segments(self.workspace_bytes_f64(B, T), lambda K: lib.vit_workspace_bytes_f64_checkpointed(self._plan, B, T, K),
-                                   None if max_workspace_bytes is None else int(max_workspace_bytes), f"float64 decode of a [{B}, {T}, {self.S}] batch")
+        need, budget = self.workspace_bytes_f64(B, T), None if max_workspace_bytes is None else int(max_workspace_bytes)
+        return self._plan_segments(need, lambda K: lib.vit_workspace_bytes_f64_checkpointed(self._plan, B, T, K), budget,
+                                   lambda _: f"no float64 decode of a [{B}, {T}, {self.S}] batch fits a workspace of {budget} bytes "
+                                             f"(the whole history needs {need})")
 
     def decode_f64_checkpointed(self, emission_logits: torch.Tensor, segment_frames: int = 1024, lengths: Optional[torch.Tensor] = None,
                                 out_dtype: torch.dtype = torch.int64, workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -364,25 +403,7 @@ class ViterbiDecoder:
         optional uint8 tensor of at least ``workspace_bytes_f64_checkpointed(...) + 256`` bytes to decode in (the caller then keeps it
         alive until the stream has run the decode: the call does not synchronise); without one the call allocates its own and
         synchronises the stream before it returns."""
-        lib = _lib.load()
-        logE, single, dt = self._check_emissions(emission_logits)
-        B, T, _ = logE.shape
-        if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
-            raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
-        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=torch.float64, device=self.device)
-        if B > 0:
-            ws, ws_ptr, ws_bytes, mine = self._call_workspace(self.workspace_bytes_f64_checkpointed(B, T, segment_frames), workspace)
-            with torch.cuda.device(self.device):
-                rc = lib.vit_decode_f64_checkpointed(self._plan, logE.data_ptr(), dt, B, T, lengths.data_ptr() if lengths is not None else None,
-                                                     ws_ptr, ws_bytes, states.data_ptr(), loglik.data_ptr(), int(segment_frames),
-                                                     torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_f64_checkpointed")
-            if mine:
-                torch.cuda.current_stream(self.device).synchronize()
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return (states[0], loglik[0]) if single else (states, loglik)
+        return self._decode_padded("f64_checkpointed", emission_logits, lengths, out_dtype, torch.float64, workspace, (int(segment_frames),))
 
     def decode_f64(self, emission_logits: torch.Tensor, lengths: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.int64,
                    workspace: Optional[torch.Tensor] = None, max_workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -398,11 +419,9 @@ class ViterbiDecoder:
         goes through ``decode_f64_checkpointed`` with the largest segment length that does -- the same bits -- and raises
         ``ViterbiHipError`` before anything is enqueued when none does.  Under a budget the decoder's own buffer is not used where
         it is larger than the budget: it is dropped and allocated anew at the size needed."""
-        lib = _lib.load()
-        logE, single, dt = self._check_emissions(emission_logits)
+        logE, single, _ = self._check_emissions(emission_logits)
         B, T, _ = logE.shape
-        if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
-            raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
+        self._check_lengths(lengths, B)
         if B > 0 and max_workspace_bytes is not None:
             mode = self.plan_workspace_f64(B, T, int(max_workspace_bytes))
             if mode["mode"] == "checkpointed":
@@ -411,24 +430,7 @@ class ViterbiDecoder:
                 return (st[0], ll[0]) if single else (st, ll)
             if workspace is None and self._ws is not None and self._ws.numel() > int(max_workspace_bytes) + 256:
                 self._ws = None                              # (a larger buffer kept from an earlier decode would defeat the budget)
-        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=torch.float64, device=self.device)
-        if B > 0:
-            need = self.workspace_bytes_f64(B, T)
-            if workspace is None:                            # the decoder's slot-0 buffer, shared with decode() and grown like it: no synchronisation
-                if self._ws is None or self._ws.numel() < need + 256:
-                    self._ws = None
-                    self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-                workspace = self._ws
-            _, ws_ptr, ws_bytes, _ = self._call_workspace(need, workspace)
-            with torch.cuda.device(self.device):
-                rc = lib.vit_decode_f64(self._plan, logE.data_ptr(), dt, B, T, lengths.data_ptr() if lengths is not None else None,
-                                        ws_ptr, ws_bytes, states.data_ptr(), loglik.data_ptr(),
-                                        torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_f64")
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return (states[0], loglik[0]) if single else (states, loglik)
+        return self._decode_padded("f64", emission_logits, lengths, out_dtype, torch.float64, workspace, own_buffer=True)
 
     # ------------------------------------------------------------------ the same over a packed (ragged) batch
     def workspace_bytes_f64_packed(self, B: int, total_frames: int) -> int:
@@ -528,25 +530,7 @@ class ViterbiDecoder:
         Durrieu matrix); any other plan raises ``ViterbiHipError`` before anything is enqueued.  ``workspace``: an optional uint8
         tensor of at least ``workspace_bytes_checkpointed(...) + 256`` bytes to decode in (the caller then keeps it alive until the
         stream has run the decode: the call does not synchronise)."""
-        lib = _lib.load()
-        logE, single, dt = self._check_emissions(emission_logits)
-        B, T, _ = logE.shape
-        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
-        if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
-            raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
-        if B > 0:
-            ws, ws_ptr, ws_bytes, mine = self._call_workspace(self.workspace_bytes_checkpointed(B, T, segment_frames), workspace)
-            with torch.cuda.device(self.device):
-                rc = lib.vit_decode_checkpointed(self._plan, logE.data_ptr(), dt, B, T, lengths.data_ptr() if lengths is not None else None,
-                                                 ws_ptr, ws_bytes, states.data_ptr(), loglik.data_ptr(),
-                                                 int(segment_frames), torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_checkpointed")
-            if mine:
-                torch.cuda.current_stream(self.device).synchronize()
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return (states[0], loglik[0]) if single else (states, loglik)
+        return self._decode_padded("checkpointed", emission_logits, lengths, out_dtype, torch.float32, workspace, (int(segment_frames),))
 
     # ------------------------------------------------------------------ packed (ragged) decode
     def _check_packed(self, emission_logits: torch.Tensor, offsets) -> Tuple[int, np.ndarray]:
@@ -555,12 +539,7 @@ class ViterbiDecoder:
             raise ValueError("emission_logits must be a torch tensor on the decoder's device")
         if emission_logits.dim() != 2 or emission_logits.shape[1] != self.S or not emission_logits.is_contiguous():
             raise ValueError(f"emission_logits must be a C-contiguous [sum T_b, {self.S}] tensor")
-        if emission_logits.dtype == torch.float32:
-            dt = _lib.VIT_F32
-        elif emission_logits.dtype == torch.float16:
-            dt = _lib.VIT_F16
-        else:
-            raise TypeError("emission_logits must be float32 or float16")
+        dt = self._emission_dtype(emission_logits)
         off = self._host_offsets(offsets)
         if off[-1] != emission_logits.shape[0]:
             raise ValueError("offsets must be B + 1 strictly increasing frame offsets from 0 to the number of emission rows")
@@ -686,20 +665,13 @@ class ViterbiDecoder:
         need = self.workspace_bytes_packed(B, N)
         if need == 0 and B > 0:
             raise _lib.ViterbiHipError(_NO_PACKED_DECODE)
-        if max_workspace_bytes is None or need <= max_workspace_bytes:
-            return {"mode": "full", "workspace_bytes": need}
-        least, K = 0, 8192
-        while K >= 64:
-            ck = int(size_of(self._plan, B, off.ctypes.data, K))
-            if 0 < ck <= max_workspace_bytes:           # the largest segment that fits: fewest launches
-                return {"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ck}
-            least = ck if least == 0 or 0 < ck < least else least
-            K //= 2
-        if least == 0:
-            raise _lib.ViterbiHipError(f"the packed decode of {B} recordings ({N} frames) needs a workspace of {need} bytes, the budget is "
-                                       f"{max_workspace_bytes}, and this plan has {unserved}")
-        raise _lib.ViterbiHipError(f"no packed decode of {B} recordings ({N} frames) fits a workspace of {max_workspace_bytes} bytes "
-                                   f"(the full history needs {need}, the {kind} decode at least {least})")
+        def no_fit(least):
+            if least == 0:
+                return (f"the packed decode of {B} recordings ({N} frames) needs a workspace of {need} bytes, the budget is "
+                        f"{max_workspace_bytes}, and this plan has {unserved}")
+            return (f"no packed decode of {B} recordings ({N} frames) fits a workspace of {max_workspace_bytes} bytes "
+                    f"(the full history needs {need}, the {kind} decode at least {least})")
+        return self._plan_segments(need, lambda K: size_of(self._plan, B, off.ctypes.data, K), max_workspace_bytes, no_fit)
 
     # ------------------------------------------------------------------ the same for every plan with a packed decode
     def workspace_bytes_packed_bounded(self, offsets, segment_frames: int) -> int:
@@ -781,8 +753,7 @@ class ViterbiDecoder:
         if lg.dtype != torch.float32 or lg.dim() != 3 or lg.shape[2] != cols or lg.shape[1] < 1 or not lg.is_contiguous():
             raise ValueError(f"logits must be a C-contiguous float32 [B,T,{cols}] or [T,{cols}] tensor with T >= 1")
         B, T, _ = lg.shape
-        if lengths is not None and (lengths.dtype != torch.int64 or tuple(lengths.shape) != (B,) or lengths.device != self.device):
-            raise ValueError("lengths must be an int64 [B] tensor on the decoder's device")
+        self._check_lengths(lengths, B)
         if emissions_out is not None:
             eo = emissions_out
             if (eo.dtype != torch.float32 or eo.device != self.device or not eo.is_contiguous() or
