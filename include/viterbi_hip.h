@@ -113,7 +113,8 @@ int vit_plan_query(const vit_plan *plan, vit_plan_info *info);
  *                      256 < S < 384: the six-wave grids; what 0 picks there up to 256 songs with fp32 emissions.  Elsewhere 6 runs the
  *                      one-target kernel, as 2 does for a plan without pair_ok)
  *   "backtrace_form"   0 auto | 1 generic kernel | 2 whole-row kernels (no sparse fetch) | 4 one (song, chunk) stream per LANE
- *                      instead of per wavefront (banded plans, full history; up to 256 chunks per song; VIT_EUNSUPPORTED elsewhere)
+ *                      instead of per wavefront (banded plans, full history; up to 256 chunks per song; VIT_EUNSUPPORTED elsewhere:
+ *                      from vit_decode() before anything is enqueued, from vit_backtrace() behind a vit_forward() that has run)
  *   "dense_songs"      songs per workgroup of the dense kernel (0 auto); "dense_one_thread" 1 = one thread per target;
  *                      "dense_form" 0 = matrix-resident dense kernel where it applies (64 < S <= 368), 1 = always stream the matrix
  *   "step_form"        step-structured kernel, four targets per lane: 0 bands split over two waves | 3 one wave per lane group
@@ -167,6 +168,21 @@ size_t vit_workspace_bytes_for(const vit_plan *plan, int64_t B, int64_t T, int a
  *   states    : device, [B,T] int32; frames past a song's length are set to -1
  *   loglik    : device, [B] float32 or NULL
  * Enqueues kernels on `stream` and returns; no host synchronisation.
+ *
+ * ALIGNMENT, for this and every other entry point of this header: a data pointer needs the alignment of its element type and
+ * nothing more -- logE 4 bytes (VIT_F32) or 2 bytes (VIT_F16), logits, logE_out, hf0, stats, notes and float32 loglik 4 bytes,
+ * states and bins 4 bytes, the float64 loglik 8 bytes, voiced 1 byte.  A tensor may start anywhere inside a larger buffer; rows of
+ * S = 361 or 722 elements start at every alignment anyway.  The kernels read and write these buffers with element-aligned vector
+ * types and 16- / 32-bit buffer accesses; no access is wider than its proven alignment.  The two exceptions are the buffers the
+ * library lays out itself: `workspace` and the plan's device image need a 256-byte aligned base, and a workspace pointer that is not
+ * is refused with VIT_EINVAL before anything is enqueued.
+ *
+ * OUTPUTS NEED NOT BE INITIALISED: every call that returns VIT_OK writes every states[b][t], t < len_b (the path), and -1 into every
+ * states[b][t], len_b <= t < T (the packed decodes: every entry of states, no -1), and every loglik[b]; what the buffers held before
+ * the call has no influence on the result (the verify pass of the time-parallel back-trace reads back `states`, but only entries
+ * this call has written).  Nothing is written outside [states, states + B * T), [loglik, loglik + B) and [workspace, workspace +
+ * the bytes the size query of the call returns), and what an earlier call left in the workspace has no influence either.  A call that returns VIT_EINVAL, VIT_EWORKSPACE, VIT_EUNSUPPORTED or
+ * VIT_ENOTUPLOADED has written nothing; vit_decode() included where "backtrace_form" 4 does not apply to the plan.
  */
 int vit_decode(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B, int64_t T,
                const int64_t *lengths, void *workspace, size_t workspace_bytes,

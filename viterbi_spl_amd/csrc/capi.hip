@@ -444,9 +444,14 @@ size_t vit_workspace_bytes_for(const vit_plan* plan, int64_t B, int64_t T, int a
     return ws_layout_family(plan, family, B, T).bytes;
 }
 
-int vit_forward(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T,
-                const int64_t* lengths, void* workspace, size_t workspace_bytes, float* loglik, int algo,
-                vit_stream stream) {
+static void bt_args_from_plan(const vit_plan* plan, vit::BtArgs& b);
+
+// vit_forward; then_backtrace: the call is vit_decode's, which refuses BEFORE anything is enqueued what its back-trace would refuse
+// behind the forward pass ("backtrace_form" 4 where the lane kernel does not apply) -- a refused decode writes nothing.  The check sits
+// behind every other one, so that a call with two defects is answered as it always was.
+static int forward_impl(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T,
+                        const int64_t* lengths, void* workspace, size_t workspace_bytes, float* loglik, int algo,
+                        vit_stream stream, bool then_backtrace) {
     int rc = check_common(plan, B, T, workspace);
     if (rc != VIT_OK) return rc;
     if (!logE) return VIT_EINVAL;
@@ -459,9 +464,16 @@ int vit_forward(const vit_plan* plan, const void* logE, int emis_dtype, int64_t 
     const WsLayout w = ws_layout_family(plan, family, B, T);
     if (workspace_bytes < w.bytes) return VIT_EWORKSPACE;
     if (B == 0) return VIT_OK;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    if (then_backtrace && tn.backtrace_form == 4 && !half) {      // backtrace_impl's own test, on the layout this pass would record
+        vit::BtArgs b{};
+        bt_args_from_plan(plan, b);
+        hist_layout_apply(hist_layout(plan, family), b);
+        b.mask = reinterpret_cast<uint32_t*>(ws + w.off_mask);
+        if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
+    }
     stamp_erase(plan, workspace);      // whatever this workspace held is gone once the kernel below starts; re-stamped on success
 
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
     vit::FwdArgs a{};
     fwd_args_from_plan(plan, a);
     a.logE = logE;
@@ -503,6 +515,12 @@ int vit_forward(const vit_plan* plan, const void* logE, int emis_dtype, int64_t 
     VIT_TRY(e);
     stamp_put(plan, st);
     return VIT_OK;
+}
+
+int vit_forward(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T,
+                const int64_t* lengths, void* workspace, size_t workspace_bytes, float* loglik, int algo,
+                vit_stream stream) {
+    return forward_impl(plan, logE, emis_dtype, B, T, lengths, workspace, workspace_bytes, loglik, algo, stream, false);
 }
 
 // the fields of BtArgs that depend on the plan and its options only
@@ -631,7 +649,7 @@ int vit_decode(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B
                const int64_t* lengths, void* workspace, size_t workspace_bytes, int32_t* states, float* loglik,
                int algo, vit_stream stream) {
     if (!states) return VIT_EINVAL;
-    int rc = vit_forward(plan, logE, emis_dtype, B, T, lengths, workspace, workspace_bytes, loglik, algo, stream);
+    int rc = forward_impl(plan, logE, emis_dtype, B, T, lengths, workspace, workspace_bytes, loglik, algo, stream, true);
     if (rc != VIT_OK) return rc;
     return vit_backtrace(plan, B, T, lengths, workspace, workspace_bytes, states, algo, stream);
 }
