@@ -139,6 +139,8 @@ int vit_plan_query(const vit_plan *plan, vit_plan_info *info);
  *                      entries the plan proves live for their targets (rows 0 .. 255: the trailing entries that equal the row constant or
  *                      are an extra column are covered by the frame-maximum candidate and the extra-column path; 29 of 32 on the
  *                      reference's 361-state grid, 25 on its 321-state grids) | 1 = always the whole window
+ *   "f64_units_per_cu" vit_decode_f64_packed_checkpointed(): (recording, segment) units per compute unit and launch, 1 .. 4 (0 = the forward
+ *                      instantiation's own); it changes vit_f64_packed_bounded_units() and the workspace size with it
  *   "timing"           ablation / probe mask: accepted only by a -DVIT_TIMING_HOOKS build (VIT_EUNSUPPORTED otherwise;
  *                      those bits change results)
  *   "reset"            back to the defaults
@@ -421,6 +423,49 @@ size_t vit_workspace_bytes_f64_checkpointed(const vit_plan *plan, int64_t B, int
 int vit_decode_f64_checkpointed(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B, int64_t T, const int64_t *lengths,
                                 void *workspace, size_t workspace_bytes, int32_t *states, double *loglik /* [B] or NULL */,
                                 int64_t segment_frames, vit_stream stream);
+
+/*
+ * vit_decode_f64_packed() under a workspace budget: recordings of different lengths, unpadded, with segments per recording -- the
+ * scheme of vit_decode_packed_bounded() with the float64 kernels.  Buffers are vit_decode_f64_packed()'s: logE [offsets[B], S], states
+ * [offsets[B]] (no -1 entries), offsets on the HOST.  States and log-likelihoods are bit for bit those of vit_decode_f64_packed() on
+ * the same input, hence those of vit_decode_f64() of each recording alone.
+ * Plans served: exactly those of vit_decode_f64() (one predicate behind all float64 entry points); every other plan gets size 0,
+ * vit_f64_packed_bounded_units() 0 and VIT_EUNSUPPORTED before anything is enqueued; a size > 0 means the decode launches.
+ * segment_frames = K: 64 <= K <= 2^24, a value above the longest recording acts like that length.  Recording b has
+ * n_b = ceil(T_b / K) segments.
+ * Checks, in this order (vit_decode_packed_bounded()'s): null plan / offsets / workspace, B out of range, a misaligned workspace or a
+ * bad dtype VIT_EINVAL (VIT_ENOTUPLOADED in its place); K out of range VIT_EINVAL; VIT_EUNSUPPORTED; bad offsets VIT_EINVAL; B = 0
+ * VIT_OK; null logE / states VIT_EINVAL; a workspace below the size function's answer VIT_EWORKSPACE.  A refused call writes nothing.
+ * Pass 1 is vit_decode_f64_packed()'s slot walk; it keeps the d row of the frame in front of every segment but a recording's first
+ * (sum (n_b - 1) rows, nothing else) and every recording's terminal state and log-likelihood.  Pass 2 works on (recording, segment)
+ * units, a recording's from its last segment to its first, at most one unit per recording in a launch: the forward kernel resumed
+ * from the unit's checkpoint row into the unit's own rows, then the units' back-trace, which writes states[offsets[b] + segment * K ..].
+ * vit_f64_packed_bounded_units(): the units one launch takes, n_units = min(B, u x compute units); u is a constant of the forward
+ * instantiation (window width W, target waves n = 2 / 4 / 6 / 8 / 12, the least with 64 n >= S): 1 on twelve waves, else the workgroups
+ * whose waves one compute unit's registers hold, min(4, 4 r / n) with r = 4, 3, 2 waves per SIMD at W = 16, 32, wider -- 2 at S = 361
+ * ("f64_units_per_cu" 1 .. 4 overrides it, for measurements; it changes the size).  Every unit owns its rows:
+ * u is tuning, not correctness.  Compute units: of the device the plan was uploaded to, 256 before the upload.
+ * Workspace, with K = min(segment_frames, longest recording), SD = (S + 3) / 2 * 2, U = sum n_b and r(x) = x rounded up to 256:
+ *   r(sum (n_b - 1) * SD * 8)        checkpoint rows
+ * + r(n_units * (K + 1) * SD * 8)    unit rows: one in front of the segment (it receives M of the checkpoint frame: written, never
+ *                                    read) and the K of the segment; no frame past the segment is run
+ * + r(4 B) + r(n_units * 32 * 4)     terminal states, chunk entries
+ * + r(8 n_units) + r(4 n_units) + r(8 n_units)   the units' lengths, start states and first entries in `states`
+ * + r(8 (B + 1)) + r(8 (B + 1)) + r(4 (min(B, 8 x compute units) + 1)) + r(4 B) + r(4 U) + r(4 U)
+ *                                    the tables: offsets, checkpoint bases, pass 1's slots and their recordings, the units' recordings
+ *                                    and segments in launch order -- staged in the plan's pinned buffer and sent in one upload.
+ * A launch back-traces its n units in min(32, ceil(2048 / n), (K + 1) / max(2 * warm, 64)) chunks each (at least one), warm-up 64.
+ * Like vit_decode_f64_packed() the call is not thread-safe against other packed decodes on the same plan, may wait for the previous
+ * packed call's upload, does no other host synchronisation and no device allocation; it drops the workspace's vit_forward() record and
+ * writes none.  Honoured options: "bt_chunks", "bt_warm" (per unit), "f64_units_per_cu"; every other option is ignored.
+ */
+size_t vit_workspace_bytes_f64_packed_checkpointed(const vit_plan *plan, int64_t B, const int64_t *offsets /* HOST, [B+1] */,
+                                                   int64_t segment_frames);
+int vit_decode_f64_packed_checkpointed(const vit_plan *plan, const void *logE, int emis_dtype, int64_t B,
+                                       const int64_t *offsets /* HOST, [B+1] */, void *workspace, size_t workspace_bytes,
+                                       int32_t *states /* [offsets[B]] */, double *loglik /* [B] or NULL */, int64_t segment_frames,
+                                       vit_stream stream);
+int64_t vit_f64_packed_bounded_units(const vit_plan *plan, int64_t B);
 
 /*
  * Fused logits -> path decode: what callers of the reference run is Viterbi.__call__ (tonet/for_paper.py:1817-1831) -- pitch

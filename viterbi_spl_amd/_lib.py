@@ -27,6 +27,7 @@ EXPORTS = (
     "vit_workspace_bytes_packed_bounded", "vit_decode_packed_bounded", "vit_packed_bounded_units",
     "vit_workspace_bytes_f64", "vit_decode_f64", "vit_workspace_bytes_f64_packed", "vit_decode_f64_packed",
     "vit_workspace_bytes_f64_checkpointed", "vit_decode_f64_checkpointed",
+    "vit_workspace_bytes_f64_packed_checkpointed", "vit_decode_f64_packed_checkpointed", "vit_f64_packed_bounded_units",
 )
 ABI_VERSION = 4
 
@@ -135,6 +136,12 @@ def load() -> ctypes.CDLL:
     lib.vit_workspace_bytes_f64_checkpointed.argtypes = [vp, i64, i64, i64]
     lib.vit_decode_f64_checkpointed.restype = i32
     lib.vit_decode_f64_checkpointed.argtypes = [vp, vp, i32, i64, i64, vp, vp, sz, vp, vp, i64, vp]
+    lib.vit_workspace_bytes_f64_packed_checkpointed.restype = sz
+    lib.vit_workspace_bytes_f64_packed_checkpointed.argtypes = [vp, i64, vp, i64]
+    lib.vit_decode_f64_packed_checkpointed.restype = i32
+    lib.vit_decode_f64_packed_checkpointed.argtypes = [vp, vp, i32, i64, vp, vp, sz, vp, vp, i64, vp]
+    lib.vit_f64_packed_bounded_units.restype = i64
+    lib.vit_f64_packed_bounded_units.argtypes = [vp, i64]
     lib.vit_workspace_bytes_logits.restype = sz
     lib.vit_workspace_bytes_logits.argtypes = [vp, ctypes.POINTER(ObsParams), i64, i64]
     lib.vit_decode_logits.restype = i32

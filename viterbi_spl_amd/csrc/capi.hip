@@ -41,6 +41,7 @@ struct Tuning {
     int bt_block_waves = 0;    // half back-trace: waves per workgroup, 0 = 16 | 8 | 4 (to start beside the next batch's resident forward waves)
     int floor_live_window = 0; // split floor kernel: 0 = the full waves evaluate the window entries the plan proves live | 1 = always the whole window
     int wave_history = 0;      // wave form: 0 / 1 every delta row | 2 the rows of even frames only (VIT_EUNSUPPORTED where the plan does not allow it)
+    int f64_units_per_cu = 0;  // vit_decode_f64_packed_checkpointed: units per CU and launch, 1 .. 4 (0 = the instantiation's own, f64_pckpt_units_per_cu)
     int timing = 0;
 };
 // The bt_chunks / bt_warm overrides applied to a default (test hooks: they force the chunking / warm-up so that the verify-and-repair
@@ -67,7 +68,7 @@ inline hipError_t family_resident(int family, vit::WgVariant v, const vit::FwdAr
 }
 // The packed forward kernels whose launches are sized by their occupancy (vit_plan::resident): the Packed and the PackedCkpt variant of
 // the plan's workgroup family, the Packed variant of the float64 kernel.  kResNone: nothing to ask (the wave family).
-enum ResidentKey : int { kResNone = -1, kResPacked = 0, kResPackedCkpt = 1, kResF64Packed = 2, kResKeys = 3 };
+enum ResidentKey : int { kResNone = -1, kResPacked = 0, kResPackedCkpt = 1, kResF64Packed = 2, kResF64PackedCkpt = 3, kResKeys = 4 };
 
 // Where a state's column, the frame maximum and the copies of the extra columns sit in a history row: hist_layout(plan, family).
 struct HistLayout {
@@ -352,7 +353,7 @@ static int* tuning_field(Tuning& t, const char* key) {
         {"step_form", &Tuning::step_form}, {"bt_chunks", &Tuning::bt_chunks}, {"bt_warm", &Tuning::bt_warm},
         {"win_shift", &Tuning::win_shift}, {"wave_min_batch", &Tuning::wave_min_batch}, {"wave_two", &Tuning::wave_two},
         {"bt_fast_rows", &Tuning::bt_fast_rows}, {"bt_block_waves", &Tuning::bt_block_waves}, {"wave_history", &Tuning::wave_history}, {"wave_uniform", &Tuning::wave_uniform},
-        {"floor_live_window", &Tuning::floor_live_window}, {"timing", &Tuning::timing},
+        {"floor_live_window", &Tuning::floor_live_window}, {"f64_units_per_cu", &Tuning::f64_units_per_cu}, {"timing", &Tuning::timing},
     };
     for (const auto& e : tab)
         if (std::strcmp(e.k, key) == 0) return &(t.*(e.f));
@@ -1468,20 +1469,31 @@ struct PcLayout {
     size_t off_offsets, off_ckpt_base, off_slot_begin, off_slot_songs, off_unit_song, off_unit_seg, bytes;
     size_t tables_bytes;      // offsets .. unit_seg: one contiguous upload
 };
-// false: bad offsets (offsets_ok), or more units than an int32 counts.  One layout for the three families: for a wave plan
-// vit_workspace_bytes_packed_bounded IS vit_workspace_bytes_packed_checkpointed.
-bool pc_layout(const vit_plan* p, int family, int64_t B, const int64_t* offsets, int64_t K, PcLayout& c) {
+// What the layout takes from the kernels that run: the bytes of a history row, the units of one pass-2 launch, the rows a unit holds
+// besides its K, and whether pass 1 needs a scratch row per slot behind the checkpoint rows.
+struct PcRows {
+    size_t row_bytes;
+    int64_t n_units;
+    int extra_rows;
+    bool scratch;
+};
+PcRows pc_rows(const vit_plan* p, int family, int64_t B) {
+    return {(size_t)hist_layout(p, family).SD * sizeof(float), pb_units(p, family, B), budget_form(family).extra_rows, true};
+}
+// false: bad offsets (offsets_ok), or more units than an int32 counts.  One layout for the three float32 families -- for a wave plan
+// vit_workspace_bytes_packed_bounded IS vit_workspace_bytes_packed_checkpointed -- and for the float64 decode (f64_pc_rows).
+bool pc_layout(const vit_plan* p, const PcRows& r, int64_t B, const int64_t* offsets, int64_t K, PcLayout& c) {
     if (!offsets_ok(offsets, B, &c.tmax)) return false;
     c.K = K > c.tmax ? c.tmax : K;                             // (a segment longer than every song: one segment per song)
     c.units = vit::packed_ckpt_units(offsets, B, c.K);
     if (c.units < 0 || c.units > 0x7fffffff) return false;
     c.n_ckpt = c.units - B;
-    c.n_units = pb_units(p, family, B);                        // units per launch: at most one per song
+    c.n_units = r.n_units;                                     // units per launch: at most one per song
     c.n_slots = pk_slots(p, B);                                // pass 1's slots (an upper bound, as in pk_layout): one scratch row each
-    const size_t sd = (size_t)hist_layout(p, family).SD * sizeof(float);
-    c.off_ckpt = 0;                                            // [n_ckpt] checkpoint rows, then [n_slots] scratch rows
-    c.off_seg = align256((size_t)(c.n_ckpt + c.n_slots) * sd); // [n_units][K + extra_rows] rows of the segments being walked
-    c.off_last = c.off_seg + align256((size_t)c.n_units * (size_t)(c.K + budget_form(family).extra_rows) * sd);
+    const size_t sd = r.row_bytes;
+    c.off_ckpt = 0;                                            // [n_ckpt] checkpoint rows, then (r.scratch) [n_slots] scratch rows
+    c.off_seg = align256((size_t)(c.n_ckpt + (r.scratch ? c.n_slots : 0)) * sd);   // [n_units][K + extra_rows] rows of the segments being walked
+    c.off_last = c.off_seg + align256((size_t)c.n_units * (size_t)(c.K + r.extra_rows) * sd);
     c.off_entry = c.off_last + align256((size_t)B * sizeof(int32_t));
     c.off_slen = c.off_entry + align256((size_t)c.n_units * vit::kBtMaxChunks * sizeof(int32_t));
     c.off_slast = c.off_slen + align256((size_t)c.n_units * sizeof(int64_t));
@@ -1500,7 +1512,7 @@ size_t budgeted_bytes(const vit_plan* plan, int (*family_of)(const vit_plan*), i
     if (!plan || !offsets || B < 0 || B > (int64_t)1 << 30 || !ck_segment_ok(segment_frames)) return 0;
     const int family = family_of(plan);
     PcLayout c;
-    return family != kFamNone && pc_layout(plan, family, B, offsets, segment_frames, c) ? c.bytes : 0;
+    return family != kFamNone && pc_layout(plan, pc_rows(plan, family, B), B, offsets, segment_frames, c) ? c.bytes : 0;
 }
 
 // The host tables of a budgeted packed decode -- offsets, checkpoint bases, pass 1's slots, pass 2's units in launch order (sc) --
@@ -1532,7 +1544,7 @@ int decode_packed_budgeted(const vit_plan* plan, int (*family_of)(const vit_plan
     const int family = family_of(plan);                   // (everything that can refuse the plan is asked here, before anything is enqueued)
     if (family == kFamNone) return VIT_EUNSUPPORTED;
     PcLayout c;
-    if (!pc_layout(plan, family, B, offsets, segment_frames, c)) return VIT_EINVAL;
+    if (!pc_layout(plan, pc_rows(plan, family, B), B, offsets, segment_frames, c)) return VIT_EINVAL;
     if (B == 0) return VIT_OK;
     if (!logE || !states) return VIT_EINVAL;
     if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
@@ -1631,6 +1643,109 @@ size_t vit_workspace_bytes_packed_bounded(const vit_plan* plan, int64_t B, const
 int vit_decode_packed_bounded(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
                               size_t workspace_bytes, int32_t* states, float* loglik, int64_t segment_frames, vit_stream stream) {
     return decode_packed_budgeted(plan, pb_family, logE, emis_dtype, B, offsets, workspace, workspace_bytes, states, loglik, segment_frames, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Packed float64 decode under a workspace budget: the sibling of decode_packed_budgeted with vit_decode_f64's kernels in their PackedCkpt
+// variant (f64.hip).  The scheme, the workspace layout (pc_layout over f64_pc_rows), the staged tables (pc_stage_tables) and the unit
+// prep (launch_packed_segment_prep) are the float32 driver's; what differs: rows of doubles, K + 1 rows per unit (one in front for M of
+// the checkpoint frame; M of the segment's last row is formed behind its last frame, so no frame past the segment is run), no scratch
+// row in pass 1 (what is not kept is not stored), the float64 back-trace over the units with f64_segment_chunks chunks each.
+namespace {
+
+int f64_pc_units_per_cu(const vit_plan* p) {
+    const int u = p->tune.f64_units_per_cu;
+    return u >= 1 && u <= 4 ? u : vit::f64_pckpt_units_per_cu(p->bp.W, vit::banded_waves_for(p->S));
+}
+PcRows f64_pc_rows(const vit_plan* p, int64_t B) {
+    const int64_t cap = f64_pc_units_per_cu(p) * (int64_t)p->n_cus;
+    return {(size_t)vit::f64_hist_stride(p->S) * sizeof(double), B < cap ? B : cap, 1, false};
+}
+
+}  // namespace
+
+int64_t vit_f64_packed_bounded_units(const vit_plan* plan, int64_t B) {
+    if (!plan || B < 0 || B > (int64_t)1 << 30 || !f64_applies(plan)) return 0;
+    return f64_pc_rows(plan, B).n_units;
+}
+
+size_t vit_workspace_bytes_f64_packed_checkpointed(const vit_plan* plan, int64_t B, const int64_t* offsets, int64_t segment_frames) {
+    if (!plan || !offsets || B < 0 || B > (int64_t)1 << 30 || !ck_segment_ok(segment_frames) || !f64_applies(plan)) return 0;
+    PcLayout c;
+    return pc_layout(plan, f64_pc_rows(plan, B), B, offsets, segment_frames, c) ? c.bytes : 0;
+}
+
+int vit_decode_f64_packed_checkpointed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, const int64_t* offsets, void* workspace,
+                                       size_t workspace_bytes, int32_t* states, double* loglik, int64_t segment_frames, vit_stream stream) {
+    int rc = check_packed(plan, B, offsets, workspace, emis_dtype);
+    if (rc != VIT_OK) return rc;
+    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
+    if (!f64_applies(plan)) return VIT_EUNSUPPORTED;
+    PcLayout c;
+    if (!pc_layout(plan, f64_pc_rows(plan, B), B, offsets, segment_frames, c)) return VIT_EINVAL;
+    if (B == 0) return VIT_OK;
+    if (!logE || !states) return VIT_EINVAL;
+    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
+    const int64_t N = offsets[B], K = c.K;
+    const bool f16 = emis_dtype == VIT_F16;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    vit::F64Args a{};
+    f64_args_from_plan(plan, a);
+    int64_t n_slots = c.n_slots;                          // pass 1's slots, as vit_decode_f64_packed chooses them (this variant's occupancy)
+    rc = pk_lower_slots(plan, kResF64PackedCkpt, f16, [&](int* n) { return vit::f64_forward_resident(a, vit::F64Variant::PackedCkpt, f16, n); }, N, c.tmax,
+                        &n_slots);
+    if (rc != VIT_OK) return rc;
+    stamp_erase(plan, workspace);
+    vit::PackedCkptSchedule sc;
+    rc = pc_stage_tables(plan, c, offsets, B, n_slots, ws, st, sc);
+    if (rc != VIT_OK) return rc;
+
+    // ---- pass 1: checkpoint rows + terminal state and log-likelihood, one workgroup per slot
+    a.logE = logE;
+    a.lengths = nullptr;
+    a.hist = reinterpret_cast<double*>(ws + c.off_ckpt);
+    a.last_state = reinterpret_cast<int32_t*>(ws + c.off_last);
+    a.loglik = loglik;
+    a.states = states;
+    a.entry = reinterpret_cast<int32_t*>(ws + c.off_entry);
+    a.B = B;
+    a.T = 1;                      // (unused by the packed kernels: a song's rows come from the offsets)
+    a.ckpt_every = (int)K;
+    a.offsets = reinterpret_cast<const int64_t*>(ws + c.off_offsets);
+    a.n_slots = (int)n_slots;
+    a.slot_begin = reinterpret_cast<const int32_t*>(ws + c.off_slot_begin);
+    a.slot_songs = reinterpret_cast<const int32_t*>(ws + c.off_slot_songs);
+    a.ckpt_base = reinterpret_cast<const int64_t*>(ws + c.off_ckpt_base);
+    a.unit_song = nullptr;
+    VIT_TRY(vit::launch_f64_forward(a, vit::F64Variant::PackedCkpt, f16, st));
+
+    // ---- pass 2: the launches of the schedule; every unit's back-trace starts from what the launch before it wrote
+    vit::F64Args f = a;
+    f.hist = reinterpret_cast<double*>(ws + c.off_seg) + a.SD64;          // a unit's row 0 is the second of its K + 1 rows
+    f.hist_song_stride = (K + 1) * (int64_t)a.SD64;
+    f.loglik = nullptr;
+    f.init_rows = reinterpret_cast<const double*>(ws + c.off_ckpt);
+    f.seg_len = reinterpret_cast<const int64_t*>(ws + c.off_slen);
+    f.seg_last = reinterpret_cast<const int32_t*>(ws + c.off_slast);
+    f.unit_states = reinterpret_cast<const int64_t*>(ws + c.off_sbase);
+    f.warm = tuned_warm(plan->tune, vit::kBtWarmSparse);
+    const int32_t* d_unit_song = reinterpret_cast<const int32_t*>(ws + c.off_unit_song);
+    const int32_t* d_unit_seg = reinterpret_cast<const int32_t*>(ws + c.off_unit_seg);
+    for (size_t l = 0; l + 1 < sc.launch_begin.size(); ++l) {
+        const int64_t u0 = sc.launch_begin[l], nu = sc.launch_begin[l + 1] - u0;
+        if (nu < 1 || nu > c.n_units) return VIT_EINVAL;                  // (cannot happen: the schedule takes at most n_units per launch)
+        f.B = nu;
+        f.unit_song = d_unit_song + u0;
+        f.unit_seg = d_unit_seg + u0;
+        VIT_TRY(vit::launch_f64_forward(f, vit::F64Variant::PackedCkpt, f16, st));
+        VIT_TRY(vit::launch_packed_segment_prep(a.offsets, f.unit_song, f.unit_seg, (int)nu, (int)K, states, a.last_state,
+                                                reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast),
+                                                reinterpret_cast<int64_t*>(ws + c.off_sbase), st));
+        f.chunks = tuned_chunks(plan->tune, f64_segment_chunks(nu, (int)(K + 1), f.warm));
+        VIT_TRY(vit::launch_f64_backtrace(f, vit::F64Variant::PackedCkpt, st));
+    }
+    return VIT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -17,7 +17,8 @@
 // Both kernels take one F64Variant (kernels.hpp), described at each.  Packed (vit_decode_f64_packed): a workgroup per forward slot
 // that walks its songs back to back, back-trace waves over per-song chunk lists, rows at offsets[b] of the packed buffers.
 // Ckpt (vit_decode_f64_checkpointed): the forward kernel as pass 1 (checkpoint rows only) or over one segment resumed from a
-// checkpoint row, the back-trace over one segment's sub-problems.
+// checkpoint row, the back-trace over one segment's sub-problems.  PackedCkpt (vit_decode_f64_packed_checkpointed): the two combined --
+// pass 1 as a slot walk that keeps checkpoint rows only, pass 2 over (song, segment) units.
 // The wave primitives on doubles are device_common.hpp's (wave_scan_max_f64, wave_max_all_f64), the lowest-index argmax of a d row is
 // the double overload of bt_row_argmax (backtrace_common.hpp).
 #include "backtrace_common.hpp"
@@ -74,10 +75,19 @@ constexpr int kF64Prefetch = 4;    // emission rows in flight (frames ahead)
 //     buffer (where the song goes on: the back-trace of the segment decides that row's frame).  No terminal.
 // Both modes share one store: the next frame to keep (`keep`) and its row (`hrow`) advance by K frames / one row in pass 1 and by
 // one frame / one row in a segment.
-// Plain compiles to the code it was before the variants existed (PK / CK below: the variant as two flags).
+// PackedCkpt: packed checkpointed decode (vit_decode_f64_packed_checkpointed), K = a.ckpt_every frames per segment, song b with
+// n_b = ceil(T_b / K) of them; two wave-uniform runtime modes, as WgVariant::PackedCkpt of the float32 floor kernel.
+//   pass 1 (a.unit_song null): Packed's slot walk (hand-over barrier and prefetch clamp included) storing as Ckpt's pass 1 does, but
+//     per song: the d rows of frames mK - 1, m = 1 .. n_b - 1, at rows ckpt_base[b] + m - 1 of hist.  The area holds sum (n_b - 1)
+//     rows: frame T_b - 1 of a song whose length K divides has NO row (the next song's rows, or the end of the area, stand there),
+//     so the store is bounded by t < T_b - 1 -- exactly the frames mK - 1 with m <= n_b - 1.  Terminal state and log-likelihood per song.
+//   pass 2 (a.unit_song set): workgroup u < a.B runs Ckpt's one segment for segment g = unit_seg[u] of song b = unit_song[u]: frames
+//     gK .. min(T_b, gK + K) - 1 with emission rows at offsets[b], resumed from row ckpt_base[b] + g - 1 of init_rows where g > 0,
+//     into the unit's own rows at hist + u * hist_song_stride (K + 1 rows per unit, hist at the second).
+// Plain compiles to the code it was before the variants existed (PK / CK / PC below: the variant as flags).
 template <int W, int NWT, typename ET, F64Variant V = F64Variant::Plain>
 __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) {
-    constexpr bool PK = V == F64Variant::Packed, CK = V == F64Variant::Ckpt;
+    constexpr bool PC = V == F64Variant::PackedCkpt, PK = V == F64Variant::Packed || PC, CK = V == F64Variant::Ckpt || PC;
     using L = F64Lds<W, NWT>;
     constexpr int NP = L::NP, DC = L::DC, BUF = L::BUF, WR = L::WR, PF = kF64Prefetch;
     constexpr int CH = (W > 64 && NWT > 8) ? 8 : 16;        // window sources in flight
@@ -98,12 +108,14 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
     // (CK) wave-uniform: pass 1 or a segment, whether the song goes on behind this launch's last frame, the next frame whose row
     // is kept, the frames between two kept rows, and the kept row's place.  From here on Tb counts LOCAL frames and E starts at
     // local frame 0.
-    [[maybe_unused]] const bool pass1 = CK && a.ckpt_every > 0;
-    [[maybe_unused]] const bool resumed = CK && a.t_begin > 0;
+    // (PC) pass 1 or a unit's segment (wave-uniform); the unit's segment within its song
+    [[maybe_unused]] const int ug = PC && a.unit_song ? a.unit_seg[blockIdx.x] : 0;
+    [[maybe_unused]] const bool pass1 = PC ? a.unit_song == nullptr : CK && a.ckpt_every > 0;
+    [[maybe_unused]] const bool resumed = PC ? ug > 0 : CK && a.t_begin > 0;
     [[maybe_unused]] bool goes_on = false;
     [[maybe_unused]] int keep = 0, keep_step = 1;
     [[maybe_unused]] double* hrow = hist;
-    if constexpr (CK) {
+    if constexpr (CK && !PC) {
         const int t_last = Tb < a.t_end ? Tb : a.t_end;   // one past the last frame this launch computes
         if (t_last <= a.t_begin) return;                  // the song ended before this segment
         goes_on = !pass1 && Tb > t_last;
@@ -122,14 +134,41 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
         const long long r0 = a.offsets[song];
         Tb = (int)(a.offsets[song + 1] - r0);
         E = reinterpret_cast<const ET*>(a.logE) + (size_t)r0 * S;
-        hist = a.hist + (size_t)r0 * SD;
+        if constexpr (!PC) {
+            hist = a.hist + (size_t)r0 * SD;
+        } else {                                          // (pass 1) the song's first kept frame and its checkpoint row
+            keep = a.ckpt_every - 1;
+            hrow = a.hist + (size_t)a.ckpt_base[song] * SD;
+        }
     };
     if constexpr (PK) {
-        if ((int)blockIdx.x >= a.n_slots) return;
-        si = a.slot_begin[blockIdx.x];
-        si_end = a.slot_begin[blockIdx.x + 1];
-        if (si >= si_end) return;                         // an empty slot (the host makes none)
-        take_song();
+        if (!PC || pass1) {                               // (PC: pass 1 is the slot walk)
+            if ((int)blockIdx.x >= a.n_slots) return;
+            si = a.slot_begin[blockIdx.x];
+            si_end = a.slot_begin[blockIdx.x + 1];
+            if (si >= si_end) return;                     // an empty slot (the host makes none)
+            take_song();
+        }
+    }
+    if constexpr (PC) {
+        if (pass1) {
+            keep_step = a.ckpt_every;
+        } else {
+            // the unit's segment, as Ckpt's one segment: Tb counts LOCAL frames from the checkpoint's frame (or from frame 0), E
+            // starts at local frame 0, every local frame from 1 on is stored
+            song = a.unit_song[blockIdx.x];
+            const long long r0 = a.offsets[song];
+            const int Tfull = (int)(a.offsets[song + 1] - r0);
+            const int t_begin = ug * a.ckpt_every;
+            const int t_last = Tfull - t_begin < a.ckpt_every ? Tfull : t_begin + a.ckpt_every;
+            goes_on = Tfull > t_last;
+            const int base = resumed ? t_begin - 1 : 0;
+            Tb = t_last - base;
+            E = reinterpret_cast<const ET*>(a.logE) + (size_t)(r0 + base) * S;
+            hist = a.hist + (size_t)blockIdx.x * a.hist_song_stride;
+            keep = 1;
+            hrow = resumed ? hist : hist + SD;
+        }
     }
 
     // ---------------- per-lane constants.  Idle lanes (j >= S) publish -inf.
@@ -223,7 +262,7 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
         if constexpr (!CK) {
             if (tvalid) hist[(size_t)t * SD + j] = dn;
             if (wv == 0 && lane == 0) hist[(size_t)(t - 1) * SD + S] = M;   // M_{t-1}, next to the row it was taken over
-        } else if (t == keep) {
+        } else if (PC ? t == keep && (!pass1 || t + 1 < Tb) : t == keep) {   // (PC pass 1: a song's last frame has no checkpoint row)
             if (tvalid) hrow[j] = dn;
             if (wv == 0 && lane == 0 && !pass1) hrow[S - SD] = M;           // (a resumed segment's first frame: the row in front)
             hrow += SD;
@@ -243,7 +282,8 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
             if constexpr (!CK) {
                 if (tvalid) hist[j] = d0;
             } else {
-                if (resumed) d0 = tvalid ? a.init_rows[(size_t)song * a.init_stride + jc] : -INFINITY;   // the checkpoint row: d_{t_begin - 1}
+                // the checkpoint row: d_{t_begin - 1} (PC: in front of segment ug of the song)
+                if (resumed) d0 = tvalid ? a.init_rows[(PC ? (size_t)(a.ckpt_base[song] + ug - 1) * SD : (size_t)song * a.init_stride) + jc] : -INFINITY;
                 else if (tvalid && !pass1) hist[j] = d0;
             }
             produce(d0, 0);
@@ -317,12 +357,15 @@ __global__ void __launch_bounds__(NWT * 64) f64_floor_forward_kernel(F64Args a) 
 // ended before the segment; its waves leave) whose last frame already has its state, seg_last[b]; its rows start at
 // hist_song_stride * b and its states at states + b * T, a.states being advanced to the segment's first frame.  Nothing is filled
 // past a song's end: the host fills the whole buffer once.
+// PackedCkpt: Ckpt's walk over the units of one launch of a packed checkpointed decode (vit_decode_f64_packed_checkpointed): unit u has
+// seg_len[u] frames from state seg_last[u], rows at hist_song_stride * u, chunk entries at u * chunks and its states at states +
+// unit_states[u] (offsets[song] + segment * K, 64-bit).  Nothing past a unit's end is filled: those frames are the next song's.
 constexpr int kF64BtWaves = 4;
 constexpr int kF64BtSlots = 3;     // candidate slots per lane: W + kMaxExtras <= 192
 
 template <int NWT, int MODE, F64Variant V = F64Variant::Plain>
 __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args a) {
-    constexpr bool PK = V == F64Variant::Packed, CK = V == F64Variant::Ckpt;
+    constexpr bool PC = V == F64Variant::PackedCkpt, PK = V == F64Variant::Packed, CK = V == F64Variant::Ckpt || PC;
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int EPL = NWT, NP = NWT * 64, KC = kF64BtSlots;
     const int S = a.S, SD = a.SD64, T = a.T, W = a.W, nx = a.n_extras;
@@ -343,7 +386,7 @@ __global__ void __launch_bounds__(kF64BtWaves * 64) f64_backtrace_kernel(F64Args
     const long long row0 = PK ? (long long)a.offsets[song] : 0;   // (PK) first history row / state of the song
     const int Tb = PK ? (int)(a.offsets[song + 1] - row0) : CK ? (int)a.seg_len[song] : song_length(a.lengths, song, T);
     if (CK && Tb < 1) return;
-    int32_t* states = a.states + (PK ? (size_t)row0 : (size_t)song * T);       // (no __restrict__: MODE 1 reads what chase() stored)
+    int32_t* states = a.states + (PK ? (size_t)row0 : PC ? (size_t)a.unit_states[song] : (size_t)song * T);       // (no __restrict__: MODE 1 reads what chase() stored)
     int32_t* entry = a.entry + (PK ? (size_t)cbase : (size_t)song * C);
     const double* __restrict__ hist = a.hist + (PK ? (size_t)row0 * SD : CK ? (size_t)song * a.hist_song_stride : (size_t)song * T * SD);
     const float* __restrict__ tabX = reinterpret_cast<const float*>(a.image + a.off_tabX);
@@ -513,21 +556,30 @@ static bool f64_variant_args_ok(const F64Args& a, F64Variant v, bool bt) {
             // pass 1 (a.ckpt_every > 0, from frame 0) or one segment (resumed from a.init_rows where a.t_begin > 0)
             return a.T >= 1 && a.t_begin >= 0 && a.t_end <= a.T && a.t_begin < a.t_end && (a.t_begin <= 0 || a.init_rows) &&
                    (a.ckpt_every <= 0 || a.t_begin <= 0) && a.ckpt_every >= 0;
+        case F64Variant::PackedCkpt:
+            if (!a.offsets || !a.ckpt_base || a.ckpt_every < 1) return false;
+            if (bt) return a.seg_len && a.seg_last && a.unit_states;
+            // pass 1 (a.unit_song null: the slot walk) or the units of one launch, each with K + 1 rows of its own
+            return a.unit_song ? a.unit_seg && a.init_rows && a.hist_song_stride >= ((int64_t)a.ckpt_every + 1) * a.SD64
+                               : a.slot_begin && a.slot_songs && a.n_slots >= 1;
     }
     return false;
 }
 
-// The forward instantiation of the plan for variant V: launched over one workgroup per song (Packed: per slot), or (per_cu set) asked
-// how many of its workgroups one compute unit holds at once (the occupancy query at its LDS size)
+// The forward instantiation of the plan for variant V: launched over one workgroup per song (Packed: per slot; PackedCkpt: per slot in
+// pass 1, per unit in pass 2), or (per_cu set) asked how many of its workgroups one compute unit holds at once (the occupancy query at
+// its LDS size)
 template <F64Variant V>
 static hipError_t f64_forward_v(const F64Args& a, bool f16, hipStream_t st, int* per_cu) {
     return f64_dispatch_width(a.W, [&](auto w) {
         return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
             constexpr int W = decltype(w)::value, NWT = decltype(n)::value;
             constexpr size_t lds = F64Lds<W, NWT>::bytes();
+            static_assert(f64_pckpt_units_per_cu(W, NWT) * lds <= kLdsBytes || f64_pckpt_units_per_cu(W, NWT) == 1, "the units of one CU fit its LDS");
+            const bool slots = V == F64Variant::Packed || (V == F64Variant::PackedCkpt && !a.unit_song);
             auto go = [&](auto kern) -> hipError_t {
                 if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, NWT * 64, lds);
-                hipLaunchKernelGGL(kern, dim3((unsigned)(V == F64Variant::Packed ? a.n_slots : a.B)), dim3(NWT * 64), lds, st, a);
+                hipLaunchKernelGGL(kern, dim3((unsigned)(slots ? a.n_slots : a.B)), dim3(NWT * 64), lds, st, a);
                 return hipGetLastError();
             };
             return f16 ? go(f64_floor_forward_kernel<W, NWT, __half, V>) : go(f64_floor_forward_kernel<W, NWT, float, V>);
@@ -539,6 +591,7 @@ static hipError_t f64_forward(const F64Args& a, F64Variant v, bool f16, hipStrea
         case F64Variant::Plain: return f64_forward_v<F64Variant::Plain>(a, f16, st, per_cu);
         case F64Variant::Packed: return f64_forward_v<F64Variant::Packed>(a, f16, st, per_cu);
         case F64Variant::Ckpt: return f64_forward_v<F64Variant::Ckpt>(a, f16, st, per_cu);
+        case F64Variant::PackedCkpt: return f64_forward_v<F64Variant::PackedCkpt>(a, f16, st, per_cu);
     }
     return hipErrorInvalidValue;
 }
@@ -549,12 +602,13 @@ hipError_t launch_f64_forward(const F64Args& a, F64Variant v, bool f16, hipStrea
 }
 
 hipError_t f64_forward_resident(const F64Args& a, F64Variant v, bool f16, int* per_cu) {
-    if (v != F64Variant::Packed || a.W > a.S) return hipErrorInvalidValue;   // (the one variant whose launch is sized by it)
+    if ((v != F64Variant::Packed && v != F64Variant::PackedCkpt) || a.W > a.S) return hipErrorInvalidValue;   // (the variants whose slot launches are sized by it)
     return f64_forward(a, v, f16, nullptr, per_cu);
 }
 
 // The two passes (launch_two_pass): one wave per (song, chunk) -- Packed: per entry of wave_song, a.chunks the largest chunk count of
-// any song; Ckpt: a.chunks chunks per sub-problem whatever its length, an empty chunk stands by itself -- then one wave per song.
+// any song; Ckpt, PackedCkpt: a.chunks chunks per sub-problem whatever its length, an empty chunk stands by itself -- then one wave
+// per song.
 template <F64Variant V>
 static hipError_t f64_backtrace_v(const F64Args& a, hipStream_t st) {
     return f64_dispatch_waves(a.S, [&](auto n) -> hipError_t {
@@ -570,6 +624,7 @@ hipError_t launch_f64_backtrace(const F64Args& a, F64Variant v, hipStream_t st) 
         case F64Variant::Plain: return f64_backtrace_v<F64Variant::Plain>(a, st);
         case F64Variant::Packed: return f64_backtrace_v<F64Variant::Packed>(a, st);
         case F64Variant::Ckpt: return f64_backtrace_v<F64Variant::Ckpt>(a, st);
+        case F64Variant::PackedCkpt: return f64_backtrace_v<F64Variant::PackedCkpt>(a, st);
     }
     return hipErrorInvalidValue;
 }

@@ -239,6 +239,16 @@ struct F64Args {
     int64_t hist_song_stride;
     const int64_t* seg_len;     // [B]
     const int32_t* seg_last;    // [B]
+    // packed checkpointed decode (vit_decode_f64_packed_checkpointed; the PackedCkpt variant of both kernels; FwdArgs' fields of the same
+    // names).  ckpt_every = K always; song b has n_b = ceil(T_b / K) segments.  unit_song null = pass 1: the slot walk of the packed
+    // batch, the d rows of frames mK - 1 (m = 1 .. n_b - 1) kept at rows ckpt_base[b] + m - 1 of hist.  unit_song set = the B units of
+    // one launch: workgroup u runs segment unit_seg[u] of song unit_song[u], resumed from row ckpt_base[song] + segment - 1 of init_rows
+    // (segment 0: from the prior), into rows hist + u * hist_song_stride (the row in front of them takes M of the checkpoint frame).
+    // Back-trace: unit u is the sub-problem seg_len[u] / seg_last[u] over those rows, its states start at states + unit_states[u].
+    const int64_t* ckpt_base;   // [songs] checkpoint rows in front of song b's = sum of (n_b' - 1) over b' < b
+    const int32_t* unit_song;   // [B units of this launch]
+    const int32_t* unit_seg;    // [B units of this launch]
+    const int64_t* unit_states; // [B units of this launch] offsets[song] + segment * K (launch_packed_segment_prep)
 };
 // What a workgroup of f64_floor_forward_kernel decodes and what the waves of f64_backtrace_kernel walk (described at the kernels):
 //   Plain   a song each, every row kept; a.chunks chunks per song                                   (vit_decode_f64)
@@ -246,9 +256,21 @@ struct F64Args {
 //           a.wave_song, rows at offsets[song]                                                      (vit_decode_f64_packed)
 //   Ckpt    forward: pass 1 (a.ckpt_every > 0) or one segment (a.t_begin / a.t_end, resumed from
 //           a.init_rows); back-trace: the sub-problems a.seg_len / a.seg_last of one segment         (vit_decode_f64_checkpointed)
-// f64_forward_resident: workgroups of the forward instantiation one compute unit holds at once (Packed, whose launch is sized by it;
-// hipErrorInvalidValue for the others, as *_variant_resident).
-enum class F64Variant { Plain, Packed, Ckpt };
+//   PackedCkpt  forward: pass 1 over the songs of a slot (a.unit_song null), or one (song, segment) unit per
+//           workgroup (a.B units); back-trace: the units' sub-problems, states at a.unit_states      (vit_decode_f64_packed_checkpointed)
+// f64_forward_resident: workgroups of the forward instantiation one compute unit holds at once (Packed and PackedCkpt, whose slot
+// launches are sized by it; hipErrorInvalidValue for the others, as *_variant_resident).
+enum class F64Variant { Plain, Packed, Ckpt, PackedCkpt };
+// Units per compute unit and launch of the packed checkpointed decode's pass 2, per forward instantiation (W, target waves): 1 where the
+// workgroup runs twelve waves (W >= 84 there also fills most of the LDS), elsewhere the workgroups whose waves fit one CU's registers
+// -- four SIMDs x the waves per SIMD the kernel's register count allows (4 at W = 16, 3 at W = 32, 2 above:
+// profiles/f64_packed_ckpt_resources.txt) over the workgroup's waves -- capped at 4; the LDS (at most 17 KB on eight waves) never binds.
+// Every unit owns its rows: tuning, not correctness.  Measured at (32, 6), S = 361, 804 recordings: 2 beats 1 and 4 with disjoint
+// ranges, also at equal bytes (profiles/f64_packed_ckpt_time.json).
+constexpr int f64_pckpt_units_per_cu(int W, int nwt) {
+    const int by_regs = 4 * (W <= 16 ? 4 : W <= 32 ? 3 : 2) / nwt;
+    return nwt >= 12 || by_regs < 1 ? 1 : by_regs > 4 ? 4 : by_regs;
+}
 hipError_t launch_f64_forward(const F64Args& a, F64Variant v, bool f16, hipStream_t st);
 hipError_t f64_forward_resident(const F64Args& a, F64Variant v, bool f16, int* per_cu);
 hipError_t launch_f64_backtrace(const F64Args& a, F64Variant v, hipStream_t st);

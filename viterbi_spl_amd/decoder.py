@@ -460,8 +460,9 @@ class ViterbiDecoder:
 
     def plan_workspace_f64_packed(self, offsets, max_workspace_bytes: Optional[int] = None) -> dict:
         """How ``decode_f64_packed`` meets a workspace budget (bytes; None = whatever it takes): the checkpointed float64 decode
-        (``decode_f64_checkpointed``) takes padded batches only, so the recordings are decoded in consecutive groups, each taking recordings in order while its
-        ``workspace_bytes_f64_packed`` fits.  Returns ``{"groups": [(b0, b1), ...], "bytes": the largest group's need}``; raises
+        the recordings are decoded in consecutive groups, each taking recordings in order while its
+        ``workspace_bytes_f64_packed`` fits (``plan_workspace_f64_packed_bounded`` / ``decode_f64_packed_bounded`` meet a budget by
+        segments instead: one decode over all recordings, and no recording is too long for it).  Returns ``{"groups": [(b0, b1), ...], "bytes": the largest group's need}``; raises
         ViterbiHipError when one recording alone does not fit, or for a plan that is not served."""
         off = self._host_offsets(offsets)
         B = off.size - 1
@@ -506,6 +507,62 @@ class ViterbiDecoder:
         if out_dtype != torch.int32:
             states = states.to(out_dtype)
         return states, loglik
+
+    # ------------------------------------------------------------------ the packed float64 decode under a workspace budget
+    def workspace_bytes_f64_packed_checkpointed(self, offsets, segment_frames: int) -> int:
+        """Workspace bytes of ``decode_f64_packed_checkpointed`` for the recordings ``offsets`` describes (B + 1 host frame offsets);
+        raises ViterbiHipError for a plan or a segment length it does not serve."""
+        off = self._host_offsets(offsets)
+        need = int(_lib.load().vit_workspace_bytes_f64_packed_checkpointed(self._plan, off.size - 1, off.ctypes.data, int(segment_frames)))
+        if need == 0:
+            raise _lib.ViterbiHipError("the packed checkpointed float64 decode needs 64 <= segment_frames <= 2**24 and a plan decode_f64 "
+                                       "serves: banded, its floor form proven, without dense rows (unstructured matrices, the Durrieu "
+                                       "step matrices and scan-only plans are not served)")
+        return need
+
+    def decode_f64_packed_checkpointed(self, emission_logits: torch.Tensor, offsets, segment_frames: int = 1024,
+                                       out_dtype: torch.dtype = torch.int64, workspace: Optional[torch.Tensor] = None
+                                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_f64_packed`` with a bounded workspace (``vit_decode_f64_packed_checkpointed``): ``n_units * (K + 1)`` rows of doubles
+        for the (recording, segment) units being walked (``n_units = min(B, u x compute units)``, ``K = segment_frames``) plus one row
+        per K frames of every recording, instead of one row per frame.  Same arguments, same states, same float64 log-likelihoods,
+        bit for bit; about twice the forward work.  Plans: those of ``decode_f64``; any other raises ``ViterbiHipError`` before
+        anything is enqueued.  ``workspace``: an optional uint8 tensor of at least ``workspace_bytes_f64_packed_checkpointed(...) +
+        256`` bytes to decode in (the caller then keeps it alive until the stream has run the decode: the call does not synchronise);
+        without one the call allocates its own and synchronises the stream before it returns."""
+        return self._decode_packed_segments("f64_packed_checkpointed", emission_logits, offsets, segment_frames, out_dtype, workspace,
+                                            torch.float64)
+
+    def plan_workspace_f64_packed_bounded(self, offsets, max_workspace_bytes: Optional[int] = None) -> dict:
+        """How ``decode_f64_packed_bounded`` decodes the recordings ``offsets`` describes under a workspace budget (bytes; None =
+        whatever it takes): ``{"mode": "full", "workspace_bytes": n}`` -- ``vit_decode_f64_packed`` fits -- or ``{"mode":
+        "checkpointed", "segment_frames": K, "workspace_bytes": n}`` -- ``vit_decode_f64_packed_checkpointed`` with the largest K of
+        8192, 4096, ..., 64 that fits.  Raises ViterbiHipError when nothing fits or the plan is not served.  Both modes decode the
+        same bits."""
+        off = self._host_offsets(offsets)
+        B, N = off.size - 1, int(off[-1])
+        if B == 0:
+            return {"mode": "full", "workspace_bytes": 0}
+        need, budget = self.workspace_bytes_f64_packed(B, N), None if max_workspace_bytes is None else int(max_workspace_bytes)
+        size_of = _lib.load().vit_workspace_bytes_f64_packed_checkpointed
+        return self._plan_segments(need, lambda K: size_of(self._plan, B, off.ctypes.data, K), budget,
+                                   lambda least: f"no packed float64 decode of {B} recordings ({N} frames) fits a workspace of {budget} "
+                                                 f"bytes (the whole history needs {need}, the checkpointed decode at least {least})")
+
+    def decode_f64_packed_bounded(self, emission_logits: torch.Tensor, offsets, max_workspace_bytes: Optional[int] = None,
+                                  out_dtype: torch.dtype = torch.int64, workspace: Optional[torch.Tensor] = None
+                                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_f64_packed`` under a workspace budget met by segments, not by groups of recordings (``plan_workspace_f64_packed_bounded``):
+        the whole history where it fits, else ``decode_f64_packed_checkpointed`` with the largest segment length that does -- one
+        launch sequence over all recordings, and a recording longer than the budget's worth of rows is decoded all the same.  The
+        same bits either way; ``ViterbiHipError`` before anything is enqueued when nothing fits.  Without ``workspace`` the call
+        decodes in a tensor of its own of the planned bytes + 256, never more, and synchronises the stream before it returns."""
+        _, off = self._check_packed(emission_logits, offsets)
+        mode = self.plan_workspace_f64_packed_bounded(off, max_workspace_bytes)
+        if mode["mode"] == "checkpointed":
+            return self.decode_f64_packed_checkpointed(emission_logits, off, segment_frames=mode["segment_frames"], out_dtype=out_dtype,
+                                                       workspace=workspace)
+        return self.decode_f64_packed(emission_logits, off, out_dtype=out_dtype, workspace=workspace)
 
     # ------------------------------------------------------------------ bounded-workspace decode
     def workspace_bytes_checkpointed(self, B: int, T: int, segment_frames: int) -> int:
@@ -625,13 +682,14 @@ class ViterbiDecoder:
         return self._decode_packed_segments("packed_checkpointed", emission_logits, offsets, segment_frames, out_dtype, workspace)
 
     def _decode_packed_segments(self, entry: str, emission_logits: torch.Tensor, offsets, segment_frames: int, out_dtype: torch.dtype,
-                                workspace: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """``decode_packed_checkpointed`` / ``decode_packed_bounded``: `entry` names the pair ``workspace_bytes_<entry>`` (which
-        raises for a plan or a segment length that is not served) and ``vit_decode_<entry>``."""
+                                workspace: Optional[torch.Tensor], loglik_dtype: torch.dtype = torch.float32
+                                ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_packed_checkpointed`` / ``decode_packed_bounded`` / ``decode_f64_packed_checkpointed``: `entry` names the pair
+        ``workspace_bytes_<entry>`` (which raises for a plan or a segment length that is not served) and ``vit_decode_<entry>``."""
         dt, off = self._check_packed(emission_logits, offsets)
         B, N = off.size - 1, int(off[-1])
         states = torch.empty((N,), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
+        loglik = torch.empty((B,), dtype=loglik_dtype, device=self.device)
         if B > 0:
             ws, ws_ptr, ws_bytes, mine = self._call_workspace(getattr(self, "workspace_bytes_" + entry)(off, segment_frames), workspace)
             with torch.cuda.device(self.device):

@@ -90,11 +90,13 @@ def viterbi_librosa_f64_fn(*, transition_matrix, prob_init, probs_st):
     return states.cpu().numpy()
 
 
-def viterbi_librosa_f64_recordings_fn(*, transition_matrix, prob_init, probs_st_list):
+def viterbi_librosa_f64_recordings_fn(*, transition_matrix, prob_init, probs_st_list, max_workspace_bytes=None):
     """``viterbi_librosa_f64_fn`` over many recordings of different lengths in ONE packed decode
     (``ViterbiDecoder.decode_f64_packed``; the reference calls its function once per recording, as at tonet/for_paper.py:2304-2309):
     ``probs_st_list`` holds one float32 ``[S, T_b]`` array per recording; a list of ``int64[T_b]`` comes back, entry b equal to
-    ``viterbi_librosa_f64_fn`` of recording b alone.  The asserts and the host ``np.log`` step are that function's, per recording."""
+    ``viterbi_librosa_f64_fn`` of recording b alone.  The asserts and the host ``np.log`` step are that function's, per recording.
+    ``max_workspace_bytes``: a budget for the decode's workspace, met by segments (``ViterbiDecoder.decode_f64_packed_bounded``) --
+    the same paths; ``ViterbiHipError`` when nothing fits."""
     probs_st_list = list(probs_st_list)
     if not probs_st_list:
         return []
@@ -108,7 +110,11 @@ def viterbi_librosa_f64_recordings_fn(*, transition_matrix, prob_init, probs_st_
     log_pi = np.log(prob_init + tinyp).astype(np.float32)
     offsets = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
     dec = get_decoder(logA_T, log_pi)
-    states, _ = dec.decode_f64_packed(torch.from_numpy(np.concatenate(parts, axis=0)).to(dec.device), offsets, out_dtype=torch.int64)
+    logE = torch.from_numpy(np.concatenate(parts, axis=0)).to(dec.device)
+    if max_workspace_bytes is None:
+        states, _ = dec.decode_f64_packed(logE, offsets, out_dtype=torch.int64)
+    else:
+        states, _ = dec.decode_f64_packed_bounded(logE, offsets, max_workspace_bytes=int(max_workspace_bytes), out_dtype=torch.int64)
     states = states.cpu().numpy()
     return [states[offsets[b]:offsets[b + 1]] for b in range(len(parts))]
 
