@@ -448,8 +448,18 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
             }
         }
 
+        // Full waves without the extra column's select (XQ, or no extra column at all): the four copy stores and the quad maximum are one
+        // asm statement (lds_store_addtid4_quad_max) -- each DPP step has its two wait states in two of the stores, where the compiler,
+        // which counts no instruction inside an asm statement, put an s_nop 1 in front of either step.  These waves close the frame.
+        constexpr bool QUADASM = !HALF && (XQ || NXL == 0);
         auto produce = [&](const float dn, auto wbc, const int G, const int Z) {
             constexpr int WB = decltype(wbc)::value;                      // (a constant: the add-tid stores carry it in their immediate)
+            if constexpr (QUADASM) {
+                const float q = lds_store_addtid4_quad_max<split_addtid_imm(WB, 0), split_addtid_imm(WB, 1), split_addtid_imm(WB, 2),
+                                                           split_addtid_imm(WB, 3)>(dn);
+                __hip_atomic_fetch_max(fmp + G * kFmGroupFloats, q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                return;
+            }
             if constexpr (HALF) {
 #pragma unroll
                 for (int c = 0; c < 2; ++c) wp[WB * BUF + floor_copy_off(DC, c)] = dn;
@@ -572,8 +582,11 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
                 static_assert(split_reads_behind(NQ, 0) <= 15, "lgkmcnt is a four-bit field");
                 static_assert(split_reads_behind(NQ, NPB - 1) == TQ + 1, "behind the last pair stand the tail's reads -- TQ quads and the float -- and nothing else");
                 static_assert(split_reads_behind(NQ, NPB) + 2 == TQ + 1 && TQ <= 2, "the tail's wait, lgkmcnt(0), leaves no window read out");
-                float mb = xd[0] + xa[0];                                 // the second chain starts from the extra-column sum (the burst's first read)
-                asm volatile("" ::"v"(mb));
+                // The hazard recognizer takes an asm statement with register outputs for a writer whose result the next instruction must
+                // not read, and a packed add for one whose result the next instruction (an asm statement included) must not read: a fence
+                // of the form "+v" right behind the last packed add of its group, or right in front of the first maximum that reads one of
+                // its outputs, costs an s_nop 0.  Hence the seed of the second chain below and the shape of the tail's fence.
+                float mb;                                                 // the second chain starts from the extra-column sum (the burst's first read)
                 split_frames(std::make_integer_sequence<int, NPB>{}, [&](auto gc) {
                     constexpr int w = 8 * decltype(gc)::value;
                     f32x4 da = dw[w / 4], db = dw[w / 4 + 1];
@@ -587,6 +600,12 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
                     f32x2 c1_ = f32x2{da.z, da.w} + f32x2{aw[w + 2], aw[w + 3]};
                     f32x2 c2_ = f32x2{db.x, db.y} + f32x2{aw[w + 4], aw[w + 5]};
                     f32x2 c3_ = f32x2{db.z, db.w} + f32x2{aw[w + 6], aw[w + 7]};
+                    if constexpr (decltype(gc)::value == 0) {
+                        // the seed add stands between the first group's last packed add and its fence (later groups have the maxima of
+                        // the group before there)
+                        mb = xd[0] + xa[0];
+                        asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_) : "v"(mb));
+                    } else
                     asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_));   // a group's sums before its maxima: no hazard s_nop
                     m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
                     mb = fmaxf(fmaxf(mb, c1_.x), c1_.y);
@@ -604,13 +623,15 @@ __global__ void __launch_bounds__(64 * (kSplitFullWaves + kSplitHalfWaves)) band
                     if constexpr (TQ == 2) {
                         f32x2 c2_ = f32x2{db.x, db.y} + f32x2{aw[w + 4], aw[w + 5]};
                         f32x2 c3_ = f32x2{db.z, db.w} + f32x2{aw[w + 6], aw[w + 7]};
-                        asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(c2_), "+v"(c3_), "+v"(cs));
+                        asm volatile("" : "+v"(c1_), "+v"(c2_), "+v"(c3_), "+v"(cs) : "v"(c0_));   // (c0_: see below)
                         m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
                         mb = fmaxf(fmaxf(mb, c1_.x), c1_.y);
                         m0 = fmaxf(fmaxf(m0, c2_.x), c2_.y);
                         mb = fmaxf(fmaxf(mb, c3_.x), c3_.y);
                     } else {
-                        asm volatile("" : "+v"(c0_), "+v"(c1_), "+v"(cs));
+                        // c0_ is an input only: it is formed in front of the fence like the others, and the first maximum behind the fence,
+                        // which reads it, reads no output of the fence
+                        asm volatile("" : "+v"(c1_), "+v"(cs) : "v"(c0_));
                         m0 = fmaxf(fmaxf(m0, c0_.x), c0_.y);
                         mb = fmaxf(fmaxf(mb, c1_.x), c1_.y);
                     }

@@ -109,24 +109,19 @@ struct FloorLds {
 // Where a lane writes: from its own entry of copy 0 (wp = dls + 4 + sh + j), copy c's entry lies floor_copy_off(DC, c) floats on; an
 // upper lane of the split kernel's half waves writes copies 2 and 3, so its wp starts split_upper_off(DC) floats further on.  (Shared
 // with floor_lds_check.hip, which holds them against where the readers look.)
-constexpr int floor_copy_off(int DC, int c) { return c * DC - c; }
-constexpr int split_upper_off(int DC) { return floor_copy_off(DC, 2); }
+// (floor_copy_off, split_upper_off, the half waves' lane map and the split kernel's slot map: plan.hpp, where the host library's replay
+// of a frame's LDS conflicts, split_lds_conflicts, is written with them)
 // the split kernel (banded.hip): four full waves and four half-window waves over 384 target slots, in the six-wave kernel's LDS
-inline constexpr int kSplitFullWaves = 4, kSplitHalfWaves = 4;
-inline constexpr int kSplitStates = 64 * kSplitFullWaves + 32 * kSplitHalfWaves;   // 384 target slots
 using FloorSplitLds = FloorLds<32, kSplitStates / 64>;   // the six-wave kernel's LDS, byte for byte
+static_assert(FloorSplitLds::DC == kSplitCopyStride && FloorSplitLds::fmg == kSplitSlotGroups, "plan.hpp replays this layout");
 // Lane map of a half wave: the two lanes of a target are l and l ^ 8, partners under the DPP control row_ror:8, so that the two halves
 // of a window are joined by one v_max_f32_dpp (max_lane_xor8).  Lanes with bit 3 clear hold the lower half of the window, and the 32
 // of them take the wave's 32 targets in ascending lane order.  A target's quad mates are the same in both halves.
 // (Shared with floor_lds_check.hip, which replays the map against the LDS layout and the ds_read_b128 lane groups.)
-constexpr int split_half_of(int lane) { return (lane >> 3) & 1; }
-constexpr int split_half_target(int lane) { return ((lane >> 4) << 3) | (lane & 7); }   // 0 .. 31 within the wave
 // Frame-maximum slots of the split kernel where the extra column leaves M by address (XQ): the lane with l & 3 == r of quad q adds into
 // slot 4 r + q % 3, so slots 0 .. 2 see all sixteen quads of every wave and M is one v_max3_f32 of them.  Slot 3, the fourth float of the
 // same 16-byte read, belongs to the extra column x: its two lanes (r = 0, quad mates idle) add delta[x] into it and into nothing else, and
 // a ds_max_f32 into a slot that was reset to -inf leaves exactly the value added.  Slots 4 .. 15 are written and never read.
-inline constexpr int kSplitXSlot = 3;
-constexpr int split_fm_slot(int lane, bool is_x) { return 4 * (lane & 3) + (is_x ? kSplitXSlot : (lane >> 2) % 3); }
 
 // V = Packed is the packed variant (vit_decode_packed, plans without the wave form): the workgroup is a SLOT and decodes the
 // songs slot_songs[slot_begin[w] .. slot_begin[w+1]) back to back, as a wave does in wave.hip.  Emission and history rows of

@@ -144,6 +144,27 @@ __device__ __forceinline__ void lds_store_addtid(float v) {
     static_assert(BYTE_OFF >= 0 && BYTE_OFF < 65536 && BYTE_OFF % 4 == 0, "the instruction's 16-bit offset field");
     asm volatile("ds_write_addtid_b32 %0 offset:%1" ::"v"(v), "n"(BYTE_OFF) : "memory");
 }
+// Four add-tid stores of v (byte offsets O0 .. O3 from M0, as lds_store_addtid) and the maximum of v over the lane's quad (fm_publish's
+// two DPP steps), one statement.  A DPP step may read a register two wait states behind the VALU instruction that wrote it, and every
+// instruction issued in between is one: the first step stands behind the first two stores, the second behind the other two, and v
+// itself may come from the instruction right in front of the statement.  Left to the compiler, whose hazard recognizer counts no
+// instruction inside an asm statement, the same six instructions took an s_nop 1 in front of each step.
+// KEEP TWO INSTRUCTIONS IN FRONT OF EACH STEP: the compiler knows nothing of the DPP reads in this string and pads nothing inside it.
+// Whoever reorders it, drops a store or reuses it with another mix must leave at least two instructions (or an s_nop 1) between the
+// start of the string and the first step -- the writer of v may be the instruction in front of the statement -- and between the two steps.
+// Counts, waits and M0 as for lds_store_addtid: the compiler counts no lgkmcnt for these stores.
+template <int O0, int O1, int O2, int O3>
+__device__ __forceinline__ float lds_store_addtid4_quad_max(float v) {
+    static_assert(O0 >= 0 && O1 >= 0 && O2 >= 0 && O3 >= 0 && O0 < 65536 && O1 < 65536 && O2 < 65536 && O3 < 65536 &&
+                  (O0 | O1 | O2 | O3) % 4 == 0, "the instruction's 16-bit offset field");
+    float q;
+    asm volatile("ds_write_addtid_b32 %1 offset:%2\n\tds_write_addtid_b32 %1 offset:%3\n\t"
+                 "v_max_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                 "ds_write_addtid_b32 %1 offset:%4\n\tds_write_addtid_b32 %1 offset:%5\n\t"
+                 "v_max_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                 : "=&v"(q) : "v"(v), "n"(O0), "n"(O1), "n"(O2), "n"(O3) : "memory");
+    return q;
+}
 // lane l <- x[l-1], lane 0 <- fill   (wave_shr:1)
 __device__ __forceinline__ float wave_shift_up(float x, float fill) {
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(fill), __float_as_int(x), 0x138, 0xf, 0xf, false));

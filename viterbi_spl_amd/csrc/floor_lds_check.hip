@@ -8,6 +8,8 @@
 //   * the half waves' lane map (split_half_of, split_half_target): partner lanes l and l ^ 8, 32 targets in ascending lane order, and
 //     the LDS cycles of a half wave's four ds_read_b128 under the hardware's lane groups, against the map with the halves 32 lanes apart;
 //   * the split kernel's frame-maximum slots with the extra column in M's quad (split_fm_slot);
+//   * the conflict cycles of every LDS instruction of a split-kernel frame per role (split_lds_conflicts, plan.hpp), for the present copy
+//     assignment of the half waves and the three alternatives: counted and printed, and none may beat the present one;
 //   * which pairs of copy writes one ds_write2_b32 / ds_write2st64_b32 could encode (two 8-bit offsets in units of 1 / 64 dwords
 //     from one address): printed per layout, and checked against the argument in DESIGN.md 7 for why none exists from NP = 256 on.
 #include <cstdio>
@@ -264,6 +266,39 @@ static void replay_slot_map() {
     std::printf("split slot map: every quad without x reaches one of slots 0 .. 2, x reaches slot %d alone: ok (%d state counts)\n", kSplitXSlot, cases);
 }
 
+// ---- LDS conflict cycles of a frame of the split kernel, per instruction kind and role (split_lds_conflicts, plan.hpp): the present
+// copy assignment of the half waves against the three others a lane pair can take without another instruction (the two stores of a
+// lane share one address register, so its copies lie one fixed distance apart: (0, 1) / (2, 3) or (0, 2) / (1, 3), either way round),
+// and the slot map with same-address lanes of the ds_max_f32 counted once (they combine) or one by one (they serialise).
+static void replay_conflicts(int S, int off, int WF) {
+    static const int pairs[4][2][2] = {{{0, 1}, {2, 3}}, {{2, 3}, {0, 1}}, {{0, 2}, {1, 3}}, {{1, 3}, {0, 2}}};
+    static const char* kind[6] = {"slot quad read", "window b128", "window b32", "copy writes", "ds_max_f32", "slot reset"};
+    const auto slot = [](int lane, bool is_x) { return split_fm_slot(lane, is_x); };
+    int frame_total[4][2] = {};
+    for (int as = 0; as < 4; ++as)
+        for (int ser = 0; ser < 2; ++ser)
+            for (int rb = 0; rb < 2; ++rb)
+                for (int wv = 0; wv < kSplitFullWaves + kSplitHalfWaves; ++wv) {
+                    int c[6];
+                    split_lds_conflicts(S, off, WF, wv, rb, ser != 0, [&](int half, int k) { return pairs[as][half][k]; }, slot, c);
+                    for (int k = 0; k < 6; ++k) frame_total[as][ser] += c[k];
+                    if (as == 0 && ser == 1 && (rb == 0 || wv == 0))
+                        std::printf("split conflicts S %d WF %d buffer %d wave %d (%s):", S, WF, rb, wv, wv < kSplitFullWaves ? "full" : wv == 7 ? "half, resets" : "half");
+                    if (as == 0 && ser == 1 && (rb == 0 || wv == 0)) {
+                        for (int k = 0; k < 6; ++k) std::printf(" %s %d", kind[k], c[k]);
+                        std::printf("\n");
+                    }
+                    CHECK(c[0] == 0 && c[5] == 0, "S %d wave %d: the broadcast slot read and the linear reset must be conflict-free", S, wv);
+                    if (wv < kSplitFullWaves) CHECK(c[3] == 0, "S %d wave %d: the add-tid stores are linear in the lane", S, wv);
+                }
+    for (int as = 0; as < 4; ++as) {
+        // per wave-frame: two buffers, eight waves
+        std::printf("split conflicts S %d WF %d, half-wave copies lower (%d, %d) upper (%d, %d)%s: %.3f extra LDS cycles per wave-frame, %.3f with the ds_max_f32 lanes of one address serialised\n",
+                    S, WF, pairs[as][0][0], pairs[as][0][1], pairs[as][1][0], pairs[as][1][1], as == 0 ? " (the kernel's)" : "", frame_total[as][0] / 16.0, frame_total[as][1] / 16.0);
+        CHECK(frame_total[as][0] >= frame_total[0][0] && frame_total[as][1] >= frame_total[0][1], "S %d: copy assignment %d has fewer conflict cycles than the kernel's", S, as);
+    }
+}
+
 template <int W, int NWT>
 static void replay_pair() {
     char name[64];
@@ -296,6 +331,9 @@ int main() {
     replay_slot_map();
     replay_read_cycles(361, 15);                                          // the reference's 361-state grid: rows 344 .. 359 are clamped to S - W
     replay_read_cycles(321, 13);
+    replay_conflicts(361, 15, 29);                                        // the two trimmed grids and the whole window
+    replay_conflicts(321, 13, 25);
+    replay_conflicts(361, 15, 32);
     // two workgroups per CU up to B = 512 at the production shape
     static_assert(2 * FloorSplitLds::bytes() <= kLdsBytes && 2 * FloorLds<32, 6>::bytes() <= kLdsBytes, "two workgroups share a CU's LDS");
     if (failures) { std::printf("%d check(s) failed\n", failures); return 1; }

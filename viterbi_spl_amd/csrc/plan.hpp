@@ -144,6 +144,93 @@ inline constexpr int kSplitCopyStride = 384 + 16;
 constexpr int split_copy_pos(int sh, int j, int b, int c) { return 4 + sh + j + b * 4 * kSplitCopyStride + c * kSplitCopyStride - c; }
 constexpr int split_addtid_base(int sh, int wave) { return 4 * (4 + sh + 64 * wave); }
 constexpr int split_addtid_imm(int b, int c) { return 4 * (b * 4 * kSplitCopyStride + c * kSplitCopyStride - c); }
+// Copy, lane and slot maps of the floor kernels' publication (used by the kernels in banded_floor.inc / banded.hip, by
+// floor_lds_check.hip and by the replay below).  Copy c of a delta buffer holds delta[i] floor_copy_off(DC, c) floats behind copy 0's
+// entry; an upper lane of the split kernel's half waves writes copies 2 and 3, so its write pointer starts split_upper_off(DC) further on.
+constexpr int floor_copy_off(int DC, int c) { return c * DC - c; }
+constexpr int split_upper_off(int DC) { return floor_copy_off(DC, 2); }
+inline constexpr int kSplitFullWaves = 4, kSplitHalfWaves = 4;
+inline constexpr int kSplitStates = 64 * kSplitFullWaves + 32 * kSplitHalfWaves;   // 384 target slots
+inline constexpr int kSplitSlotGroups = 2 * 4 * kSplitCopyStride;                  // float position of the frame-maximum slot groups
+constexpr int split_half_of(int lane) { return (lane >> 3) & 1; }
+constexpr int split_half_target(int lane) { return ((lane >> 4) << 3) | (lane & 7); }   // 0 .. 31 within the wave
+inline constexpr int kSplitXSlot = 3;
+constexpr int split_fm_slot(int lane, bool is_x) { return 4 * (lane & 3) + (is_x ? kSplitXSlot : (lane >> 2) % 3); }
+// target slot of lane `lane` of wave `wave` (0 .. 3 full, 4 .. 7 half)
+constexpr int split_lane_target(int wave, int lane) {
+    return wave < kSplitFullWaves ? 64 * wave + lane : 64 * kSplitFullWaves + 32 * (wave - kSplitFullWaves) + split_half_target(lane);
+}
+// float position of the first window entry lane `lane` of wave `wave` reads from buffer rb (affine plans: lo_j = clamp(j - off, 0, S - 32);
+// idle targets read the last window), and of copy `c` of its own target in buffer wb
+constexpr int split_window_pos(int S, int off, int sh, int wave, int lane, int rb) {
+    const int j = split_lane_target(wave, lane);
+    const int lo = j - off < 0 ? 0 : (j - off > S - 32 ? S - 32 : j - off);
+    const int lov = (j < S ? lo : S - 32) + sh;
+    return 4 + (lov & 3) * kSplitCopyStride + (lov & ~3) + (wave >= kSplitFullWaves ? 16 * split_half_of(lane) : 0) + rb * 4 * kSplitCopyStride;
+}
+// Extra LDS cycles (what SQ_LDS_BANK_CONFLICT counts) of one wave-instruction: the lanes are served in `ngroups` groups, a group takes
+// one cycle and one more for every further distinct address on its busiest bank; `width` dwords per lane, `banks` banks of 4 bytes.
+// same_address_serialises: lanes with one address count like lanes with different ones (an LDS atomic applies them one by one).
+inline int lds_extra_cycles(const int* pos, const int (*groups)[16], int ngroups, int per_group, int width, int banks, bool same_address_serialises) {
+    int total = 0;
+    for (int g = 0; g < ngroups; ++g) {
+        int worst = 1;
+        for (int bank = 0; bank < banks; ++bank) {
+            int seen[64], n = 0, lanes = 0;
+            for (int i = 0; i < per_group; ++i) {
+                const int lane = groups ? groups[g][i] : g * per_group + i;
+                for (int k = 0; k < width; ++k) {
+                    const int a = pos[lane] + k;
+                    if (a % banks != bank) continue;
+                    ++lanes;
+                    bool dup = false;
+                    for (int q = 0; q < n; ++q) dup |= seen[q] == a;
+                    if (!dup) seen[n++] = a;
+                }
+            }
+            const int ways = same_address_serialises ? lanes : n;
+            if (ways > worst) worst = ways;
+        }
+        total += worst - 1;
+    }
+    return total;
+}
+inline constexpr int kLdsReadB128Groups[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
+                                                  {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
+                                                  {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
+                                                  {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
+// Extra LDS cycles of every LDS instruction one wave of the split kernel issues in a frame that reads buffer rb and writes the other,
+// by instruction kind: [0] the slot quad's ds_read_b128, [1] the window's ds_read_b128 (WF / 4 of a full wave, 4 of a half wave),
+// [2] a trimmed full wave's ds_read_b32, [3] the copy writes (4 add-tid stores | 2 ds_write_b32), [4] ds_max_f32, [5] the last half
+// wave's slot reset.  Bank rules: reads of 16 bytes in four 16-lane groups over 64 banks, everything else in two 32-lane groups over 32.
+// copy_of(half, k): the copy a half-wave lane of window half `half` writes with its k-th store (today 2 * half + k).
+template <typename CopyOf, typename SlotOf>
+inline void split_lds_conflicts(int S, int off, int WF, int wave, int rb, bool atomics_serialise, CopyOf copy_of, SlotOf slot_of, int out[6]) {
+    const int sh = off % 4, wb = rb ^ 1, x = S - 1;
+    const bool hw = wave >= kSplitFullWaves;
+    int pos[64];
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    for (int l = 0; l < 64; ++l) pos[l] = kSplitSlotGroups;
+    out[0] = lds_extra_cycles(pos, kLdsReadB128Groups, 4, 16, 4, 64, false);
+    for (int q = 0; q < (hw ? 4 : WF / 4); ++q) {
+        for (int l = 0; l < 64; ++l) pos[l] = split_window_pos(S, off, sh, wave, l, rb) + 4 * q;
+        out[1] += lds_extra_cycles(pos, kLdsReadB128Groups, 4, 16, 4, 64, false);
+    }
+    if (!hw && WF % 4) {
+        for (int l = 0; l < 64; ++l) pos[l] = split_window_pos(S, off, sh, wave, l, rb) + WF - 1;
+        out[2] = lds_extra_cycles(pos, nullptr, 2, 32, 1, 32, false);
+    }
+    for (int k = 0; k < (hw ? 2 : 4); ++k) {
+        for (int l = 0; l < 64; ++l) pos[l] = split_copy_pos(sh, split_lane_target(wave, l), wb, hw ? copy_of(split_half_of(l), k) : k);
+        out[3] += lds_extra_cycles(pos, nullptr, 2, 32, 1, 32, false);
+    }
+    for (int l = 0; l < 64; ++l) pos[l] = kSplitSlotGroups + slot_of(l, split_lane_target(wave, l) == x);
+    out[4] = lds_extra_cycles(pos, nullptr, 2, 32, 1, 32, atomics_serialise);
+    if (wave == kSplitFullWaves + kSplitHalfWaves - 1) {
+        for (int l = 0; l < 64; ++l) pos[l] = kSplitSlotGroups + 64 + l;
+        out[5] = lds_extra_cycles(pos, nullptr, 2, 32, 1, 32, false);
+    }
+}
 
 // Byte layout of the device image (all offsets in bytes from the image base,
 // every section 256-byte aligned).

@@ -90,6 +90,34 @@ int vph_split_addtid(int sh, int wave, int lane, int b, int c, int* out) {
     out[2] = vit::split_copy_pos(sh, 64 * wave + lane, b, c);
     return 0;
 }
+// Extra LDS cycles per instruction kind of wave `wave` in a frame that reads buffer rb (vit::split_lds_conflicts; out[6]).  assignment:
+// which copies the two lanes of a half-wave target write, first and second store -- 0 lower (0, 1) upper (2, 3), the kernel's;
+// 1 lower (2, 3) upper (0, 1); 2 lower (0, 2) upper (1, 3); 3 lower (1, 3) upper (0, 2).  Returns -1 for arguments outside the split kernel.
+int vph_split_lds_conflicts(int S, int off, int WF, int wave, int rb, int atomics_serialise, int assignment, int* out) {
+    if (S <= vit::kSplitFullRows || S >= vit::kSplitStates || off < 0 || off > 31 || (WF != 25 && WF != 29 && WF != 32) || wave < 0 ||
+        wave >= vit::kSplitFullWaves + vit::kSplitHalfWaves || rb < 0 || rb > 1 || assignment < 0 || assignment > 3)
+        return -1;
+    static const int pairs[4][2][2] = {{{0, 1}, {2, 3}}, {{2, 3}, {0, 1}}, {{0, 2}, {1, 3}}, {{1, 3}, {0, 2}}};
+    vit::split_lds_conflicts(S, off, WF, wave, rb, atomics_serialise != 0, [&](int half, int k) { return pairs[assignment][half][k]; },
+                             [](int lane, bool is_x) { return vit::split_fm_slot(lane, is_x); }, out);
+    return 0;
+}
+// where the kernel's maps put things, for the host tests: out[0] target slot of (wave, lane), out[1] window half, out[2] frame-maximum
+// slot of the lane when its target is not / out[3] is the extra column, out[4 + k] float position of the lane's k-th copy write into buffer b
+// (4 for a full wave, 2 for a half wave; the rest -1), out[8] float position of the lane's first window entry in buffer b
+int vph_split_maps(int S, int off, int wave, int lane, int b, int* out) {
+    if (S <= vit::kSplitFullRows || S >= vit::kSplitStates || off < 0 || off > 31 || wave < 0 || wave >= 8 || lane < 0 || lane > 63 || b < 0 || b > 1) return -1;
+    const bool hw = wave >= vit::kSplitFullWaves;
+    const int sh = off % 4, j = vit::split_lane_target(wave, lane), hh = hw ? vit::split_half_of(lane) : 0;
+    out[0] = j; out[1] = hh; out[2] = vit::split_fm_slot(lane, false); out[3] = vit::split_fm_slot(lane, true);
+    for (int k = 0; k < 4; ++k) {
+        out[4 + k] = -1;
+        if (!hw) out[4 + k] = vit::split_copy_pos(sh, j, b, k);
+        else if (k < 2) out[4 + k] = 4 + sh + j + hh * vit::split_upper_off(vit::kSplitCopyStride) + b * 4 * vit::kSplitCopyStride + vit::floor_copy_off(vit::kSplitCopyStride, k);
+    }
+    out[8] = vit::split_window_pos(S, off, sh, wave, lane, b);
+    return 0;
+}
 void vph_image(const vph_plan* p, unsigned char* out) { std::memcpy(out, p->image.data(), p->image.size()); }
 
 // Launch schedule of the packed checkpointed decode (vit::packed_ckpt_schedule), for the CPU tests.  Returns the number of launches,
