@@ -501,6 +501,33 @@ int vit_decode_logits(const vit_plan *plan, const float *logits, const vit_obs_p
                       const int64_t *lengths, void *workspace, size_t workspace_bytes, float *logE_out,
                       int32_t *states, float *loglik, vit_stream stream);
 
+/*
+ * The fused logits -> path decode with a bounded workspace: vit_decode_checkpointed()'s scheme with the fused workgroup as its
+ * forward launch.  Pass 1 builds every emission row once, in LDS, and keeps one delta row per segment of K = segment_frames frames
+ * plus the terminal state and the log-likelihood; pass 2 walks the segments from the last to the first: the fused workgroup builds
+ * the segment's emission rows AGAIN from the logits (the builders work per frame: the same bits), resumes the recursion from the
+ * segment's checkpoint row into K rows per song, and the segment is back-traced from the state the segment behind it decided.
+ * Neither a [B,T,S] emission tensor nor a [B,T] delta history exists: besides logits and outputs only the workspace is resident,
+ * 1.7 GB for [1024, 30000, 361] at K = 1024 where vit_decode_logits() takes 47 GB.  About twice the forward work.
+ *   arguments : as for vit_decode_logits(), without logE_out (the rows are built twice; the call exists to save memory), and
+ *               segment_frames as for vit_decode_checkpointed(): 64 .. 2^24, a value above T acts like T.
+ *   workspace >= vit_workspace_bytes_logits_checkpointed(plan, obs, B, T, segment_frames), which equals
+ *               vit_workspace_bytes_checkpointed(plan, B, T, segment_frames) wherever it is not 0.
+ * States and log-likelihoods are bit-identical to vit_decode_logits() and so to vit_obs_*() + vit_decode(..., VIT_ALGO_WAVE).
+ * Which plans and builders: those of vit_decode_logits().  Everything else, and a segment length out of range, gets 0 from the size
+ * function; a size > 0 means the decode launches.  Status, in this order: NULL plan or obs VIT_EINVAL; VIT_ENOTUPLOADED; NULL or
+ * misaligned workspace, B or T out of range VIT_EINVAL; a bad obs or obs->n_bins + 1 != S VIT_EINVAL; segment_frames out of range
+ * VIT_EINVAL; VIT_EUNSUPPORTED; NULL logits or states with B > 0 VIT_EINVAL; VIT_EWORKSPACE; B = 0 VIT_OK.  A refused call enqueues
+ * and writes nothing.  Honoured options: "wave_uniform", "bt_fast_rows"; ignored: "bt_chunks", "bt_warm" (every segment warms up 64
+ * frames, as in vit_decode_checkpointed() for wave-form plans), "bt_block_waves", "backtrace_form", "wave_history", "forward_form",
+ * "wave_two".  No host synchronisation, no allocation; the call drops the workspace's vit_forward() record and writes none.
+ */
+size_t vit_workspace_bytes_logits_checkpointed(const vit_plan *plan, const vit_obs_params *obs, int64_t B, int64_t T,
+                                               int64_t segment_frames);
+int vit_decode_logits_checkpointed(const vit_plan *plan, const float *logits, const vit_obs_params *obs, int64_t B, int64_t T,
+                                   const int64_t *lengths, void *workspace, size_t workspace_bytes, int32_t *states,
+                                   float *loglik, int64_t segment_frames, vit_stream stream);
+
 /* Event counts of the last vit_backtrace() on this workspace (banded plans; all zero for the kernels that do not count):
  * *offset = byte offset, inside the workspace, of an int32 [B][*n_per_song] device array (valid once the back-trace has run
  * on its stream): per song [0] tiles fetched, [1] span misses (the path left the fetched columns), [2] whole-row evaluations

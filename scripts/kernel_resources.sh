@@ -12,7 +12,7 @@ for line in sys.stdin:
     if t.startswith('Function Name'):
         if row: print(row)
         row = t.split(': ')[1][:70].ljust(72)
-    elif re.match(r'(VGPRs:|AGPRs|ScratchSize|Occupancy|VGPRs Spill)', t):
-        row += t.replace(' [bytes/lane]', '').replace(' [waves/SIMD]', '') + '  '
+    elif re.match(r'(VGPRs:|AGPRs|ScratchSize|Occupancy|VGPRs Spill|LDS Size)', t):
+        row += t.replace(' [bytes/lane]', '').replace(' [waves/SIMD]', '').replace(' [bytes/block]', '') + '  '
 if row: print(row)
 "

@@ -28,6 +28,7 @@ EXPORTS = (
     "vit_workspace_bytes_f64", "vit_decode_f64", "vit_workspace_bytes_f64_packed", "vit_decode_f64_packed",
     "vit_workspace_bytes_f64_checkpointed", "vit_decode_f64_checkpointed",
     "vit_workspace_bytes_f64_packed_checkpointed", "vit_decode_f64_packed_checkpointed", "vit_f64_packed_bounded_units",
+    "vit_workspace_bytes_logits_checkpointed", "vit_decode_logits_checkpointed",
 )
 ABI_VERSION = 4
 
@@ -146,6 +147,10 @@ def load() -> ctypes.CDLL:
     lib.vit_workspace_bytes_logits.argtypes = [vp, ctypes.POINTER(ObsParams), i64, i64]
     lib.vit_decode_logits.restype = i32
     lib.vit_decode_logits.argtypes = [vp, vp, ctypes.POINTER(ObsParams), i64, i64, vp, vp, sz, vp, vp, vp, vp]
+    lib.vit_workspace_bytes_logits_checkpointed.restype = sz
+    lib.vit_workspace_bytes_logits_checkpointed.argtypes = [vp, ctypes.POINTER(ObsParams), i64, i64, i64]
+    lib.vit_decode_logits_checkpointed.restype = i32
+    lib.vit_decode_logits_checkpointed.argtypes = [vp, vp, ctypes.POINTER(ObsParams), i64, i64, vp, vp, sz, vp, vp, i64, vp]
     lib.vit_forward_family.restype = i32
     lib.vit_forward_family.argtypes = [vp, i64, i32]
     lib.vit_voicing_map.restype = i32

@@ -835,29 +835,20 @@ size_t vit_workspace_bytes_checkpointed(const vit_plan* plan, int64_t B, int64_t
     return ck_layout(plan, family, B, T, segment_frames).bytes;
 }
 
-int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T, const int64_t* lengths,
-                            void* workspace, size_t workspace_bytes, int32_t* states, float* loglik, int64_t segment_frames,
-                            vit_stream stream) {
-    int rc = check_common(plan, B, T, workspace);
-    if (rc != VIT_OK) return rc;
-    if (!logE || !states) return VIT_EINVAL;
-    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
-    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
-    const int family = ck_family(plan);             // (everything that can refuse the plan is asked here, before anything is enqueued)
-    if (family == kFamNone) return VIT_EUNSUPPORTED;
-    const int64_t K = segment_frames > T ? T : segment_frames;
-    const CkLayout c = ck_layout(plan, family, B, T, K);
-    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
-    if (B == 0) return VIT_OK;
+namespace {
+extern "C++" {      // (a template over the forward callable: no C linkage)
+// The checkpointed decode of a padded batch once its entry point has accepted the call -- the driver of vit_decode_checkpointed and
+// vit_decode_logits_checkpointed, which differ in what a forward launch is: forward(f, segment) -> hipError_t runs pass 1 (segment
+// false: f.ckpt_every = K) or one segment (f.t_begin / f.t_end, resumed from f.init_rows) of `family` over the rows of c = ck_layout(plan,
+// family, B, T, K), K <= T; f.logE is the caller's `logE` (the fused launch has none).  The steps: the memset of `states` where lengths
+// are given, pass 1, then the segments from the last to the first with launch_segment_prep and segment_backtrace.
+template <typename Forward>
+int ck_decode(const vit_plan* plan, int family, const CkLayout& c, int64_t K, const void* logE, int64_t B, int64_t T, const int64_t* lengths,
+              void* workspace, int32_t* states, float* loglik, hipStream_t st, Forward&& forward) {
     stamp_erase(plan, workspace);
-    hipStream_t st = (hipStream_t)stream;
     uint8_t* ws = static_cast<uint8_t*>(workspace);
-    const bool f16 = emis_dtype == VIT_F16;
     const HistLayout lay = hist_layout(plan, family);
     const bool lane_bt = family == kFamGroup && !ck_sparse_applies(plan, kFamGroup);
-    auto forward = [&](const vit::FwdArgs& f) {
-        return launch_family(family, vit::WgVariant::Ckpt, f, f16, st);
-    };
     if (lengths)       // frames past a song's end: -1 (segments a song does not reach are skipped, not written)
         VIT_TRY(hipMemsetAsync(states, 0xff, (size_t)B * (size_t)T * sizeof(int32_t), st));
     int32_t* counters = reinterpret_cast<int32_t*>(ws + c.off_cnt);
@@ -878,7 +869,7 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
     a.ckpt_every = (int)K;
     a.t_begin = 0;
     a.t_end = (int)T;
-    VIT_TRY(forward(a));
+    VIT_TRY(forward(a, false));
 
     // ---- pass 2: segments, last to first
     vit::BtArgs b{};
@@ -910,7 +901,7 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
         f.t_end = (int)e0;
         f.init_rows = sgm > 0 ? reinterpret_cast<const float*>(ws + c.off_ckpt) + (size_t)(sgm - 1) * lay.SD : nullptr;
         f.init_stride = (int64_t)c.nseg * lay.SD;
-        VIT_TRY(forward(f));
+        VIT_TRY(forward(f, true));
         VIT_TRY(vit::launch_segment_prep(lengths, B, (int)T, (int)s0, (int)e0, states, reinterpret_cast<const int32_t*>(ws + c.off_last),
                                          reinterpret_cast<int64_t*>(ws + c.off_slen), reinterpret_cast<int32_t*>(ws + c.off_slast), st));
         b.T = (int)(e0 < T ? e0 - s0 + 1 : e0 - s0);      // the frame behind the segment is the sub-problem's terminal frame
@@ -918,6 +909,29 @@ int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dty
         VIT_TRY(segment_backtrace(plan, family, lane_bt, b, st));
     }
     return VIT_OK;
+}
+}  // extern "C++"
+}  // namespace
+
+int vit_decode_checkpointed(const vit_plan* plan, const void* logE, int emis_dtype, int64_t B, int64_t T, const int64_t* lengths,
+                            void* workspace, size_t workspace_bytes, int32_t* states, float* loglik, int64_t segment_frames,
+                            vit_stream stream) {
+    int rc = check_common(plan, B, T, workspace);
+    if (rc != VIT_OK) return rc;
+    if (!logE || !states) return VIT_EINVAL;
+    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
+    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
+    const int family = ck_family(plan);             // (everything that can refuse the plan is asked here, before anything is enqueued)
+    if (family == kFamNone) return VIT_EUNSUPPORTED;
+    const int64_t K = segment_frames > T ? T : segment_frames;
+    const CkLayout c = ck_layout(plan, family, B, T, K);
+    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
+    if (B == 0) return VIT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const bool f16 = emis_dtype == VIT_F16;
+    return ck_decode(plan, family, c, K, logE, B, T, lengths, workspace, states, loglik, st, [&](const vit::FwdArgs& f, bool) {
+        return launch_family(family, vit::WgVariant::Ckpt, f, f16, st);
+    });
 }
 
 
@@ -1822,6 +1836,57 @@ int vit_decode_logits(const vit_plan* plan, const float* logits, const vit_obs_p
     rc = backtrace_impl(plan, nullptr, 0, false, B, T, lengths, workspace, workspace_bytes, states, stream);
     stamp_erase(plan, workspace);
     return rc;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The fused decode under a workspace budget: vit_decode_checkpointed's scheme and driver (ck_decode) with the fused workgroup
+// (fused_ckpt.hip) as the forward launch of the wave family -- pass 1 builds every emission row once and keeps the checkpoint rows, each
+// segment builds its rows again from the logits.  Plans and builders: vit_decode_logits's that the checkpointed decode serves in the
+// wave family; the workspace is vit_decode_checkpointed's for the same plan.
+namespace {
+
+// the ONE predicate behind vit_workspace_bytes_logits_checkpointed and vit_decode_logits_checkpointed
+bool lgck_applies(const vit_plan* p, const vit_obs_params* obs) { return lg_applies(p, obs) && ck_family(p) == kFamWave; }
+
+}  // namespace
+
+size_t vit_workspace_bytes_logits_checkpointed(const vit_plan* plan, const vit_obs_params* obs, int64_t B, int64_t T, int64_t segment_frames) {
+    if (!plan || !obs || B < 0 || T < 1 || !ck_segment_ok(segment_frames)) return 0;
+    if (!lgck_applies(plan, obs)) return 0;
+    return ck_layout(plan, kFamWave, B, T, segment_frames).bytes;
+}
+
+int vit_decode_logits_checkpointed(const vit_plan* plan, const float* logits, const vit_obs_params* obs, int64_t B, int64_t T,
+                                   const int64_t* lengths, void* workspace, size_t workspace_bytes, int32_t* states, float* loglik,
+                                   int64_t segment_frames, vit_stream stream) {
+    if (!plan || !obs) return VIT_EINVAL;
+    if (!plan->dev_image) return VIT_ENOTUPLOADED;
+    int rc = check_common(plan, B, T, workspace);
+    if (rc != VIT_OK) return rc;
+    if (obs->mode < 0 || obs->mode > 2 || obs->n_bins < 2 || (int64_t)obs->n_bins + 1 != plan->S) return VIT_EINVAL;
+    if (!ck_segment_ok(segment_frames)) return VIT_EINVAL;
+    if (!lgck_applies(plan, obs)) return VIT_EUNSUPPORTED;    // (everything that can refuse the plan or the builder is asked here)
+    if (B > 0 && (!logits || !states)) return VIT_EINVAL;
+    const int64_t K = segment_frames > T ? T : segment_frames;
+    const CkLayout c = ck_layout(plan, kFamWave, B, T, K);
+    if (workspace_bytes < c.bytes) return VIT_EWORKSPACE;
+    if (B == 0) return VIT_OK;
+    hipStream_t st = (hipStream_t)stream;
+    vit::FusedArgs fa{};
+    fa.logits = logits;
+    fa.logE_out = nullptr;           // (the rows are built twice; the call exists to save memory)
+    fa.mode = obs->mode;
+    fa.n_bins = obs->n_bins;
+    fa.spw = obs->spw;
+    fa.threshold = obs->threshold_logit;
+    fa.offset = obs->mode == 0 ? obs->offset : 0.0;
+    fa.scale = obs->mode == 0 ? obs->scale : 0.0;
+    fa.prior = obs->mode == 2 ? obs->prior : nullptr;
+    return ck_decode(plan, kFamWave, c, K, nullptr, B, T, lengths, workspace, states, loglik, st, [&](const vit::FwdArgs& f, bool segment) {
+        fa.f = f;
+        fa.f.hist_half = 0;
+        return vit::launch_fused_logits_ckpt(fa, segment, st);
+    });
 }
 
 int vit_voicing_map(const int32_t* states, int64_t n, int32_t n_bins, uint8_t* voiced, int32_t* bins,

@@ -194,6 +194,11 @@ constexpr bool fused_logits_applies(int S, int wave_ok, int wave_npl, int wave_d
            ((mode == 0 && spw == 5) || (mode == 1 && spw == 15) || (mode == 2 && spw == 5));
 }
 hipError_t launch_fused_logits(const FusedArgs& fa, hipStream_t st);
+// fused_ckpt.hip: the same workgroup for vit_decode_logits_checkpointed, with FwdArgs' checkpoint fields as wave.hip reads them (WaveHist::CkptPass /
+// Segment).  segment false = pass 1: f.ckpt_every = K, f.hist_rows = segments per song (the last row is the scratch row).  segment true:
+// frames f.t_begin .. min(f.t_end, length) - 1 resumed from f.init_rows (t_begin > 0), row t at t - t_begin of the song's f.hist_rows
+// rows; the emission rows are rebuilt from the logits.  logE_out is honoured by both but the decode passes none.
+hipError_t launch_fused_logits_ckpt(const FusedArgs& fa, bool segment, hipStream_t st);
 
 // f64.hip: the float64-accumulating decode (vit_decode_f64): float32 parameters and emissions, d (the reference's float64 T1) in double.
 // The floor form in double, so what it serves is what the floor form is proven and instantiated for: banded plans with floor_ok, no

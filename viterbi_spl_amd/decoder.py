@@ -792,17 +792,32 @@ class ViterbiDecoder:
         op = self._obs_struct(obs)
         return int(_lib.load().vit_workspace_bytes_logits(self._plan, ctypes.byref(op), int(B), int(T)))
 
-    def decode_logits(self, logits: torch.Tensor, obs: dict, lengths: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.int64,
-                      emissions_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Pitch logits -> (states, loglik) in one forward launch (``vit_decode_logits``): the emission builder runs inside the
-        forward pass and its rows never reach device memory -- no ``[B, T, S]`` emission tensor (44 GB for 1024 songs of 30000
-        frames).  ``logits``: ``[B, T, cols]`` or ``[T, cols]`` float32 on the GPU, ``cols`` = n_bins ("softmax": n_bins + 1,
-        unvoiced first); ``obs``: ``obs_params(...)``.  States and log-likelihoods are bit-identical to the builder of
-        ``emissions.py`` followed by ``decode(algo="wave")``.  ``emissions_out``: an optional contiguous float32 ``[B, T, S]`` (or
-        ``[T, S]``) tensor that also receives the emission rows (frames inside a song's length).  For plans with the wave form
-        whose extra column is the last state (S = 321 / 361) and the reference's builder geometries; anything else raises
-        ``ViterbiHipError`` before anything is enqueued.  ``workspace``: as for ``decode_checkpointed``."""
-        lib = _lib.load()
+    _LOGITS_UNSERVED = ("the fused logits decode needs a plan with the wave form whose extra column is the last state "
+                        "(S = 321 / 361), n_bins = S - 1, and a builder geometry of the reference (shaun / scaled "
+                        "softmax with peak width 5, softmax with 15): build the emissions and use decode()")
+
+    def workspace_bytes_logits_checkpointed(self, obs: dict, B: int, T: int, segment_frames: int) -> int:
+        """Workspace bytes of ``decode_logits_checkpointed`` (what ``workspace_bytes_checkpointed`` answers for the same plan); 0 when
+        the fused kernel does not serve this plan or builder geometry, or ``segment_frames`` is outside 64 .. 2**24."""
+        op = self._obs_struct(obs)
+        return int(_lib.load().vit_workspace_bytes_logits_checkpointed(self._plan, ctypes.byref(op), int(B), int(T), int(segment_frames)))
+
+    def plan_workspace_logits(self, obs: dict, B: int, T: int, max_workspace_bytes: Optional[int] = None) -> dict:
+        """How ``decode_logits`` decodes ``[B, T, cols]`` logits under a workspace budget (bytes; None = whatever it takes):
+        ``{"mode": "full", "workspace_bytes": n}`` -- ``vit_decode_logits`` with the whole delta history fits -- or ``{"mode":
+        "checkpointed", "segment_frames": K, "workspace_bytes": n}`` -- ``vit_decode_logits_checkpointed`` with the largest K of 8192,
+        4096, ..., 64 that fits.  Raises ViterbiHipError when nothing fits (the text names the least need) or the plan or builder is
+        not served.  Both modes decode the same bits."""
+        need = self.workspace_bytes_logits(obs, B, T)
+        if need == 0 and B > 0:
+            raise _lib.ViterbiHipError(self._LOGITS_UNSERVED)
+        budget = None if max_workspace_bytes is None else int(max_workspace_bytes)
+        return self._plan_segments(need, lambda K: self.workspace_bytes_logits_checkpointed(obs, B, T, K), budget,
+                                   lambda least: f"no fused logits decode of a [{B}, {T}] batch fits a workspace of {budget} bytes: the least "
+                                                 f"any segment length needs is {least} (the whole history needs {need})")
+
+    def _check_logits(self, logits: torch.Tensor, obs: dict, lengths: Optional[torch.Tensor]) -> Tuple[torch.Tensor, bool]:
+        """The argument checks of the fused logits decodes -> (the logits as [B, T, cols], whether the caller's were [T, cols])."""
         if not isinstance(logits, torch.Tensor) or logits.device != self.device:
             raise ValueError("logits must be a torch tensor on the decoder's device")
         cols = obs["n_bins"] + (1 if obs["mode"] == 1 else 0)
@@ -810,8 +825,67 @@ class ViterbiDecoder:
         lg = logits.unsqueeze(0) if single else logits
         if lg.dtype != torch.float32 or lg.dim() != 3 or lg.shape[2] != cols or lg.shape[1] < 1 or not lg.is_contiguous():
             raise ValueError(f"logits must be a C-contiguous float32 [B,T,{cols}] or [T,{cols}] tensor with T >= 1")
+        self._check_lengths(lengths, lg.shape[0])
+        return lg, single
+
+    def decode_logits_checkpointed(self, logits: torch.Tensor, obs: dict, segment_frames: int = 1024, lengths: Optional[torch.Tensor] = None,
+                                   out_dtype: torch.dtype = torch.int64, workspace: Optional[torch.Tensor] = None
+                                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``decode_logits`` with a bounded workspace (``vit_decode_logits_checkpointed``): about ``T / segment_frames +
+        segment_frames`` delta rows per song instead of ``T``, and still no emission tensor -- a segment's emission rows are built
+        again from the logits, inside the workgroup that consumes them.  Same states, same log-likelihood, bit for bit; about twice
+        the forward work.  There is no ``emissions_out``: the call exists to save memory.  Plans and builders: those of
+        ``decode_logits``; anything else raises ``ViterbiHipError`` before anything is enqueued.  ``workspace``: as for
+        ``decode_checkpointed``."""
+        lib = _lib.load()
+        lg, single = self._check_logits(logits, obs, lengths)
         B, T, _ = lg.shape
-        self._check_lengths(lengths, B)
+        K = int(segment_frames)
+        op = self._obs_struct(obs)
+        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
+        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
+        if B > 0:
+            need = int(lib.vit_workspace_bytes_logits_checkpointed(self._plan, ctypes.byref(op), B, T, K))
+            if need == 0:
+                raise _lib.ViterbiHipError("the checkpointed fused logits decode needs 64 <= segment_frames <= 2**24; " + self._LOGITS_UNSERVED)
+            ws, ws_ptr, ws_bytes, mine = self._call_workspace(need, workspace)
+            with torch.cuda.device(self.device):
+                rc = lib.vit_decode_logits_checkpointed(self._plan, lg.data_ptr(), ctypes.byref(op), B, T,
+                                                        lengths.data_ptr() if lengths is not None else None, ws_ptr, ws_bytes,
+                                                        states.data_ptr(), loglik.data_ptr(), K, torch.cuda.current_stream(self.device).cuda_stream)
+            _lib.check(rc, "vit_decode_logits_checkpointed")
+            if mine:
+                torch.cuda.current_stream(self.device).synchronize()
+            del ws
+        if out_dtype != torch.int32:
+            states = states.to(out_dtype)
+        return (states[0], loglik[0]) if single else (states, loglik)
+
+    def decode_logits(self, logits: torch.Tensor, obs: dict, lengths: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.int64,
+                      emissions_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                      max_workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Pitch logits -> (states, loglik) in one forward launch (``vit_decode_logits``): the emission builder runs inside the
+        forward pass and its rows never reach device memory -- no ``[B, T, S]`` emission tensor (44 GB for 1024 songs of 30000
+        frames).  ``logits``: ``[B, T, cols]`` or ``[T, cols]`` float32 on the GPU, ``cols`` = n_bins ("softmax": n_bins + 1,
+        unvoiced first); ``obs``: ``obs_params(...)``.  States and log-likelihoods are bit-identical to the builder of
+        ``emissions.py`` followed by ``decode(algo="wave")``.  ``emissions_out``: an optional contiguous float32 ``[B, T, S]`` (or
+        ``[T, S]``) tensor that also receives the emission rows (frames inside a song's length).  For plans with the wave form
+        whose extra column is the last state (S = 321 / 361) and the reference's builder geometries; anything else raises
+        ``ViterbiHipError`` before anything is enqueued.  ``workspace``: as for ``decode_checkpointed``.
+        ``max_workspace_bytes``: a budget for the delta history (``plan_workspace_logits``): where the whole history does not fit,
+        the decode runs as ``decode_logits_checkpointed`` with the largest segment length that does -- the same bits; that form
+        writes no emissions, so ``emissions_out`` with such a budget is a ``ValueError``."""
+        lib = _lib.load()
+        lg, single = self._check_logits(logits, obs, lengths)
+        B, T, _ = lg.shape
+        if B > 0 and max_workspace_bytes is not None:
+            mode = self.plan_workspace_logits(obs, B, T, int(max_workspace_bytes))
+            if mode["mode"] == "checkpointed":
+                if emissions_out is not None:
+                    raise ValueError(f"emissions_out needs the full-history decode, whose {self.workspace_bytes_logits(obs, B, T)} bytes of "
+                                     f"workspace exceed max_workspace_bytes = {int(max_workspace_bytes)}")
+                return self.decode_logits_checkpointed(logits, obs, segment_frames=mode["segment_frames"], lengths=lengths,
+                                                       out_dtype=out_dtype, workspace=workspace)
         if emissions_out is not None:
             eo = emissions_out
             if (eo.dtype != torch.float32 or eo.device != self.device or not eo.is_contiguous() or
@@ -823,9 +897,7 @@ class ViterbiDecoder:
         if B > 0:
             need = int(lib.vit_workspace_bytes_logits(self._plan, ctypes.byref(op), B, T))
             if need == 0:
-                raise _lib.ViterbiHipError("the fused logits decode needs a plan with the wave form whose extra column is the last state "
-                                           "(S = 321 / 361), n_bins = S - 1, and a builder geometry of the reference (shaun / scaled "
-                                           "softmax with peak width 5, softmax with 15): build the emissions and use decode()")
+                raise _lib.ViterbiHipError(self._LOGITS_UNSERVED)
             ws, ws_ptr, ws_bytes, mine = self._call_workspace(need, workspace)
             with torch.cuda.device(self.device):
                 rc = lib.vit_decode_logits(self._plan, lg.data_ptr(), ctypes.byref(op), B, T, lengths.data_ptr() if lengths is not None else None,

@@ -235,7 +235,7 @@ class _PreparedViterbi:
         """This class's emission-builder arguments for ``ViterbiDecoder.decode_logits``, computed as emissions.py computes them."""
         raise NotImplementedError
 
-    def decode_logits_batch(self, logits, lengths=None, note_range=None, fused=False):
+    def decode_logits_batch(self, logits, lengths=None, note_range=None, fused=False, max_workspace_bytes=None):
         """``decode_logits`` over a batch: logits ``[B, frames, columns]`` (NumPy or torch), ``lengths`` an optional int64 ``[B]``
         tensor (frames past a song's length: voiced False, bins -1).  Returns ``(voiced bool[B, T], bins int32[B, T])`` plus
         ``notes float32[B, T]`` when ``note_range`` is given; row b equals ``decode_logits(logits[b])``.
@@ -244,7 +244,10 @@ class _PreparedViterbi:
         less device memory), the same bits; raises ``ViterbiHipError`` where the plan is not served (the 722-state grids).
         Measured on one MI355X (`[B, 30000, 360]`, profiles/fused_logits_time.json): the fused path is slower at every batch size --
         2.7x at 256 songs, 1.7x at 512, 1.23-1.27x at 1024 and 2048 -- there is no crossover, so it is for batches whose emission
-        tensor does not fit, and the default stays unfused."""
+        tensor does not fit, and the default stays unfused.
+        ``max_workspace_bytes``: a budget for the decoder's workspace; the same result.  ``fused=True``: ``ViterbiDecoder.decode_logits``
+        falls to the checkpointed fused decode (``vit_decode_logits_checkpointed``: neither an emission tensor nor a whole delta
+        history); ``fused=False``: ``ViterbiDecoder.decode(max_workspace_bytes=)``, which still needs the emission tensor."""
         dev = self._decoder.device
         lg = logits if isinstance(logits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(logits, np.float32))
         lg = lg.to(dev).contiguous()
@@ -252,9 +255,11 @@ class _PreparedViterbi:
         if lengths is not None:
             lengths = (lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths), dtype=torch.int64)).to(dev)
         if fused:
-            states, _ = self._decoder.decode_logits(lg, self._obs_params(), lengths=lengths, out_dtype=torch.int32)
+            states, _ = self._decoder.decode_logits(lg, self._obs_params(), lengths=lengths, out_dtype=torch.int32,
+                                                    max_workspace_bytes=max_workspace_bytes)
         else:
-            states, _ = self._decoder.decode(self._log_emissions(lg), lengths=lengths, out_dtype=torch.int32)
+            states, _ = self._decoder.decode(self._log_emissions(lg), lengths=lengths, out_dtype=torch.int32,
+                                             max_workspace_bytes=max_workspace_bytes)
         if note_range is None:
             return self._decoder.voicing(states, self.num_freq_bins)
         return self._decoder.voicing_notes(states, note_range, self.num_freq_bins)
