@@ -1,7 +1,8 @@
 """GPU tests of the bounded-workspace decode for plans without the wave form (the 722-state grids): banded plans with the floor
 form (jdc722, jdc721, imm722w: the checkpoint / resume variant of the one-target floor kernel, sparse back-trace over the workgroup
 rows) and step plans (durrieu722, durrieu721: the same variant of the step kernel, lazy back-trace per segment).  Everything through
-ViterbiDecoder.  Bar: states and log-likelihood bit-equal to the CPU oracle run on every song alone."""
+ViterbiDecoder.  Bar: states and log-likelihood bit-equal to the CPU oracle run on every song alone.
+GROUP_PLANS are (W, NWT) = (84, 12) and (128, 12); every other pair of the variant: tests/test_gpu_floor_variant_grid.py."""
 import time
 
 import numpy as np

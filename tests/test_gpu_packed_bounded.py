@@ -2,7 +2,8 @@
 workspace budget by the plans without the wave form -- the 722- and 721-state floor plans (jdc722, jdc721, imm722w: the
 packed-checkpoint variant of the one-target floor kernel, sparse back-trace over the units) and step plans (durrieu722, durrieu721:
 the same variant of the step kernel, lazy back-trace over the units).  Bar: states and log-likelihood bits equal to decode_packed
-and to the CPU oracle run on every recording alone."""
+and to the CPU oracle run on every recording alone.
+GROUP_PLANS are (W, NWT) = (84, 12) and (128, 12); every other pair of the variant: tests/test_gpu_floor_variant_grid.py."""
 import numpy as np
 import pytest
 import torch

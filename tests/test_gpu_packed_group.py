@@ -1,7 +1,8 @@
 """GPU tests of the packed ragged decode for plans without the wave form (the 722-state grids): banded plans with the floor
 form (jdc722, jdc721, imm722w: one workgroup per forward slot, lane back-trace) and step plans (durrieu722, durrieu721: the step
 kernel per slot, lazy back-trace over per-song chunk lists).  All through the C ABI via ViterbiDecoder.  Bar: states bit-exact and
-log-likelihood bit-equal against the CPU oracle run on every song alone."""
+log-likelihood bit-equal against the CPU oracle run on every song alone.
+GROUP_PLANS are (W, NWT) = (84, 12) and (128, 12); every other pair of the variant: tests/test_gpu_floor_variant_grid.py."""
 import time
 
 import numpy as np
