@@ -528,6 +528,59 @@ int vit_decode_logits_checkpointed(const vit_plan *plan, const float *logits, co
                                    const int64_t *lengths, void *workspace, size_t workspace_bytes, int32_t *states,
                                    float *loglik, int64_t segment_frames, vit_stream stream);
 
+/*
+ * Streaming decode: the forward pass advances as chunks of emission rows arrive, the back-trace runs whenever a path is wanted.
+ * The callers of the reference's decoders receive a recording batch by batch (tonet/for_paper.py:2246-2327) and decode behind the
+ * last one; a session spends the forward recursion beside the acoustic model instead of behind it.  History rows, back-trace and
+ * results are exactly those of vit_decode() of the same recordings: states and log-likelihoods are bit-identical for any chunking.
+ *
+ *   vit_workspace_bytes_stream(plan, B, T_cap)  bytes of a session of B recordings of at most T_cap frames each: the [B, T_cap] delta
+ *               rows, terminal states and log-likelihoods, device lengths, the per-launch tables and the back-trace's chunk entries,
+ *               flags and counters.  0 = the plan is not served (or NULL plan, B < 1, T_cap < 1, either above 2^30).
+ *   vit_stream_open()       the session: host memory only (plan, workspace pointer, per-song positions, emission type).  The
+ *               workspace is caller-owned, 256-byte aligned, and must outlive the session, as must the plan.  Nothing is enqueued.
+ *   vit_stream_append()     logE: device [B, n, S] of emis_dtype, rows [b][0 .. counts[b]) are the next counts[b] frames of recording b
+ *               (counts: HOST [B], 0 <= counts[b] <= n; NULL = n for every recording).  One kernel launch on `stream`; where the
+ *               recordings are not all at one position with one count, also one upload of two int32 [B] tables through the plan's
+ *               pinned staging buffer, which first waits on the host for the upload before it (as vit_decode_packed()).  No other
+ *               host synchronisation.  Emission rows are never read again: the chunk buffer may be reused once the append's kernel
+ *               has run in stream order.  The emission type is fixed by the first append (vit_stream_reset() frees it).
+ *   vit_stream_lengths()    frames appended per recording so far, HOST [B].
+ *   vit_stream_backtrace()  decodes the recordings AS THEY STAND: states[b][0 .. len_b) = the best path of the len_b frames so far,
+ *               states[b][len_b .. states_stride) = -1, loglik[b] (device [B], may be NULL) = its log-likelihood.  The session stays
+ *               open: more frames may follow, and a later back-trace supersedes this one.
+ *   vit_stream_reset()      every position back to 0 (host only); the workspace is reused as it is.
+ *   vit_stream_close()      frees the session (not the workspace).  NULL is allowed.
+ * The caller orders the calls of one session -- appends, back-traces and whatever rewrites a chunk or the workspace -- on one stream
+ * or by events, as for vit_forward() / vit_backtrace().  Two sessions of one plan may run on two streams from one thread.
+ *
+ * Which plans: those with a stream instantiation of their workgroup forward kernel -- banded plans whose one-maximum ("floor") form
+ * is proven, without dense rows, with an instantiated window width and an idle target slot (the reference's 321- and 361-state grids,
+ * the 721- / 722-state grids of jdc and imm's wide matrix), and step-structured plans of the Durrieu geometry.  Unstructured
+ * matrices, banded plans that only have the scan form and plans with dense rows get size 0 and VIT_EUNSUPPORTED.  A session always
+ * runs one recording per workgroup, whatever B: it is meant for a few recordings at a time.  float32 history only.
+ *
+ * Status.  vit_stream_open(): NULL plan / out / workspace, B or T_cap out of range, misaligned workspace VIT_EINVAL; then
+ * VIT_ENOTUPLOADED; then VIT_EUNSUPPORTED; then VIT_EWORKSPACE.  vit_stream_append(): NULL session or logE, a bad emis_dtype, n < 1,
+ * an emis_dtype other than the first append's, a count outside [0, n] or pos[b] + counts[b] > T_cap for any b: VIT_EINVAL, with
+ * nothing enqueued and no position moved.  vit_stream_backtrace(): NULL session or states, a recording still at length 0,
+ * states_stride < max len_b: VIT_EINVAL; "backtrace_form" 4 where the lane kernel does not apply: VIT_EUNSUPPORTED.  A refused call
+ * enqueues and writes nothing.  Honoured options: "bt_chunks", "bt_warm", "bt_fast_rows", "win_shift", and "backtrace_form" 4 (banded
+ * plans); ignored: "forward_form", "step_form", "wave_*", "backtrace_form" 1 / 2 (the back-trace is the sparse kernel, the lane form
+ * where that does not serve the rows, the lazy kernel for step plans).  No vit_forward() record is written; the one the workspace
+ * carried is dropped by vit_stream_open().
+ */
+typedef struct vit_session vit_session; /* opaque: one streaming session */
+size_t vit_workspace_bytes_stream(const vit_plan *plan, int64_t B, int64_t T_cap);
+int vit_stream_open(const vit_plan *plan, int64_t B, int64_t T_cap, void *workspace, size_t workspace_bytes, vit_session **out);
+int vit_stream_append(vit_session *s, const void *logE /* device [B, n, S] */, int emis_dtype, int64_t n,
+                      const int64_t *counts /* HOST [B], 0 <= counts[b] <= n, or NULL = n for every song */, vit_stream stream);
+int vit_stream_lengths(const vit_session *s, int64_t *lengths /* HOST [B] */);
+int vit_stream_backtrace(vit_session *s, int32_t *states /* device [B, states_stride] */, int64_t states_stride,
+                         float *loglik /* device [B] or NULL */, vit_stream stream);
+int vit_stream_reset(vit_session *s);
+void vit_stream_close(vit_session *s);
+
 /* Event counts of the last vit_backtrace() on this workspace (banded plans; all zero for the kernels that do not count):
  * *offset = byte offset, inside the workspace, of an int32 [B][*n_per_song] device array (valid once the back-trace has run
  * on its stream): per song [0] tiles fetched, [1] span misses (the path left the fetched columns), [2] whole-row evaluations

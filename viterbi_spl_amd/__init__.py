@@ -5,7 +5,7 @@ no CPU fallback (see ``_lib.load``).
 """
 __version__ = "0.2.0"
 
-from .decoder import ViterbiDecoder, decode, get_decoder  # noqa: F401
+from .decoder import DecodeStream, ViterbiDecoder, decode, get_decoder  # noqa: F401
 from .emissions import activation_log_emissions  # noqa: F401
 from .reference_api import (  # noqa: F401
     ImmViterbi, RecordingAccumulator, ScaledSoftMaxViterbi, SoftMaxViterbi, Viterbi, tf_viterbi_librosa_fn, viterbi_librosa_c_fn,

@@ -29,6 +29,8 @@ EXPORTS = (
     "vit_workspace_bytes_f64_checkpointed", "vit_decode_f64_checkpointed",
     "vit_workspace_bytes_f64_packed_checkpointed", "vit_decode_f64_packed_checkpointed", "vit_f64_packed_bounded_units",
     "vit_workspace_bytes_logits_checkpointed", "vit_decode_logits_checkpointed",
+    "vit_workspace_bytes_stream", "vit_stream_open", "vit_stream_append", "vit_stream_lengths", "vit_stream_backtrace",
+    "vit_stream_reset", "vit_stream_close",
 )
 ABI_VERSION = 4
 
@@ -151,6 +153,20 @@ def load() -> ctypes.CDLL:
     lib.vit_workspace_bytes_logits_checkpointed.argtypes = [vp, ctypes.POINTER(ObsParams), i64, i64, i64]
     lib.vit_decode_logits_checkpointed.restype = i32
     lib.vit_decode_logits_checkpointed.argtypes = [vp, vp, ctypes.POINTER(ObsParams), i64, i64, vp, vp, sz, vp, vp, i64, vp]
+    lib.vit_workspace_bytes_stream.restype = sz
+    lib.vit_workspace_bytes_stream.argtypes = [vp, i64, i64]
+    lib.vit_stream_open.restype = i32
+    lib.vit_stream_open.argtypes = [vp, i64, i64, vp, sz, ctypes.POINTER(vp)]
+    lib.vit_stream_append.restype = i32
+    lib.vit_stream_append.argtypes = [vp, vp, i32, i64, vp, vp]
+    lib.vit_stream_lengths.restype = i32
+    lib.vit_stream_lengths.argtypes = [vp, vp]
+    lib.vit_stream_backtrace.restype = i32
+    lib.vit_stream_backtrace.argtypes = [vp, vp, i64, vp, vp]
+    lib.vit_stream_reset.restype = i32
+    lib.vit_stream_reset.argtypes = [vp]
+    lib.vit_stream_close.restype = None
+    lib.vit_stream_close.argtypes = [vp]
     lib.vit_forward_family.restype = i32
     lib.vit_forward_family.argtypes = [vp, i64, i32]
     lib.vit_voicing_map.restype = i32

@@ -150,8 +150,16 @@ static_assert(FloorSplitLds::DC == kSplitCopyStride && FloorSplitLds::fmg == kSp
 //     unit_seg[u] * K .. of song unit_song[u] (emission rows at offsets[song]) from row ckpt_base[song] + segment - 1 of init_rows
 //     (segment 0: from the prior) into rows u * hist_rows .. of a.hist, one frame past the segment where the song goes on; the row in
 //     front of those rows takes the first frame's frame-maximum store (the caller passes a.hist one row into the unit's K + 2 rows).
-// V = Plain compiles to the code it was before the variants existed.  (PK / CK / PC below: V is that variant; PKx / CKx: what the
-// packed-checkpoint variant shares with the packed and with the checkpoint / resume variant.)
+// V = Stream is the session variant (vit_stream_append; instantiated in banded_stream.hip): the workgroup's song gets its next cnt
+// frames t0 .. t0 + cnt - 1 (per song from the launch's tables, or the same for every song: wg_cursor.inc; cnt = 0 leaves without
+// writing).  Emission row t is row t - t0 of the song's chunk, and the prefetch is clamped to the chunk's last row for this song.  History
+// rows sit at their absolute index in the Plain layout, and Plain's stores are the ones used: frame t writes row t and, from lane S, M of
+// frame t - 1 into pad column S of row t - 1.  t0 > 0 publishes row t0 - 1 of the song's own rows instead of log_pi + e_0 and so
+// re-forms M of that frame, as Ckpt's segment does -- its first frame therefore completes the row the launch before ended with.  No
+// frame is run past the chunk: M of the newest row is stored by the next launch, and the back-trace of a song of n frames reads the
+// pad column of rows 0 .. n - 2 only.  The terminal state and the log-likelihood are Plain's, written after every launch.
+// V = Plain compiles to the code it was before the variants existed.  (PK / CK / PC / ST below: V is that variant; PKx / CKx: what the
+// packed-checkpoint variant shares with the packed and with the checkpoint / resume variant; RSx: CKx or ST.)
 template <int W, int NWT, int NXT, int PF, typename ET, WgVariant V = WgVariant::Plain, bool WPR = false>
 __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs a) {
     static_assert(!WPR || V == WgVariant::Plain, "the per-wave probe exists for the plain kernel only");
@@ -159,6 +167,8 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     constexpr bool PK = V == WgVariant::Packed, CK = V == WgVariant::Ckpt, PC = V == WgVariant::PackedCkpt;
     constexpr bool PKx = PK || PC;                // the song loop and its per-song preamble
     constexpr bool CKx = CK || PC;                // the row selection of the stores, the resumed first frame
+    constexpr bool ST = V == WgVariant::Stream;   // the frames of one launch of a session, rows at their absolute index
+    constexpr bool RSx = CKx || ST;               // the frame loop starts at t1 (a launch may resume a song)
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NP = L::NP, DC = L::DC, BUF = L::BUF, WR = L::WR;
     float* dls = reinterpret_cast<float*>(smem) + L::dls;
@@ -259,6 +269,15 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
                 hist[(size_t)(ck_every > 0 ? ck_scratch : 0) * SD + jf] = d0;
             }
             produce(d0, 0, 0, 1);
+        } else if constexpr (ST) {   // frame 0, or the song's own row in front of this launch's first frame (M is re-formed from it)
+            float d0 = -INFINITY;
+            if (t0 > 0) {
+                if (tvf) d0 = hist[(size_t)(t0 - 1) * SD + jf];
+            } else if (tvf) {
+                d0 = reinterpret_cast<const float*>(a.image + a.off_logpi)[jf] + load_e<ET>(E + jf);
+                hist[jf] = d0;
+            }
+            produce(d0, 0, 0, 1);
         } else {
             const float d0 = tvf ? reinterpret_cast<const float*>(a.image + a.off_logpi)[jf] + load_e<ET>(E + jf) : -INFINITY;
             if (tvf) hist[jf] = d0;
@@ -268,7 +287,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         // and the s_waitcnt before a frame's "+ e" must not be what paces the recursion.
         float er[PF];
 #pragma unroll
-        for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)((CKx ? t1 : 1) + k < Tb ? (CKx ? t1 : 1) + k : Tb - 1) * S + jldf);
+        for (int k = 0; k < PF; ++k) er[k] = load_e<ET>(E + (size_t)((RSx ? t1 : 1) + k < Tb ? (RSx ? t1 : 1) + k : Tb - 1) * S + jldf);
 #pragma unroll
         for (int w = 0; w < WR; ++w) asm volatile("" ::"v"(aw[w]));
 #pragma unroll
@@ -400,7 +419,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
 #endif
         const unsigned long long clk0 = probe ? __builtin_amdgcn_s_memtime() : 0ull;
         const unsigned long long rt0 = probe ? __builtin_amdgcn_s_memrealtime() : 0ull;
-        int t = CKx ? t1 : 1;
+        int t = RSx ? t1 : 1;
         for (; t + PF - 1 < Tb; t += PF) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) frame(t + k, er[k], k);
@@ -409,7 +428,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         for (int k = 0; k < PF - 1; ++k)
             if (t + k < Tb) frame(t + k, er[k], k);
 
-        const int fb = (Tb - (CKx ? t1 : 1)) & 1;                             // buffer holding delta_{Tb-1}
+        const int fb = (Tb - (RSx ? t1 : 1)) & 1;                             // buffer holding delta_{Tb-1}
         if constexpr (PC) {         // pass 1 only, per song (uniform test)
             if (ck_every > 0) terminal_argmax_w(tvalid ? dls[4 + sh + fb * BUF + j] : -INFINITY, j, tvalid, tot, NWT, wv, lane, a.last_state, a.loglik, song);
         } else
@@ -480,12 +499,12 @@ static hipError_t with_nxt(int n_extras, F&& f) {
     return f(std::integral_constant<int, -1>{});
 }
 
-// A variant of the one-target floor kernel: one workgroup per slot (Packed, PackedCkpt pass 1), per song (Ckpt) or per unit (PackedCkpt,
-// a.unit_song set).  With `per_cu` the launch is replaced by the occupancy query of that instantiation at its dynamic LDS size.
+// A variant of the one-target floor kernel: one workgroup per slot (Packed, PackedCkpt pass 1), per song (Ckpt, Stream) or per unit
+// (PackedCkpt, a.unit_song set).  With `per_cu` the launch is replaced by the occupancy query of that instantiation at its dynamic LDS size.
 template <int W, int NWT, typename ET, WgVariant V>
 static hipError_t floor_variant_t(const FwdArgs& a, hipStream_t st, int* per_cu) {
     constexpr size_t ldsf = FloorLds<W, NWT, V>::bytes();
-    const int groups = V == WgVariant::Ckpt || (V == WgVariant::PackedCkpt && a.unit_song) ? (int)a.B : a.n_slots;
+    const int groups = V == WgVariant::Ckpt || V == WgVariant::Stream || (V == WgVariant::PackedCkpt && a.unit_song) ? (int)a.B : a.n_slots;
     return with_nxt<W>(a.n_extras, [&](auto nxt) -> hipError_t {
         auto kern = banded_floor_forward_kernel<W, NWT, decltype(nxt)::value, floor_pf<W>(), ET, V>;
         if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, NWT * 64, ldsf);
@@ -493,10 +512,10 @@ static hipError_t floor_variant_t(const FwdArgs& a, hipStream_t st, int* per_cu)
         return hipGetLastError();
     });
 }
-// the (W, NWT) pairs a variant is instantiated for: Packed every pair of the floor form, the checkpoint variants floor_ckpt_pair's
+// the (W, NWT) pairs a variant is instantiated for: Packed and Stream every pair of the floor form, the checkpoint variants floor_ckpt_pair's
 template <typename ET, WgVariant V>
 static hipError_t floor_variant_e(const FwdArgs& a, hipStream_t st, int* per_cu) {
-    constexpr bool packed = V == WgVariant::Packed;
+    constexpr bool packed = V == WgVariant::Packed || V == WgVariant::Stream;    // (floor_stream_applies is floor_packed_applies)
     if (!(packed ? floor_packed_applies(a.S, a.W, a.floor_ok != 0, a.n_dense) : floor_ckpt_applies(a.S, a.W, a.floor_ok != 0, a.n_dense)))
         return hipErrorInvalidConfiguration;
     return dispatch_width(a.W, [&](auto w) {

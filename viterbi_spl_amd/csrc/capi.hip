@@ -802,25 +802,27 @@ CkLayout ck_layout(const vit_plan* p, int family, int64_t B, int64_t T, int64_t 
 }
 
 // The back-trace of one segment of a checkpointed decode -- b.B sub-problems of b.T frames: the songs of vit_decode_checkpointed, the
-// units of one launch of the packed budgeted decode.  Step plans: the lazy kernel, one wave per (sub-problem, chunk); banded plans:
-// the sparse kernel, or the lane form where the caller found that the sparse one does not serve the rows (lane_bt; b.mask set).
-hipError_t segment_backtrace(const vit_plan* plan, int family, bool lane_bt, vit::BtArgs& b, hipStream_t st) {
-    const Tuning& tn = plan->tune;      // (bt_chunks is not consulted here)
+// units of one launch of the packed budgeted decode -- and of a streaming session (vit_stream_backtrace: the recordings as they stand).
+// Step plans: the lazy kernel, one wave per (sub-problem, chunk); banded plans: the sparse kernel, or the lane form where the caller
+// found that the sparse one does not serve the rows (lane_bt; b.mask set).  tune_chunks: "bt_chunks" is honoured (sessions only).
+hipError_t segment_backtrace(const vit_plan* plan, int family, bool lane_bt, vit::BtArgs& b, hipStream_t st, bool tune_chunks = false) {
+    const Tuning& tn = plan->tune;      // (bt_chunks is not consulted by the checkpointed decodes)
+    auto chunks_of = [&](int chunks, int cap) { return tune_chunks ? tuned_chunks(tn, chunks, cap) : chunks; };
     if (family == kFamStep) {
-        b.chunks = vit::backtrace_chunks(b.B, b.T);
+        b.chunks = chunks_of(vit::backtrace_chunks(b.B, b.T), vit::kBtMaxChunks);
         b.warm = tuned_warm(tn, vit::kBtWarm);
         return vit::launch_backtrace_rows_segment(b, st);
     }
     if (lane_bt) {
         b.warm = tuned_warm(tn, vit::kBtWarmSparse);
-        b.chunks = vit::lane_backtrace_chunks(b.B, b.T, plan->n_cus, b.warm);
+        b.chunks = chunks_of(vit::lane_backtrace_chunks(b.B, b.T, plan->n_cus, b.warm), vit::kLaneMaxChunks);
         if (b.chunks > 1) {         // the chunk flags of this segment
             const hipError_t e = hipMemsetAsync(b.mask, 0, (size_t)b.B * vit::kLaneMaskWords * sizeof(uint32_t), st);
             if (e != hipSuccess) return e;
         }
         return vit::launch_backtrace_lane(b, st);
     }
-    b.chunks = vit::sparse_backtrace_chunks(b.B, b.T, plan->n_cus);
+    b.chunks = chunks_of(vit::sparse_backtrace_chunks(b.B, b.T, plan->n_cus), vit::kBtMaxChunks);
     // KNOWN ASYMMETRY, kept: the wave family always warms up kBtWarmSparse frames and does NOT consult bt_warm; kFamGroup does
     b.warm = family == kFamWave ? vit::kBtWarmSparse : tuned_warm(tn, vit::kBtWarmSparse);
     return vit::launch_backtrace_sparse(b, st);
@@ -1888,6 +1890,198 @@ int vit_decode_logits_checkpointed(const vit_plan* plan, const float* logits, co
         return vit::launch_fused_logits_ckpt(fa, segment, st);
     });
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Streaming decode: a session owns [B, T_cap] history rows in the Plain layout of its workgroup family and advances the forward
+// recursion by one chunk of emission rows per vit_stream_append (WgVariant::Stream of the floor and step kernels: the frames
+// pos[b] .. pos[b] + counts[b] - 1 of song b, resumed from the song's own row pos[b] - 1).  Nothing reads an emission row twice, so
+// the chunk is the caller's again once the append's kernel has run.  vit_stream_backtrace decodes the recordings as they stand, with
+// the back-trace launches a checkpointed decode uses per segment (they take the song's row count apart from the frame count): the
+// sparse kernel or the lane form for banded plans, the lazy kernel for step plans.  A session always runs the workgroup family.
+struct vit_session {
+    const vit_plan* plan = nullptr;
+    int family = kFamNone;
+    int64_t B = 0, T_cap = 0;
+    uint8_t* ws = nullptr;
+    int dtype = -1;                     // emission type of the first append (-1: none yet)
+    std::vector<int64_t> pos;           // frames appended per song
+};
+
+namespace {
+
+// The workgroup family a session of this plan runs, kFamNone = none: the ONE predicate behind vit_workspace_bytes_stream and
+// vit_stream_open -- what has a Stream instantiation and a back-trace over the rows it writes.
+int st_family(const vit_plan* p) {
+    if (p->bp.ok)
+        return vit::floor_stream_applies(p->S, p->bp.W, p->bp.floor_ok, p->bp.n_dense) && (ck_sparse_applies(p, kFamGroup) || ck_lane_applies(p)) ? kFamGroup : kFamNone;
+    return step_applies(p) ? kFamStep : kFamNone;
+}
+
+struct StLayout {
+    size_t off_hist, off_cnt, off_mask, off_last, off_loglik, off_entry, off_len, off_tab, bytes;
+};
+StLayout st_layout(const vit_plan* p, int family, int64_t B, int64_t T_cap) {
+    StLayout s;
+    s.off_hist = 0;                                                               // [B][T_cap] rows
+    s.off_cnt = align256((size_t)B * (size_t)T_cap * (size_t)hist_layout(p, family).SD * sizeof(float));
+    s.off_mask = s.off_cnt + align256((size_t)B * vit::kBtCounters * sizeof(int32_t));      // the back-trace's counters, then the lane form's chunk flags
+    s.off_last = s.off_mask + align256((size_t)B * vit::kLaneMaskWords * sizeof(uint32_t));  // terminal states
+    s.off_loglik = s.off_last + align256((size_t)B * sizeof(int32_t));             // log-likelihoods of the lengths so far
+    s.off_entry = s.off_loglik + align256((size_t)B * sizeof(float));
+    s.off_len = s.off_entry + align256((size_t)B * vit::kLaneMaxChunks * sizeof(int32_t));  // device lengths [B] (written by the back-trace call)
+    s.off_tab = s.off_len + align256((size_t)B * sizeof(int64_t));                 // per-launch tables: positions [B], counts [B]
+    s.bytes = s.off_tab + align256((size_t)B * 2 * sizeof(int32_t));
+    return s;
+}
+inline bool st_shape_ok(int64_t B, int64_t T_cap) { return B >= 1 && T_cap >= 1 && B <= (int64_t)1 << 30 && T_cap <= (int64_t)1 << 30; }
+
+}  // namespace
+
+size_t vit_workspace_bytes_stream(const vit_plan* plan, int64_t B, int64_t T_cap) {
+    if (!plan || !st_shape_ok(B, T_cap)) return 0;
+    const int family = st_family(plan);
+    if (family == kFamNone) return 0;
+    return st_layout(plan, family, B, T_cap).bytes;
+}
+
+int vit_stream_open(const vit_plan* plan, int64_t B, int64_t T_cap, void* workspace, size_t workspace_bytes, vit_session** out) {
+    if (!plan || !out || !workspace || !st_shape_ok(B, T_cap) || ((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
+    if (!plan->dev_image) return VIT_ENOTUPLOADED;
+    const int family = st_family(plan);
+    if (family == kFamNone) return VIT_EUNSUPPORTED;
+    if (workspace_bytes < st_layout(plan, family, B, T_cap).bytes) return VIT_EWORKSPACE;
+    vit_session* s = new (std::nothrow) vit_session();
+    if (!s) return VIT_ENOMEM;
+    try {
+        s->pos.assign((size_t)B, 0);
+    } catch (const std::bad_alloc&) {
+        delete s;
+        return VIT_ENOMEM;
+    }
+    s->plan = plan;
+    s->family = family;
+    s->B = B;
+    s->T_cap = T_cap;
+    s->ws = static_cast<uint8_t*>(workspace);
+    stamp_erase(plan, workspace);       // (whatever vit_forward left here is the session's to overwrite)
+    *out = s;
+    return VIT_OK;
+}
+
+int vit_stream_append(vit_session* s, const void* logE, int emis_dtype, int64_t n, const int64_t* counts, vit_stream stream) {
+    if (!s || !logE) return VIT_EINVAL;
+    if (emis_dtype != VIT_F32 && emis_dtype != VIT_F16) return VIT_EINVAL;
+    if (n < 1 || n > (int64_t)1 << 30) return VIT_EINVAL;
+    if (s->dtype >= 0 && s->dtype != emis_dtype) return VIT_EINVAL;
+    const vit_plan* plan = s->plan;
+    const int64_t B = s->B;
+    bool uniform = true;                // every song at the same position, taking the same count: two scalars instead of the tables
+    int64_t any = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t c = counts ? counts[b] : n;
+        if (c < 0 || c > n || s->pos[(size_t)b] + c > s->T_cap) return VIT_EINVAL;
+        uniform = uniform && c == (counts ? counts[0] : n) && s->pos[(size_t)b] == s->pos[0];
+        any |= c;
+    }
+    if (any == 0) return VIT_OK;        // (nothing to append)
+    hipStream_t st = (hipStream_t)stream;
+    const StLayout L = st_layout(plan, s->family, B, s->T_cap);
+    vit::FwdArgs a{};
+    fwd_args_from_plan(plan, a);
+    a.debug = 0;
+    a.logE = logE;
+    a.lengths = nullptr;
+    a.hist = reinterpret_cast<float*>(s->ws + L.off_hist);
+    a.fmax = nullptr;
+    a.last_state = reinterpret_cast<int32_t*>(s->ws + L.off_last);
+    a.loglik = reinterpret_cast<float*>(s->ws + L.off_loglik);
+    a.B = B;
+    a.T = (int)s->T_cap;
+    a.hist_rows = s->T_cap;
+    a.init_stride = n * (int64_t)plan->S;
+    if (uniform) {
+        a.t_begin = (int)s->pos[0];
+        a.t_end = (int)(s->pos[0] + (counts ? counts[0] : n));
+    } else {
+        // the launch's tables through the plan's pinned staging buffer (the upload before must have read it)
+        const size_t bytes = (size_t)B * 2 * sizeof(int32_t);
+        const int rc = pk_stage(plan, bytes);
+        if (rc != VIT_OK) return rc;
+        int32_t* h = static_cast<int32_t*>(plan->pk_host);
+        for (int64_t b = 0; b < B; ++b) {
+            h[b] = (int32_t)s->pos[(size_t)b];
+            h[B + b] = (int32_t)(counts ? counts[b] : n);
+        }
+        const int ru = pk_upload(plan, s->ws + L.off_tab, bytes, st);
+        if (ru != VIT_OK) return ru;
+        a.unit_song = reinterpret_cast<const int32_t*>(s->ws + L.off_tab);
+        a.unit_seg = a.unit_song + B;
+    }
+    VIT_TRY(launch_family(s->family, vit::WgVariant::Stream, a, emis_dtype == VIT_F16, st));
+    for (int64_t b = 0; b < B; ++b) s->pos[(size_t)b] += counts ? counts[b] : n;
+    s->dtype = emis_dtype;
+    return VIT_OK;
+}
+
+int vit_stream_lengths(const vit_session* s, int64_t* lengths) {
+    if (!s || !lengths) return VIT_EINVAL;
+    std::memcpy(lengths, s->pos.data(), (size_t)s->B * sizeof(int64_t));
+    return VIT_OK;
+}
+
+int vit_stream_backtrace(vit_session* s, int32_t* states, int64_t states_stride, float* loglik, vit_stream stream) {
+    if (!s || !states) return VIT_EINVAL;
+    const vit_plan* plan = s->plan;
+    const int64_t B = s->B;
+    int64_t tmax = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        if (s->pos[(size_t)b] < 1) return VIT_EINVAL;       // (a song without a frame has no path)
+        tmax = std::max(tmax, s->pos[(size_t)b]);
+    }
+    if (states_stride < tmax || states_stride > (int64_t)1 << 30) return VIT_EINVAL;
+    const Tuning& tn = plan->tune;
+    const StLayout L = st_layout(plan, s->family, B, s->T_cap);
+    vit::BtArgs b{};
+    bt_args_from_plan(plan, b);
+    hist_layout_apply(hist_layout(plan, s->family), b);
+    b.aux_frames = 1;
+    b.hist = reinterpret_cast<const float*>(s->ws + L.off_hist);
+    b.hist_rows = s->T_cap;
+    b.last_state = reinterpret_cast<const int32_t*>(s->ws + L.off_last);
+    b.lengths = reinterpret_cast<const int64_t*>(s->ws + L.off_len);
+    b.states = states;
+    b.states_stride = states_stride;
+    b.entry = reinterpret_cast<int32_t*>(s->ws + L.off_entry);
+    b.B = B;
+    b.T = (int)tmax;                    // the frames the kernels walk and pad to; the caller's stride beyond: the memset below
+    b.skip_nonpositive = 1;             // (the launches of a checkpointed decode's segments: rows by hist_rows, states by states_stride)
+    b.counters = reinterpret_cast<int32_t*>(s->ws + L.off_cnt);
+    b.mask = s->family == kFamGroup ? reinterpret_cast<uint32_t*>(s->ws + L.off_mask) : nullptr;
+    const bool lane_bt = s->family == kFamGroup && (tn.backtrace_form == 4 || !ck_sparse_applies(plan, kFamGroup));
+    b.bt_form = s->family == kFamStep ? 1 : (lane_bt ? 4 : 0);
+    if (lane_bt && !vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    // the lengths so far through the plan's pinned staging buffer
+    const int rc = pk_stage(plan, (size_t)B * sizeof(int64_t));
+    if (rc != VIT_OK) return rc;
+    std::memcpy(plan->pk_host, s->pos.data(), (size_t)B * sizeof(int64_t));
+    const int ru = pk_upload(plan, s->ws + L.off_len, (size_t)B * sizeof(int64_t), st);
+    if (ru != VIT_OK) return ru;
+    VIT_TRY(hipMemsetAsync(states, 0xff, (size_t)B * (size_t)states_stride * sizeof(int32_t), st));   // -1 behind every length
+    VIT_TRY(hipMemsetAsync(s->ws + L.off_cnt, 0, L.off_mask - L.off_cnt, st));                       // the event counters
+    VIT_TRY(segment_backtrace(plan, s->family, lane_bt, b, st, true));
+    if (loglik) VIT_TRY(hipMemcpyAsync(loglik, s->ws + L.off_loglik, (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return VIT_OK;
+}
+
+int vit_stream_reset(vit_session* s) {
+    if (!s) return VIT_EINVAL;
+    std::fill(s->pos.begin(), s->pos.end(), (int64_t)0);
+    s->dtype = -1;
+    return VIT_OK;
+}
+
+void vit_stream_close(vit_session* s) { delete s; }
 
 int vit_voicing_map(const int32_t* states, int64_t n, int32_t n_bins, uint8_t* voiced, int32_t* bins,
                     vit_stream stream) {

@@ -39,7 +39,8 @@ constexpr int banded_target_waves(int S, int W) {
 //   Packed      the songs of its slot, back to back, rows at offsets[song]       (vit_decode_packed)
 //   Ckpt        its own song: pass 1 (checkpoint rows only) or one segment       (vit_decode_checkpointed)
 //   PackedCkpt  pass 1 over the songs of its slot, or one segment unit           (vit_decode_packed_bounded)
-enum class WgVariant { Plain, Packed, Ckpt, PackedCkpt };
+//   Stream      its own song of a session: the next frames, from a chunk of rows (vit_stream_append)
+enum class WgVariant { Plain, Packed, Ckpt, PackedCkpt, Stream };
 // packed variant of the one-target floor kernel (banded_floor_forward_kernel<.., WgVariant::Packed>, vit_decode_packed for plans without
 // the wave form): every instantiated (W, NWT) pair of the floor form; idle slot S stores the frame maximum, so S < 64 * NWT
 constexpr bool floor_packed_applies(int S, int W, bool floor_ok, int n_dense) {
@@ -56,6 +57,10 @@ constexpr bool floor_ckpt_applies(int S, int W, bool floor_ok, int n_dense) {
 // packed-checkpoint variant of the same kernel (banded_floor_forward_kernel<.., WgVariant::PackedCkpt> in banded_pc.hip, vit_decode_packed_bounded
 // for plans without the wave form): every pair of the checkpoint / resume variant -- each of them compiles free of scratch
 constexpr bool floor_pckpt_applies(int S, int W, bool floor_ok, int n_dense) { return floor_ckpt_applies(S, W, floor_ok, n_dense); }
+// stream variant of the same kernel (banded_floor_forward_kernel<.., WgVariant::Stream> in banded_stream.hip, vit_stream_append): every
+// pair of the packed variant -- the narrow windows on six waves (S = 321 / 361), which floor_ckpt_pair leaves out, are the sessions
+// it is for; a session runs the workgroup family whatever its batch
+constexpr bool floor_stream_applies(int S, int W, bool floor_ok, int n_dense) { return floor_packed_applies(S, W, floor_ok, n_dense); }
 // step-structured kernel (plan.step_ok): instantiated for the Durrieu geometry -- 20-bin bands, 9 near bands, 705..768 voiced states
 constexpr bool step_kernel_instantiated(int S, int bw, int kb) { return bw == 20 && kb == 9 && S - 1 > 704 && S - 1 <= 768; }
 // the dense kernel keeps NS running (best, arg) pairs per thread
@@ -116,6 +121,11 @@ struct FwdArgs {
     const int64_t* ckpt_base;    // device [songs]: checkpoint rows in front of song b's = sum of (n_b' - 1) over b' < b
     const int32_t* unit_song;    // device [B units of this launch]
     const int32_t* unit_seg;     // device [B units of this launch]
+    // stream session (vit_stream_append; WgVariant::Stream of the workgroup kernels), in fields the other variants leave unused: song b
+    // computes frames pos[b] .. pos[b] + cnt[b] - 1 (cnt 0: nothing) with pos = unit_song and cnt = unit_seg, device [B] tables of this
+    // launch -- or, both null, pos = t_begin and cnt = t_end - t_begin for every song.  Frame t reads emission row t - pos[b] of the
+    // chunk logE + b * init_stride (init_stride in elements) and is stored at row t of the song's T rows of hist (T = the session's
+    // capacity) in the Plain layout; pos > 0 resumes from row pos - 1 of those rows.
     int win_shift;         // 0..3: delta is stored shifted by this many floats in LDS so that the window starts of a
                             // 16-lane group are 16-byte aligned in the SAME copy order (bank-conflict-free b128 reads)
     int floor_live;         // split floor kernel (host side only): window entries the full waves' targets [0, 64 * kSplitFullWaves) must evaluate
@@ -293,12 +303,17 @@ hipError_t launch_wave(const FwdArgs& a, bool f16, hipStream_t st);   // wave.hi
 //               resumed from row ckpt_base[song] + segment - 1 of a.init_rows, into rows u * a.hist_rows .. of a.hist (the banded kernel
 //               also writes one pad column of the row in front of them and runs one frame past the segment where the song goes on:
 //               K + 2 rows per unit, a.hist at the second; the step kernel: K + 1).
+//   Stream      one workgroup per song of a session (a.B): a.unit_song / a.unit_seg = this launch's positions and counts, or both null and
+//               a.t_begin / a.t_end for every song; a.logE = the chunk, a.init_stride its elements per song; rows at their absolute
+//               index of the song's a.T rows, resumed from the row in front of the first (see FwdArgs)
 // *_variant_resident: workgroups of that instantiation one compute unit holds at once (the occupancy query at its LDS size; Packed and
 // PackedCkpt, whose launches are sized by it).
 hipError_t launch_banded_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st);
 hipError_t banded_variant_resident(const FwdArgs& a, WgVariant v, bool f16, int* per_cu);
 // banded.hip -> banded_pc.hip: the PackedCkpt instantiations of the floor kernel build in a translation unit of their own
 hipError_t floor_pckpt(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu);
+// banded.hip -> banded_stream.hip: the Stream instantiations, likewise
+hipError_t floor_stream(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu);
 hipError_t launch_step_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st);
 hipError_t step_variant_resident(const FwdArgs& a, WgVariant v, bool f16, int* per_cu);
 // what a variant launch needs of FwdArgs; rows_in_front: extra rows the check demands of a unit's hist_rows beyond K (as before: banded 2, step 0)
@@ -310,6 +325,9 @@ inline bool wg_variant_args_ok(const FwdArgs& a, WgVariant v, int rows_in_front)
         case WgVariant::PackedCkpt:
             if (!a.offsets || !a.ckpt_base || a.ckpt_every < 1 || a.hist_rows < 0) return false;
             return a.unit_song ? (a.unit_seg && a.init_rows && a.B >= 1 && a.hist_rows >= (int64_t)a.ckpt_every + rows_in_front) : slots;
+        case WgVariant::Stream:
+            if (a.offsets || a.lengths || a.B < 1 || a.T < 1 || a.init_stride < 0 || !a.unit_song != !a.unit_seg) return false;
+            return a.unit_song || (a.t_begin >= 0 && a.t_end >= a.t_begin && a.t_end <= a.T);
         default: return false;   // (Plain has no variant launch)
     }
 }

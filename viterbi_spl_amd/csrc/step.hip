@@ -331,8 +331,11 @@ struct Step4sLds {
 //     other store goes to the slot's scratch row hist_rows + slot; the terminal state and the log-likelihood are written per song;
 //   unit (unit_song set): Ckpt's segment per workgroup: workgroup u runs the K frames of segment unit_seg[u] of song unit_song[u] (emission
 //     rows at offsets[song]) from row ckpt_base[song] + segment - 1 of init_rows (segment 0: from the prior) into rows u * hist_rows ..
-// WV = Plain compiles to the code it was before the variants existed.  (PK / CK / PC below: WV is that variant; PKx / CKx: what the
-// packed-checkpoint variant shares with the packed and with the checkpoint / resume variant.)
+// WV = Stream is the session variant (vit_stream_append): the workgroup's song gets its next cnt frames t0 .. t0 + cnt - 1 (wg_cursor.inc;
+// cnt = 0 leaves without writing) from the rows of its chunk; rows are stored at their absolute index as Plain stores them, t0 > 0 loads
+// dn from row t0 - 1 of the song's own rows, and the terminal state and log-likelihood are written after every launch.
+// WV = Plain compiles to the code it was before the variants existed.  (PK / CK / PC / ST below: WV is that variant; PKx / CKx: what the
+// packed-checkpoint variant shares with the packed and with the checkpoint / resume variant; RSx: CKx or ST.)
 template <int BW, int KB, int PF, typename ET, WgVariant WV = WgVariant::Plain>
 __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     static_assert(BW == 20 && KB == 9 && PF % 2 == 0, "written for nine 20-bin bands");
@@ -340,6 +343,8 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     constexpr bool PK = WV == WgVariant::Packed, CK = WV == WgVariant::Ckpt, PC = WV == WgVariant::PackedCkpt;
     constexpr bool PKx = PK || PC;                // the song loop and its per-song preamble
     constexpr bool CKx = CK || PC;                // the row selection of the stores, the resumed first frame
+    constexpr bool ST = WV == WgVariant::Stream;  // the frames of one launch of a session, rows at their absolute index
+    constexpr bool RSx = CKx || ST;               // the frame loop starts at t1 (a launch may resume a song)
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NQL = L::NQL, PAD = L::PAD, VLEN = L::VLEN, FLEN = L::FLEN;
     constexpr int KA = 5;                         // half A: bands 0 .. KA-1; half B: KA .. KB-1 and the far band KB
@@ -435,6 +440,15 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
             dn = mask4(f32x4{lpi[col[0]], lpi[col[1]], lpi[col[2]], lpi[col[3]]} + e0);
             store4(ck_every > 0 ? ck_scratch : 0, dn);
         }
+    } else if constexpr (ST) {                                            // frame 0, or the song's own row in front of this launch's first frame
+        if (t0 > 0) {
+            const float* __restrict__ ir = hist + (size_t)(t0 - 1) * SD;
+            dn = mask4(f32x4{ir[col[0]], ir[col[1]], ir[col[2]], ir[col[3]]});
+        } else {
+            const f32x4 e0 = load4(0);
+            dn = mask4(f32x4{lpi[col[0]], lpi[col[1]], lpi[col[2]], lpi[col[3]]} + e0);
+            store4(0, dn);
+        }
     } else {
         const f32x4 e0 = load4(0);
         dn = mask4(f32x4{lpi[col[0]], lpi[col[1]], lpi[col[2]], lpi[col[3]]} + e0);
@@ -442,7 +456,7 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     }
     f32x4 er[PF];
 #pragma unroll
-    for (int k = 0; k < PF; ++k) er[k] = load4((CKx ? t1 : 1) + k < Tb ? (CKx ? t1 : 1) + k : Tb - 1);
+    for (int k = 0; k < PF; ++k) er[k] = load4((RSx ? t1 : 1) + k < Tb ? (RSx ? t1 : 1) + k : Tb - 1);
 
 #ifdef VIT_TIMING_HOOKS
     const bool prof = !PKx && !CKx && (a.debug & 256) != 0;      // phase stamps: publish | barrier | reads | exchange + store -> scratch[song][4*wave ..]
@@ -585,7 +599,7 @@ __global__ void __launch_bounds__(448) step4s_forward_kernel(FwdArgs a) {
     };
     // ---------------- one pass per song (PK: the songs of the slot, back to back)
     for (;;) {
-        int t = CKx ? t1 : 1;
+        int t = RSx ? t1 : 1;
         for (; t + PF - 1 < Tb; t += PF) {
 #pragma unroll
             for (int k = 0; k < PF; ++k) frame(t + k, er[k]);
@@ -652,7 +666,7 @@ template <WgVariant V>
 static hipError_t step4s_launch(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu) {
     constexpr int BW = 20, KB = 9, PF = 2;
     constexpr size_t ldss = Step4sLds<BW, KB>::bytes();
-    const bool per_song = V == WgVariant::Plain || V == WgVariant::Ckpt || (V == WgVariant::PackedCkpt && a.unit_song);
+    const bool per_song = V == WgVariant::Plain || V == WgVariant::Ckpt || V == WgVariant::Stream || (V == WgVariant::PackedCkpt && a.unit_song);
     auto go = [&](auto kern) -> hipError_t {
         if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, 448, ldss);
         hipLaunchKernelGGL(kern, dim3(per_song ? (int)a.B : a.n_slots), dim3(448), ldss, st, a);
@@ -660,12 +674,15 @@ static hipError_t step4s_launch(const FwdArgs& a, bool f16, hipStream_t st, int*
     };
     return f16 ? go(step4s_forward_kernel<BW, KB, PF, __half, V>) : go(step4s_forward_kernel<BW, KB, PF, float, V>);
 }
+// (defined at the end of the file: the Stream kernels are emitted behind every earlier kernel, whose code then keeps its place)
+static hipError_t step_stream(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu);
 static hipError_t step_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st, int* per_cu) {
     if (!step_kernel_instantiated(a.S, a.step_bw, a.step_kb)) return hipErrorInvalidConfiguration;
     switch (v) {
         case WgVariant::Packed: return step4s_launch<WgVariant::Packed>(a, f16, st, per_cu);
         case WgVariant::Ckpt: return step4s_launch<WgVariant::Ckpt>(a, f16, st, per_cu);
         case WgVariant::PackedCkpt: return step4s_launch<WgVariant::PackedCkpt>(a, f16, st, per_cu);
+        case WgVariant::Stream: return step_stream(a, f16, st, per_cu);
         default: return hipErrorInvalidValue;   // (Plain is launch_step's)
     }
 }
@@ -692,5 +709,7 @@ hipError_t launch_step(const FwdArgs& a, bool f16, hipStream_t st) {
         hipLaunchKernelGGL((step4_forward_kernel<BW, KB, PF, float>), dim3((int)a.B), dim3(256), lds4, st, a);
     return hipGetLastError();
 }
+
+static hipError_t step_stream(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu) { return step4s_launch<WgVariant::Stream>(a, f16, st, per_cu); }
 
 }  // namespace vit

@@ -7,8 +7,9 @@
 // VIT_WG_CURSOR == 1 and 2, one after the other at kernel top level (the early returns are the kernel's; the step kernel forms its
 // prior pointer between them, where its kernel-argument loads have always been): which song the workgroup decodes, its rows, the
 // frames of this launch and the checkpoint counters.
-//   In scope: a, S, T, SD, ET, PK / CK / PC / PKx; kPast = 1 where a segment runs one frame past its end if the song goes on (the
-//   floor kernel stores the frame maximum of row t with frame t + 1), 0 where it ends with the segment (the step kernel).
+//   In scope: a, S, T, SD, ET, PK / CK / PC / PKx / ST; kPast = 1 where a segment runs one frame past its end if the song goes on (the
+//   floor kernel stores the frame maximum of row t with frame t + 1), 0 where it ends with the segment (the step kernel).  (Stream
+//   runs no frame past its chunk: the next launch's first frame stores that maximum.)
 //   Declares: song, Tb, E, hist (1); si, si_end, take_song() (slot walks: `if (++si >= si_end) break; take_song();`), t0, t1,
 //   ck_every, ck_scratch, ck_next, ck_row, pc_init (2).
 // VIT_WG_CURSOR == 3, in the frame: the row select of a checkpoint variant's pass 1.
@@ -18,7 +19,7 @@
     // the song being decoded: the workgroup's own, or (slot walks) the slot's songs one after the other
     int song = blockIdx.x;
     int Tb = PKx ? 1 : song_length(a.lengths, song, T);
-    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PKx ? (size_t)0 : (size_t)song * T * S);
+    const ET* __restrict__ E = reinterpret_cast<const ET*>(a.logE) + (PKx || ST ? (size_t)0 : (size_t)song * T * S);
     float* __restrict__ hist = a.hist + (PKx ? (size_t)0 : (CK ? (size_t)song * (size_t)a.hist_rows * SD : (size_t)song * T * SD));
 #elif VIT_WG_CURSOR == 2
     // (Ckpt) first frame of this launch, first frame the loop computes, pass 1's segment length and its row bookkeeping
@@ -34,6 +35,22 @@
         const int stop = ck_every > 0 || a.t_end >= T ? T : a.t_end + kPast;
         Tb = Tb < stop ? Tb : stop;
         if (Tb <= t0) return;                                             // (segments: the song ended before this one)
+    }
+    if constexpr (ST) {
+        // (Stream) the frames of this launch: t0 .. t0 + cnt - 1 of the song's T rows; E is moved so that row t of it is row t - t0 of the
+        // song's chunk, and the kernel goes on indexing emission rows by frame
+        // (two branches, and the loaded values declared uniform: as one select between a table entry and a kernel argument the
+        // compiler loads per lane, and t0, Tb and the row bases then live in VGPRs -- a waterfall loop at every store and prefetch)
+        int cnt = a.t_end - a.t_begin;
+        t0 = a.t_begin;
+        if (a.unit_song) {
+            t0 = __builtin_amdgcn_readfirstlane(a.unit_song[song]);
+            cnt = __builtin_amdgcn_readfirstlane(a.unit_seg[song]);
+        }
+        if (cnt <= 0) return;                                           // (nothing appended to this song)
+        t1 = t0 > 0 ? t0 : 1;
+        Tb = t0 + cnt;
+        E += (ptrdiff_t)song * (ptrdiff_t)a.init_stride - (ptrdiff_t)t0 * S;
     }
     [[maybe_unused]] int si = 0, si_end = 1;                              // (slot walks) position in slot_songs, end of the slot's list
     // (slot walks) the song at si: its emission rows; Packed: its history rows; PackedCkpt: its first checkpoint row (a.hist is the

@@ -654,6 +654,20 @@ class ViterbiDecoder:
             states = states.to(out_dtype)
         return states, loglik
 
+    # ------------------------------------------------------------------ streaming
+    def workspace_bytes_stream(self, B: int, max_frames: int) -> int:
+        """Workspace bytes of a ``stream(B, max_frames)`` session (``vit_workspace_bytes_stream``); 0 when the plan has no stream
+        form (see ``stream``)."""
+        return int(_lib.load().vit_workspace_bytes_stream(self._plan, int(B), int(max_frames)))
+
+    def stream(self, B: int, max_frames: int, workspace: Optional[torch.Tensor] = None) -> "DecodeStream":
+        """A streaming session for B recordings of at most ``max_frames`` frames: ``append`` advances the forward pass chunk by
+        chunk as emission rows arrive, ``decode`` back-traces the recordings as they stand -- the states and log-likelihoods of
+        ``decode`` on the same frames, bit for bit, for any chunking.  For banded plans whose floor form is proven (the 321-, 361-
+        and 722-state grids) and step-structured plans (the Durrieu matrix); any other plan raises ``ViterbiHipError``.
+        ``workspace``: a uint8 tensor of at least ``workspace_bytes_stream(B, max_frames) + 256`` bytes, or None to allocate one."""
+        return DecodeStream(self, B, max_frames, workspace)
+
     def workspace_bytes_packed(self, B: int, total_frames: int) -> int:
         """Workspace bytes of ``decode_packed`` for B recordings of ``total_frames`` frames together; 0 when the plan has none of
         the forms the packed decode runs (see ``decode_packed``)."""
@@ -943,6 +957,94 @@ class ViterbiDecoder:
 
 
 _DECODERS: dict = {}
+
+
+class DecodeStream:
+    """One streaming session of a ``ViterbiDecoder`` (``vit_stream_*``): see ``ViterbiDecoder.stream``.  Calls are enqueued on the
+    current stream of the decoder's device; the caller orders the calls of one session as for any other tensor work (one stream, or
+    events).  A chunk tensor may be rewritten as soon as its ``append`` has run in stream order: nothing reads emission rows again."""
+
+    def __init__(self, decoder: ViterbiDecoder, B: int, max_frames: int, workspace: Optional[torch.Tensor] = None):
+        lib = _lib.load()
+        self._dec = decoder                    # (keeps the plan alive)
+        self.B, self.max_frames = int(B), int(max_frames)
+        self._session = ctypes.c_void_p()
+        if self.B < 1 or self.max_frames < 1:
+            raise ValueError("a stream needs B >= 1 recordings and max_frames >= 1")
+        need = decoder.workspace_bytes_stream(self.B, self.max_frames)
+        if need == 0:
+            raise _lib.ViterbiHipError("no streaming decode for this plan: it needs a banded plan whose floor form is proven "
+                                       "(no dense rows) or a step-structured plan of the Durrieu geometry")
+        self._ws, ws_ptr, ws_bytes, _ = decoder._call_workspace(need, workspace)
+        _lib.check(lib.vit_stream_open(decoder._plan, self.B, self.max_frames, ws_ptr, ws_bytes, ctypes.byref(self._session)), "vit_stream_open")
+
+    def _handle(self) -> ctypes.c_void_p:
+        if not self._session.value:
+            raise _lib.ViterbiHipError("the stream is closed")
+        return self._session
+
+    def append(self, emissions: torch.Tensor, counts=None) -> None:
+        """The next frames: ``emissions`` [B, n, S] (or [n, S] for a one-recording stream), float32 or float16 (the type of the
+        first append holds for the session); ``counts``: a host sequence of B ints, recording b takes rows ``[b, :counts[b]]``
+        (None: n each).  Raises ``ViterbiHipError`` -- with nothing enqueued and no length changed -- for a count out of range or
+        frames beyond ``max_frames``."""
+        dec = self._dec
+        logE, _, dt = dec._check_emissions(emissions)
+        if logE.shape[0] != self.B:
+            raise ValueError(f"emissions must be [{self.B}, n, {dec.S}]")
+        cnt = None
+        if counts is not None:
+            cnt = np.ascontiguousarray(np.asarray(counts, dtype=np.int64))
+            if cnt.shape != (self.B,):
+                raise ValueError("counts must hold one entry per recording")
+        with torch.cuda.device(dec.device):
+            rc = _lib.load().vit_stream_append(self._handle(), logE.data_ptr(), dt, int(logE.shape[1]), cnt.ctypes.data if cnt is not None else None,
+                                               torch.cuda.current_stream(dec.device).cuda_stream)
+        _lib.check(rc, "vit_stream_append")
+
+    @property
+    def lengths(self) -> np.ndarray:
+        """Frames appended per recording so far (host int64 [B])."""
+        out = np.zeros(self.B, np.int64)
+        _lib.check(_lib.load().vit_stream_lengths(self._handle(), out.ctypes.data), "vit_stream_lengths")
+        return out
+
+    def decode_into(self, states: torch.Tensor, loglik: Optional[torch.Tensor] = None) -> None:
+        """Enqueue the back-trace of the recordings as they stand: ``states`` int32 [B, stride], stride >= the longest length (-1
+        behind each length), ``loglik`` float32 [B] or None."""
+        dec = self._dec
+        if states.dtype != torch.int32 or states.dim() != 2 or states.shape[0] != self.B or not states.is_contiguous() or states.device != dec.device:
+            raise ValueError("states must be a contiguous int32 [B, stride] tensor on the decoder's device")
+        if loglik is not None and (loglik.dtype != torch.float32 or tuple(loglik.shape) != (self.B,) or not loglik.is_contiguous() or loglik.device != dec.device):
+            raise ValueError("loglik must be a float32 [B] tensor on the decoder's device")
+        with torch.cuda.device(dec.device):
+            rc = _lib.load().vit_stream_backtrace(self._handle(), states.data_ptr(), int(states.shape[1]), loglik.data_ptr() if loglik is not None else None,
+                                                  torch.cuda.current_stream(dec.device).cuda_stream)
+        _lib.check(rc, "vit_stream_backtrace")
+
+    def decode(self, out_dtype: torch.dtype = torch.int64) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> ``(states [B, max length so far], loglik [B])`` of the frames appended so far; the session stays open, and a later
+        ``decode`` after more appends supersedes this one."""
+        states = torch.empty((self.B, int(self.lengths.max())), dtype=torch.int32, device=self._dec.device)
+        loglik = torch.empty((self.B,), dtype=torch.float32, device=self._dec.device)
+        self.decode_into(states, loglik)
+        return (states if out_dtype == torch.int32 else states.to(out_dtype)), loglik
+
+    def reset(self) -> None:
+        """Every recording back to length 0; the workspace is reused."""
+        _lib.check(_lib.load().vit_stream_reset(self._handle()), "vit_stream_reset")
+
+    def close(self) -> None:
+        """Free the session (also on garbage collection).  The workspace tensor is released with the object."""
+        try:
+            if getattr(self, "_session", None) is not None and self._session.value:
+                _lib.load().vit_stream_close(self._session)
+                self._session = ctypes.c_void_p()
+        except Exception:
+            pass
+
+    def __del__(self):
+        self.close()
 
 
 def get_decoder(transition_matrix, init_probs, device=None) -> ViterbiDecoder:

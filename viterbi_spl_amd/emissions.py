@@ -69,17 +69,17 @@ def softmax_log_emissions(logits: torch.Tensor, single_side_peak_width: int = 15
 
 
 def softmax_scaled_log_emissions(logits: torch.Tensor, voicing_threshold_prob: float, prior: torch.Tensor | None,
-                                 single_side_peak_width: int = 5) -> torch.Tensor:
+                                 single_side_peak_width: int = 5, out: torch.Tensor | None = None) -> torch.Tensor:
     """dcnet's ``SoftMaxViterbi.observation_probs_fn`` (dcnet/softmax_viterbi.py:2530-2579) + log: logits ``[..., T, n_bins]``
     -> log of the scaled likelihoods ``[..., T, n_bins+1]`` (unvoiced last; values above 0 are normal).  ``prior``: the
-    state prior ``[n_bins+1]`` (unvoiced last) on the GPU, or None for the unscaled variant."""
+    state prior ``[n_bins+1]`` (unvoiced last) on the GPU, or None for the unscaled variant.  ``out``: a caller's emission buffer."""
     n_bins = logits.shape[-1]
     logits = _check(logits, n_bins)
     assert 0 < voicing_threshold_prob < 1
     if prior is not None:
         if prior.device != logits.device or prior.dtype != torch.float32 or tuple(prior.shape) != (n_bins + 1,) or not prior.is_contiguous():
             raise ValueError(f"prior must be a contiguous float32 [{n_bins + 1}] tensor on the logits' device")
-    out = torch.empty(logits.shape[:-1] + (n_bins + 1,), dtype=torch.float32, device=logits.device)
+    out = _out(out, logits.shape[:-1] + (n_bins + 1,), logits.device)
     n = logits.numel() // n_bins
     # the reference pads with log(vth / (1. - vth)) computed from an np.float32 scalar (dcnet/softmax_viterbi.py:2546-2548): float32
     # arithmetic under NumPy >= 2 -- the NumPy that generated tests/golden/obs_goldens.npz -- (NumPy 1.x promoted the scalar

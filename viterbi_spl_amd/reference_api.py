@@ -217,7 +217,8 @@ class _PreparedViterbi:
         return voiced, bins
 
     # ---- the post-processor on the GPU: logits -> log-emissions -> decode -> (voiced, bins)
-    def _log_emissions(self, logits: torch.Tensor) -> torch.Tensor:
+    def _log_emissions(self, logits: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """This class's stand-alone emission builder: ``[frames, columns]`` logits -> ``[frames, S]`` log-emissions (into ``out`` when given)."""
         raise NotImplementedError
 
     def decode_logits(self, logits, note_range=None):
@@ -318,9 +319,9 @@ class Viterbi(_PreparedViterbi):
         probs = np.require(probs_st.T, np.float32, ['C'])
         return _run(self.log_transition_matrix_T, self.log_ini_probs, probs, self._decoder)
 
-    def _log_emissions(self, logits):
+    def _log_emissions(self, logits, out=None):
         from .emissions import shaun_log_emissions
-        return shaun_log_emissions(logits, self.voicing_threshold, self.single_side_peak_width)
+        return shaun_log_emissions(logits, self.voicing_threshold, self.single_side_peak_width, out=out)
 
     def _obs_params(self):
         import math
@@ -348,9 +349,9 @@ class SoftMaxViterbi(_PreparedViterbi):
         np.log(probs_ts, out=probs_ts)
         return _run(self.log_transition_matrix_T, self.log_ini_probs, probs_ts, self._decoder)
 
-    def _log_emissions(self, logits):
+    def _log_emissions(self, logits, out=None):
         from .emissions import softmax_log_emissions
-        return softmax_log_emissions(logits, self.single_side_peak_width)
+        return softmax_log_emissions(logits, self.single_side_peak_width, out=out)
 
     def _obs_params(self):
         return ViterbiDecoder.obs_params("softmax", self.num_freq_bins, self.single_side_peak_width)
@@ -372,9 +373,9 @@ class ScaledSoftMaxViterbi(SoftMaxViterbi):
             assert self.ini_probs.min() > 0.3 / (self.num_freq_bins * 10)       # dcnet/softmax_viterbi.py:2536
         self._prior_dev = torch.from_numpy(np.ascontiguousarray(self.ini_probs, np.float32)).to(self._decoder.device) if self.scaled else None
 
-    def _log_emissions(self, logits):
+    def _log_emissions(self, logits, out=None):
         from .emissions import softmax_scaled_log_emissions
-        return softmax_scaled_log_emissions(logits, self.voicing_threshold_prob, self._prior_dev, self.single_side_peak_width)
+        return softmax_scaled_log_emissions(logits, self.voicing_threshold_prob, self._prior_dev, self.single_side_peak_width, out=out)
 
     def _obs_params(self):
         vth = np.float32(self.voicing_threshold_prob)       # float32 arithmetic, as softmax_scaled_log_emissions hands it to the kernel
@@ -516,9 +517,16 @@ class RecordingAccumulator:
     ``vit_snippets_append``; "shaun" rows are relative to the unvoiced channel, :2296-2297), ``finish`` runs emission
     builder, decoder, voicing map and the bin -> note gather without a host visit.  Channels per snippet: n_bins + 1 with the
     unvoiced channel first for Viterbi (subtracted and dropped) and SoftMaxViterbi (kept); the n_bins pitch channels only for
-    ScaledSoftMaxViterbi, whose unvoiced logit is a constant (dcnet/softmax_viterbi.py:2548-2550)."""
+    ScaledSoftMaxViterbi, whose unvoiced logit is a constant (dcnet/softmax_viterbi.py:2548-2550).
 
-    def __init__(self, viterbi: _PreparedViterbi, max_frames: int):
+    ``streaming=True`` spends the forward pass beside the acoustic model instead of behind it: ``append`` also builds the emission
+    rows of the new frames with the wrapped class's stand-alone builder (the builders work per frame: the rows a whole-recording
+    call would build, bit for bit) into a chunk buffer it keeps, and advances a one-recording ``ViterbiDecoder.stream`` by them; ``finish`` is then the
+    back-trace, the voicing map and the note gather, with the result of ``streaming=False``.  The default is ``False``, and
+    ``logits()`` works in both modes.  The class wraps the three logits decoders only: ``ImmViterbi`` callers stream with
+    ``viterbi._decoder.stream(...)`` and ``emissions.activation_log_emissions`` per chunk."""
+
+    def __init__(self, viterbi: _PreparedViterbi, max_frames: int, streaming: bool = False):
         self.viterbi = viterbi
         if isinstance(viterbi, Viterbi):
             self.mode, self.channels, self.cols = 0, viterbi.num_freq_bins + 1, viterbi.num_freq_bins
@@ -531,9 +539,14 @@ class RecordingAccumulator:
         dev = viterbi._decoder.device
         self._rows = torch.empty((int(max_frames), self.cols), dtype=torch.float32, device=dev)
         self.n_frames = 0
+        self.streaming = bool(streaming)
+        self._stream = viterbi._decoder.stream(1, int(max_frames)) if self.streaming else None
+        self._chunk = None                 # (streaming) the emission rows of one append, reused: it grows to the largest append seen
 
     def reset(self):
         self.n_frames = 0
+        if self._stream is not None:
+            self._stream.reset()
 
     def append(self, pitch_logits: torch.Tensor, padded_frames: int = 0):
         from . import _lib
@@ -550,6 +563,10 @@ class RecordingAccumulator:
             rc = _lib.load().vit_snippets_append(x.data_ptr(), n, C, F, self.mode, self._rows[self.n_frames:].data_ptr(), rows,
                                                  torch.cuda.current_stream(x.device).cuda_stream)
         _lib.check(rc, "vit_snippets_append")
+        if self._stream is not None and rows > 0:      # the new frames' emission rows, then the forward pass over them
+            if self._chunk is None or self._chunk.shape[0] < rows:
+                self._chunk = torch.empty((rows, self.viterbi.num_freq_bins + 1), dtype=torch.float32, device=self._rows.device)
+            self._stream.append(self.viterbi._log_emissions(self._rows[self.n_frames:self.n_frames + rows], out=self._chunk[:rows]))
         self.n_frames += rows
 
     def logits(self) -> torch.Tensor:
@@ -557,6 +574,11 @@ class RecordingAccumulator:
         return self._rows[: self.n_frames]
 
     def finish(self, note_range=None):
-        out = self.viterbi.decode_logits(self.logits(), note_range)
+        if self._stream is not None:
+            dec = self.viterbi._decoder
+            states, _ = self._stream.decode(out_dtype=torch.int32)
+            out = dec.voicing(states[0], self.viterbi.num_freq_bins) if note_range is None else dec.voicing_notes(states[0], note_range, self.viterbi.num_freq_bins)
+        else:
+            out = self.viterbi.decode_logits(self.logits(), note_range)
         self.reset()
         return out
