@@ -23,8 +23,8 @@ import torch
 
 from oracle import viterbi_oracle as vo
 from tests import floor_grid as fg
+from tests import stream_grid as sg
 from tests.f64_ref import band_params
-from tests.plan_replay import HostPlan
 from viterbi_spl_amd import ViterbiDecoder, _lib, synth
 
 pytestmark = pytest.mark.gpu
@@ -61,31 +61,11 @@ def _bits(x):
     return x.view(np.uint32)
 
 
-_plan_cache = {}
-
-
 def _plan_case(dev, entry):
     """decoder and, per batch, (name, emissions float32 on the fp16 grid, lengths, the oracle's states and log-likelihoods): built once
-    per plan and left unchanged."""
-    if entry not in _plan_cache:
-        _plan_cache.clear()                          # one plan at a time: the parametrisation walks plan by plan
-        W, n, S, half, recipe = entry
-        A, pi = fg.plan_params(entry)
-        hp = HostPlan(A, pi)
-        dec = ViterbiDecoder(A, pi, dev)
-        info = dec.info
-        assert info["banded_ok"] and info["floor_ok"] and not info["wave_ok"] and info["n_dense_rows"] == 0, info
-        assert info["group_window"] == W and fg.waves_for(S) == n and S < 64 * n and info["extras"] == hp.extras, info
-        batches = []
-        for name, E, lens in fg.plan_batches(entry, A, hp.lo[:S], hp.extras):
-            ref_s, ref_l = vo.decode_c(A, pi, E, lengths=lens)
-            for x in (E, lens, ref_s, ref_l):
-                x.setflags(write=False)
-            batches.append((name, E, lens, ref_s, ref_l))
-        fg.premise_forced(batches[1][3][-1], W, hp.lo[:S], hp.extras[0] if hp.extras else None)
-        fg.premise_hops(batches[2][3], batches[2][2], W, hp.lo[:S], hp.extras)
-        _plan_cache[entry] = (dec, batches)
-    return _plan_cache[entry]
+    per plan and left unchanged (tests/stream_grid.py plan_case, shared with tests/test_gpu_stream_grid.py)."""
+    dec, batches, _ = sg.plan_case(dev, entry)
+    return dec, batches
 
 
 def _same_padded(st, ll, ref_s, ref_l, what):

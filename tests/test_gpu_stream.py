@@ -1,6 +1,7 @@
 """GPU tests of the streaming decode (vit_stream_*, ViterbiDecoder.stream, RecordingAccumulator(streaming=True)): whatever the
 chunking, the states and the log-likelihood of ``decode`` on the same frames and of the CPU oracle, bit for bit; the history rows of
-``vit_forward``; refusals that write nothing."""
+``vit_forward``; refusals that write nothing.  Every other (window width, target waves) pair, the edges of the step range, launch
+boundaries on forced hops and the chunked back-trace forms of a session: tests/test_gpu_stream_grid.py."""
 import ctypes
 
 import numpy as np
