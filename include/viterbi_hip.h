@@ -581,6 +581,42 @@ int vit_stream_backtrace(vit_session *s, int32_t *states /* device [B, states_st
 int vit_stream_reset(vit_session *s);
 void vit_stream_close(vit_session *s);
 
+/* The commit point of a session: the path prefix that no later frame can change, and incremental output.
+ *
+ * For one recording with n frames appended and f frames committed so far (f = 0 after vit_stream_commit_begin() and after
+ * vit_stream_reset()): psi_t[j] = the lowest-index argmax of vit_decode()'s recursion, U_{n-1} = all S states, U_{t-1} = psi_t[U_t].
+ * With L = max_lookback, c = the LARGEST t with max(f, n-1-L) <= t <= n-2 and |U_t| = 1, s_c = its element.  If c exists the new
+ * frontier is f' = c + 1 and states[f .. c] are written (s_c at frame c, s_{t-1} = psi_t[s_t] below it); otherwise, or with n < 2,
+ * f' = f and nothing is written.  Exact, not a fixed-lag rule: every path through frame n-1, whatever is appended later, passes
+ * frame c in state s_c, because a back-pointer is a function of the delta row below it and rows never change once written.
+ *
+ *   vit_workspace_bytes_stream_commit(plan, B)  bytes of the commit state (device frontiers [B], the call's length table, the
+ *               committed ranges' first rows, lengths and start states, the back-trace's chunk entries and flags): a separate
+ *               caller-owned, 256-byte-aligned buffer; the session's own workspace and its size are what they were.  0 where the plan
+ *               is not served.
+ *   vit_stream_commit_begin()  binds the buffer to the session and marks every frontier as 0.  Host only.
+ *   vit_stream_commit()  for every recording b: states[b][f_b .. f'_b) and committed[b] = f'_b (device int64 [B]), NOTHING else of
+ *               `states` (no -1 fill, nothing below f_b or from f'_b on).  A recording of 0 or 1 frames commits nothing and is no
+ *               error.  No host synchronisation and no host read of a frontier: one upload (the lengths, through the plan's pinned
+ *               staging buffer as in vit_stream_backtrace(), with the thread-safety of that call) and a constant number of launches on
+ *               `stream`: the survivor merge kernel, then the lane back-trace (chunk flags' memset, speculative pass, verify, repair)
+ *               over the committed ranges, whose bounds stay on the device.
+ *               max_lookback bounds the frames the merge is looked for in (a call that finds none commits nothing; a later one may);
+ *               the frames committed are walked whatever their number.
+ * vit_stream_backtrace() is unchanged and may be called at any time; its prefix [0, f') equals what the commits wrote.
+ *
+ * Which plans: the banded session plans (every (window, waves) pair a session serves: the 321-, 361-, 721- and 722-state grids).
+ * Step-structured plans (the Durrieu matrix) get size 0 and VIT_EUNSUPPORTED: their back-pointer decision is a whole-row kernel,
+ * not a per-lane one.
+ *
+ * Status.  vit_stream_commit_begin(): NULL session, NULL or misaligned buffer VIT_EINVAL; then VIT_EUNSUPPORTED; then VIT_EWORKSPACE.
+ * vit_stream_commit(): NULL session / states / committed, max_lookback < 1 or > 2^30: VIT_EINVAL; no vit_stream_commit_begin() on this
+ * session: VIT_EINVAL; states_stride < max n_b: VIT_EINVAL.  A refused call enqueues and writes nothing. */
+size_t vit_workspace_bytes_stream_commit(const vit_plan *plan, int64_t B);
+int vit_stream_commit_begin(vit_session *s, void *commit_ws, size_t bytes);
+int vit_stream_commit(vit_session *s, int32_t *states /* device [B, states_stride] */, int64_t states_stride,
+                      int64_t *committed /* device [B] */, int64_t max_lookback, vit_stream stream);
+
 /* Event counts of the last vit_backtrace() on this workspace (banded plans; all zero for the kernels that do not count):
  * *offset = byte offset, inside the workspace, of an int32 [B][*n_per_song] device array (valid once the back-trace has run
  * on its stream): per song [0] tiles fetched, [1] span misses (the path left the fetched columns), [2] whole-row evaluations

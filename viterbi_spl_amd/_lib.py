@@ -31,6 +31,7 @@ EXPORTS = (
     "vit_workspace_bytes_logits_checkpointed", "vit_decode_logits_checkpointed",
     "vit_workspace_bytes_stream", "vit_stream_open", "vit_stream_append", "vit_stream_lengths", "vit_stream_backtrace",
     "vit_stream_reset", "vit_stream_close",
+    "vit_workspace_bytes_stream_commit", "vit_stream_commit_begin", "vit_stream_commit",
 )
 ABI_VERSION = 4
 
@@ -167,6 +168,12 @@ def load() -> ctypes.CDLL:
     lib.vit_stream_reset.argtypes = [vp]
     lib.vit_stream_close.restype = None
     lib.vit_stream_close.argtypes = [vp]
+    lib.vit_workspace_bytes_stream_commit.restype = sz
+    lib.vit_workspace_bytes_stream_commit.argtypes = [vp, i64]
+    lib.vit_stream_commit_begin.restype = i32
+    lib.vit_stream_commit_begin.argtypes = [vp, vp, sz]
+    lib.vit_stream_commit.restype = i32
+    lib.vit_stream_commit.argtypes = [vp, vp, i64, vp, i64, vp]
     lib.vit_forward_family.restype = i32
     lib.vit_forward_family.argtypes = [vp, i64, i32]
     lib.vit_voicing_map.restype = i32

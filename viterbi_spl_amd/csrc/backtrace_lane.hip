@@ -279,8 +279,9 @@ __global__ void __launch_bounds__(kLnThreads) lane_spec_kernel(BtArgs a) {
     }
     const long long off = packed ? a.offsets[song] : 0;
     const int Tb = packed ? (int)(a.offsets[song + 1] - off) : song_length(a, song), Lf = Tb - 1;
-    int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride);
-    const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows) * SD;
+    const size_t fr = a.first_row ? (size_t)a.first_row[song] : 0;       // (a session's commit: the sub-problem starts at row / frame fr of its song)
+    int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride + fr);
+    const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows + fr) * SD;
     int32_t* __restrict__ entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
     int lo_c, hi_c;
     bt_chunk_bounds(Lf, chunk, C, lo_c, hi_c);
@@ -365,7 +366,7 @@ __global__ void lane_verify_kernel(BtArgs a, uint32_t* __restrict__ mask) {
     int lo_c, hi_c;
     bt_chunk_bounds(Lf, c, C, lo_c, hi_c);
     if (hi_c <= lo_c) return;
-    const int truth = a.states[(packed ? (size_t)off : (size_t)song * a.states_stride) + hi_c];
+    const int truth = a.states[(packed ? (size_t)off : (size_t)song * a.states_stride + (a.first_row ? (size_t)a.first_row[song] : 0)) + hi_c];
     const int32_t* entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
     if (entry[c] != truth) atomicOr(mask + (size_t)song * kLaneMaskWords + (c >> 5), 1u << (c & 31));
 }
@@ -394,8 +395,9 @@ __global__ void __launch_bounds__(kLnThreads) lane_repair_kernel(BtArgs a, const
     ln_load_tables<WQ, GT>(a, tabL, loL);
     const long long off = packed ? a.offsets[song] : 0;
     const int Lf = (packed ? (int)(a.offsets[song + 1] - off) : song_length(a, song)) - 1;
-    int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride);
-    const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows) * SD;
+    const size_t fr = a.first_row ? (size_t)a.first_row[song] : 0;
+    int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride + fr);
+    const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows + fr) * SD;
     const int32_t* entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
     LaneDecider<WQ, GT, NWT> decide{a, tabL, loL, lane};
     decide.init();

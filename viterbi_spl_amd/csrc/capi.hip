@@ -1905,6 +1905,8 @@ struct vit_session {
     uint8_t* ws = nullptr;
     int dtype = -1;                     // emission type of the first append (-1: none yet)
     std::vector<int64_t> pos;           // frames appended per song
+    uint8_t* cws = nullptr;             // the commit state (vit_stream_commit_begin), or null
+    bool commit_reset = true;           // the next commit counts every frontier as 0 (after commit_begin / reset: a host flag, nothing enqueued)
 };
 
 namespace {
@@ -1934,6 +1936,25 @@ StLayout st_layout(const vit_plan* p, int family, int64_t B, int64_t T_cap) {
     return s;
 }
 inline bool st_shape_ok(int64_t B, int64_t T_cap) { return B >= 1 && T_cap >= 1 && B <= (int64_t)1 << 30 && T_cap <= (int64_t)1 << 30; }
+
+// The commit state of a session (vit_stream_commit): its own caller-owned buffer, so that st_layout stays what it is.  Served: the
+// banded session plans whose rows the per-lane decision reads (the lane back-trace's predicate); step plans decide by whole rows.
+inline bool sc_served(const vit_plan* p) { return st_family(p) == kFamGroup && ck_lane_applies(p); }
+struct ScLayout {
+    size_t off_front, off_pos, off_first, off_len, off_last, off_mask, off_entry, bytes;
+};
+ScLayout sc_layout(int64_t B) {
+    ScLayout c;
+    c.off_front = 0;                                                              // frames committed so far [B]
+    c.off_pos = align256((size_t)B * sizeof(int64_t));                            // per-call table: frames appended so far [B]
+    c.off_first = c.off_pos + align256((size_t)B * sizeof(int64_t));              // the committed ranges as sub-problems of the lane back-trace:
+    c.off_len = c.off_first + align256((size_t)B * sizeof(int64_t));              //   first rows, lengths,
+    c.off_last = c.off_len + align256((size_t)B * sizeof(int64_t));               //   start states,
+    c.off_mask = c.off_last + align256((size_t)B * sizeof(int32_t));              //   chunk flags
+    c.off_entry = c.off_mask + align256((size_t)B * vit::kLaneMaskWords * sizeof(uint32_t));    // and chunk entries
+    c.bytes = c.off_entry + align256((size_t)B * vit::kLaneMaxChunks * sizeof(int32_t));
+    return c;
+}
 
 }  // namespace
 
@@ -2078,6 +2099,75 @@ int vit_stream_reset(vit_session* s) {
     if (!s) return VIT_EINVAL;
     std::fill(s->pos.begin(), s->pos.end(), (int64_t)0);
     s->dtype = -1;
+    s->commit_reset = true;
+    return VIT_OK;
+}
+
+size_t vit_workspace_bytes_stream_commit(const vit_plan* plan, int64_t B) {
+    if (!plan || B < 1 || B > (int64_t)1 << 30 || !sc_served(plan)) return 0;
+    return sc_layout(B).bytes;
+}
+
+int vit_stream_commit_begin(vit_session* s, void* commit_ws, size_t bytes) {
+    if (!s || !commit_ws || ((uintptr_t)commit_ws & 255) != 0) return VIT_EINVAL;
+    if (!sc_served(s->plan)) return VIT_EUNSUPPORTED;
+    if (bytes < sc_layout(s->B).bytes) return VIT_EWORKSPACE;
+    s->cws = static_cast<uint8_t*>(commit_ws);
+    s->commit_reset = true;
+    return VIT_OK;
+}
+
+int vit_stream_commit(vit_session* s, int32_t* states, int64_t states_stride, int64_t* committed, int64_t max_lookback, vit_stream stream) {
+    if (!s || !states || !committed || max_lookback < 1 || max_lookback > (int64_t)1 << 30) return VIT_EINVAL;
+    if (!s->cws) return VIT_EINVAL;
+    const vit_plan* plan = s->plan;
+    const int64_t B = s->B;
+    int64_t tmax = 0;
+    for (int64_t b = 0; b < B; ++b) tmax = std::max(tmax, s->pos[(size_t)b]);
+    if (states_stride < tmax || states_stride > (int64_t)1 << 30) return VIT_EINVAL;
+    const StLayout L = st_layout(plan, s->family, B, s->T_cap);
+    const ScLayout C = sc_layout(B);
+    vit::CommitArgs c{};
+    bt_args_from_plan(plan, c.b);
+    hist_layout_apply(hist_layout(plan, s->family), c.b);
+    c.b.aux_frames = 1;
+    c.b.hist = reinterpret_cast<const float*>(s->ws + L.off_hist);
+    c.b.hist_rows = s->T_cap;
+    c.b.states = states;
+    c.b.states_stride = states_stride;
+    c.b.B = B;
+    c.b.T = (int)tmax;
+    c.pos = reinterpret_cast<const int64_t*>(s->cws + C.off_pos);
+    c.frontier = reinterpret_cast<int64_t*>(s->cws + C.off_front);
+    c.committed = committed;
+    c.sub_first = reinterpret_cast<int64_t*>(s->cws + C.off_first);
+    c.sub_len = reinterpret_cast<int64_t*>(s->cws + C.off_len);
+    c.sub_last = reinterpret_cast<int32_t*>(s->cws + C.off_last);
+    c.max_lookback = max_lookback;
+    c.reset = s->commit_reset ? 1 : 0;
+    if (!vit::stream_commit_applies(c.b)) return VIT_EUNSUPPORTED;
+    // the committed ranges [f_b, c_b]: the lane back-trace over sub-problems whose first rows, lengths and start states the merge
+    // kernel leaves on the device (a length of 0 is skipped); the chunk count is that of the longest recording, the host knows no range
+    vit::BtArgs b = c.b;
+    b.first_row = c.sub_first;
+    b.lengths = c.sub_len;
+    b.last_state = c.sub_last;
+    b.skip_nonpositive = 1;
+    b.counters = nullptr;
+    b.mask = reinterpret_cast<uint32_t*>(s->cws + C.off_mask);
+    b.entry = reinterpret_cast<int32_t*>(s->cws + C.off_entry);
+    b.bt_form = 4;
+    if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    // the lengths so far through the plan's pinned staging buffer: the call's only upload
+    const int rc = pk_stage(plan, (size_t)B * sizeof(int64_t));
+    if (rc != VIT_OK) return rc;
+    std::memcpy(plan->pk_host, s->pos.data(), (size_t)B * sizeof(int64_t));
+    const int ru = pk_upload(plan, s->cws + C.off_pos, (size_t)B * sizeof(int64_t), st);
+    if (ru != VIT_OK) return ru;
+    VIT_TRY(vit::launch_stream_commit(c, st));
+    s->commit_reset = false;
+    if (tmax >= 2) VIT_TRY(segment_backtrace(plan, s->family, true, b, st));
     return VIT_OK;
 }
 

@@ -183,6 +183,9 @@ struct BtArgs {
     // sparse kernel and the lazy kernel's segment form over the segment units of a packed checkpointed decode: the states of sub-problem b start at states +
     // unit_states[b] (not b * states_stride), and nothing is written behind its lengths[b] frames -- those belong to the next song
     const int64_t* unit_states;  // device [B], or null
+    // lane form over the committed ranges of a streaming session (vit_stream_commit): sub-problem b is rows / frames first_row[b] ..
+    // first_row[b] + lengths[b] - 1 of song b (history by hist_rows, states by states_stride, both moved by first_row[b]); null: 0
+    const int64_t* first_row;    // device [B], or null
 };
 
 // fused.hip: emission builder + wave-form forward recursion in one workgroup (vit_decode_logits).  f: the forward pass's arguments
@@ -366,6 +369,23 @@ int sparse_backtrace_chunks(int64_t B, int T, int n_cus);
 bool lane_backtrace_applies(const BtArgs& a);
 hipError_t launch_backtrace_lane(const BtArgs& a, hipStream_t st, int phases = 3);
 int lane_backtrace_chunks(int64_t B, int T, int n_cus, int warm);
+// stream_commit.hip: the commit point of a streaming session (vit_stream_commit).  b: the plan's fields, the session's rows (hist,
+// hist_rows, the workgroup row layout with aux_frames = 1) and the caller's states / states_stride; one workgroup per recording.
+struct CommitArgs {
+    BtArgs b;
+    const int64_t* pos;       // device [B]: frames appended so far
+    int64_t* frontier;        // device [B]: frames committed so far (the commit state; read unless `reset`, then written)
+    int64_t* committed;       // device [B]: the caller's copy of the new frontier
+    // the committed range [f, c] as a sub-problem of the lane back-trace (BtArgs::first_row / lengths / last_state), device [B] each
+    int64_t* sub_first;       // f
+    int64_t* sub_len;         // c - f + 1, or 0: nothing committed (skip_nonpositive)
+    int32_t* sub_last;        // s_c
+    int64_t max_lookback;     // the merge is looked for in frames [max(f, n - 1 - max_lookback), n - 2]
+    int reset;                // 1: every frontier counts as 0 (first commit after vit_stream_commit_begin / vit_stream_reset)
+};
+bool stream_commit_applies(const BtArgs& a);
+bool stream_commit_table_in_lds(const BtArgs& a);
+hipError_t launch_stream_commit(const CommitArgs& c, hipStream_t st);
 hipError_t launch_voicing_map(const int32_t* states, int64_t n, int32_t n_bins, uint8_t* voiced, int32_t* bins,
                               hipStream_t st);
 hipError_t launch_scan_selftest(const float* vals, int n_waves, int mode, float* out_v, int32_t* out_i,

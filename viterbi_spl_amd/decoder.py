@@ -1030,9 +1030,69 @@ class DecodeStream:
         self.decode_into(states, loglik)
         return (states if out_dtype == torch.int32 else states.to(out_dtype)), loglik
 
+    # the default lookback of ``commit`` / ``commit_into``: no cap (2^30 frames, the most vit_stream_commit takes)
+    MAX_LOOKBACK = 1 << 30
+
+    def _commit_begin(self) -> None:
+        if getattr(self, "_commit_ws", None) is not None:
+            return
+        lib = _lib.load()
+        need = int(lib.vit_workspace_bytes_stream_commit(self._dec._plan, self.B))
+        if need == 0:
+            raise _lib.ViterbiHipError("no commit point for this plan: it needs a banded session plan (step-structured plans decide "
+                                       "back-pointers by whole rows)")
+        ws, ptr, nbytes, _ = self._dec._call_workspace(need, None)
+        _lib.check(lib.vit_stream_commit_begin(self._handle(), ptr, nbytes), "vit_stream_commit_begin")
+        self._commit_ws = ws
+        self._committed = np.zeros(self.B, np.int64)     # the frontiers ``commit`` last read back (host)
+
+    def commit_into(self, states: torch.Tensor, committed: torch.Tensor, max_lookback: Optional[int] = None) -> None:
+        """Enqueue ``vit_stream_commit``: for every recording the states of the frames that became final since the last commit are
+        written to ``states[b, f_b:f'_b]`` (int32 [B, stride], stride >= the longest length; nothing else of it is touched) and the
+        new frontier f'_b to ``committed[b]`` (int64 [B]).  Asynchronous: no host synchronisation.  ``max_lookback``: the most
+        frames behind the newest one in which the merge of the survivor paths is looked for (None: no cap).  The commit state is
+        allocated on the first call."""
+        dec = self._dec
+        if states.dtype != torch.int32 or states.dim() != 2 or states.shape[0] != self.B or not states.is_contiguous() or states.device != dec.device:
+            raise ValueError("states must be a contiguous int32 [B, stride] tensor on the decoder's device")
+        if committed.dtype != torch.int64 or tuple(committed.shape) != (self.B,) or not committed.is_contiguous() or committed.device != dec.device:
+            raise ValueError("committed must be an int64 [B] tensor on the decoder's device")
+        self._handle()
+        self._commit_begin()
+        L = self.MAX_LOOKBACK if max_lookback is None else int(max_lookback)
+        with torch.cuda.device(dec.device):
+            rc = _lib.load().vit_stream_commit(self._handle(), states.data_ptr(), int(states.shape[1]), committed.data_ptr(), L,
+                                               torch.cuda.current_stream(dec.device).cuda_stream)
+        _lib.check(rc, "vit_stream_commit")
+
+    def commit(self, max_lookback: Optional[int] = None, out_dtype: torch.dtype = torch.int64):
+        """-> ``(committed lengths (host int64 [B]), [the newly final states of recording b: frames [f_b, f'_b)])``.  The slice
+        bounds live on the device, so this call SYNCHRONISES with the stream to read them; ``commit_into`` does not.  The session
+        keeps an int32 [B, max_frames] tensor of everything committed so far (``committed_states``).  Use either ``commit`` or
+        ``commit_into`` on one session between resets: both advance the same device frontiers, and ``commit`` slices by the ones it read."""
+        dev = self._dec.device
+        if getattr(self, "_commit_states", None) is None:
+            self._commit_states = torch.empty((self.B, self.max_frames), dtype=torch.int32, device=dev)
+            self._commit_dev = torch.zeros((self.B,), dtype=torch.int64, device=dev)
+        self.commit_into(self._commit_states, self._commit_dev, max_lookback)
+        new = self._commit_dev.cpu().numpy().astype(np.int64)
+        old = self._committed
+        self._committed = new
+        fresh = [self._commit_states[b, int(old[b]):int(new[b])] for b in range(self.B)]
+        if out_dtype != torch.int32:
+            fresh = [x.to(out_dtype) for x in fresh]
+        return new.copy(), fresh
+
+    @property
+    def committed_states(self) -> Optional[torch.Tensor]:
+        """int32 [B, max_frames]: row b holds the final states of frames [0, committed length) as of the last ``commit`` (None before)."""
+        return getattr(self, "_commit_states", None)
+
     def reset(self) -> None:
-        """Every recording back to length 0; the workspace is reused."""
+        """Every recording back to length 0 and every commit frontier to 0; the workspace is reused."""
         _lib.check(_lib.load().vit_stream_reset(self._handle()), "vit_stream_reset")
+        if getattr(self, "_commit_ws", None) is not None:
+            self._committed = np.zeros(self.B, np.int64)
 
     def close(self) -> None:
         """Free the session (also on garbage collection).  The workspace tensor is released with the object."""

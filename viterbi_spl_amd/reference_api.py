@@ -542,6 +542,7 @@ class RecordingAccumulator:
         self.streaming = bool(streaming)
         self._stream = viterbi._decoder.stream(1, int(max_frames)) if self.streaming else None
         self._chunk = None                 # (streaming) the emission rows of one append, reused: it grows to the largest append seen
+        self._partial = None               # (streaming) partial(): voiced / bins / notes of the committed frames
 
     def reset(self):
         self.n_frames = 0
@@ -572,6 +573,28 @@ class RecordingAccumulator:
     def logits(self) -> torch.Tensor:
         """The recording so far: ``[n_frames, columns]`` on the GPU (a view)."""
         return self._rows[: self.n_frames]
+
+    def partial(self, note_range=None, max_lookback=None):
+        """``(n_final, voiced, bins, notes)`` of frames ``[0, n_final)``: the part of the recording whose path no later frame can
+        change (``DecodeStream.commit``), a prefix of what ``finish`` will return.  ``streaming=True`` only.  The voicing map and the
+        note gather run over the states committed by this call only; earlier ones are kept.  ``notes`` is None without a
+        ``note_range`` (pass the same one every time).  Synchronises, like ``DecodeStream.commit``."""
+        if self._stream is None:
+            raise ValueError("partial() needs streaming=True")
+        dec, dev, cap = self.viterbi._decoder, self._rows.device, self._rows.shape[0]
+        if self._partial is None:
+            self._partial = (torch.empty(cap, dtype=torch.bool, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+                             torch.empty(cap, dtype=torch.float32, device=dev))
+        voiced, bins, notes = self._partial
+        lens, fresh = self._stream.commit(max_lookback=max_lookback, out_dtype=torch.int32)
+        n_final, k = int(lens[0]), int(fresh[0].numel())
+        if k > 0:
+            nb = self.viterbi.num_freq_bins
+            out = dec.voicing(fresh[0], nb) if note_range is None else dec.voicing_notes(fresh[0], note_range, nb)
+            voiced[n_final - k:n_final], bins[n_final - k:n_final] = out[0], out[1]
+            if note_range is not None:
+                notes[n_final - k:n_final] = out[2]
+        return n_final, voiced[:n_final], bins[:n_final], (notes[:n_final] if note_range is not None else None)
 
     def finish(self, note_range=None):
         if self._stream is not None:
