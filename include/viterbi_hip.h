@@ -617,6 +617,56 @@ int vit_stream_commit_begin(vit_session *s, void *commit_ws, size_t bytes);
 int vit_stream_commit(vit_session *s, int32_t *states /* device [B, states_stride] */, int64_t states_stride,
                       int64_t *committed /* device [B] */, int64_t max_lookback, vit_stream stream);
 
+/* Ring sessions: recordings of any length in a fixed window of history rows.
+ *
+ * No commit and no back-trace of the frames from the frontier f on ever reads a row below f (the proof above).  A ring session keeps
+ * R = ring_rows history rows per recording, frame t in row t mod R of its recording, and a recording may grow to 2^30 frames.  The
+ * results are those of vit_decode() of the whole recording, bit for bit: the concatenated vit_stream_commit_rel() outputs followed
+ * by one vit_stream_tail().
+ *
+ *   vit_workspace_bytes_stream_ring(plan, B, ring_rows)  the layout of vit_workspace_bytes_stream() with ring_rows in place of T_cap:
+ *               [B][ring_rows] delta rows, then the same counters, chunk flags, terminal states, log-likelihoods, chunk entries,
+ *               device lengths and per-launch tables.  64 <= ring_rows <= 2^30, else 0.  0 where the plan is not served.
+ *   vit_stream_open_ring()  as vit_stream_open().  Served: exactly the plans vit_stream_commit() serves (a ring advances by commits
+ *               only); every other plan, step plans included: size 0 / VIT_EUNSUPPORTED.
+ *   vit_stream_append()  on a ring session: the same call, still ONE kernel launch, also where the frames wrap.  Residency: rows
+ *               [f_b, n_b) must stay in the ring.  The library never reads a frontier from the device; it keeps a HOST lower bound a_b
+ *               of every frontier, 0 until the caller reports more with vit_stream_commit_ack().  pos[b] + counts[b] - a_b > R for
+ *               any b: VIT_EWORKSPACE, nothing enqueued, no position moved -- acknowledge newer frontiers, or open with a larger R.
+ *               pos[b] + counts[b] > 2^30: VIT_EINVAL.  STALL: where the survivors of a recording do not merge inside R frames its
+ *               frontier stands, and once n_b - a_b = R the session cannot advance.  Merges come within tens of frames on the
+ *               reference's matrices (the longest merge walk measured is 147 frames); choose R well above that plus the append size.
+ *   vit_stream_commit_ack(s, frontiers)  HOST int64 [B]: frontiers the caller has READ BACK from the `committed` buffer of an earlier
+ *               commit of this session.  Host only: no device access, no synchronisation.  A value below the last acknowledged one
+ *               or above pos[b], or a session that is not a ring session: VIT_EINVAL, nothing changed.  A caller that acknowledges
+ *               values it did not read lets appends overwrite rows a commit still needs: it gets WRONG STATES, but never an access
+ *               outside the buffers (every row index is taken mod R, every range is cut to R frames).
+ *   vit_stream_commit_rel()  vit_stream_commit()'s definition word for word, with a window-relative output: states[b][0 .. f'_b - f_b)
+ *               = the states of frames f_b .. f'_b - 1, first[b] = f_b, committed[b] = f'_b (device int64 [B] each), NOTHING else.
+ *               states_stride >= min(max n_b, R) suffices on a ring session (max n_b on a linear one).  Valid on ring and linear
+ *               sessions after vit_stream_commit_begin(); vit_stream_commit()'s launch shape (one lengths upload, merge, flags'
+ *               memset, speculative pass, verify, repair), no host synchronisation.
+ *   vit_stream_tail()  the frames behind the frontier: states[b][0 .. n_b - f_b) = the best path of the n_b frames so far restricted
+ *               to frames f_b .. n_b - 1, from the terminal state the last append wrote; first[b] = f_b; loglik as in
+ *               vit_stream_backtrace().  Nothing else is written and the frontier does not move.  Before any commit f_b = 0: the call
+ *               then equals vit_stream_backtrace() without the -1 fill.  Valid on both session kinds after vit_stream_commit_begin()
+ *               (it uses the commit buffer's sub-problem tables: order it with the session's commits).  Range lengths and first rows
+ *               are formed on the device from the frontier and the uploaded lengths: no host read.
+ *   On a ring session vit_stream_backtrace() and vit_stream_commit() (absolute output) return VIT_EUNSUPPORTED before anything is
+ *   enqueued; vit_stream_reset() also zeroes the acknowledged frontiers; vit_stream_lengths() and vit_stream_close() work as before.
+ *
+ * Status.  vit_stream_open_ring(): vit_stream_open()'s order (ring_rows outside [64, 2^30] is VIT_EINVAL).  vit_stream_commit_rel():
+ * vit_stream_commit()'s, with NULL first VIT_EINVAL and states_stride below the bound above VIT_EINVAL.  vit_stream_tail(): NULL
+ * session / states / first, no vit_stream_commit_begin(), a recording with 0 frames, states_stride below the longest possible tail
+ * (min(max n_b, R) on a ring, max n_b on a linear session): VIT_EINVAL.  A refused call enqueues and writes nothing. */
+size_t vit_workspace_bytes_stream_ring(const vit_plan *plan, int64_t B, int64_t ring_rows);
+int vit_stream_open_ring(const vit_plan *plan, int64_t B, int64_t ring_rows, void *workspace, size_t workspace_bytes, vit_session **out);
+int vit_stream_commit_ack(vit_session *s, const int64_t *frontiers /* HOST [B] */);
+int vit_stream_commit_rel(vit_session *s, int32_t *states /* device [B, states_stride] */, int64_t states_stride,
+                          int64_t *first /* device [B] */, int64_t *committed /* device [B] */, int64_t max_lookback, vit_stream stream);
+int vit_stream_tail(vit_session *s, int32_t *states /* device [B, states_stride] */, int64_t states_stride,
+                    int64_t *first /* device [B] */, float *loglik /* device [B] or NULL */, vit_stream stream);
+
 /* Event counts of the last vit_backtrace() on this workspace (banded plans; all zero for the kernels that do not count):
  * *offset = byte offset, inside the workspace, of an int32 [B][*n_per_song] device array (valid once the back-trace has run
  * on its stream): per song [0] tiles fetched, [1] span misses (the path left the fetched columns), [2] whole-row evaluations

@@ -13,6 +13,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libviterbi_hip.so")
 
 VIT_OK = 0
+VIT_EWORKSPACE = -4
 VIT_F32, VIT_F16 = 0, 1
 ALGO = {"auto": 0, "dense": 1, "banded": 2, "wave": 3, "group": 4}
 
@@ -32,6 +33,7 @@ EXPORTS = (
     "vit_workspace_bytes_stream", "vit_stream_open", "vit_stream_append", "vit_stream_lengths", "vit_stream_backtrace",
     "vit_stream_reset", "vit_stream_close",
     "vit_workspace_bytes_stream_commit", "vit_stream_commit_begin", "vit_stream_commit",
+    "vit_workspace_bytes_stream_ring", "vit_stream_open_ring", "vit_stream_commit_ack", "vit_stream_commit_rel", "vit_stream_tail",
 )
 ABI_VERSION = 4
 
@@ -174,6 +176,16 @@ def load() -> ctypes.CDLL:
     lib.vit_stream_commit_begin.argtypes = [vp, vp, sz]
     lib.vit_stream_commit.restype = i32
     lib.vit_stream_commit.argtypes = [vp, vp, i64, vp, i64, vp]
+    lib.vit_workspace_bytes_stream_ring.restype = sz
+    lib.vit_workspace_bytes_stream_ring.argtypes = [vp, i64, i64]
+    lib.vit_stream_open_ring.restype = i32
+    lib.vit_stream_open_ring.argtypes = [vp, i64, i64, vp, sz, ctypes.POINTER(vp)]
+    lib.vit_stream_commit_ack.restype = i32
+    lib.vit_stream_commit_ack.argtypes = [vp, vp]
+    lib.vit_stream_commit_rel.restype = i32
+    lib.vit_stream_commit_rel.argtypes = [vp, vp, i64, vp, vp, i64, vp]
+    lib.vit_stream_tail.restype = i32
+    lib.vit_stream_tail.argtypes = [vp, vp, i64, vp, vp, vp]
     lib.vit_forward_family.restype = i32
     lib.vit_forward_family.argtypes = [vp, i64, i32]
     lib.vit_voicing_map.restype = i32

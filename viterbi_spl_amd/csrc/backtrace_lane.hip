@@ -248,6 +248,23 @@ struct LaneOut {
     }
 };
 
+// Where the rows of a sub-problem that starts at row fr of its song live: at fr + k -- or, over a ring session (BtArgs::ring_rows = R),
+// at (fr + k) mod R: the song's rows start at `base`, row k of the sub-problem is row of(k) from there (k < R: one conditional subtract).
+struct LaneRows {
+    size_t base;
+    int first, wrap;
+    __device__ __forceinline__ LaneRows(const BtArgs& a, const size_t fr) {
+        const bool ring = a.ring_rows > 0;
+        base = ring ? 0 : fr;
+        first = ring ? (int)(fr % (size_t)a.ring_rows) : 0;
+        wrap = ring ? (int)a.ring_rows : 0x7fffffff;
+    }
+    __device__ __forceinline__ int of(const int k) const {
+        const int r = first + k;
+        return r >= wrap ? r - wrap : r;
+    }
+};
+
 }  // namespace
 
 // Speculative pass: thread g = song * C + chunk.
@@ -280,8 +297,9 @@ __global__ void __launch_bounds__(kLnThreads) lane_spec_kernel(BtArgs a) {
     const long long off = packed ? a.offsets[song] : 0;
     const int Tb = packed ? (int)(a.offsets[song + 1] - off) : song_length(a, song), Lf = Tb - 1;
     const size_t fr = a.first_row ? (size_t)a.first_row[song] : 0;       // (a session's commit: the sub-problem starts at row / frame fr of its song)
-    int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride + fr);
-    const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows + fr) * SD;
+    const LaneRows rows(a, fr);
+    int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride + (a.states_rel ? 0 : fr));
+    const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows + rows.base) * SD;
     int32_t* __restrict__ entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
     int lo_c, hi_c;
     bt_chunk_bounds(Lf, chunk, C, lo_c, hi_c);
@@ -296,7 +314,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_spec_kernel(BtArgs a) {
     }
     if (__any(guess)) {
         // lowest-index argmax of delta row top+1 (any state would do: a wrong guess costs a repair, not the result)
-        const float* __restrict__ grow = hist + (size_t)(guess ? top + 1 : 0) * SD + a.col0;
+        const float* __restrict__ grow = hist + (size_t)rows.of(guess ? top + 1 : 0) * SD + a.col0;
         float gm = -INFINITY;
         int gi = 0;
         int i = 0;
@@ -320,7 +338,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_spec_kernel(BtArgs a) {
     int entry_v = cur;                      // the state this chunk assumed at frame hi_c (no warm-up: what it started from)
     while (__any(act)) {
         const int tr = t < 0 ? 0 : t;
-        const float* __restrict__ row = hist + (size_t)tr * SD;
+        const float* __restrict__ row = hist + (size_t)rows.of(tr) * SD;
         int nxt;
         if (decide.step(row, tr, Lf, cur, act, nxt)) {
             if (t >= hi_c) { if (t == hi_c) entry_v = nxt; }
@@ -366,7 +384,7 @@ __global__ void lane_verify_kernel(BtArgs a, uint32_t* __restrict__ mask) {
     int lo_c, hi_c;
     bt_chunk_bounds(Lf, c, C, lo_c, hi_c);
     if (hi_c <= lo_c) return;
-    const int truth = a.states[(packed ? (size_t)off : (size_t)song * a.states_stride + (a.first_row ? (size_t)a.first_row[song] : 0)) + hi_c];
+    const int truth = a.states[(packed ? (size_t)off : (size_t)song * a.states_stride + (a.first_row && !a.states_rel ? (size_t)a.first_row[song] : 0)) + hi_c];
     const int32_t* entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
     if (entry[c] != truth) atomicOr(mask + (size_t)song * kLaneMaskWords + (c >> 5), 1u << (c & 31));
 }
@@ -396,8 +414,9 @@ __global__ void __launch_bounds__(kLnThreads) lane_repair_kernel(BtArgs a, const
     const long long off = packed ? a.offsets[song] : 0;
     const int Lf = (packed ? (int)(a.offsets[song + 1] - off) : song_length(a, song)) - 1;
     const size_t fr = a.first_row ? (size_t)a.first_row[song] : 0;
-    int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride + fr);
-    const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows + fr) * SD;
+    const LaneRows rows(a, fr);
+    int32_t* __restrict__ states = a.states + (packed ? (size_t)off : (size_t)song * a.states_stride + (a.states_rel ? 0 : fr));
+    const float* __restrict__ hist = a.hist + (packed ? (size_t)off : (size_t)song * a.hist_rows + rows.base) * SD;
     const int32_t* entry = a.entry + (packed ? (size_t)a.chunk_base[song] : (size_t)song * C);
     LaneDecider<WQ, GT, NWT> decide{a, tabL, loL, lane};
     decide.init();
@@ -437,7 +456,7 @@ __global__ void __launch_bounds__(kLnThreads) lane_repair_kernel(BtArgs a, const
         }
         const bool act = repairing && !done;
         const int tr = act ? t : 0;
-        const float* __restrict__ row = hist + (size_t)tr * SD;
+        const float* __restrict__ row = hist + (size_t)rows.of(tr) * SD;
         int nxt;
         if (decide.step(row, tr, Lf, cur, act, nxt)) {
             const int old = states[t];

@@ -1093,6 +1093,7 @@ static hipError_t floor_variant(const FwdArgs& a, WgVariant v, bool f16, hipStre
         case WgVariant::Ckpt: return f16 ? floor_variant_e<__half, WgVariant::Ckpt>(a, st, per_cu) : floor_variant_e<float, WgVariant::Ckpt>(a, st, per_cu);
         case WgVariant::PackedCkpt: return floor_pckpt(a, f16, st, per_cu);
         case WgVariant::Stream: return floor_stream(a, f16, st, per_cu);
+        case WgVariant::StreamRing: return floor_stream_ring(a, f16, st, per_cu);
         default: return hipErrorInvalidValue;   // (Plain is launch_banded's)
     }
 }

@@ -158,6 +158,10 @@ static_assert(FloorSplitLds::DC == kSplitCopyStride && FloorSplitLds::fmg == kSp
 // re-forms M of that frame, as Ckpt's segment does -- its first frame therefore completes the row the launch before ended with.  No
 // frame is run past the chunk: M of the newest row is stored by the next launch, and the back-trace of a song of n frames reads the
 // pad column of rows 0 .. n - 2 only.  The terminal state and the log-likelihood are Plain's, written after every launch.
+// V = StreamRing is Stream over a ring session (vit_stream_open_ring; instantiated in banded_stream_ring.hip): the song owns a.hist_rows = R
+// rows and frame t lives in row t mod R.  Frames stay absolute (emission rows, t0, Tb); only the row bases differ: a scalar cursor rs holds
+// the slot of row t - 1, the launch resumes from slot (t0 - 1) mod R, and the frame whose row t - 1 sits in slot R - 1 stores M there and
+// its own row into slot 0.  Everything else is Stream's, instruction for instruction.
 // V = Plain compiles to the code it was before the variants existed.  (PK / CK / PC / ST below: V is that variant; PKx / CKx: what the
 // packed-checkpoint variant shares with the packed and with the checkpoint / resume variant; RSx: CKx or ST.)
 template <int W, int NWT, int NXT, int PF, typename ET, WgVariant V = WgVariant::Plain, bool WPR = false>
@@ -167,7 +171,8 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
     constexpr bool PK = V == WgVariant::Packed, CK = V == WgVariant::Ckpt, PC = V == WgVariant::PackedCkpt;
     constexpr bool PKx = PK || PC;                // the song loop and its per-song preamble
     constexpr bool CKx = CK || PC;                // the row selection of the stores, the resumed first frame
-    constexpr bool ST = V == WgVariant::Stream;   // the frames of one launch of a session, rows at their absolute index
+    constexpr bool RG = V == WgVariant::StreamRing;        // Stream with row t at t mod a.hist_rows (the row cursor rs below)
+    constexpr bool ST = V == WgVariant::Stream || RG;      // the frames of one launch of a session, rows at their absolute index
     constexpr bool RSx = CKx || ST;               // the frame loop starts at t1 (a launch may resume a song)
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int NP = L::NP, DC = L::DC, BUF = L::BUF, WR = L::WR;
@@ -188,6 +193,13 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
 #include "wg_cursor.inc"
 #define VIT_WG_CURSOR 2
 #include "wg_cursor.inc"
+    // (StreamRing) the song's ring and the row cursor: the slot of the row in front of the first frame the loop computes.  Scalars.
+    [[maybe_unused]] int ring_rows = 0, rs = 0;
+    if constexpr (RG) {
+        ring_rows = (int)a.hist_rows;
+        hist = a.hist + (size_t)song * (size_t)ring_rows * SD;
+        rs = (int)((unsigned)(t1 - 1) % (unsigned)ring_rows);
+    }
 
     // ---------------- per-lane constants.  Idle lanes (j >= S) carry -inf tables: their delta stays -inf.
     const int j = tid;
@@ -272,7 +284,7 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
         } else if constexpr (ST) {   // frame 0, or the song's own row in front of this launch's first frame (M is re-formed from it)
             float d0 = -INFINITY;
             if (t0 > 0) {
-                if (tvf) d0 = hist[(size_t)(t0 - 1) * SD + jf];
+                if (tvf) d0 = hist[(size_t)(RG ? rs : t0 - 1) * SD + jf];
             } else if (tvf) {
                 d0 = reinterpret_cast<const float*>(a.image + a.off_logpi)[jf] + load_e<ET>(E + jf);
                 hist[jf] = d0;
@@ -402,6 +414,24 @@ __global__ void __launch_bounds__(NWT * 64) banded_floor_forward_kernel(FwdArgs 
 #define VIT_WG_CURSOR 3
 #include "wg_cursor.inc"
                 row_store_f32(hist + row * SD, hoffb, is_fm ? M : dn);
+            } else if constexpr (RG) {
+                // rs = the slot of row t - 1.  Row t is the next slot, and the lanes' offsets reach it from there -- but for the frame whose
+                // row t - 1 sits in the last slot: there lane S stores M into that slot and every other lane from slot 0 (a uniform branch
+                // taken once per ring_rows frames; the cursor is a scalar increment with a scalar compare-and-reset)
+                if (rs != ring_rows - 1) {
+                    row_store_f32(hist + (size_t)rs * SD, hoffb, is_fm ? M : dn);
+                    ++rs;
+                } else {
+                    // (two stores with a uniform row base each, kept apart: joined into one store the row base is a per-lane select, the
+                    // descriptor lives in VGPRs and the store becomes a waterfall loop)
+                    // (the offsets from slot 0 are formed here, from an opaque copy: hoisted out of the loop they cost every frame a VGPR)
+                    unsigned hoff0 = hoffb;
+                    asm volatile("" : "+v"(hoff0));
+                    if (!is_fm) row_store_f32(hist, hoff0 - 4u * (unsigned)SD, dn);
+                    asm volatile("" ::: "memory");
+                    if (is_fm) row_store_f32(hist + (size_t)rs * SD, hoffb, M);
+                    rs = 0;
+                }
             } else {
                 row_store_f32(hist + (size_t)(t - 1) * SD, hoffb, is_fm ? M : dn);
             }
@@ -504,7 +534,7 @@ static hipError_t with_nxt(int n_extras, F&& f) {
 template <int W, int NWT, typename ET, WgVariant V>
 static hipError_t floor_variant_t(const FwdArgs& a, hipStream_t st, int* per_cu) {
     constexpr size_t ldsf = FloorLds<W, NWT, V>::bytes();
-    const int groups = V == WgVariant::Ckpt || V == WgVariant::Stream || (V == WgVariant::PackedCkpt && a.unit_song) ? (int)a.B : a.n_slots;
+    const int groups = V == WgVariant::Ckpt || V == WgVariant::Stream || V == WgVariant::StreamRing || (V == WgVariant::PackedCkpt && a.unit_song) ? (int)a.B : a.n_slots;
     return with_nxt<W>(a.n_extras, [&](auto nxt) -> hipError_t {
         auto kern = banded_floor_forward_kernel<W, NWT, decltype(nxt)::value, floor_pf<W>(), ET, V>;
         if (per_cu) return hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kern, NWT * 64, ldsf);
@@ -515,7 +545,7 @@ static hipError_t floor_variant_t(const FwdArgs& a, hipStream_t st, int* per_cu)
 // the (W, NWT) pairs a variant is instantiated for: Packed and Stream every pair of the floor form, the checkpoint variants floor_ckpt_pair's
 template <typename ET, WgVariant V>
 static hipError_t floor_variant_e(const FwdArgs& a, hipStream_t st, int* per_cu) {
-    constexpr bool packed = V == WgVariant::Packed || V == WgVariant::Stream;    // (floor_stream_applies is floor_packed_applies)
+    constexpr bool packed = V == WgVariant::Packed || V == WgVariant::Stream || V == WgVariant::StreamRing;    // (floor_stream_applies is floor_packed_applies)
     if (!(packed ? floor_packed_applies(a.S, a.W, a.floor_ok != 0, a.n_dense) : floor_ckpt_applies(a.S, a.W, a.floor_ok != 0, a.n_dense)))
         return hipErrorInvalidConfiguration;
     return dispatch_width(a.W, [&](auto w) {

@@ -1898,6 +1898,8 @@ int vit_decode_logits_checkpointed(const vit_plan* plan, const float* logits, co
 // the chunk is the caller's again once the append's kernel has run.  vit_stream_backtrace decodes the recordings as they stand, with
 // the back-trace launches a checkpointed decode uses per segment (they take the song's row count apart from the frame count): the
 // sparse kernel or the lane form for banded plans, the lazy kernel for step plans.  A session always runs the workgroup family.
+// A ring session (vit_stream_open_ring) owns [B, R] rows instead, frame t in row t mod R (WgVariant::StreamRing), and
+// returns its path by vit_stream_commit_rel and vit_stream_tail; its appends are checked against the acknowledged frontiers (ack).
 struct vit_session {
     const vit_plan* plan = nullptr;
     int family = kFamNone;
@@ -1907,6 +1909,10 @@ struct vit_session {
     std::vector<int64_t> pos;           // frames appended per song
     uint8_t* cws = nullptr;             // the commit state (vit_stream_commit_begin), or null
     bool commit_reset = true;           // the next commit counts every frontier as 0 (after commit_begin / reset: a host flag, nothing enqueued)
+    // ring session (vit_stream_open_ring): ring = R > 0 history rows per song, frame t in row t mod R; T_cap = R (st_layout's rows).
+    // ack[b] <= the song's frontier on the device: what the caller has reported (vit_stream_commit_ack).  Rows [ack[b], pos[b]) stay resident.
+    int64_t ring = 0;
+    std::vector<int64_t> ack;
 };
 
 namespace {
@@ -1936,6 +1942,9 @@ StLayout st_layout(const vit_plan* p, int family, int64_t B, int64_t T_cap) {
     return s;
 }
 inline bool st_shape_ok(int64_t B, int64_t T_cap) { return B >= 1 && T_cap >= 1 && B <= (int64_t)1 << 30 && T_cap <= (int64_t)1 << 30; }
+constexpr int64_t kStMaxFrames = (int64_t)1 << 30;      // frames a recording of a ring session may grow to
+constexpr int64_t kStMinRing = 64;
+inline bool st_ring_ok(int64_t B, int64_t R) { return st_shape_ok(B, R) && R >= kStMinRing; }
 
 // The commit state of a session (vit_stream_commit): its own caller-owned buffer, so that st_layout stays what it is.  Served: the
 // banded session plans whose rows the per-lane decision reads (the lane back-trace's predicate); step plans decide by whole rows.
@@ -1965,16 +1974,19 @@ size_t vit_workspace_bytes_stream(const vit_plan* plan, int64_t B, int64_t T_cap
     return st_layout(plan, family, B, T_cap).bytes;
 }
 
-int vit_stream_open(const vit_plan* plan, int64_t B, int64_t T_cap, void* workspace, size_t workspace_bytes, vit_session** out) {
-    if (!plan || !out || !workspace || !st_shape_ok(B, T_cap) || ((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
+namespace {
+// vit_stream_open (ring = 0: T_cap rows per song) and vit_stream_open_ring (ring = T_cap = R rows per song): one status order
+int st_open(const vit_plan* plan, int64_t B, int64_t T_cap, int64_t ring, void* workspace, size_t workspace_bytes, vit_session** out) {
+    if (!plan || !out || !workspace || !(ring ? st_ring_ok(B, ring) : st_shape_ok(B, T_cap)) || ((uintptr_t)workspace & 255) != 0) return VIT_EINVAL;
     if (!plan->dev_image) return VIT_ENOTUPLOADED;
-    const int family = st_family(plan);
+    const int family = ring && !sc_served(plan) ? kFamNone : st_family(plan);     // (a ring advances by commits only)
     if (family == kFamNone) return VIT_EUNSUPPORTED;
     if (workspace_bytes < st_layout(plan, family, B, T_cap).bytes) return VIT_EWORKSPACE;
     vit_session* s = new (std::nothrow) vit_session();
     if (!s) return VIT_ENOMEM;
     try {
         s->pos.assign((size_t)B, 0);
+        if (ring) s->ack.assign((size_t)B, 0);
     } catch (const std::bad_alloc&) {
         delete s;
         return VIT_ENOMEM;
@@ -1983,9 +1995,33 @@ int vit_stream_open(const vit_plan* plan, int64_t B, int64_t T_cap, void* worksp
     s->family = family;
     s->B = B;
     s->T_cap = T_cap;
+    s->ring = ring;
     s->ws = static_cast<uint8_t*>(workspace);
     stamp_erase(plan, workspace);       // (whatever vit_forward left here is the session's to overwrite)
     *out = s;
+    return VIT_OK;
+}
+}  // namespace
+
+int vit_stream_open(const vit_plan* plan, int64_t B, int64_t T_cap, void* workspace, size_t workspace_bytes, vit_session** out) {
+    return st_open(plan, B, T_cap, 0, workspace, workspace_bytes, out);
+}
+
+size_t vit_workspace_bytes_stream_ring(const vit_plan* plan, int64_t B, int64_t ring_rows) {
+    if (!plan || !st_ring_ok(B, ring_rows) || !sc_served(plan)) return 0;
+    return st_layout(plan, st_family(plan), B, ring_rows).bytes;
+}
+
+int vit_stream_open_ring(const vit_plan* plan, int64_t B, int64_t ring_rows, void* workspace, size_t workspace_bytes, vit_session** out) {
+    if (ring_rows < 1) return VIT_EINVAL;
+    return st_open(plan, B, ring_rows, ring_rows, workspace, workspace_bytes, out);
+}
+
+int vit_stream_commit_ack(vit_session* s, const int64_t* frontiers) {
+    if (!s || !frontiers || !s->ring) return VIT_EINVAL;
+    for (int64_t b = 0; b < s->B; ++b)
+        if (frontiers[b] < s->ack[(size_t)b] || frontiers[b] > s->pos[(size_t)b]) return VIT_EINVAL;
+    std::memcpy(s->ack.data(), frontiers, (size_t)s->B * sizeof(int64_t));
     return VIT_OK;
 }
 
@@ -1998,12 +2034,15 @@ int vit_stream_append(vit_session* s, const void* logE, int emis_dtype, int64_t 
     const int64_t B = s->B;
     bool uniform = true;                // every song at the same position, taking the same count: two scalars instead of the tables
     int64_t any = 0;
+    bool resident = true;               // (ring) rows [ack, pos + c) of every song fit its R rows
     for (int64_t b = 0; b < B; ++b) {
         const int64_t c = counts ? counts[b] : n;
-        if (c < 0 || c > n || s->pos[(size_t)b] + c > s->T_cap) return VIT_EINVAL;
+        if (c < 0 || c > n || s->pos[(size_t)b] + c > (s->ring ? kStMaxFrames : s->T_cap)) return VIT_EINVAL;
+        if (s->ring && s->pos[(size_t)b] + c - s->ack[(size_t)b] > s->ring) resident = false;
         uniform = uniform && c == (counts ? counts[0] : n) && s->pos[(size_t)b] == s->pos[0];
         any |= c;
     }
+    if (!resident) return VIT_EWORKSPACE;   // (acknowledge newer frontiers, or open with more rows)
     if (any == 0) return VIT_OK;        // (nothing to append)
     hipStream_t st = (hipStream_t)stream;
     const StLayout L = st_layout(plan, s->family, B, s->T_cap);
@@ -2017,7 +2056,7 @@ int vit_stream_append(vit_session* s, const void* logE, int emis_dtype, int64_t 
     a.last_state = reinterpret_cast<int32_t*>(s->ws + L.off_last);
     a.loglik = reinterpret_cast<float*>(s->ws + L.off_loglik);
     a.B = B;
-    a.T = (int)s->T_cap;
+    a.T = (int)(s->ring ? kStMaxFrames : s->T_cap);     // (ring: frames are absolute, rows are taken mod hist_rows)
     a.hist_rows = s->T_cap;
     a.init_stride = n * (int64_t)plan->S;
     if (uniform) {
@@ -2038,7 +2077,7 @@ int vit_stream_append(vit_session* s, const void* logE, int emis_dtype, int64_t 
         a.unit_song = reinterpret_cast<const int32_t*>(s->ws + L.off_tab);
         a.unit_seg = a.unit_song + B;
     }
-    VIT_TRY(launch_family(s->family, vit::WgVariant::Stream, a, emis_dtype == VIT_F16, st));
+    VIT_TRY(launch_family(s->family, s->ring ? vit::WgVariant::StreamRing : vit::WgVariant::Stream, a, emis_dtype == VIT_F16, st));
     for (int64_t b = 0; b < B; ++b) s->pos[(size_t)b] += counts ? counts[b] : n;
     s->dtype = emis_dtype;
     return VIT_OK;
@@ -2052,6 +2091,7 @@ int vit_stream_lengths(const vit_session* s, int64_t* lengths) {
 
 int vit_stream_backtrace(vit_session* s, int32_t* states, int64_t states_stride, float* loglik, vit_stream stream) {
     if (!s || !states) return VIT_EINVAL;
+    if (s->ring) return VIT_EUNSUPPORTED;                   // (rows below the frontier are gone: vit_stream_commit_rel + vit_stream_tail)
     const vit_plan* plan = s->plan;
     const int64_t B = s->B;
     int64_t tmax = 0;
@@ -2098,6 +2138,7 @@ int vit_stream_backtrace(vit_session* s, int32_t* states, int64_t states_stride,
 int vit_stream_reset(vit_session* s) {
     if (!s) return VIT_EINVAL;
     std::fill(s->pos.begin(), s->pos.end(), (int64_t)0);
+    std::fill(s->ack.begin(), s->ack.end(), (int64_t)0);
     s->dtype = -1;
     s->commit_reset = true;
     return VIT_OK;
@@ -2117,17 +2158,15 @@ int vit_stream_commit_begin(vit_session* s, void* commit_ws, size_t bytes) {
     return VIT_OK;
 }
 
-int vit_stream_commit(vit_session* s, int32_t* states, int64_t states_stride, int64_t* committed, int64_t max_lookback, vit_stream stream) {
-    if (!s || !states || !committed || max_lookback < 1 || max_lookback > (int64_t)1 << 30) return VIT_EINVAL;
-    if (!s->cws) return VIT_EINVAL;
+namespace {
+// The arguments vit_stream_commit, vit_stream_commit_rel and vit_stream_tail share: the merge kernel's (c) over the session's rows and
+// commit state, and the lane back-trace's (b) over the sub-problems c.sub_* name.  rel: the states of a sub-problem start at its song's
+// states_stride row, not at its first frame.  rows = the frames a sub-problem can hold: the chunk count's and the kernels' limit.
+int sc_args(vit_session* s, int32_t* states, int64_t states_stride, int64_t rows, bool rel, vit::CommitArgs& c, vit::BtArgs& b) {
     const vit_plan* plan = s->plan;
     const int64_t B = s->B;
-    int64_t tmax = 0;
-    for (int64_t b = 0; b < B; ++b) tmax = std::max(tmax, s->pos[(size_t)b]);
-    if (states_stride < tmax || states_stride > (int64_t)1 << 30) return VIT_EINVAL;
     const StLayout L = st_layout(plan, s->family, B, s->T_cap);
     const ScLayout C = sc_layout(B);
-    vit::CommitArgs c{};
     bt_args_from_plan(plan, c.b);
     hist_layout_apply(hist_layout(plan, s->family), c.b);
     c.b.aux_frames = 1;
@@ -2136,19 +2175,17 @@ int vit_stream_commit(vit_session* s, int32_t* states, int64_t states_stride, in
     c.b.states = states;
     c.b.states_stride = states_stride;
     c.b.B = B;
-    c.b.T = (int)tmax;
+    c.b.T = (int)rows;
     c.pos = reinterpret_cast<const int64_t*>(s->cws + C.off_pos);
     c.frontier = reinterpret_cast<int64_t*>(s->cws + C.off_front);
-    c.committed = committed;
     c.sub_first = reinterpret_cast<int64_t*>(s->cws + C.off_first);
     c.sub_len = reinterpret_cast<int64_t*>(s->cws + C.off_len);
     c.sub_last = reinterpret_cast<int32_t*>(s->cws + C.off_last);
-    c.max_lookback = max_lookback;
     c.reset = s->commit_reset ? 1 : 0;
     if (!vit::stream_commit_applies(c.b)) return VIT_EUNSUPPORTED;
-    // the committed ranges [f_b, c_b]: the lane back-trace over sub-problems whose first rows, lengths and start states the merge
-    // kernel leaves on the device (a length of 0 is skipped); the chunk count is that of the longest recording, the host knows no range
-    vit::BtArgs b = c.b;
+    // the ranges as sub-problems of the lane back-trace: first rows, lengths and start states stay on the device (a length of 0 is
+    // skipped); the chunk count is that of the longest range there can be, the host knows no range
+    b = c.b;
     b.first_row = c.sub_first;
     b.lengths = c.sub_len;
     b.last_state = c.sub_last;
@@ -2157,17 +2194,80 @@ int vit_stream_commit(vit_session* s, int32_t* states, int64_t states_stride, in
     b.mask = reinterpret_cast<uint32_t*>(s->cws + C.off_mask);
     b.entry = reinterpret_cast<int32_t*>(s->cws + C.off_entry);
     b.bt_form = 4;
+    b.ring_rows = s->ring;
+    b.states_rel = rel ? 1 : 0;
     if (!vit::lane_backtrace_applies(b)) return VIT_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    // the lengths so far through the plan's pinned staging buffer: the call's only upload
-    const int rc = pk_stage(plan, (size_t)B * sizeof(int64_t));
+    return VIT_OK;
+}
+// the lengths so far through the plan's pinned staging buffer: the call's only upload
+int sc_upload_pos(vit_session* s, hipStream_t st) {
+    const vit_plan* plan = s->plan;
+    const size_t bytes = (size_t)s->B * sizeof(int64_t);
+    const int rc = pk_stage(plan, bytes);
     if (rc != VIT_OK) return rc;
-    std::memcpy(plan->pk_host, s->pos.data(), (size_t)B * sizeof(int64_t));
-    const int ru = pk_upload(plan, s->cws + C.off_pos, (size_t)B * sizeof(int64_t), st);
+    std::memcpy(plan->pk_host, s->pos.data(), bytes);
+    return pk_upload(plan, s->cws + sc_layout(s->B).off_pos, bytes, st);
+}
+inline int64_t sc_tmax(const vit_session* s) {
+    int64_t tmax = 0;
+    for (int64_t b = 0; b < s->B; ++b) tmax = std::max(tmax, s->pos[(size_t)b]);
+    return tmax;
+}
+
+int sc_commit(vit_session* s, int32_t* states, int64_t states_stride, int64_t* first, int64_t* committed, int64_t max_lookback, bool rel,
+              vit_stream stream) {
+    if (!s || !states || !committed || (rel && !first) || max_lookback < 1 || max_lookback > (int64_t)1 << 30) return VIT_EINVAL;
+    if (!s->cws) return VIT_EINVAL;
+    if (s->ring && !rel) return VIT_EUNSUPPORTED;           // (absolute output over a ring: the stride would be the recording's length)
+    const int64_t tmax = sc_tmax(s);
+    const int64_t rows = s->ring ? std::min(tmax, s->ring) : tmax;      // the longest range: the resident rows
+    if (states_stride < rows || states_stride > (int64_t)1 << 30) return VIT_EINVAL;
+    vit::CommitArgs c{};
+    vit::BtArgs b{};
+    const int ra = sc_args(s, states, states_stride, rows, rel, c, b);
+    if (ra != VIT_OK) return ra;
+    c.committed = committed;
+    c.first = rel ? first : nullptr;
+    c.max_lookback = max_lookback;
+    hipStream_t st = (hipStream_t)stream;
+    const int ru = sc_upload_pos(s, st);
     if (ru != VIT_OK) return ru;
     VIT_TRY(vit::launch_stream_commit(c, st));
     s->commit_reset = false;
-    if (tmax >= 2) VIT_TRY(segment_backtrace(plan, s->family, true, b, st));
+    if (tmax >= 2) VIT_TRY(segment_backtrace(s->plan, s->family, true, b, st));
+    return VIT_OK;
+}
+}  // namespace
+
+int vit_stream_commit(vit_session* s, int32_t* states, int64_t states_stride, int64_t* committed, int64_t max_lookback, vit_stream stream) {
+    return sc_commit(s, states, states_stride, nullptr, committed, max_lookback, false, stream);
+}
+
+int vit_stream_commit_rel(vit_session* s, int32_t* states, int64_t states_stride, int64_t* first, int64_t* committed, int64_t max_lookback,
+                          vit_stream stream) {
+    return sc_commit(s, states, states_stride, first, committed, max_lookback, true, stream);
+}
+
+int vit_stream_tail(vit_session* s, int32_t* states, int64_t states_stride, int64_t* first, float* loglik, vit_stream stream) {
+    if (!s || !states || !first) return VIT_EINVAL;
+    if (!s->cws) return VIT_EINVAL;
+    for (int64_t b = 0; b < s->B; ++b)
+        if (s->pos[(size_t)b] < 1) return VIT_EINVAL;       // (a song without a frame has no path)
+    const int64_t tmax = sc_tmax(s);
+    const int64_t rows = s->ring ? std::min(tmax, s->ring) : tmax;      // the longest tail there can be
+    if (states_stride < rows || states_stride > (int64_t)1 << 30) return VIT_EINVAL;
+    vit::CommitArgs c{};
+    vit::BtArgs b{};
+    const int ra = sc_args(s, states, states_stride, rows, true, c, b);
+    if (ra != VIT_OK) return ra;
+    c.first = first;
+    hipStream_t st = (hipStream_t)stream;
+    const int ru = sc_upload_pos(s, st);
+    if (ru != VIT_OK) return ru;
+    const StLayout L = st_layout(s->plan, s->family, s->B, s->T_cap);
+    VIT_TRY(vit::launch_stream_tail_prep(c, reinterpret_cast<const int32_t*>(s->ws + L.off_last), st));
+    VIT_TRY(segment_backtrace(s->plan, s->family, true, b, st));
+    if (loglik) VIT_TRY(hipMemcpyAsync(loglik, s->ws + L.off_loglik, (size_t)s->B * sizeof(float), hipMemcpyDeviceToDevice, st));
     return VIT_OK;
 }
 

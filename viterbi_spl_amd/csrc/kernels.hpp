@@ -40,7 +40,8 @@ constexpr int banded_target_waves(int S, int W) {
 //   Ckpt        its own song: pass 1 (checkpoint rows only) or one segment       (vit_decode_checkpointed)
 //   PackedCkpt  pass 1 over the songs of its slot, or one segment unit           (vit_decode_packed_bounded)
 //   Stream      its own song of a session: the next frames, from a chunk of rows (vit_stream_append)
-enum class WgVariant { Plain, Packed, Ckpt, PackedCkpt, Stream };
+//   StreamRing  Stream over a ring of a.hist_rows rows per song: frame t in row t mod hist_rows (vit_stream_open_ring; floor kernel only)
+enum class WgVariant { Plain, Packed, Ckpt, PackedCkpt, Stream, StreamRing };
 // packed variant of the one-target floor kernel (banded_floor_forward_kernel<.., WgVariant::Packed>, vit_decode_packed for plans without
 // the wave form): every instantiated (W, NWT) pair of the floor form; idle slot S stores the frame maximum, so S < 64 * NWT
 constexpr bool floor_packed_applies(int S, int W, bool floor_ok, int n_dense) {
@@ -186,6 +187,11 @@ struct BtArgs {
     // lane form over the committed ranges of a streaming session (vit_stream_commit): sub-problem b is rows / frames first_row[b] ..
     // first_row[b] + lengths[b] - 1 of song b (history by hist_rows, states by states_stride, both moved by first_row[b]); null: 0
     const int64_t* first_row;    // device [B], or null
+    // the same over a ring session (vit_stream_open_ring): ring_rows = R > 0 -- row k of sub-problem b is row (first_row[b] + k) mod R of
+    // song b's R rows (hist_rows = R; lengths[b] <= R); 0: rows as above.  states_rel = 1: the states of sub-problem b start at states +
+    // b * states_stride, not moved by first_row[b] (vit_stream_commit_rel, vit_stream_tail); 0: as above
+    int64_t ring_rows;
+    int states_rel;
 };
 
 // fused.hip: emission builder + wave-form forward recursion in one workgroup (vit_decode_logits).  f: the forward pass's arguments
@@ -317,6 +323,8 @@ hipError_t banded_variant_resident(const FwdArgs& a, WgVariant v, bool f16, int*
 hipError_t floor_pckpt(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu);
 // banded.hip -> banded_stream.hip: the Stream instantiations, likewise
 hipError_t floor_stream(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu);
+// banded.hip -> banded_stream_ring.hip: the StreamRing instantiations, likewise
+hipError_t floor_stream_ring(const FwdArgs& a, bool f16, hipStream_t st, int* per_cu);
 hipError_t launch_step_variant(const FwdArgs& a, WgVariant v, bool f16, hipStream_t st);
 hipError_t step_variant_resident(const FwdArgs& a, WgVariant v, bool f16, int* per_cu);
 // what a variant launch needs of FwdArgs; rows_in_front: extra rows the check demands of a unit's hist_rows beyond K (as before: banded 2, step 0)
@@ -331,6 +339,9 @@ inline bool wg_variant_args_ok(const FwdArgs& a, WgVariant v, int rows_in_front)
         case WgVariant::Stream:
             if (a.offsets || a.lengths || a.B < 1 || a.T < 1 || a.init_stride < 0 || !a.unit_song != !a.unit_seg) return false;
             return a.unit_song || (a.t_begin >= 0 && a.t_end >= a.t_begin && a.t_end <= a.T);
+        case WgVariant::StreamRing:     // frames are absolute (a.T: their limit), rows live in a ring of a.hist_rows rows per song
+            if (a.offsets || a.lengths || a.B < 1 || a.T < 1 || a.init_stride < 0 || !a.unit_song != !a.unit_seg || a.hist_rows < 2) return false;
+            return a.unit_song || (a.t_begin >= 0 && a.t_end >= a.t_begin && a.t_end <= a.T && a.t_end - a.t_begin <= a.hist_rows);
         default: return false;   // (Plain has no variant launch)
     }
 }
@@ -382,7 +393,11 @@ struct CommitArgs {
     int32_t* sub_last;        // s_c
     int64_t max_lookback;     // the merge is looked for in frames [max(f, n - 1 - max_lookback), n - 2]
     int reset;                // 1: every frontier counts as 0 (first commit after vit_stream_commit_begin / vit_stream_reset)
+    int64_t* first;           // device [B], or null: the caller's copy of f, the frontier before this commit (vit_stream_commit_rel)
 };
+// the frames behind the frontier as sub-problems of the lane back-trace (vit_stream_tail): sub_first[b] = first[b] = f_b (0 with `reset`),
+// sub_len[b] = pos[b] - f_b, sub_last[b] = last_state[b]; the frontier is read only
+hipError_t launch_stream_tail_prep(const CommitArgs& c, const int32_t* last_state, hipStream_t st);
 bool stream_commit_applies(const BtArgs& a);
 bool stream_commit_table_in_lds(const BtArgs& a);
 hipError_t launch_stream_commit(const CommitArgs& c, hipStream_t st);

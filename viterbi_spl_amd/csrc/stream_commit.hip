@@ -20,7 +20,9 @@
 //     which is why it is a per-lane scan here and not the lane kernel's whole-wave evaluation of two lanes per call;
 //   * the survivors are deduplicated through an S-bit set in LDS: lane k takes the k-th set bit, a count of 1 ends the walk.
 //     All lanes stand at the same frame at all times, so the merge test needs no catching up.
-// The kernel writes the frontier, committed[b] and the sub-problem, nothing else.
+// The kernel writes the frontier, committed[b], the sub-problem and (vit_stream_commit_rel) first[b] = f, nothing else.
+// Rows are addressed as t mod hist_rows: on a ring session (vit_stream_open_ring) the walk runs backwards across slot 0 -> R - 1; the
+// rows [f, n) it may read are resident by the session's residency rule.  stream_tail_prep_kernel forms vit_stream_tail's sub-problems.
 #include "backtrace_common.hpp"
 
 namespace vit {
@@ -94,7 +96,10 @@ __global__ void __launch_bounds__(kScMaxThreads) stream_commit_kernel(CommitArgs
     const long long t_stop = f > n - 1 - c.max_lookback ? f : n - 1 - c.max_lookback;     // the lowest frame the merge may be found at
     if (n < 2 || t_stop > n - 2) {          // nothing to walk: the frontier stands (uniform in the workgroup)
         __syncthreads();
-        if (tid == 0) { c.frontier[song] = f; c.committed[song] = f; c.sub_first[song] = f; c.sub_len[song] = 0; c.sub_last[song] = 0; }
+        if (tid == 0) {
+            c.frontier[song] = f; c.committed[song] = f; c.sub_first[song] = f; c.sub_len[song] = 0; c.sub_last[song] = 0;
+            if (c.first) c.first[song] = f;
+        }
         return;
     }
     {
@@ -109,22 +114,25 @@ __global__ void __launch_bounds__(kScMaxThreads) stream_commit_kernel(CommitArgs
     const float* tab = GT ? reinterpret_cast<const float*>(a.image + a.off_tabX) : tabL;
 
     float pre0 = 0.f, pre1 = 0.f;           // this thread's share of the row in flight: columns tid and tid + NT (S + 1 <= 2 NT)
-    auto fetch = [&](const long long t) {
-        const float* __restrict__ r = hist + (size_t)t * SD;
+    // frame t lives in row t mod hist_rows (a linear session: hist_rows = its capacity, the cursor never wraps); slot = the row in flight
+    const long long R = a.hist_rows;
+    long long slot = (n - 2) % R;
+    auto fetch = [&]() {
+        const float* __restrict__ r = hist + (size_t)slot * SD;
         if (tid <= S) pre0 = r[tid];
         if (tid + NT <= S) pre1 = r[tid + NT];
     };
     int cur = tid;                          // lane k < count: the k-th survivor at frame t + 1
     int count = S;
     long long t = n - 2;
-    fetch(t);
+    fetch();
     for (;; --t) {
         float* rowL = rowbuf + (t & 1) * SDL;
         uint32_t* bits = bitbuf + (t & 1) * BW;
         if (tid <= S) rowL[tid] = pre0;
         if (tid + NT <= S) rowL[tid + NT] = pre1;
         if (tid < BW) bits[tid] = 0u;
-        if (t > t_stop) fetch(t - 1);
+        if (t > t_stop) { slot = slot == 0 ? R - 1 : slot - 1; fetch(); }
         __syncthreads();
         if (tid < count) {
             int lo;
@@ -156,7 +164,21 @@ __global__ void __launch_bounds__(kScMaxThreads) stream_commit_kernel(CommitArgs
         c.sub_first[song] = f;
         c.sub_len[song] = f2 - f;
         c.sub_last[song] = cur;
+        if (c.first) c.first[song] = f;
     }
+}
+
+// vit_stream_tail: the frames behind the frontier as one sub-problem per recording, formed from the frontier and the uploaded lengths
+__global__ void stream_tail_prep_kernel(CommitArgs c, const int32_t* __restrict__ last_state) {
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= c.b.B) return;
+    const long long n = c.pos[b];
+    long long f = c.reset ? 0 : c.frontier[b];
+    f = f > n ? n : f;
+    c.sub_first[b] = f;
+    c.sub_len[b] = n - f;
+    c.sub_last[b] = last_state[b];
+    c.first[b] = f;
 }
 
 size_t sc_lds_bytes(const BtArgs& a, const bool table_in_lds) {
@@ -181,6 +203,12 @@ hipError_t launch_stream_commit(const CommitArgs& c, hipStream_t st) {
     const dim3 grid((unsigned)a.B), block((unsigned)((a.S + 63) / 64 * 64));
     if (in_lds) hipLaunchKernelGGL(stream_commit_kernel<false>, grid, block, sc_lds_bytes(a, true), st, c);
     else hipLaunchKernelGGL(stream_commit_kernel<true>, grid, block, sc_lds_bytes(a, false), st, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_tail_prep(const CommitArgs& c, const int32_t* last_state, hipStream_t st) {
+    if (c.b.B < 1 || !c.first || !last_state) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_tail_prep_kernel, dim3((unsigned)((c.b.B + 255) / 256)), dim3(256), 0, st, c, last_state);
     return hipGetLastError();
 }
 

@@ -660,13 +660,26 @@ class ViterbiDecoder:
         form (see ``stream``)."""
         return int(_lib.load().vit_workspace_bytes_stream(self._plan, int(B), int(max_frames)))
 
-    def stream(self, B: int, max_frames: int, workspace: Optional[torch.Tensor] = None) -> "DecodeStream":
+    def workspace_bytes_stream_ring(self, B: int, ring_frames: int) -> int:
+        """Workspace bytes of a ``stream(B, ring_frames=R)`` session (``vit_workspace_bytes_stream_ring``); 0 when the plan has no
+        commit point or R is outside [64, 2**30]."""
+        return int(_lib.load().vit_workspace_bytes_stream_ring(self._plan, int(B), int(ring_frames)))
+
+    def stream(self, B: int, max_frames: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
+               ring_frames: Optional[int] = None) -> "DecodeStream":
         """A streaming session for B recordings of at most ``max_frames`` frames: ``append`` advances the forward pass chunk by
         chunk as emission rows arrive, ``decode`` back-traces the recordings as they stand -- the states and log-likelihoods of
         ``decode`` on the same frames, bit for bit, for any chunking.  For banded plans whose floor form is proven (the 321-, 361-
         and 722-state grids) and step-structured plans (the Durrieu matrix); any other plan raises ``ViterbiHipError``.
-        ``workspace``: a uint8 tensor of at least ``workspace_bytes_stream(B, max_frames) + 256`` bytes, or None to allocate one."""
-        return DecodeStream(self, B, max_frames, workspace)
+        ``workspace``: a uint8 tensor of at least ``workspace_bytes_stream(B, max_frames) + 256`` bytes, or None to allocate one.
+
+        ``ring_frames=R`` (64 <= R <= 2**30) opens a RING session instead: R history rows per recording whatever its length
+        (``max_frames`` is not needed), for the plans that have a commit point (the banded session plans).  Output then comes from
+        ``commit()`` -- the frames that became final, which also lets the ring advance -- and ``tail()``, the frames behind the
+        frontier; ``decode()`` and ``commit_into`` raise.  An ``append`` that would overwrite rows a commit may still need raises
+        ``ViterbiHipError`` (commit first, or open with a larger R); where survivors do not merge inside R frames the session
+        cannot advance.  ``workspace``: at least ``workspace_bytes_stream_ring(B, R) + 256`` bytes."""
+        return DecodeStream(self, B, max_frames, workspace, ring_frames)
 
     def workspace_bytes_packed(self, B: int, total_frames: int) -> int:
         """Workspace bytes of ``decode_packed`` for B recordings of ``total_frames`` frames together; 0 when the plan has none of
@@ -964,11 +977,27 @@ class DecodeStream:
     current stream of the decoder's device; the caller orders the calls of one session as for any other tensor work (one stream, or
     events).  A chunk tensor may be rewritten as soon as its ``append`` has run in stream order: nothing reads emission rows again."""
 
-    def __init__(self, decoder: ViterbiDecoder, B: int, max_frames: int, workspace: Optional[torch.Tensor] = None):
+    def __init__(self, decoder: ViterbiDecoder, B: int, max_frames: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
+                 ring_frames: Optional[int] = None):
         lib = _lib.load()
         self._dec = decoder                    # (keeps the plan alive)
-        self.B, self.max_frames = int(B), int(max_frames)
         self._session = ctypes.c_void_p()
+        self.ring_frames = None if ring_frames is None else int(ring_frames)
+        if self.ring_frames is not None:
+            self.B, self.max_frames = int(B), None
+            if self.B < 1:
+                raise ValueError("a stream needs B >= 1 recordings")
+            need = decoder.workspace_bytes_stream_ring(self.B, self.ring_frames)
+            if need == 0:
+                raise _lib.ViterbiHipError("no ring session for this plan or size: it needs a banded session plan (one with a commit "
+                                           "point) and 64 <= ring_frames <= 2**30")
+            self._ws, ws_ptr, ws_bytes, _ = decoder._call_workspace(need, workspace)
+            _lib.check(lib.vit_stream_open_ring(decoder._plan, self.B, self.ring_frames, ws_ptr, ws_bytes, ctypes.byref(self._session)),
+                       "vit_stream_open_ring")
+            return
+        if max_frames is None:
+            raise ValueError("a stream needs max_frames (or ring_frames)")
+        self.B, self.max_frames = int(B), int(max_frames)
         if self.B < 1 or self.max_frames < 1:
             raise ValueError("a stream needs B >= 1 recordings and max_frames >= 1")
         need = decoder.workspace_bytes_stream(self.B, self.max_frames)
@@ -1000,6 +1029,10 @@ class DecodeStream:
         with torch.cuda.device(dec.device):
             rc = _lib.load().vit_stream_append(self._handle(), logE.data_ptr(), dt, int(logE.shape[1]), cnt.ctypes.data if cnt is not None else None,
                                                torch.cuda.current_stream(dec.device).cuda_stream)
+        if rc == _lib.VIT_EWORKSPACE and self.ring_frames is not None:
+            raise _lib.ViterbiHipError(f"vit_stream_append: the frames would overwrite ring rows behind the acknowledged frontier "
+                                       f"(ring_frames = {self.ring_frames}): commit() first (or ack() frontiers read from commit_rel_into), "
+                                       "or open the stream with a larger ring")
         _lib.check(rc, "vit_stream_append")
 
     @property
@@ -1013,8 +1046,9 @@ class DecodeStream:
         """Enqueue the back-trace of the recordings as they stand: ``states`` int32 [B, stride], stride >= the longest length (-1
         behind each length), ``loglik`` float32 [B] or None."""
         dec = self._dec
-        if states.dtype != torch.int32 or states.dim() != 2 or states.shape[0] != self.B or not states.is_contiguous() or states.device != dec.device:
-            raise ValueError("states must be a contiguous int32 [B, stride] tensor on the decoder's device")
+        if self.ring_frames is not None:
+            raise _lib.ViterbiHipError("decode() needs every history row: a ring session returns its path by commit() and tail()")
+        self._check_states(states)
         if loglik is not None and (loglik.dtype != torch.float32 or tuple(loglik.shape) != (self.B,) or not loglik.is_contiguous() or loglik.device != dec.device):
             raise ValueError("loglik must be a float32 [B] tensor on the decoder's device")
         with torch.cuda.device(dec.device):
@@ -1053,10 +1087,10 @@ class DecodeStream:
         frames behind the newest one in which the merge of the survivor paths is looked for (None: no cap).  The commit state is
         allocated on the first call."""
         dec = self._dec
-        if states.dtype != torch.int32 or states.dim() != 2 or states.shape[0] != self.B or not states.is_contiguous() or states.device != dec.device:
-            raise ValueError("states must be a contiguous int32 [B, stride] tensor on the decoder's device")
-        if committed.dtype != torch.int64 or tuple(committed.shape) != (self.B,) or not committed.is_contiguous() or committed.device != dec.device:
-            raise ValueError("committed must be an int64 [B] tensor on the decoder's device")
+        if self.ring_frames is not None:
+            raise _lib.ViterbiHipError("commit_into writes at absolute frames: a ring session commits with commit_rel_into (or commit())")
+        self._check_states(states)
+        self._check_i64(committed, "committed")
         self._handle()
         self._commit_begin()
         L = self.MAX_LOOKBACK if max_lookback is None else int(max_lookback)
@@ -1065,11 +1099,101 @@ class DecodeStream:
                                                torch.cuda.current_stream(dec.device).cuda_stream)
         _lib.check(rc, "vit_stream_commit")
 
+    def _check_states(self, states: torch.Tensor) -> None:
+        if states.dtype != torch.int32 or states.dim() != 2 or states.shape[0] != self.B or not states.is_contiguous() or states.device != self._dec.device:
+            raise ValueError("states must be a contiguous int32 [B, stride] tensor on the decoder's device")
+
+    def _check_i64(self, x: torch.Tensor, name: str) -> None:
+        if x.dtype != torch.int64 or tuple(x.shape) != (self.B,) or not x.is_contiguous() or x.device != self._dec.device:
+            raise ValueError(f"{name} must be an int64 [B] tensor on the decoder's device")
+
+    def commit_rel_into(self, states: torch.Tensor, first: torch.Tensor, committed: torch.Tensor, max_lookback: Optional[int] = None) -> None:
+        """Enqueue ``vit_stream_commit_rel``: ``commit_into`` with a window-relative output -- the states of the frames
+        ``[f_b, f'_b)`` that became final go to ``states[b, :f'_b - f_b]`` (int32 [B, stride]; on a ring session stride >=
+        min(longest length, ring_frames) suffices), ``first[b] = f_b`` and ``committed[b] = f'_b`` (int64 [B] each); nothing else is
+        written.  Asynchronous.  On a ring session, report the frontiers you read back with ``ack`` so that appends may go on."""
+        dec = self._dec
+        self._check_states(states)
+        self._check_i64(first, "first")
+        self._check_i64(committed, "committed")
+        self._handle()
+        self._commit_begin()
+        L = self.MAX_LOOKBACK if max_lookback is None else int(max_lookback)
+        with torch.cuda.device(dec.device):
+            rc = _lib.load().vit_stream_commit_rel(self._handle(), states.data_ptr(), int(states.shape[1]), first.data_ptr(), committed.data_ptr(), L,
+                                                   torch.cuda.current_stream(dec.device).cuda_stream)
+        _lib.check(rc, "vit_stream_commit_rel")
+
+    def ack(self, frontiers) -> None:
+        """Ring sessions: tell the session the frontiers (host, B ints) READ BACK from a ``committed`` tensor of an earlier commit;
+        rows below them may then be overwritten by appends (``vit_stream_commit_ack``: host only).  Values that go down or lie
+        beyond the lengths raise.  Acknowledging values that were not read gives wrong states."""
+        fr = np.ascontiguousarray(np.asarray(frontiers, dtype=np.int64))
+        if fr.shape != (self.B,):
+            raise ValueError("frontiers must hold one entry per recording")
+        _lib.check(_lib.load().vit_stream_commit_ack(self._handle(), fr.ctypes.data), "vit_stream_commit_ack")
+
+    def tail_into(self, states: torch.Tensor, first: torch.Tensor, loglik: Optional[torch.Tensor] = None) -> None:
+        """Enqueue ``vit_stream_tail``: the best path of the frames so far, restricted to the frames behind the frontier:
+        ``states[b, :n_b - f_b]`` (int32 [B, stride], stride >= the longest possible tail), ``first[b] = f_b`` (int64 [B]),
+        ``loglik`` float32 [B] or None.  The frontier does not move.  Asynchronous; ring and linear sessions alike."""
+        dec = self._dec
+        self._check_states(states)
+        self._check_i64(first, "first")
+        if loglik is not None and (loglik.dtype != torch.float32 or tuple(loglik.shape) != (self.B,) or not loglik.is_contiguous() or loglik.device != dec.device):
+            raise ValueError("loglik must be a float32 [B] tensor on the decoder's device")
+        self._handle()
+        self._commit_begin()
+        with torch.cuda.device(dec.device):
+            rc = _lib.load().vit_stream_tail(self._handle(), states.data_ptr(), int(states.shape[1]), first.data_ptr(),
+                                             loglik.data_ptr() if loglik is not None else None, torch.cuda.current_stream(dec.device).cuda_stream)
+        _lib.check(rc, "vit_stream_tail")
+
+    def _window(self) -> int:
+        n = max(int(self.lengths.max()), 1)
+        return n if self.ring_frames is None else min(n, self.ring_frames)
+
+    def tail(self, out_dtype: torch.dtype = torch.int64):
+        """-> ``(first (host int64 [B]), [the states of frames [f_b, n_b) of recording b], loglik [B])``: with the commits so far,
+        the whole best path of the frames appended.  SYNCHRONISES to read the slice bounds."""
+        dev = self._dec.device
+        states = torch.empty((self.B, self._window()), dtype=torch.int32, device=dev)
+        first = torch.zeros((self.B,), dtype=torch.int64, device=dev)
+        loglik = torch.empty((self.B,), dtype=torch.float32, device=dev)
+        n = self.lengths
+        self.tail_into(states, first, loglik)
+        f = first.cpu().numpy().astype(np.int64)
+        out = [states[b, :int(n[b] - f[b])] for b in range(self.B)]
+        if out_dtype != torch.int32:
+            out = [x.to(out_dtype) for x in out]
+        return f, out, loglik
+
+    def _commit_ring(self, max_lookback: Optional[int], out_dtype: torch.dtype):
+        dev = self._dec.device
+        if getattr(self, "_commit_dev", None) is None:
+            self._commit_dev = torch.zeros((self.B,), dtype=torch.int64, device=dev)
+            self._first_dev = torch.zeros((self.B,), dtype=torch.int64, device=dev)
+        states = torch.empty((self.B, self._window()), dtype=torch.int32, device=dev)
+        self.commit_rel_into(states, self._first_dev, self._commit_dev, max_lookback)
+        first = self._first_dev.cpu().numpy().astype(np.int64)
+        new = self._commit_dev.cpu().numpy().astype(np.int64)
+        self.ack(new)
+        self._committed = new
+        fresh = [states[b, :int(new[b] - first[b])] for b in range(self.B)]
+        if out_dtype != torch.int32:
+            fresh = [x.to(out_dtype) for x in fresh]
+        return first, new.copy(), fresh
+
     def commit(self, max_lookback: Optional[int] = None, out_dtype: torch.dtype = torch.int64):
         """-> ``(committed lengths (host int64 [B]), [the newly final states of recording b: frames [f_b, f'_b)])``.  The slice
         bounds live on the device, so this call SYNCHRONISES with the stream to read them; ``commit_into`` does not.  The session
         keeps an int32 [B, max_frames] tensor of everything committed so far (``committed_states``).  Use either ``commit`` or
-        ``commit_into`` on one session between resets: both advance the same device frontiers, and ``commit`` slices by the ones it read."""
+        ``commit_into`` on one session between resets: both advance the same device frontiers, and ``commit`` slices by the ones it read.
+
+        On a RING session the result is ``(first, committed, [states of frames [first_b, committed_b)])`` (``commit_rel_into``), the
+        frontiers read are acknowledged so that appends may reuse the rows below them, and no tensor of everything committed is kept."""
+        if self.ring_frames is not None:
+            return self._commit_ring(max_lookback, out_dtype)
         dev = self._dec.device
         if getattr(self, "_commit_states", None) is None:
             self._commit_states = torch.empty((self.B, self.max_frames), dtype=torch.int32, device=dev)

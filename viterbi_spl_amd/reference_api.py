@@ -523,10 +523,13 @@ class RecordingAccumulator:
     rows of the new frames with the wrapped class's stand-alone builder (the builders work per frame: the rows a whole-recording
     call would build, bit for bit) into a chunk buffer it keeps, and advances a one-recording ``ViterbiDecoder.stream`` by them; ``finish`` is then the
     back-trace, the voicing map and the note gather, with the result of ``streaming=False``.  The default is ``False``, and
-    ``logits()`` works in both modes.  The class wraps the three logits decoders only: ``ImmViterbi`` callers stream with
+    ``logits()`` works in both modes.  ``ring_frames=R`` (with ``streaming=True``) runs the stream as a ring session: R history rows
+    whatever ``max_frames`` is; ``partial()`` works as before (call it often enough that R frames never pile up behind the frontier),
+    ``finish()`` is the last commit plus the tail behind it and returns what ``streaming=True`` returns.  Only the history is bounded
+    by R: the logits rows and the outputs keep ``max_frames``.  The class wraps the three logits decoders only: ``ImmViterbi`` callers stream with
     ``viterbi._decoder.stream(...)`` and ``emissions.activation_log_emissions`` per chunk."""
 
-    def __init__(self, viterbi: _PreparedViterbi, max_frames: int, streaming: bool = False):
+    def __init__(self, viterbi: _PreparedViterbi, max_frames: int, streaming: bool = False, ring_frames: int | None = None):
         self.viterbi = viterbi
         if isinstance(viterbi, Viterbi):
             self.mode, self.channels, self.cols = 0, viterbi.num_freq_bins + 1, viterbi.num_freq_bins
@@ -540,7 +543,11 @@ class RecordingAccumulator:
         self._rows = torch.empty((int(max_frames), self.cols), dtype=torch.float32, device=dev)
         self.n_frames = 0
         self.streaming = bool(streaming)
-        self._stream = viterbi._decoder.stream(1, int(max_frames)) if self.streaming else None
+        if ring_frames is not None and not self.streaming:
+            raise ValueError("ring_frames needs streaming=True")
+        self._stream = viterbi._decoder.stream(1, int(max_frames), ring_frames=ring_frames) if self.streaming else None
+        # (ring) the states committed so far: the ring bounds the history rows only, the outputs keep max_frames
+        self._ring_states = torch.empty(int(max_frames), dtype=torch.int32, device=dev) if ring_frames is not None else None
         self._chunk = None                 # (streaming) the emission rows of one append, reused: it grows to the largest append seen
         self._partial = None               # (streaming) partial(): voiced / bins / notes of the committed frames
 
@@ -586,7 +593,11 @@ class RecordingAccumulator:
             self._partial = (torch.empty(cap, dtype=torch.bool, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
                              torch.empty(cap, dtype=torch.float32, device=dev))
         voiced, bins, notes = self._partial
-        lens, fresh = self._stream.commit(max_lookback=max_lookback, out_dtype=torch.int32)
+        if self._ring_states is not None:
+            first, lens, fresh = self._stream.commit(max_lookback=max_lookback, out_dtype=torch.int32)
+            self._ring_states[int(first[0]):int(lens[0])] = fresh[0]
+        else:
+            lens, fresh = self._stream.commit(max_lookback=max_lookback, out_dtype=torch.int32)
         n_final, k = int(lens[0]), int(fresh[0].numel())
         if k > 0:
             nb = self.viterbi.num_freq_bins
@@ -599,7 +610,14 @@ class RecordingAccumulator:
     def finish(self, note_range=None):
         if self._stream is not None:
             dec = self.viterbi._decoder
-            states, _ = self._stream.decode(out_dtype=torch.int32)
+            if self._ring_states is not None:      # the last commit, then the frames behind the frontier
+                first, lens, fresh = self._stream.commit(out_dtype=torch.int32)
+                self._ring_states[int(first[0]):int(lens[0])] = fresh[0]
+                f, tail, _ = self._stream.tail(out_dtype=torch.int32)
+                self._ring_states[int(f[0]):self.n_frames] = tail[0]
+                states = self._ring_states[None, :self.n_frames]
+            else:
+                states, _ = self._stream.decode(out_dtype=torch.int32)
             out = dec.voicing(states[0], self.viterbi.num_freq_bins) if note_range is None else dec.voicing_notes(states[0], note_range, self.viterbi.num_freq_bins)
         else:
             out = self.viterbi.decode_logits(self.logits(), note_range)
