@@ -17,6 +17,7 @@ libviterbi_hip.so.  Nothing in this module falls back to the CPU.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import hashlib
 from typing import Optional, Tuple
@@ -25,10 +26,43 @@ import numpy as np
 import torch
 
 from . import _lib
+from .stream import DecodeStream  # noqa: F401  (the sessions' module; this one stays the surface callers import)
 
 
-_NO_PACKED_DECODE = ("the packed decode needs a plan with the wave form, the floor form or the step form "
-                     "(unstructured matrices and scan-only banded plans: pad and use decode(lengths=))")
+_NO_F64 = ("banded, its floor form proven, without dense rows (unstructured matrices, the Durrieu step matrices and scan-only plans "
+           "are not served)")
+_NO_LOGITS = ("the fused logits decode needs a plan with the wave form whose extra column is the last state (S = 321 / 361), "
+              "n_bins = S - 1, and a builder geometry of the reference (shaun / scaled softmax with peak width 5, softmax with 15): "
+              "build the emissions and use decode()")
+# The entry table: `entry` names the pair ``vit_workspace_bytes_<entry>`` / ``vit_decode_<entry>`` (sessions: ``vit_stream_open*``,
+# ``vit_stream_commit_begin``) -> what a caller is told when the size query answers 0: the plan, or the segment length, is not served.
+_NOT_SERVED = {
+    "checkpointed": "the checkpointed decode needs 64 <= segment_frames <= 2**24 and a plan with the wave form, the floor form (banded, "
+                    "no dense rows) or the step form (unstructured matrices and scan-only banded plans: decode() with the full history)",
+    "f64": "the float64 decode needs a banded plan whose floor form is proven, without dense rows (unstructured matrices, the Durrieu "
+           "step matrices and scan-only plans are not served)",
+    "f64_checkpointed": "the checkpointed float64 decode needs 64 <= segment_frames <= 2**24 and a plan decode_f64 serves: " + _NO_F64,
+    "f64_packed": "the packed float64 decode needs a banded plan whose floor form is proven, without dense rows (unstructured matrices, "
+                  "the Durrieu step matrices and scan-only plans are not served)",
+    "f64_packed_checkpointed": "the packed checkpointed float64 decode needs 64 <= segment_frames <= 2**24 and a plan decode_f64 "
+                               "serves: " + _NO_F64,
+    "packed": "the packed decode needs a plan with the wave form, the floor form or the step form (unstructured matrices and scan-only "
+              "banded plans: pad and use decode(lengths=))",
+    "packed_checkpointed": "the packed checkpointed decode needs 64 <= segment_frames <= 2**24 and a plan with the wave form (S = 321 / "
+                           "361; the 722-state grids: pad and use decode_checkpointed(lengths=), or split the recordings into groups "
+                           "whose workspace_bytes_packed fits)",
+    "packed_bounded": "the bounded packed decode needs 64 <= segment_frames <= 2**24 and a plan with the wave form, the floor form with "
+                      "the sparse back-trace, or the step form (unstructured matrices and scan-only banded plans: pad and use "
+                      "decode(lengths=))",
+    "logits": _NO_LOGITS,
+    "logits_checkpointed": "the checkpointed fused logits decode needs 64 <= segment_frames <= 2**24; " + _NO_LOGITS,
+    "stream": "no streaming decode for this plan: it needs a banded plan whose floor form is proven (no dense rows) or a "
+              "step-structured plan of the Durrieu geometry",
+    "stream_ring": "no ring session for this plan or size: it needs a banded session plan (one with a commit point) and 64 <= "
+                   "ring_frames <= 2**30",
+    "stream_commit": "no commit point for this plan: it needs a banded session plan (step-structured plans decide back-pointers by whole "
+                     "rows)",
+}
 
 
 def _as_host_f32(x, shape=None) -> np.ndarray:
@@ -38,6 +72,11 @@ def _as_host_f32(x, shape=None) -> np.ndarray:
     if shape is not None and a.shape != shape:
         raise ValueError(f"expected shape {shape}, got {a.shape}")
     return a
+
+
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    """The address of an optional tensor argument (None stays None: the library's NULL)."""
+    return t.data_ptr() if t is not None else None
 
 
 class ViterbiDecoder:
@@ -97,6 +136,16 @@ class ViterbiDecoder:
             self._options = {}
         else:
             self._options[key] = int(value)
+
+    @contextlib.contextmanager
+    def _option(self, key: str, value: int):
+        """Hold option `key` at `value` inside a ``with`` block, then put back what was set before (0: the library's default)."""
+        prev = self._options.get(key, 0)
+        self.set_option(key, value)
+        try:
+            yield
+        finally:
+            self.set_option(key, prev)
 
     def chunks_beside_forward(self, B: int) -> int:
         """``bt_chunks`` for the two-stream schedule (the back-trace of batch i beside the forward pass of batch i + 1): while one
@@ -165,6 +214,54 @@ class ViterbiDecoder:
         if ws.dtype != torch.uint8 or ws.device != self.device or ws.numel() < need + 256:
             raise ValueError(f"workspace must be a uint8 tensor of at least {need + 256} bytes on the decoder's device")
         return ws, (ws.data_ptr() + 255) & ~255, ws.numel() - 256, workspace is None
+
+    # ------------------------------------------------------------------ the one call path of the decodes that take a workspace
+    def _need(self, entry: str, required: bool, *args) -> int:
+        """``vit_workspace_bytes_<entry>(plan, *args)``.  0 means the plan (or the segment length) is not served: ViterbiHipError
+        with the entry's text of ``_NOT_SERVED`` when `required`, else the 0."""
+        need = int(getattr(_lib.load(), "vit_workspace_bytes_" + entry)(self._plan, *args))
+        if need == 0 and required:
+            raise _lib.ViterbiHipError(_NOT_SERVED[entry])
+        return need
+
+    def _enqueue(self, entry: str, *args) -> None:
+        """``vit_decode_<entry>(plan, *args, stream)`` on the current stream of the decoder's device."""
+        with torch.cuda.device(self.device):
+            rc = getattr(_lib.load(), "vit_decode_" + entry)(self._plan, *args, torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.check(rc, "vit_decode_" + entry)
+
+    def _finish(self, states: torch.Tensor, loglik: torch.Tensor, out_dtype: torch.dtype, allocated: bool, single: bool = False
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The end of every such decode: a workspace `allocated` by the call must outlive its kernels, so the stream is synchronised
+        then and only then; the states as ``out_dtype``; a `single` [T, S] input gets its [T] path and scalar back."""
+        if allocated:
+            torch.cuda.current_stream(self.device).synchronize()
+        if out_dtype != torch.int32:
+            states = states.to(out_dtype)
+        return (states[0], loglik[0]) if single else (states, loglik)
+
+    def _decode_entry(self, entry: str, B: int, shape: tuple, loglik_dtype: torch.dtype, out_dtype: torch.dtype,
+                      workspace: Optional[torch.Tensor], size_args: tuple, head: tuple, mid: tuple = (), tail: tuple = (),
+                      single: bool = False, own_buffer: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One decode of B recordings through ``vit_decode_<entry>``, after the caller's argument checks: the outputs (int32 states of
+        `shape`, loglik [B]), the size query (``vit_workspace_bytes_<entry>(plan, *size_args)``; not served raises), the workspace, the
+        call -- the library takes ``head..., workspace, bytes, mid..., states, loglik, tail...`` -- and the finish.  The workspace is
+        the caller's tensor, else one allocated for this call (followed by a stream synchronise); `own_buffer` (``decode_f64``): else
+        the decoder's slot-0 buffer, shared with ``decode`` and grown like it, and no synchronisation.  B == 0 asks the library
+        nothing."""
+        states = torch.empty(shape, dtype=torch.int32, device=self.device)
+        loglik = torch.empty((B,), dtype=loglik_dtype, device=self.device)
+        ws, allocated = None, False                         # (ws: a buffer allocated here lives until the synchronise in _finish)
+        if B > 0:
+            need = self._need(entry, True, *size_args)
+            if own_buffer and workspace is None:
+                if self._ws is None or self._ws.numel() < need + 256:
+                    self._ws = None
+                    self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                workspace = self._ws
+            ws, ws_ptr, ws_bytes, allocated = self._call_workspace(need, workspace)
+            self._enqueue(entry, *head, ws_ptr, ws_bytes, *mid, states.data_ptr(), loglik.data_ptr(), *tail)
+        return self._finish(states, loglik, out_dtype, allocated, single)
 
     # ------------------------------------------------------------------ checks
     def _check_emissions(self, logE: torch.Tensor) -> Tuple[torch.Tensor, bool, int]:
@@ -265,21 +362,18 @@ class ViterbiDecoder:
         need = self.workspace_bytes(B, T, algo)
         if max_workspace_bytes is None or need <= max_workspace_bytes:
             return {"mode": "full", "workspace_bytes": need}
-        lib = _lib.load()
         wave = self.info["wave_ok"] and algo in ("auto", "banded", "wave") and T >= 2
         # plans without the wave form: the workgroup kernels of the checkpointed decode stand in for the banded workgroup family
         # or (step plans) for what "auto" picks; an `algo` that means the dense kernel keeps raising
         group = not self.info["wave_ok"] and ((self.info["banded_ok"] and algo in ("auto", "banded", "group")) or
                                               (not self.info["banded_ok"] and self.info["step_ok"] and algo == "auto"))
         if wave:
-            prev = self._options.get("wave_history", 0)
-            _lib.check(lib.vit_plan_set_option(self._plan, b"wave_history", 2), "vit_plan_set_option(wave_history)")
-            half = int(lib.vit_workspace_bytes_for(self._plan, B, T, _lib.ALGO["wave"]))
-            _lib.check(lib.vit_plan_set_option(self._plan, b"wave_history", prev), "vit_plan_set_option(wave_history)")
+            with self._option("wave_history", 2):
+                half = int(_lib.load().vit_workspace_bytes_for(self._plan, B, T, _lib.ALGO["wave"]))
             if 0 < half <= max_workspace_bytes:
                 return {"mode": "half", "workspace_bytes": half}
         def checkpointed(K):                                # (0: an `algo` the checkpointed decode does not stand in for)
-            return lib.vit_workspace_bytes_checkpointed(self._plan, B, T, K) if wave or group else 0
+            return self._need("checkpointed", False, B, T, K) if wave or group else 0
         return self._plan_segments(need, checkpointed, max_workspace_bytes,
                                    lambda _: f"no decode of a [{B}, {T}, {self.S}] batch fits a workspace of {max_workspace_bytes} bytes "
                                              f"(the normal decode needs {need})")
@@ -300,13 +394,9 @@ class ViterbiDecoder:
                 st, ll = self.decode_checkpointed(logE, segment_frames=mode["segment_frames"], lengths=lengths, out_dtype=out_dtype)
                 return (st[0], ll[0]) if single else (st, ll)
             if mode["mode"] == "half":
-                prev = self._options.get("wave_history", 0)
-                self.set_option("wave_history", 2)
-                self._ws = None                              # (a larger buffer kept from an earlier decode would defeat the budget)
-                try:
+                with self._option("wave_history", 2):
+                    self._ws = None                          # (a larger buffer kept from an earlier decode would defeat the budget)
                     st, ll = self.decode(logE, lengths=lengths, algo="wave", out_dtype=out_dtype)
-                finally:
-                    self.set_option("wave_history", prev)
                 return (st[0], ll[0]) if single else (st, ll)
         states = torch.empty((B, T), dtype=torch.int32, device=self.device)
         loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
@@ -319,53 +409,22 @@ class ViterbiDecoder:
     def _decode_padded(self, entry: str, emission_logits: torch.Tensor, lengths: Optional[torch.Tensor], out_dtype: torch.dtype,
                        loglik_dtype: torch.dtype, workspace: Optional[torch.Tensor], extra: tuple = (), own_buffer: bool = False
                        ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """``decode_checkpointed`` / ``decode_f64_checkpointed`` / the unbudgeted ``decode_f64``: `entry` names the pair
-        ``workspace_bytes_<entry>`` (which raises for what is not served) and ``vit_decode_<entry>``, `extra` the arguments both take
-        behind the shape (the segment length).  The workspace is the caller's tensor, else one allocated for this call, which is
-        followed by a stream synchronise; `own_buffer` (``decode_f64``): else the decoder's slot-0 buffer, shared with ``decode`` and
-        grown like it, and no synchronisation."""
+        """``decode_checkpointed`` / ``decode_f64_checkpointed`` / the unbudgeted ``decode_f64``: the checks of a padded batch, then
+        ``_decode_entry``; `extra`: the arguments size query and decode take behind the shape (the segment length)."""
         logE, single, dt = self._check_emissions(emission_logits)
         B, T, _ = logE.shape
         self._check_lengths(lengths, B)
-        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=loglik_dtype, device=self.device)
-        if B > 0:
-            need = getattr(self, "workspace_bytes_" + entry)(B, T, *extra)
-            if own_buffer and workspace is None:
-                if self._ws is None or self._ws.numel() < need + 256:
-                    self._ws = None
-                    self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-                workspace = self._ws
-            ws_keep, ws_ptr, ws_bytes, mine = self._call_workspace(need, workspace)   # (ws_keep: a buffer allocated here lives until the synchronise below)
-            with torch.cuda.device(self.device):
-                rc = getattr(_lib.load(), "vit_decode_" + entry)(self._plan, logE.data_ptr(), dt, B, T, lengths.data_ptr() if lengths is not None else None,
-                                                                 ws_ptr, ws_bytes, states.data_ptr(), loglik.data_ptr(), *extra,
-                                                                 torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_" + entry)
-            if mine:
-                torch.cuda.current_stream(self.device).synchronize()
-            del ws_keep
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return (states[0], loglik[0]) if single else (states, loglik)
+        return self._decode_entry(entry, B, (B, T), loglik_dtype, out_dtype, workspace, (B, T) + extra,
+                                  (logE.data_ptr(), dt, B, T, _ptr(lengths)), tail=extra, single=single, own_buffer=own_buffer)
 
     # ------------------------------------------------------------------ float64-accumulating decode
     def workspace_bytes_f64(self, B: int, T: int) -> int:
         """Workspace bytes of ``decode_f64``; raises ViterbiHipError for a plan it does not serve."""
-        need = int(_lib.load().vit_workspace_bytes_f64(self._plan, B, T))
-        if need == 0 and B > 0:
-            raise _lib.ViterbiHipError("the float64 decode needs a banded plan whose floor form is proven, without dense rows (unstructured "
-                                       "matrices, the Durrieu step matrices and scan-only plans are not served)")
-        return need
+        return self._need("f64", B > 0, B, T)
 
     def workspace_bytes_f64_checkpointed(self, B: int, T: int, segment_frames: int) -> int:
         """Workspace bytes of ``decode_f64_checkpointed``; raises ViterbiHipError for a plan or a segment length it does not serve."""
-        need = int(_lib.load().vit_workspace_bytes_f64_checkpointed(self._plan, int(B), int(T), int(segment_frames)))
-        if need == 0 and B > 0:
-            raise _lib.ViterbiHipError("the checkpointed float64 decode needs 64 <= segment_frames <= 2**24 and a plan decode_f64 serves: "
-                                       "banded, its floor form proven, without dense rows (unstructured matrices, the Durrieu step "
-                                       "matrices and scan-only plans are not served)")
-        return need
+        return self._need("f64_checkpointed", B > 0, int(B), int(T), int(segment_frames))
 
     @staticmethod
     def _plan_segments(full_need: int, size_of, budget: Optional[int], no_fit=None) -> dict:
@@ -389,9 +448,8 @@ class ViterbiDecoder:
         ``{"mode": "full", "workspace_bytes": n}`` -- ``vit_decode_f64`` fits -- or ``{"mode": "checkpointed", "segment_frames": K,
         "workspace_bytes": n}`` -- ``vit_decode_f64_checkpointed`` with the largest K of 8192, 4096, ..., 64 that fits.  Raises
         ViterbiHipError when nothing fits or the plan is not served.  Both modes decode the same bits."""
-        lib = _lib.load()
         need, budget = self.workspace_bytes_f64(B, T), None if max_workspace_bytes is None else int(max_workspace_bytes)
-        return self._plan_segments(need, lambda K: lib.vit_workspace_bytes_f64_checkpointed(self._plan, B, T, K), budget,
+        return self._plan_segments(need, lambda K: self._need("f64_checkpointed", False, B, T, K), budget,
                                    lambda _: f"no float64 decode of a [{B}, {T}, {self.S}] batch fits a workspace of {budget} bytes "
                                              f"(the whole history needs {need})")
 
@@ -436,11 +494,7 @@ class ViterbiDecoder:
     def workspace_bytes_f64_packed(self, B: int, total_frames: int) -> int:
         """Workspace bytes of ``decode_f64_packed`` for B recordings of ``total_frames`` frames together; raises ViterbiHipError for
         a plan it does not serve (the plans of ``decode_f64``)."""
-        need = int(_lib.load().vit_workspace_bytes_f64_packed(self._plan, int(B), int(total_frames)))
-        if need == 0:
-            raise _lib.ViterbiHipError("the packed float64 decode needs a banded plan whose floor form is proven, without dense rows "
-                                       "(unstructured matrices, the Durrieu step matrices and scan-only plans are not served)")
-        return need
+        return self._need("f64_packed", True, int(B), int(total_frames))
 
     @staticmethod
     def _greedy_groups(offsets, size_of, budget: int) -> list:
@@ -487,38 +541,26 @@ class ViterbiDecoder:
         in one workspace (``plan_workspace_f64_packed``) -- the same bytes out; ``ViterbiHipError`` before anything is enqueued when
         one recording alone does not fit.  ``workspace``: an optional uint8 tensor of at least the need + 256 bytes (the caller
         then keeps it alive until the stream has run the decode: the call does not synchronise)."""
-        lib = _lib.load()
         dt, off = self._check_packed(emission_logits, offsets)
         B, N = off.size - 1, int(off[-1])
         states = torch.empty((N,), dtype=torch.int32, device=self.device)
         loglik = torch.empty((B,), dtype=torch.float64, device=self.device)
+        ws, allocated = None, False                         # (ws: one buffer for every group, alive until the synchronise in _finish)
         if B > 0:
             mode = self.plan_workspace_f64_packed(off, max_workspace_bytes)
-            ws, ws_ptr, ws_bytes, mine = self._call_workspace(mode["bytes"], workspace)
-            stream = torch.cuda.current_stream(self.device)
+            ws, ws_ptr, ws_bytes, allocated = self._call_workspace(mode["bytes"], workspace)
             for b0, b1 in mode["groups"]:                   # (a group: the same entry point on a row slice with rebased offsets)
                 goff = np.ascontiguousarray(off[b0:b1 + 1] - off[b0])
-                with torch.cuda.device(self.device):
-                    rc = lib.vit_decode_f64_packed(self._plan, emission_logits[int(off[b0]):].data_ptr(), dt, b1 - b0, goff.ctypes.data, ws_ptr,
-                                                   ws_bytes, states[int(off[b0]):].data_ptr(), loglik[b0:].data_ptr(), stream.cuda_stream)
-                _lib.check(rc, "vit_decode_f64_packed")
-            if mine:
-                stream.synchronize()
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return states, loglik
+                self._enqueue("f64_packed", emission_logits[int(off[b0]):].data_ptr(), dt, b1 - b0, goff.ctypes.data, ws_ptr, ws_bytes,
+                              states[int(off[b0]):].data_ptr(), loglik[b0:].data_ptr())
+        return self._finish(states, loglik, out_dtype, allocated)
 
     # ------------------------------------------------------------------ the packed float64 decode under a workspace budget
     def workspace_bytes_f64_packed_checkpointed(self, offsets, segment_frames: int) -> int:
         """Workspace bytes of ``decode_f64_packed_checkpointed`` for the recordings ``offsets`` describes (B + 1 host frame offsets);
         raises ViterbiHipError for a plan or a segment length it does not serve."""
         off = self._host_offsets(offsets)
-        need = int(_lib.load().vit_workspace_bytes_f64_packed_checkpointed(self._plan, off.size - 1, off.ctypes.data, int(segment_frames)))
-        if need == 0:
-            raise _lib.ViterbiHipError("the packed checkpointed float64 decode needs 64 <= segment_frames <= 2**24 and a plan decode_f64 "
-                                       "serves: banded, its floor form proven, without dense rows (unstructured matrices, the Durrieu "
-                                       "step matrices and scan-only plans are not served)")
-        return need
+        return self._need("f64_packed_checkpointed", True, off.size - 1, off.ctypes.data, int(segment_frames))
 
     def decode_f64_packed_checkpointed(self, emission_logits: torch.Tensor, offsets, segment_frames: int = 1024,
                                        out_dtype: torch.dtype = torch.int64, workspace: Optional[torch.Tensor] = None
@@ -544,8 +586,7 @@ class ViterbiDecoder:
         if B == 0:
             return {"mode": "full", "workspace_bytes": 0}
         need, budget = self.workspace_bytes_f64_packed(B, N), None if max_workspace_bytes is None else int(max_workspace_bytes)
-        size_of = _lib.load().vit_workspace_bytes_f64_packed_checkpointed
-        return self._plan_segments(need, lambda K: size_of(self._plan, B, off.ctypes.data, K), budget,
+        return self._plan_segments(need, lambda K: self._need("f64_packed_checkpointed", False, B, off.ctypes.data, K), budget,
                                    lambda least: f"no packed float64 decode of {B} recordings ({N} frames) fits a workspace of {budget} "
                                                  f"bytes (the whole history needs {need}, the checkpointed decode at least {least})")
 
@@ -567,16 +608,11 @@ class ViterbiDecoder:
     # ------------------------------------------------------------------ bounded-workspace decode
     def workspace_bytes_checkpointed(self, B: int, T: int, segment_frames: int) -> int:
         """Workspace bytes of ``decode_checkpointed``; raises ViterbiHipError for a plan or a segment length it does not serve."""
-        need = int(_lib.load().vit_workspace_bytes_checkpointed(self._plan, B, T, int(segment_frames)))
-        if need == 0 and B > 0:
-            raise _lib.ViterbiHipError("the checkpointed decode needs 64 <= segment_frames <= 2**24 and a plan with the wave form, the "
-                                       "floor form (banded, no dense rows) or the step form (unstructured matrices and scan-only "
-                                       "banded plans: decode() with the full history)")
-        return need
+        return self._need("checkpointed", B > 0, B, T, int(segment_frames))
 
     def workspace_bytes_checkpointed_or_zero(self, B: int, T: int, segment_frames: int) -> int:
         """The same without the exception: 0 when the checkpointed decode does not serve this plan or segment length."""
-        return int(_lib.load().vit_workspace_bytes_checkpointed(self._plan, int(B), int(T), int(segment_frames)))
+        return self._need("checkpointed", False, int(B), int(T), int(segment_frames))
 
     def decode_checkpointed(self, emission_logits: torch.Tensor, segment_frames: int = 1024, lengths: Optional[torch.Tensor] = None,
                             out_dtype: torch.dtype = torch.int64, workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -623,7 +659,6 @@ class ViterbiDecoder:
         ``ViterbiHipError`` when nothing fits.  Plans with the wave form: ``plan_workspace_packed`` and
         ``decode_packed_checkpointed``; the other plans (the 722-state grids): ``plan_workspace_packed_bounded`` and
         ``decode_packed_bounded``.  ``None``: the full history, whatever it takes."""
-        lib = _lib.load()
         dt, off = self._check_packed(emission_logits, offsets)
         B, N = off.size - 1, int(off[-1])
         if B > 0 and max_workspace_bytes is not None:
@@ -637,33 +672,19 @@ class ViterbiDecoder:
                 if mode["mode"] == "checkpointed":
                     return self.decode_packed_bounded(emission_logits, off, segment_frames=mode["segment_frames"], out_dtype=out_dtype,
                                                       workspace=workspace)
-        states = torch.empty((N,), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
-        if B > 0:
-            need = int(lib.vit_workspace_bytes_packed(self._plan, B, N))
-            if need == 0:
-                raise _lib.ViterbiHipError(_NO_PACKED_DECODE)
-            ws, ws_ptr, ws_bytes, mine = self._call_workspace(need, workspace)
-            with torch.cuda.device(self.device):
-                rc = lib.vit_decode_packed(self._plan, emission_logits.data_ptr(), dt, B, off.ctypes.data, ws_ptr,
-                                           ws_bytes, states.data_ptr(), loglik.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_packed")
-            if mine:
-                torch.cuda.current_stream(self.device).synchronize()
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return states, loglik
+        return self._decode_entry("packed", B, (N,), torch.float32, out_dtype, workspace, (B, N),
+                                  (emission_logits.data_ptr(), dt, B, off.ctypes.data))
 
     # ------------------------------------------------------------------ streaming
     def workspace_bytes_stream(self, B: int, max_frames: int) -> int:
         """Workspace bytes of a ``stream(B, max_frames)`` session (``vit_workspace_bytes_stream``); 0 when the plan has no stream
         form (see ``stream``)."""
-        return int(_lib.load().vit_workspace_bytes_stream(self._plan, int(B), int(max_frames)))
+        return self._need("stream", False, int(B), int(max_frames))
 
     def workspace_bytes_stream_ring(self, B: int, ring_frames: int) -> int:
         """Workspace bytes of a ``stream(B, ring_frames=R)`` session (``vit_workspace_bytes_stream_ring``); 0 when the plan has no
         commit point or R is outside [64, 2**30]."""
-        return int(_lib.load().vit_workspace_bytes_stream_ring(self._plan, int(B), int(ring_frames)))
+        return self._need("stream_ring", False, int(B), int(ring_frames))
 
     def stream(self, B: int, max_frames: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
                ring_frames: Optional[int] = None) -> "DecodeStream":
@@ -684,19 +705,14 @@ class ViterbiDecoder:
     def workspace_bytes_packed(self, B: int, total_frames: int) -> int:
         """Workspace bytes of ``decode_packed`` for B recordings of ``total_frames`` frames together; 0 when the plan has none of
         the forms the packed decode runs (see ``decode_packed``)."""
-        return int(_lib.load().vit_workspace_bytes_packed(self._plan, int(B), int(total_frames)))
+        return self._need("packed", False, int(B), int(total_frames))
 
     # ------------------------------------------------------------------ packed decode under a workspace budget
     def workspace_bytes_packed_checkpointed(self, offsets, segment_frames: int) -> int:
         """Workspace bytes of ``decode_packed_checkpointed`` for the recordings ``offsets`` describes (B + 1 host frame offsets); raises
         ViterbiHipError for a plan or a segment length it does not serve."""
         off = self._host_offsets(offsets)
-        need = int(_lib.load().vit_workspace_bytes_packed_checkpointed(self._plan, off.size - 1, off.ctypes.data, int(segment_frames)))
-        if need == 0:
-            raise _lib.ViterbiHipError("the packed checkpointed decode needs 64 <= segment_frames <= 2**24 and a plan with the wave form "
-                                       "(S = 321 / 361; the 722-state grids: pad and use decode_checkpointed(lengths=), or split the "
-                                       "recordings into groups whose workspace_bytes_packed fits)")
-        return need
+        return self._need("packed_checkpointed", True, off.size - 1, off.ctypes.data, int(segment_frames))
 
     def decode_packed_checkpointed(self, emission_logits: torch.Tensor, offsets, segment_frames: int = 1024, out_dtype: torch.dtype = torch.int64,
                                    workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -711,24 +727,12 @@ class ViterbiDecoder:
     def _decode_packed_segments(self, entry: str, emission_logits: torch.Tensor, offsets, segment_frames: int, out_dtype: torch.dtype,
                                 workspace: Optional[torch.Tensor], loglik_dtype: torch.dtype = torch.float32
                                 ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """``decode_packed_checkpointed`` / ``decode_packed_bounded`` / ``decode_f64_packed_checkpointed``: `entry` names the pair
-        ``workspace_bytes_<entry>`` (which raises for a plan or a segment length that is not served) and ``vit_decode_<entry>``."""
+        """``decode_packed_checkpointed`` / ``decode_packed_bounded`` / ``decode_f64_packed_checkpointed``: the checks of a packed
+        batch, then ``_decode_entry``."""
         dt, off = self._check_packed(emission_logits, offsets)
-        B, N = off.size - 1, int(off[-1])
-        states = torch.empty((N,), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=loglik_dtype, device=self.device)
-        if B > 0:
-            ws, ws_ptr, ws_bytes, mine = self._call_workspace(getattr(self, "workspace_bytes_" + entry)(off, segment_frames), workspace)
-            with torch.cuda.device(self.device):
-                rc = getattr(_lib.load(), "vit_decode_" + entry)(self._plan, emission_logits.data_ptr(), dt, B, off.ctypes.data, ws_ptr, ws_bytes,
-                                                                 states.data_ptr(), loglik.data_ptr(), int(segment_frames),
-                                                                 torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_" + entry)
-            if mine:
-                torch.cuda.current_stream(self.device).synchronize()
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return states, loglik
+        B, K = off.size - 1, int(segment_frames)
+        return self._decode_entry(entry, B, (int(off[-1]),), loglik_dtype, out_dtype, workspace, (B, off.ctypes.data, K),
+                                  (emission_logits.data_ptr(), dt, B, off.ctypes.data), tail=(K,))
 
     def plan_workspace_packed(self, offsets, max_workspace_bytes: Optional[int] = None) -> dict:
         """How the recordings ``offsets`` describes are decoded under a workspace budget (bytes; None = whatever it takes):
@@ -738,37 +742,30 @@ class ViterbiDecoder:
           largest K of 8192, 4096, ..., 64 that fits (fewest launches; the rule of ``plan_workspace``).
 
         Raises ViterbiHipError naming the need when nothing fits or the plan is not served.  Both modes decode the same bits."""
-        return self._plan_packed(offsets, max_workspace_bytes, _lib.load().vit_workspace_bytes_packed_checkpointed, "checkpointed",
+        return self._plan_packed(offsets, max_workspace_bytes, "packed_checkpointed", "checkpointed",
                                  "no packed checkpointed decode (wave-form plans only: split the recordings into groups whose "
                                  "workspace_bytes_packed fits)")
 
-    def _plan_packed(self, offsets, max_workspace_bytes: Optional[int], size_of, kind: str, unserved: str) -> dict:
-        """``plan_workspace_packed`` / ``plan_workspace_packed_bounded``: `size_of` is the library's size query of the budgeted decode,
+    def _plan_packed(self, offsets, max_workspace_bytes: Optional[int], entry: str, kind: str, unserved: str) -> dict:
+        """``plan_workspace_packed`` / ``plan_workspace_packed_bounded``: `entry` is the budgeted decode whose size query is asked,
         `kind` and `unserved` what the errors call it."""
         off = self._host_offsets(offsets)
         B, N = off.size - 1, int(off[-1])
-        need = self.workspace_bytes_packed(B, N)
-        if need == 0 and B > 0:
-            raise _lib.ViterbiHipError(_NO_PACKED_DECODE)
+        need = self._need("packed", B > 0, B, N)
         def no_fit(least):
             if least == 0:
                 return (f"the packed decode of {B} recordings ({N} frames) needs a workspace of {need} bytes, the budget is "
                         f"{max_workspace_bytes}, and this plan has {unserved}")
             return (f"no packed decode of {B} recordings ({N} frames) fits a workspace of {max_workspace_bytes} bytes "
                     f"(the full history needs {need}, the {kind} decode at least {least})")
-        return self._plan_segments(need, lambda K: size_of(self._plan, B, off.ctypes.data, K), max_workspace_bytes, no_fit)
+        return self._plan_segments(need, lambda K: self._need(entry, False, B, off.ctypes.data, K), max_workspace_bytes, no_fit)
 
     # ------------------------------------------------------------------ the same for every plan with a packed decode
     def workspace_bytes_packed_bounded(self, offsets, segment_frames: int) -> int:
         """Workspace bytes of ``decode_packed_bounded`` for the recordings ``offsets`` describes (B + 1 host frame offsets); raises
         ViterbiHipError for a plan or a segment length it does not serve."""
         off = self._host_offsets(offsets)
-        need = int(_lib.load().vit_workspace_bytes_packed_bounded(self._plan, off.size - 1, off.ctypes.data, int(segment_frames)))
-        if need == 0:
-            raise _lib.ViterbiHipError("the bounded packed decode needs 64 <= segment_frames <= 2**24 and a plan with the wave form, the floor "
-                                       "form with the sparse back-trace, or the step form (unstructured matrices and scan-only banded "
-                                       "plans: pad and use decode(lengths=))")
-        return need
+        return self._need("packed_bounded", True, off.size - 1, off.ctypes.data, int(segment_frames))
 
     def decode_packed_bounded(self, emission_logits: torch.Tensor, offsets, segment_frames: int = 1024, out_dtype: torch.dtype = torch.int64,
                               workspace: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -787,7 +784,7 @@ class ViterbiDecoder:
         fits the budget, else ``{"mode": "checkpointed", "segment_frames": K, "workspace_bytes": ...}`` with the largest K of 8192,
         4096, ..., 64 whose ``workspace_bytes_packed_bounded`` fits.  Raises ViterbiHipError naming the least need when nothing fits
         or the plan is not served."""
-        return self._plan_packed(offsets, max_workspace_bytes, _lib.load().vit_workspace_bytes_packed_bounded, "bounded",
+        return self._plan_packed(offsets, max_workspace_bytes, "packed_bounded", "bounded",
                                  "no bounded packed decode (pad and use decode_checkpointed(lengths=))")
 
     # ------------------------------------------------------------------ fused logits -> path decode
@@ -816,18 +813,12 @@ class ViterbiDecoder:
     def workspace_bytes_logits(self, obs: dict, B: int, T: int) -> int:
         """Workspace bytes of ``decode_logits`` (a full delta history in the wave layout, nothing for emissions); 0 when the
         fused kernel does not serve this plan or builder geometry (see ``decode_logits``)."""
-        op = self._obs_struct(obs)
-        return int(_lib.load().vit_workspace_bytes_logits(self._plan, ctypes.byref(op), int(B), int(T)))
-
-    _LOGITS_UNSERVED = ("the fused logits decode needs a plan with the wave form whose extra column is the last state "
-                        "(S = 321 / 361), n_bins = S - 1, and a builder geometry of the reference (shaun / scaled "
-                        "softmax with peak width 5, softmax with 15): build the emissions and use decode()")
+        return self._need("logits", False, ctypes.byref(self._obs_struct(obs)), int(B), int(T))
 
     def workspace_bytes_logits_checkpointed(self, obs: dict, B: int, T: int, segment_frames: int) -> int:
         """Workspace bytes of ``decode_logits_checkpointed`` (what ``workspace_bytes_checkpointed`` answers for the same plan); 0 when
         the fused kernel does not serve this plan or builder geometry, or ``segment_frames`` is outside 64 .. 2**24."""
-        op = self._obs_struct(obs)
-        return int(_lib.load().vit_workspace_bytes_logits_checkpointed(self._plan, ctypes.byref(op), int(B), int(T), int(segment_frames)))
+        return self._need("logits_checkpointed", False, ctypes.byref(self._obs_struct(obs)), int(B), int(T), int(segment_frames))
 
     def plan_workspace_logits(self, obs: dict, B: int, T: int, max_workspace_bytes: Optional[int] = None) -> dict:
         """How ``decode_logits`` decodes ``[B, T, cols]`` logits under a workspace budget (bytes; None = whatever it takes):
@@ -835,9 +826,7 @@ class ViterbiDecoder:
         "checkpointed", "segment_frames": K, "workspace_bytes": n}`` -- ``vit_decode_logits_checkpointed`` with the largest K of 8192,
         4096, ..., 64 that fits.  Raises ViterbiHipError when nothing fits (the text names the least need) or the plan or builder is
         not served.  Both modes decode the same bits."""
-        need = self.workspace_bytes_logits(obs, B, T)
-        if need == 0 and B > 0:
-            raise _lib.ViterbiHipError(self._LOGITS_UNSERVED)
+        need = self._need("logits", B > 0, ctypes.byref(self._obs_struct(obs)), B, T)
         budget = None if max_workspace_bytes is None else int(max_workspace_bytes)
         return self._plan_segments(need, lambda K: self.workspace_bytes_logits_checkpointed(obs, B, T, K), budget,
                                    lambda least: f"no fused logits decode of a [{B}, {T}] batch fits a workspace of {budget} bytes: the least "
@@ -864,29 +853,11 @@ class ViterbiDecoder:
         the forward work.  There is no ``emissions_out``: the call exists to save memory.  Plans and builders: those of
         ``decode_logits``; anything else raises ``ViterbiHipError`` before anything is enqueued.  ``workspace``: as for
         ``decode_checkpointed``."""
-        lib = _lib.load()
         lg, single = self._check_logits(logits, obs, lengths)
         B, T, _ = lg.shape
-        K = int(segment_frames)
-        op = self._obs_struct(obs)
-        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
-        if B > 0:
-            need = int(lib.vit_workspace_bytes_logits_checkpointed(self._plan, ctypes.byref(op), B, T, K))
-            if need == 0:
-                raise _lib.ViterbiHipError("the checkpointed fused logits decode needs 64 <= segment_frames <= 2**24; " + self._LOGITS_UNSERVED)
-            ws, ws_ptr, ws_bytes, mine = self._call_workspace(need, workspace)
-            with torch.cuda.device(self.device):
-                rc = lib.vit_decode_logits_checkpointed(self._plan, lg.data_ptr(), ctypes.byref(op), B, T,
-                                                        lengths.data_ptr() if lengths is not None else None, ws_ptr, ws_bytes,
-                                                        states.data_ptr(), loglik.data_ptr(), K, torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_logits_checkpointed")
-            if mine:
-                torch.cuda.current_stream(self.device).synchronize()
-            del ws
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return (states[0], loglik[0]) if single else (states, loglik)
+        K, op = int(segment_frames), ctypes.byref(self._obs_struct(obs))
+        return self._decode_entry("logits_checkpointed", B, (B, T), torch.float32, out_dtype, workspace, (op, B, T, K),
+                                  (lg.data_ptr(), op, B, T, _ptr(lengths)), tail=(K,), single=single)
 
     def decode_logits(self, logits: torch.Tensor, obs: dict, lengths: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.int64,
                       emissions_out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
@@ -902,7 +873,6 @@ class ViterbiDecoder:
         ``max_workspace_bytes``: a budget for the delta history (``plan_workspace_logits``): where the whole history does not fit,
         the decode runs as ``decode_logits_checkpointed`` with the largest segment length that does -- the same bits; that form
         writes no emissions, so ``emissions_out`` with such a budget is a ``ValueError``."""
-        lib = _lib.load()
         lg, single = self._check_logits(logits, obs, lengths)
         B, T, _ = lg.shape
         if B > 0 and max_workspace_bytes is not None:
@@ -918,24 +888,9 @@ class ViterbiDecoder:
             if (eo.dtype != torch.float32 or eo.device != self.device or not eo.is_contiguous() or
                     tuple(eo.shape) != ((T, self.S) if single else (B, T, self.S))):
                 raise ValueError(f"emissions_out must be a contiguous float32 tensor shaped like the logits with {self.S} columns")
-        op = self._obs_struct(obs)
-        states = torch.empty((B, T), dtype=torch.int32, device=self.device)
-        loglik = torch.empty((B,), dtype=torch.float32, device=self.device)
-        if B > 0:
-            need = int(lib.vit_workspace_bytes_logits(self._plan, ctypes.byref(op), B, T))
-            if need == 0:
-                raise _lib.ViterbiHipError(self._LOGITS_UNSERVED)
-            ws, ws_ptr, ws_bytes, mine = self._call_workspace(need, workspace)
-            with torch.cuda.device(self.device):
-                rc = lib.vit_decode_logits(self._plan, lg.data_ptr(), ctypes.byref(op), B, T, lengths.data_ptr() if lengths is not None else None,
-                                           ws_ptr, ws_bytes, emissions_out.data_ptr() if emissions_out is not None else None,
-                                           states.data_ptr(), loglik.data_ptr(), torch.cuda.current_stream(self.device).cuda_stream)
-            _lib.check(rc, "vit_decode_logits")
-            if mine:
-                torch.cuda.current_stream(self.device).synchronize()
-        if out_dtype != torch.int32:
-            states = states.to(out_dtype)
-        return (states[0], loglik[0]) if single else (states, loglik)
+        op = ctypes.byref(self._obs_struct(obs))
+        return self._decode_entry("logits", B, (B, T), torch.float32, out_dtype, workspace, (op, B, T),
+                                  (lg.data_ptr(), op, B, T, _ptr(lengths)), mid=(_ptr(emissions_out),), single=single)
 
     def voicing(self, states: torch.Tensor, n_bins: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """voiced = state < n_bins, bins = min(state, n_bins-1) (tonet/for_paper.py:1828-1829)."""
@@ -970,265 +925,6 @@ class ViterbiDecoder:
 
 
 _DECODERS: dict = {}
-
-
-class DecodeStream:
-    """One streaming session of a ``ViterbiDecoder`` (``vit_stream_*``): see ``ViterbiDecoder.stream``.  Calls are enqueued on the
-    current stream of the decoder's device; the caller orders the calls of one session as for any other tensor work (one stream, or
-    events).  A chunk tensor may be rewritten as soon as its ``append`` has run in stream order: nothing reads emission rows again."""
-
-    def __init__(self, decoder: ViterbiDecoder, B: int, max_frames: Optional[int] = None, workspace: Optional[torch.Tensor] = None,
-                 ring_frames: Optional[int] = None):
-        lib = _lib.load()
-        self._dec = decoder                    # (keeps the plan alive)
-        self._session = ctypes.c_void_p()
-        self.ring_frames = None if ring_frames is None else int(ring_frames)
-        if self.ring_frames is not None:
-            self.B, self.max_frames = int(B), None
-            if self.B < 1:
-                raise ValueError("a stream needs B >= 1 recordings")
-            need = decoder.workspace_bytes_stream_ring(self.B, self.ring_frames)
-            if need == 0:
-                raise _lib.ViterbiHipError("no ring session for this plan or size: it needs a banded session plan (one with a commit "
-                                           "point) and 64 <= ring_frames <= 2**30")
-            self._ws, ws_ptr, ws_bytes, _ = decoder._call_workspace(need, workspace)
-            _lib.check(lib.vit_stream_open_ring(decoder._plan, self.B, self.ring_frames, ws_ptr, ws_bytes, ctypes.byref(self._session)),
-                       "vit_stream_open_ring")
-            return
-        if max_frames is None:
-            raise ValueError("a stream needs max_frames (or ring_frames)")
-        self.B, self.max_frames = int(B), int(max_frames)
-        if self.B < 1 or self.max_frames < 1:
-            raise ValueError("a stream needs B >= 1 recordings and max_frames >= 1")
-        need = decoder.workspace_bytes_stream(self.B, self.max_frames)
-        if need == 0:
-            raise _lib.ViterbiHipError("no streaming decode for this plan: it needs a banded plan whose floor form is proven "
-                                       "(no dense rows) or a step-structured plan of the Durrieu geometry")
-        self._ws, ws_ptr, ws_bytes, _ = decoder._call_workspace(need, workspace)
-        _lib.check(lib.vit_stream_open(decoder._plan, self.B, self.max_frames, ws_ptr, ws_bytes, ctypes.byref(self._session)), "vit_stream_open")
-
-    def _handle(self) -> ctypes.c_void_p:
-        if not self._session.value:
-            raise _lib.ViterbiHipError("the stream is closed")
-        return self._session
-
-    def append(self, emissions: torch.Tensor, counts=None) -> None:
-        """The next frames: ``emissions`` [B, n, S] (or [n, S] for a one-recording stream), float32 or float16 (the type of the
-        first append holds for the session); ``counts``: a host sequence of B ints, recording b takes rows ``[b, :counts[b]]``
-        (None: n each).  Raises ``ViterbiHipError`` -- with nothing enqueued and no length changed -- for a count out of range or
-        frames beyond ``max_frames``."""
-        dec = self._dec
-        logE, _, dt = dec._check_emissions(emissions)
-        if logE.shape[0] != self.B:
-            raise ValueError(f"emissions must be [{self.B}, n, {dec.S}]")
-        cnt = None
-        if counts is not None:
-            cnt = np.ascontiguousarray(np.asarray(counts, dtype=np.int64))
-            if cnt.shape != (self.B,):
-                raise ValueError("counts must hold one entry per recording")
-        with torch.cuda.device(dec.device):
-            rc = _lib.load().vit_stream_append(self._handle(), logE.data_ptr(), dt, int(logE.shape[1]), cnt.ctypes.data if cnt is not None else None,
-                                               torch.cuda.current_stream(dec.device).cuda_stream)
-        if rc == _lib.VIT_EWORKSPACE and self.ring_frames is not None:
-            raise _lib.ViterbiHipError(f"vit_stream_append: the frames would overwrite ring rows behind the acknowledged frontier "
-                                       f"(ring_frames = {self.ring_frames}): commit() first (or ack() frontiers read from commit_rel_into), "
-                                       "or open the stream with a larger ring")
-        _lib.check(rc, "vit_stream_append")
-
-    @property
-    def lengths(self) -> np.ndarray:
-        """Frames appended per recording so far (host int64 [B])."""
-        out = np.zeros(self.B, np.int64)
-        _lib.check(_lib.load().vit_stream_lengths(self._handle(), out.ctypes.data), "vit_stream_lengths")
-        return out
-
-    def decode_into(self, states: torch.Tensor, loglik: Optional[torch.Tensor] = None) -> None:
-        """Enqueue the back-trace of the recordings as they stand: ``states`` int32 [B, stride], stride >= the longest length (-1
-        behind each length), ``loglik`` float32 [B] or None."""
-        dec = self._dec
-        if self.ring_frames is not None:
-            raise _lib.ViterbiHipError("decode() needs every history row: a ring session returns its path by commit() and tail()")
-        self._check_states(states)
-        if loglik is not None and (loglik.dtype != torch.float32 or tuple(loglik.shape) != (self.B,) or not loglik.is_contiguous() or loglik.device != dec.device):
-            raise ValueError("loglik must be a float32 [B] tensor on the decoder's device")
-        with torch.cuda.device(dec.device):
-            rc = _lib.load().vit_stream_backtrace(self._handle(), states.data_ptr(), int(states.shape[1]), loglik.data_ptr() if loglik is not None else None,
-                                                  torch.cuda.current_stream(dec.device).cuda_stream)
-        _lib.check(rc, "vit_stream_backtrace")
-
-    def decode(self, out_dtype: torch.dtype = torch.int64) -> Tuple[torch.Tensor, torch.Tensor]:
-        """-> ``(states [B, max length so far], loglik [B])`` of the frames appended so far; the session stays open, and a later
-        ``decode`` after more appends supersedes this one."""
-        states = torch.empty((self.B, int(self.lengths.max())), dtype=torch.int32, device=self._dec.device)
-        loglik = torch.empty((self.B,), dtype=torch.float32, device=self._dec.device)
-        self.decode_into(states, loglik)
-        return (states if out_dtype == torch.int32 else states.to(out_dtype)), loglik
-
-    # the default lookback of ``commit`` / ``commit_into``: no cap (2^30 frames, the most vit_stream_commit takes)
-    MAX_LOOKBACK = 1 << 30
-
-    def _commit_begin(self) -> None:
-        if getattr(self, "_commit_ws", None) is not None:
-            return
-        lib = _lib.load()
-        need = int(lib.vit_workspace_bytes_stream_commit(self._dec._plan, self.B))
-        if need == 0:
-            raise _lib.ViterbiHipError("no commit point for this plan: it needs a banded session plan (step-structured plans decide "
-                                       "back-pointers by whole rows)")
-        ws, ptr, nbytes, _ = self._dec._call_workspace(need, None)
-        _lib.check(lib.vit_stream_commit_begin(self._handle(), ptr, nbytes), "vit_stream_commit_begin")
-        self._commit_ws = ws
-        self._committed = np.zeros(self.B, np.int64)     # the frontiers ``commit`` last read back (host)
-
-    def commit_into(self, states: torch.Tensor, committed: torch.Tensor, max_lookback: Optional[int] = None) -> None:
-        """Enqueue ``vit_stream_commit``: for every recording the states of the frames that became final since the last commit are
-        written to ``states[b, f_b:f'_b]`` (int32 [B, stride], stride >= the longest length; nothing else of it is touched) and the
-        new frontier f'_b to ``committed[b]`` (int64 [B]).  Asynchronous: no host synchronisation.  ``max_lookback``: the most
-        frames behind the newest one in which the merge of the survivor paths is looked for (None: no cap).  The commit state is
-        allocated on the first call."""
-        dec = self._dec
-        if self.ring_frames is not None:
-            raise _lib.ViterbiHipError("commit_into writes at absolute frames: a ring session commits with commit_rel_into (or commit())")
-        self._check_states(states)
-        self._check_i64(committed, "committed")
-        self._handle()
-        self._commit_begin()
-        L = self.MAX_LOOKBACK if max_lookback is None else int(max_lookback)
-        with torch.cuda.device(dec.device):
-            rc = _lib.load().vit_stream_commit(self._handle(), states.data_ptr(), int(states.shape[1]), committed.data_ptr(), L,
-                                               torch.cuda.current_stream(dec.device).cuda_stream)
-        _lib.check(rc, "vit_stream_commit")
-
-    def _check_states(self, states: torch.Tensor) -> None:
-        if states.dtype != torch.int32 or states.dim() != 2 or states.shape[0] != self.B or not states.is_contiguous() or states.device != self._dec.device:
-            raise ValueError("states must be a contiguous int32 [B, stride] tensor on the decoder's device")
-
-    def _check_i64(self, x: torch.Tensor, name: str) -> None:
-        if x.dtype != torch.int64 or tuple(x.shape) != (self.B,) or not x.is_contiguous() or x.device != self._dec.device:
-            raise ValueError(f"{name} must be an int64 [B] tensor on the decoder's device")
-
-    def commit_rel_into(self, states: torch.Tensor, first: torch.Tensor, committed: torch.Tensor, max_lookback: Optional[int] = None) -> None:
-        """Enqueue ``vit_stream_commit_rel``: ``commit_into`` with a window-relative output -- the states of the frames
-        ``[f_b, f'_b)`` that became final go to ``states[b, :f'_b - f_b]`` (int32 [B, stride]; on a ring session stride >=
-        min(longest length, ring_frames) suffices), ``first[b] = f_b`` and ``committed[b] = f'_b`` (int64 [B] each); nothing else is
-        written.  Asynchronous.  On a ring session, report the frontiers you read back with ``ack`` so that appends may go on."""
-        dec = self._dec
-        self._check_states(states)
-        self._check_i64(first, "first")
-        self._check_i64(committed, "committed")
-        self._handle()
-        self._commit_begin()
-        L = self.MAX_LOOKBACK if max_lookback is None else int(max_lookback)
-        with torch.cuda.device(dec.device):
-            rc = _lib.load().vit_stream_commit_rel(self._handle(), states.data_ptr(), int(states.shape[1]), first.data_ptr(), committed.data_ptr(), L,
-                                                   torch.cuda.current_stream(dec.device).cuda_stream)
-        _lib.check(rc, "vit_stream_commit_rel")
-
-    def ack(self, frontiers) -> None:
-        """Ring sessions: tell the session the frontiers (host, B ints) READ BACK from a ``committed`` tensor of an earlier commit;
-        rows below them may then be overwritten by appends (``vit_stream_commit_ack``: host only).  Values that go down or lie
-        beyond the lengths raise.  Acknowledging values that were not read gives wrong states."""
-        fr = np.ascontiguousarray(np.asarray(frontiers, dtype=np.int64))
-        if fr.shape != (self.B,):
-            raise ValueError("frontiers must hold one entry per recording")
-        _lib.check(_lib.load().vit_stream_commit_ack(self._handle(), fr.ctypes.data), "vit_stream_commit_ack")
-
-    def tail_into(self, states: torch.Tensor, first: torch.Tensor, loglik: Optional[torch.Tensor] = None) -> None:
-        """Enqueue ``vit_stream_tail``: the best path of the frames so far, restricted to the frames behind the frontier:
-        ``states[b, :n_b - f_b]`` (int32 [B, stride], stride >= the longest possible tail), ``first[b] = f_b`` (int64 [B]),
-        ``loglik`` float32 [B] or None.  The frontier does not move.  Asynchronous; ring and linear sessions alike."""
-        dec = self._dec
-        self._check_states(states)
-        self._check_i64(first, "first")
-        if loglik is not None and (loglik.dtype != torch.float32 or tuple(loglik.shape) != (self.B,) or not loglik.is_contiguous() or loglik.device != dec.device):
-            raise ValueError("loglik must be a float32 [B] tensor on the decoder's device")
-        self._handle()
-        self._commit_begin()
-        with torch.cuda.device(dec.device):
-            rc = _lib.load().vit_stream_tail(self._handle(), states.data_ptr(), int(states.shape[1]), first.data_ptr(),
-                                             loglik.data_ptr() if loglik is not None else None, torch.cuda.current_stream(dec.device).cuda_stream)
-        _lib.check(rc, "vit_stream_tail")
-
-    def _window(self) -> int:
-        n = max(int(self.lengths.max()), 1)
-        return n if self.ring_frames is None else min(n, self.ring_frames)
-
-    def tail(self, out_dtype: torch.dtype = torch.int64):
-        """-> ``(first (host int64 [B]), [the states of frames [f_b, n_b) of recording b], loglik [B])``: with the commits so far,
-        the whole best path of the frames appended.  SYNCHRONISES to read the slice bounds."""
-        dev = self._dec.device
-        states = torch.empty((self.B, self._window()), dtype=torch.int32, device=dev)
-        first = torch.zeros((self.B,), dtype=torch.int64, device=dev)
-        loglik = torch.empty((self.B,), dtype=torch.float32, device=dev)
-        n = self.lengths
-        self.tail_into(states, first, loglik)
-        f = first.cpu().numpy().astype(np.int64)
-        out = [states[b, :int(n[b] - f[b])] for b in range(self.B)]
-        if out_dtype != torch.int32:
-            out = [x.to(out_dtype) for x in out]
-        return f, out, loglik
-
-    def _commit_ring(self, max_lookback: Optional[int], out_dtype: torch.dtype):
-        dev = self._dec.device
-        if getattr(self, "_commit_dev", None) is None:
-            self._commit_dev = torch.zeros((self.B,), dtype=torch.int64, device=dev)
-            self._first_dev = torch.zeros((self.B,), dtype=torch.int64, device=dev)
-        states = torch.empty((self.B, self._window()), dtype=torch.int32, device=dev)
-        self.commit_rel_into(states, self._first_dev, self._commit_dev, max_lookback)
-        first = self._first_dev.cpu().numpy().astype(np.int64)
-        new = self._commit_dev.cpu().numpy().astype(np.int64)
-        self.ack(new)
-        self._committed = new
-        fresh = [states[b, :int(new[b] - first[b])] for b in range(self.B)]
-        if out_dtype != torch.int32:
-            fresh = [x.to(out_dtype) for x in fresh]
-        return first, new.copy(), fresh
-
-    def commit(self, max_lookback: Optional[int] = None, out_dtype: torch.dtype = torch.int64):
-        """-> ``(committed lengths (host int64 [B]), [the newly final states of recording b: frames [f_b, f'_b)])``.  The slice
-        bounds live on the device, so this call SYNCHRONISES with the stream to read them; ``commit_into`` does not.  The session
-        keeps an int32 [B, max_frames] tensor of everything committed so far (``committed_states``).  Use either ``commit`` or
-        ``commit_into`` on one session between resets: both advance the same device frontiers, and ``commit`` slices by the ones it read.
-
-        On a RING session the result is ``(first, committed, [states of frames [first_b, committed_b)])`` (``commit_rel_into``), the
-        frontiers read are acknowledged so that appends may reuse the rows below them, and no tensor of everything committed is kept."""
-        if self.ring_frames is not None:
-            return self._commit_ring(max_lookback, out_dtype)
-        dev = self._dec.device
-        if getattr(self, "_commit_states", None) is None:
-            self._commit_states = torch.empty((self.B, self.max_frames), dtype=torch.int32, device=dev)
-            self._commit_dev = torch.zeros((self.B,), dtype=torch.int64, device=dev)
-        self.commit_into(self._commit_states, self._commit_dev, max_lookback)
-        new = self._commit_dev.cpu().numpy().astype(np.int64)
-        old = self._committed
-        self._committed = new
-        fresh = [self._commit_states[b, int(old[b]):int(new[b])] for b in range(self.B)]
-        if out_dtype != torch.int32:
-            fresh = [x.to(out_dtype) for x in fresh]
-        return new.copy(), fresh
-
-    @property
-    def committed_states(self) -> Optional[torch.Tensor]:
-        """int32 [B, max_frames]: row b holds the final states of frames [0, committed length) as of the last ``commit`` (None before)."""
-        return getattr(self, "_commit_states", None)
-
-    def reset(self) -> None:
-        """Every recording back to length 0 and every commit frontier to 0; the workspace is reused."""
-        _lib.check(_lib.load().vit_stream_reset(self._handle()), "vit_stream_reset")
-        if getattr(self, "_commit_ws", None) is not None:
-            self._committed = np.zeros(self.B, np.int64)
-
-    def close(self) -> None:
-        """Free the session (also on garbage collection).  The workspace tensor is released with the object."""
-        try:
-            if getattr(self, "_session", None) is not None and self._session.value:
-                _lib.load().vit_stream_close(self._session)
-                self._session = ctypes.c_void_p()
-        except Exception:
-            pass
-
-    def __del__(self):
-        self.close()
 
 
 def get_decoder(transition_matrix, init_probs, device=None) -> ViterbiDecoder:
