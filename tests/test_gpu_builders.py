@@ -9,18 +9,15 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import observation_oracle as oo
 from tests.common import RANGE_SPANS, RANGE_TOPS, logits_case, range_edge_logits
+# (the oracle side of the comparison and its bar are shared with tests/test_gpu_far_offsets_rows.py)
+from tests.far_offsets import FLOOR, TINY, VTH2, assert_builder_matches as _assert_matches, builder_oracle as _oracle, builder_prior as _prior
 from viterbi_spl_amd import ViterbiDecoder, _lib, synth
 from viterbi_spl_amd import emissions as em
 from viterbi_spl_amd import reference_api as ra
 
 pytestmark = pytest.mark.gpu
 
-TINY = np.float32(np.finfo(np.float32).tiny)
-FLOOR = np.log(TINY)                                   # log(0 + tiny): a structural zero
-ULP = float(np.spacing(-FLOOR))                        # float32 spacing at |log(tiny)|: 7.6e-6
-VTH2 = 0.5                                             # mode 2's voicing-threshold probability: unvoiced logit 0
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
@@ -46,11 +43,6 @@ def _fstep(U, spw, n_cus):
     return (32 if _register_form(U, spw) else 24) * n_cus
 
 
-def _prior(U):
-    p = np.random.default_rng(U).random(U + 1).astype(np.float32) + np.float32(1e-3)
-    return p / p.sum()
-
-
 def _gpu(mode, x, spw, prior=None, out=None):
     """The GPU builder of `mode` on device logits -> log-emissions [n, U+1]."""
     if mode == 0:
@@ -59,44 +51,6 @@ def _gpu(mode, x, spw, prior=None, out=None):
         return em.softmax_log_emissions(x, single_side_peak_width=spw, out=out)
     assert out is None
     return em.softmax_scaled_log_emissions(x, VTH2, prior, single_side_peak_width=spw)
-
-
-def _oracle(mode, x, spw, prior=None):
-    """The oracle restatement of the reference's builder of `mode` -> probabilities float32 [n, U+1], unvoiced last."""
-    x = np.ascontiguousarray(x)
-    if mode == 0:
-        return np.ascontiguousarray(oo.shaun_observation_probs(x, 0.32, spw=spw).T)
-    if mode == 1:
-        return oo.softmax_observation_probs(x, spw=spw)
-    return oo.softmax_scaled_observation_probs(x, np.float32(VTH2), prior if prior is not None else np.ones(x.shape[1] + 1, np.float32),
-                                               scaled=prior is not None, spw=spw)
-
-
-def _first(mask, k=4):
-    return [tuple(int(i) for i in ix) for ix in np.argwhere(mask)[:k]]
-
-
-def _assert_matches(got, want_p, mode, what):
-    """got: GPU log-emissions; want_p: the oracle's probabilities.  The structural log(tiny) set must be the same and the values within
-    the bar.  Reference values a few ulp above log(tiny) (a subnormal p of up to ~190 times the smallest one) round onto log(tiny)
-    or not by the last bit of the log - NumPy's or the GPU's - not by the builder: they leave the structural comparison and are held,
-    with every value within 1.0 of log(tiny), to 3e-5 (4 ulp) in the log domain.  A flushed subnormal misses that by 4.7e-4 or more
-    at spans up to 95 nats and is a structural difference below that."""
-    want = np.log(want_p + TINY)
-    exact = np.log(want_p.astype(np.float64) + np.float64(TINY))
-    edge = (want_p > 0) & (exact < np.float64(FLOOR) + 3 * ULP)
-    bad = ((got == FLOOR) != (want == FLOOR)) & ~edge
-    assert not bad.any(), f"{what}: peak set / structural zeros differ at {_first(bad)}"
-    live = (want != FLOOR) & ~edge
-    if mode == 2:
-        ok = np.isclose(got, want, rtol=0, atol=2e-5)                # log-likelihoods up to +8: compared in the log domain
-    else:
-        ok = np.isclose(np.exp(got), np.exp(want), rtol=1e-5, atol=1e-30)
-    bad = live & ~ok
-    assert not bad.any(), f"{what}: values differ at {_first(bad)}"
-    near = (want_p > 0) & (exact < np.float64(FLOOR) + 1.0)
-    bad = near & ~np.isclose(got, want, rtol=0, atol=3e-5)
-    assert not bad.any(), f"{what}: the subnormal band differs at {_first(bad)}: got {got[bad][:4]}, want {want[bad][:4]}"
 
 
 def _special_frames(U, spw, mode, rng):
