@@ -253,3 +253,83 @@ def wave_geometry(seed):
     A = _banded_matrix(S, half, rng, extras, (), floor=-50.0, quant=2)
     pi = -(rng.integers(0, 8, S) / 2).astype(np.float32)
     return S, half, extras, A, pi, rng
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Structure cases: the matrices of tests/test_gpu_parity.py::test_every_kernel_path_is_exercised,
+# ::test_random_banded_structures_on_gpu and ::test_generic_backtrace_with_windows_wider_than_a_wave, shared with the
+# off-grid twins of tests/inexact_cases.py
+# ---------------------------------------------------------------------------------------------------------------------
+def kernel_path_matrices(rng):
+    """One matrix per forward / back-trace combination, named "<forward>+<back-trace>", drawn from `rng` in this order."""
+    from tests.test_plan_host import _banded_matrix
+
+    def varying_band(S):                       # lower half-width depends on the row: window start not affine in j
+        A = np.full((S, S), -60.0, np.float32)
+        for j in range(S):
+            lo, hi = max(0, j - 1 - j % 5), min(S, j + 4)
+            A[j, lo:hi] = -(rng.integers(0, 40, hi - lo) / 2)
+        return A
+
+    return {
+        "floor+lean_affine": _banded_matrix(150, 5, rng, extras=(149,), floor=-50.0, quant=2),
+        "floor+lean_table": varying_band(170),
+        "scan+lean": _banded_matrix(150, 5, rng, extras=(40,), floor=-3.0, quant=2),        # window entries below the floor
+        "scan+generic": _banded_matrix(150, 5, rng, extras=(149,), dense_rows=(7, 100), floor=-50.0, quant=2),
+        "scan(full waves)+lean": _banded_matrix(128, 4, rng, floor=-50.0, quant=2),          # S == 64 * waves
+    }
+
+
+def selected_kernels(info):
+    """("floor" | "scan", "lean_affine" | "lean_table" | "generic") the launchers pick for a banded plan with this ViterbiDecoder.info."""
+    S = info["S"]
+    nwt = next(w for w in (2, 4, 6, 8, 12) if w * 64 >= S)
+    fwd = "floor" if info["floor_ok"] and info["n_dense_rows"] == 0 and S < nwt * 64 else "scan"
+    bt = ("lean_affine" if info["lo_affine"] else "lean_table") if info["n_dense_rows"] == 0 else "generic"
+    return fwd, bt
+
+
+RANDOM_BANDED_SEEDS = tuple(range(8))
+
+
+def random_banded_structure(seed):
+    """Structure `seed` (0 .. 7): 70 .. 399 states, half-widths 1 .. 14, 0 - 2 extra columns and dense rows anywhere, floor -50 / -3 /
+    -inf by seed -> (S, half, extras, dense_rows, A, pi, rng), the generator left where the draws ended."""
+    from tests.test_plan_host import _banded_matrix
+    rng = np.random.default_rng(100 + seed)
+    S = int(rng.integers(70, 400))
+    half = int(rng.integers(1, 15))
+    extras = sorted(set(int(x) for x in rng.integers(0, S, int(rng.integers(0, 3)))))
+    dense_rows = sorted(set(int(x) for x in rng.integers(0, S, int(rng.integers(0, 3)))))
+    floor = [-50.0, -3.0, -np.inf][seed % 3]
+    A = _banded_matrix(S, half, rng, extras, dense_rows, floor=floor, quant=2)
+    pi = -(rng.integers(0, 8, S) / 2).astype(np.float32)
+    return S, half, extras, dense_rows, A, pi, rng
+
+
+WIDE_ROWS = (50, 70, 90, 110, 130, 150)
+
+
+def few_wide_rows(S, rng, wide_rows, half_wide=40, half=5):
+    """Narrow band everywhere, a handful of rows with a wide one: more than kMaxDenseRows of them, so the plan widens the
+    evaluated window (W = 96) instead of declaring them dense rows -- while S stays small enough for the generic
+    back-trace to keep its tables in LDS."""
+    A = np.full((S, S), -50.0, np.float32)
+    for j in range(S):
+        h = half_wide if j in wide_rows else half
+        lo, hi = max(0, j - h), min(S, j + h + 1)
+        A[j, lo:hi] = -(rng.integers(0, 40, hi - lo) / 2)
+    A[:, S - 1] = -(rng.integers(0, 40, S) / 2)
+    return A
+
+
+def wide_row_emissions(rng, B, T, S, wide=WIDE_ROWS):
+    """Emissions on the half-integer grid that force the paths through the wide rows: odd frames strongly favour a wide row j, the
+    frame before a state 24 .. 40 above it, so the path enters j through a window source beyond the first 64 (window = j - 40 ..
+    j + 40)."""
+    E = -(rng.integers(0, 12, (B, T, S)) / 2).astype(np.float32)
+    for t in range(1, T, 2):
+        j = wide[(t // 2) % len(wide)]
+        E[:, t, j] = 6.0
+        E[:, t - 1, j + 24 + (t // 2) % 17] = 6.0
+    return E
