@@ -721,6 +721,32 @@ int vit_obs_softmax_scaled(const float *logits, int64_t n_frames, int32_t n_bins
                            const float *prior, float *logE, vit_stream stream);
 
 /*
+ * The three builders with typed buffers: float32 or float16 pitch logits in, float32 or float16 log-emissions out, so that a model
+ * under autocast hands its logits over as they are and the decoder (which reads float16 rows in every form) gets rows of half the
+ * size without a float32 emission tensor ever existing.
+ *   obs          : HOST, as for vit_decode_logits(): mode 0 = vit_obs_shaun (threshold_logit, offset, scale), 1 = vit_obs_softmax,
+ *                  2 = vit_obs_softmax_scaled (threshold_logit = the unvoiced logit; obs->prior device [n_bins+1] float32 or NULL)
+ *   logits       : device, [n_frames, n_bins] (mode 1: [n_frames, n_bins+1], unvoiced first) of logits_dtype (VIT_F32 / VIT_F16)
+ *   logE         : device, [n_frames, n_bins+1] of emis_dtype (VIT_F32 / VIT_F16); buffers need their element's alignment only
+ * Rounding contract, bit for bit: a float16 logit is widened exactly where it is loaded and all arithmetic is the float32 builder's,
+ * so with logits_dtype VIT_F16 the rows are those of the float32 entry point on the widened logits; the float32 result is rounded to
+ * nearest even where it is stored (float16 subnormals kept; the emission range [-87.34, ~+9] cannot overflow), so with emis_dtype
+ * VIT_F16 the rows are the float32 entry point's rows after that rounding.  Float16 rows are a different decoder input: a decode of
+ * them is the reference decoder's result on the rounded rows, not on the float32 rows.
+ * With both dtypes VIT_F32 the call launches exactly what vit_obs_shaun / _softmax / _softmax_scaled launch; every geometry those
+ * serve is served in all four combinations by the same kernel form, and one they refuse gets the status they return
+ * (VIT_EUNSUPPORTED).  VIT_EINVAL: NULL obs, a bad mode or dtype, n_frames < 0, n_bins < 2, a null buffer with n_frames > 0.
+ * n_frames == 0 is VIT_OK and launches nothing.  A refused call writes nothing.  One kernel launch on `stream`; no host
+ * synchronisation, no allocation.
+ */
+int vit_obs_build(const vit_obs_params *obs, const void *logits, int logits_dtype, int64_t n_frames, void *logE, int emis_dtype,
+                  vit_stream stream);
+/* vit_snippets_append() for float16 snippets (device; a model under autocast): each value is widened exactly, mode 0's subtraction of
+ * channel 0 is a float32 subtraction and the rows are float32 -- bit-equal to vit_snippets_append() on the widened snippets. */
+int vit_snippets_append_f16(const void *snippets /* device float16 */, int32_t n_snippets, int32_t n_channels, int32_t n_frames,
+                            int32_t mode, float *rows_out, int64_t n_rows, vit_stream stream);
+
+/*
  * Activation front-end of imm's decoder (Viterbi.process_HF0_fn, imm/tf_imm.py:70-88; the decoder it feeds is
  * Viterbi.__call__, :129-135): NMF source activations -> log-emissions in the [frames, n_bins+1] layout vit_decode() /
  * vit_decode_packed() read (unvoiced state last).  Per recording the reference takes t = the smallest positive entry

@@ -34,6 +34,7 @@ EXPORTS = (
     "vit_stream_reset", "vit_stream_close",
     "vit_workspace_bytes_stream_commit", "vit_stream_commit_begin", "vit_stream_commit",
     "vit_workspace_bytes_stream_ring", "vit_stream_open_ring", "vit_stream_commit_ack", "vit_stream_commit_rel", "vit_stream_tail",
+    "vit_obs_build", "vit_snippets_append_f16",
 )
 ABI_VERSION = 4
 
@@ -201,6 +202,10 @@ def load() -> ctypes.CDLL:
     lib.vit_obs_activations.argtypes = [vp, i64, i32, i64, vp, i64, ctypes.c_float, ctypes.c_float, vp, vp, i32, vp]
     lib.vit_snippets_append.restype = i32
     lib.vit_snippets_append.argtypes = [vp, i32, i32, i32, i32, vp, i64, vp]
+    lib.vit_obs_build.restype = i32
+    lib.vit_obs_build.argtypes = [ctypes.POINTER(ObsParams), vp, i32, i64, vp, i32, vp]
+    lib.vit_snippets_append_f16.restype = i32
+    lib.vit_snippets_append_f16.argtypes = [vp, i32, i32, i32, i32, vp, i64, vp]
     lib.vit_voicing_notes.restype = i32
     lib.vit_voicing_notes.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp, vp]
     lib.vit_debug_scan.restype = i32

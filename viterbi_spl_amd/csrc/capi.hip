@@ -2302,6 +2302,34 @@ int vit_obs_softmax_scaled(const float* logits, int64_t n_frames, int32_t n_bins
     return hip_status(e);
 }
 
+int vit_obs_build(const vit_obs_params* obs, const void* logits, int logits_dtype, int64_t n_frames, void* logE, int emis_dtype,
+                  vit_stream stream) {
+    if (!obs || obs->mode < 0 || obs->mode > 2) return VIT_EINVAL;
+    if ((logits_dtype != VIT_F32 && logits_dtype != VIT_F16) || (emis_dtype != VIT_F32 && emis_dtype != VIT_F16)) return VIT_EINVAL;
+    if (logits_dtype == VIT_F32 && emis_dtype == VIT_F32) {              // the float32 entry points themselves
+        const float* x = static_cast<const float*>(logits);
+        float* o = static_cast<float*>(logE);
+        if (obs->mode == 0) return vit_obs_shaun(x, n_frames, obs->n_bins, obs->spw, obs->threshold_logit, obs->offset, obs->scale, o, stream);
+        if (obs->mode == 1) return vit_obs_softmax(x, n_frames, obs->n_bins, obs->spw, o, stream);
+        return vit_obs_softmax_scaled(x, n_frames, obs->n_bins, obs->spw, obs->threshold_logit, obs->prior, o, stream);
+    }
+    if (n_frames < 0 || obs->n_bins < 2 || (n_frames > 0 && (!logits || !logE))) return VIT_EINVAL;
+    if (n_frames == 0) return VIT_OK;
+    hipError_t e = vit::launch_obs_half(obs->mode, logits, logits_dtype == VIT_F16, n_frames, obs->n_bins, obs->spw, obs->threshold_logit,
+                                        obs->offset, obs->scale, obs->mode == 2 ? obs->prior : nullptr, logE, emis_dtype == VIT_F16,
+                                        (hipStream_t)stream);
+    if (e == hipErrorInvalidValue) return VIT_EUNSUPPORTED;
+    return hip_status(e);
+}
+
+int vit_snippets_append_f16(const void* snippets, int32_t n_snippets, int32_t n_channels, int32_t n_frames, int32_t mode,
+                            float* rows_out, int64_t n_rows, vit_stream stream) {
+    if (n_snippets < 0 || n_channels < 2 || n_frames < 1 || (mode != 0 && mode != 1) || n_rows < 0 ||
+        n_rows > (int64_t)n_snippets * n_frames || (n_rows > 0 && (!snippets || !rows_out)))
+        return VIT_EINVAL;
+    return hip_status(vit::launch_snippets_append_f16(snippets, n_snippets, n_channels, n_frames, mode, rows_out, n_rows, (hipStream_t)stream));
+}
+
 int vit_obs_activations(const float* hf0, int64_t ld, int32_t n_bins, int64_t B, const int64_t* offsets_dev, int64_t total_frames,
                         float clamp_below, float clamp_to, float* stats, void* logE, int out_dtype, vit_stream stream) {
     if (!hf0 || !offsets_dev || !stats || !logE) return VIT_EINVAL;

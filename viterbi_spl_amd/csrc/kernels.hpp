@@ -410,6 +410,11 @@ hipError_t launch_obs_shaun(const float* logits, int64_t n_frames, int U, int sp
 hipError_t launch_obs_softmax(const float* logits, int64_t n_frames, int U, int spw, float* out, hipStream_t st);
 hipError_t launch_obs_softmax_scaled(const float* logits, int64_t n_frames, int U, int spw, double unvoiced_logit,
                                      const float* prior, float* out, hipStream_t st);
+// emission_half.hip: the same builders with float16 logits (l16) and / or float16 emissions (e16), at least one of the two; mode 0 / 1 / 2
+// = shaun / softmax / softmax_scaled, thr = the threshold logit (0) or the unvoiced logit (2)
+hipError_t launch_obs_half(int mode, const void* logits, bool l16, int64_t n_frames, int U, int spw, double thr, double off, double sc,
+                           const float* prior, void* out, bool e16, hipStream_t st);
+hipError_t launch_snippets_append_f16(const void* snips, int n, int C, int F, int mode, float* out, int64_t rows, hipStream_t st);
 // activations.hip: imm's activation front-end (vit_obs_activations): hf0 [U, total] with row stride ld -> log(hf0 + t_b) transposed to
 // [total, U + 1], statistics per recording into stats [B][4]
 hipError_t launch_activations(const float* hf0, int64_t ld, int U, int B, const int64_t* offsets, int64_t total, uint32_t clamp_below_bits,

@@ -3,7 +3,7 @@
 The reference builds the observation probabilities of a song with Python loops over its frames on the
 host (``Viterbi.observation_probs_fn`` tonet/for_paper.py:1733-1778, ``SoftMaxViterbi.observation_probs_fn``
 :1911-1944) and takes ``log(p + tiny)`` inside ``viterbi_librosa_fn``.  These functions do both steps in
-one kernel launch (``vit_obs_shaun`` / ``vit_obs_softmax``) and return the ``[..., T, n_bins+1]`` float32
+one kernel launch (``vit_obs_build``) and return the ``[..., T, n_bins+1]`` float32 (or float16)
 log-emission tensor that ``decode()`` consumes, so logits produced by an acoustic model on the GPU never
 visit the host (the ``.cpu().numpy()`` round trip at tonet/for_paper.py:2282).
 """
@@ -18,81 +18,96 @@ import torch
 from . import _lib
 
 
+_DTYPES = {torch.float32: _lib.VIT_F32, torch.float16: _lib.VIT_F16}
+
+
 def _check(logits: torch.Tensor, last: int) -> torch.Tensor:
     if not isinstance(logits, torch.Tensor) or logits.device.type != "cuda":
         raise ValueError("logits must be a torch tensor on a ROCm GPU (there is no CPU path)")
-    if logits.dtype != torch.float32 or logits.dim() < 2 or logits.shape[-1] != last:
-        raise ValueError(f"logits must be float32 [..., frames, {last}]")
+    if logits.dtype not in _DTYPES or logits.dim() < 2 or logits.shape[-1] != last:
+        raise ValueError(f"logits must be float32 or float16 [..., frames, {last}]")
     if not logits.is_contiguous():
         raise ValueError("logits must be C-contiguous")
     return logits
 
 
-def _out(out, shape, device) -> torch.Tensor:
+def _out(out, shape, device, dtype=torch.float32) -> torch.Tensor:
+    if dtype not in _DTYPES:
+        raise ValueError("dtype must be torch.float32 or torch.float16")
     if out is None:
-        return torch.empty(shape, dtype=torch.float32, device=device)
-    if out.dtype != torch.float32 or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous float32 {tuple(shape)} tensor on the logits' device")
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or out.device != device or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous {dtype} {tuple(shape)} tensor on the logits' device")
     return out
+
+
+def _build(mode: int, logits: torch.Tensor, n_bins: int, spw: int, threshold_logit: float, offset: float, scale: float,
+           prior: torch.Tensor | None, out: torch.Tensor) -> torch.Tensor:
+    """One ``vit_obs_build`` launch: ``logits`` and ``out`` in their own dtypes (float32 or float16 each)."""
+    obs = _lib.ObsParams(mode, n_bins, spw, threshold_logit, offset, scale, prior.data_ptr() if prior is not None else None)
+    n = out.numel() // (n_bins + 1)
+    with torch.cuda.device(logits.device):
+        rc = _lib.load().vit_obs_build(obs, logits.data_ptr(), _DTYPES[logits.dtype], n, out.data_ptr(), _DTYPES[out.dtype],
+                                       torch.cuda.current_stream(logits.device).cuda_stream)
+    _lib.check(rc, "vit_obs_build")
+    return out
+
+
+# Storage types of the three builders below.  ``logits`` may be float32 or float16 (a model under autocast): a float16 logit is
+# widened exactly, so the result is that of the float32 call on ``logits.float()``, bit for bit.  ``dtype`` is the emission dtype:
+# with ``torch.float16`` every float32 result is rounded to nearest even as it is stored (the call on float32 followed by
+# ``.half()``, bit for bit, without the float32 tensor ever existing) -- half the bytes for the decoder to read.  Float16 emissions
+# are a DIFFERENT decoder input: a decode of them is the reference decoder's result on the rounded rows, not on the float32 rows
+# (on the synthetic logits of scripts/obs_half_time.py 3.75e-5 of the frames at [1024 x 30000, 360] and 1.9e-5 at [256 x 30000, 722] decode
+# to another state than with float32 rows: profiles/obs_half_time.json).
 
 
 def shaun_log_emissions(logits: torch.Tensor, voicing_threshold: float = 0.32, single_side_peak_width: int = 5,
-                        p: float = 0.8, scale: float = 2.0, out: torch.Tensor | None = None) -> torch.Tensor:
-    """``Viterbi.observation_probs_fn`` + log: logits ``[..., T, n_bins]`` -> log-emissions ``[..., T, n_bins+1]`` (into ``out``
-    when given: a caller's emission buffer)."""
+                        p: float = 0.8, scale: float = 2.0, out: torch.Tensor | None = None,
+                        dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``Viterbi.observation_probs_fn`` + log: logits ``[..., T, n_bins]`` (float32 or float16) -> log-emissions
+    ``[..., T, n_bins+1]`` in ``dtype`` (float32 or float16; into ``out`` when given: a caller's emission buffer of that dtype).
+    Float16 emissions are the float32 ones rounded to nearest even -- a different decoder input, see above."""
     n_bins = logits.shape[-1]
     logits = _check(logits, n_bins)
     assert 0 < voicing_threshold < 1
-    out = _out(out, logits.shape[:-1] + (n_bins + 1,), logits.device)
-    n = logits.numel() // n_bins
-    with torch.cuda.device(logits.device):
-        rc = _lib.load().vit_obs_shaun(logits.data_ptr(), n, n_bins, single_side_peak_width,
-                                       math.log(voicing_threshold / (1.0 - voicing_threshold)),
-                                       math.log(p / (1.0 - p)), scale, out.data_ptr(),
-                                       torch.cuda.current_stream(logits.device).cuda_stream)
-    _lib.check(rc, "vit_obs_shaun")
-    return out
+    out = _out(out, logits.shape[:-1] + (n_bins + 1,), logits.device, dtype)
+    return _build(0, logits, n_bins, single_side_peak_width, math.log(voicing_threshold / (1.0 - voicing_threshold)),
+                  math.log(p / (1.0 - p)), scale, None, out)
 
 
-def softmax_log_emissions(logits: torch.Tensor, single_side_peak_width: int = 15, out: torch.Tensor | None = None) -> torch.Tensor:
-    """``SoftMaxViterbi.observation_probs_fn`` + log: logits ``[..., T, n_bins+1]`` (column 0 = unvoiced) ->
-    log-emissions ``[..., T, n_bins+1]`` with the unvoiced state last."""
+def softmax_log_emissions(logits: torch.Tensor, single_side_peak_width: int = 15, out: torch.Tensor | None = None,
+                          dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``SoftMaxViterbi.observation_probs_fn`` + log: logits ``[..., T, n_bins+1]`` (column 0 = unvoiced; float32 or float16) ->
+    log-emissions ``[..., T, n_bins+1]`` in ``dtype`` (float32 or float16) with the unvoiced state last.  Float16 emissions are
+    the float32 ones rounded to nearest even -- a different decoder input, see above."""
     S = logits.shape[-1]
     logits = _check(logits, S)
-    out = _out(out, logits.shape, logits.device)
-    n = logits.numel() // S
-    with torch.cuda.device(logits.device):
-        rc = _lib.load().vit_obs_softmax(logits.data_ptr(), n, S - 1, single_side_peak_width, out.data_ptr(),
-                                         torch.cuda.current_stream(logits.device).cuda_stream)
-    _lib.check(rc, "vit_obs_softmax")
-    return out
+    out = _out(out, logits.shape, logits.device, dtype)
+    return _build(1, logits, S - 1, single_side_peak_width, 0.0, 0.0, 0.0, None, out)
 
 
 def softmax_scaled_log_emissions(logits: torch.Tensor, voicing_threshold_prob: float, prior: torch.Tensor | None,
-                                 single_side_peak_width: int = 5, out: torch.Tensor | None = None) -> torch.Tensor:
+                                 single_side_peak_width: int = 5, out: torch.Tensor | None = None,
+                                 dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """dcnet's ``SoftMaxViterbi.observation_probs_fn`` (dcnet/softmax_viterbi.py:2530-2579) + log: logits ``[..., T, n_bins]``
-    -> log of the scaled likelihoods ``[..., T, n_bins+1]`` (unvoiced last; values above 0 are normal).  ``prior``: the
-    state prior ``[n_bins+1]`` (unvoiced last) on the GPU, or None for the unscaled variant.  ``out``: a caller's emission buffer."""
+    (float32 or float16) -> log of the scaled likelihoods ``[..., T, n_bins+1]`` in ``dtype`` (float32 or float16; unvoiced last;
+    values above 0 are normal).  ``prior``: the state prior ``[n_bins+1]`` (float32, unvoiced last) on the GPU, or None for the
+    unscaled variant.  ``out``: a caller's emission buffer of ``dtype``.  Float16 emissions are the float32 ones rounded to nearest
+    even -- a different decoder input, see above."""
     n_bins = logits.shape[-1]
     logits = _check(logits, n_bins)
     assert 0 < voicing_threshold_prob < 1
     if prior is not None:
         if prior.device != logits.device or prior.dtype != torch.float32 or tuple(prior.shape) != (n_bins + 1,) or not prior.is_contiguous():
             raise ValueError(f"prior must be a contiguous float32 [{n_bins + 1}] tensor on the logits' device")
-    out = _out(out, logits.shape[:-1] + (n_bins + 1,), logits.device)
-    n = logits.numel() // n_bins
+    out = _out(out, logits.shape[:-1] + (n_bins + 1,), logits.device, dtype)
     # the reference pads with log(vth / (1. - vth)) computed from an np.float32 scalar (dcnet/softmax_viterbi.py:2546-2548): float32
     # arithmetic under NumPy >= 2 -- the NumPy that generated tests/golden/obs_goldens.npz -- (NumPy 1.x promoted the scalar
     # expression to float64 before the float32 pad: at most one ulp apart); hand the kernel exactly the float32 value
     vth = np.float32(voicing_threshold_prob)
     unvoiced_logit = float(np.log(vth / (np.float32(1) - vth)))
-    with torch.cuda.device(logits.device):
-        rc = _lib.load().vit_obs_softmax_scaled(logits.data_ptr(), n, n_bins, single_side_peak_width,
-                                                unvoiced_logit,
-                                                prior.data_ptr() if prior is not None else None, out.data_ptr(),
-                                                torch.cuda.current_stream(logits.device).cuda_stream)
-    _lib.check(rc, "vit_obs_softmax_scaled")
-    return out
+    return _build(2, logits, n_bins, single_side_peak_width, unvoiced_logit, 0.0, 0.0, prior, out)
 
 
 @functools.lru_cache(maxsize=None)

@@ -176,9 +176,23 @@ def tf_viterbi_librosa_fn(*, tf_log_transition_matrix_T, tf_log_prob_init, tf_or
 
 # ----------------------------------------------------------------------------- families B / C
 class _PreparedViterbi:
-    """Parameters logged and transposed once (tonet/for_paper.py:1780-1815)."""
+    """Parameters logged and transposed once (tonet/for_paper.py:1780-1815).
 
-    def __init__(self, transition_matrix, init_probs, num_freq_bins=None, device=None):
+    ``emission_dtype``: storage of the emission tensor the GPU builder writes for ``decode_logits`` / ``decode_logits_batch`` /
+    ``decode_recordings`` (and ``RecordingAccumulator``), "float32" or "float16".  With "float16" every float32 emission is rounded to
+    nearest even as the builder stores it (``vit_obs_build``): half the tensor, and no float32 tensor on the way.  Float16 rows are a
+    DIFFERENT decoder input: the result is the reference decoder's result on the rounded rows (bit for bit), not on the float32 rows
+    (on the synthetic logits of scripts/obs_half_time.py the two differ in 3.75e-5 of the frames at [1024 x 30000, 360] and 1.9e-5 at
+    [256 x 30000, 722]; on the first shape builder + decode is 1.08x slower with float16 rows than with float32 rows, on the second as
+    fast: profiles/obs_half_time.json).
+    Logits may be float32 or float16 torch tensors (float16 is widened exactly inside the builder: the result of their
+    ``.float()`` copy); NumPy logits are converted to float32 as before.  ``emission_dtype`` is fixed at construction: it is read
+    through ``_torch_dtype()`` at every call, so do not assign to it while a ``RecordingAccumulator`` or a stream over this object is open."""
+
+    def __init__(self, transition_matrix, init_probs, num_freq_bins=None, device=None, emission_dtype="float32"):
+        if emission_dtype not in ("float32", "float16"):
+            raise ValueError('emission_dtype must be "float32" or "float16"')
+        self.emission_dtype = emission_dtype
         transition_matrix = np.asarray(transition_matrix)
         init_probs = np.asarray(init_probs)
         U = transition_matrix.shape[0] - 1 if num_freq_bins is None else int(num_freq_bins)
@@ -210,6 +224,9 @@ class _PreparedViterbi:
         assert name == 'viterbi_init_probs'
         return cls(A, pi, **kw)
 
+    def _torch_dtype(self):
+        return torch.float16 if self.emission_dtype == "float16" else torch.float32
+
     def _post(self, bins):
         n_bins = self.num_freq_bins
         voiced = bins < n_bins
@@ -218,7 +235,8 @@ class _PreparedViterbi:
 
     # ---- the post-processor on the GPU: logits -> log-emissions -> decode -> (voiced, bins)
     def _log_emissions(self, logits: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        """This class's stand-alone emission builder: ``[frames, columns]`` logits -> ``[frames, S]`` log-emissions (into ``out`` when given)."""
+        """This class's stand-alone emission builder: ``[frames, columns]`` logits (float32 or float16) -> ``[frames, S]`` log-emissions
+        in ``emission_dtype`` (into ``out`` when given)."""
         raise NotImplementedError
 
     def decode_logits(self, logits, note_range=None):
@@ -248,11 +266,16 @@ class _PreparedViterbi:
         tensor does not fit, and the default stays unfused.
         ``max_workspace_bytes``: a budget for the decoder's workspace; the same result.  ``fused=True``: ``ViterbiDecoder.decode_logits``
         falls to the checkpointed fused decode (``vit_decode_logits_checkpointed``: neither an emission tensor nor a whole delta
-        history); ``fused=False``: ``ViterbiDecoder.decode(max_workspace_bytes=)``, which still needs the emission tensor."""
+        history); ``fused=False``: ``ViterbiDecoder.decode(max_workspace_bytes=)``, which still needs the emission tensor.
+        The fused kernels are float32 only (there is no emission tensor to shrink): ``fused=True`` raises ``ValueError`` with
+        ``emission_dtype="float16"`` or float16 logits."""
         dev = self._decoder.device
         lg = logits if isinstance(logits, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(logits, np.float32))
         lg = lg.to(dev).contiguous()
         assert lg.dim() == 3
+        if fused and (self.emission_dtype != "float32" or lg.dtype == torch.float16):
+            raise ValueError('fused=True decodes float32 logits through float32 emission rows only: use fused=False with '
+                             'emission_dtype="float16" or float16 logits')
         if lengths is not None:
             lengths = (lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths), dtype=torch.int64)).to(dev)
         if fused:
@@ -292,7 +315,9 @@ class _PreparedViterbi:
         five seeds per builder ("shaun", softmax, scaled likelihoods) -- 100 % of the frames of all fifteen songs decode to
         the reference's states; the test's bar is 99.9 % per song with every differing frame on a path whose exact score
         ties the reference's to 1e-6.  Callers that need the reference's bits by construction build the probabilities
-        themselves and call :meth:`viterbi_librosa_fn`, which is bit-exact."""
+        themselves and call :meth:`viterbi_librosa_fn`, which is bit-exact.  All of this is the default, ``emission_dtype="float32"``:
+        with ``"float16"`` the call returns the decode of the rounded rows (see the class docstring), which is not the reference's
+        result on the float32 rows."""
         voiced, bins = self.decode_logits(logits)
         return voiced.cpu().numpy(), bins.cpu().numpy().astype(np.int64)
 
@@ -302,8 +327,8 @@ class Viterbi(_PreparedViterbi):
     probabilities and logs them IN PLACE, as in the reference.  ``__call__(logits)`` is the whole
     post-processor (:1817-1831): emission builder -> decode -> (voiced, bins)."""
 
-    def __init__(self, transition_matrix, init_probs, voicing_threshold=0.32, num_freq_bins=None, device=None):
-        super().__init__(transition_matrix, init_probs, num_freq_bins, device)
+    def __init__(self, transition_matrix, init_probs, voicing_threshold=0.32, num_freq_bins=None, device=None, emission_dtype="float32"):
+        super().__init__(transition_matrix, init_probs, num_freq_bins, device, emission_dtype)
         assert 0 < voicing_threshold < 1
         self.voicing_threshold = voicing_threshold
         self.threshold = np.log(voicing_threshold / (1. - voicing_threshold))
@@ -321,7 +346,7 @@ class Viterbi(_PreparedViterbi):
 
     def _log_emissions(self, logits, out=None):
         from .emissions import shaun_log_emissions
-        return shaun_log_emissions(logits, self.voicing_threshold, self.single_side_peak_width, out=out)
+        return shaun_log_emissions(logits, self.voicing_threshold, self.single_side_peak_width, out=out, dtype=self._torch_dtype())
 
     def _obs_params(self):
         import math
@@ -335,8 +360,8 @@ class SoftMaxViterbi(_PreparedViterbi):
     exceed 1 for scaled likelihoods), logged IN PLACE.  ``__call__(logits)`` as above; logits carry the unvoiced
     column first ([T, n_bins+1])."""
 
-    def __init__(self, transition_matrix, init_probs, num_freq_bins=None, device=None):
-        super().__init__(transition_matrix, init_probs, num_freq_bins, device)
+    def __init__(self, transition_matrix, init_probs, num_freq_bins=None, device=None, emission_dtype="float32"):
+        super().__init__(transition_matrix, init_probs, num_freq_bins, device, emission_dtype)
         self.single_side_peak_width = 15
 
     def viterbi_librosa_fn(self, probs_ts):
@@ -351,7 +376,7 @@ class SoftMaxViterbi(_PreparedViterbi):
 
     def _log_emissions(self, logits, out=None):
         from .emissions import softmax_log_emissions
-        return softmax_log_emissions(logits, self.single_side_peak_width, out=out)
+        return softmax_log_emissions(logits, self.single_side_peak_width, out=out, dtype=self._torch_dtype())
 
     def _obs_params(self):
         return ViterbiDecoder.obs_params("softmax", self.num_freq_bins, self.single_side_peak_width)
@@ -363,8 +388,8 @@ class ScaledSoftMaxViterbi(SoftMaxViterbi):
     with ``scaled=True`` -- every softmax probability is divided by its state prior ("scaled likelihood": values far
     above 1, i.e. positive log-emissions)."""
 
-    def __init__(self, transition_matrix, init_probs, voicing_threshold_prob, scaled, num_freq_bins=None, device=None):
-        super().__init__(transition_matrix, init_probs, num_freq_bins, device)
+    def __init__(self, transition_matrix, init_probs, voicing_threshold_prob, scaled, num_freq_bins=None, device=None, emission_dtype="float32"):
+        super().__init__(transition_matrix, init_probs, num_freq_bins, device, emission_dtype)
         assert 0 < voicing_threshold_prob < 1
         self.voicing_threshold_prob = float(voicing_threshold_prob)
         self.scaled = bool(scaled)
@@ -375,7 +400,7 @@ class ScaledSoftMaxViterbi(SoftMaxViterbi):
 
     def _log_emissions(self, logits, out=None):
         from .emissions import softmax_scaled_log_emissions
-        return softmax_scaled_log_emissions(logits, self.voicing_threshold_prob, self._prior_dev, self.single_side_peak_width, out=out)
+        return softmax_scaled_log_emissions(logits, self.voicing_threshold_prob, self._prior_dev, self.single_side_peak_width, out=out, dtype=self._torch_dtype())
 
     def _obs_params(self):
         vth = np.float32(self.voicing_threshold_prob)       # float32 arithmetic, as softmax_scaled_log_emissions hands it to the kernel
@@ -527,7 +552,11 @@ class RecordingAccumulator:
     whatever ``max_frames`` is; ``partial()`` works as before (call it often enough that R frames never pile up behind the frontier),
     ``finish()`` is the last commit plus the tail behind it and returns what ``streaming=True`` returns.  Only the history is bounded
     by R: the logits rows and the outputs keep ``max_frames``.  The class wraps the three logits decoders only: ``ImmViterbi`` callers stream with
-    ``viterbi._decoder.stream(...)`` and ``emissions.activation_log_emissions`` per chunk."""
+    ``viterbi._decoder.stream(...)`` and ``emissions.activation_log_emissions`` per chunk.
+
+    ``append`` takes float32 or float16 snippets (``vit_snippets_append_f16`` widens exactly; the rows kept are float32 either way), and the
+    emission rows of ``finish`` and of the streaming chunk buffer have the wrapped class's ``emission_dtype``: with "float16" the result is
+    the decode of the rounded rows (see ``_PreparedViterbi``), the same for ``streaming=False``, ``streaming=True`` and ``ring_frames=``."""
 
     def __init__(self, viterbi: _PreparedViterbi, max_frames: int, streaming: bool = False, ring_frames: int | None = None):
         self.viterbi = viterbi
@@ -560,20 +589,25 @@ class RecordingAccumulator:
         from . import _lib
         if not isinstance(pitch_logits, torch.Tensor) or pitch_logits.device != self._rows.device:
             raise ValueError("pitch_logits must be a torch tensor on the decoder's device")
-        if pitch_logits.dtype != torch.float32 or pitch_logits.dim() != 3 or pitch_logits.shape[1] != self.channels:
-            raise ValueError(f"pitch_logits must be float32 [snippets, {self.channels}, frames]")
+        if pitch_logits.dtype not in (torch.float32, torch.float16) or pitch_logits.dim() != 3 or pitch_logits.shape[1] != self.channels:
+            raise ValueError(f"pitch_logits must be float32 or float16 [snippets, {self.channels}, frames]")
         x = pitch_logits.contiguous()
         n, C, F = x.shape
         rows = n * F - int(padded_frames)
         if rows < 0 or self.n_frames + rows > self._rows.shape[0]:
             raise ValueError("recording longer than max_frames (or padded_frames out of range)")
+        # (float16 snippets are widened inside the kernel: the float32 rows of their .float() copy)
+        fn = _lib.load().vit_snippets_append_f16 if x.dtype == torch.float16 else _lib.load().vit_snippets_append
         with torch.cuda.device(x.device):
-            rc = _lib.load().vit_snippets_append(x.data_ptr(), n, C, F, self.mode, self._rows[self.n_frames:].data_ptr(), rows,
-                                                 torch.cuda.current_stream(x.device).cuda_stream)
+            rc = fn(x.data_ptr(), n, C, F, self.mode, self._rows[self.n_frames:].data_ptr(), rows,
+                    torch.cuda.current_stream(x.device).cuda_stream)
         _lib.check(rc, "vit_snippets_append")
         if self._stream is not None and rows > 0:      # the new frames' emission rows, then the forward pass over them
+            dt = self.viterbi._torch_dtype()             # (read where finish() reads it: the adapter; a session's type is fixed by its first append)
+            if self._chunk is not None and self._chunk.dtype != dt:
+                raise ValueError("the wrapped decoder's emission_dtype changed while the recording was being accumulated")
             if self._chunk is None or self._chunk.shape[0] < rows:
-                self._chunk = torch.empty((rows, self.viterbi.num_freq_bins + 1), dtype=torch.float32, device=self._rows.device)
+                self._chunk = torch.empty((rows, self.viterbi.num_freq_bins + 1), dtype=dt, device=self._rows.device)
             self._stream.append(self.viterbi._log_emissions(self._rows[self.n_frames:self.n_frames + rows], out=self._chunk[:rows]))
         self.n_frames += rows
 
